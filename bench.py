@@ -19,6 +19,9 @@ stream), `cpu_baseline` (oracle port on the host cores, N = 1 only), `event_bloc
 5 blocks of K steps), and for N > 1 `strong_scaling` (global batch B split over the ranks) and `ddp_head`
 (the same step behind a DDP-wrapped stand-in acoustic model whose gradient size is stated; RCCL all-reduce
 over xGMI) -- extra information, never `value`.
+
+`--dump-outputs DIR` writes what the last timed step returned (loss.npy [1], grad.npy [B,T,V], float32) for comparing two
+builds output for output: the inputs are seeded, identical from run to run for the same arguments.
 """
 import argparse
 import json
@@ -60,7 +63,38 @@ def parse():
                          "without it such a run prints a `not_measured` record and exits 3")
     ap.add_argument("--share-device", action="store_true",
                     help="harness check on a 1-GPU box: N ranks on cuda:0 over gloo; every world_size > 1 leg runs, `value` is null (not a measurement)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to its caller (the loss and the gradient w.r.t. "
+                         "the log-probs) as DIR/<name>.npy, float32, at most 64 MB in all (per rank: rank<r>_<name>.npy)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, limit_bytes=DUMP_LIMIT_BYTES, prefix=""):
+    """Write {name: array} as path/<prefix><name>.npy (float32 / float64), smallest first, within `limit_bytes` in all.
+    An array that no longer fits is replaced by a fixed sample of its flattened entries (seed 0, sorted): <name>_sample.npy
+    holds the values, <name>_sample_index.npy their flat indices (float64, exact).  Returns {file name: shape}."""
+    os.makedirs(path, exist_ok=True)
+    left = limit_bytes - 4096                                  # (.npy headers)
+    written = {}
+    for name, a in sorted(((k, np.asarray(v)) for k, v in arrays.items()), key=lambda kv: kv[1].nbytes):
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if a.nbytes <= left:
+            out = {name: a}
+        else:
+            k = min(a.size, max(0, left) // (a.itemsize + 8))  # the values and their float64 indices together
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))
+            out = {f"{name}_sample": a.reshape(-1)[idx], f"{name}_sample_index": idx.astype(np.float64)}
+        for n, v in out.items():
+            np.save(os.path.join(path, f"{prefix}{n}.npy"), v)
+            written[f"{prefix}{n}.npy"] = list(v.shape)
+            left -= v.nbytes
+    return written
 
 
 def algorithmic_bytes(lx, ly, S, A, V):
@@ -180,21 +214,26 @@ def main():
         torch.cuda.synchronize()
 
     def timed(fn, steps, warmup):
+        """-> (seconds of exactly `steps` calls of fn, what the last of them returned)"""
         for _ in range(warmup):
             fn()
         barrier()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1):
             fn()
+        last = fn()   # (held only from here on: the steps before it allocate exactly as without it)
         barrier()
         dt = time.perf_counter() - t0
         if use_dist:
             t = torch.tensor([dt], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
-        return dt
+        return dt, last
 
-    dt = timed(step, args.steps, args.warmup)
+    dt, last_loss = timed(step, args.steps, args.warmup)
+    # what the last timed step handed its caller, copied off the device before any further step runs
+    outputs = {"loss": last_loss.detach().cpu().numpy(), "grad": x.grad.detach().cpu().numpy()} if args.dump_outputs else None
+    del last_loss
     loss_val = float(step().item())
     # a timing of a call whose gradient is NaN is not a measurement (round 3 found T = 3000 points of rounds 1 - 2 that were)
     assert np.isfinite(loss_val) and bool(torch.isfinite(x.grad).all().item()), "non-finite loss or gradient at this bench point"
@@ -322,7 +361,7 @@ def main():
             x2.grad = None
             crit(x2, l2, lx2t, ly2t).backward()
 
-        dts = timed(step2, args.steps, args.warmup)
+        dts, _ = timed(step2, args.steps, args.warmup)
         strong = {"global_batch": B, "per_gpu": Bs, "value": round(B * args.steps / dts, 2), "ms_per_step": round(dts / args.steps * 1e3, 4)}
 
     # --- the same step behind a DDP-wrapped stand-in acoustic model (N > 1, or --ddp-head) -------------
@@ -343,7 +382,7 @@ def main():
             lp = torch.log_softmax(out.float(), dim=-1)
             crit(lp, labels_t, lx_t, ly_t).backward()
 
-        dt2 = timed(ddp_step, args.ddp_steps, 2)
+        dt2, _ = timed(ddp_step, args.ddp_steps, 2)
         assert all(bool(torch.isfinite(p.grad).all().item()) for p in model.parameters() if p.grad is not None), "non-finite gradient behind the DDP head"
         ddp_info = {"value": round(world * B * args.ddp_steps / dt2, 2), "ms_per_step": round(dt2 / args.ddp_steps * 1e3, 4),
                     "steps": args.ddp_steps, "parameters": nparam, "den_kernel": ctc_crf._C.last_den_kernel(), "call_streams": ctc_crf._C.last_call_streams(), "gradient_bytes_per_step": 4 * nparam,
@@ -366,6 +405,9 @@ def main():
         cpu = {"value": round(n / cdt, 4), "unit": "utterances/s", "cores": int(min(cores, n)), "kind": "port",
                "sample": f"{n} of the {B} utterances of the same batch (T={T}, V={V}, same den_lm), "
                          f"oracle/crf_oracle.c fp32, one OpenMP thread per utterance, {cdt:.1f} s"}
+
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs, DUMP_LIMIT_BYTES // world, prefix=f"rank{rank}_" if world > 1 else "")
 
     if rank == 0 and share:
         rec = {"metric": "utterances/sec CTC-CRF fwd+bwd", "value": None, "unit": "utterances/s", "n_gpus": world,

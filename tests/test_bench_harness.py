@@ -2,15 +2,26 @@
 reference does with mp.spawn, cat/shared/coreutils.py:493-504); a node with fewer GPUs gets a "not measured" line, never
 an extrapolation; under torch.distributed.run the rank initialises RCCL ("nccl"), checks world size and device
 distinctness, and the DDP stand-in leg runs (1-rank NCCL on the single GPU of the test box)."""
+import importlib.util
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
+from tests.util import rel_err
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _bench_module():
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
 
 
 def test_not_measured_when_gpus_missing():
@@ -53,3 +64,50 @@ def test_committed_pmc_traffic_belongs_to_the_default_bench_line():
     assert 1.0 < d["whole_path"]["ratio"] < 3.0
     src = d["source"].split(":")[0]
     assert os.path.exists(os.path.join(ROOT, src)), src
+
+
+def test_dump_outputs_stays_within_its_limit(tmp_path):
+    """bench.py --dump-outputs: arrays that fit are written whole; past the limit a fixed, seeded sample of the flattened entries
+    (values + float64 flat indices) fills what is left, the same sample on every run; everything is float32 / float64."""
+    bench = _bench_module()
+    grad = np.random.default_rng(1).normal(size=(4, 50, 72)).astype(np.float32)
+    loss = np.array([1.5], dtype=np.float32)
+    w = bench.dump_outputs(str(tmp_path / "whole"), {"loss": loss, "grad": grad})
+    assert w == {"loss.npy": [1], "grad.npy": [4, 50, 72]}
+    assert np.array_equal(np.load(tmp_path / "whole" / "grad.npy"), grad)
+    limit = 20000
+    for d in ("a", "b"):
+        w = bench.dump_outputs(str(tmp_path / d), {"loss": loss, "grad": grad}, limit_bytes=limit)
+        assert sorted(w) == ["grad_sample.npy", "grad_sample_index.npy", "loss.npy"]
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= limit
+        val, idx = np.load(tmp_path / d / "grad_sample.npy"), np.load(tmp_path / d / "grad_sample_index.npy")
+        assert val.dtype == np.float32 and idx.dtype == np.float64 and len(val) == len(idx) > 1000
+        assert np.all(np.diff(idx) > 0) and np.array_equal(val, grad.reshape(-1)[idx.astype(np.int64)])
+        assert np.array_equal(np.load(tmp_path / d / "loss.npy"), loss)
+    assert all(np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)) for f in w)
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_the_last_timed_step(tmp_path):
+    """Two runs with the same arguments: the same seeded inputs, so the dumped loss and gradient agree; the loss is the one the
+    result line reports (a step on the same batch), the gradient has the caller's shape and is finite."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    B, T, V = 8, 200, 72
+    runs = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--B", str(B), "--T", str(T),
+               "--histories", "256", "--fanout", "8", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-1500:]
+        line = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        assert sorted(os.listdir(tmp_path / d)) == ["grad.npy", "loss.npy"]
+        loss, grad = np.load(tmp_path / d / "loss.npy"), np.load(tmp_path / d / "grad.npy")
+        assert loss.dtype == np.float32 and loss.shape == (1,) and grad.dtype == np.float32 and grad.shape == (B, T, V)
+        assert np.isfinite(grad).all() and np.abs(grad).max() > 0
+        assert abs(float(loss[0]) - line["loss"]) <= 1e-5 * abs(line["loss"])
+        runs.append((loss, grad))
+    assert abs(float(runs[0][0][0] - runs[1][0][0])) <= 1e-6 * abs(float(runs[1][0][0]))
+    assert rel_err(runs[0][1], runs[1][1]) <= 1e-6
+    print("two runs bit-identical:", bool(np.array_equal(runs[0][1], runs[1][1]) and np.array_equal(runs[0][0], runs[1][0])))

@@ -1,6 +1,6 @@
 import os, sys, tempfile
 import numpy as np, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ctc_crf, oracle
 from oracle import fst_io
 from tests.test_gpu_fuzz import CAMPAIGN, _case
