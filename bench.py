@@ -14,11 +14,12 @@ data-path collective: every rank runs B utterances with its own grap
 process per GPU, like the reference's mp.spawn, cat/shared/coreutils.py:493-504).
 
 Rank 0 prints ONE JSON line: `value` (exactly K steps between barrier + synchronize on both sides, max
-over ranks), `roofline` (dominant kernel = the denominator recursions' launch, HIP-event timed on its own
-stream), `cpu_baseline` (oracle port on the host cores, N = 1 only), `event_blocks` (hipEvent median over
-5 blocks of K steps), and for N > 1 `strong_scaling` (global batch B split over the ranks) and `ddp_head`
-(the same step behind a DDP-wrapped stand-in acoustic model whose gradient size is stated; RCCL all-reduce
-over xGMI) -- extra information, never `value`.
+over ranks) and `ms_per_step`, with the loss and schedule of the last timed step.  A plain run does nothing
+else.  `--full` adds, after the timed steps: `roofline` (dominant kernel = the denominator recursions' launch,
+HIP-event timed on its own stream), `cpu_baseline` (oracle port on the host cores, N = 1 only), `event_blocks`
+(hipEvent median over 5 blocks of K steps), and for N > 1 `strong_scaling` (global batch B split over the
+ranks) and `ddp_head` (the same step behind a DDP-wrapped stand-in acoustic model whose gradient size is
+stated; RCCL all-reduce over xGMI) -- extra information, never `value`.
 
 `--dump-outputs DIR` writes what the last timed step returned (loss.npy [1], grad.npy [B,T,V], float32) for comparing two
 builds output for output: the inputs are seeded, identical from run to run for the same arguments.
@@ -53,9 +54,12 @@ def parse():
     ap.add_argument("--fanout", type=int, default=24, help="synthetic den_lm: tokens per LM state")
     ap.add_argument("--lamb", type=float, default=0.1)
     ap.add_argument("--ragged", action="store_true", help="T_b ~ U[0.6T, T] instead of all = T")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure event blocks, per-kernel roofline, the CPU baseline (N = 1) and, "
+                         "for N > 1, strong scaling and the DDP stand-in; without it a run times the steps and nothing else")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-sample", type=int, default=0, help="utterances in the CPU sample (0 = one per core)")
-    ap.add_argument("--ddp-head", action="store_true", help="time the DDP stand-in model also at N = 1")
+    ap.add_argument("--ddp-head", action="store_true", help="--full: time the DDP stand-in model also at N = 1")
     ap.add_argument("--ddp-layers", type=int, default=12, help="stand-in acoustic model: residual MLP blocks (8.4 M parameters each)")
     ap.add_argument("--ddp-steps", type=int, default=5)
     ap.add_argument("--allow-serial", action="store_true",
@@ -69,6 +73,8 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.ddp_head and not args.full:
+        ap.error("--ddp-head is a leg of --full")
     return args
 
 
@@ -233,9 +239,10 @@ def main():
     dt, last_loss = timed(step, args.steps, args.warmup)
     # what the last timed step handed its caller, copied off the device before any further step runs
     outputs = {"loss": last_loss.detach().cpu().numpy(), "grad": x.grad.detach().cpu().numpy()} if args.dump_outputs else None
+    loss_val = float(last_loss.item())
     del last_loss
-    loss_val = float(step().item())
-    # a timing of a call whose gradient is NaN is not a measurement (round 3 found T = 3000 points of rounds 1 - 2 that were)
+    # a timing of a call whose gradient is NaN is not a measurement (round 3 found T = 3000 points of rounds 1 - 2 that were);
+    # checked on the last timed step, the call that the library's last_* queries below describe as well
     assert np.isfinite(loss_val) and bool(torch.isfinite(x.grad).all().item()), "non-finite loss or gradient at this bench point"
     side_stream, call_streams = ctc_crf._C.last_side_stream(), ctc_crf._C.last_call_streams()
     fallback_den, fallback_num = ctc_crf._C.last_fallback_counts(torch.cuda.current_stream(dev).cuda_stream)
@@ -255,103 +262,106 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     value = world * B * args.steps / dt
 
-    # --- hipEvent timing on the compute stream, median over 5 blocks of K steps ----------
-    blocks = []
-    for _ in range(5):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(args.steps):
-            step()
-        e1.record()
-        torch.cuda.synchronize()
-        blocks.append(e0.elapsed_time(e1) / args.steps)
-    event_blocks = {"blocks": 5, "steps_per_block": args.steps, "median_ms_per_step": round(float(np.median(blocks)), 4),
-                    "min_ms_per_step": round(min(blocks), 4), "max_ms_per_step": round(max(blocks), 4),
-                    "utt_per_s_at_median": round(B / (float(np.median(blocks)) * 1e-3), 1)}
-
-    # --- per-kernel durations, measured live with HIP events on the launch streams -------------
-    ctc_crf._C.profile_enable(True)
-    acc = {}
-    nprof = max(3, min(10, args.steps))
-    for _ in range(nprof):
-        step()
-        for k, v in ctc_crf._C.profile_read().items():
-            if v >= 0:
-                acc.setdefault(k, []).append(v)
-    ctc_crf._C.profile_enable(False)
-    kern_ms = {k: float(np.mean(v)) for k, v in acc.items()}
-    bytes_den, bytes_num, bytes_den_pair = algorithmic_bytes(lx, ly, dims["S"], dims["A"], V)
-    dom = "den_fwd_chain"   # forward and backward recursions are ONE launch (slots den_fwd_chain and den_bwd_chain both time it)
-    dom_ms = kern_ms[dom]
-    achieved = bytes_den_pair / (dom_ms * 1e-3) / 1e9
     gstats = ctc_crf._C.graph_stats(ctc_crf._C.graph_for(dev))
     den_path = ctc_crf._C.den_kernels(ctc_crf._C.graph_for(dev), B, T, V)   # what a call of this shape takes (asked of the library)
     batch_path = den_path == "batch"
-    kname = {"factored": "crf_fac2_pair_kernel" if gstats.get("fac_geom") == 3 else "crf_fac_pair_kernel", "resident": "crf_res_pair_kernel",
-             "batch": "crf_batch_persist_kernel", "streaming": "crf_den_pair_kernel"}[den_path]
     den_symbol = ctc_crf._C.last_den_kernel()    # e.g. crf_fac_pair_kernel<true,768,21,4,4,false,false,0> (this thread's last call)
-    # utterance-minor kernels: one persistent launch (round 6), or one launch per frame (forward frame j + backward frame T-j) when the grid is not co-resident
-    launches = (T + 1) if batch_path and "persist" not in (den_symbol or "") else 1
-    # HBM traffic from the PMC counters: measured by tools/gpu_prof.sh (separate rocprofv3 --pmc passes) and committed
-    # keyed by workload; any other workload prints null instead of a number that does not belong to it
-    traffic, traffic_path = None, None
-    tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    if os.path.exists(tpath):
+
+    # --full: what the benchmark measures besides its headline, all of it after the timed steps
+    if args.full:
+        # --- hipEvent timing on the compute stream, median over 5 blocks of K steps ----------
+        blocks = []
+        for _ in range(5):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.steps):
+                step()
+            e1.record()
+            torch.cuda.synchronize()
+            blocks.append(e0.elapsed_time(e1) / args.steps)
+        event_blocks = {"blocks": 5, "steps_per_block": args.steps, "median_ms_per_step": round(float(np.median(blocks)), 4),
+                        "min_ms_per_step": round(min(blocks), 4), "max_ms_per_step": round(max(blocks), 4),
+                        "utt_per_s_at_median": round(B / (float(np.median(blocks)) * 1e-3), 1)}
+
+        # --- per-kernel durations, measured live with HIP events on the launch streams -------------
+        ctc_crf._C.profile_enable(True)
+        acc = {}
+        nprof = max(3, min(10, args.steps))
+        for _ in range(nprof):
+            step()
+            for k, v in ctc_crf._C.profile_read().items():
+                if v >= 0:
+                    acc.setdefault(k, []).append(v)
+        ctc_crf._C.profile_enable(False)
+        kern_ms = {k: float(np.mean(v)) for k, v in acc.items()}
+        bytes_den, bytes_num, bytes_den_pair = algorithmic_bytes(lx, ly, dims["S"], dims["A"], V)
+        dom = "den_fwd_chain"   # forward and backward recursions are ONE launch (slots den_fwd_chain and den_bwd_chain both time it)
+        dom_ms = kern_ms[dom]
+        achieved = bytes_den_pair / (dom_ms * 1e-3) / 1e9
+        kname = {"factored": "crf_fac2_pair_kernel" if gstats.get("fac_geom") == 3 else "crf_fac_pair_kernel", "resident": "crf_res_pair_kernel",
+                 "batch": "crf_batch_persist_kernel", "streaming": "crf_den_pair_kernel"}[den_path]
+        # utterance-minor kernels: one persistent launch (round 6), or one launch per frame (forward frame j + backward frame T-j) when the grid is not co-resident
+        launches = (T + 1) if batch_path and "persist" not in (den_symbol or "") else 1
+        # HBM traffic from the PMC counters: measured by tools/gpu_prof.sh (separate rocprofv3 --pmc passes) and committed
+        # keyed by workload; any other workload prints null instead of a number that does not belong to it
+        traffic, traffic_path = None, None
+        tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+        if os.path.exists(tpath):
+            try:
+                tj = json.load(open(tpath))
+                # ... AND by the template instantiation the library reports for the call that was timed: a number captured on another
+                # build of the kernel does not belong to this line either
+                if tj.get("workload") == workload_key(args, dims) and tj.get("den_kernel") == den_symbol:
+                    traffic = tj.get("kernels", {}).get(kname)
+                    traffic_path = tj.get("whole_path")
+            except Exception:
+                traffic = None
+        roofline = {
+            "bound": "hbm", "kernel": "%s (denominator forward + backward recursions of all utterances, %s)" % (
+                den_symbol or kname, "one launch" if launches == 1 else f"{launches} launches per call, one per frame; bytes and time below are per call"),
+            "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
+            "kernel_ms": round(dom_ms, 4), "algorithmic_bytes_per_launch": bytes_den_pair,
+            "kernels_ms": {k: round(v, 4) for k, v in kern_ms.items()},
+            # the BASELINE target is stated on the whole denominator forward-backward: official
+            # bytes_den (+ bytes_num) over the span first launch .. end of the grad pass
+            "den_fwd_bwd": {"bytes": bytes_den, "bytes_num": bytes_num, "ms": round(kern_ms.get("call", 0.0), 4),
+                            "frac_of_peak": round((bytes_den + bytes_num) / (kern_ms.get("call", 1e9) * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                            # every kernel of the call, PMC bytes over algorithmic bytes (Q and BP rows are both
+                            # materialised and read back; the numerator rows are fp64)
+                            "traffic_whole_path": traffic_path},
+        }
+
+        # secondary ceilings: arc evaluations and the 2T-step dependency chain bind before HBM does
+        arc_evals = 2 * int(np.asarray(lx, dtype=np.int64).sum()) * dims["A"]
+        roofline["ceilings"] = {
+            "arc_evals_per_step": arc_evals,
+            "arc_evals_per_s": round(arc_evals / (dom_ms * 1e-3)),
+            "dependent_frames": 2 * int(max(lx)),
+            "us_per_frame_den": round(dom_ms * 1e3 / max(1, int(max(lx))), 3),
+            "arc_stream_bytes_reference_style": 2 * B * int(max(lx)) * dims["A"] * 12,
+        }
+
+        # attainable HBM rate on this device ("confirm on the box"): a 1 GiB device-to-device copy, read + write
         try:
-            tj = json.load(open(tpath))
-            # ... AND by the template instantiation the library reports for the call that was timed: a number captured on another
-            # build of the kernel does not belong to this line either
-            if tj.get("workload") == workload_key(args, dims) and tj.get("den_kernel") == den_symbol:
-                traffic = tj.get("kernels", {}).get(kname)
-                traffic_path = tj.get("whole_path")
-        except Exception:
-            traffic = None
-    roofline = {
-        "bound": "hbm", "kernel": "%s (denominator forward + backward recursions of all utterances, %s)" % (
-            den_symbol or kname, "one launch" if launches == 1 else f"{launches} launches per call, one per frame; bytes and time below are per call"),
-        "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-        "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
-        "kernel_ms": round(dom_ms, 4), "algorithmic_bytes_per_launch": bytes_den_pair,
-        "kernels_ms": {k: round(v, 4) for k, v in kern_ms.items()},
-        # the BASELINE target is stated on the whole denominator forward-backward: official
-        # bytes_den (+ bytes_num) over the span first launch .. end of the grad pass
-        "den_fwd_bwd": {"bytes": bytes_den, "bytes_num": bytes_num, "ms": round(kern_ms.get("call", 0.0), 4),
-                        "frac_of_peak": round((bytes_den + bytes_num) / (kern_ms.get("call", 1e9) * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                        # every kernel of the call, PMC bytes over algorithmic bytes (Q and BP rows are both
-                        # materialised and read back; the numerator rows are fp64)
-                        "traffic_whole_path": traffic_path},
-    }
-
-    # secondary ceilings: arc evaluations and the 2T-step dependency chain bind before HBM does
-    arc_evals = 2 * int(np.asarray(lx, dtype=np.int64).sum()) * dims["A"]
-    roofline["ceilings"] = {
-        "arc_evals_per_step": arc_evals,
-        "arc_evals_per_s": round(arc_evals / (dom_ms * 1e-3)),
-        "dependent_frames": 2 * int(max(lx)),
-        "us_per_frame_den": round(dom_ms * 1e3 / max(1, int(max(lx))), 3),
-        "arc_stream_bytes_reference_style": 2 * B * int(max(lx)) * dims["A"] * 12,
-    }
-
-    # attainable HBM rate on this device ("confirm on the box"): a 1 GiB device-to-device copy, read + write
-    try:
-        buf = torch.empty(1 << 28, dtype=torch.float32, device=dev)
-        dst = torch.empty_like(buf)
-        dst.copy_(buf)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(4):
+            buf = torch.empty(1 << 28, dtype=torch.float32, device=dev)
+            dst = torch.empty_like(buf)
             dst.copy_(buf)
-        e1.record()
-        torch.cuda.synchronize()
-        roofline["ceilings"]["hbm_copy_GBs_measured"] = round(4 * 2 * buf.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9, 1)
-        del buf, dst
-    except Exception:  # informational only
-        pass
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(4):
+                dst.copy_(buf)
+            e1.record()
+            torch.cuda.synchronize()
+            roofline["ceilings"]["hbm_copy_GBs_measured"] = round(4 * 2 * buf.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9, 1)
+            del buf, dst
+        except Exception:  # informational only
+            pass
 
-    # --- strong scaling (N > 1): the SAME global batch of B utterances split over the ranks -------------
+    # --- strong scaling (--full, N > 1): the SAME global batch of B utterances split over the ranks -------------
     strong = None
-    if world > 1 and B % world == 0:
+    if args.full and world > 1 and B % world == 0:
         Bs = B // world
         lg2, lab2, lx2, ly2 = make_batch(g, Bs, T, V, seed=100 + rank, ragged=args.ragged)
         x2 = torch.tensor(lg2, device=dev, requires_grad=True)
@@ -364,9 +374,9 @@ def main():
         dts, _ = timed(step2, args.steps, args.warmup)
         strong = {"global_batch": B, "per_gpu": Bs, "value": round(B * args.steps / dts, 2), "ms_per_step": round(dts / args.steps * 1e3, 4)}
 
-    # --- the same step behind a DDP-wrapped stand-in acoustic model (N > 1, or --ddp-head) -------------
+    # --- the same step behind a DDP-wrapped stand-in acoustic model (--full, N > 1 or --ddp-head) -------------
     ddp_info = None
-    if world > 1 or args.ddp_head:
+    if args.full and (world > 1 or args.ddp_head):
         torch.manual_seed(0)
         model = StandInAM(V, args.ddp_layers).to(dev)
         nparam = sum(p.numel() for p in model.parameters())
@@ -392,7 +402,7 @@ def main():
 
     # --- CPU baseline: the oracle port (fp32, OpenMP over utterances) on this box's cores ------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import oracle
         from oracle import fst_io
         cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
@@ -438,10 +448,9 @@ def main():
                          "serial": bool(serial_run)},
             "fallback_utterances": {"denominator": fallback_den, "numerator": fallback_num},
             "workspace_bytes": workspace_bytes,
-            "event_blocks": event_blocks,
-            "roofline": roofline,
-            "cpu_baseline": cpu,
         }
+        if args.full:
+            out.update({"event_blocks": event_blocks, "roofline": roofline, "cpu_baseline": cpu})
         if strong:
             out["strong_scaling"] = strong
         if ddp_info:

@@ -1,7 +1,7 @@
 """bench.py's launcher contract: `--gpus N` without a launcher spawns N ranks itself (one process per GPU, as the
 reference does with mp.spawn, cat/shared/coreutils.py:493-504); a node with fewer GPUs gets a "not measured" line, never
 an extrapolation; under torch.distributed.run the rank initialises RCCL ("nccl"), checks world size and device
-distinctness, and the DDP stand-in leg runs (1-rank NCCL on the single GPU of the test box)."""
+distinctness, and with --full the DDP stand-in leg runs (1-rank NCCL on the single GPU of the test box)."""
 import importlib.util
 import json
 import os
@@ -33,6 +33,20 @@ def test_not_measured_when_gpus_missing():
     assert d["value"] is None and "not_measured" in d and d["n_gpus"] == have + 2
 
 
+def test_full_legs_are_opt_in(monkeypatch):
+    """A plain run times its steps and nothing else; the legs beside the headline run only with --full, and --ddp-head, which asks
+    for one of them, is refused without it instead of being ignored."""
+    bench = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--ddp-head"])
+    a = bench.parse()
+    assert a.full and a.ddp_head
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--ddp-head"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
 @pytest.mark.gpu
 def test_one_rank_nccl_with_ddp_stand_in():
     if not torch.cuda.is_available():
@@ -40,7 +54,7 @@ def test_one_rank_nccl_with_ddp_stand_in():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--B", "8", "--T", "200", "--histories", "256", "--fanout", "8", "--no-cpu-baseline", "--ddp-head", "--ddp-layers", "1",
+           "--B", "8", "--T", "200", "--histories", "256", "--fanout", "8", "--full", "--no-cpu-baseline", "--ddp-head", "--ddp-layers", "1",
            "--ddp-steps", "2"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-1500:]

@@ -61,6 +61,9 @@ def test_ddp_sharding_matches_full_batch(tmp_path):
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     out_dir = tempfile.mkdtemp()
+    # the oracle builds itself on first use when its library is missing or stale: do that here, once, so that the two
+    # ranks do not run the same make at the same time (one rank's build removes the objects the other is linking)
+    oracle._load()
     mp.spawn(_worker, args=(2, port, fst, (feats, labels, lx, ly), out_dir), nprocs=2, join=True)
     got = torch.load(os.path.join(out_dir, "ddp.pt"))
     torch.manual_seed(0)

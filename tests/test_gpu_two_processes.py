@@ -9,7 +9,7 @@ kernels on the same device at the same time.
       same encoder weights, and both ranks' losses average to the full-batch loss;
   (b) the same on a graph that takes the two-CUs-per-recursion layout forced (co-resident workgroups that spin on their
       peers: the second process's grid competes for the CUs);
-  (c) bench.py --gpus 2 --share-device: the harness' world_size > 1 legs (self-spawn, all_gather_object, strong scaling,
+  (c) bench.py --gpus 2 --share-device --full: the harness' world_size > 1 legs (self-spawn, all_gather_object, strong scaling,
       DDP head) executed once; the record says "not measured" instead of a value.
 """
 import json
@@ -118,13 +118,13 @@ def test_two_processes_share_a_device(tmp_path, switches):
 
 
 def test_bench_world_size_two_on_one_device():
-    """bench.py --gpus 2 --share-device: both ranks on cuda:0 over gloo; every world_size > 1 leg runs, nothing is reported as a
+    """bench.py --gpus 2 --share-device --full: both ranks on cuda:0 over gloo; every world_size > 1 leg runs, nothing is reported as a
     measurement (two ranks on one GPU are not the scaling the metric asks for)."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-device", "--steps", "3", "--warmup", "1",
-                          "--B", "8", "--T", "200", "--ddp-layers", "1", "--ddp-steps", "2", "--no-cpu-baseline"],
+                          "--B", "8", "--T", "200", "--full", "--ddp-layers", "1", "--ddp-steps", "2", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])

@@ -12,7 +12,7 @@ for spec in "$@"; do
   case "$rest" in @*) lib=${rest#@}; lib=${lib%%+*};; esac
   case "$rest" in *+*) dbg=${rest#*+};; esac
   L=""; [ -n "$lib" ] && L=$PWD/cat_amd/lib_ab/lib$lib.so
-  CRF_LIB=$L CRF_DEBUG=$dbg timeout 300 python bench.py --no-cpu-baseline --steps 20 --warmup 3 $EXTRA > $OUT/ab_$name.json 2> $OUT/ab_$name.err
+  CRF_LIB=$L CRF_DEBUG=$dbg timeout 300 python bench.py --full --no-cpu-baseline --steps 20 --warmup 3 $EXTRA > $OUT/ab_$name.json 2> $OUT/ab_$name.err
   python - <<PY
 import json
 try:

@@ -6,7 +6,7 @@ for rep in 1 2; do
 for n in "$@"; do
   lib=$PWD/cat_amd/lib_ab/lib$n.so; [ "$n" = prod ] && lib=$PWD/cat_amd/lib/libctc_crf_hip.so
   for ps in 1 0; do
-    CRF_LIB=$lib CRF_DEBUG=bat_persist=$ps timeout 300 python bench.py --no-cpu-baseline --histories ${H:-8192} --fanout ${D:-32} --steps 3 --warmup 1 2>/dev/null | python -c "
+    CRF_LIB=$lib CRF_DEBUG=bat_persist=$ps timeout 300 python bench.py --full --no-cpu-baseline --histories ${H:-8192} --fanout ${D:-32} --steps 3 --warmup 1 2>/dev/null | python -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.read()); k=d['roofline']['kernels_ms']; print('$n persist=$ps: step %.3f ms  den %.2f ms  %s  fallback %s' % (d['ms_per_step'], k['den_fwd_chain'], d['roofline']['kernel'].split(' ')[0], d['fallback_utterances']))

@@ -3,7 +3,7 @@
 # large-graph points persistent vs per-frame, and with `tm` the in-kernel phase stamps of a timing build (cat_amd/lib_ab/libtm.so).
 TAG=${1:-r6}; OUT=$PWD/gpurun_out; mkdir -p $OUT
 timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -x -q -k "batch" > $OUT/${TAG}_pytest_batch.log 2>&1; tail -2 $OUT/${TAG}_pytest_batch.log
-pt() { name=$1; shift; timeout 400 python bench.py --no-cpu-baseline "$@" > $OUT/${TAG}_$name.json 2> $OUT/${TAG}_$name.err || tail -3 $OUT/${TAG}_$name.err
+pt() { name=$1; shift; timeout 400 python bench.py --full --no-cpu-baseline "$@" > $OUT/${TAG}_$name.json 2> $OUT/${TAG}_$name.err || tail -3 $OUT/${TAG}_$name.err
   python -c "
 import json
 try:

@@ -5,7 +5,7 @@
 TAG=${1:-r2}
 OUT=$PWD/gpurun_out; mkdir -p $OUT
 REPO=$PWD
-run() { name=$1; shift; timeout 900 python bench.py --no-cpu-baseline "$@" > $OUT/pt_${TAG}_$name.json 2> $OUT/pt_${TAG}_$name.err || tail -5 $OUT/pt_${TAG}_$name.err
+run() { name=$1; shift; timeout 900 python bench.py --full --no-cpu-baseline "$@" > $OUT/pt_${TAG}_$name.json 2> $OUT/pt_${TAG}_$name.err || tail -5 $OUT/pt_${TAG}_$name.err
   python - <<PY
 import json
 try:

@@ -3,7 +3,7 @@
 # large synthetic den_lm (one JSON line each, no CPU baseline)
 TAG=${1:-r1}
 OUT=$PWD/gpurun_out; mkdir -p $OUT
-run() { name=$1; shift; timeout 600 python bench.py --no-cpu-baseline "$@" > $OUT/pt_${TAG}_$name.json 2> $OUT/pt_${TAG}_$name.err || tail -3 $OUT/pt_${TAG}_$name.err
+run() { name=$1; shift; timeout 600 python bench.py --full --no-cpu-baseline "$@" > $OUT/pt_${TAG}_$name.json 2> $OUT/pt_${TAG}_$name.err || tail -3 $OUT/pt_${TAG}_$name.err
   python - <<PY
 import json
 try:

@@ -8,7 +8,7 @@ OUT=$PWD/gpurun_out; mkdir -p $OUT
 if [ -z "$QUICK" ]; then
   timeout 2400 python -m pytest tests -m gpu -q -x --timeout 1500 > $OUT/pytest_$TAG.log 2>&1; echo "pytest rc=$?" >> $OUT/pytest_$TAG.log; tail -4 $OUT/pytest_$TAG.log
 fi
-timeout 600 python bench.py > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; echo "bench rc=$?"; cut -c1-600 $OUT/bench_$TAG.json
+timeout 600 python bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; echo "bench rc=$?"; cut -c1-600 $OUT/bench_$TAG.json
 bash tools/gpu_prof.sh $TAG 2>&1 | grep -v amdgpu.ids | tail -22
 # (gpu_prof.sh leaves RCCL's banner in front of the torchrun record: keep the JSON line only)
 grep '^{' $OUT/torchrun1_$TAG.json > $OUT/torchrun1_$TAG.tmp && mv $OUT/torchrun1_$TAG.tmp $OUT/torchrun1_$TAG.json
