@@ -1,7 +1,8 @@
 """cat_amd/build.py -- compile the gfx950 HIP library in-tree (cat_amd/lib/libctc_crf_hip.so).
 
 `python -m cat_amd.build [--force] [-v] [--only k_fac.hip,...]`.  hipcc cross-compiles without a GPU.  One translation unit per kernel
-family (csrc/k_*.hip) plus the host side (crf_host.hip) and the graph compiler (fst_graph.cpp, res_layout.cpp), compiled IN PARALLEL into
+family (csrc/k_*.hip) plus the host side (crf_host.hip, and ctc_api.cpp: the warp-ctc C API of include/ctc.h) and the graph compiler
+(fst_graph.cpp, res_layout.cpp), compiled IN PARALLEL into
 objects under cat_amd/lib/obj[-<tag>]/ and linked with -z defs (a kernel instantiation the host launches but no family instantiates is a
 link error).  Objects are rebuilt when their source or any header is newer.  The .so is git-ignored but travels with gpurun snapshots.
 
@@ -17,9 +18,9 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 FAMILIES = ["k_fac_768.hip", "k_fac_pair2.hip", "k_fac_1024.hip", "k_batch.hip", "k_grad.hip", "k_res.hip", "k_chain.hip", "k_robust.hip"]   # slowest first
-UNITS = FAMILIES + ["crf_host.hip", "res_layout.cpp", "fst_graph.cpp"]
+UNITS = FAMILIES + ["crf_host.hip", "res_layout.cpp", "fst_graph.cpp", "ctc_api.cpp"]
 HEADERS = [os.path.join(CSRC, h) for h in ("crf_internal.h", "crf_device.h", "crf_kernels_decl.h", "k_res_common.h", "k_fac_body.h")] + \
-          [os.path.join(os.path.dirname(HERE), "include", "ctc_crf_hip.h")]
+          [os.path.join(os.path.dirname(HERE), "include", h) for h in ("ctc_crf_hip.h", "ctc.h")]
 OUT = os.environ.get("CRF_BUILD_OUT") or os.path.join(HERE, "lib", "libctc_crf_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SRCS = [os.path.join(CSRC, u) for u in UNITS]
@@ -55,7 +56,7 @@ def build(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
     defs = os.environ.get("CRF_BUILD_DEFS", "").split()
     units = list(UNITS)
     if any(d.startswith("-DCRF_TIMING") for d in defs):
-        units = ["crf_unity.hip", "res_layout.cpp", "fst_graph.cpp"]
+        units = ["crf_unity.hip", "res_layout.cpp", "fst_graph.cpp", "ctc_api.cpp"]
     jobs = jobs or int(os.environ.get("CRF_BUILD_JOBS", "0")) or min(len(units), os.cpu_count() or 4)
     with ThreadPoolExecutor(jobs) as ex:
         objs = list(ex.map(lambda u: _compile(u, defs, verbose, force), units))

@@ -87,6 +87,10 @@ struct LossParams {
     const float *logp;
     const int *labels, *lab_off, *lx, *ly;
     int B, T, V;
+    // Row (b, t) of the caller's activations `logp` and of `grad` starts at b * xs_b + t * xs_t floats: [B][T][V] (xs_b = T V, xs_t = V), or
+    // time-major [T][B][V] (xs_b = V, xs_t = B V; numerator-only calls).  The staged rows (ep, mx, moff, inv_s, CA, CB, ...) stay [B][T].
+    int64_t xs_b, xs_t;
+    int blank;    // numerator: the blank's column (0 with a den_lm: label = ilabel - 1)
     int res_lds_rows_f, res_lds_rows_b;  // max rows per CU (LDS carve of the resident kernels)
     int Sc;       // row stride of the ctc per-frame stores: 2*max_label_len+1 rounded up to 64
     float c_den, c_ctc;
@@ -333,6 +337,9 @@ __device__ __forceinline__ float ld_x(const LossParams &p, int64_t i) {
     return (float)__builtin_bit_cast(_Float16, u);
 }
 
+// first element of row (b, t) of the caller's activations / gradient (see LossParams::xs_b)
+__device__ __forceinline__ int64_t xrow(const LossParams &p, int b, int t) { return (int64_t)b * p.xs_b + (int64_t)t * p.xs_t; }
+
 // block-wide helpers for the 1024-thread chain workgroups --------------------------------------
 __device__ __forceinline__ float block_sum(float v, float *red, int tid) {
     v = wave_sum(v);
@@ -425,7 +432,7 @@ __device__ __forceinline__ bool ctc_setup(const LossParams &p, int b, const CtcL
     const int *ul = p.labels + p.lab_off[b];
     const int Sx = 2 * L + 1;
     float rep = 0.f;
-    for (int s = tid; s < Sx; s += kCtcThreads) c.lab[s] = (s & 1) ? ul[s >> 1] : 0;
+    for (int s = tid; s < Sx; s += kCtcThreads) c.lab[s] = (s & 1) ? ul[s >> 1] : p.blank;
     for (int i = tid + 1; i < L; i += kCtcThreads) rep += (ul[i] == ul[i - 1]) ? 1.f : 0.f;
     const int repeats = (int)(ctc_block_sum(rep, (float *)c.red, tid) + 0.5f);  // also orders the lab[] writes
     __syncthreads();

@@ -747,7 +747,7 @@ static int loss_impl(const crf_graph *g, const float *logp, int fused, int in_dt
                      const int32_t *lx, const int32_t *ly, int64_t B, int64_t T, int64_t V,
                      int64_t max_label_len, float c_den, float c_ctc, float *grad, float *loss,
                      float *costs_den, float *costs_beta, float *costs_ctc, int32_t *invalid, void *ws,
-                     int64_t ws_bytes, void *stream_);
+                     int64_t ws_bytes, void *stream_, int time_major = 0, int blank = 0);
 
 int crf_loss_fwd_bwd(const crf_graph *g, const float *logp, const int32_t *labels, const int32_t *lab_off,
                      const int32_t *lx, const int32_t *ly, int64_t B, int64_t T, int64_t V,
@@ -769,11 +769,19 @@ int crf_loss_fwd_bwd_logits(const crf_graph *g, const void *logits, int dtype, c
                      costs_den, costs_beta, costs_ctc, invalid, ws, ws_bytes, stream_);
 }
 
+int crf_ctc_fwd_bwd(const float *act, int time_major, int blank, const int32_t *labels, const int32_t *lab_off, const int32_t *lx,
+                    const int32_t *ly, int64_t B, int64_t T, int64_t V, int64_t max_label_len, float c_ctc, float *grad, float *loss,
+                    float *costs_ctc, int32_t *invalid, void *ws, int64_t ws_bytes, void *stream_) {
+    if (c_ctc == 0.f) { set_error("crf_ctc_fwd_bwd: c_ctc is zero"); return CRF_ERR_ARG; }
+    return loss_impl(nullptr, act, 0, 0, labels, lab_off, lx, ly, B, T, V, max_label_len, 0.f, c_ctc, grad, loss, nullptr, nullptr,
+                     costs_ctc, invalid, ws, ws_bytes, stream_, time_major, blank);
+}
+
 static int loss_impl(const crf_graph *g, const float *logp, int fused, int in_dtype, const int32_t *labels, const int32_t *lab_off,
                      const int32_t *lx, const int32_t *ly, int64_t B, int64_t T, int64_t V,
                      int64_t max_label_len, float c_den, float c_ctc, float *grad, float *loss,
                      float *costs_den, float *costs_beta, float *costs_ctc, int32_t *invalid, void *ws,
-                     int64_t ws_bytes, void *stream_) {
+                     int64_t ws_bytes, void *stream_, int time_major, int blank) {
     hipStream_t stream = (hipStream_t)stream_;
     const bool den = c_den != 0.f, ctc = c_ctc != 0.f;
     if (!logp || !lx || !grad || !loss || !ws) { set_error("null argument"); return CRF_ERR_ARG; }
@@ -781,6 +789,13 @@ static int loss_impl(const crf_graph *g, const float *logp, int fused, int in_dt
     if (!den && !ctc) { set_error("c_den and c_ctc are both zero"); return CRF_ERR_ARG; }
     if (den && (!g || !g->h)) { set_error("denominator requested without a graph"); return CRF_ERR_ARG; }
     if (ctc && (!labels || !lab_off || !ly || max_label_len < 0)) { set_error("numerator requested without labels"); return CRF_ERR_ARG; }
+    // The blank's column and the row layout are options of the numerator alone: a den_lm fixes the blank at 0 (label = ilabel - 1),
+    // and the denominator and fused-logits kernels read [B][T][V] rows.  (Labels are device memory here: the callers check them.)
+    if (blank < 0 || blank >= V) { set_error("blank " + std::to_string(blank) + " outside [0, V=" + std::to_string(V) + ")"); return CRF_ERR_ARG; }
+    if (den && blank != 0) { set_error("a blank other than 0 is for numerator-only calls: a den_lm fixes the blank at 0"); return CRF_ERR_UNSUPPORTED; }
+    if (time_major && (den || fused)) {
+        set_error("time-major activations are for numerator-only calls on log-probs (no den_lm, no fused log_softmax)"); return CRF_ERR_UNSUPPORTED;
+    }
     const HostGraph *h = den ? g->h : nullptr;
     if (den && V <= h->dev.max_label) {
         set_error("den_lm has label " + std::to_string(h->dev.max_label) + " but log_probs has only V=" + std::to_string(V) + " classes");
@@ -818,6 +833,8 @@ static int loss_impl(const crf_graph *g, const float *logp, int fused, int in_dt
     if (FX) p.g.fac = *FX;
     p.logp = logp; p.labels = labels; p.lab_off = lab_off; p.lx = lx; p.ly = ly;
     p.B = (int)B; p.T = (int)T; p.V = (int)V; p.Sc = Sc;
+    p.xs_b = time_major ? V : T * V; p.xs_t = time_major ? B * V : V;
+    p.blank = blank;
     p.c_den = c_den; p.c_ctc = c_ctc;
     char *base = (char *)ws;
     p.ep = (float *)(base + w.off_ep); p.mx = (float *)(base + w.off_mx);

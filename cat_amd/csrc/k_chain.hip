@@ -27,7 +27,7 @@ __global__ __launch_bounds__(256) void crf_prep_kernel(LossParams p) {
     if (f >= (int64_t)p.B * p.T) return;
     const int b = (int)(f / p.T), t = (int)(f % p.T);
     if (p.zero_grad) {                            // (every frame, the ones past the utterance's length too)
-        float *gr = p.grad + f * p.V;
+        float *gr = p.grad + xrow(p, b, t);
         for (int v = sub; v < p.V; v += G) gr[v] = 0.f;
     }
     if (t >= p.lx[b]) return;                     // (whole groups of G lanes leave together)
@@ -41,7 +41,7 @@ __global__ __launch_bounds__(256) void crf_prep_kernel(LossParams p) {
         for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, G);
         return v;
     };
-    const int64_t r0 = f * p.V;
+    const int64_t r0 = xrow(p, b, t);             // (the caller's layout; the staged rows below are [B][T])
     float m = -INFINITY;
     float *er = p.ep + f * p.V;
     float ssum = 0.f;
@@ -431,13 +431,13 @@ template <int NR>
 __device__ __forceinline__ void ctc_forward(const LossParams &p, int b, float *lds) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int V = p.V, lx = p.lx[b], L = p.ly[b], Sx = 2 * L + 1, Sxp = rup64(Sx);
+    const int lx = p.lx[b], L = p.ly[b], Sx = 2 * L + 1, Sxp = rup64(Sx);
     const CtcLds c = ctc_carve(lds, Sxp);
     double *A = c.A;
     int *wmi = (int *)c.wm;                    // [3] frame maxima (high words) in rotation
     int sr = 1;                                // slot read by the next frame (frame 1 reads slot 1)
     const int *lab = c.lab;
-    const int64_t bt0 = (int64_t)b * p.T;
+    const int64_t bt0 = (int64_t)b * p.T, xb = xrow(p, b, 0);
     const bool valid = ctc_setup(p, b, c, L, lx, tid);
     if (!valid) {
         if (tid == 0) {
@@ -452,7 +452,7 @@ __device__ __forceinline__ void ctc_forward(const LossParams &p, int b, float *l
     for (int i = 0; i < NR; ++i) {
         const int s = tid + i * kCtcThreads;
         mylab[i] = s < Sx ? lab[s] : 0;
-        skip[i] = s < Sx && s >= 2 && mylab[i] != 0 && mylab[i] != lab[s - 2];
+        skip[i] = s < Sx && s >= 2 && mylab[i] != p.blank && mylab[i] != lab[s - 2];
     }
     // the label as an UNSIGNED byte offset: the emission loads are then `global_load v, v_off, s[row]` -- a uniform row base and one VGPR; with
     // a signed index the compiler kept a 64-bit pointer per lane (logp + label) and added the row to it with a v_lshl_add_u64 per load: the
@@ -465,7 +465,7 @@ __device__ __forceinline__ void ctc_forward(const LossParams &p, int b, float *l
     // The frame maximum used for the (exact, power-of-two) rescale is taken from the values as they are
     // WRITTEN: one barrier per frame instead of a separate reduction pass plus barrier.
     {   // t = 0 (gpu_ctc_kernels.h:146-152)
-        const int64_t lr0 = bt0 * V;
+        const int64_t lr0 = xb;
         const float m0 = p.mx[bt0];
         double *CArow = p.CA + bt0 * p.Sc;
         double vmax = 0.0;
@@ -502,7 +502,7 @@ __device__ __forceinline__ void ctc_forward(const LossParams &p, int b, float *l
     auto fetch1 = [&](auto SET, auto F, int t) __attribute__((always_inline)) {
         constexpr int st = decltype(SET)::value, f = decltype(F)::value;
         if (t < lx) {
-            const int64_t row0 = (bt0 + t) * V;
+            const int64_t row0 = xb + (int64_t)t * p.xs_t;
             unsigned vz;   // (a fresh zero per load: hoisted out of the loop, `p.mx + vz` was a 64-bit pointer per lane -- and the register the kernel spilled)
             asm volatile("v_mov_b32 %0, 0" : "=v"(vz));
             mr[st][f] = *(const float *)((const char *)(p.mx + bt0 + t) + vz);
@@ -641,13 +641,13 @@ template <int NR>
 __device__ __forceinline__ void ctc_backward(const LossParams &p, int b, float *lds) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int V = p.V, lx = p.lx[b], L = p.ly[b], Sx = 2 * L + 1, Sxp = rup64(Sx);
+    const int lx = p.lx[b], L = p.ly[b], Sx = 2 * L + 1, Sxp = rup64(Sx);
     const CtcLds c = ctc_carve(lds, Sxp);
     double *Y = c.A;
     int *wmi = (int *)c.wm;
     int sr = 1;
     const int *lab = c.lab;
-    const int64_t bt0 = (int64_t)b * p.T;
+    const int64_t bt0 = (int64_t)b * p.T, xb = xrow(p, b, 0);
     if (!ctc_setup(p, b, c, L, lx, tid)) return;
     int mylab[NR];
     bool skip[NR];
@@ -655,7 +655,7 @@ __device__ __forceinline__ void ctc_backward(const LossParams &p, int b, float *
     for (int i = 0; i < NR; ++i) {
         const int s = tid + i * kCtcThreads;
         mylab[i] = s < Sx ? lab[s] : 0;
-        skip[i] = (s + 2 < Sx) && lab[s + 2] != 0 && lab[s + 2] != mylab[i];
+        skip[i] = (s + 2 < Sx) && lab[s + 2] != p.blank && lab[s + 2] != mylab[i];
     }
     unsigned labo[NR];   // (see ctc_forward)
 #pragma unroll
@@ -663,7 +663,7 @@ __device__ __forceinline__ void ctc_backward(const LossParams &p, int b, float *
     int F_ = kScaleExpD;
     const double rho = ctc_rho(p, b, Sx, lx, c.red, tid), rho2 = rho * rho;
     {   // t = lx-1
-        const int64_t lr0 = (bt0 + lx - 1) * V;
+        const int64_t lr0 = xb + (int64_t)(lx - 1) * p.xs_t;
         const float ml = p.mx[bt0 + lx - 1];
         double *CBrow = p.CB + (bt0 + lx - 1) * p.Sc;
         double vmax = 0.0;
@@ -691,7 +691,7 @@ __device__ __forceinline__ void ctc_backward(const LossParams &p, int b, float *
     auto fetch1 = [&](auto SET, auto F, int t) __attribute__((always_inline)) {
         constexpr int st = decltype(SET)::value, f = decltype(F)::value;
         if (t >= 0) {
-            const int64_t row0 = (bt0 + t) * V;
+            const int64_t row0 = xb + (int64_t)t * p.xs_t;
             unsigned vz;   // (a fresh zero per load: hoisted out of the loop, `p.mx + vz` was a 64-bit pointer per lane -- and the register the kernel spilled)
             asm volatile("v_mov_b32 %0, 0" : "=v"(vz));
             mr[st][f] = *(const float *)((const char *)(p.mx + bt0 + t) + vz);

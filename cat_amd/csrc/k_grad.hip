@@ -37,7 +37,7 @@ __global__ __launch_bounds__(kGradThreads) void crf_grad_kernel(LossParams p) {
 
     const int t0 = blockIdx.x * kGradFrames;
     for (int t = t0; t < t0 + kGradFrames && t < p.T; ++t) {
-        float *row = p.grad + (bt0 + t) * V;
+        float *row = p.grad + xrow(p, b, t);
         if (t >= lx) {
             if (!accumulate)
                 for (int v = tid; v < V; v += kGradThreads) row[v] = 0.f;
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(kGradThreads) void crf_grad_kernel(LossParams p) {
                     else blank += pr;
                 }
                 blank = wave_sum(blank);
-                if (lane == 0) atomicAdd(&gc[0], blank);
+                if (lane == 0) atomicAdd(&gc[p.blank], blank);
             }
         }
         __syncthreads();
@@ -582,7 +582,7 @@ __global__ __launch_bounds__(kGCThreads) void crf_grad_ctc_kernel(LossParams p) 
             if (s < Sx) { an[i] = Ar[s]; bn[i] = Br[s]; }                                        \
         }                                                                                        \
         if (accumulate) {                                                                        \
-            const float *row_ = p.grad + (bt0 + (t)) * V;                                        \
+            const float *row_ = p.grad + xrow(p, b, (t));                                        \
             _Pragma("unroll") for (int q = 0; q < kGCVRegs; ++q) rown[q] = row_[min(tid + q * kGCThreads, V - 1)]; \
         }                                                                                        \
         if (p.fused) {   /* softmax term of log_softmax's backward, folded (in CONSUME) into the row the frame starts from */ \
@@ -632,7 +632,7 @@ __global__ __launch_bounds__(kGCThreads) void crf_grad_ctc_kernel(LossParams p) 
                 }
             blank = wave_sum(blank);
             if (CRF_X_CTCSUM) tot = wave_sum(tot);
-            if (lane == 0) { atomicAdd(&g[0], blank); if (CRF_X_CTCSUM) atomicAdd(&gt[t & 3], tot + blank); }
+            if (lane == 0) { atomicAdd(&g[p.blank], blank); if (CRF_X_CTCSUM) atomicAdd(&gt[t & 3], tot + blank); }
         }
 #pragma unroll
         for (int q = 0; q < kGCVRegs; ++q) {
@@ -655,7 +655,7 @@ __global__ __launch_bounds__(kGCThreads) void crf_grad_ctc_kernel(LossParams p) 
         // take the next frame's loads out of their registers BEFORE this frame's stores are issued (a
         // vmcnt wait behind the stores would also wait for their acknowledgement)
         if constexpr (more) CRF_GC_CONSUME();
-        float *row = p.grad + (bt0 + t) * V;
+        float *row = p.grad + xrow(p, b, t);
 #pragma unroll
         for (int q = 0; q < kGCVRegs; ++q) {
             const int v = tid + q * kGCThreads;
@@ -671,7 +671,7 @@ __global__ __launch_bounds__(kGCThreads) void crf_grad_ctc_kernel(LossParams p) 
 #undef CRF_GC_FETCH
     if (!accumulate && !atomic)
         for (int t = max(t0, tl); t < t1; ++t) {
-            float *row = p.grad + (bt0 + t) * V;
+            float *row = p.grad + xrow(p, b, t);
             for (int v = tid; v < V; v += kGCThreads) row[v] = 0.f;
         }
 }

@@ -397,7 +397,7 @@ __global__ __launch_bounds__(kCtcThreads) void crf_robust_ctc_kernel(LossParams 
     const int redo = p.redo_ctc[b], done = p.ctc_logdom[b];
     if (!redo || (done != 0 && done != p.ctc_pass)) return;   // not marked, or redone by an earlier pass of this call
     const int tid = threadIdx.x;
-    const int V = p.V, lx = p.lx[b], L = p.ly[b], Sx = 2 * L + 1, Sxp = rup64(Sx);
+    const int lx = p.lx[b], L = p.ly[b], Sx = 2 * L + 1, Sxp = rup64(Sx);
     const CtcLds c = ctc_carve(lds, Sxp);
     double *A = c.A;
     const int *lab = c.lab;
@@ -410,8 +410,8 @@ __global__ __launch_bounds__(kCtcThreads) void crf_robust_ctc_kernel(LossParams 
     for (int i = 0; i < NR; ++i) {
         const int s = tid + i * kCtcThreads;
         mylab[i] = s < Sx ? lab[s] : 0;
-        skip[i] = fwd ? (s < Sx && s >= 2 && mylab[i] != 0 && mylab[i] != lab[s - 2])
-                      : ((s + 2 < Sx) && lab[s + 2] != 0 && lab[s + 2] != mylab[i]);
+        skip[i] = fwd ? (s < Sx && s >= 2 && mylab[i] != p.blank && mylab[i] != lab[s - 2])
+                      : ((s + 2 < Sx) && lab[s + 2] != p.blank && lab[s + 2] != mylab[i]);
     }
     // log p_t[l'_s] = (x_t[l] - max_t) + offset_t (offset = the row maximum, or -log sum exp(x - max) with the fused log_softmax).
     // Emissions are fetched in BATCHES of kCtcPF frames into two alternating register sets, as in the scaled chains: one wait on
@@ -427,12 +427,12 @@ __global__ __launch_bounds__(kCtcThreads) void crf_robust_ctc_kernel(LossParams 
             if (t >= 0 && t < lx) {
                 of[st][f] = (double)p.moff[bt0 + t] - (double)p.mx[bt0 + t];
 #pragma unroll
-                for (int i = 0; i < NR; ++i) lr[st][f][i] = (tid + i * kCtcThreads < Sx) ? ld_x(p, (bt0 + t) * V + mylab[i]) : 0.f;
+                for (int i = 0; i < NR; ++i) lr[st][f][i] = (tid + i * kCtcThreads < Sx) ? ld_x(p, xrow(p, b, t) + mylab[i]) : 0.f;
             }
         }
     };
     auto lp0 = [&](int t, int i) -> double {   // (set-up frames only)
-        return ((double)ld_x(p, (bt0 + t) * V + mylab[i]) - (double)p.mx[bt0 + t]) + (double)p.moff[bt0 + t];
+        return ((double)ld_x(p, xrow(p, b, t) + mylab[i]) - (double)p.mx[bt0 + t]) + (double)p.moff[bt0 + t];
     };
     if (fwd) {
         double *CArow = p.CA + bt0 * p.Sc;
@@ -558,9 +558,9 @@ __global__ __launch_bounds__(kGradThreads) void crf_robust_ctc_fix_kernel(LossPa
             else blank += pr;
         }
         blank = wave_sum(blank);
-        if (lane == 0) atomicAdd(&gc[0], blank);
+        if (lane == 0) atomicAdd(&gc[p.blank], blank);
         __syncthreads();
-        float *row = p.grad + (bt0 + t) * V;
+        float *row = p.grad + xrow(p, b, t);
         // (an utterance redone whole went through the grad pass as "no numerator": with the fused log_softmax its softmax term
         // was taken with the factor c_den instead of c_den - c_ctc)
         const float ks = (redo == 2 && p.fused) ? p.c_ctc * pow2f(-kEpExp) * p.inv_s[bt0 + t] : 0.f;

@@ -45,6 +45,9 @@ _lib.crf_loss_fwd_bwd.restype = ctypes.c_int
 _lib.crf_loss_fwd_bwd_logits.argtypes = [_vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _f32,
                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]
 _lib.crf_loss_fwd_bwd_logits.restype = ctypes.c_int
+_lib.crf_ctc_fwd_bwd.argtypes = [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32,
+                                 _vp, _vp, _vp, _vp, _vp, _i64, _vp]
+_lib.crf_ctc_fwd_bwd.restype = ctypes.c_int
 _lib.crf_profile_enable.argtypes = [ctypes.c_int]
 _lib.crf_profile_enable.restype = None
 _lib.crf_profile_read.argtypes = [ctypes.POINTER(_f32), ctypes.c_int]
@@ -69,7 +72,7 @@ _lib.crf_build_switches.restype = ctypes.c_char_p
 
 EXPORTED_SYMBOLS = (
     "crf_graph_create", "crf_graph_create_from_arcs", "crf_graph_destroy", "crf_graph_dims", "crf_graph_stats",
-    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
+    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
     "crf_debug_set", "crf_debug_unset", "crf_debug_list", "crf_last_den_kernel", "crf_last_call_streams", "crf_last_side_stream", "crf_last_fallback_counts", "crf_build_switches", "crf_last_error", "crf_version",
 )
 
@@ -396,7 +399,7 @@ def set_debug_poison(on: bool) -> None:
     _POISON_WS = bool(on)
 
 
-def _validate_meta(lx_cpu, ly_cpu, lab_cpu, T: int, V: int) -> None:
+def _validate_meta(lx_cpu, ly_cpu, lab_cpu, T: int, V: int, blank: int = 0) -> None:
     """Host-resident metadata is checked before the launch (no device sync: these tensors are on the CPU already).
     The reference does not check: lx > T walks past the buffers, a label >= V indexes the logits out of bounds
     (gpu_ctc_kernels.h:146-152 reads probs[... + label])."""
@@ -408,19 +411,30 @@ def _validate_meta(lx_cpu, ly_cpu, lab_cpu, T: int, V: int) -> None:
         if int(ly_cpu.sum()) > lab_cpu.numel():
             raise RuntimeError(f"sum(label_lengths)={int(ly_cpu.sum())} exceeds len(labels)={lab_cpu.numel()}")
         n = int(ly_cpu.sum())
-        if n and (int(lab_cpu[:n].min()) <= 0 or int(lab_cpu[:n].max()) >= V):
-            raise RuntimeError(f"labels must lie in [1, V-1={V - 1}] (0 is the blank), got [{int(lab_cpu[:n].min())}, {int(lab_cpu[:n].max())}]")
+        if blank == 0:
+            if n and (int(lab_cpu[:n].min()) <= 0 or int(lab_cpu[:n].max()) >= V):
+                raise RuntimeError(f"labels must lie in [1, V-1={V - 1}] (0 is the blank), got [{int(lab_cpu[:n].min())}, {int(lab_cpu[:n].max())}]")
+        elif n and (int(lab_cpu[:n].min()) < 0 or int(lab_cpu[:n].max()) >= V or bool((lab_cpu[:n] == blank).any())):
+            raise RuntimeError(f"labels must lie in [0, V-1={V - 1}] without the blank {blank}, got [{int(lab_cpu[:n].min())}, {int(lab_cpu[:n].max())}]"
+                               + (" and the blank itself" if bool((lab_cpu[:n] == blank).any()) else ""))
 
 
 def loss_fwd_bwd(logits: torch.Tensor, labels: Optional[torch.Tensor], lx: torch.Tensor,
                  ly: Optional[torch.Tensor], c_den: float, c_ctc: float, graph: Optional[int],
-                 want_costs: bool = False, fused: bool = False):
+                 want_costs: bool = False, fused: bool = False, time_major: bool = False, blank: int = 0,
+                 grad_out: Optional[torch.Tensor] = None):
     """One call of the hot path (include/ctc_crf_hip.h ``crf_loss_fwd_bwd``).
 
     logits [N,T,V] f32 on the GPU, contiguous; labels/lx/ly int32 on CPU (as CAT passes them,
     cat/ctc/train.py:176-190) or on the GPU.  Returns (loss[1], grad[N,T,V], extras dict).
+    Numerator-only calls (c_den == 0, not fused; ``crf_ctc_fwd_bwd``) also take time_major=True -- logits and the
+    returned gradient are [T,N,V] -- and any blank column in [0, V); grad_out: a contiguous f32 tensor of logits'
+    shape that receives the gradient (else one is allocated).
     """
     assert logits.is_cuda and logits.is_contiguous() and logits.dim() == 3
+    if (time_major or blank != 0) and (c_den != 0.0 or fused):
+        raise RuntimeError("time_major and a blank other than 0 are for numerator-only calls (WARP_CTC_LOSS / gpu_ctc): "
+                           "the den_lm fixes the blank at 0 and the CTC-CRF kernels read [N,T,V] log-probs")
     if fused:   # raw network output, log_softmax fused in (crf_loss_fwd_bwd_logits)
         if logits.dtype not in _FUSED_DTYPES:
             raise RuntimeError(f"fused log_softmax: expect float32, bfloat16 or float16 network output, got {logits.dtype}")
@@ -428,6 +442,10 @@ def loss_fwd_bwd(logits: torch.Tensor, labels: Optional[torch.Tensor], lx: torch
         assert logits.dtype == torch.float32
     dev = logits.device
     N, T, V = logits.shape
+    if time_major:
+        T, N = N, T
+    if not 0 <= blank < V:
+        raise RuntimeError(f"blank must lie in [0, V-1={V - 1}], got {blank}")
     lx32 = lx.to(torch.int32)
     if c_ctc != 0.0:
         ly32 = ly.to(torch.int32)
@@ -436,7 +454,7 @@ def loss_fwd_bwd(logits: torch.Tensor, labels: Optional[torch.Tensor], lx: torch
         off = (torch.cumsum(ly_cpu, 0, dtype=torch.int32) - ly_cpu).to(torch.int32)
         lab32 = labels.to(torch.int32).reshape(-1)
         if not lx32.is_cuda and not lab32.is_cuda:
-            _validate_meta(lx32, ly_cpu, lab32, T, V)
+            _validate_meta(lx32, ly_cpu, lab32, T, V, blank)
         if lab32.numel() == 0:
             lab32 = torch.zeros(1, dtype=torch.int32)
         # one H2D copy for all integer metadata (the reference issues ~5, gpu_ctc.h:143-229), through pinned
@@ -455,7 +473,11 @@ def loss_fwd_bwd(logits: torch.Tensor, labels: Optional[torch.Tensor], lx: torch
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     if _POISON_WS:
         ws.fill_(0xFF)   # every float / double / int32 of the workspace reads as NaN / -1
-    grad = torch.empty(logits.shape, dtype=torch.float32, device=dev)
+    if grad_out is not None:
+        assert grad_out.shape == logits.shape and grad_out.dtype == torch.float32 and grad_out.is_contiguous() and grad_out.device == dev
+        grad = grad_out
+    else:
+        grad = torch.empty(logits.shape, dtype=torch.float32, device=dev)
     out = torch.empty(1 + 3 * N, dtype=torch.float32, device=dev)
     invalid = torch.empty(N, dtype=torch.int32, device=dev) if c_ctc != 0.0 else None
     loss, c_alpha, c_beta, c_ctc_t = out[:1], out[1:1 + N], out[1 + N:1 + 2 * N], out[1 + 2 * N:]
@@ -465,6 +487,10 @@ def loss_fwd_bwd(logits: torch.Tensor, labels: Optional[torch.Tensor], lx: torch
             rc = _lib.crf_loss_fwd_bwd_logits(gh, _ptr(logits), _FUSED_DTYPES[logits.dtype], _ptr(lab_d), _ptr(off_d), _ptr(lx_d),
                                               _ptr(ly_d), N, T, V, max_l, c_den, c_ctc, _ptr(grad), _ptr(loss), _ptr(c_alpha),
                                               _ptr(c_beta), _ptr(c_ctc_t), _ptr(invalid), _ptr(ws), ws_bytes, _vp(stream))
+        elif c_den == 0.0:   # numerator only: the layout and blank options (crf_loss_fwd_bwd's arguments, c_den = 0, in the default layout)
+            rc = _lib.crf_ctc_fwd_bwd(_ptr(logits), 1 if time_major else 0, blank, _ptr(lab_d), _ptr(off_d), _ptr(lx_d), _ptr(ly_d),
+                                      N, T, V, max_l, c_ctc, _ptr(grad), _ptr(loss), _ptr(c_ctc_t), _ptr(invalid), _ptr(ws), ws_bytes,
+                                      _vp(stream))
         else:
             rc = _lib.crf_loss_fwd_bwd(gh, _ptr(logits), _ptr(lab_d), _ptr(off_d), _ptr(lx_d), _ptr(ly_d),
                                        N, T, V, max_l, c_den, c_ctc, _ptr(grad), _ptr(loss), _ptr(c_alpha),
@@ -489,12 +515,16 @@ def gpu_den(logits: torch.Tensor, grad_net: torch.Tensor, input_lengths: torch.T
 def gpu_ctc(probs: torch.Tensor, grads: torch.Tensor, labels: torch.Tensor, label_sizes: torch.Tensor,
             sizes: torch.Tensor, minibatch_size: int, costs: torch.Tensor, blank_label: int = 0) -> None:
     """Same signature as the reference's ``_C.gpu_ctc`` (binding.cpp:86-117): probs/grads are
-    [T,N,V] (the reference's transposed layout, __init__.py:70), costs is a CPU tensor receiving
-    +loglike.  Our kernels work on [N,T,V] directly, so this mirror transposes at the edge."""
-    assert blank_label == 0 and probs.size(1) == minibatch_size
+    [T,N,V] (the reference's time-major layout, __init__.py:70), any blank_label in [0, V), costs is a
+    CPU tensor receiving +loglike.  The kernels read probs and write grads in that layout in place
+    (crf_ctc_fwd_bwd, time_major = 1): no transposed copies."""
+    assert probs.size(1) == minibatch_size
+    direct = (grads.shape == probs.shape and grads.dtype == torch.float32 and grads.is_contiguous() and grads.device == probs.device)
     # c_ctc = -1  ->  grad = +gamma_ctc, exactly what the reference's kernel writes (:431-435)
-    _, g, ex = loss_fwd_bwd(probs.transpose(0, 1).contiguous(), labels, sizes, label_sizes, 0.0, -1.0, None, True)
-    grads.copy_(g.transpose(0, 1))
+    _, g, ex = loss_fwd_bwd(probs.contiguous(), labels, sizes, label_sizes, 0.0, -1.0, None, True, time_major=True,
+                            blank=int(blank_label), grad_out=grads if direct else None)
+    if not direct:
+        grads.copy_(g)
     costs.copy_(ex["costs_ctc"].to(costs.device))
 
 

@@ -3,7 +3,7 @@ src/ctc_crf/ctc_crf/__init__.py), backed by the MI355X-native HIP library (cat_a
 
 Same names, arguments and error behaviour as the reference:
   CTC_CRF_LOSS(lamb=0.1, size_average=True)(logits, labels, lx, ly) -> FloatTensor[1]   (:97-125)
-  WARP_CTC_LOSS(size_average=True)(logits, labels, input_lengths, label_lengths)         (:128-144)
+  WARP_CTC_LOSS(size_average=True, blank_label=0)(logits, labels, input_lengths, label_lengths)   (:128-144; blank_label added)
   CRFContext(den_lm, gpus)                                                               (:147-171)
   _CTC_CRF, _WARP_CTC_GPU  autograd Functions                                             (:25-94)
 plus the functional form named by BASELINE.json:
@@ -30,14 +30,15 @@ def _assert_no_grad(tensor):
 
 
 class _WARP_CTC_GPU(Function):
-    """Plain CTC NLL (reference __init__.py:25-55): costs = -sum_b logp_b, grad = -gamma_ctc."""
+    """Plain CTC NLL (reference __init__.py:25-55): costs = -sum_b logp_b, grad = -gamma_ctc.
+    blank_label (not in the reference's Function; warp-ctc's ctcOptions::blank_label): the blank's column."""
 
     @staticmethod
-    def forward(ctx, logits, labels, input_lengths, label_lengths, size_average=True):
+    def forward(ctx, logits, labels, input_lengths, label_lengths, size_average=True, blank_label=0):
         logits = logits.contiguous()
         batch_size = logits.size(0)
         s = 1.0 / batch_size if size_average else 1.0
-        costs, grads, _ = core.loss_fwd_bwd(logits, labels, input_lengths, label_lengths, 0.0, s, None)
+        costs, grads, _ = core.loss_fwd_bwd(logits, labels, input_lengths, label_lengths, 0.0, s, None, blank=int(blank_label))
         ctx.grads = grads
         return costs
 
@@ -126,17 +127,20 @@ class CTC_CRF_LOSS(Module):
 class WARP_CTC_LOSS(Module):
     """Kept for parity with the reference (which itself recommends torch.nn.CTCLoss)."""
 
-    def __init__(self, size_average=True):
+    def __init__(self, size_average=True, blank_label=0):
+        """blank_label (not in the reference, which fixes 0; as torch.nn.CTCLoss(blank=...)): the blank's column of the log-probs;
+        labels then lie in [0, V) without it."""
         super(WARP_CTC_LOSS, self).__init__()
         self.ctc = _WARP_CTC_GPU.apply
         self.size_average = size_average
+        self.blank_label = blank_label
 
     def forward(self, logits, labels, input_lengths, label_lengths):
         assert len(labels.size()) == 1
         _assert_no_grad(labels)
         _assert_no_grad(input_lengths)
         _assert_no_grad(label_lengths)
-        return self.ctc(logits, labels, input_lengths, label_lengths, self.size_average)
+        return self.ctc(logits, labels, input_lengths, label_lengths, self.size_average, self.blank_label)
 
 
 class CRFContext:

@@ -2,12 +2,14 @@
  * include/ctc_crf_hip.h -- C ABI of libctc_crf_hip.so, the MI355X-native (gfx950) CTC-CRF loss.
  *
  * This is the drop-in boundary for the reference's native layer L0:
- * plain pointers and sizes, no torch types.  It deliberately does NOT keep the reference's C
- * symbols (binding.cpp:20-49: Init / Release / compute_alpha / compute_beta_and_grad, and
- * gpu_ctc/ctc.h:76-109: compute_ctc_loss / get_workspace_size) because those bake in the
- * per-frame-launch design (separate alpha and beta entry points, [32]-striped grad_storage,
- * host-resident labels with two stream syncs).  Each entry point below names the reference
- * interface it replaces.
+ * plain pointers and sizes, no torch types.  It deliberately does NOT keep the reference's
+ * denominator symbols (binding.cpp:20-49: Init / Release / compute_alpha / compute_beta_and_grad)
+ * because those bake in the per-frame-launch design (separate alpha and beta entry points,
+ * [32]-striped grad_storage).  Each entry point below names the reference interface it replaces.
+ * The numerator's warp-ctc C API (gpu_ctc/ctc.h:76-109: compute_ctc_loss, get_workspace_size,
+ * ctcGetStatusString) IS exported by this library as well, declared in include/ctc.h with the
+ * warp-ctc semantics (host-resident labels, host costs, one stream sync per call); it sits on
+ * crf_ctc_fwd_bwd below.
  *
  * Conventions
  *   - every pointer named *_dev is device memory on the graph's device; all work is enqueued on
@@ -16,7 +18,8 @@
  *     (the reference printf()s and exit(1)s, den_calculate.cu:16-25, or drops the status,
  *     binding.cpp:111).
  *   - log_probs: [B][T][V] float32, contiguous (the reference's `logits`, ctc_crf/__init__.py:61);
- *     labels: flattened int32 without padding, blank = 0; lx/ly: int32 [B].
+ *     labels: flattened int32 without padding, blank = 0; lx/ly: int32 [B].  (crf_ctc_fwd_bwd:
+ *     also time-major [T][B][V] and any blank.)
  */
 #ifndef CTC_CRF_HIP_H_
 #define CTC_CRF_HIP_H_
@@ -78,9 +81,10 @@ int crf_graph_dims(const crf_graph *g, int64_t *num_states, int64_t *num_arcs, i
  * only (no GPU needed) and can be used with crf_graph_dims / crf_graph_stats / crf_graph_destroy. */
 int crf_graph_stats(const crf_graph *g, int64_t *out, int n);
 
-/* Replaces get_workspace_size (ctc.h:99-109) and the torch::empty temporaries of gpu_den
- * (binding.cpp:77-79): bytes of device scratch crf_loss_fwd_bwd needs.  `g` may be NULL when
- * c_den == 0 (plain CTC).  `max_label_len` >= max(ly). */
+/* Replaces the torch::empty temporaries of gpu_den (binding.cpp:77-79): bytes of device scratch
+ * crf_loss_fwd_bwd / crf_ctc_fwd_bwd need (include/ctc.h's get_workspace_size adds the host
+ * metadata and outputs of compute_ctc_loss to this).  `g` may be NULL when c_den == 0 (plain CTC).
+ * `max_label_len` >= max(ly). */
 int64_t crf_workspace_bytes(const crf_graph *g, int64_t B, int64_t T, int64_t V, int64_t max_label_len);
 
 /* Which denominator kernels a call of this shape takes (no reference counterpart: the reference has one set of kernels,
@@ -142,6 +146,20 @@ int crf_loss_fwd_bwd(const crf_graph *g, const float *log_probs_dev, const int32
                      float *grad_dev, float *loss_dev, float *costs_den_dev, float *costs_beta_dev,
                      float *costs_ctc_dev, int32_t *invalid_dev, void *workspace_dev,
                      int64_t workspace_bytes, void *stream);
+
+/* Numerator only (plain CTC), with the two options of warp-ctc's ctcOptions / the reference's gpu_ctc (binding.cpp:86-117):
+ *   time_major = 0: act_dev and grad_dev are [B][T][V] (as crf_loss_fwd_bwd);
+ *   time_major = 1: they are [T][B][V], the layout gpu_ctc hands warp-ctc (ctc.h:49-62) -- no transposed copy is made;
+ *   blank: the blank's column, in [0, V); labels must lie in [0, V) and differ from it (not checked here: labels are device memory).
+ * Otherwise crf_loss_fwd_bwd with g = NULL, c_den = 0 and the same conventions (no host sync; workspace from
+ * crf_workspace_bytes(NULL, B, T, V, max_label_len)):
+ *   grad_dev[row (b, t)] = -c_ctc * gamma_ctc[b][t]  (0 for t >= lx[b]),  loss_dev[0] = -c_ctc * sum_b logp_ctc[b],
+ *   costs_ctc_dev[b] = logp_ctc[b] (may be NULL), invalid_dev[b] (may be NULL). */
+int crf_ctc_fwd_bwd(const float *act_dev, int time_major, int blank, const int32_t *labels_dev,
+                    const int32_t *label_off_dev, const int32_t *lx_dev, const int32_t *ly_dev,
+                    int64_t B, int64_t T, int64_t V, int64_t max_label_len, float c_ctc,
+                    float *grad_dev, float *loss_dev, float *costs_ctc_dev, int32_t *invalid_dev,
+                    void *workspace_dev, int64_t workspace_bytes, void *stream);
 
 /* Replaces the cudaMemcpyAsync calls that bring labels, label lengths and input lengths to the device
  * (gpu_ctc.h:143-229; `input_lengths.cuda()`, ctc_crf/__init__.py:73): copies n int32 from PINNED host
