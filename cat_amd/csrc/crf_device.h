@@ -13,6 +13,8 @@ namespace crf {
 constexpr int kEpRegs = 8;    // ep row prefetch registers per thread  -> V  <= 8 * 1024
 constexpr int kCtcThreads = 512, kCtcWaves = kCtcThreads / 64;  // numerator chains: 8 waves (S' = 2L+1 is a few hundred)
 constexpr int kCtcRegs = 8;   // ctc states per thread                  -> 2L+1 <= 8 * 512
+static_assert(kEpRegs * kChainThreads == kMaxVocab && 2 * kMaxCtcLabelLen + 1 <= kCtcRegs * kCtcThreads &&
+              2 * (kMaxCtcLabelLen + 1) + 1 > kCtcRegs * kCtcThreads, "the host's limits (crf_internal.h) follow the kernels' registers");
 constexpr int kCtcPF = 4;     // frames per emission prefetch batch (ctc_forward)
 constexpr int kGradThreads = 256;
 constexpr int kGradFrames = 4;  // frames per crf_grad_kernel workgroup
@@ -252,13 +254,19 @@ __device__ __forceinline__ int rescale_exp_d(double m) {
 }
 __device__ __forceinline__ double pow2d(int k) { return __longlong_as_double((long long)(k + 1023) << 52); }
 // exp(d) * 2^add for d <= 0 without intermediate underflow: d = k ln2 + r, result = exp(r) * 2^(k+add)
+// d = -inf (a -inf log-prob: a masked vocabulary entry) must give 0, not rint(-inf) - (-inf) = NaN: d is clamped where exp(d) is 0
+// in either precision anyway (NaN stays NaN).  tests/test_gpu_ctc_variants.py::test_masked_vocabulary found NaN emission factors here --
+// NaN gradient entries in the masked columns behind the numerator's log-domain fix (0 * NaN), and chains sent to the log domain.
+constexpr float kExpFloor = -1.0e4f;
 __device__ __forceinline__ float exp_scaled(float d, int add) {
+    d = d < kExpFloor ? kExpFloor : d;
     const float k = rintf(d * 1.4426950408889634f);
     float r = fmaf(-k, 0.693145751953125f, d);
     r = fmaf(-k, 1.428606765330187e-06f, r);
     return ldexpf(expf(r), (int)k + add);
 }
 __device__ __forceinline__ double exp_scaled_d(float d) {
+    d = d < kExpFloor ? kExpFloor : d;
     const float k = rintf(d * 1.4426950408889634f);
     float r = fmaf(-k, 0.693145751953125f, d);
     r = fmaf(-k, 1.428606765330187e-06f, r);

@@ -801,9 +801,9 @@ static int loss_impl(const crf_graph *g, const float *logp, int fused, int in_dt
         set_error("den_lm has label " + std::to_string(h->dev.max_label) + " but log_probs has only V=" + std::to_string(V) + " classes");
         return CRF_ERR_ARG;
     }
-    if (V > kEpRegs * kChainThreads) { set_error("V > 8192 not supported by this build"); return CRF_ERR_UNSUPPORTED; }
+    if (V > kMaxVocab) { set_error("V > " + std::to_string(kMaxVocab) + " not supported by this build"); return CRF_ERR_UNSUPPORTED; }
     const int Sc = rup64((int)(2 * (ctc ? max_label_len : 0) + 1));
-    if (ctc && 2 * max_label_len + 1 > kCtcRegs * kCtcThreads) { set_error("label length > 2047 not supported by this build"); return CRF_ERR_UNSUPPORTED; }
+    if (ctc && max_label_len > kMaxCtcLabelLen) { set_error("label length > " + std::to_string(kMaxCtcLabelLen) + " not supported by this build"); return CRF_ERR_UNSUPPORTED; }
     const WsLayout w = ws_layout(h, B, T, V, Sc);
     if (ws_bytes < w.total) { set_error("workspace too small: need " + std::to_string(w.total)); return CRF_ERR_WORKSPACE; }
     const bool res = den && w.res, gv = den && w.gv, fac = den && w.fac, bat = den && w.bat;

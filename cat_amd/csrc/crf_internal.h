@@ -12,6 +12,8 @@ namespace crf {
 constexpr int kWave = 64;          // gfx950 wavefront
 constexpr int kChainWaves = 16;    // waves per chain workgroup (1024 threads = one full CU)
 constexpr int kChainThreads = kChainWaves * kWave;
+constexpr int kMaxVocab = 8 * kChainThreads;      // largest V of a call: the emission rows' kEpRegs (crf_device.h) x kChainThreads
+constexpr int kMaxCtcLabelLen = 2047;             // longest label sequence of the numerator: 2L + 1 states <= kCtcRegs x kCtcThreads
 constexpr int kChunk = 32;         // pairs per grad-pass chunk
 constexpr int kScaleExp = 20;      // den per-frame rescale target: max entry in [2^20, 2^21)
 constexpr int kEpExp = 64;         // den emission factors are stored as exp(logp - rowmax) * 2^64, so

@@ -15,7 +15,22 @@
 
 namespace {
 
-constexpr int kMaxLabelLen = 2047;   // 2L + 1 states per utterance <= the chains' 8 x 512 (crf_device.h kCtcRegs x kCtcThreads)
+constexpr int kMaxLabelLen = crf::kMaxCtcLabelLen;   // 2L + 1 states per utterance <= the chains' 8 x 512 (crf_device.h kCtcRegs x kCtcThreads)
+constexpr int kMaxAlphabet = crf::kMaxVocab;        // the limit crf_ctc_fwd_bwd applies (loss_impl)
+
+// alphabet_size in [1, kMaxAlphabet] and minibatch > 0: checked first, before anything touches the device
+ctcStatus_t check_sizes(const char *fn, int alphabet_size, int minibatch) {
+    if (alphabet_size <= 0 || minibatch <= 0) {
+        crf::set_error(std::string(fn) + ": alphabet_size <= 0 or minibatch <= 0");
+        return CTC_STATUS_INVALID_VALUE;
+    }
+    if (alphabet_size > kMaxAlphabet) {
+        crf::set_error(std::string(fn) + ": alphabet_size " + std::to_string(alphabet_size) + " > " + std::to_string(kMaxAlphabet) +
+                       " not supported by this build");
+        return CTC_STATUS_INVALID_VALUE;
+    }
+    return CTC_STATUS_SUCCESS;
+}
 
 int64_t al256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
@@ -82,12 +97,14 @@ const char *ctcGetStatusString(ctcStatus_t status) {
 ctcStatus_t get_workspace_size(const int *const label_lengths, const int *const input_lengths, int alphabet_size, int minibatch,
                                struct ctcOptions info, size_t *size_bytes) {
     (void)info;
-    if (!label_lengths || !input_lengths || !size_bytes || alphabet_size <= 0 || minibatch <= 0) {
-        crf::set_error("get_workspace_size: null pointer, alphabet_size <= 0 or minibatch <= 0");
+    if (!label_lengths || !input_lengths || !size_bytes) {
+        crf::set_error("get_workspace_size: null pointer");
         return CTC_STATUS_INVALID_VALUE;
     }
+    ctcStatus_t st = check_sizes("get_workspace_size", alphabet_size, minibatch);
+    if (st != CTC_STATUS_SUCCESS) return st;
     Lengths s;
-    const ctcStatus_t st = scan_lengths(label_lengths, input_lengths, minibatch, &s);
+    st = scan_lengths(label_lengths, input_lengths, minibatch, &s);
     if (st != CTC_STATUS_SUCCESS) return st;
     *size_bytes = (size_t)layout(minibatch, alphabet_size, s).total;
     return CTC_STATUS_SUCCESS;
@@ -96,17 +113,19 @@ ctcStatus_t get_workspace_size(const int *const label_lengths, const int *const 
 ctcStatus_t compute_ctc_loss(const float *const activations, float *gradients, const int *const flat_labels, const int *const label_lengths,
                              const int *const input_lengths, int alphabet_size, int minibatch, float *costs, void *workspace,
                              struct ctcOptions options) {
-    if (!activations || !flat_labels || !label_lengths || !input_lengths || !costs || !workspace || alphabet_size <= 0 || minibatch <= 0) {
-        crf::set_error("compute_ctc_loss: null pointer, alphabet_size <= 0 or minibatch <= 0");
+    if (!activations || !flat_labels || !label_lengths || !input_lengths || !costs || !workspace) {
+        crf::set_error("compute_ctc_loss: null pointer");
         return CTC_STATUS_INVALID_VALUE;
     }
+    ctcStatus_t st = check_sizes("compute_ctc_loss", alphabet_size, minibatch);
+    if (st != CTC_STATUS_SUCCESS) return st;
     const int B = minibatch, V = alphabet_size, blank = options.blank_label;
     if (blank < 0 || blank >= V) {
         crf::set_error("compute_ctc_loss: blank_label " + std::to_string(blank) + " outside [0, alphabet_size=" + std::to_string(V) + ")");
         return CTC_STATUS_INVALID_VALUE;
     }
     Lengths s;
-    ctcStatus_t st = scan_lengths(label_lengths, input_lengths, B, &s);
+    st = scan_lengths(label_lengths, input_lengths, B, &s);
     if (st != CTC_STATUS_SUCCESS) return st;
     // metadata as crf_ctc_fwd_bwd reads it; labels in [0, V) and not the blank (the kernels index the activation rows with them)
     std::vector<int32_t> meta(3 * (size_t)B + std::max<int64_t>(s.totL, 1), 0);

@@ -480,9 +480,13 @@ __global__ __launch_bounds__(kCtcThreads) void crf_robust_ctc_kernel(LossParams 
             const double *Af = A + ((lx - 1) & 1) * Sxp;
             const double lz = lse3(Af[Sx - 1], Sx > 1 ? Af[Sx - 2] : -INFINITY, -INFINITY);
             const bool ok = lz > -INFINITY && lz < INFINITY;
+            // a valid label sequence of probability 0 (every alignment meets a -inf emission): cost -inf, as the fp64 oracle and torch's ctc_loss
+            // give it, not invalid; its gradient rows stay 0 (include/ctc.h; tests/test_gpu_ctc_variants.py::test_zero_probability_utterance
+            // found cost 0 and invalid = 1 here)
+            const bool zero_p = lz == -INFINITY;
             p.ctc_zc[b] = lz;                    // (from here on the LOG of the partition sum)
-            p.cost_ctc[b] = ok ? (float)lz : 0.f;
-            p.invalid[b] = ok ? 0 : 1;
+            p.cost_ctc[b] = ok ? (float)lz : zero_p ? -INFINITY : 0.f;
+            p.invalid[b] = (ok || zero_p) ? 0 : 1;
             p.ctc_logdom[b] = p.ctc_pass;        // (the backward workgroup of this pass may start later: it lets its own pass through)
         }
     } else {

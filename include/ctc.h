@@ -17,6 +17,10 @@
  *     rows t >= input_lengths[b] are zero.
  *   - an utterance without an alignment (label length + repeats > input length) gets cost 0 and zero
  *     gradient rows (warp-ctc leaves both untouched).
+ *   - an utterance whose every alignment meets a -inf activation (probability 0) gets cost -inf, the
+ *     exact log-probability, and zero gradient rows.
+ *   - alphabet_size <= 8192 and label lengths <= 2047; larger ones are refused with
+ *     CTC_STATUS_INVALID_VALUE, by get_workspace_size as by compute_ctc_loss.
  *   - workspace: device memory of get_workspace_size() bytes, for this call only.
  * Details of a failure: crf_last_error() (include/ctc_crf_hip.h).
  */

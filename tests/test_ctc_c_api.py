@@ -62,6 +62,9 @@ def test_workspace_size_rejects_bad_arguments(lib):
     assert _ws(lib, [2048, 2], [5000, 8], 72)[0] == INVALID_VALUE      # label length over the build's limit
     st, n = _ws(lib, [2047, 2], [5000, 8], 72)
     assert st == 0 and n > 0
+    assert _ws(lib, [3, 2], [10, 8], 8193)[0] == INVALID_VALUE         # alphabet over the build's limit (what compute_ctc_loss refuses)
+    st, n = _ws(lib, [3, 2], [10, 8], 8192)
+    assert st == 0 and n > 0
     size = ctypes.c_size_t(0)
     ll = (ctypes.c_int * 1)(1)
     assert lib.get_workspace_size(None, ll, 72, 1, Opt(None, 0), ctypes.byref(size)) == INVALID_VALUE
@@ -114,3 +117,23 @@ def test_options_struct_size_matches_ctypes(tmp_path):
     m.ctc_options_size.restype = m.ctc_options_blank_offset.restype = ctypes.c_size_t
     assert m.ctc_options_size() == ctypes.sizeof(Opt)
     assert m.ctc_options_blank_offset() == Opt.blank_label.offset
+
+
+def test_compute_ctc_loss_refuses_alphabet_over_the_limit_on_the_host(lib):
+    """alphabet_size > 8192 is refused before the first HIP call: the arguments here are HOST buffers, which a call that went on would
+    hand to hipMemcpyAsync / the kernels (no GPU needed -- the status and the message show which check answered)."""
+    import ctc_crf
+    ip = ctypes.POINTER(ctypes.c_int)
+    lib.compute_ctc_loss.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ip, ip, ip, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float),
+                                     ctypes.c_void_p, Opt]
+    lib.compute_ctc_loss.restype = ctypes.c_int
+    V, B, T = 8193, 2, 4
+    act = (ctypes.c_float * (T * B * V))()
+    grads = (ctypes.c_float * (T * B * V))()
+    labels, ll, il = (ctypes.c_int * 2)(1, 2), (ctypes.c_int * 2)(1, 1), (ctypes.c_int * 2)(T, T)
+    costs = (ctypes.c_float * B)(-7.0, -7.0)
+    ws = (ctypes.c_char * 4096)()
+    st = lib.compute_ctc_loss(ctypes.addressof(act), ctypes.addressof(grads), labels, ll, il, V, B, costs, ctypes.addressof(ws), Opt(None, 0))
+    assert st == INVALID_VALUE
+    assert "8192" in ctc_crf._C._lib.crf_last_error().decode()
+    assert list(costs) == [-7.0, -7.0]

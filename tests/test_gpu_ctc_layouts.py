@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import oracle
-from tests.util import crf_env, log_softmax_np, rel_err
+from tests.util import crf_env, ctc_batch as _batch, oracle_blank as _oracle_blank, rel_err
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -35,7 +35,7 @@ def _ref_lib_path():
 
 def _warp_ctc(so, logits, labels, lx, ly, blank, with_grad=True):
     """compute_ctc_loss of the library `so` (ctc.h:76-109) on logits [B,T,V] handed over time-major, with a NaN-poisoned workspace
-    -> (status, costs [B] (+log p), grads [B,T,V] or None)."""
+    (and, for this library, a NaN-filled gradient buffer) -> (status, costs [B] (+log p), grads [B,T,V] or None)."""
     lib = ctypes.CDLL(so)
     B, T, V = logits.shape
     ly_a, lx_a = np.ascontiguousarray(ly, dtype=np.int32), np.ascontiguousarray(lx, dtype=np.int32)
@@ -48,7 +48,10 @@ def _warp_ctc(so, logits, labels, lx, ly, blank, with_grad=True):
     assert lib.get_workspace_size(ip(ly_a), ip(lx_a), V, B, opt, ctypes.byref(size)) == 0
     T_ = int(lx_a.max())
     act = torch.tensor(logits[:, :T_], device="cuda:0").transpose(0, 1).contiguous()      # [maxT, B, V]
-    grads = torch.zeros_like(act) if with_grad else None
+    # this library promises zero rows t >= input_lengths[b] (ctc.h): its buffer starts as NaN so that the rows it skipped would show;
+    # the reference's kernel leaves those rows alone (its callers zero the buffer)
+    fill = 0.0 if os.path.realpath(so) == os.path.realpath(_ref_lib_path()) else float("nan")
+    grads = torch.full_like(act, fill) if with_grad else None
     ws = torch.full(((size.value + 3) // 4,), float("nan"), device="cuda:0")
     costs = np.full(B, np.nan, dtype=np.float32)
     lib.compute_ctc_loss.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
@@ -63,48 +66,6 @@ def _warp_ctc(so, logits, labels, lx, ly, blank, with_grad=True):
         g = np.zeros((B, T, V), dtype=np.float32)
         g[:, :T_] = grads.transpose(0, 1).cpu().numpy()
     return status, costs.astype(np.float64), g
-
-
-def _batch(seed, B, T, V, L, blank, repeats=False, empty=False, at_most_twice=False):
-    """Ragged batch: frames T, T - T/5, T/2, ...; labels in [0, V) without `blank` (so label 0 appears whenever blank != 0).
-    at_most_twice: no label more than twice in an utterance (as a single or as a repeated pair)."""
-    rng = np.random.default_rng(seed)
-    logits = log_softmax_np(rng.normal(0.0, 2.0, size=(B, T, V))).astype(np.float32)
-    lx = np.array([max(1, T - (T * b) // (B + 1)) for b in range(B)], dtype=np.int32)
-    ly = np.array([max(1, min(L - b, (int(lx[b]) - 1) // 2)) for b in range(B)], dtype=np.int32)
-    pool = np.array([v for v in range(V) if v != blank])
-    lab = []
-    for b in range(B):
-        n = int(ly[b])
-        if at_most_twice:
-            d = rng.permutation(pool)
-            x = []
-            for i, v in enumerate(d):
-                if len(x) >= n:
-                    break
-                x.append(v)
-                if len(x) < n and (n - len(x) > len(d) - i - 1 or rng.random() < 0.5):
-                    x.append(v)
-            assert len(x) == n
-            x = np.array(x)
-        elif repeats and b % 2 == 0:
-            x = np.repeat(pool[rng.integers(0, len(pool), size=(n + 2) // 3)], 3)[:n]
-        else:
-            x = pool[rng.integers(0, len(pool), size=n)]
-        lab.append(x)
-    if empty:
-        ly[B - 1] = 0
-        lab[B - 1] = lab[B - 1][:0]
-    return logits, np.concatenate(lab).astype(np.int32), lx, ly
-
-
-def _oracle_blank(logits, labels, lx, ly, blank):
-    """The fp64 oracle's blank-0 numerator on the columns blank <-> 0 swapped and the labels renamed likewise: (+gamma [B,T,V], +log p [B], valid)."""
-    perm = np.arange(logits.shape[2])
-    perm[0], perm[blank] = blank, 0
-    lab = np.where(labels == 0, blank, labels) if blank else labels
-    g, c, v = oracle.ctc(np.ascontiguousarray(logits[:, :, perm]), lab, lx, ly)
-    return g[:, :, perm], c, v
 
 
 def _blanks(V):

@@ -13,7 +13,7 @@ import oracle
 from oracle import fst_io
 from oracle.brute import brute_ctc, brute_den
 from cat_amd.den_lm import synth_den_lm, write_fst
-from tests.util import make_batch, small_synth
+from tests.util import ctc_batch, make_batch, oracle_blank, small_synth
 
 
 def test_fixture_bytes_match_reference_hash(golden_dir):
@@ -107,6 +107,30 @@ def test_oracle_ctc_vs_torch_cpu():
     mask = (np.arange(T)[None, :] < lx[:, None])[..., None]
     gamma_torch = (x.exp().numpy() * mask - xr.grad.numpy())  # torch returns softmax - gamma
     assert np.abs(gc - gamma_torch).max() < 2e-5
+
+
+@pytest.mark.parametrize("blank_at", ["first", "second", "middle", "last"])
+def test_blank_swapped_oracle_vs_torch_cpu(blank_at):
+    """The reference the GPU tests use for a blank k != 0 -- the oracle's blank-0 numerator on the columns k <-> 0 swapped, labels renamed
+    likewise (tests/util.py oracle_blank) -- against torch's fp64 CPU ctc_loss(blank=k): costs, and gamma recovered from torch's gradient
+    (d(-log p)/d logp = exp(logp) - gamma on frames t < T_b with zero_infinity off).  Repeats, an empty label sequence, L up to 300."""
+    V = 23
+    blank = {"first": 0, "second": 1, "middle": 11, "last": V - 1}[blank_at]
+    logits, labels, lx, ly = ctc_batch(17 + blank, 4, 700, V, 300, blank, repeats=True, empty=True)
+    ly[0] = 300                                          # (ctc_batch caps L - b at (lx - 1) / 2; the first utterance takes all 300)
+    assert int(ly.max()) == 300 and int(ly.min()) == 0
+    labels = np.concatenate([np.random.default_rng(blank).choice([v for v in range(V) if v != blank], size=300)]
+                            + np.split(labels, np.cumsum(ly)[:-1])[1:]).astype(np.int32)
+    g64, c64, valid = oracle_blank(logits, labels, lx, ly, blank)
+    assert valid.all()
+    x = torch.tensor(logits, dtype=torch.float64, requires_grad=True)
+    nll = torch.nn.functional.ctc_loss(x.transpose(0, 1), torch.tensor(labels, dtype=torch.long), torch.tensor(lx, dtype=torch.long),
+                                       torch.tensor(ly, dtype=torch.long), blank=blank, reduction="none")
+    nll.sum().backward()
+    np.testing.assert_allclose(c64, -nll.detach().numpy(), rtol=1e-9, atol=1e-9)
+    mask = (np.arange(logits.shape[1])[None, :] < lx[:, None])[..., None]
+    gamma = np.exp(logits.astype(np.float64)) * mask - x.grad.numpy()
+    assert np.abs(g64 - gamma).max() <= 1e-5, float(np.abs(g64 - gamma).max())   # (g64 is stored as float32)
 
 
 def test_oracle_invariants_and_ragged(tmp_path):

@@ -3,6 +3,8 @@ import os
 
 import numpy as np
 
+import oracle
+
 from cat_amd.den_lm import synth_den_lm, write_fst
 from cat_amd.synth import log_softmax_np, make_batch  # noqa: F401  (re-exported: the tests import them from here)
 
@@ -93,3 +95,45 @@ class crf_env:
 
     def __exit__(self, *a):
         return self._cm.__exit__(*a)
+
+
+def ctc_batch(seed, B, T, V, L, blank, repeats=False, empty=False, at_most_twice=False):
+    """Ragged batch: frames T, T - T/5, T/2, ...; labels in [0, V) without `blank` (so label 0 appears whenever blank != 0).
+    at_most_twice: no label more than twice in an utterance (as a single or as a repeated pair)."""
+    rng = np.random.default_rng(seed)
+    logits = log_softmax_np(rng.normal(0.0, 2.0, size=(B, T, V))).astype(np.float32)
+    lx = np.array([max(1, T - (T * b) // (B + 1)) for b in range(B)], dtype=np.int32)
+    ly = np.array([max(1, min(L - b, (int(lx[b]) - 1) // 2)) for b in range(B)], dtype=np.int32)
+    pool = np.array([v for v in range(V) if v != blank])
+    lab = []
+    for b in range(B):
+        n = int(ly[b])
+        if at_most_twice:
+            d = rng.permutation(pool)
+            x = []
+            for i, v in enumerate(d):
+                if len(x) >= n:
+                    break
+                x.append(v)
+                if len(x) < n and (n - len(x) > len(d) - i - 1 or rng.random() < 0.5):
+                    x.append(v)
+            assert len(x) == n
+            x = np.array(x)
+        elif repeats and b % 2 == 0:
+            x = np.repeat(pool[rng.integers(0, len(pool), size=(n + 2) // 3)], 3)[:n]
+        else:
+            x = pool[rng.integers(0, len(pool), size=n)]
+        lab.append(x)
+    if empty:
+        ly[B - 1] = 0
+        lab[B - 1] = lab[B - 1][:0]
+    return logits, np.concatenate(lab).astype(np.int32), lx, ly
+
+
+def oracle_blank(logits, labels, lx, ly, blank):
+    """The fp64 oracle's blank-0 numerator on the columns blank <-> 0 swapped and the labels renamed likewise: (+gamma [B,T,V], +log p [B], valid)."""
+    perm = np.arange(logits.shape[2])
+    perm[0], perm[blank] = blank, 0
+    lab = np.where(labels == 0, blank, labels) if blank else labels
+    g, c, v = oracle.ctc(np.ascontiguousarray(logits[:, :, perm]), lab, lx, ly)
+    return g[:, :, perm], c, v
