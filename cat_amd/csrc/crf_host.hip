@@ -433,6 +433,31 @@ static int launch_ctc_pair(const LossParams &p, size_t lds, hipStream_t st, int6
     return CRF_OK;
 }
 
+// forced alignment (k_align.hip): one workgroup per utterance, states per thread from the longest label sequence as for the chains
+template <int NR>
+static int launch_align_nr(const AlignParams &p, hipStream_t st) {
+    hipLaunchKernelGGL((crf_ctc_align_kernel<NR>), dim3((unsigned)p.B), dim3(kCtcThreads), 0, st, p);
+    hipError_t e;
+    if ((e = hipGetLastError()) != hipSuccess) { set_error(std::string("crf_ctc_align_kernel: ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
+    return CRF_OK;
+}
+static int launch_align(const AlignParams &p, hipStream_t st, int64_t max_label_len) {
+    const int64_t ni = (2 * max_label_len + 1 + kCtcThreads - 1) / kCtcThreads;
+    if (ni <= 1) return launch_align_nr<1>(p, st);
+    if (ni <= 2) return launch_align_nr<2>(p, st);
+    if (ni <= 4) return launch_align_nr<4>(p, st);
+    return launch_align_nr<kCtcRegs>(p, st);
+}
+// its workspace: the back-pointer words [B][ceil(T / kAlnFrames)][2 * max_label_len + 1 rounded up to 64]; < 0 with the message set
+static int64_t align_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t max_label_len) {
+    if (B <= 0 || T <= 0 || V <= 0 || max_label_len < 0) { set_error("crf_ctc_align: bad B/T/V/max_label_len"); return -CRF_ERR_ARG; }
+    if (V > kMaxVocab) { set_error("V > " + std::to_string(kMaxVocab) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
+    if (max_label_len > kMaxCtcLabelLen) { set_error("label length > " + std::to_string(kMaxCtcLabelLen) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
+    if (B * T > INT32_MAX) { set_error("crf_ctc_align: B * T > INT32_MAX"); return -CRF_ERR_ARG; }
+    const int64_t Sc = rup64((int)(2 * max_label_len + 1)), NB = (T + kAlnFrames - 1) / kAlnFrames;
+    return al(B * NB * Sc * (int64_t)sizeof(unsigned));
+}
+
 static ResParams res_params(const LossParams &lp, int dir, int b0) {
     const ResDev &R = lp.g.res;
     ResParams p{};
@@ -775,6 +800,28 @@ int crf_ctc_fwd_bwd(const float *act, int time_major, int blank, const int32_t *
     if (c_ctc == 0.f) { set_error("crf_ctc_fwd_bwd: c_ctc is zero"); return CRF_ERR_ARG; }
     return loss_impl(nullptr, act, 0, 0, labels, lab_off, lx, ly, B, T, V, max_label_len, 0.f, c_ctc, grad, loss, nullptr, nullptr,
                      costs_ctc, invalid, ws, ws_bytes, stream_, time_major, blank);
+}
+
+int64_t crf_ctc_align_workspace_bytes(int64_t B, int64_t T, int64_t V, int64_t max_label_len) {
+    const int64_t n = align_ws_bytes(B, T, V, max_label_len);
+    return n < 0 ? -1 : n;
+}
+
+int crf_ctc_align(const float *act, int time_major, int blank, const int32_t *labels, const int32_t *lab_off, const int32_t *lx,
+                  const int32_t *ly, int64_t B, int64_t T, int64_t V, int64_t max_label_len, int32_t *pos, float *score,
+                  int32_t *invalid, void *ws, int64_t ws_bytes, void *stream_) {
+    if (!act || !labels || !lab_off || !lx || !ly || !pos || !score || !ws) { set_error("crf_ctc_align: null argument"); return CRF_ERR_ARG; }
+    const int64_t need = align_ws_bytes(B, T, V, max_label_len);
+    if (need < 0) return (int)-need;
+    if (blank < 0 || blank >= V) { set_error("blank " + std::to_string(blank) + " outside [0, V=" + std::to_string(V) + ")"); return CRF_ERR_ARG; }
+    if (ws_bytes < need) { set_error("workspace too small: need " + std::to_string(need)); return CRF_ERR_WORKSPACE; }
+    AlignParams p{};
+    p.x = act; p.labels = labels; p.lab_off = lab_off; p.lx = lx; p.ly = ly;
+    p.B = (int)B; p.T = (int)T; p.V = (int)V; p.blank = blank;
+    p.Sc = rup64((int)(2 * max_label_len + 1)); p.NB = (int)((T + kAlnFrames - 1) / kAlnFrames);
+    p.xs_b = time_major ? V : T * V; p.xs_t = time_major ? B * V : V;
+    p.bp = (unsigned *)ws; p.pos = pos; p.score = score; p.invalid = invalid;
+    return launch_align(p, (hipStream_t)stream_, max_label_len);
 }
 
 static int loss_impl(const crf_graph *g, const float *logp, int fused, int in_dtype, const int32_t *labels, const int32_t *lab_off,

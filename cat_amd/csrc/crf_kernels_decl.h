@@ -14,6 +14,23 @@ template <bool GV> __global__ void crf_den_pair_kernel(LossParams p);
 template <int NR> __global__ void crf_ctc_pair_kernel(LossParams p);
 __global__ void crf_ctc_check_kernel(LossParams p);
 
+// ---- k_align.hip ----
+constexpr int kAlnFrames = 16;   // frames per back-pointer word (2 bits per frame and state)
+constexpr int kAlnG = 4;         // blocks of kAlnFrames frames per back-trace tile: kAlnG x (2 kAlnFrames kAlnG) words, one per thread
+// Kernel arguments of the forced alignment (crf_ctc_align): the activations are read in place, row (b, t) at b * xs_b + t * xs_t floats
+struct AlignParams {
+    const float *x;
+    const int *labels, *lab_off, *lx, *ly;
+    int B, T, V, blank;
+    int Sc, NB;                 // back-pointer words: [B][NB = ceil(T / kAlnFrames)][Sc = 2 * max_label_len + 1 rounded up to 64]
+    int64_t xs_b, xs_t;
+    unsigned *bp;
+    int *pos;                   // [B][T]
+    float *score;               // [B]
+    int *invalid;               // [B] or null
+};
+template <int NR> __global__ void crf_ctc_align_kernel(AlignParams p);
+
 // ---- k_res.hip ----
 constexpr int kEpRegsR = 2;   // emission-row prefetch registers (V <= 2*512 for the resident kernels)
 constexpr int kPoll = 4;      // granules polled concurrently per thread

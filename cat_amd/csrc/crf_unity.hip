@@ -8,4 +8,5 @@
 #include "k_grad.hip"
 #include "k_batch.hip"
 #include "k_robust.hip"
+#include "k_align.hip"
 #include "crf_host.hip"

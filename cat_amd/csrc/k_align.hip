@@ -1,0 +1,195 @@
+// cat_amd/csrc/k_align.hip -- CTC forced alignment: the best path through the numerator's 2L+1 states (the max-plus twin of the forward
+// chain in k_chain.hip), with back-pointers and the back-trace in the same launch.  Host side: crf_ctc_align (crf_host.hip).
+//
+//   v_t[s] = x[b][t][lab(s)] + max(v_{t-1}[s], v_{t-1}[s-1], v_{t-1}[s-2] if s is odd and lab(s) != lab(s-2))      log domain, fp32
+//
+// One workgroup of kCtcThreads per utterance, state s = tid + i * kCtcThreads in register set i < NR (the chains' geometry).  Ties go to the
+// smallest move (stay, advance, skip; at the end state 2L before 2L-1): the comparisons below are strict, in that order.
+// Frame 0 is an ordinary frame on the virtual vector v_{-1} = (0, -inf, -inf, ...): x + 0 is exact, and it yields v_0[0] = x[blank],
+// v_0[1] = x[lab(1)], -inf elsewhere.  States s >= 2L+1 of the last register set run along on the blank's column: values only move UP the
+// state axis, so nothing they hold reaches a real state, and they are never stored.
+//
+// Back-pointers: 2 bits per (frame, state), the move taken into the state.  A thread keeps the moves of 16 consecutive frames of its state
+// in one register and stores the word once per 16 frames:  bp[b][t / 16][s], bits 2 (t % 16) ..  -- coalesced along s, and every word of
+// the blocks [0, ceil(lx / 16)) x [0, 2L+1) is written before the back-trace starts (the workspace may hold anything).
+// Back-trace: the state falls by at most 2 per frame, so the words of the next kAlnG blocks (64 frames) for the 32 kAlnG states below the
+// current one are ONE word per thread: the workgroup fetches that tile into LDS in one pass (one dependent global round trip per 64 frames
+// instead of one per frame), and wave 0 walks it -- per block of 16 frames 32 lanes take their state's word from LDS, the walk itself is
+// v_readlane + scalar arithmetic, and the 16 positions of the block leave as one store of 16 lanes.
+#include "crf_device.h"
+#include "crf_kernels_decl.h"
+
+namespace crf {
+
+template <int NR>
+__global__ __launch_bounds__(kCtcThreads) void crf_ctc_align_kernel(AlignParams p) {
+    constexpr int S = NR * kCtcThreads;       // states this instantiation holds
+    constexpr int PF = NR == 1 ? 8 : 4;      // frames per emission prefetch batch (two register sets in flight)
+    static_assert((2 * PF) <= kAlnFrames && kAlnFrames % (2 * PF) == 0, "a back-pointer word is closed at the end of a loop iteration");
+    static_assert(kAlnG * 2 * kAlnFrames * kAlnG == kCtcThreads, "the back-trace tile is one word per thread");
+    __shared__ float A[2][S + 2];             // v of the previous / this frame, two -inf entries in front of state 0
+    __shared__ int lab[S];
+    __shared__ unsigned tile[kCtcThreads];
+    __shared__ int red[kCtcWaves];
+    __shared__ int ctl[2];                    // [0] the back-trace's current state, [1] 1 = a path exists
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = blockIdx.x;
+    const int lx = min(p.lx[b], p.T), L = p.ly[b];
+    const bool fits = L >= 0 && 2 * L + 1 <= S;
+    const int Sx = fits ? 2 * L + 1 : 1;
+    int *prow = p.pos + (int64_t)b * p.T;
+
+    // the label sequence with blanks; repeats and labels outside [0, V) counted in one reduction
+    {
+        const int *ul = p.labels + p.lab_off[b];
+        int cnt = 0;                          // repeats | out-of-range labels << 12  (each <= 2047)
+        for (int s = tid; s < S; s += kCtcThreads) lab[s] = (s < Sx && (s & 1)) ? ul[s >> 1] : p.blank;
+        for (int i = tid; i < (fits ? L : 0); i += kCtcThreads) {
+            const int l = ul[i];
+            if ((unsigned)l >= (unsigned)p.V) cnt += 1 << 12;
+            else if (i > 0 && l == ul[i - 1]) cnt += 1;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+        if (lane == 0) red[wave] = cnt;
+        if (tid < 2) { A[0][tid] = -INFINITY; A[1][tid] = -INFINITY; }
+    }
+    __syncthreads();
+    int cnt = 0;
+#pragma unroll
+    for (int i = 0; i < kCtcWaves; ++i) cnt += red[i];
+    const bool valid = fits && lx > 0 && (cnt >> 12) == 0 && L + (cnt & 0xfff) <= lx;   // (gpu_ctc.h:161-174: L + repeats <= T_b)
+    for (int t = tid; t < p.T; t += kCtcThreads)
+        if (!valid || t >= lx) prow[t] = -2;
+    if (!valid) {
+        if (tid == 0) { p.score[b] = -INFINITY; if (p.invalid) p.invalid[b] = 1; }
+        return;
+    }
+
+    unsigned labo[NR];                        // the state's column as a byte offset into a row
+    bool skip[NR];
+    unsigned bpw[NR];
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        const int s = tid + i * kCtcThreads;
+        const int l = lab[s];
+        // a label outside [0, V) has ended the utterance above; the states past Sx hold the blank
+        labo[i] = (unsigned)l * 4u;
+        skip[i] = s < Sx && (s & 1) && s >= 2 && l != lab[s - 2];
+        bpw[i] = 0u;
+        A[0][2 + s] = s == 0 ? 0.f : -INFINITY;
+    }
+    __syncthreads();
+
+    const float *xb = p.x + (int64_t)b * p.xs_b;
+    unsigned *bpb = p.bp + (int64_t)b * p.NB * p.Sc;
+    // Emissions: unconditional loads (the frame is clamped to lx - 1, the column is always a valid one), so that nothing but the
+    // loop itself branches around them and the compiler can count what is in flight instead of waiting for everything.
+    auto fetch = [&](float (&e)[PF][NR], int t) __attribute__((always_inline)) {
+#pragma unroll
+        for (int f = 0; f < PF; ++f) {
+            const char *row = (const char *)(xb + (int64_t)min(t + f, lx - 1) * p.xs_t);
+#pragma unroll
+            for (int i = 0; i < NR; ++i) e[f][i] = *(const float *)(row + labo[i]);
+        }
+    };
+    // One frame; a frame at or past lx copies the vector (the loop runs in whole batches).
+    auto frame = [&](const float (&e)[NR], int t) __attribute__((always_inline)) {
+        const float *Ac = &A[t & 1][2];
+        float *An = &A[(t + 1) & 1][2];
+        const bool live = t < lx;
+        const int sh = 2 * (t & (kAlnFrames - 1));
+        float a0[NR], a1[NR], a2[NR];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            const int s = tid + i * kCtcThreads;
+            a0[i] = Ac[s]; a1[i] = Ac[s - 1]; a2[i] = Ac[s - 2];
+        }
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            const int s = tid + i * kCtcThreads;
+            const float c2 = skip[i] ? a2[i] : -INFINITY;
+            float best = a0[i];
+            unsigned mv = 0u;
+            if (a1[i] > best) { best = a1[i]; mv = 1u; }
+            if (c2 > best) { best = c2; mv = 2u; }
+            An[s] = live ? e[i] + best : a0[i];
+            bpw[i] |= mv << sh;
+        }
+        sync_lds();
+    };
+
+    float ea[PF][NR], eb[PF][NR];
+    fetch(ea, 0);
+    int t0 = 0;
+    for (; t0 < lx; t0 += 2 * PF) {
+        fetch(eb, t0 + PF);
+#pragma unroll
+        for (int f = 0; f < PF; ++f) frame(ea[f], t0 + f);
+        fetch(ea, t0 + 2 * PF);
+#pragma unroll
+        for (int f = 0; f < PF; ++f) frame(eb[f], t0 + PF + f);
+        if (((t0 + 2 * PF) & (kAlnFrames - 1)) == 0 || t0 + 2 * PF >= lx) {    // the block of 16 frames is complete, or the utterance is
+            unsigned *w = bpb + (int64_t)(t0 / kAlnFrames) * p.Sc;
+#pragma unroll
+            for (int i = 0; i < NR; ++i) {
+                const int s = tid + i * kCtcThreads;
+                if (s < Sx) w[s] = bpw[i];
+                bpw[i] = 0u;
+            }
+        }
+    }
+    __syncthreads();                          // the back-pointer words are in memory, the last vector in LDS
+    if (tid == 0) {
+        const float *Af = &A[t0 & 1][2];      // t0 frames have run
+        float best = Af[Sx - 1];
+        int s = Sx - 1;
+        if (Sx > 1 && Af[Sx - 2] > best) { best = Af[Sx - 2]; s = Sx - 2; }
+        const bool alive = best > -INFINITY;  // (false for NaN as well)
+        ctl[0] = s; ctl[1] = alive ? 1 : 0;
+        p.score[b] = alive ? best : -INFINITY;
+        if (p.invalid) p.invalid[b] = 0;
+    }
+    __syncthreads();
+    if (!ctl[1]) {                            // a valid label sequence, no alignment of non-zero probability
+        for (int t = tid; t < lx; t += kCtcThreads) prow[t] = -2;
+        return;
+    }
+
+    constexpr int kTileStates = 2 * kAlnFrames * kAlnG;   // 128 states below the current one
+    for (int blk = (lx - 1) / kAlnFrames; blk >= 0; blk -= kAlnG) {
+        const int s_top = __builtin_amdgcn_readfirstlane(ctl[0]);
+        {
+            const int bj = blk - tid / kTileStates, st = s_top - (tid & (kTileStates - 1));
+            tile[tid] = (bj >= 0 && st >= 0) ? bpb[(int64_t)bj * p.Sc + st] : 0u;
+        }
+        __syncthreads();
+        if (wave == 0) {
+            int cur = s_top;
+            for (int j = 0; j < kAlnG && blk - j >= 0; ++j) {
+                const int bj = blk - j, tb = bj * kAlnFrames;
+                const int c0 = cur;           // s_top - c0 <= 32 j: lanes 0 .. 31 hold the words of the states c0, c0 - 1, ...
+                const int w = lane < 2 * kAlnFrames ? (int)tile[j * kTileStates + (s_top - c0) + lane] : 0;
+                int val = -2;
+                for (int t = min(lx - 1, tb + kAlnFrames - 1); t >= tb; --t) {
+                    const int k = t & (kAlnFrames - 1);
+                    val = lane == k ? ((cur & 1) ? (cur >> 1) : -1) : val;
+                    const unsigned word = (unsigned)__builtin_amdgcn_readlane(w, c0 - cur);   // c0 - cur <= 30 inside a block
+                    cur -= (int)((word >> (2 * k)) & 3u);
+                }
+                if (lane < kAlnFrames && tb + lane < lx) prow[tb + lane] = val;
+            }
+            if (lane == 0) ctl[0] = cur;
+        }
+        __syncthreads();
+    }
+}
+
+template __global__ void crf_ctc_align_kernel<1>(AlignParams);
+template __global__ void crf_ctc_align_kernel<2>(AlignParams);
+template __global__ void crf_ctc_align_kernel<4>(AlignParams);
+template __global__ void crf_ctc_align_kernel<kCtcRegs>(AlignParams);
+
+}  // namespace crf

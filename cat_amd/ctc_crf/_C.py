@@ -48,6 +48,10 @@ _lib.crf_loss_fwd_bwd_logits.restype = ctypes.c_int
 _lib.crf_ctc_fwd_bwd.argtypes = [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32,
                                  _vp, _vp, _vp, _vp, _vp, _i64, _vp]
 _lib.crf_ctc_fwd_bwd.restype = ctypes.c_int
+_lib.crf_ctc_align_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64]
+_lib.crf_ctc_align_workspace_bytes.restype = _i64
+_lib.crf_ctc_align.argtypes = [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]
+_lib.crf_ctc_align.restype = ctypes.c_int
 _lib.crf_profile_enable.argtypes = [ctypes.c_int]
 _lib.crf_profile_enable.restype = None
 _lib.crf_profile_read.argtypes = [ctypes.POINTER(_f32), ctypes.c_int]
@@ -72,7 +76,7 @@ _lib.crf_build_switches.restype = ctypes.c_char_p
 
 EXPORTED_SYMBOLS = (
     "crf_graph_create", "crf_graph_create_from_arcs", "crf_graph_destroy", "crf_graph_dims", "crf_graph_stats",
-    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
+    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
     "crf_debug_set", "crf_debug_unset", "crf_debug_list", "crf_last_den_kernel", "crf_last_call_streams", "crf_last_side_stream", "crf_last_fallback_counts", "crf_build_switches", "crf_last_error", "crf_version",
 )
 
@@ -501,6 +505,62 @@ def loss_fwd_bwd(logits: torch.Tensor, labels: Optional[torch.Tensor], lx: torch
     del meta
     extras = dict(costs_alpha=c_alpha, costs_beta=c_beta, costs_ctc=c_ctc_t, invalid=invalid) if want_costs else {}
     return loss, grad, extras
+
+
+def ctc_align(log_probs: torch.Tensor, labels: torch.Tensor, lx: torch.Tensor, ly: torch.Tensor, blank: int = 0,
+              time_major: bool = False, pos_out: Optional[torch.Tensor] = None, scores_out: Optional[torch.Tensor] = None):
+    """Forced alignment (include/ctc_crf_hip.h ``crf_ctc_align``): the best path of every transcript through its 2L+1 states.
+
+    log_probs [N,T,V] (time_major: [T,N,V]) f32 on the GPU, contiguous, read in place; labels / lx / ly int tensors on the CPU,
+    labels flattened as for WARP_CTC_LOSS.  Returns (pos [N,T] int32, tokens [N,T] int32, scores [N] f32, invalid [N] int32), all on
+    the device, no host synchronisation: pos = transcript index per frame, -1 for a blank frame, -2 past lx; tokens = the class emitted
+    per frame (the blank's index where pos == -1, -1 where pos == -2), ONE gather of pos into a per-utterance table that travels with
+    the staged metadata.  pos_out / scores_out: contiguous int32 [N,T] / f32 [N] device tensors that receive the results (else allocated)."""
+    assert log_probs.is_cuda and log_probs.is_contiguous() and log_probs.dim() == 3 and log_probs.dtype == torch.float32
+    dev = log_probs.device
+    N, T, V = log_probs.shape
+    if time_major:
+        T, N = N, T
+    if not 0 <= blank < V:
+        raise RuntimeError(f"blank must lie in [0, V-1={V - 1}], got {blank}")
+    if labels.is_cuda or lx.is_cuda or ly.is_cuda:
+        raise RuntimeError("ctc_align: labels, input_lengths and label_lengths are CPU tensors")
+    lx32 = lx.to(torch.int32).reshape(-1)
+    ly32 = ly.to(torch.int32).reshape(-1)
+    lab32 = labels.to(torch.int32).reshape(-1)
+    if lx32.numel() != N or ly32.numel() != N:
+        raise RuntimeError(f"ctc_align: expect {N} input lengths and label lengths, got {lx32.numel()} and {ly32.numel()}")
+    _validate_meta(lx32, ly32, lab32, T, V, blank)
+    max_l = int(ly32.max()) if N > 0 else 0
+    nlab = int(ly32.sum())
+    off = (torch.cumsum(ly32, 0, dtype=torch.int32) - ly32).to(torch.int32)
+    # tokens = table[n][pos + 2]: column 0 for pos = -2, column 1 the blank, then the transcript
+    table = torch.full((N, max_l + 2), -1, dtype=torch.int32)
+    table[:, 1] = blank
+    table[:, 2:][torch.arange(max_l)[None, :] < ly32[:, None]] = lab32[:nlab]
+    lab_pad = lab32[:nlab] if nlab else torch.zeros(1, dtype=torch.int32)
+    meta = _h2d_async(torch.cat([lx32, ly32, off, table.reshape(-1), lab_pad]), dev)
+    nt = N * (max_l + 2)
+    lx_d, ly_d, off_d, table_d, lab_d = meta[:N], meta[N:2 * N], meta[2 * N:3 * N], meta[3 * N:3 * N + nt], meta[3 * N + nt:]
+    ws_bytes = _lib.crf_ctc_align_workspace_bytes(N, T, V, max_l)
+    if ws_bytes < 0:
+        _check(1)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    if _POISON_WS:
+        ws.fill_(0xFF)
+    pos = torch.empty((N, T), dtype=torch.int32, device=dev) if pos_out is None else pos_out
+    scores = torch.empty(N, dtype=torch.float32, device=dev) if scores_out is None else scores_out
+    assert pos.shape == (N, T) and pos.dtype == torch.int32 and pos.is_contiguous() and pos.device == dev
+    assert scores.shape == (N,) and scores.dtype == torch.float32 and scores.is_contiguous() and scores.device == dev
+    invalid = torch.empty(N, dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        rc = _lib.crf_ctc_align(_ptr(log_probs), 1 if time_major else 0, blank, _ptr(lab_d), _ptr(off_d), _ptr(lx_d), _ptr(ly_d),
+                                N, T, V, max_l, _ptr(pos), _ptr(scores), _ptr(invalid), _ptr(ws), ws_bytes, _vp(stream))
+    _check(rc)
+    tokens = torch.gather(table_d.view(N, max_l + 2), 1, (pos + 2).long())
+    del meta
+    return pos, tokens, scores, invalid
 
 
 def gpu_den(logits: torch.Tensor, grad_net: torch.Tensor, input_lengths: torch.Tensor,

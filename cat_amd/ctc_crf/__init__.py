@@ -6,6 +6,7 @@ Same names, arguments and error behaviour as the reference:
   WARP_CTC_LOSS(size_average=True, blank_label=0)(logits, labels, input_lengths, label_lengths)   (:128-144; blank_label added)
   CRFContext(den_lm, gpus)                                                               (:147-171)
   _CTC_CRF, _WARP_CTC_GPU  autograd Functions                                             (:25-94)
+  ctc_align(log_probs, labels, input_lengths, label_lengths, blank=0, time_major=False) -> (pos, tokens, scores)   (forced alignment; not in the reference)
 plus the functional form named by BASELINE.json:
   ctc_crf_loss(log_probs, labels, frame_lens, label_lens, den_lm, lamb=0.1, size_average=True)
 
@@ -177,6 +178,29 @@ class CRFContext:
             except Exception:  # interpreter shutdown
                 pass
             del self._handles
+
+
+def ctc_align(log_probs: torch.Tensor, labels: torch.Tensor, input_lengths: torch.Tensor, label_lengths: torch.Tensor,
+              blank: int = 0, time_major: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Forced alignment (not in the reference): the single best CTC alignment of every transcript, on the GPU.
+
+    log_probs (torch.FloatTensor): (N, T, V) log-probs on the GPU, or (T, N, V) with time_major=True; read in place.
+    labels, input_lengths, label_lengths (torch.IntTensor): on the CPU, labels flattened without padding as for WARP_CTC_LOSS.
+    blank (int): the blank's column; labels lie in [0, V) without it (in [1, V) for blank = 0).
+
+    Returns (pos, tokens, scores), all on log_probs' device, without a host synchronisation and without autograd:
+      pos    IntTensor[N, T]: the index k in [0, label_lengths[n]) of the transcript position emitted at frame t, -1 for a blank
+             frame, -2 for t >= input_lengths[n];
+      tokens IntTensor[N, T]: the class emitted at frame t -- labels[k], the blank's index where pos == -1, -1 where pos == -2;
+      scores FloatTensor[N] : the log-probability of the path (-inf, and a row of -2: no alignment exists -- the transcript does
+             not fit into input_lengths[n] frames, or every alignment has probability 0).
+    Among alignments of equal score the one that stays longest in each state wins (stay, then advance, then skip a blank)."""
+    assert len(labels.size()) == 1
+    assert log_probs.dtype == torch.float, f"expect log_probs to be torch.float object, instead: {log_probs.dtype}"
+    with torch.no_grad():
+        pos, tokens, scores, _ = core.ctc_align(log_probs.detach().contiguous(), labels, input_lengths, label_lengths, int(blank),
+                                                bool(time_major))
+    return pos, tokens, scores
 
 
 _CTX_CACHE: Dict[Tuple[str, int], CRFContext] = {}

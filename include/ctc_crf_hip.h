@@ -161,6 +161,27 @@ int crf_ctc_fwd_bwd(const float *act_dev, int time_major, int blank, const int32
                     float *grad_dev, float *loss_dev, float *costs_ctc_dev, int32_t *invalid_dev,
                     void *workspace_dev, int64_t workspace_bytes, void *stream);
 
+/* Forced alignment: the single best alignment of each transcript through the numerator's 2L+1 states (no reference counterpart:
+ * the reference returns the sum over alignments only).  Conventions of crf_ctc_fwd_bwd: no host sync, all work on `stream`, act_dev
+ * read in place as [B][T][V] (time_major = 0) or [T][B][V] (1), any blank in [0, V), labels_dev / label_off_dev / lx_dev / ly_dev as
+ * there.  Log domain, fp32:  v_t[s] = act[b][t][lab(s)] + max(v_{t-1}[s], v_{t-1}[s-1], v_{t-1}[s-2] if s odd and lab(s) != lab(s-2)).
+ * Ties go to the smallest move -- stay, then advance by one, then skip; at the end state 2L before 2L-1 -- so the result is
+ * reproducible bit for bit.
+ *   pos_dev[b][t]   always [B][T]: the index k in [0, ly[b]) of the transcript position emitted at frame t < lx[b], -1 for a blank
+ *                   frame, -2 for t >= lx[b];
+ *   score_dev[b]    the log-probability of that path (the fp32 sum of its entries in frame order);
+ *   invalid_dev[b]  (may be NULL) 1 for an utterance with L + repeats > lx, lx <= 0 or a label outside [0, V): score -inf, row -2.
+ * A valid utterance whose every alignment has probability 0: score -inf, row -2, invalid 0.  ly = 0 is valid (all frames -1).
+ * Workspace: crf_ctc_align_workspace_bytes (2 bits per frame and state; its contents on entry do not matter); -1 with
+ * crf_last_error() set for a shape this build does not take.  CRF_ERR_ARG: null pointer, blank outside [0, V), B * T > INT32_MAX;
+ * CRF_ERR_UNSUPPORTED: V > 8192, max_label_len > 2047; CRF_ERR_WORKSPACE: workspace too small -- all answered before any HIP call. */
+int64_t crf_ctc_align_workspace_bytes(int64_t B, int64_t T, int64_t V, int64_t max_label_len);
+int crf_ctc_align(const float *act_dev, int time_major, int blank, const int32_t *labels_dev,
+                  const int32_t *label_off_dev, const int32_t *lx_dev, const int32_t *ly_dev,
+                  int64_t B, int64_t T, int64_t V, int64_t max_label_len,
+                  int32_t *pos_dev, float *score_dev, int32_t *invalid_dev,
+                  void *workspace_dev, int64_t workspace_bytes, void *stream);
+
 /* Replaces the cudaMemcpyAsync calls that bring labels, label lengths and input lengths to the device
  * (gpu_ctc.h:143-229; `input_lengths.cuda()`, ctc_crf/__init__.py:73): copies n int32 from PINNED host
  * memory (hipHostMalloc / torch pin_memory: device-accessible) to device memory with a kernel on `stream` --
