@@ -434,19 +434,30 @@ static int launch_ctc_pair(const LossParams &p, size_t lds, hipStream_t st, int6
 }
 
 // forced alignment (k_align.hip): one workgroup per utterance, states per thread from the longest label sequence as for the chains
-template <int NR>
+template <int NR, typename E, bool LSE>
 static int launch_align_nr(const AlignParams &p, hipStream_t st) {
-    hipLaunchKernelGGL((crf_ctc_align_kernel<NR>), dim3((unsigned)p.B), dim3(kCtcThreads), 0, st, p);
+    hipLaunchKernelGGL((crf_ctc_align_kernel<NR, E, LSE>), dim3((unsigned)p.B), dim3(kCtcThreads), 0, st, p);
     hipError_t e;
     if ((e = hipGetLastError()) != hipSuccess) { set_error(std::string("crf_ctc_align_kernel: ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
     return CRF_OK;
 }
+template <typename E = float, bool LSE = false>
 static int launch_align(const AlignParams &p, hipStream_t st, int64_t max_label_len) {
     const int64_t ni = (2 * max_label_len + 1 + kCtcThreads - 1) / kCtcThreads;
-    if (ni <= 1) return launch_align_nr<1>(p, st);
-    if (ni <= 2) return launch_align_nr<2>(p, st);
-    if (ni <= 4) return launch_align_nr<4>(p, st);
-    return launch_align_nr<kCtcRegs>(p, st);
+    if (ni <= 1) return launch_align_nr<1, E, LSE>(p, st);
+    if (ni <= 2) return launch_align_nr<2, E, LSE>(p, st);
+    if (ni <= 4) return launch_align_nr<4, E, LSE>(p, st);
+    return launch_align_nr<kCtcRegs, E, LSE>(p, st);
+}
+// raw network output: the frames' lse values first (G lanes per frame), then the alignment on the upcast values, on the same stream
+template <typename E>
+static int launch_align_logits(const AlignParams &p, hipStream_t st, int64_t max_label_len) {
+    const int64_t frames = (int64_t)p.B * p.T;
+    if (p.V <= kAlnLseSmallV) hipLaunchKernelGGL((crf_align_lse_kernel<16, E>), dim3((unsigned)((frames + 15) / 16)), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((crf_align_lse_kernel<64, E>), dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, st, p);
+    hipError_t e;
+    if ((e = hipGetLastError()) != hipSuccess) { set_error(std::string("crf_align_lse_kernel: ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
+    return launch_align<E, true>(p, st, max_label_len);
 }
 // its workspace: the back-pointer words [B][ceil(T / kAlnFrames)][2 * max_label_len + 1 rounded up to 64]; < 0 with the message set
 static int64_t align_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t max_label_len) {
@@ -802,26 +813,68 @@ int crf_ctc_fwd_bwd(const float *act, int time_major, int blank, const int32_t *
                      costs_ctc, invalid, ws, ws_bytes, stream_, time_major, blank);
 }
 
+int crf_ctc_fwd_bwd_logits(const void *act, int dtype, int time_major, int blank, const int32_t *labels, const int32_t *lab_off,
+                           const int32_t *lx, const int32_t *ly, int64_t B, int64_t T, int64_t V, int64_t max_label_len, float c_ctc,
+                           float *grad, float *loss, float *costs_ctc, int32_t *invalid, void *ws, int64_t ws_bytes, void *stream_) {
+    if (dtype < 0 || dtype > 2) { set_error("crf_ctc_fwd_bwd_logits: dtype must be 0 (f32), 1 (bf16) or 2 (f16)"); return CRF_ERR_ARG; }
+    if (c_ctc == 0.f) { set_error("crf_ctc_fwd_bwd_logits: c_ctc is zero"); return CRF_ERR_ARG; }
+    return loss_impl(nullptr, (const float *)act, 1, dtype, labels, lab_off, lx, ly, B, T, V, max_label_len, 0.f, c_ctc, grad, loss, nullptr,
+                     nullptr, costs_ctc, invalid, ws, ws_bytes, stream_, time_major, blank);
+}
+
 int64_t crf_ctc_align_workspace_bytes(int64_t B, int64_t T, int64_t V, int64_t max_label_len) {
     const int64_t n = align_ws_bytes(B, T, V, max_label_len);
     return n < 0 ? -1 : n;
 }
 
-int crf_ctc_align(const float *act, int time_major, int blank, const int32_t *labels, const int32_t *lab_off, const int32_t *lx,
-                  const int32_t *ly, int64_t B, int64_t T, int64_t V, int64_t max_label_len, int32_t *pos, float *score,
-                  int32_t *invalid, void *ws, int64_t ws_bytes, void *stream_) {
-    if (!act || !labels || !lab_off || !lx || !ly || !pos || !score || !ws) { set_error("crf_ctc_align: null argument"); return CRF_ERR_ARG; }
-    const int64_t need = align_ws_bytes(B, T, V, max_label_len);
-    if (need < 0) return (int)-need;
+// the checks and the argument block both entry points share; dtype < 0: log-probs (crf_ctc_align), else raw output of that dtype with
+// the lse values [B][T] behind the back-pointer words.  Every error is answered here, before any HIP call.
+static int align_args(const char *who, const void *act, int dtype, int time_major, int blank, const int32_t *labels, const int32_t *lab_off,
+                      const int32_t *lx, const int32_t *ly, int64_t B, int64_t T, int64_t V, int64_t max_label_len, int32_t *pos,
+                      float *score, int32_t *invalid, void *ws, int64_t ws_bytes, AlignParams &p) {
+    if (!act || !labels || !lab_off || !lx || !ly || !pos || !score || !ws) { set_error(std::string(who) + ": null argument"); return CRF_ERR_ARG; }
+    if (dtype > 2) { set_error(std::string(who) + ": dtype must be 0 (f32), 1 (bf16) or 2 (f16)"); return CRF_ERR_ARG; }
+    const int64_t bpb = align_ws_bytes(B, T, V, max_label_len);
+    if (bpb < 0) return (int)-bpb;
+    const int64_t need = bpb + (dtype >= 0 ? al(B * T * (int64_t)sizeof(float)) : 0);
     if (blank < 0 || blank >= V) { set_error("blank " + std::to_string(blank) + " outside [0, V=" + std::to_string(V) + ")"); return CRF_ERR_ARG; }
     if (ws_bytes < need) { set_error("workspace too small: need " + std::to_string(need)); return CRF_ERR_WORKSPACE; }
-    AlignParams p{};
+    p = AlignParams{};
     p.x = act; p.labels = labels; p.lab_off = lab_off; p.lx = lx; p.ly = ly;
     p.B = (int)B; p.T = (int)T; p.V = (int)V; p.blank = blank;
     p.Sc = rup64((int)(2 * max_label_len + 1)); p.NB = (int)((T + kAlnFrames - 1) / kAlnFrames);
     p.xs_b = time_major ? V : T * V; p.xs_t = time_major ? B * V : V;
     p.bp = (unsigned *)ws; p.pos = pos; p.score = score; p.invalid = invalid;
+    p.lse = dtype >= 0 ? (float *)((char *)ws + bpb) : nullptr;
+    return CRF_OK;
+}
+
+int crf_ctc_align(const float *act, int time_major, int blank, const int32_t *labels, const int32_t *lab_off, const int32_t *lx,
+                  const int32_t *ly, int64_t B, int64_t T, int64_t V, int64_t max_label_len, int32_t *pos, float *score,
+                  int32_t *invalid, void *ws, int64_t ws_bytes, void *stream_) {
+    AlignParams p;
+    const int rc = align_args("crf_ctc_align", act, -1, time_major, blank, labels, lab_off, lx, ly, B, T, V, max_label_len, pos, score, invalid,
+                              ws, ws_bytes, p);
+    if (rc) return rc;
     return launch_align(p, (hipStream_t)stream_, max_label_len);
+}
+
+int64_t crf_ctc_align_logits_workspace_bytes(int64_t B, int64_t T, int64_t V, int64_t max_label_len) {
+    const int64_t n = align_ws_bytes(B, T, V, max_label_len);
+    return n < 0 ? -1 : n + al(B * T * (int64_t)sizeof(float));
+}
+
+int crf_ctc_align_logits(const void *act, int dtype, int time_major, int blank, const int32_t *labels, const int32_t *lab_off,
+                         const int32_t *lx, const int32_t *ly, int64_t B, int64_t T, int64_t V, int64_t max_label_len, int32_t *pos,
+                         float *score, int32_t *invalid, void *ws, int64_t ws_bytes, void *stream_) {
+    if (dtype < 0) { set_error("crf_ctc_align_logits: dtype must be 0 (f32), 1 (bf16) or 2 (f16)"); return CRF_ERR_ARG; }
+    AlignParams p;
+    const int rc = align_args("crf_ctc_align_logits", act, dtype, time_major, blank, labels, lab_off, lx, ly, B, T, V, max_label_len, pos,
+                              score, invalid, ws, ws_bytes, p);
+    if (rc) return rc;
+    if (dtype == 0) return launch_align_logits<float>(p, (hipStream_t)stream_, max_label_len);
+    if (dtype == 1) return launch_align_logits<AlnBf16>(p, (hipStream_t)stream_, max_label_len);
+    return launch_align_logits<AlnF16>(p, (hipStream_t)stream_, max_label_len);
 }
 
 static int loss_impl(const crf_graph *g, const float *logp, int fused, int in_dtype, const int32_t *labels, const int32_t *lab_off,
@@ -837,12 +890,10 @@ static int loss_impl(const crf_graph *g, const float *logp, int fused, int in_dt
     if (den && (!g || !g->h)) { set_error("denominator requested without a graph"); return CRF_ERR_ARG; }
     if (ctc && (!labels || !lab_off || !ly || max_label_len < 0)) { set_error("numerator requested without labels"); return CRF_ERR_ARG; }
     // The blank's column and the row layout are options of the numerator alone: a den_lm fixes the blank at 0 (label = ilabel - 1),
-    // and the denominator and fused-logits kernels read [B][T][V] rows.  (Labels are device memory here: the callers check them.)
+    // and the denominator kernels read [B][T][V] rows.  (Labels are device memory here: the callers check them.)
     if (blank < 0 || blank >= V) { set_error("blank " + std::to_string(blank) + " outside [0, V=" + std::to_string(V) + ")"); return CRF_ERR_ARG; }
     if (den && blank != 0) { set_error("a blank other than 0 is for numerator-only calls: a den_lm fixes the blank at 0"); return CRF_ERR_UNSUPPORTED; }
-    if (time_major && (den || fused)) {
-        set_error("time-major activations are for numerator-only calls on log-probs (no den_lm, no fused log_softmax)"); return CRF_ERR_UNSUPPORTED;
-    }
+    if (time_major && den) { set_error("time-major activations are for numerator-only calls (no den_lm)"); return CRF_ERR_UNSUPPORTED; }
     const HostGraph *h = den ? g->h : nullptr;
     if (den && V <= h->dev.max_label) {
         set_error("den_lm has label " + std::to_string(h->dev.max_label) + " but log_probs has only V=" + std::to_string(V) + " classes");

@@ -17,9 +17,12 @@ __global__ void crf_ctc_check_kernel(LossParams p);
 // ---- k_align.hip ----
 constexpr int kAlnFrames = 16;   // frames per back-pointer word (2 bits per frame and state)
 constexpr int kAlnG = 4;         // blocks of kAlnFrames frames per back-trace tile: kAlnG x (2 kAlnFrames kAlnG) words, one per thread
-// Kernel arguments of the forced alignment (crf_ctc_align): the activations are read in place, row (b, t) at b * xs_b + t * xs_t floats
+// Kernel arguments of the forced alignment (crf_ctc_align, crf_ctc_align_logits): the activations are read in place, row (b, t) at
+// b * xs_b + t * xs_t ELEMENTS (floats; with raw network output in 16 bits, AlnBf16 / AlnF16)
+struct AlnBf16 { unsigned short u; };   // element types of the kernel template: two bytes, upcast in registers (a shift / a convert)
+struct AlnF16 { _Float16 h; };
 struct AlignParams {
-    const float *x;
+    const void *x;
     const int *labels, *lab_off, *lx, *ly;
     int B, T, V, blank;
     int Sc, NB;                 // back-pointer words: [B][NB = ceil(T / kAlnFrames)][Sc = 2 * max_label_len + 1 rounded up to 64]
@@ -28,8 +31,13 @@ struct AlignParams {
     int *pos;                   // [B][T]
     float *score;               // [B]
     int *invalid;               // [B] or null
+    float *lse;                 // [B][T] crf_ctc_align_logits: log sum_v exp(x[b][t][v]) of the frames t < lx[b] (crf_align_lse_kernel)
 };
-template <int NR> __global__ void crf_ctc_align_kernel(AlignParams p);
+// E: float, AlnBf16, AlnF16.  LSE: the score is normalised, raw best sum - sum_t lse[b][t] in fp64 (raw network output).
+template <int NR, typename E = float, bool LSE = false> __global__ void crf_ctc_align_kernel(AlignParams p);
+// lanes per frame of the lse kernel: 16 for rows of up to 256 entries (four frames per wave), else a whole wave
+constexpr int kAlnLseSmallV = 256;
+template <int G, typename E> __global__ void crf_align_lse_kernel(AlignParams p);
 
 // ---- k_res.hip ----
 constexpr int kEpRegsR = 2;   // emission-row prefetch registers (V <= 2*512 for the resident kernels)

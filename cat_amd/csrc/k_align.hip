@@ -16,12 +16,63 @@
 // current one are ONE word per thread: the workgroup fetches that tile into LDS in one pass (one dependent global round trip per 64 frames
 // instead of one per frame), and wave 0 walks it -- per block of 16 frames 32 lanes take their state's word from LDS, the walk itself is
 // v_readlane + scalar arithmetic, and the 16 positions of the block leave as one store of 16 lanes.
+//
+// Raw network output (crf_ctc_align_logits): the kernel is instantiated on the element type E -- float, or 2-byte bf16 / fp16 elements
+// upcast in registers -- and runs the SAME recursion on the upcast values: every alignment takes one entry of each of its lx frames, so
+// log_softmax's normaliser sum_t lse_t is common to all of them and the best path is the same.  crf_align_lse_kernel writes lse[b][t]
+// in front of it; with LSE the workgroup sums its utterance's lse values in fp64 in a fixed order at the end (no atomics: the order is
+// part of the contract) and the score is float(double(raw best sum) - that sum).
 #include "crf_device.h"
 #include "crf_kernels_decl.h"
 
 namespace crf {
 
-template <int NR>
+// one element, upcast: a row of 16-bit elements starts on a 2-byte boundary only (odd V), so these are 2-byte loads
+template <typename E> __device__ __forceinline__ float aln_ld(const char *a);
+template <> __device__ __forceinline__ float aln_ld<float>(const char *a) { return *(const float *)a; }
+template <> __device__ __forceinline__ float aln_ld<AlnBf16>(const char *a) { return __uint_as_float((unsigned)*(const unsigned short *)a << 16); }
+template <> __device__ __forceinline__ float aln_ld<AlnF16>(const char *a) { return (float)*(const _Float16 *)a; }
+
+// lse[b][t] = m + log sum_v exp(x[b][t][v] - m), m = max_v x[b][t][v], fp32, for the frames t < lx[b] (the others are never written, and
+// never read).  G lanes per frame: a lane adds its entries v = sub, sub + G, ... in that order, the lanes' sums meet in a butterfly -- the
+// same arithmetic in either layout.  expf / logf, not the fast intrinsics: this kernel is memory-bound and not on the chain.
+template <int G, typename E>
+__global__ __launch_bounds__(256) void crf_align_lse_kernel(AlignParams p) {
+    const int sub = threadIdx.x & (G - 1);
+    const int64_t f = (int64_t)blockIdx.x * (256 / G) + (threadIdx.x / G);
+    if (f >= (int64_t)p.B * p.T) return;
+    const int b = (int)(f / p.T), t = (int)(f % p.T);
+    if (t >= p.lx[b]) return;                     // (whole groups of G lanes leave together)
+    const E *row = (const E *)p.x + ((int64_t)b * p.xs_b + (int64_t)t * p.xs_t);
+    float m = -INFINITY, s = 0.f;
+    constexpr int NX = 16;                        // row entries a lane keeps between the two passes
+    if (p.V <= NX * G) {
+        float x[NX];
+#pragma unroll
+        for (int k = 0; k < NX; ++k) {
+            const int v = sub + k * G;
+            x[k] = v < p.V ? aln_ld<E>((const char *)(row + v)) : -INFINITY;
+            m = fmaxf(m, x[k]);
+        }
+#pragma unroll
+        for (int o = G / 2; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, G));
+        if (m == -INFINITY) m = 0.f;
+#pragma unroll
+        for (int k = 0; k < NX; ++k)
+            if (sub + k * G < p.V) s += expf(x[k] - m);
+    } else {
+        for (int v = sub; v < p.V; v += G) m = fmaxf(m, aln_ld<E>((const char *)(row + v)));
+#pragma unroll
+        for (int o = G / 2; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, G));
+        if (m == -INFINITY) m = 0.f;
+        for (int v = sub; v < p.V; v += G) s += expf(aln_ld<E>((const char *)(row + v)) - m);
+    }
+#pragma unroll
+    for (int o = G / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, G);
+    if (sub == 0) p.lse[f] = m + logf(s);
+}
+
+template <int NR, typename E, bool LSE>
 __global__ __launch_bounds__(kCtcThreads) void crf_ctc_align_kernel(AlignParams p) {
     constexpr int S = NR * kCtcThreads;       // states this instantiation holds
     constexpr int PF = NR == 1 ? 8 : 4;      // frames per emission prefetch batch (two register sets in flight)
@@ -76,14 +127,14 @@ __global__ __launch_bounds__(kCtcThreads) void crf_ctc_align_kernel(AlignParams 
         const int s = tid + i * kCtcThreads;
         const int l = lab[s];
         // a label outside [0, V) has ended the utterance above; the states past Sx hold the blank
-        labo[i] = (unsigned)l * 4u;
+        labo[i] = (unsigned)l * (unsigned)sizeof(E);
         skip[i] = s < Sx && (s & 1) && s >= 2 && l != lab[s - 2];
         bpw[i] = 0u;
         A[0][2 + s] = s == 0 ? 0.f : -INFINITY;
     }
     __syncthreads();
 
-    const float *xb = p.x + (int64_t)b * p.xs_b;
+    const E *xb = (const E *)p.x + (int64_t)b * p.xs_b;
     unsigned *bpb = p.bp + (int64_t)b * p.NB * p.Sc;
     // Emissions: unconditional loads (the frame is clamped to lx - 1, the column is always a valid one), so that nothing but the
     // loop itself branches around them and the compiler can count what is in flight instead of waiting for everything.
@@ -92,7 +143,7 @@ __global__ __launch_bounds__(kCtcThreads) void crf_ctc_align_kernel(AlignParams 
         for (int f = 0; f < PF; ++f) {
             const char *row = (const char *)(xb + (int64_t)min(t + f, lx - 1) * p.xs_t);
 #pragma unroll
-            for (int i = 0; i < NR; ++i) e[f][i] = *(const float *)(row + labo[i]);
+            for (int i = 0; i < NR; ++i) e[f][i] = aln_ld<E>(row + labo[i]);
         }
     };
     // One frame; a frame at or past lx copies the vector (the loop runs in whole batches).
@@ -142,6 +193,7 @@ __global__ __launch_bounds__(kCtcThreads) void crf_ctc_align_kernel(AlignParams 
         }
     }
     __syncthreads();                          // the back-pointer words are in memory, the last vector in LDS
+    [[maybe_unused]] float raw = 0.f;         // (thread 0: the best sum of raw entries)
     if (tid == 0) {
         const float *Af = &A[t0 & 1][2];      // t0 frames have run
         float best = Af[Sx - 1];
@@ -151,11 +203,30 @@ __global__ __launch_bounds__(kCtcThreads) void crf_ctc_align_kernel(AlignParams 
         ctl[0] = s; ctl[1] = alive ? 1 : 0;
         p.score[b] = alive ? best : -INFINITY;
         if (p.invalid) p.invalid[b] = 0;
+        raw = best;
     }
     __syncthreads();
     if (!ctl[1]) {                            // a valid label sequence, no alignment of non-zero probability
         for (int t = tid; t < lx; t += kCtcThreads) prow[t] = -2;
         return;
+    }
+    if constexpr (LSE) {
+        // score = raw best sum - sum_{t < lx} lse_t in fp64, in a fixed order: a thread's frames t = tid, tid + 512, ..., the wave's
+        // butterfly, the eight wave sums in order.  Frames at or past lx are never read.
+        __shared__ double lred[kCtcWaves];
+        const float *lr = p.lse + (int64_t)b * p.T;
+        double part = 0.0;
+        for (int t = tid; t < lx; t += kCtcThreads) part += (double)lr[t];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
+        if (lane == 0) lred[wave] = part;
+        __syncthreads();
+        if (tid == 0) {
+            double sum = 0.0;
+#pragma unroll
+            for (int i = 0; i < kCtcWaves; ++i) sum += lred[i];
+            p.score[b] = (float)((double)raw - sum);
+        }
     }
 
     constexpr int kTileStates = 2 * kAlnFrames * kAlnG;   // 128 states below the current one
@@ -187,9 +258,22 @@ __global__ __launch_bounds__(kCtcThreads) void crf_ctc_align_kernel(AlignParams 
     }
 }
 
-template __global__ void crf_ctc_align_kernel<1>(AlignParams);
-template __global__ void crf_ctc_align_kernel<2>(AlignParams);
-template __global__ void crf_ctc_align_kernel<4>(AlignParams);
-template __global__ void crf_ctc_align_kernel<kCtcRegs>(AlignParams);
+#define CRF_ALN_INST(E, LSE)                                                    \
+    template __global__ void crf_ctc_align_kernel<1, E, LSE>(AlignParams);        \
+    template __global__ void crf_ctc_align_kernel<2, E, LSE>(AlignParams);        \
+    template __global__ void crf_ctc_align_kernel<4, E, LSE>(AlignParams);        \
+    template __global__ void crf_ctc_align_kernel<kCtcRegs, E, LSE>(AlignParams);
+CRF_ALN_INST(float, false)      // crf_ctc_align: log-probs
+CRF_ALN_INST(float, true)       // crf_ctc_align_logits
+CRF_ALN_INST(AlnBf16, true)
+CRF_ALN_INST(AlnF16, true)
+#undef CRF_ALN_INST
+#define CRF_LSE_INST(E)                                                      \
+    template __global__ void crf_align_lse_kernel<16, E>(AlignParams);       \
+    template __global__ void crf_align_lse_kernel<64, E>(AlignParams);
+CRF_LSE_INST(float)
+CRF_LSE_INST(AlnBf16)
+CRF_LSE_INST(AlnF16)
+#undef CRF_LSE_INST
 
 }  // namespace crf

@@ -48,6 +48,14 @@ _lib.crf_loss_fwd_bwd_logits.restype = ctypes.c_int
 _lib.crf_ctc_fwd_bwd.argtypes = [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32,
                                  _vp, _vp, _vp, _vp, _vp, _i64, _vp]
 _lib.crf_ctc_fwd_bwd.restype = ctypes.c_int
+_lib.crf_ctc_fwd_bwd_logits.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32,
+                                        _vp, _vp, _vp, _vp, _vp, _i64, _vp]
+_lib.crf_ctc_fwd_bwd_logits.restype = ctypes.c_int
+_lib.crf_ctc_align_logits_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64]
+_lib.crf_ctc_align_logits_workspace_bytes.restype = _i64
+_lib.crf_ctc_align_logits.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp,
+                                      _vp, _i64, _vp]
+_lib.crf_ctc_align_logits.restype = ctypes.c_int
 _lib.crf_ctc_align_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64]
 _lib.crf_ctc_align_workspace_bytes.restype = _i64
 _lib.crf_ctc_align.argtypes = [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]
@@ -76,7 +84,7 @@ _lib.crf_build_switches.restype = ctypes.c_char_p
 
 EXPORTED_SYMBOLS = (
     "crf_graph_create", "crf_graph_create_from_arcs", "crf_graph_destroy", "crf_graph_dims", "crf_graph_stats",
-    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
+    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
     "crf_debug_set", "crf_debug_unset", "crf_debug_list", "crf_last_den_kernel", "crf_last_call_streams", "crf_last_side_stream", "crf_last_fallback_counts", "crf_build_switches", "crf_last_error", "crf_version",
 )
 
@@ -431,12 +439,12 @@ def loss_fwd_bwd(logits: torch.Tensor, labels: Optional[torch.Tensor], lx: torch
 
     logits [N,T,V] f32 on the GPU, contiguous; labels/lx/ly int32 on CPU (as CAT passes them,
     cat/ctc/train.py:176-190) or on the GPU.  Returns (loss[1], grad[N,T,V], extras dict).
-    Numerator-only calls (c_den == 0, not fused; ``crf_ctc_fwd_bwd``) also take time_major=True -- logits and the
-    returned gradient are [T,N,V] -- and any blank column in [0, V); grad_out: a contiguous f32 tensor of logits'
+    Numerator-only calls (c_den == 0; ``crf_ctc_fwd_bwd``, fused: ``crf_ctc_fwd_bwd_logits``) also take time_major=True -- logits and
+    the returned gradient are [T,N,V] -- and any blank column in [0, V); grad_out: a contiguous f32 tensor of logits'
     shape that receives the gradient (else one is allocated).
     """
     assert logits.is_cuda and logits.is_contiguous() and logits.dim() == 3
-    if (time_major or blank != 0) and (c_den != 0.0 or fused):
+    if (time_major or blank != 0) and c_den != 0.0:
         raise RuntimeError("time_major and a blank other than 0 are for numerator-only calls (WARP_CTC_LOSS / gpu_ctc): "
                            "the den_lm fixes the blank at 0 and the CTC-CRF kernels read [N,T,V] log-probs")
     if fused:   # raw network output, log_softmax fused in (crf_loss_fwd_bwd_logits)
@@ -487,7 +495,11 @@ def loss_fwd_bwd(logits: torch.Tensor, labels: Optional[torch.Tensor], lx: torch
     loss, c_alpha, c_beta, c_ctc_t = out[:1], out[1:1 + N], out[1 + N:1 + 2 * N], out[1 + 2 * N:]
     stream = torch.cuda.current_stream(dev).cuda_stream
     with torch.cuda.device(dev):
-        if fused:
+        if fused and c_den == 0.0:   # plain CTC on raw network output, either layout, any blank
+            rc = _lib.crf_ctc_fwd_bwd_logits(_ptr(logits), _FUSED_DTYPES[logits.dtype], 1 if time_major else 0, blank, _ptr(lab_d), _ptr(off_d),
+                                             _ptr(lx_d), _ptr(ly_d), N, T, V, max_l, c_ctc, _ptr(grad), _ptr(loss), _ptr(c_ctc_t),
+                                             _ptr(invalid), _ptr(ws), ws_bytes, _vp(stream))
+        elif fused:
             rc = _lib.crf_loss_fwd_bwd_logits(gh, _ptr(logits), _FUSED_DTYPES[logits.dtype], _ptr(lab_d), _ptr(off_d), _ptr(lx_d),
                                               _ptr(ly_d), N, T, V, max_l, c_den, c_ctc, _ptr(grad), _ptr(loss), _ptr(c_alpha),
                                               _ptr(c_beta), _ptr(c_ctc_t), _ptr(invalid), _ptr(ws), ws_bytes, _vp(stream))
@@ -508,15 +520,23 @@ def loss_fwd_bwd(logits: torch.Tensor, labels: Optional[torch.Tensor], lx: torch
 
 
 def ctc_align(log_probs: torch.Tensor, labels: torch.Tensor, lx: torch.Tensor, ly: torch.Tensor, blank: int = 0,
-              time_major: bool = False, pos_out: Optional[torch.Tensor] = None, scores_out: Optional[torch.Tensor] = None):
+              time_major: bool = False, pos_out: Optional[torch.Tensor] = None, scores_out: Optional[torch.Tensor] = None,
+              fused: bool = False):
     """Forced alignment (include/ctc_crf_hip.h ``crf_ctc_align``): the best path of every transcript through its 2L+1 states.
 
     log_probs [N,T,V] (time_major: [T,N,V]) f32 on the GPU, contiguous, read in place; labels / lx / ly int tensors on the CPU,
     labels flattened as for WARP_CTC_LOSS.  Returns (pos [N,T] int32, tokens [N,T] int32, scores [N] f32, invalid [N] int32), all on
     the device, no host synchronisation: pos = transcript index per frame, -1 for a blank frame, -2 past lx; tokens = the class emitted
     per frame (the blank's index where pos == -1, -1 where pos == -2), ONE gather of pos into a per-utterance table that travels with
-    the staged metadata.  pos_out / scores_out: contiguous int32 [N,T] / f32 [N] device tensors that receive the results (else allocated)."""
-    assert log_probs.is_cuda and log_probs.is_contiguous() and log_probs.dim() == 3 and log_probs.dtype == torch.float32
+    the staged metadata.  pos_out / scores_out: contiguous int32 [N,T] / f32 [N] device tensors that receive the results (else allocated).
+    fused: log_probs is the RAW network output in f32 / bf16 / f16 (``crf_ctc_align_logits``): the path is the best one on the upcast
+    values, the scores are those of log_softmax (the frames' normalisers subtracted in fp64)."""
+    assert log_probs.is_cuda and log_probs.is_contiguous() and log_probs.dim() == 3
+    if fused:
+        if log_probs.dtype not in _FUSED_DTYPES:
+            raise RuntimeError(f"fused log_softmax: expect float32, bfloat16 or float16 network output, got {log_probs.dtype}")
+    else:
+        assert log_probs.dtype == torch.float32
     dev = log_probs.device
     N, T, V = log_probs.shape
     if time_major:
@@ -542,7 +562,7 @@ def ctc_align(log_probs: torch.Tensor, labels: torch.Tensor, lx: torch.Tensor, l
     meta = _h2d_async(torch.cat([lx32, ly32, off, table.reshape(-1), lab_pad]), dev)
     nt = N * (max_l + 2)
     lx_d, ly_d, off_d, table_d, lab_d = meta[:N], meta[N:2 * N], meta[2 * N:3 * N], meta[3 * N:3 * N + nt], meta[3 * N + nt:]
-    ws_bytes = _lib.crf_ctc_align_workspace_bytes(N, T, V, max_l)
+    ws_bytes = (_lib.crf_ctc_align_logits_workspace_bytes if fused else _lib.crf_ctc_align_workspace_bytes)(N, T, V, max_l)
     if ws_bytes < 0:
         _check(1)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
@@ -555,8 +575,13 @@ def ctc_align(log_probs: torch.Tensor, labels: torch.Tensor, lx: torch.Tensor, l
     invalid = torch.empty(N, dtype=torch.int32, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
     with torch.cuda.device(dev):
-        rc = _lib.crf_ctc_align(_ptr(log_probs), 1 if time_major else 0, blank, _ptr(lab_d), _ptr(off_d), _ptr(lx_d), _ptr(ly_d),
-                                N, T, V, max_l, _ptr(pos), _ptr(scores), _ptr(invalid), _ptr(ws), ws_bytes, _vp(stream))
+        if fused:
+            rc = _lib.crf_ctc_align_logits(_ptr(log_probs), _FUSED_DTYPES[log_probs.dtype], 1 if time_major else 0, blank, _ptr(lab_d),
+                                           _ptr(off_d), _ptr(lx_d), _ptr(ly_d), N, T, V, max_l, _ptr(pos), _ptr(scores), _ptr(invalid),
+                                           _ptr(ws), ws_bytes, _vp(stream))
+        else:
+            rc = _lib.crf_ctc_align(_ptr(log_probs), 1 if time_major else 0, blank, _ptr(lab_d), _ptr(off_d), _ptr(lx_d), _ptr(ly_d),
+                                    N, T, V, max_l, _ptr(pos), _ptr(scores), _ptr(invalid), _ptr(ws), ws_bytes, _vp(stream))
     _check(rc)
     tokens = torch.gather(table_d.view(N, max_l + 2), 1, (pos + 2).long())
     del meta

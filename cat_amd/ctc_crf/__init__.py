@@ -3,10 +3,12 @@ src/ctc_crf/ctc_crf/__init__.py), backed by the MI355X-native HIP library (cat_a
 
 Same names, arguments and error behaviour as the reference:
   CTC_CRF_LOSS(lamb=0.1, size_average=True)(logits, labels, lx, ly) -> FloatTensor[1]   (:97-125)
-  WARP_CTC_LOSS(size_average=True, blank_label=0)(logits, labels, input_lengths, label_lengths)   (:128-144; blank_label added)
+  WARP_CTC_LOSS(size_average=True, blank_label=0, fuse_log_softmax=False, time_major=False)(logits, labels, input_lengths, label_lengths)
+                                                                                         (:128-144; the keywords after size_average added)
   CRFContext(den_lm, gpus)                                                               (:147-171)
   _CTC_CRF, _WARP_CTC_GPU  autograd Functions                                             (:25-94)
-  ctc_align(log_probs, labels, input_lengths, label_lengths, blank=0, time_major=False) -> (pos, tokens, scores)   (forced alignment; not in the reference)
+  ctc_align(log_probs, labels, input_lengths, label_lengths, blank=0, time_major=False, fuse_log_softmax=False) -> (pos, tokens, scores)
+                                                                                         (forced alignment; not in the reference)
 plus the functional form named by BASELINE.json:
   ctc_crf_loss(log_probs, labels, frame_lens, label_lens, den_lm, lamb=0.1, size_average=True)
 
@@ -32,20 +34,43 @@ def _assert_no_grad(tensor):
 
 class _WARP_CTC_GPU(Function):
     """Plain CTC NLL (reference __init__.py:25-55): costs = -sum_b logp_b, grad = -gamma_ctc.
-    blank_label (not in the reference's Function; warp-ctc's ctcOptions::blank_label): the blank's column."""
+    blank_label (not in the reference's Function; warp-ctc's ctcOptions::blank_label): the blank's column.
+    time_major (as torch.nn.CTCLoss): logits and the gradient are (T, N, V), read and written in place."""
 
     @staticmethod
-    def forward(ctx, logits, labels, input_lengths, label_lengths, size_average=True, blank_label=0):
+    def forward(ctx, logits, labels, input_lengths, label_lengths, size_average=True, blank_label=0, time_major=False):
         logits = logits.contiguous()
-        batch_size = logits.size(0)
+        batch_size = logits.size(1 if time_major else 0)
         s = 1.0 / batch_size if size_average else 1.0
-        costs, grads, _ = core.loss_fwd_bwd(logits, labels, input_lengths, label_lengths, 0.0, s, None, blank=int(blank_label))
+        costs, grads, _ = core.loss_fwd_bwd(logits, labels, input_lengths, label_lengths, 0.0, s, None, blank=int(blank_label),
+                                            time_major=bool(time_major))
         ctx.grads = grads
         return costs
 
     @staticmethod
     def backward(ctx, grad_output):
         return ctx.grads * grad_output.to(ctx.grads.device), None, None, None, None, None, None
+
+
+class _WARP_CTC_LOGITS_GPU(Function):
+    """_WARP_CTC_GPU with the log_softmax in front of it fused in (the caller's ``torch.log_softmax(x.float(), -1)``,
+    cat/ctc/train.py:191-196): takes the RAW network output in fp32 / bf16 / fp16, (N, T, V) or (T, N, V); the loss is that of
+    log_softmax(netout), the gradient d loss / d netout is computed in fp32 and returned in netout's dtype (as _CTC_CRF_LOGITS)."""
+
+    @staticmethod
+    def forward(ctx, netout, labels, input_lengths, label_lengths, size_average=True, blank_label=0, time_major=False):
+        netout = netout.contiguous()
+        batch_size = netout.size(1 if time_major else 0)
+        s = 1.0 / batch_size if size_average else 1.0
+        costs, grads, _ = core.loss_fwd_bwd(netout, labels, input_lengths, label_lengths, 0.0, s, None, fused=True,
+                                            blank=int(blank_label), time_major=bool(time_major))
+        ctx.grads = grads
+        ctx.out_dtype = netout.dtype
+        return costs
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        return (ctx.grads * grad_output.to(ctx.grads.device)).to(ctx.out_dtype), None, None, None, None, None, None
 
 
 class _CTC_CRF(Function):
@@ -128,20 +153,27 @@ class CTC_CRF_LOSS(Module):
 class WARP_CTC_LOSS(Module):
     """Kept for parity with the reference (which itself recommends torch.nn.CTCLoss)."""
 
-    def __init__(self, size_average=True, blank_label=0):
+    def __init__(self, size_average=True, blank_label=0, fuse_log_softmax=False, time_major=False):
         """blank_label (not in the reference, which fixes 0; as torch.nn.CTCLoss(blank=...)): the blank's column of the log-probs;
-        labels then lie in [0, V) without it."""
+        labels then lie in [0, V) without it.
+        fuse_log_softmax (not in the reference): ``forward`` takes the RAW network output (fp32, bf16 or fp16) instead of log-probs;
+            log_softmax and its backward run inside the loss kernels, the gradient comes back in the input's dtype.
+        time_major (not in the reference): logits are (T, N, V), as torch.nn.CTCLoss takes them, read in place."""
         super(WARP_CTC_LOSS, self).__init__()
-        self.ctc = _WARP_CTC_GPU.apply
+        self.ctc = _WARP_CTC_LOGITS_GPU.apply if fuse_log_softmax else _WARP_CTC_GPU.apply
         self.size_average = size_average
         self.blank_label = blank_label
+        self.fuse_log_softmax = fuse_log_softmax
+        self.time_major = time_major
 
     def forward(self, logits, labels, input_lengths, label_lengths):
         assert len(labels.size()) == 1
         _assert_no_grad(labels)
         _assert_no_grad(input_lengths)
         _assert_no_grad(label_lengths)
-        return self.ctc(logits, labels, input_lengths, label_lengths, self.size_average, self.blank_label)
+        if self.fuse_log_softmax:
+            assert logits.dtype in (torch.float, torch.bfloat16, torch.float16), f"expect float/bfloat16/float16 network output, instead: {logits.dtype}"
+        return self.ctc(logits, labels, input_lengths, label_lengths, self.size_average, self.blank_label, self.time_major)
 
 
 class CRFContext:
@@ -181,12 +213,15 @@ class CRFContext:
 
 
 def ctc_align(log_probs: torch.Tensor, labels: torch.Tensor, input_lengths: torch.Tensor, label_lengths: torch.Tensor,
-              blank: int = 0, time_major: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+              blank: int = 0, time_major: bool = False, fuse_log_softmax: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Forced alignment (not in the reference): the single best CTC alignment of every transcript, on the GPU.
 
     log_probs (torch.FloatTensor): (N, T, V) log-probs on the GPU, or (T, N, V) with time_major=True; read in place.
     labels, input_lengths, label_lengths (torch.IntTensor): on the CPU, labels flattened without padding as for WARP_CTC_LOSS.
     blank (int): the blank's column; labels lie in [0, V) without it (in [1, V) for blank = 0).
+    fuse_log_softmax (bool): log_probs is the RAW network output in fp32, bf16 or fp16 (no log_softmax, no fp32 copy): the path is the
+        best one on the upcast values -- the best under log_softmax as well, since every alignment collects the same normalisers --
+        and scores are the log-probabilities under log_softmax.
 
     Returns (pos, tokens, scores), all on log_probs' device, without a host synchronisation and without autograd:
       pos    IntTensor[N, T]: the index k in [0, label_lengths[n]) of the transcript position emitted at frame t, -1 for a blank
@@ -196,10 +231,13 @@ def ctc_align(log_probs: torch.Tensor, labels: torch.Tensor, input_lengths: torc
              not fit into input_lengths[n] frames, or every alignment has probability 0).
     Among alignments of equal score the one that stays longest in each state wins (stay, then advance, then skip a blank)."""
     assert len(labels.size()) == 1
-    assert log_probs.dtype == torch.float, f"expect log_probs to be torch.float object, instead: {log_probs.dtype}"
+    if fuse_log_softmax:
+        assert log_probs.dtype in (torch.float, torch.bfloat16, torch.float16), f"expect float/bfloat16/float16 network output, instead: {log_probs.dtype}"
+    else:
+        assert log_probs.dtype == torch.float, f"expect log_probs to be torch.float object, instead: {log_probs.dtype}"
     with torch.no_grad():
         pos, tokens, scores, _ = core.ctc_align(log_probs.detach().contiguous(), labels, input_lengths, label_lengths, int(blank),
-                                                bool(time_major))
+                                                bool(time_major), fused=bool(fuse_log_softmax))
     return pos, tokens, scores
 
 

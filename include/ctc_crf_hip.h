@@ -18,8 +18,8 @@
  *     (the reference printf()s and exit(1)s, den_calculate.cu:16-25, or drops the status,
  *     binding.cpp:111).
  *   - log_probs: [B][T][V] float32, contiguous (the reference's `logits`, ctc_crf/__init__.py:61);
- *     labels: flattened int32 without padding, blank = 0; lx/ly: int32 [B].  (crf_ctc_fwd_bwd:
- *     also time-major [T][B][V] and any blank.)
+ *     labels: flattened int32 without padding, blank = 0; lx/ly: int32 [B].  (crf_ctc_fwd_bwd, crf_ctc_align
+ *     and their *_logits twins: also time-major [T][B][V] and any blank.)
  */
 #ifndef CTC_CRF_HIP_H_
 #define CTC_CRF_HIP_H_
@@ -161,6 +161,22 @@ int crf_ctc_fwd_bwd(const float *act_dev, int time_major, int blank, const int32
                     float *grad_dev, float *loss_dev, float *costs_ctc_dev, int32_t *invalid_dev,
                     void *workspace_dev, int64_t workspace_bytes, void *stream);
 
+/* crf_ctc_fwd_bwd on the RAW network output: the log_softmax in front of plain CTC and its backward fused in, as
+ * crf_loss_fwd_bwd_logits does for the CTC-CRF loss, in either layout and with any blank.  Replaces, besides gpu_ctc,
+ *   torch.log_softmax(x.float(), -1)  (cat/ctc/train.py:191-196, the non-CRF branch) and its backward.
+ * act_dev: [B][T][V] or [T][B][V] (time_major) of dtype 0 = fp32, 1 = bf16, 2 = fp16, upcast in registers; everything else as
+ * crf_ctc_fwd_bwd (workspace from crf_workspace_bytes(NULL, ...), no host sync):
+ *   costs_ctc_dev[b] = logp_ctc[b] under log_softmax of the upcast input,   loss_dev[0] = -c_ctc * sum_b costs_ctc_dev[b],
+ *   grad_dev (fp32, the caller's layout): for a valid utterance and t < lx[b]
+ *       grad[row (b, t)][v] = -c_ctc * (gamma_ctc[b][t][v] - softmax(x[b][t])[v]),
+ *   exactly 0 for rows t >= lx[b] and for invalid utterances; invalid_dev as in crf_ctc_fwd_bwd.
+ * CRF_ERR_ARG: dtype outside 0..2, c_ctc == 0. */
+int crf_ctc_fwd_bwd_logits(const void *act_dev, int dtype, int time_major, int blank, const int32_t *labels_dev,
+                           const int32_t *label_off_dev, const int32_t *lx_dev, const int32_t *ly_dev,
+                           int64_t B, int64_t T, int64_t V, int64_t max_label_len, float c_ctc,
+                           float *grad_dev, float *loss_dev, float *costs_ctc_dev, int32_t *invalid_dev,
+                           void *workspace_dev, int64_t workspace_bytes, void *stream);
+
 /* Forced alignment: the single best alignment of each transcript through the numerator's 2L+1 states (no reference counterpart:
  * the reference returns the sum over alignments only).  Conventions of crf_ctc_fwd_bwd: no host sync, all work on `stream`, act_dev
  * read in place as [B][T][V] (time_major = 0) or [T][B][V] (1), any blank in [0, V), labels_dev / label_off_dev / lx_dev / ly_dev as
@@ -181,6 +197,29 @@ int crf_ctc_align(const float *act_dev, int time_major, int blank, const int32_t
                   int64_t B, int64_t T, int64_t V, int64_t max_label_len,
                   int32_t *pos_dev, float *score_dev, int32_t *invalid_dev,
                   void *workspace_dev, int64_t workspace_bytes, void *stream);
+
+/* Forced alignment on the RAW network output: act_dev is [B][T][V] or [T][B][V] of dtype 0 = fp32, 1 = bf16, 2 = fp16, read in place
+ * (2-byte elements are upcast in registers; rows of 16-bit elements need 2-byte alignment only).  Everything else -- arguments, limits
+ * (V <= 8192, max_label_len <= 2047, B * T <= INT32_MAX), pos_dev / invalid_dev, errors answered before any HIP call -- as crf_ctc_align,
+ * plus CRF_ERR_ARG for a dtype outside 0..2.  Contract, with x^ the exact fp32 upcast of the input:
+ *   - the path is the one crf_ctc_align's recursion finds on x^ ITSELF: fp32, sums in frame order, the same strict tie rule (stay, then
+ *     advance, then skip; state 2L before 2L-1), no normalisation inside the recursion.  Every alignment of an utterance takes one
+ *     entry from each of its lx frames, so log_softmax's normaliser sum_t lse_t is common to all of them: in exact arithmetic this is
+ *     the best path under log_softmax(x^) as well;
+ *   - score_dev[b] = float(double(raw best sum) - sum_{t < lx[b]} double(lse_t)),  lse_t = m_t + log sum_v exp(x^[t][v] - m_t),
+ *     m_t = max_v x^[t][v], each lse_t computed in fp32 by a row kernel (16 lanes per frame for V <= 256, 64 otherwise: a lane adds
+ *     its entries v = lane, lane + G, ... in order, the lanes' sums meet in a butterfly), the sum over t in fp64 in a fixed order
+ *     (no atomics);
+ *   - pos_dev and score_dev are reproducible bit for bit across calls and across the two layouts;
+ *   - a dead utterance (raw best sum = -inf) or an invalid one returns exactly what crf_ctc_align returns; the lse sum is not used.
+ * Workspace: crf_ctc_align_logits_workspace_bytes = crf_ctc_align_workspace_bytes + the lse values [B][T] (fp32; those of frames
+ * t >= lx[b] are neither written nor read); -1 for a shape this build does not take. */
+int64_t crf_ctc_align_logits_workspace_bytes(int64_t B, int64_t T, int64_t V, int64_t max_label_len);
+int crf_ctc_align_logits(const void *act_dev, int dtype, int time_major, int blank, const int32_t *labels_dev,
+                         const int32_t *label_off_dev, const int32_t *lx_dev, const int32_t *ly_dev,
+                         int64_t B, int64_t T, int64_t V, int64_t max_label_len,
+                         int32_t *pos_dev, float *score_dev, int32_t *invalid_dev,
+                         void *workspace_dev, int64_t workspace_bytes, void *stream);
 
 /* Replaces the cudaMemcpyAsync calls that bring labels, label lengths and input lengths to the device
  * (gpu_ctc.h:143-229; `input_lengths.cuda()`, ctc_crf/__init__.py:73): copies n int32 from PINNED host
