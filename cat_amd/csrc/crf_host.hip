@@ -607,18 +607,22 @@ static int launch_fac_pair(const LossParams &lp, size_t lds, hipStream_t st, int
     else if (g3 && F.rcl == 2) CRF_LAUNCH_RL(kFac3LNCH, true, "21,4,4,true", mk21m)
 #undef CRF_LAUNCH_RL
     else if (F.threads == kFac4Threads) {   // 1024 threads: four waves per SIMD (the planner's first choice)
-        static LdsMark m4n, m4m;
-        if (ml) {
-            auto *k = crf_fac_pair_kernel<FLAG, kFac4Threads, kFac4NCH, CRF_FAC4_NB_ML, CRF_FAC4_NB_ML, true, true>;
-            g_den_kernel = FLAG ? "crf_fac_pair_kernel<true,1024," CRF_STR(CRF_FAC4_NCH) "," CRF_STR(CRF_FAC4_NB_ML) "," CRF_STR(CRF_FAC4_NB_ML) ",true,true>" : "crf_fac_pair_kernel<false,1024," CRF_STR(CRF_FAC4_NCH) "," CRF_STR(CRF_FAC4_NB_ML) "," CRF_STR(CRF_FAC4_NB_ML) ",true,true>";
-            if ((rc = ensure_lds((const void *)k, lds, m4m, "fac pair"))) return rc;
-            hipLaunchKernelGGL(k, grid, dim3(kFac4Threads), lds, st, pf, pb);
-        } else {
-            auto *k = crf_fac_pair_kernel<FLAG, kFac4Threads, kFac4NCH, CRF_FAC4_NB, CRF_FAC4_NB, false, true>;
-            g_den_kernel = FLAG ? "crf_fac_pair_kernel<true,1024," CRF_STR(CRF_FAC4_NCH) "," CRF_STR(CRF_FAC4_NB) "," CRF_STR(CRF_FAC4_NB) ",false,true>" : "crf_fac_pair_kernel<false,1024," CRF_STR(CRF_FAC4_NCH) "," CRF_STR(CRF_FAC4_NB) "," CRF_STR(CRF_FAC4_NB) ",false,true>";
-            if ((rc = ensure_lds((const void *)k, lds, m4n, "fac pair"))) return rc;
-            hipLaunchKernelGGL(k, grid, dim3(kFac4Threads), lds, st, pf, pb);
-        }
+        // (the last template argument: next-vector stores by ds_write_addtid_b32, the planner's choice per graph -- FacDev::addtid)
+#define CRF_LAUNCH_1024(ML_, ADT_, NB_, MARK_)                                                                                  \
+    {                                                                                                                           \
+        static LdsMark MARK_;                                                                                                   \
+        auto *k = crf_fac_pair_kernel<FLAG, kFac4Threads, kFac4NCH, NB_, NB_, ML_, true, ADT_>;                                 \
+        g_den_kernel = FLAG ? "crf_fac_pair_kernel<true,1024," CRF_STR(CRF_FAC4_NCH) "," CRF_STR(NB_) "," CRF_STR(NB_) "," #ML_ ",true," #ADT_ ">"  \
+                            : "crf_fac_pair_kernel<false,1024," CRF_STR(CRF_FAC4_NCH) "," CRF_STR(NB_) "," CRF_STR(NB_) "," #ML_ ",true," #ADT_ ">"; \
+        if ((rc = ensure_lds((const void *)k, lds, MARK_, "fac pair"))) return rc;                                              \
+        hipLaunchKernelGGL(k, grid, dim3(kFac4Threads), lds, st, pf, pb);                                                       \
+    }
+        const bool adt = F.addtid != 0;
+        if (ml && adt) CRF_LAUNCH_1024(true, true, CRF_FAC4_NB_ML, m4ma)
+        else if (ml) CRF_LAUNCH_1024(true, false, CRF_FAC4_NB_ML, m4m)
+        else if (adt) CRF_LAUNCH_1024(false, true, CRF_FAC4_NB, m4na)
+        else CRF_LAUNCH_1024(false, false, CRF_FAC4_NB, m4n)
+#undef CRF_LAUNCH_1024
     }
     else if (g3 && ml) {
         auto *k = crf_fac_pair_kernel<FLAG, kFac3Threads, kFac3NCH, CRF_FAC3_NB_F, CRF_FAC3_NB_B, true>;

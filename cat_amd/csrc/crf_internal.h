@@ -103,6 +103,9 @@ struct ResDev {
 // Both halve the arc registers: the 104 k-arc benchmark graph fits 512 threads x 180 words per direction.
 // Graphs without that structure (or with states entered by several labels) keep the generic layout.
 // ---------------------------------------------------------------------------------------------
+// z entry (backward gather vector of the factored layout) of output `o` of row `rid`: the slice of 64 rows that a wave finishes together
+// owns the entries [2 * rid0, 2 * rid0 + 128) -- its 64 outputs 0, then its 64 outputs 1
+__host__ __device__ constexpr int fac_zent(int rid, int o) { return 2 * (rid & ~63) + (rid & 63) + 64 * o; }
 struct FacDirDev {
     const unsigned *arcs;    // [words][threads]
     const uint4 *wave_info;  // [waves] {slice-end mask, chunks used, first row id, unused}
@@ -127,8 +130,11 @@ struct FacDev {
     int xlist_off[3];          //   [xlist_off[k], xlist_off[k + 1]); the U entries cross as a range, everything once more at the end
     int rcl;                   // 768 threads with the row constants in an LDS table read one slice ahead (any number of slices per wave)
     int multilane;             // some rows lie on several adjacent lanes (wave_info.w != 0 somewhere): kernel variant with the butterfly
+    int addtid;                // the row epilogues store the next vector with ds_write_addtid_b32 (fac_chain_body ADT): the 1024-thread geometry with
+                               // one CU per recursion unless the switch fac_addtid says otherwise (build_factored)
     const float *x_start, *x_end;   // [Gf]
-    // backward: rows = one or two states with common out-arcs; z entry of output o of row r = 2r + o.
+    // backward: rows = one or two states with common out-arcs; BP position (rows in memory, brow_start / brow_end, gb) of output o of
+    // row r = 2r + o; its z entry in the LDS vector = fac_zent(r, o): planar within the slice of 64 rows.
     const int4 *brow_meta;     // [Rb] {extra-arc z byte offset 0 | offset 1 << 16, weight 0 bits, weight 1 bits, label 0 | label 1 << 16}
     const int *z_lab;          // [Gb] label of each z entry (V = none)
     const float *z_end;        // [Gb] exp(end weight) of the entry's state
@@ -321,6 +327,7 @@ void set_error(const std::string &msg);
     X(fac_threads,      "G  512 / 768 / 1024: that geometry of the factored layout (default: 1024 threads first, then the 768-thread geometries, then 512)")                                            \
     X(fac_no_dup,       "G  factored layout: no second copy of the gathered entries")                                        \
     X(fac_bank_shift,   "G  factored layout: bank distance of the second copy (default 5)")                                  \
+    X(fac_addtid,       "G  factored layout, 1024 threads: the row epilogues store the next vector with 0 = ds_write_b32 / ds_write2st64_b32, 1 = ds_write_addtid_b32 (the default there)") \
     X(res_mink,         "G  generic layout: at least this many CUs per recursion")                                           \
     X(res_epi,          "G  layout cost model: slice end in chunks (default 4)")                                             \
     X(res_piece,        "G  multi-lane rows: piece size in percent of a lane's chunks (default: the cost model's choice)")   \

@@ -137,7 +137,7 @@ struct FacParams {
     int npair, dump_stride;
     float *dump;                // [2 directions][npair][dump_stride]
 };
-template <bool FLAG, int NTH, int NCH, int NBF, int NBB, bool ML, bool RL = false> __global__ void crf_fac_pair_kernel(FacParams pf, FacParams pb);
+template <bool FLAG, int NTH, int NCH, int NBF, int NBB, bool ML, bool RL = false, bool ADT = false> __global__ void crf_fac_pair_kernel(FacParams pf, FacParams pb);
 template <bool FLAG, int NTH, int NCH, int NBF, int NBB, bool ML, bool RL> __global__ void crf_fac_pair2_kernel(FacParams pf, FacParams pb);
 template <int NTH, int NCH, int NBF, int NBB> __global__ void crf_fac2_pair_kernel(FacParams pf, FacParams pb);
 

@@ -6,7 +6,9 @@ namespace crf {
 
 #define CRF_INST_FAC(FLAG)                                                                                                                  \
     template __global__ void crf_fac_pair_kernel<FLAG, kFac4Threads, kFac4NCH, CRF_FAC4_NB, CRF_FAC4_NB, false, true>(FacParams, FacParams);           \
-    template __global__ void crf_fac_pair_kernel<FLAG, kFac4Threads, kFac4NCH, CRF_FAC4_NB_ML, CRF_FAC4_NB_ML, true, true>(FacParams, FacParams);
+    template __global__ void crf_fac_pair_kernel<FLAG, kFac4Threads, kFac4NCH, CRF_FAC4_NB_ML, CRF_FAC4_NB_ML, true, true>(FacParams, FacParams);      \
+    template __global__ void crf_fac_pair_kernel<FLAG, kFac4Threads, kFac4NCH, CRF_FAC4_NB, CRF_FAC4_NB, false, true, true>(FacParams, FacParams);     \
+    template __global__ void crf_fac_pair_kernel<FLAG, kFac4Threads, kFac4NCH, CRF_FAC4_NB_ML, CRF_FAC4_NB_ML, true, true, true>(FacParams, FacParams);
 CRF_INST_FAC(true)
 CRF_INST_FAC(false)
 #undef CRF_INST_FAC

@@ -16,7 +16,8 @@ namespace crf {
 //             A' = e'[l1] * w * U is a[s1] (its own row is exactly w * (a[s1] + a[s2]) = w * U); U' = A' + L'
 //             is the entry every other row gathers for the pair.  Q row: [rowsum of each row | w*U of each row].
 //   backward: a row is the common out-arc sum of one or two states; the epilogue adds each state's one
-//             extra arc (BP positions / z entries 2*rid, 2*rid + 1).
+//             extra arc (BP positions 2*rid, 2*rid + 1 in memory; z entries fac_zent(rid, 0 / 1) in the LDS vector: planar within
+//             the slice of 64 rows, which stores two runs of 64 consecutive floats, 256 bytes apart, per copy).
 // LDS: V0 | V1 (two state vectors of Gp floats) | row metadata int4[R] | EP[2][Vp] | wm | red
 // =============================================================================================
 
@@ -31,9 +32,15 @@ namespace crf {
 // also published as {frame tag, value} granules (res_chain_body's protocol: the data is the flag), and after its last chunk the
 // CU fetches the peer's entries into its own vector before the frame barrier.  Table geometry (RL) only, one copy of the
 // gathered entries, no stages (2 B x 2 workgroups are every CU of the device: nothing runs beside the recursions).
-template <int DIR, bool FLAG, int NTH, int NCH, int NB, bool ML, bool RL, bool K2 = false>
+// ADT: the row epilogues store the entries of the next vector with ds_write_addtid_b32 -- every one of them lies at (uniform base) + 4 * lane:
+// the base travels in M0 (written with s_mov, one wait state), no address VGPR and no v_add per store, and half the VGPR -> LDS traffic of a
+// ds_write_b32 (M0 reaches the whole LDS: tools/addtid_probe).  Forward: U, its copy, L, A -- four bases; backward: the slice's two planes share
+// a base (the instruction's offset field), so two.  Implicit entries and one CU per recursion only; instantiated for the 1024-thread geometry,
+// where it is the planner's default (FacDev::addtid, switch fac_addtid; profiles/ab_row_epilogues.txt).
+template <int DIR, bool FLAG, int NTH, int NCH, int NB, bool ML, bool RL, bool K2 = false, bool ADT = false>
 __device__ __forceinline__ void fac_chain_body(const FacParams &p, float *lds, const int b, const int k = 0) {
     static_assert(!K2 || (RL && !FLAG), "two CUs per recursion: table geometry, no stage flags");
+    static_assert(!ADT || (NTH != kResThreads && !K2), "ds_write_addtid stores: implicit entries, one CU per recursion");
     constexpr int NW = NTH / kWave;
     // 768-thread geometry: the last chunk slot of a thread holds ROW CONSTANTS instead of arcs -- two words for each of
     // the (at most three) rows the lane finishes per frame -- and the entries of a row sit where its row id says
@@ -394,9 +401,7 @@ __device__ __forceinline__ void fac_chain_body(const FacParams &p, float *lds, c
                         *(float *)((char *)Orow + r4 + 4u * (unsigned)R) = qt;
                     }
                     const float Lp = em * rv, Ap = et * qt, Up = Ap + Lp;           // a_{t+1}[main], [tail], their sum
-                    if constexpr (CRF_X_ADDTID != 0 && !K2) {
-                        // the four entries lie at (uniform base) + 4 * lane: ds_write_addtid_b32 takes the base from M0 and no address VGPR -- half the
-                        // VGPR -> LDS traffic of a ds_write_b32 and no v_add per store (M0 reaches the whole LDS: tools/addtid_probe)
+                    if constexpr (ADT) {
                         const unsigned mb = (unsigned)(uintptr_t)xnb + (unsigned)__builtin_amdgcn_readfirstlane((int)r4);
                         lds_st_addtid(Up, mb); lds_st_addtid(Up, mb + dup); lds_st_addtid(Lp, mb + 4u * (unsigned)R); lds_st_addtid(Ap, mb + 8u * (unsigned)R);
                     } else {
@@ -427,12 +432,18 @@ __device__ __forceinline__ void fac_chain_body(const FacParams &p, float *lds, c
                     f32x2 zv;                                                        // z_{t-1} of the pairs entering them
                     zv.x = e0 * bv.x;
                     zv.y = e1 * bv.y;
-                    *(f32x2 *)(xnb + 2u * r4) = zv;
-                    typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
-                    *(f32x2u *)(xnb + 2u * r4 + dup) = zv;
-                    if constexpr (K2) {           // entries 2 rid, 2 rid + 1
-                        gu64 *gs = (gu64 *)((char *)slot + 4u * r4);
-                        res_publish(gs, 0, tag, zv.x, same_l2); res_publish(gs, 1, tag, zv.y, same_l2);
+                    // z entries fac_zent(rid, 0 / 1): the slice's two planes at 8 * rid0 + 4 * lane and 256 bytes behind, and their copies
+                    if constexpr (ADT) {          // (lane 0 holds rid0: one write of M0 per copy, the second plane by the instruction's offset)
+                        const unsigned mb = (unsigned)(uintptr_t)xnb + 2u * (unsigned)__builtin_amdgcn_readfirstlane((int)r4);
+                        lds_st_addtid2(zv.x, zv.y, mb); lds_st_addtid2(zv.x, zv.y, mb + dup);
+                    } else {
+                        char *zp = xnb + r4 + (r4 & ~255u);
+                        *(float *)zp = zv.x; *(float *)(zp + 256) = zv.y;                  // (one ds_write2_b32 per copy)
+                        *(float *)(zp + dup) = zv.x; *(float *)(zp + dup + 256) = zv.y;
+                    }
+                    if constexpr (K2) {           // the same entries of the peer's vector
+                        gu64 *gs = (gu64 *)((char *)slot + 2u * (r4 + (r4 & ~255u)));
+                        res_publish(gs, 0, tag, zv.x, same_l2); res_publish(gs, 64, tag, zv.y, same_l2);
                     }
                     mymax = __int_as_float(max(__float_as_int(mymax), max(__float_as_int(zv.x), __float_as_int(zv.y))));
                 }
@@ -474,9 +485,9 @@ __device__ __forceinline__ void fac_chain_body(const FacParams &p, float *lds, c
                 f32x2 zv;                                                    // z_{t-1} of the pairs entering them
                 zv.x = e0 * bv.x;
                 zv.y = e1 * bv.y;
-                *(f32x2 *)(xnb + 2u * r4) = zv;
-                typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
-                if (dup) *(f32x2u *)(xnb + 2u * r4 + dup) = zv;   // the copy's distance is an odd number of floats: ds_write2_b32
+                char *zp = xnb + r4 + (r4 & ~255u);              // z entries fac_zent(rid, 0 / 1)
+                *(float *)zp = zv.x; *(float *)(zp + 256) = zv.y;
+                if (dup) { *(float *)(zp + dup) = zv.x; *(float *)(zp + dup + 256) = zv.y; }
                 mymax = fmaxf(mymax, fmaxf(zv.x, zv.y));
             }
             }
@@ -558,7 +569,7 @@ __device__ __forceinline__ void fac_chain_body(const FacParams &p, float *lds, c
                     fm = res_fetch_both<NTH>(slot, Xn, p0, p1, p.xlist, p.xlist_off[k], p.xlist_off[k + 1], tag, p.err, tid);   // (one polling loop for both)
                 }
             } else {
-                fm = res_fetch<NTH>(slot, Xn, 2 * p0, 2 * p1, tag, p.err, tid);
+                fm = res_fetch<NTH>(slot, Xn, 2 * p0, 2 * p1, tag, p.err, tid);   // (whole slices: the entries of the peer's rows are one range)
             }
             mymax = fmaxf(mymax, fm);
         }
@@ -930,10 +941,11 @@ __device__ __forceinline__ void fac_chain_body2(const FacParams &p, float *lds, 
                         *(f32x2 *)((char *)Orow[u] + 2u * r4) = f32x2{bx[u], by[u]};
                 }
                 const f32x2 zx = e0 * bx, zy = e1 * by;           // z_{t-1} of the pairs entering them
-                lds_st2(xnb + 4u * r4, zx);
-                lds_st2(xnb + 4u * r4 + 8u, zy);
-                lds_st2(xnb + 4u * r4 + dup2, zx);
-                lds_st2(xnb + 4u * r4 + dup2 + 8u, zy);
+                const unsigned zp = xnb + 2u * (r4 + (r4 & ~255u));   // z entries fac_zent(rid, 0 / 1), a float2 each
+                lds_st2(zp, zx);
+                lds_st2(zp + 512u, zy);
+                lds_st2(zp + dup2, zx);
+                lds_st2(zp + dup2 + 512u, zy);
                 mymax.x = __int_as_float(max(__float_as_int(mymax.x), max(__float_as_int(zx.x), __float_as_int(zy.x))));
                 mymax.y = __int_as_float(max(__float_as_int(mymax.y), max(__float_as_int(zx.y), __float_as_int(zy.y))));
             }
@@ -1042,12 +1054,13 @@ __device__ __forceinline__ void fac_chain_body2(const FacParams &p, float *lds, 
 // guaranteed inside a training process (HIP maps all streams of a process onto GPU_MAX_HW_QUEUES = 4 queues; with
 // RCCL's and torch's streams around, the recursions were observed to run one after the other: 5.3 instead of 3.25 ms).
 // NBF / NBB: chunks gathered per batch, forward / backward.
-template <bool FLAG, int NTH, int NCH, int NBF, int NBB, bool ML, bool RL>
+// ADT: next-vector stores by ds_write_addtid_b32 in both directions (fac_chain_body)
+template <bool FLAG, int NTH, int NCH, int NBF, int NBB, bool ML, bool RL, bool ADT>
 __global__ __launch_bounds__(NTH) void crf_fac_pair_kernel(FacParams pf, FacParams pb) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int B = pf.B;
-    if ((int)blockIdx.x < B) fac_chain_body<0, FLAG, NTH, NCH, NBF, ML, RL>(pf, lds, (int)blockIdx.x);
-    else fac_chain_body<1, FLAG, NTH, NCH, NBB, ML, RL>(pb, lds, (int)blockIdx.x - B);
+    if ((int)blockIdx.x < B) fac_chain_body<0, FLAG, NTH, NCH, NBF, ML, RL, false, ADT>(pf, lds, (int)blockIdx.x);
+    else fac_chain_body<1, FLAG, NTH, NCH, NBB, ML, RL, false, ADT>(pb, lds, (int)blockIdx.x - B);
 }
 // ... with TWO UTTERANCES per workgroup: 2 * ceil(B / 2) workgroups, forward recursions first
 template <bool FLAG, int NTH, int NCH, int NBF, int NBB, bool ML, bool RL>

@@ -1340,9 +1340,10 @@ static int build_factored_impl(HostGraph *h, int S, int P, const std::vector<int
                     for (auto &c : common) { float w; memcpy(&w, &c.second, 4); r.arcs.push_back({c.first, w}); }
                     if (!ea.empty()) { r.e0 = ea[0].first; memcpy(&r.w0, &ea[0].second, 4); }
                     if (!eb.empty()) { r.e1 = eb[0].first; memcpy(&r.w1, &eb[0].second, 4); }
-                    // which of the two states is output 0 alternates: the z entries 2*rid + output are what the
-                    // rows gather, and in a T o LM graph nearly all arcs enter the "token" state of a pair -- with
-                    // a fixed order every gather would hit an odd entry, i.e. half of the LDS banks
+                    // which of the two states is output 0 alternates: in a T o LM graph nearly all arcs enter the
+                    // "token" state of a pair, and with a fixed order every gather would hit the entries of ONE output
+                    // (under the BP rows' numbering 2*rid + output, which the z entries shared until the slices became
+                    // planar: half of the LDS banks; the order also fixes the BP rows in memory, which the grad pass reads)
                     if (brow.size() & 1) { std::swap(r.s0, r.s1); std::swap(r.e0, r.e1); std::swap(r.w0, r.w1); }
                     brow.push_back(r);
                     done[s] = done[m] = 1;
@@ -1387,14 +1388,19 @@ static int build_factored_impl(HostGraph *h, int S, int P, const std::vector<int
         if (!no_dupb) { *new_mask = dup_mask & ~2; return CRF_OK; }
         return give_up("backward gather vector > 64 KiB");
     }
-    std::vector<int> zpos(S, -1);   // BP / z position of state s: 2*rid + output
+    // BP position of state s (rows in memory): 2*rid + output.  Its z entry in the LDS vector is PLANAR WITHIN THE SLICE of 64 rows that a wave
+    // finishes together (fac_zent): the slice's 128 entries are the 64 outputs 0, then the 64 outputs 1 -- two runs of 64 consecutive floats
+    // 256 bytes apart (and two more in the second copy), which a wave stores with ONE ds_write2_b32 per copy, or with two
+    // ds_write_addtid_b32 (no address register at all) behind one write of M0.  A slice still owns the entries [2 * rid0, 2 * rid0 + 128),
+    // so whatever speaks of ranges of rows (the second copy, the two-CU exchange) is as before.
+    std::vector<int> zpos(S, -1), zent(S, -1);
     for (int rid = 0; rid < Rb; ++rid) {
         const int r = bo.row_of[rid];
         if (r < 0) continue;
-        zpos[brow[r].s0] = 2 * rid;
-        if (brow[r].s1 >= 0) zpos[brow[r].s1] = 2 * rid + 1;
+        zpos[brow[r].s0] = 2 * rid; zent[brow[r].s0] = fac_zent(rid, 0);
+        if (brow[r].s1 >= 0) { zpos[brow[r].s1] = 2 * rid + 1; zent[brow[r].s1] = fac_zent(rid, 1); }
     }
-    auto zof_pair = [&](int p) { return zpos[pair_dst[p]]; };
+    auto zof_pair = [&](int p) { return zent[pair_dst[p]]; };
     for (auto &row : bsub)
         for (auto &a : row) a.first = zof_pair(a.first);
     for (int s = 0; s < S; ++s)   // rowless states: b_0[s] * start[s] = start[s] * sum over their arcs of w * z_0[pair]
@@ -1415,10 +1421,10 @@ static int build_factored_impl(HostGraph *h, int S, int P, const std::vector<int
         const int l1 = (br.s1 >= 0 && pair_of[br.s1] >= 0) ? pair_lab[pair_of[br.s1]] : noLab;
         brow_meta[rid] = int4{(o0 * 4) | ((o1 * 4) << 16), (int)wbits(br.w0), (int)wbits(br.w1), (l0 & 0xffff) | (l1 << 16)};
         brow_start[2 * rid] = start_lin[br.s0]; brow_end[2 * rid] = end_lin[br.s0];
-        z_lab[2 * rid] = l0; z_end[2 * rid] = end_lin[br.s0];
+        z_lab[fac_zent(rid, 0)] = l0; z_end[fac_zent(rid, 0)] = end_lin[br.s0];
         if (br.s1 >= 0) {
             brow_start[2 * rid + 1] = start_lin[br.s1]; brow_end[2 * rid + 1] = end_lin[br.s1];
-            z_lab[2 * rid + 1] = l1; z_end[2 * rid + 1] = end_lin[br.s1];
+            z_lab[fac_zent(rid, 1)] = l1; z_end[fac_zent(rid, 1)] = end_lin[br.s1];
         }
     }
 
@@ -1496,6 +1502,15 @@ static int build_factored_impl(HostGraph *h, int S, int P, const std::vector<int
     F.multilane = 0;
     for (auto &wi : fo.wave_info) if (wi.w) F.multilane = 1;
     for (auto &wi : bo.wave_info) if (wi.w) F.multilane = 1;
+    // Next-vector stores by ds_write_addtid_b32 (fac_chain_body ADT): every graph on the 1024-thread geometry with one CU per recursion -- the only
+    // instantiations that have them.  Measured against the ds_write stores on one box (profiles/ab_row_epilogues.txt): metric graph 2.664 -> 2.622 ms per
+    // step, V = 217 (rows on several lanes) 3.136 -> 3.003, and S = 513 -- four backward slices on sixteen waves, where four M0 writes per forward
+    // epilogue alone had cost 5 % (profiles/round6_ab_addtid.txt) -- 1.905 -> 1.888 with two per backward epilogue beside them.
+    F.addtid = 0;
+    if (implicit && K == 1 && gm->threads == kFac4Threads) {
+        const int sw = opt(kOpt_fac_addtid, -1);
+        F.addtid = sw >= 0 ? (sw != 0) : 1;
+    }
     F.f.R = Rf; F.f.G = Gf; F.b.R = Rb; F.b.G = Gb; F.f.dup = fdup * 4; F.b.dup = bdup * 4;
     F.NT = NT; F.Rq = Rq; F.Rbp = 2 * Rb; F.NC = (int)gchunk.size() - 1; F.chunk_cap = cap; F.threads = gm->threads; F.imp = implicit ? 1 : 0; F.rcl = level == 1 ? 1 : level == 3 ? 2 : (level == 4 || level == 6) ? 1 : 0; F.K = K;
     for (int k = 0; k < 3; ++k) F.xlist_off[k] = xlist_off[k];
@@ -1637,6 +1652,7 @@ int debug_emulate_factored(const HostGraph *h, int T, unsigned seed, double *out
                     const int nch = (int)wi.y;
                     int row = (int)wi.z, slice = 0;
                     if (nch > (rcregs ? kFac3ArcCh : words / 6)) return fail("a wave uses more chunks than the geometry has");
+                    if (row % kWave) return fail("a wave's first row is not the first of a slice");   // (lane l finishes row rid0 + l: what the planar slices and the add-TID stores rest on)
                     double acc[kWave];
                     for (double &x : acc) x = 0.0;
                     for (int c = 0; c < nch; ++c) {
@@ -1696,8 +1712,8 @@ int debug_emulate_factored(const HostGraph *h, int T, unsigned seed, double *out
                                 if (t == 0) { b0rows[(size_t)2 * rid] = bv0; b0rows[(size_t)2 * rid + 1] = bv1; }
                                 else { BProws[(size_t)t - 1][(size_t)2 * rid] = bv0; BProws[(size_t)t - 1][(size_t)2 * rid + 1] = bv1; }
                                 const double zv0 = em[(size_t)(l0 == 0xffffu ? V : l0)] * bv0, zv1 = em[(size_t)(l1 == 0xffffu ? V : l1)] * bv1;
-                                dst[(size_t)2 * rid] = zv0; dst[(size_t)2 * rid + 1] = zv1;
-                                if (dup) { dst[(size_t)2 * rid + dup] = zv0; dst[(size_t)2 * rid + 1 + dup] = zv1; }
+                                dst[(size_t)fac_zent(rid, 0)] = zv0; dst[(size_t)fac_zent(rid, 1)] = zv1;   // (planar within the slice)
+                                if (dup) { dst[(size_t)fac_zent(rid, 0) + dup] = zv0; dst[(size_t)fac_zent(rid, 1) + dup] = zv1; }
                             }
                         }
                         for (double &x : acc) x = 0.0;
@@ -1719,6 +1735,7 @@ int debug_emulate_factored(const HostGraph *h, int T, unsigned seed, double *out
                             mine[(size_t)en] = peer[(size_t)en];
                         }
                     } else {
+                        if (p0 % kWave || p1 % kWave) return fail("a CU's backward rows are not whole slices");   // (a slice owns the entries [2 rid0, 2 rid0 + 128))
                         for (int z = 2 * p0; z < 2 * p1; ++z) mine[(size_t)z] = peer[(size_t)z];
                     }
                 }
