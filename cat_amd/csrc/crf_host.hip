@@ -181,12 +181,37 @@ struct DevCtx {
     hipEvent_t fork{}, join{}, ev[kMaxStages]{}, evb[kMaxStages]{};
     int *flags = nullptr;     // fine-grained (uncached, cross-XCD coherent) words: [0] error word, [1] start counter, [16..32) stage counters
     bool warned = false;
-    int reprobes = 0;         // probes for a side stream after the first one found none (loss_impl: at calls 256, 1 024, 4 096)
+    int reprobes = 0;         // probes for a side stream after the first one found none (reprobe_side: at calls 256, 1 024, 4 096)
     int side_kind = 0, side_tries = 0;   // find_beside: what kind of stream the side stream is, how many candidates were probed
     char side_desc[96] = "none";
 };
 static std::mutex g_ctx_mu;
 static std::vector<DevCtx *> g_ctxs;
+
+// Dynamic LDS above 64 KiB must be opted into per kernel AND per device (hipFuncSetAttribute acts on the current
+// device's copy of the function): high-water mark per device.
+struct LdsMark { std::atomic<size_t> v[kMaxDev]; };
+static int ensure_lds(const void *fn, size_t bytes, LdsMark &m, const char *what) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) { set_error("hipGetDevice failed"); return CRF_ERR_HIP; }
+    if (bytes <= m.v[dev].load()) return CRF_OK;
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) { set_error(std::string("hipFuncSetAttribute(") + what + "): " + hipGetErrorString(e)); return CRF_ERR_HIP; }
+    m.v[dev] = bytes;
+    return CRF_OK;
+}
+// Every kernel launch of this file.  K is a template argument, so each instantiation has its own mark; a launch with dynamic LDS raises
+// it first; a launch error comes back as CRF_ERR_HIP with the kernel's name (the text is built on failure only).
+template <auto K, typename... A>
+static int launch(const char *name, dim3 grid, dim3 block, size_t lds, hipStream_t st, const A &...args) {
+    static LdsMark mark;
+    int rc;
+    if (lds > 0 && (rc = ensure_lds((const void *)K, lds, mark, name))) return rc;
+    hipLaunchKernelGGL(K, grid, block, lds, st, args...);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error(std::string(name) + ": " + hipGetErrorString(e)); return CRF_ERR_HIP; }
+    return CRF_OK;
+}
 
 // Do two streams run side by side?  HIP maps every stream of the process onto GPU_MAX_HW_QUEUES (default 4) hardware
 // queues; two streams on one queue run their kernels one after the other.  Two single-wave kernels shake hands through
@@ -237,10 +262,10 @@ static bool runs_beside(hipStream_t owner, hipStream_t cand, int *flags) {
     int res[4] = {0, 0, 0, 0};
     // (a first launch on a new stream may pay for its queue's set-up: get that out of the way, or the owner's probe kernel
     // gives up before the candidate's has started -- the kernel below shakes hands with itself)
-    hipLaunchKernelGGL(crf_probe_kernel, dim3(1), dim3(1), 0, cand, flags + 8, 0, 0);
-    bool ran = hipStreamSynchronize(cand) == hipSuccess && hipMemset(flags, 0, sizeof(res)) == hipSuccess;
-    hipLaunchKernelGGL(crf_probe_kernel, dim3(1), dim3(1), 0, owner, flags, 0, 1);
-    hipLaunchKernelGGL(crf_probe_kernel, dim3(1), dim3(1), 0, cand, flags, 1, 0);
+    bool ran = launch<crf_probe_kernel>("crf_probe_kernel", dim3(1), dim3(1), 0, cand, flags + 8, 0, 0) == CRF_OK;
+    ran = ran && hipStreamSynchronize(cand) == hipSuccess && hipMemset(flags, 0, sizeof(res)) == hipSuccess;
+    ran = ran && launch<crf_probe_kernel>("crf_probe_kernel", dim3(1), dim3(1), 0, owner, flags, 0, 1) == CRF_OK;
+    ran = ran && launch<crf_probe_kernel>("crf_probe_kernel", dim3(1), dim3(1), 0, cand, flags, 1, 0) == CRF_OK;
     ran = ran && hipStreamSynchronize(cand) == hipSuccess && hipStreamSynchronize(owner) == hipSuccess &&
           hipMemcpy(res, flags, sizeof(res), hipMemcpyDeviceToHost) == hipSuccess;
     if (!ran) (void)hipGetLastError();
@@ -337,6 +362,22 @@ static int get_ctx(hipStream_t owner, DevCtx **out) {
     return CRF_OK;
 }
 
+// A context whose probe found no stream beside the caller's (a device shared with another busy process at that moment can make the
+// two single-wave probe kernels miss each other) asks again every 256 calls instead of staying on the serial schedule for good.
+// (at most three more probes, at calls 256, 1 024 and 4 096: a process that cannot have a second queue at all -- GPU_MAX_HW_QUEUES=1 --
+// must not pay a dozen candidates' time-outs every 256 steps for the rest of the run; never while the caller's stream is being captured)
+static void reprobe_side(DevCtx *cx, hipStream_t stream) {
+    if (cx->side || !cx->flags || opt_on(kOpt_no_side_stream) || opt_on(kOpt_trust_side) || cx->reprobes >= 3 ||
+        cx->call_id + 1 != (256 << (2 * cx->reprobes))) return;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
+    ++cx->reprobes;
+    if (cap != hipStreamCaptureStatusNone) return;
+    (void)hipStreamSynchronize(stream);
+    cx->side = find_beside(stream, cx->flags, cx->dev, &cx->side_kind, &cx->side_tries);
+    snprintf(cx->side_desc, sizeof(cx->side_desc), "%s (candidate %d, found at call %d)", kSideNames[cx->side_kind], cx->side_tries, cx->call_id + 1);
+}
+
 // Grids whose workgroups WAIT FOR EACH OTHER (layouts over K > 1 CUs per recursion: every workgroup of a launch spins on its
 // peers) are sized to fill the device; two callers enqueueing such grids on different streams at once could each become
 // partially resident and wait for peers that are not (the bounded spins would then time out into the error word).  They are
@@ -359,18 +400,6 @@ struct CoresGuard {
     }
 };
 
-// Dynamic LDS above 64 KiB must be opted into per kernel AND per device (hipFuncSetAttribute acts on the current
-// device's copy of the function): high-water mark per device.
-struct LdsMark { std::atomic<size_t> v[kMaxDev]; };
-static int ensure_lds(const void *fn, size_t bytes, LdsMark &m, const char *what) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) { set_error("hipGetDevice failed"); return CRF_ERR_HIP; }
-    if (bytes <= m.v[dev].load()) return CRF_OK;
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) { set_error(std::string("hipFuncSetAttribute(") + what + "): " + hipGetErrorString(e)); return CRF_ERR_HIP; }
-    m.v[dev] = bytes;
-    return CRF_OK;
-}
 
 // optional per-kernel timing (crf_profile_enable / crf_profile_read)
 struct Prof {
@@ -396,68 +425,42 @@ static void prof_mark(int slot, bool stop, hipStream_t st) {
 // streaming denominator recursions, forward + backward in one grid (profile slots 1 and 2 both time this launch)
 template <bool GV>
 static int launch_den_pair(const LossParams &p, size_t lds, hipStream_t st) {
-    static LdsMark mark;
-    int rc;
-    if ((rc = ensure_lds((const void *)crf_den_pair_kernel<GV>, lds, mark, "den pair"))) return rc;
     g_den_kernel = GV ? "crf_den_pair_kernel<true>" : "crf_den_pair_kernel<false>";
     prof_mark(1, false, st); prof_mark(2, false, st);
-    hipLaunchKernelGGL((crf_den_pair_kernel<GV>), dim3((unsigned)(2 * p.B)), dim3(kChainThreads), lds, st, p);
+    const int rc = launch<crf_den_pair_kernel<GV>>("crf_den_pair_kernel", dim3((unsigned)(2 * p.B)), dim3(kChainThreads), lds, st, p);
     prof_mark(1, true, st); prof_mark(2, true, st);
-    hipError_t e;
-    if ((e = hipGetLastError()) != hipSuccess) { set_error(std::string("crf_den_pair_kernel: ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
-    return CRF_OK;
+    return rc;
 }
 // numerator chains, forward + backward in one grid (profile slots 3 and 4); states per thread from the longest label sequence
-template <int NR>
-static int launch_ctc_pair_nr(const LossParams &p, size_t lds, hipStream_t st) {
-    static LdsMark mark;
-    int rc;
-    if ((rc = ensure_lds((const void *)crf_ctc_pair_kernel<NR>, lds, mark, "ctc pair"))) return rc;
-    prof_mark(3, false, st); prof_mark(4, false, st);
-    hipLaunchKernelGGL((crf_ctc_pair_kernel<NR>), dim3((unsigned)(2 * p.B)), dim3(kCtcThreads), lds, st, p);
-    prof_mark(3, true, st); prof_mark(4, true, st);
-    hipError_t e;
-    if ((e = hipGetLastError()) != hipSuccess) { set_error(std::string("crf_ctc_pair_kernel: ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
-    return CRF_OK;
-}
 static int launch_ctc_pair(const LossParams &p, size_t lds, hipStream_t st, int64_t max_label_len) {
     const int64_t ni = (2 * max_label_len + 1 + kCtcThreads - 1) / kCtcThreads;
-    int rc;
-    if (ni <= 1) rc = launch_ctc_pair_nr<1>(p, lds, st);
-    else if (ni <= 2) rc = launch_ctc_pair_nr<2>(p, lds, st);
-    else if (ni <= 4) rc = launch_ctc_pair_nr<4>(p, lds, st);
-    else rc = launch_ctc_pair_nr<kCtcRegs>(p, lds, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(crf_ctc_check_kernel, dim3((unsigned)p.B), dim3(256), 0, st, p);
-    if (hipGetLastError() != hipSuccess) { set_error("crf_ctc_check_kernel"); return CRF_ERR_HIP; }
-    return CRF_OK;
+    const dim3 grid((unsigned)(2 * p.B)), block(kCtcThreads);
+    prof_mark(3, false, st); prof_mark(4, false, st);
+    const int rc = ni <= 1 ? launch<crf_ctc_pair_kernel<1>>("crf_ctc_pair_kernel", grid, block, lds, st, p)
+                 : ni <= 2 ? launch<crf_ctc_pair_kernel<2>>("crf_ctc_pair_kernel", grid, block, lds, st, p)
+                 : ni <= 4 ? launch<crf_ctc_pair_kernel<4>>("crf_ctc_pair_kernel", grid, block, lds, st, p)
+                           : launch<crf_ctc_pair_kernel<kCtcRegs>>("crf_ctc_pair_kernel", grid, block, lds, st, p);
+    prof_mark(3, true, st); prof_mark(4, true, st);
+    return rc ? rc : launch<crf_ctc_check_kernel>("crf_ctc_check_kernel", dim3((unsigned)p.B), dim3(256), 0, st, p);
 }
 
 // forced alignment (k_align.hip): one workgroup per utterance, states per thread from the longest label sequence as for the chains
-template <int NR, typename E, bool LSE>
-static int launch_align_nr(const AlignParams &p, hipStream_t st) {
-    hipLaunchKernelGGL((crf_ctc_align_kernel<NR, E, LSE>), dim3((unsigned)p.B), dim3(kCtcThreads), 0, st, p);
-    hipError_t e;
-    if ((e = hipGetLastError()) != hipSuccess) { set_error(std::string("crf_ctc_align_kernel: ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
-    return CRF_OK;
-}
 template <typename E = float, bool LSE = false>
 static int launch_align(const AlignParams &p, hipStream_t st, int64_t max_label_len) {
     const int64_t ni = (2 * max_label_len + 1 + kCtcThreads - 1) / kCtcThreads;
-    if (ni <= 1) return launch_align_nr<1, E, LSE>(p, st);
-    if (ni <= 2) return launch_align_nr<2, E, LSE>(p, st);
-    if (ni <= 4) return launch_align_nr<4, E, LSE>(p, st);
-    return launch_align_nr<kCtcRegs, E, LSE>(p, st);
+    const dim3 grid((unsigned)p.B), block(kCtcThreads);
+    if (ni <= 1) return launch<crf_ctc_align_kernel<1, E, LSE>>("crf_ctc_align_kernel", grid, block, 0, st, p);
+    if (ni <= 2) return launch<crf_ctc_align_kernel<2, E, LSE>>("crf_ctc_align_kernel", grid, block, 0, st, p);
+    if (ni <= 4) return launch<crf_ctc_align_kernel<4, E, LSE>>("crf_ctc_align_kernel", grid, block, 0, st, p);
+    return launch<crf_ctc_align_kernel<kCtcRegs, E, LSE>>("crf_ctc_align_kernel", grid, block, 0, st, p);
 }
 // raw network output: the frames' lse values first (G lanes per frame), then the alignment on the upcast values, on the same stream
 template <typename E>
 static int launch_align_logits(const AlignParams &p, hipStream_t st, int64_t max_label_len) {
     const int64_t frames = (int64_t)p.B * p.T;
-    if (p.V <= kAlnLseSmallV) hipLaunchKernelGGL((crf_align_lse_kernel<16, E>), dim3((unsigned)((frames + 15) / 16)), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((crf_align_lse_kernel<64, E>), dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, st, p);
-    hipError_t e;
-    if ((e = hipGetLastError()) != hipSuccess) { set_error(std::string("crf_align_lse_kernel: ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
-    return launch_align<E, true>(p, st, max_label_len);
+    const int rc = p.V <= kAlnLseSmallV ? launch<crf_align_lse_kernel<16, E>>("crf_align_lse_kernel", dim3((unsigned)((frames + 15) / 16)), dim3(256), 0, st, p)
+                                        : launch<crf_align_lse_kernel<64, E>>("crf_align_lse_kernel", dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, st, p);
+    return rc ? rc : launch_align<E, true>(p, st, max_label_len);
 }
 // its workspace: the back-pointer words [B][ceil(T / kAlnFrames)][2 * max_label_len + 1 rounded up to 64]; < 0 with the message set
 static int64_t align_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t max_label_len) {
@@ -486,15 +489,8 @@ static ResParams res_params(const LossParams &lp, int dir, int b0) {
 }
 // generic register-resident recursions of the utterances [b0, b0 + nb): 2 * nb * K workgroups, forward first
 static int launch_res_pair(const LossParams &lp, size_t lds, int b0, int nb, hipStream_t st) {
-    static LdsMark mark;
-    int rc;
-    if ((rc = ensure_lds((const void *)crf_res_pair_kernel, lds, mark, "res pair"))) return rc;
-    g_den_kernel = "crf_res_pair_kernel";
     const ResParams pf = res_params(lp, 0, b0), pb = res_params(lp, 1, b0);
-    hipLaunchKernelGGL(crf_res_pair_kernel, dim3((unsigned)(2 * nb * lp.g.res.K)), dim3(kResThreads), lds, st, pf, pb);
-    hipError_t e;
-    if ((e = hipGetLastError()) != hipSuccess) { set_error(std::string("crf_res_pair_kernel: ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
-    return CRF_OK;
+    return launch<crf_res_pair_kernel>(g_den_kernel = "crf_res_pair_kernel", dim3((unsigned)(2 * nb * lp.g.res.K)), dim3(kResThreads), lds, st, pf, pb);
 }
 
 static size_t fac_lds_bytes(const HostGraph *h, int V, int dir) {
@@ -559,144 +555,103 @@ static FacParams fac_params(const LossParams &lp, int dir, int *started, int i0,
 // factored recursions over TWO CUs each, utterances [b0, b0 + nbu): every workgroup of a launch must be resident at once
 // (its peer spins on it), so the caller launches groups of at most CUs / 4 utterances
 static int launch_fac2_pair(const LossParams &lp, size_t lds, hipStream_t st, int b0, int nbu) {
-    static LdsMark mk;
     FacParams pf = fac_params(lp, 0, nullptr, 0, lp.T, nullptr, 0, nullptr, nullptr);
     FacParams pb = fac_params(lp, 1, nullptr, 0, lp.T, nullptr, 0, nullptr, nullptr);
     pf.b0 = pb.b0 = b0; pf.nbu = pb.nbu = nbu;
-    int rc;
-    if (lp.g.fac.threads == kFac4Threads) {   // 1024 threads x 15 chunks, four waves per SIMD (round 4)
-        static LdsMark mk4;
-        auto *k4 = crf_fac2_pair_kernel<kFac4Threads, kFac4NCH, CRF_FAC4_NB_ML, CRF_FAC4_NB_ML>;
-        g_den_kernel = "crf_fac2_pair_kernel<1024,15," CRF_STR(CRF_FAC4_NB_ML) "," CRF_STR(CRF_FAC4_NB_ML) ">";
-        if ((rc = ensure_lds((const void *)k4, lds, mk4, "fac2 pair"))) return rc;
-        hipLaunchKernelGGL(k4, dim3((unsigned)(2 * nbu * 2)), dim3(kFac4Threads), lds, st, pf, pb);
-    } else {
-        auto *k = crf_fac2_pair_kernel<kFac3Threads, kFac3ArcCh, CRF_FAC3_NB_F, CRF_FAC3_NB_B>;
-        g_den_kernel = "crf_fac2_pair_kernel<768,20,4,4>";
-        if ((rc = ensure_lds((const void *)k, lds, mk, "fac2 pair"))) return rc;
-        hipLaunchKernelGGL(k, dim3((unsigned)(2 * nbu * 2)), dim3(kFac3Threads), lds, st, pf, pb);
-    }
-    hipError_t e;
-    if ((e = hipGetLastError()) != hipSuccess) { set_error(std::string("crf_fac2_pair_kernel: ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
-    return CRF_OK;
+    const dim3 grid((unsigned)(2 * nbu * 2));
+    if (lp.g.fac.threads == kFac4Threads)   // 1024 threads x 15 chunks, four waves per SIMD (round 4)
+        return launch<crf_fac2_pair_kernel<kFac4Threads, kFac4NCH, CRF_FAC4_NB_ML, CRF_FAC4_NB_ML>>(
+            g_den_kernel = "crf_fac2_pair_kernel<1024,15," CRF_STR(CRF_FAC4_NB_ML) "," CRF_STR(CRF_FAC4_NB_ML) ">", grid, dim3(kFac4Threads), lds, st, pf, pb);
+    return launch<crf_fac2_pair_kernel<kFac3Threads, kFac3ArcCh, CRF_FAC3_NB_F, CRF_FAC3_NB_B>>(
+        g_den_kernel = "crf_fac2_pair_kernel<768,20,4,4>", grid, dim3(kFac3Threads), lds, st, pf, pb);
 }
+// (a den kernel's name as crf_last_den_kernel reports it: the kernel, FLAG, the other template arguments as written at the instantiation)
+#define CRF_DEN_NAME(KERNEL_, ARGS_) (FLAG ? KERNEL_ "<true," ARGS_ ">" : KERNEL_ "<false," ARGS_ ">")
 // factored recursions, iterations [i0, i1) of both directions as one grid of 2B workgroups; FLAG: publish stage counters
 // (both directions bump the same counters: a stage is complete at 2B) and store the rows write-through
 template <bool FLAG>
 static int launch_fac_pair(const LossParams &lp, size_t lds, hipStream_t st, int *started, int i0, int i1, float *fstate, float *bstate,
                            int nb = 0, const int *bound = nullptr, int *stage_cnt = nullptr) {
-    static LdsMark m3, m3m, m5;
     const FacDev &F = lp.g.fac;
-    const bool g3 = F.threads == kFac3Threads, ml = F.multilane != 0;
+    const bool g3 = F.threads == kFac3Threads, ml = F.multilane != 0, adt = F.addtid != 0;
     const FacParams pf = fac_params(lp, 0, started, i0, i1, fstate, nb, bound, stage_cnt);
     const FacParams pb = fac_params(lp, 1, started, i0, i1, bstate, nb, bound, stage_cnt);
-    const dim3 grid((unsigned)(2 * lp.B));
-    int rc;
-#define CRF_LAUNCH_RL(NCH_, ML_, NAME_, MARK_)                                                                                   \
-    {                                                                                                                           \
-        static LdsMark MARK_;                                                                                                   \
-        auto *k = crf_fac_pair_kernel<FLAG, kFac3Threads, NCH_, CRF_FAC3_NB_F, CRF_FAC3_NB_B, ML_, true>;                       \
-        g_den_kernel = FLAG ? "crf_fac_pair_kernel<true,768," NAME_ ",true>" : "crf_fac_pair_kernel<false,768," NAME_ ",true>"; \
-        if ((rc = ensure_lds((const void *)k, lds, MARK_, "fac pair"))) return rc;                                              \
-        hipLaunchKernelGGL(k, grid, dim3(kFac3Threads), lds, st, pf, pb);                                                       \
-    }
-    // row constants in the LDS table: 20 chunks of arcs per thread (F.rcl == 1), or all 21 slots (== 2: graphs that need them)
-    if (g3 && F.rcl == 1 && !ml) CRF_LAUNCH_RL(kFac3ArcCh, false, "20,4,4,false", mk20n)
-    else if (g3 && F.rcl == 1) CRF_LAUNCH_RL(kFac3ArcCh, true, "20,4,4,true", mk20m)
-    else if (g3 && F.rcl == 2 && !ml) CRF_LAUNCH_RL(kFac3LNCH, false, "21,4,4,false", mk21n)
-    else if (g3 && F.rcl == 2) CRF_LAUNCH_RL(kFac3LNCH, true, "21,4,4,true", mk21m)
-#undef CRF_LAUNCH_RL
-    else if (F.threads == kFac4Threads) {   // 1024 threads: four waves per SIMD (the planner's first choice)
-        // (the last template argument: next-vector stores by ds_write_addtid_b32, the planner's choice per graph -- FacDev::addtid)
-#define CRF_LAUNCH_1024(ML_, ADT_, NB_, MARK_)                                                                                  \
-    {                                                                                                                           \
-        static LdsMark MARK_;                                                                                                   \
-        auto *k = crf_fac_pair_kernel<FLAG, kFac4Threads, kFac4NCH, NB_, NB_, ML_, true, ADT_>;                                 \
-        g_den_kernel = FLAG ? "crf_fac_pair_kernel<true,1024," CRF_STR(CRF_FAC4_NCH) "," CRF_STR(NB_) "," CRF_STR(NB_) "," #ML_ ",true," #ADT_ ">"  \
-                            : "crf_fac_pair_kernel<false,1024," CRF_STR(CRF_FAC4_NCH) "," CRF_STR(NB_) "," CRF_STR(NB_) "," #ML_ ",true," #ADT_ ">"; \
-        if ((rc = ensure_lds((const void *)k, lds, MARK_, "fac pair"))) return rc;                                              \
-        hipLaunchKernelGGL(k, grid, dim3(kFac4Threads), lds, st, pf, pb);                                                       \
-    }
-        const bool adt = F.addtid != 0;
-        if (ml && adt) CRF_LAUNCH_1024(true, true, CRF_FAC4_NB_ML, m4ma)
-        else if (ml) CRF_LAUNCH_1024(true, false, CRF_FAC4_NB_ML, m4m)
-        else if (adt) CRF_LAUNCH_1024(false, true, CRF_FAC4_NB, m4na)
-        else CRF_LAUNCH_1024(false, false, CRF_FAC4_NB, m4n)
-#undef CRF_LAUNCH_1024
-    }
-    else if (g3 && ml) {
-        auto *k = crf_fac_pair_kernel<FLAG, kFac3Threads, kFac3NCH, CRF_FAC3_NB_F, CRF_FAC3_NB_B, true>;
-        g_den_kernel = FLAG ? "crf_fac_pair_kernel<true,768,21,4,4,true,false>" : "crf_fac_pair_kernel<false,768,21,4,4,true,false>";
-        if ((rc = ensure_lds((const void *)k, lds, m3m, "fac pair"))) return rc;
-        hipLaunchKernelGGL(k, grid, dim3(kFac3Threads), lds, st, pf, pb);
-    } else if (g3) {
-        auto *k = crf_fac_pair_kernel<FLAG, kFac3Threads, kFac3NCH, CRF_FAC3_NB_F, CRF_FAC3_NB_B, false>;
-        g_den_kernel = FLAG ? "crf_fac_pair_kernel<true,768,21,4,4,false,false>" : "crf_fac_pair_kernel<false,768,21,4,4,false,false>";
-        if ((rc = ensure_lds((const void *)k, lds, m3, "fac pair"))) return rc;
-        hipLaunchKernelGGL(k, grid, dim3(kFac3Threads), lds, st, pf, pb);
-    } else {
-        auto *k = crf_fac_pair_kernel<FLAG, kResThreads, kResNCH, kResBatch, kResBatch, true>;
-        g_den_kernel = FLAG ? "crf_fac_pair_kernel<true,512,30,6,6,true,false>" : "crf_fac_pair_kernel<false,512,30,6,6,true,false>";
-        if ((rc = ensure_lds((const void *)k, lds, m5, "fac pair"))) return rc;
-        hipLaunchKernelGGL(k, grid, dim3(kResThreads), lds, st, pf, pb);
-    }
-    hipError_t e;
-    if ((e = hipGetLastError()) != hipSuccess) { set_error(std::string("crf_fac_pair_kernel: ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
-    return CRF_OK;
+    const dim3 grid((unsigned)(2 * lp.B)), b3(kFac3Threads), b4(kFac4Threads);
+    // 768 threads, row constants in the LDS table: 20 chunks of arcs per thread (F.rcl == 1), or all 21 slots (== 2: graphs that need them)
+    if (g3 && F.rcl == 1 && !ml)
+        return launch<crf_fac_pair_kernel<FLAG, kFac3Threads, kFac3ArcCh, CRF_FAC3_NB_F, CRF_FAC3_NB_B, false, true>>(
+            g_den_kernel = CRF_DEN_NAME("crf_fac_pair_kernel", "768,20,4,4,false,true"), grid, b3, lds, st, pf, pb);
+    if (g3 && F.rcl == 1)
+        return launch<crf_fac_pair_kernel<FLAG, kFac3Threads, kFac3ArcCh, CRF_FAC3_NB_F, CRF_FAC3_NB_B, true, true>>(
+            g_den_kernel = CRF_DEN_NAME("crf_fac_pair_kernel", "768,20,4,4,true,true"), grid, b3, lds, st, pf, pb);
+    if (g3 && F.rcl == 2 && !ml)
+        return launch<crf_fac_pair_kernel<FLAG, kFac3Threads, kFac3LNCH, CRF_FAC3_NB_F, CRF_FAC3_NB_B, false, true>>(
+            g_den_kernel = CRF_DEN_NAME("crf_fac_pair_kernel", "768,21,4,4,false,true"), grid, b3, lds, st, pf, pb);
+    if (g3 && F.rcl == 2)
+        return launch<crf_fac_pair_kernel<FLAG, kFac3Threads, kFac3LNCH, CRF_FAC3_NB_F, CRF_FAC3_NB_B, true, true>>(
+            g_den_kernel = CRF_DEN_NAME("crf_fac_pair_kernel", "768,21,4,4,true,true"), grid, b3, lds, st, pf, pb);
+    // 1024 threads: four waves per SIMD (the planner's first choice)
+    // (the last template argument: next-vector stores by ds_write_addtid_b32, the planner's choice per graph -- FacDev::addtid)
+    if (F.threads == kFac4Threads && ml && adt)
+        return launch<crf_fac_pair_kernel<FLAG, kFac4Threads, kFac4NCH, CRF_FAC4_NB_ML, CRF_FAC4_NB_ML, true, true, true>>(
+            g_den_kernel = CRF_DEN_NAME("crf_fac_pair_kernel", "1024," CRF_STR(CRF_FAC4_NCH) "," CRF_STR(CRF_FAC4_NB_ML) "," CRF_STR(CRF_FAC4_NB_ML) ",true,true,true"), grid, b4, lds, st, pf, pb);
+    if (F.threads == kFac4Threads && ml)
+        return launch<crf_fac_pair_kernel<FLAG, kFac4Threads, kFac4NCH, CRF_FAC4_NB_ML, CRF_FAC4_NB_ML, true, true, false>>(
+            g_den_kernel = CRF_DEN_NAME("crf_fac_pair_kernel", "1024," CRF_STR(CRF_FAC4_NCH) "," CRF_STR(CRF_FAC4_NB_ML) "," CRF_STR(CRF_FAC4_NB_ML) ",true,true,false"), grid, b4, lds, st, pf, pb);
+    if (F.threads == kFac4Threads && adt)
+        return launch<crf_fac_pair_kernel<FLAG, kFac4Threads, kFac4NCH, CRF_FAC4_NB, CRF_FAC4_NB, false, true, true>>(
+            g_den_kernel = CRF_DEN_NAME("crf_fac_pair_kernel", "1024," CRF_STR(CRF_FAC4_NCH) "," CRF_STR(CRF_FAC4_NB) "," CRF_STR(CRF_FAC4_NB) ",false,true,true"), grid, b4, lds, st, pf, pb);
+    if (F.threads == kFac4Threads)
+        return launch<crf_fac_pair_kernel<FLAG, kFac4Threads, kFac4NCH, CRF_FAC4_NB, CRF_FAC4_NB, false, true, false>>(
+            g_den_kernel = CRF_DEN_NAME("crf_fac_pair_kernel", "1024," CRF_STR(CRF_FAC4_NCH) "," CRF_STR(CRF_FAC4_NB) "," CRF_STR(CRF_FAC4_NB) ",false,true,false"), grid, b4, lds, st, pf, pb);
+    // 768 threads, row constants in registers
+    if (g3 && ml)
+        return launch<crf_fac_pair_kernel<FLAG, kFac3Threads, kFac3NCH, CRF_FAC3_NB_F, CRF_FAC3_NB_B, true>>(
+            g_den_kernel = CRF_DEN_NAME("crf_fac_pair_kernel", "768,21,4,4,true,false"), grid, b3, lds, st, pf, pb);
+    if (g3)
+        return launch<crf_fac_pair_kernel<FLAG, kFac3Threads, kFac3NCH, CRF_FAC3_NB_F, CRF_FAC3_NB_B, false>>(
+            g_den_kernel = CRF_DEN_NAME("crf_fac_pair_kernel", "768,21,4,4,false,false"), grid, b3, lds, st, pf, pb);
+    return launch<crf_fac_pair_kernel<FLAG, kResThreads, kResNCH, kResBatch, kResBatch, true>>(
+        g_den_kernel = CRF_DEN_NAME("crf_fac_pair_kernel", "512,30,6,6,true,false"), grid, dim3(kResThreads), lds, st, pf, pb);
 }
 
 // ... two utterances per workgroup: 2 * ceil(B / 2) workgroups
 template <bool FLAG>
 static int launch_fac_pair2(const LossParams &lp, size_t lds, hipStream_t st, int *started, int nb = 0, const int *bound = nullptr, int *stage_cnt = nullptr) {
-    static LdsMark m2, m2m;
     const FacDev &F = lp.g.fac;
     const bool ml = F.multilane != 0;
     const FacParams pf = fac_params(lp, 0, started, 0, lp.T, nullptr, nb, bound, stage_cnt);
     const FacParams pb = fac_params(lp, 1, started, 0, lp.T, nullptr, nb, bound, stage_cnt);
-    const dim3 grid((unsigned)(2 * pf.npair));
-    int rc;
-#define CRF_LAUNCH_RL2(NCH_, ML_, NAME_, MARK_)                                                                                 \
-    {                                                                                                                           \
-        static LdsMark MARK_;                                                                                                   \
-        auto *k = crf_fac_pair2_kernel<FLAG, kFac3Threads, NCH_, CRF_FAC3_NB2, CRF_FAC3_NB2, ML_, true>;                        \
-        g_den_kernel = FLAG ? "crf_fac_pair2_kernel<true,768," NAME_ ",true>" : "crf_fac_pair2_kernel<false,768," NAME_ ",true>"; \
-        if ((rc = ensure_lds((const void *)k, lds, MARK_, "fac pair2"))) return rc;                                             \
-        hipLaunchKernelGGL(k, grid, dim3(kFac3Threads), lds, st, pf, pb);                                                       \
-    }
-#define CRF_LAUNCH_P512(ML_, NAME_, MARK_)                                                                                      \
-    {                                                                                                                           \
-        static LdsMark MARK_;                                                                                                   \
-        auto *k = crf_fac_pair2_kernel<FLAG, kResThreads, kResNCH, CRF_FAC5_NB2, CRF_FAC5_NB2, ML_, true>;                      \
-        g_den_kernel = FLAG ? "crf_fac_pair2_kernel<true,512,30," NAME_ ",true>" : "crf_fac_pair2_kernel<false,512,30," NAME_ ",true>"; \
-        if ((rc = ensure_lds((const void *)k, lds, MARK_, "fac pair2"))) return rc;                                             \
-        hipLaunchKernelGGL(k, grid, dim3(kResThreads), lds, st, pf, pb);                                                        \
-    }
+    const dim3 grid((unsigned)(2 * pf.npair)), b3(kFac3Threads);
     if (F.threads == kResThreads) {   // the second layout (HostGraph::facp): 512 threads x 30 chunks, row table, implicit entries
         if (!F.imp || !F.rcl) { set_error("two-utterance kernel on 512 threads: not the second layout"); return CRF_ERR_ARG; }
-        if (!ml) CRF_LAUNCH_P512(false, CRF_STR(CRF_FAC5_NB2) "," CRF_STR(CRF_FAC5_NB2) ",false", mp512n)
-        else CRF_LAUNCH_P512(true, CRF_STR(CRF_FAC5_NB2) "," CRF_STR(CRF_FAC5_NB2) ",true", mp512m)
-    } else
-    if (F.rcl == 1 && !ml) CRF_LAUNCH_RL2(kFac3ArcCh, false, "20," CRF_STR(CRF_FAC3_NB2) "," CRF_STR(CRF_FAC3_NB2) ",false", mp20n)
-    else if (F.rcl == 1) CRF_LAUNCH_RL2(kFac3ArcCh, true, "20," CRF_STR(CRF_FAC3_NB2) "," CRF_STR(CRF_FAC3_NB2) ",true", mp20m)
-    else if (F.rcl == 2 && !ml) CRF_LAUNCH_RL2(kFac3LNCH, false, "21," CRF_STR(CRF_FAC3_NB2) "," CRF_STR(CRF_FAC3_NB2) ",false", mp21n)
-    else if (F.rcl == 2) CRF_LAUNCH_RL2(kFac3LNCH, true, "21," CRF_STR(CRF_FAC3_NB2) "," CRF_STR(CRF_FAC3_NB2) ",true", mp21m)
-#undef CRF_LAUNCH_RL2
-#undef CRF_LAUNCH_P512
-    else if (ml) {
-        auto *k = crf_fac_pair2_kernel<FLAG, kFac3Threads, kFac3NCH, CRF_FAC3_NB2, CRF_FAC3_NB2, true, false>;
-        g_den_kernel = FLAG ? "crf_fac_pair2_kernel<true,768,21," CRF_STR(CRF_FAC3_NB2) "," CRF_STR(CRF_FAC3_NB2) ",true,false>" : "crf_fac_pair2_kernel<false,768,21," CRF_STR(CRF_FAC3_NB2) "," CRF_STR(CRF_FAC3_NB2) ",true,false>";
-        if ((rc = ensure_lds((const void *)k, lds, m2m, "fac pair2"))) return rc;
-        hipLaunchKernelGGL(k, grid, dim3(kFac3Threads), lds, st, pf, pb);
-    } else {
-        auto *k = crf_fac_pair2_kernel<FLAG, kFac3Threads, kFac3NCH, CRF_FAC3_NB2, CRF_FAC3_NB2, false, false>;
-        g_den_kernel = FLAG ? "crf_fac_pair2_kernel<true,768,21," CRF_STR(CRF_FAC3_NB2) "," CRF_STR(CRF_FAC3_NB2) ",false,false>" : "crf_fac_pair2_kernel<false,768,21," CRF_STR(CRF_FAC3_NB2) "," CRF_STR(CRF_FAC3_NB2) ",false,false>";
-        if ((rc = ensure_lds((const void *)k, lds, m2, "fac pair2"))) return rc;
-        hipLaunchKernelGGL(k, grid, dim3(kFac3Threads), lds, st, pf, pb);
+        if (!ml)
+            return launch<crf_fac_pair2_kernel<FLAG, kResThreads, kResNCH, CRF_FAC5_NB2, CRF_FAC5_NB2, false, true>>(
+                g_den_kernel = CRF_DEN_NAME("crf_fac_pair2_kernel", "512,30," CRF_STR(CRF_FAC5_NB2) "," CRF_STR(CRF_FAC5_NB2) ",false,true"), grid, dim3(kResThreads), lds, st, pf, pb);
+        return launch<crf_fac_pair2_kernel<FLAG, kResThreads, kResNCH, CRF_FAC5_NB2, CRF_FAC5_NB2, true, true>>(
+            g_den_kernel = CRF_DEN_NAME("crf_fac_pair2_kernel", "512,30," CRF_STR(CRF_FAC5_NB2) "," CRF_STR(CRF_FAC5_NB2) ",true,true"), grid, dim3(kResThreads), lds, st, pf, pb);
     }
-    hipError_t e;
-    if ((e = hipGetLastError()) != hipSuccess) { set_error(std::string("crf_fac_pair2_kernel: ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
-    return CRF_OK;
+    // 768 threads: row constants in the LDS table (20 chunks of arcs, or all 21 slots), else in registers
+    if (F.rcl == 1 && !ml)
+        return launch<crf_fac_pair2_kernel<FLAG, kFac3Threads, kFac3ArcCh, CRF_FAC3_NB2, CRF_FAC3_NB2, false, true>>(
+            g_den_kernel = CRF_DEN_NAME("crf_fac_pair2_kernel", "768,20," CRF_STR(CRF_FAC3_NB2) "," CRF_STR(CRF_FAC3_NB2) ",false,true"), grid, b3, lds, st, pf, pb);
+    if (F.rcl == 1)
+        return launch<crf_fac_pair2_kernel<FLAG, kFac3Threads, kFac3ArcCh, CRF_FAC3_NB2, CRF_FAC3_NB2, true, true>>(
+            g_den_kernel = CRF_DEN_NAME("crf_fac_pair2_kernel", "768,20," CRF_STR(CRF_FAC3_NB2) "," CRF_STR(CRF_FAC3_NB2) ",true,true"), grid, b3, lds, st, pf, pb);
+    if (F.rcl == 2 && !ml)
+        return launch<crf_fac_pair2_kernel<FLAG, kFac3Threads, kFac3LNCH, CRF_FAC3_NB2, CRF_FAC3_NB2, false, true>>(
+            g_den_kernel = CRF_DEN_NAME("crf_fac_pair2_kernel", "768,21," CRF_STR(CRF_FAC3_NB2) "," CRF_STR(CRF_FAC3_NB2) ",false,true"), grid, b3, lds, st, pf, pb);
+    if (F.rcl == 2)
+        return launch<crf_fac_pair2_kernel<FLAG, kFac3Threads, kFac3LNCH, CRF_FAC3_NB2, CRF_FAC3_NB2, true, true>>(
+            g_den_kernel = CRF_DEN_NAME("crf_fac_pair2_kernel", "768,21," CRF_STR(CRF_FAC3_NB2) "," CRF_STR(CRF_FAC3_NB2) ",true,true"), grid, b3, lds, st, pf, pb);
+    if (ml)
+        return launch<crf_fac_pair2_kernel<FLAG, kFac3Threads, kFac3NCH, CRF_FAC3_NB2, CRF_FAC3_NB2, true, false>>(
+            g_den_kernel = CRF_DEN_NAME("crf_fac_pair2_kernel", "768,21," CRF_STR(CRF_FAC3_NB2) "," CRF_STR(CRF_FAC3_NB2) ",true,false"), grid, b3, lds, st, pf, pb);
+    return launch<crf_fac_pair2_kernel<FLAG, kFac3Threads, kFac3NCH, CRF_FAC3_NB2, CRF_FAC3_NB2, false, false>>(
+        g_den_kernel = CRF_DEN_NAME("crf_fac_pair2_kernel", "768,21," CRF_STR(CRF_FAC3_NB2) "," CRF_STR(CRF_FAC3_NB2) ",false,false"), grid, b3, lds, st, pf, pb);
 }
+#undef CRF_DEN_NAME
+
 
 }  // namespace crf
 
@@ -881,71 +836,186 @@ int crf_ctc_align_logits(const void *act, int dtype, int time_major, int blank, 
     return launch_align_logits<AlnF16>(p, (hipStream_t)stream_, max_label_len);
 }
 
-static int loss_impl(const crf_graph *g, const float *logp, int fused, int in_dtype, const int32_t *labels, const int32_t *lab_off,
-                     const int32_t *lx, const int32_t *ly, int64_t B, int64_t T, int64_t V,
-                     int64_t max_label_len, float c_den, float c_ctc, float *grad, float *loss,
-                     float *costs_den, float *costs_beta, float *costs_ctc, int32_t *invalid, void *ws,
-                     int64_t ws_bytes, void *stream_, int time_major, int blank) {
-    hipStream_t stream = (hipStream_t)stream_;
-    const bool den = c_den != 0.f, ctc = c_ctc != 0.f;
-    if (!logp || !lx || !grad || !loss || !ws) { set_error("null argument"); return CRF_ERR_ARG; }
+// ---------------------------------------------------------------------------------------------
+// The loss call in parts: the arguments are checked (check_loss_args), the kernels, LDS sizes and the schedule are chosen as data
+// (CallPlan: plan_kernels from the graph and the shape alone, plan_schedule with the facts of the device and the context), the workspace
+// is carved into LossParams (bind_params), and a LossCall enqueues one of four stream schedules -- utterance-minor, staged, two streams,
+// one stream -- followed by the fallbacks and finalize.
+// ---------------------------------------------------------------------------------------------
+struct LossArgs {
+    const crf_graph *g; const float *logp; int fused, in_dtype;
+    const int32_t *labels, *lab_off, *lx, *ly;
+    int64_t B, T, V, max_label_len;
+    float c_den, c_ctc, *grad, *loss, *costs_den, *costs_beta, *costs_ctc;
+    int32_t *invalid; void *ws; int64_t ws_bytes; int time_major, blank;
+};
+// what a call's schedule depends on beside its arguments: plain values, read once per call
+struct DevFacts {
+    int ncu = 256;            // compute units of the context's device
+    bool have_flags = false, have_side = false, have_aux = false;   // DevCtx::flags, side, aux
+    bool segments = false;    // hipStreamWaitValue32 has been refused in this process
+    bool gd_fallback = false; // DevCtx::gd_fallback
+    int call_id = 0, seen = 0;   // this call's number; the call that last ran the numerator's log-domain chains (DevCtx::seen: a racing word, ONE read per call)
+};
+struct CallPlan {
+    // kernel families and sizes, from the graph and the shape alone (plan_kernels)
+    const HostGraph *h;
+    bool den, ctc, res, gv, fac, bat;   // "res": register-resident kernels of either layout
+    const FacDev *FX;                   // the factored layout this call works with: the main one, or -- two utterances per workgroup on 512 threads -- the second one
+    bool pair2;
+    int Sc, gnc, gcap, robust_env;
+    bool grad_stage, gd_wide, gd_wide6, fast_den, fast_ctc;
+    size_t lds_den, lds_ctc, lds_grad;  // dynamic LDS of the den recursions (whichever family), the numerator chains, the generic grad kernel
+    // the schedule (plan_schedule)
+    int ncu; int64_t den_wgs; bool have_flags, serial, no_overlap, segmode, staged, per_stage, ctc_wants_aux, par3;
+    int nstage, gd_piece, bound[kMaxStages + 1];
+};
+static std::atomic<bool> g_use_segments{false};      // set when hipStreamWaitValue32 is refused
+
+static CallPlan plan_kernels(const HostGraph *h, const WsLayout &w, int64_t V, int64_t max_label_len, int Sc, bool den, bool ctc) {
+    CallPlan pl{};
+    pl.h = h; pl.den = den; pl.ctc = ctc; pl.Sc = Sc;
+    pl.res = den && w.res; pl.gv = den && w.gv; pl.fac = den && w.fac; pl.bat = den && w.bat;
+    const bool res = pl.res, gv = pl.gv, fac = pl.fac, bat = pl.bat;
+    // (ws_layout has sized the rows for the layout pair2_mode names; everything reads it through p.g.fac / FX)
+    pl.FX = fac ? (w.p2mode == 2 ? &h->facp : &h->dev.fac) : nullptr;
+    // two utterances per workgroup (use_fac_pair2): the den grid is 2 * ceil(B / 2) workgroups instead of 2 B
+    pl.pair2 = fac && w.p2mode != 0;   // (pair2_mode, decided with the workspace layout: the rows are sized for the layout it names)
+    if (den && !res && !bat) pl.lds_den = std::max(chain_lds_bytes(h, (int)V, pl.Sc, 0, gv), chain_lds_bytes(h, (int)V, pl.Sc, 1, gv));
+    if (res && !fac) pl.lds_den = std::max(res_lds_bytes(h, (int)V, 0, h->res_rows_cu_f), res_lds_bytes(h, (int)V, 1, h->res_rows_cu_b));
+    if (fac) pl.lds_den = pl.pair2 ? std::max(fac2u_lds_bytes(*pl.FX, (int)V, 0), fac2u_lds_bytes(*pl.FX, (int)V, 1))
+                                   : std::max(fac_lds_bytes(h, (int)V, 0), fac_lds_bytes(h, (int)V, 1));
+    pl.lds_ctc = chain_lds_bytes(h, (int)V, pl.Sc, 2);
+    const int gnc_all = den ? std::max(std::max(h->dev.NC, h->dev.res.NC), std::max(h->dev.fac.ok ? h->dev.fac.NC : 0, h->facp.ok ? h->facp.NC : 0)) : 0;
+    // the generic grad kernel stages the two rows of a frame in LDS when they fit, else gathers them from L2
+    pl.grad_stage = !den || bat || ((size_t)rup64((int)w.Rq) + rup64((int)w.Rb) + rup64(gnc_all) + 2 * (size_t)rup64((int)V)) * 4 <= 150 * 1024;
+    pl.lds_grad = ((den && !bat && pl.grad_stage ? (size_t)rup64((int)w.Rq) + rup64((int)w.Rb) : 0) + rup64(bat ? 0 : gnc_all) + 2 * (size_t)rup64((int)V)) * sizeof(float);
+    // The denominator half of the grad pass has a streaming kernel (index pairs in registers, rows
+    // prefetched); it needs 16-bit row indices, rows of <= kGDRowRegs*256 floats and <= 2 chunks per thread.
+    pl.gnc = den ? (fac ? pl.FX->NC : res ? h->dev.res.NC : h->dev.NC) : 0;
+    pl.gcap = fac ? pl.FX->chunk_cap : kChunk;       // entries per chunk of the grad pass's pair lists
+    pl.gd_wide = den && (w.Rq > 4 * kGDRowRegs * kGDThreads || w.Rb > 4 * kGDRowRegs * kGDThreads);   // 512-thread grad workgroups
+    // (rows of up to 12 288 floats since round 6 -- 512 threads x 6 row registers: a den_lm with a state per seen bigram history has ~5.3 k forward rows
+    // at 72 tokens, Rq = Rb = 10 752, 5 % beyond the 10 240 of five registers, and took the generic grad kernel: 10.8 ms of a 17.5 ms step)
+    pl.gd_wide6 = den && (w.Rq > 8 * kGDRowRegs * kGDThreads || w.Rb > 8 * kGDRowRegs * kGDThreads);
+    pl.fast_den = den && w.Rq <= 8 * 6 * kGDThreads && w.Rb <= 8 * 6 * kGDThreads && w.Rq % 4 == 0 && w.Rb % 4 == 0 && (!pl.gd_wide6 || (pl.gnc <= 2 * kGDThreads && pl.gcap != 8)) &&
+                  pl.gnc <= 4 * kGDThreads && V <= kGDEpRegs * kGDThreads && !opt_on(kOpt_no_fast_grad);
+    // numerator half of the grad pass: streaming kernel when the vocabulary fits its registers
+    pl.fast_ctc = ctc && V <= kGCVRegs * kGCThreads && 2 * max_label_len + 1 <= kGCRegs * kGCThreads &&
+                  !opt_on(kOpt_no_fast_grad);
+    // CRF_ROBUST: 0 = never run the robust fallback, 1 = every utterance takes it (tests, or "safe mode"); default: the
+    // utterances the fast kernels flag
+    pl.robust_env = opt(kOpt_robust, -1);   // (read per call: tests switch it)
+    return pl;
+}
+
+// every early return of a call, before any HIP call; fills the workspace layout and the device-independent part of the plan
+static int check_loss_args(const LossArgs &a, WsLayout &w, CallPlan &pl) {
+    const int64_t B = a.B, T = a.T, V = a.V;
+    const bool den = a.c_den != 0.f, ctc = a.c_ctc != 0.f;
+    if (!a.logp || !a.lx || !a.grad || !a.loss || !a.ws) { set_error("null argument"); return CRF_ERR_ARG; }
     if (B <= 0 || T <= 0 || V <= 0 || B * T > INT32_MAX) { set_error("bad B/T/V"); return CRF_ERR_ARG; }
     if (!den && !ctc) { set_error("c_den and c_ctc are both zero"); return CRF_ERR_ARG; }
-    if (den && (!g || !g->h)) { set_error("denominator requested without a graph"); return CRF_ERR_ARG; }
-    if (ctc && (!labels || !lab_off || !ly || max_label_len < 0)) { set_error("numerator requested without labels"); return CRF_ERR_ARG; }
+    if (den && (!a.g || !a.g->h)) { set_error("denominator requested without a graph"); return CRF_ERR_ARG; }
+    if (ctc && (!a.labels || !a.lab_off || !a.ly || a.max_label_len < 0)) { set_error("numerator requested without labels"); return CRF_ERR_ARG; }
     // The blank's column and the row layout are options of the numerator alone: a den_lm fixes the blank at 0 (label = ilabel - 1),
     // and the denominator kernels read [B][T][V] rows.  (Labels are device memory here: the callers check them.)
-    if (blank < 0 || blank >= V) { set_error("blank " + std::to_string(blank) + " outside [0, V=" + std::to_string(V) + ")"); return CRF_ERR_ARG; }
-    if (den && blank != 0) { set_error("a blank other than 0 is for numerator-only calls: a den_lm fixes the blank at 0"); return CRF_ERR_UNSUPPORTED; }
-    if (time_major && den) { set_error("time-major activations are for numerator-only calls (no den_lm)"); return CRF_ERR_UNSUPPORTED; }
-    const HostGraph *h = den ? g->h : nullptr;
+    if (a.blank < 0 || a.blank >= V) { set_error("blank " + std::to_string(a.blank) + " outside [0, V=" + std::to_string(V) + ")"); return CRF_ERR_ARG; }
+    if (den && a.blank != 0) { set_error("a blank other than 0 is for numerator-only calls: a den_lm fixes the blank at 0"); return CRF_ERR_UNSUPPORTED; }
+    if (a.time_major && den) { set_error("time-major activations are for numerator-only calls (no den_lm)"); return CRF_ERR_UNSUPPORTED; }
+    const HostGraph *h = den ? a.g->h : nullptr;
     if (den && V <= h->dev.max_label) {
         set_error("den_lm has label " + std::to_string(h->dev.max_label) + " but log_probs has only V=" + std::to_string(V) + " classes");
         return CRF_ERR_ARG;
     }
     if (V > kMaxVocab) { set_error("V > " + std::to_string(kMaxVocab) + " not supported by this build"); return CRF_ERR_UNSUPPORTED; }
-    const int Sc = rup64((int)(2 * (ctc ? max_label_len : 0) + 1));
-    if (ctc && max_label_len > kMaxCtcLabelLen) { set_error("label length > " + std::to_string(kMaxCtcLabelLen) + " not supported by this build"); return CRF_ERR_UNSUPPORTED; }
-    const WsLayout w = ws_layout(h, B, T, V, Sc);
-    if (ws_bytes < w.total) { set_error("workspace too small: need " + std::to_string(w.total)); return CRF_ERR_WORKSPACE; }
-    const bool res = den && w.res, gv = den && w.gv, fac = den && w.fac, bat = den && w.bat;
-    if (fac && T * std::max<int64_t>(V, std::max(w.Rq, w.Rb)) >= ((int64_t)1 << 32)) {   // (the factored frame loop adds 32-bit row offsets)
+    const int Sc = rup64((int)(2 * (ctc ? a.max_label_len : 0) + 1));
+    if (ctc && a.max_label_len > kMaxCtcLabelLen) { set_error("label length > " + std::to_string(kMaxCtcLabelLen) + " not supported by this build"); return CRF_ERR_UNSUPPORTED; }
+    w = ws_layout(h, B, T, V, Sc);
+    if (a.ws_bytes < w.total) { set_error("workspace too small: need " + std::to_string(w.total)); return CRF_ERR_WORKSPACE; }
+    pl = plan_kernels(h, w, V, a.max_label_len, Sc, den, ctc);
+    if (pl.fac && T * std::max<int64_t>(V, std::max(w.Rq, w.Rb)) >= ((int64_t)1 << 32)) {   // (the factored frame loop adds 32-bit row offsets)
         set_error("T * max(V, row length) >= 2^32 not supported by the factored kernels"); return CRF_ERR_UNSUPPORTED;
     }
-    size_t lds_chain = 0;
-    if (den && !res && !bat) lds_chain = std::max(chain_lds_bytes(h, (int)V, Sc, 0, gv), chain_lds_bytes(h, (int)V, Sc, 1, gv));
-    if (res && !fac) lds_chain = std::max(res_lds_bytes(h, (int)V, 0, h->res_rows_cu_f), res_lds_bytes(h, (int)V, 1, h->res_rows_cu_b));
-    if (fac) lds_chain = w.p2mode ? std::max(fac2u_lds_bytes(w.p2mode == 2 ? h->facp : h->dev.fac, (int)V, 0), fac2u_lds_bytes(w.p2mode == 2 ? h->facp : h->dev.fac, (int)V, 1))
-                                  : std::max(fac_lds_bytes(h, (int)V, 0), fac_lds_bytes(h, (int)V, 1));
-    if (ctc) lds_chain = std::max(lds_chain, chain_lds_bytes(h, (int)V, Sc, 2));
-    const int gnc_all = den ? std::max(std::max(h->dev.NC, h->dev.res.NC), std::max(h->dev.fac.ok ? h->dev.fac.NC : 0, h->facp.ok ? h->facp.NC : 0)) : 0;
-    // the generic grad kernel stages the two rows of a frame in LDS when they fit, else gathers them from L2
-    const bool grad_stage = !den || bat || ((size_t)rup64((int)w.Rq) + rup64((int)w.Rb) + rup64(gnc_all) + 2 * (size_t)rup64((int)V)) * 4 <= 150 * 1024;
-    const size_t lds_grad = ((den && !bat && grad_stage ? (size_t)rup64((int)w.Rq) + rup64((int)w.Rb) : 0) + rup64(bat ? 0 : gnc_all) + 2 * (size_t)rup64((int)V)) * sizeof(float);
-    if (lds_chain > 160 * 1024 || lds_grad > 160 * 1024) {
+    if (std::max(pl.lds_den, ctc ? pl.lds_ctc : 0) > 160 * 1024 || pl.lds_grad > 160 * 1024) {
         set_error("graph too large for this build (states=" + std::to_string(h ? h->S : 0) + ")");
         return CRF_ERR_UNSUPPORTED;
     }
+    return CRF_OK;
+}
 
+static void plan_schedule(CallPlan &pl, int64_t B, int64_t T, const DevFacts &f) {
+    pl.ncu = f.ncu; pl.have_flags = f.have_flags;
+    pl.serial = opt_on(kOpt_serial_chains) || !f.have_side;              // no side stream: everything in order on the caller's stream
+    // Factored den kernels: 2B workgroups, one CU each.  While that is at most half of the chip, everything else
+    // runs BESIDE them on the other half, on the side stream: numerator chains, their grad half, and the den half of
+    // the grad pass.  The den half of the grad pass needs rows of BOTH recursions, which work towards each other; it
+    // is released in stages: the recursions bump a counter at every stage bound, the grad launch of stage k is queued
+    // behind a STREAM-level wait on that counter and takes the 16-frame blocks the stage completed.
+    // (A grad pass that SPINS on progress counters of the running den kernels is faster still on a quiet device,
+    // but with many launches queued ahead the den kernels were observed to stop for seconds while the waiting
+    // workgroups kept their queue busy -- one kernel must never wait for another.)
+    pl.no_overlap = opt_on(kOpt_no_overlap);   // diagnostics
+    // how stage k of the grad pass is released: a stream-level wait on a counter the running recursions bump
+    // (default), or -- CRF_SEGMENTS=1, and automatically if hipStreamWaitValue32 is refused -- by cutting the
+    // recursions into one launch per stage with an event after each (~40 us per relaunch, state parked in HBM)
+    pl.segmode = f.segments || opt_on(kOpt_segments);
+    const int stages_env = opt(kOpt_stages, 0);
+    const int pieces = stages_env > 0 ? stages_env : (pl.segmode ? 4 : 12);   // measured: 4 / 8 / 12 pieces -> call 4.06 / 3.98 / 3.93 ms (flags)
+    pl.den_wgs = pl.pair2 ? 2 * ((B + 1) / 2) : 2 * B;
+    // (the two-utterance kernel has no segment relaunches: where stream-level waits are refused it runs unstaged)
+    pl.staged = pl.fac && pl.FX->K == 1 && pl.ctc && pl.fast_den && pl.fast_ctc && !pl.serial && !pl.no_overlap && f.have_flags && !(pl.pair2 && pl.segmode) && pl.den_wgs * 100 <= (int64_t)f.ncu * opt(kOpt_stage_fill, 75);   // (B = 80: 4.16 -> 3.56 ms, B = 96: 4.37 -> 4.26, B = 112 at 90 %: 5.33 -> 5.57)
+    // Stage bounds.  Nothing can be released before the two recursions have met, so the first stage ends at half of
+    // the frames or later; after that a piece of `piece` iterations releases 2 * piece / 16 frame blocks per
+    // utterance.  The grad pass has half of the chip and is bandwidth-bound there (~2 TB/s against the 2.2 TB/s the
+    // two recursions produce), with a fixed cost per stage (launch, the workgroups' set-up, partial rounds); what is
+    // left when the recursions end is its backlog plus the last stage.  Measured (B=64, T=1500, recursions 2.95 ms):
+    // pieces of 32 / 48 / 64 / 96 / 128 / 192 / 256 / 384 iterations -> step 3.88 / 3.62 / 3.42 / 3.38 / 3.33 / 3.35 /
+    // 3.41 / 3.53 ms; pieces that shrink towards the end (256,192,128,96,64 ...) were no better than equal ones.
+    // CRF_PIECE / CRF_STAGES override (segment mode: 4 pieces, each relaunch costs ~40 us).
+    pl.nstage = 1; pl.gd_piece = 0;
+    pl.bound[1] = (int)T;
+    // (a context whose one-launch grad pass has timed out goes back to one grad launch per stage: DevCtx::gd_fallback)
+    pl.per_stage = opt_on(kOpt_gd_stage_launches) || f.gd_fallback;
+    if (pl.staged && T >= 256) pl.nstage = plan_grad_stages(T, pl.segmode, stages_env, pieces, pl.bound, &pl.gd_piece, pl.per_stage ? 1 : 0);
+    // Did a recent call need the numerator's log-domain fallback?  (the third stream costs the call ~20 us of event traffic whether or not an
+    // utterance is marked -- B = 64, T = 1 500: 3.172 -> 3.192 ms -- so it is taken when one of this context's last 16 calls ran the log-domain
+    // chains: they write the call's number to a pinned host word, read without any synchronisation, once per call; `aux_stream` 1 / 0 forces
+    // it on / off)
+    const int aux_env = opt(kOpt_aux_stream, -1);
+    pl.ctc_wants_aux = aux_env >= 0 ? aux_env != 0 : (f.seen > 0 && f.call_id - f.seen <= 16);
+    // Three streams (round 5, switch grad_par3; OFF): the numerator half of the grad pass (side stream) and the staged den half (third stream)
+    // run BESIDE each other and both ADD into gradient rows the prep kernel has zeroed (0 + x + y: two addends per element, the same bits
+    // in either order).  The idea: on one stream the stages queue behind the numerator chains and their grad half, and graphs whose
+    // recursions are shorter than that (S = 513: recursions 1.25 ms, step 1.92) wait for them.  Measured SLOWER everywhere
+    // (profiles/round5_ab_three_streams.txt: metric 2.79 -> 2.85 ms, S = 513 1.92 -> 2.01, V = 217 3.39 -> 3.51, estimated S = 3 006 2.44 -> 2.78):
+    // the stage workgroups then share the free CUs with the numerator chains -- a serial fp64 latency chain whose frames get longer -- and
+    // what the stages gain by starting early the chains lose.  Not when a recent call needed the numerator's log-domain fallback (the
+    // third stream then carries its chains), nor in segment mode.
+    pl.par3 = pl.staged && !pl.segmode && f.have_aux && !(pl.robust_env != 0 && pl.ctc_wants_aux) && opt(kOpt_grad_par3, 0) != 0;
+}
+
+// the workspace carved into the kernels' parameter block
+static LossParams bind_params(const LossArgs &a, const WsLayout &w, const CallPlan &pl, const DevCtx *cx, int call_id) {
+    const int64_t B = a.B, T = a.T, V = a.V;
+    const HostGraph *h = pl.h;
+    const bool den = pl.den, ctc = pl.ctc, res = pl.res, fac = pl.fac;
     LossParams p{};
     if (den) p.g = h->dev;
-    // the factored layout this call works with: the main one, or -- two utterances per workgroup on 512 threads -- the second one
-    // (ws_layout has sized the rows for it); everything below reads it through p.g.fac / FX
-    const FacDev *FX = (den && w.fac) ? (w.p2mode == 2 ? &h->facp : &h->dev.fac) : nullptr;
-    if (FX) p.g.fac = *FX;
-    p.logp = logp; p.labels = labels; p.lab_off = lab_off; p.lx = lx; p.ly = ly;
-    p.B = (int)B; p.T = (int)T; p.V = (int)V; p.Sc = Sc;
-    p.xs_b = time_major ? V : T * V; p.xs_t = time_major ? B * V : V;
-    p.blank = blank;
-    p.c_den = c_den; p.c_ctc = c_ctc;
-    char *base = (char *)ws;
+    if (pl.FX) p.g.fac = *pl.FX;
+    p.logp = a.logp; p.labels = a.labels; p.lab_off = a.lab_off; p.lx = a.lx; p.ly = a.ly;
+    p.B = (int)B; p.T = (int)T; p.V = (int)V; p.Sc = pl.Sc;
+    p.xs_b = a.time_major ? V : T * V; p.xs_t = a.time_major ? B * V : V;
+    p.blank = a.blank;
+    p.c_den = a.c_den; p.c_ctc = a.c_ctc;
+    char *base = (char *)a.ws;
     p.ep = (float *)(base + w.off_ep); p.mx = (float *)(base + w.off_mx);
-    p.fused = fused; p.in_dtype = in_dtype;
-    p.moff = fused ? (float *)(base + w.off_moff) : p.mx; p.inv_s = (float *)(base + w.off_invs);
+    p.fused = a.fused; p.in_dtype = a.in_dtype;
+    p.moff = a.fused ? (float *)(base + w.off_moff) : p.mx; p.inv_s = (float *)(base + w.off_invs);
     p.Q = (float *)(base + w.off_Q); p.BP = (float *)(base + w.off_BP);
-    p.Rq = (int)w.Rq; p.Rb = (int)w.Rb; p.res = fac ? 2 : res ? 1 : 0; p.grad_stage = grad_stage ? 1 : 0;
+    p.Rq = (int)w.Rq; p.Rb = (int)w.Rb; p.res = fac ? 2 : res ? 1 : 0; p.grad_stage = pl.grad_stage ? 1 : 0;
     if (fac) {
-        const FacDev &F = *FX;
+        const FacDev &F = *pl.FX;
         p.gq = F.gq; p.gb = F.gb; p.gchunk = F.chunk_off; p.glab = F.lab_chunk_off; p.gNC = F.NC;
     } else if (den) {
         p.gq = res ? h->dev.res.gq : h->dev.perm; p.gb = res ? h->dev.res.gb : h->dev.perm;
@@ -964,11 +1034,8 @@ static int loss_impl(const crf_graph *g, const float *logp, int fused, int in_dt
     p.redo_ctc = (int *)(pb + 18 * B);   // [B]
     p.ctc_logdom = (int *)(pb + 19 * B); // [B]
     p.ctc_bad = (int *)(base + w.off_cbad);
-    // CRF_ROBUST: 0 = never run the robust fallback, 1 = every utterance takes it (tests, or "safe mode"); default: the
-    // utterances the fast kernels flag
-    const int robust_env = opt(kOpt_robust, -1);   // (read per call: tests switch it)
-    p.force_redo = (den && robust_env == 1) ? 1 : 0;
-    p.force_redo_ctc = (ctc && (robust_env == 1 || opt_on(kOpt_robust_ctc))) ? 1 : 0;
+    p.force_redo = (den && pl.robust_env == 1) ? 1 : 0;
+    p.force_redo_ctc = (ctc && (pl.robust_env == 1 || opt_on(kOpt_robust_ctc))) ? 1 : 0;
     p.ctc_tilt = std::min(400, std::max(0, opt(kOpt_ctc_tilt, 100)));
     p.xch = (unsigned long long *)(base + w.off_xch);
     p.err = (int *)(base + w.off_xch + w.xch_bytes);
@@ -978,115 +1045,537 @@ static int loss_impl(const crf_graph *g, const float *logp, int fused, int in_dt
     p.gvec_stride = w.gvec_stride;
     p.den_zs = pb; p.den_ez = (int *)(pb + B); p.ctc_ez = (int *)(pb + 2 * B);
     p.cost_alpha = pb + 3 * B; p.cost_beta = pb + 4 * B; p.cost_ctc = pb + 5 * B; p.invalid = (int *)(pb + 6 * B);
-    p.grad = grad; p.loss = loss; p.out_den = costs_den; p.out_beta = costs_beta; p.out_ctc = costs_ctc;
-    p.out_invalid = invalid;
-
-    hipError_t e;
-#define LAUNCH_CHECK(what)                                                                         \
-    if ((e = hipGetLastError()) != hipSuccess) { set_error(std::string(what) + ": " + hipGetErrorString(e)); return CRF_ERR_HIP; }
-
-    const int64_t frames = B * T;
-    // Two streams at most: the caller's and one side stream of this (device, caller stream)'s context.  Forward and
-    // backward recursions are one grid each (denominator pair, numerator pair); the two grids are independent.
-    const bool serial_env = opt_on(kOpt_serial_chains);
-    DevCtx *cx = nullptr;
-    int rc;
-    if ((rc = get_ctx(stream, &cx))) return rc;
-    std::lock_guard<std::mutex> call_lock(cx->mu);
-    // A context whose probe found no stream beside the caller's (a device shared with another busy process at that moment can make the
-    // two single-wave probe kernels miss each other) asks again every 256 calls instead of staying on the serial schedule for good.
-    // (at most three more probes, at calls 256, 1 024 and 4 096: a process that cannot have a second queue at all -- GPU_MAX_HW_QUEUES=1 --
-    // must not pay a dozen candidates' time-outs every 256 steps for the rest of the run; never while the caller's stream is being captured)
-    if (!cx->side && cx->flags && !opt_on(kOpt_no_side_stream) && !opt_on(kOpt_trust_side) && cx->reprobes < 3 &&
-        cx->call_id + 1 == (256 << (2 * cx->reprobes))) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
-        ++cx->reprobes;
-        if (cap == hipStreamCaptureStatusNone) {
-            (void)hipStreamSynchronize(stream);
-            cx->side = find_beside(stream, cx->flags, cx->dev, &cx->side_kind, &cx->side_tries);
-            snprintf(cx->side_desc, sizeof(cx->side_desc), "%s (candidate %d, found at call %d)", kSideNames[cx->side_kind], cx->side_tries, cx->call_id + 1);
-        }
-    }
-    const bool serial = serial_env || !cx->side;              // no side stream: everything in order on the caller's stream
-    hipStream_t side = serial ? stream : cx->side;
+    p.grad = a.grad; p.loss = a.loss; p.out_den = a.costs_den; p.out_beta = a.costs_beta; p.out_ctc = a.costs_ctc;
+    p.out_invalid = a.invalid;
     // error word, start counter and stage counters live in fine-grained memory (get_ctx); the prep kernel clears them
-    const bool have_flags = cx->flags != nullptr;
     p.clear = nullptr; p.nclear = 0;
-    p.call_id = ++cx->call_id; p.ctc_seen = cx->seen;
-    g_call_streams = 1;
-    g_side_desc = cx->side_desc;
-    if (have_flags) { p.err = cx->flags; p.clear = cx->flags; p.nclear = 64; }
-    g_last_err_word = p.err;
-    static LdsMark lds_mark_grad;
-    if ((rc = ensure_lds((const void *)crf_grad_kernel, lds_grad, lds_mark_grad, "grad"))) return rc;
+    p.call_id = call_id; p.ctc_seen = cx->seen;
+    if (cx->flags) { p.err = cx->flags; p.clear = cx->flags; p.nclear = 64; }
+    p.gd_timeout_host = cx->hostw ? cx->hostw + 4 : nullptr;
+    p.gd_nb = pl.nstage + 1;
+    for (int k = 0; k <= pl.nstage && k < 16; ++k) p.gd_bound[k] = pl.bound[k];
+    p.zero_grad = pl.par3 ? 1 : 0;
+    return p;
+}
+
+// the utterance-minor kernel is chosen at run time over UL x factored and launched through a pointer (no dynamic LDS: no marks)
+static const void *bat_kernel(bool persist, int UL, bool bfac) {
+#define CRF_BAT_FN(K) (UL == 64 ? (bfac ? (const void *)K<64, 4, true> : (const void *)K<64, 4, false>)    \
+                     : UL == 32 ? (bfac ? (const void *)K<32, 4, true> : (const void *)K<32, 4, false>)    \
+                     : UL == 16 ? (bfac ? (const void *)K<16, 4, true> : (const void *)K<16, 4, false>)    \
+                                : (bfac ? (const void *)K<8, 4, true> : (const void *)K<8, 4, false>))
+    return persist ? CRF_BAT_FN(crf_batch_persist_kernel) : CRF_BAT_FN(crf_batch_frame_kernel);
+#undef CRF_BAT_FN
+}
+static const char *bat_kernel_name(bool persist, int UL, bool bfac) {
+    static const char *const kBatNames[2][4][2] = {
+        {{"crf_batch_frame_kernel<8,4,false>", "crf_batch_frame_kernel<8,4,true>"}, {"crf_batch_frame_kernel<16,4,false>", "crf_batch_frame_kernel<16,4,true>"},
+         {"crf_batch_frame_kernel<32,4,false>", "crf_batch_frame_kernel<32,4,true>"}, {"crf_batch_frame_kernel<64,4,false>", "crf_batch_frame_kernel<64,4,true>"}},
+        {{"crf_batch_persist_kernel<8,4,false>", "crf_batch_persist_kernel<8,4,true>"}, {"crf_batch_persist_kernel<16,4,false>", "crf_batch_persist_kernel<16,4,true>"},
+         {"crf_batch_persist_kernel<32,4,false>", "crf_batch_persist_kernel<32,4,true>"}, {"crf_batch_persist_kernel<64,4,false>", "crf_batch_persist_kernel<64,4,true>"}}};
+    return kBatNames[persist ? 1 : 0][UL == 64 ? 3 : UL == 32 ? 2 : UL == 16 ? 1 : 0][bfac ? 1 : 0];
+}
+
+// One call being enqueued.  Two streams at most (three with the context's third stream): the caller's and one side stream of this
+// (device, caller stream)'s context.  Forward and backward recursions are one grid each (denominator pair, numerator pair); the two grids
+// are independent.
+struct LossCall {
+    const LossArgs &a;
+    const WsLayout &w;
+    const CallPlan &pl;
+    DevCtx *cx;
+    hipStream_t stream, side;   // side == stream: everything in order on the caller's stream
+    LossParams p;
     bool forked = false, side_used = false;
     bool ctc_pass1 = false;   // the numerator's log-domain fallback has run in this call (staged schedule)
-    auto fork_side = [&]() -> int {   // the side stream starts behind everything queued on the caller's stream so far
-        if (serial || forked) return CRF_OK;
-        if ((e = hipEventRecord(cx->fork, stream)) != hipSuccess || (e = hipStreamWaitEvent(side, cx->fork, 0)) != hipSuccess) {
-            set_error(std::string("fork: ") + hipGetErrorString(e)); return CRF_ERR_HIP;
-        }
+
+    int *started() const { return p.err + 1; }   // workgroups of the den kernels that hold a CU (cleared with the error word)
+    // factored recursions launched in segments park their state vectors here
+    float *fstate() const { return (float *)((char *)a.ws + w.off_state); }
+    float *bstate() const { return fstate() + a.B * w.state_stride; }
+
+    int fork_side() {   // the side stream starts behind everything queued on the caller's stream so far
+        if (pl.serial || forked) return CRF_OK;
+        if (const int rc = wait_behind(side, cx->fork, stream, "fork")) return rc;
         forked = side_used = true;
         if (g_call_streams < 2) g_call_streams = 2;
         return CRF_OK;
-    };
-    auto join_side = [&]() -> int {   // the caller's stream continues behind everything queued on the side stream so far
-        if (serial || !side_used) return CRF_OK;
-        if ((e = hipEventRecord(cx->join, side)) != hipSuccess || (e = hipStreamWaitEvent(stream, cx->join, 0)) != hipSuccess) {
-            set_error(std::string("join: ") + hipGetErrorString(e)); return CRF_ERR_HIP;
-        }
+    }
+    int join_side() {   // the caller's stream continues behind everything queued on the side stream so far
+        if (pl.serial || !side_used) return CRF_OK;
+        if (const int rc = wait_behind(stream, cx->join, side, "join")) return rc;
         forked = false;
         return CRF_OK;
-    };
-    int *started = p.err + 1;   // workgroups of the den kernels that hold a CU (cleared with the error word)
-    int ncu_dev = 256;
-    (void)hipDeviceGetAttribute(&ncu_dev, hipDeviceAttributeMultiprocessorCount, cx->dev);
-    // The denominator half of the grad pass has a streaming kernel (index pairs in registers, rows
-    // prefetched); it needs 16-bit row indices, rows of <= kGDRowRegs*256 floats and <= 2 chunks per thread.
-    const int gnc = den ? (fac ? FX->NC : res ? h->dev.res.NC : h->dev.NC) : 0;
-    const int gcap = fac ? FX->chunk_cap : kChunk;       // entries per chunk of the grad pass's pair lists
-    const bool gd_wide = den && (w.Rq > 4 * kGDRowRegs * kGDThreads || w.Rb > 4 * kGDRowRegs * kGDThreads);   // 512-thread grad workgroups
-    // (rows of up to 12 288 floats since round 6 -- 512 threads x 6 row registers: a den_lm with a state per seen bigram history has ~5.3 k forward rows
-    // at 72 tokens, Rq = Rb = 10 752, 5 % beyond the 10 240 of five registers, and took the generic grad kernel: 10.8 ms of a 17.5 ms step)
-    const bool gd_wide6 = den && (w.Rq > 8 * kGDRowRegs * kGDThreads || w.Rb > 8 * kGDRowRegs * kGDThreads);
-    const bool fast_den = den && w.Rq <= 8 * 6 * kGDThreads && w.Rb <= 8 * 6 * kGDThreads && w.Rq % 4 == 0 && w.Rb % 4 == 0 && (!gd_wide6 || (gnc <= 2 * kGDThreads && gcap != 8)) &&
-                          gnc <= 4 * kGDThreads && V <= kGDEpRegs * kGDThreads && !opt_on(kOpt_no_fast_grad);
-    // numerator half of the grad pass: streaming kernel when the vocabulary fits its registers
-    const bool fast_ctc = ctc && V <= kGCVRegs * kGCThreads && 2 * max_label_len + 1 <= kGCRegs * kGCThreads &&
-                          !opt_on(kOpt_no_fast_grad);
-    // Factored den kernels: 2B workgroups, one CU each.  While that is at most half of the chip, everything else
-    // runs BESIDE them on the other half, on the side stream: numerator chains, their grad half, and the den half of
-    // the grad pass.  The den half of the grad pass needs rows of BOTH recursions, which work towards each other; it
-    // is released in stages: the recursions bump a counter at every stage bound, the grad launch of stage k is queued
-    // behind a STREAM-level wait on that counter and takes the 16-frame blocks the stage completed.
-    // (A grad pass that SPINS on progress counters of the running den kernels is faster still on a quiet device,
-    // but with many launches queued ahead the den kernels were observed to stop for seconds while the waiting
-    // workgroups kept their queue busy -- one kernel must never wait for another.)
-    const bool no_overlap = opt_on(kOpt_no_overlap);   // diagnostics
-    // how stage k of the grad pass is released: a stream-level wait on a counter the running recursions bump
-    // (default), or -- CRF_SEGMENTS=1, and automatically if hipStreamWaitValue32 is refused -- by cutting the
-    // recursions into one launch per stage with an event after each (~40 us per relaunch, state parked in HBM)
-    static std::atomic<bool> use_segments{false};      // set when hipStreamWaitValue32 is refused
-    const bool segmode = use_segments.load() || opt_on(kOpt_segments);
-    const int stages_env = opt(kOpt_stages, 0);
-    const int pieces = stages_env > 0 ? stages_env : (segmode ? 4 : 12);   // measured: 4 / 8 / 12 pieces -> call 4.06 / 3.98 / 3.93 ms (flags)
-    // two utterances per workgroup (use_fac_pair2): the den grid is 2 * ceil(B / 2) workgroups instead of 2 B
-    const bool pair2 = fac && w.p2mode != 0;   // (pair2_mode, decided with the workspace layout: the rows are sized for the layout it names)
-    const int64_t den_wgs = pair2 ? 2 * ((B + 1) / 2) : 2 * B;
-    // (the two-utterance kernel has no segment relaunches: where stream-level waits are refused it runs unstaged)
-    const bool staged = fac && FX->K == 1 && ctc && fast_den && fast_ctc && !serial && !no_overlap && have_flags && !(pair2 && segmode) && den_wgs * 100 <= (int64_t)ncu_dev * opt(kOpt_stage_fill, 75);   // (B = 80: 4.16 -> 3.56 ms, B = 96: 4.37 -> 4.26, B = 112 at 90 %: 5.33 -> 5.57)
-    // Stage bounds.  Nothing can be released before the two recursions have met, so the first stage ends at half of
-    // the frames or later; after that a piece of `piece` iterations releases 2 * piece / 16 frame blocks per
-    // utterance.  The grad pass has half of the chip and is bandwidth-bound there (~2 TB/s against the 2.2 TB/s the
-    // two recursions produce), with a fixed cost per stage (launch, the workgroups' set-up, partial rounds); what is
-    // left when the recursions end is its backlog plus the last stage.  Measured (B=64, T=1500, recursions 2.95 ms):
-    // pieces of 32 / 48 / 64 / 96 / 128 / 192 / 256 / 384 iterations -> step 3.88 / 3.62 / 3.42 / 3.38 / 3.33 / 3.35 /
-    // 3.41 / 3.53 ms; pieces that shrink towards the end (256,192,128,96,64 ...) were no better than equal ones.
-    // CRF_PIECE / CRF_STAGES override (segment mode: 4 pieces, each relaunch costs ~40 us).
-    int bound[kMaxStages + 1] = {0};
-    int nstage = 1, gd_piece = 0;
-    bound[1] = (int)T;
+    }
+    // stream `waiter` continues behind what is queued on `on` so far, through event `ev`
+    static int wait_behind(hipStream_t waiter, hipEvent_t ev, hipStream_t on, const char *what) {
+        hipError_t e;
+        if ((e = hipEventRecord(ev, on)) != hipSuccess || (e = hipStreamWaitEvent(waiter, ev, 0)) != hipSuccess) {
+            set_error(std::string(what) + ": " + hipGetErrorString(e)); return CRF_ERR_HIP;
+        }
+        return CRF_OK;
+    }
+
+    int launch_grad_den(hipStream_t st, int stage, bool persist = false) {
+        const int64_t B = a.B, T = a.T, V = a.V;
+        p.gd_stage = stage;
+        const size_t l = ((size_t)rup64((int)w.Rq + 1) + rup64((int)w.Rb + 1) + 4 * rup64((int)V) + kGDFrames + rup64(pl.gnc)) * sizeof(float);
+        dim3 gg((unsigned)((T + kGDFrames - 1) / kGDFrames), (unsigned)B);
+        p.gd_nf = 0;
+        p.gd_persist = 0;
+        const bool full_grid = opt_on(kOpt_gd_full_grid);
+        if (persist) {   // the stages `stage` .. nstage in one launch (see the kernel): 2 * nf candidates per utterance and stage, stage-major
+            p.gd_persist = 1;
+            p.gd_cnt = cx->flags + 16;
+            p.gd_target = (int)(2 * B);
+            const int64_t tot = plan_grad_grid(p.gd_bound, p.gd_nb - 1, stage, B, pl.gd_piece, p.gd_poff, p.gd_fpb);
+            gg = dim3((unsigned)tot, 1);
+        } else if (stage > 1 && !full_grid) {   // (stage 1 is the middle of every utterance: all blocks are candidates)
+            p.gd_nf = (p.gd_bound[stage] - p.gd_bound[stage - 1] + kGDFrames - 1) / kGDFrames + 3;
+            if (2 * p.gd_nf < (int)gg.x) gg.x = (unsigned)(2 * p.gd_nf); else p.gd_nf = 0;
+        }
+        const char *const name = "crf_grad_den_kernel";
+        const dim3 b1(kGDThreads), b2(2 * kGDThreads);
+        if (pl.gcap == 8)                // chunk lists cut at 8 entries (many labels with few pairs each): 512 threads, two chunks each
+            return launch<crf_grad_den_kernel<2, 2, 2 * kGDThreads, 8>>(name, gg, b2, l, st, p);
+        if (pl.gnc > 2 * kGDThreads)     // more than 512 label chunks (graphs over hundreds of classes: V = 500 has ~8 pairs per label,
+                                         // one chunk each): 512 threads with two chunks each
+            return launch<crf_grad_den_kernel<2, 2, 2 * kGDThreads>>(name, gg, b2, l, st, p);
+        if (pl.gd_wide6)                 // rows of 10 241 .. 12 288 floats: 512 threads with six row registers each
+            return launch<crf_grad_den_kernel<1, 2, 2 * kGDThreads, kChunk, 6, 1>>(name, gg, b2, l, st, p);
+        if (pl.gd_wide && CRF_X_GDW2 && w.Rq <= 32 * kGDThreads && w.Rb <= 32 * kGDThreads)
+            // rows of 5121 .. 8192 floats: 512 threads with four row registers each, held to 128 VGPRs so that a CU takes TWO workgroups (the
+            // five-register form below compiles to 148 VGPRs: one workgroup, eight waves, per CU -- the estimated S = 6836 graph ran on that)
+            return launch<crf_grad_den_kernel<1, 2, 2 * kGDThreads, kChunk, 4, 4>>(name, gg, b2, l, st, p);
+        if (pl.gd_wide)                  // rows of more than 5120 floats: 512 threads per workgroup (one chunk per thread up to 512 chunks)
+            return launch<crf_grad_den_kernel<1, 2, 2 * kGDThreads>>(name, gg, b2, l, st, p);
+        if (pl.gnc <= kGDThreads && V <= kGDThreads)   // small vocabulary
+            return launch<crf_grad_den_kernel<1, 1>>(name, gg, b1, l, st, p);
+        if (pl.gnc <= kGDThreads)
+            return launch<crf_grad_den_kernel<1, kGDEpRegs>>(name, gg, b1, l, st, p);
+        return launch<crf_grad_den_kernel<2, kGDEpRegs>>(name, gg, b1, l, st, p);
+    }
+    int launch_grad_generic(int phase, hipStream_t st, const char *name) {
+        p.grad_phase = phase;
+        return launch<crf_grad_kernel>(name, dim3((unsigned)((a.T + kGradFrames - 1) / kGradFrames), (unsigned)a.B), dim3(kGradThreads), pl.lds_grad, st, p);
+    }
+    int launch_grad_ctc(int phase, hipStream_t st) {  // phase 2: subtract from the den half; 0: plain CTC (writes)
+        if (!pl.fast_ctc) return launch_grad_generic(phase, st, "crf_grad(ctc)");
+        p.grad_phase = phase;
+        const size_t l = (size_t)4 * rup64((int)a.V) * sizeof(float) + kGCFrames * sizeof(double) + 64;
+        const dim3 gg((unsigned)((a.T + kGCFrames - 1) / kGCFrames), (unsigned)a.B);
+        const int Sxm = 2 * (int)a.max_label_len + 1;
+        if (Sxm <= 2 * kGCThreads) return launch<crf_grad_ctc_kernel<2>>("crf_grad(ctc)", gg, dim3(kGCThreads), l, st, p);
+        if (Sxm <= 4 * kGCThreads) return launch<crf_grad_ctc_kernel<4>>("crf_grad(ctc)", gg, dim3(kGCThreads), l, st, p);
+        return launch<crf_grad_ctc_kernel<kGCRegs>>("crf_grad(ctc)", gg, dim3(kGCThreads), l, st, p);
+    }
+    // The grad pass on `st` behind recursions that have ended: the streaming kernels of the halves the call has, else the generic kernel.
+    // phase 0: both halves; 1: the den half alone (the caller adds launch_grad_ctc(2) when the numerator's chains have ended too)
+    int grad_after_recursions(hipStream_t st, int phase) {
+        if (pl.den && pl.fast_den) {
+            const int rc = launch_grad_den(st, 0);
+            return (rc || phase != 0 || !pl.ctc) ? rc : launch_grad_ctc(2, st);
+        }
+        if (!pl.den && pl.fast_ctc) return launch_grad_ctc(0, st);
+        return launch_grad_generic(phase, st, phase ? "crf_grad_kernel(den)" : "crf_grad_kernel");
+    }
+    // Numerator fallback: utterances with frames the grad pass marked (or whose scaled chain lost its mass) redo their chains in the
+    // log domain, then the marked frames' posteriors are subtracted from the rows; the other utterances' workgroups leave at once --
+    // two near-empty launches.  Pass 1 runs right behind the numerator's grad half on the side stream of the staged schedule, i.e.
+    // BESIDE the denominator recursions (V = 500: 1.2 ms that followed the call's last grad launch); pass 2 at the end of every call
+    // takes what is marked and was not redone in pass 1.
+    int launch_robust_ctc_chains(hipStream_t st, int pass) {
+        const int64_t ni = (2 * a.max_label_len + 1 + kCtcThreads - 1) / kCtcThreads;
+        const dim3 grid((unsigned)(2 * a.B)), block(kCtcThreads);
+        p.ctc_pass = pass;
+        if (ni <= 1) return launch<crf_robust_ctc_kernel<1>>("crf_robust_ctc_kernel", grid, block, pl.lds_ctc, st, p);
+        if (ni <= 2) return launch<crf_robust_ctc_kernel<2>>("crf_robust_ctc_kernel", grid, block, pl.lds_ctc, st, p);
+        if (ni <= 4) return launch<crf_robust_ctc_kernel<4>>("crf_robust_ctc_kernel", grid, block, pl.lds_ctc, st, p);
+        return launch<crf_robust_ctc_kernel<kCtcRegs>>("crf_robust_ctc_kernel", grid, block, pl.lds_ctc, st, p);
+    }
+    int launch_robust_ctc_fix(hipStream_t st, int pass) {
+        p.ctc_pass = pass;
+        return launch<crf_robust_ctc_fix_kernel>("crf_robust_ctc_fix_kernel", dim3((unsigned)((a.T + kGCFrames - 1) / kGCFrames), (unsigned)a.B), dim3(kGradThreads),
+                                                 (size_t)rup64((int)a.V) * sizeof(float), st, p);
+    }
+    int launch_robust_ctc(hipStream_t st, int pass) {
+        const int rc = launch_robust_ctc_chains(st, pass);
+        return rc ? rc : launch_robust_ctc_fix(st, pass);
+    }
+    // forward log Z = backward log Z?  (crf_den_check_kernel: behind every launch of the recursions, on their stream -- in the staged schedule
+    // it runs while the side stream finishes the grad pass -- and in front of the fallback kernels, which take what it flags)
+    int launch_den_check(hipStream_t st) {
+        if (!pl.den || pl.robust_env == 0) return CRF_OK;
+        return launch<crf_den_check_kernel>("crf_den_check_kernel", dim3((unsigned)((a.B + 255) / 256)), dim3(256), 0, st, p, (pl.res || pl.fac) ? 1 : 0);
+    }
+    // the denominator recursions of the whole batch on `st` (every layout; both directions per launch)
+    int launch_den(hipStream_t st, bool with_check = true) {
+        const int B = (int)a.B;
+        const HostGraph *h = pl.h;
+        int rc = CRF_OK;
+        if (!pl.fac && !pl.res) {   // streaming kernels (launch_den_pair marks the profile slots itself)
+            rc = pl.gv ? launch_den_pair<true>(p, pl.lds_den, st) : launch_den_pair<false>(p, pl.lds_den, st);
+            return (rc || !with_check) ? rc : launch_den_check(st);
+        }
+        prof_mark(1, false, st); prof_mark(2, false, st);
+        {
+            const CoresGuard cores((pl.fac && pl.FX->K > 1) || (pl.res && !pl.fac && h->dev.res.K > 1), cx->dev, st);
+            if (pl.fac && pl.FX->K > 1) {
+                const int grp = std::max(1, pl.ncu / 4);
+                for (int b0 = 0; b0 < B && !rc; b0 += grp) rc = launch_fac2_pair(p, pl.lds_den, st, b0, std::min(grp, B - b0));
+            } else if (pl.fac && pl.pair2) {
+                rc = launch_fac_pair2<false>(p, pl.lds_den, st, started());
+            } else if (pl.fac) {
+                rc = launch_fac_pair<false>(p, pl.lds_den, st, started(), 0, (int)a.T, fstate(), bstate());
+            } else {
+                // K CUs per utterance and direction exchange the state vector through L2 every frame.  With K > 1 every
+                // workgroup of a launch must be resident at once (its peers spin on it): groups of at most CUs/(2K) utterances.
+                const int K = h->dev.res.K;
+                const int grp = K > 1 ? std::max(1, pl.ncu / (2 * K)) : B;
+                for (int b0 = 0; b0 < B && !rc; b0 += grp) rc = launch_res_pair(p, pl.lds_den, b0, std::min(grp, B - b0), st);
+            }
+            prof_mark(1, true, st); prof_mark(2, true, st);
+            if (!rc && with_check) rc = launch_den_check(st);
+        }
+        return rc;
+    }
+
+    // the prep kernel on the caller's stream (e' rows, metadata, the cleared flag words)
+    int start() {
+        const int64_t frames = a.B * a.T;
+        for (bool &u : g_prof.used) u = false;
+        prof_mark(7, false, stream);
+        prof_mark(0, false, stream);
+        const int rc = a.V <= 256 ? launch<crf_prep_kernel<16>>("crf_prep_kernel", dim3((unsigned)((frames + 15) / 16)), dim3(256), 0, stream, p)
+                                  : launch<crf_prep_kernel<64>>("crf_prep_kernel", dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, stream, p);
+        prof_mark(0, true, stream);
+        if (rc) return rc;
+        if (pl.res && (w.xch_bytes > 0 || !pl.have_flags)) {  // exchange granules (tags) and the error word start at zero in every call
+            if (hipMemsetAsync(p.xch, 0, (size_t)w.xch_bytes + 256 + 8 * (size_t)a.B, stream) != hipSuccess) { set_error("hipMemsetAsync(xch)"); return CRF_ERR_HIP; }
+        }
+        return CRF_OK;
+    }
+
+    int run_batch();
+    int run_staged();
+    int run_staged_par3();
+    int run_two_streams();
+    int run_one_stream();
+    int run_fallbacks_and_finalize();
+};
+
+// Utterance-minor denominator (large graphs): one launch per frame on the caller's stream, forward step of
+// frame j and backward step of frame T - j together; the numerator pair runs beside them on the side stream.
+int LossCall::run_batch() {
+    const int64_t B = a.B, T = a.T, V = a.V;
+    const HostGraph *h = pl.h;
+    char *base = (char *)a.ws;
+    int rc;
+    hipError_t e;
+    BatchParams bp{};
+    bp.g = h->dev.bat; bp.start_lin = h->dev.start_lin; bp.end_lin = h->dev.end_lin;
+    bp.S = h->dev.S; bp.P = h->dev.P; bp.B = (int)B; bp.Bp = (int)w.Bp; bp.T = (int)T; bp.V = (int)V; bp.max_label = h->dev.max_label;
+    bp.lx = a.lx; bp.ep = p.ep; bp.moff = p.moff;
+    bp.ept = (float *)(base + w.off_ept); bp.Af = (float *)(base + w.off_Af); bp.Zb = (float *)(base + w.off_Zb);
+    bp.Q = p.Q; bp.BP = p.BP;
+    unsigned *bsm = (unsigned *)(base + w.off_bsm);
+    bp.mxf = bsm; bp.mxb = bsm + 3 * w.Bp; bp.Ef = (int *)(bsm + 6 * w.Bp); bp.Fb = (int *)(bsm + 7 * w.Bp);
+    bp.zs = (float *)(bsm + 8 * w.Bp); bp.zb = (float *)(bsm + 9 * w.Bp);
+    bp.bar = bsm + 12 * w.Bp; bp.err = (int *)(bsm + 12 * w.Bp + 512);
+    bp.den_zs = p.den_zs; bp.cost_alpha = p.cost_alpha; bp.cost_beta = p.cost_beta; bp.den_ez = p.den_ez; bp.redo = p.redo;
+    bp.grad = a.grad; bp.c_den = a.c_den;
+    const unsigned ngrp = (unsigned)(w.Bp / w.UL);
+    bp.ngrp = (int)ngrp;
+    // one task per wave, ONE round of workgroups (a second round with a fraction of the device doubled the launch):
+    // the tasks wanted per direction follow from the occupancy the runtime reports, shared by the combos
+    const int64_t ncombo = 2 * (int64_t)ngrp;
+    const bool bfac = stream_fac(a.g->h, w.UL);                  // factored streams (T o LM graphs, groups of >= 32 utterances)
+    // ALL frames in one persistent launch (round 6) when its grid is co-resident by the runtime's own count -- switch bat_persist: 0 =
+    // one launch per frame (rounds 2 - 5; also the fallback), 1 = persistent (default)
+    const bool want_persist = opt(kOpt_bat_persist, 1) != 0;
+    int wg_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg_cu, bat_kernel(want_persist, w.UL, bfac), kBatThreads, 0) != hipSuccess || wg_cu < 1) { (void)hipGetLastError(); wg_cu = want_persist ? 0 : 2; }
+    bool persist = want_persist && wg_cu >= 1;
+    if (want_persist && !persist) wg_cu = 2;
+    // ... times 70 %: a launch is bound by the L2s and the fabric, not by the CUs, and fewer, longer tasks pay the task set-up
+    // (three dependent trips to a cold L2) less often.  Measured, S = 16 385 / B = 64 (repeatable to 0.3 %): 100 / 85 / 70 /
+    // 60 / 55 / 45 / 35 % -> 30.7 / 29.5 / 28.8 / 30.6 / 31.8 / 28.5 / 31.3 ms per step (the dips: workgroups per XCD just
+    // above a multiple of its 32 CUs); config #5 at B = 8: 100 / 70 / 50 % -> 145.3 / 143.6 / 152.6 ms.  CRF_BAT_FILL overrides.
+    const int fill_env = opt(kOpt_bat_fill, 0);
+    const int64_t fill = fill_env > 0 && fill_env <= 100 ? fill_env : 70;
+    const int64_t slots = (int64_t)pl.ncu * wg_cu;            // workgroups the device holds at once
+    const int want = (int)std::max<int64_t>(16, (int64_t)pl.ncu * wg_cu * kBatWaves * 15 / 16 * fill / 100 / ncombo);
+    const StreamDev *sdv = nullptr;
+    if ((rc = ensure_stream_tables(a.g->h, w.UL, want, &sdv))) return rc;
+    if ((sdv->fac != 0) != bfac) { set_error("arc streams: factored / plain mismatch"); return CRF_ERR_ARG; }
+    bp.SX = h->dev.S + sdv->NU; bp.x_start = sdv->x_start;
+    bp.st = *sdv;
+    // 8 * nslot workgroups (block b -> XCD b % 8, slot b / 8): every combo gets at least one wave per task of its arc
+    // stream (crf_batch_frame_kernel: a combo has nslot * nk or about nslot / ncx workgroups)
+    const int64_t tasks_max = std::max({(int64_t)sdv->f.ntasks, (int64_t)sdv->b.ntasks, (int64_t)1});
+    const int64_t wg_combo = (tasks_max + kBatWaves - 1) / kBatWaves + ((sdv->f.nrest > 64 || sdv->b.nrest > 64) ? (std::max(sdv->f.nrest, sdv->b.nrest) + 4 * kBatWaves - 1) / (4 * kBatWaves) : 0);
+    const unsigned nslot = (unsigned)(ncombo < 8 ? (wg_combo + (8 / ncombo) - 1) / (8 / ncombo) : wg_combo * ((ncombo + 7) / 8));
+    const unsigned G = 8 * nslot;
+    if (persist && (int64_t)G > slots) persist = false;        // (the grid barrier needs every workgroup resident)
+    // The numerator chains run BESIDE the per-frame launches (side stream) but BEHIND the persistent launch, beside the grad pass: a
+    // co-resident grid sized for the device's slots must not share them -- with the chains' 2 B workgroups on the CUs, G = 416 of 512
+    // slots no longer fitted at once (S = 12 289, B = 64: a CU that holds a chain workgroup has LDS for one workgroup of this kernel,
+    // not two), the rest of the grid waited for the chains, and the runtime time-sliced the queues: 1.7 ms per frame instead of 13 us
+    // and barrier time-outs (profiles/round6_ab_persistent_batch.txt)
+    if (pl.ctc && !persist) {
+        if ((rc = fork_side())) return rc;
+        if ((rc = launch_ctc_pair(p, pl.lds_ctc, side, a.max_label_len))) return rc;
+    }
+    if (opt_on(kOpt_verbose)) fprintf(stderr, "[ctc_crf_hip] utterance-minor: UL %d, %d combos, tasks %d / %d, rest rows %d / %d, grid %u of %lld slots (%d per CU), %s\n", (int)w.UL, (int)ncombo,
+                                      sdv->f.ntasks, sdv->b.ntasks, sdv->f.nrest, sdv->b.nrest, G, (long long)slots, wg_cu, persist ? "one persistent launch" : "one launch per frame");
+    prof_mark(1, false, stream); prof_mark(2, false, stream);
+#define CRF_BAT_UL(KERNEL, GRID, ...)                                                                          \
+    (w.UL == 64   ? launch<KERNEL<64>>(#KERNEL, GRID, dim3(kBatThreads), 0, stream, __VA_ARGS__)                \
+     : w.UL == 32 ? launch<KERNEL<32>>(#KERNEL, GRID, dim3(kBatThreads), 0, stream, __VA_ARGS__)                \
+     : w.UL == 16 ? launch<KERNEL<16>>(#KERNEL, GRID, dim3(kBatThreads), 0, stream, __VA_ARGS__)                \
+                  : launch<KERNEL<8>>(#KERNEL, GRID, dim3(kBatThreads), 0, stream, __VA_ARGS__))
+    if ((rc = CRF_BAT_UL(crf_batch_transpose_kernel, dim3((unsigned)((V + 63) / 64), (unsigned)T, ngrp), bp))) return rc;
+    if ((rc = launch<crf_batch_init_kernel>("crf_batch_init_kernel", dim3((unsigned)(((int64_t)bp.SX * w.Bp + kBatThreads - 1) / kBatThreads)), dim3(kBatThreads), 0, stream, bp))) return rc;
+    g_den_kernel = bat_kernel_name(persist, w.UL, bfac);
+    {
+        void *args[] = {(void *)&bp};
+        const void *fn = bat_kernel(persist, w.UL, bfac);
+        if (persist) {
+            // (co-resident grids of two callers must not interleave: each could become partially resident and wait for the rest)
+            CoresGuard guard(true, cx->dev, stream);
+            bp.j = 0;
+            if ((e = hipLaunchKernel(fn, dim3(G), dim3(kBatThreads), args, 0, stream)) != hipSuccess) { set_error(std::string("crf_batch_persist_kernel: ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
+        } else {
+            for (int j = 0; j <= (int)T; ++j) {   // (4: batches of gathers in flight per wave; 2 measured 6 % slower, 8 needs more registers than a wave has)
+                bp.j = j;
+                if ((e = hipLaunchKernel(fn, dim3(G), dim3(kBatThreads), args, 0, stream)) != hipSuccess) { set_error(std::string("crf_batch_frame_kernel: ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
+            }
+        }
+    }
+    if (pl.ctc && persist) {
+        if ((rc = fork_side())) return rc;
+        if ((rc = launch_ctc_pair(p, pl.lds_ctc, side, a.max_label_len))) return rc;
+    }
+    if ((rc = CRF_BAT_UL(crf_batch_zsum_kernel, dim3((unsigned)((h->dev.S + 255) / 256), 1, ngrp), bp))) return rc;
+    if ((rc = launch<crf_batch_cost_kernel>("crf_batch_cost_kernel", dim3((unsigned)B), dim3(kBatThreads), 0, stream, bp))) return rc;
+    prof_mark(1, true, stream); prof_mark(2, true, stream);
+    if ((rc = launch_den_check(stream))) return rc;
+    prof_mark(5, false, stream);
+    if ((rc = CRF_BAT_UL(crf_batch_grad_kernel, dim3((unsigned)T, 1, ngrp), bp))) return rc;
+#undef CRF_BAT_UL
+    if ((rc = join_side())) return rc;
+    if (pl.ctc && (rc = launch_grad_ctc(2, stream))) return rc;
+    prof_mark(5, true, stream);
+    return CRF_OK;
+}
+
+// Staged: caller's stream: the denominator pair.  Side stream, behind a short bounded start gate: numerator pair, its
+// grad half (writes -c_ctc * gamma_ctc), then the den half of the grad pass stage by stage (adds gamma_den).
+int LossCall::run_staged() {
+    const int64_t B = a.B;
+    const int nstage = pl.nstage;
+    int *const stage_cnt = cx->flags + 16;
+    int rc;
+    hipError_t e;
+    if ((rc = fork_side())) return rc;
+    prof_mark(1, false, stream); prof_mark(2, false, stream);
+    if (pl.pair2) {
+        if ((rc = launch_fac_pair2<true>(p, pl.lds_den, stream, started(), nstage + 1, pl.bound, stage_cnt))) return rc;
+    } else if (!pl.segmode) {
+        if ((rc = launch_fac_pair<true>(p, pl.lds_den, stream, started(), 0, (int)a.T, fstate(), bstate(), nstage + 1, pl.bound, stage_cnt))) return rc;
+    } else {
+        for (int k = 0; k < nstage; ++k) {
+            if ((rc = launch_fac_pair<false>(p, pl.lds_den, stream, started(), pl.bound[k], pl.bound[k + 1], fstate(), bstate()))) return rc;
+            if ((e = hipEventRecord(cx->ev[k], stream)) != hipSuccess) { set_error(std::string("hipEventRecord(segment): ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
+        }
+    }
+    prof_mark(1, true, stream); prof_mark(2, true, stream);
+    if ((rc = launch_den_check(stream))) return rc;
+    // hold the numerator back (briefly, bounded) until the den workgroups have their CUs
+    if ((rc = launch<crf_gate_kernel>("crf_gate_kernel", dim3(1), dim3(1), 0, side, started(), (int)pl.den_wgs))) return rc;
+    if ((rc = launch_ctc_pair(p, pl.lds_ctc, side, a.max_label_len))) return rc;
+    prof_mark(5, false, side);
+    if ((rc = launch_grad_ctc(pl.par3 ? 3 : 0, side))) return rc;
+    if (pl.par3) return run_staged_par3();
+    // Numerator fallback, pass 1.  The chains of the marked utterances can take as long as the scaled ones did (T = 3 000, L = 500,
+    // every utterance marked: 3 ms): on the third stream they run beside the grad stages instead of in front of them, and the
+    // marked frames' posteriors are subtracted behind the last stage (the stages ADD gamma_den: the order does not matter).
+    // Enqueued BEFORE the stage waits of the side stream: whatever hardware queues the three streams share, the chains' packets
+    // precede the wait for their event.
+    bool aux_fix = false;
+    ctc_pass1 = pl.robust_env != 0;
+    if (pl.robust_env != 0) {
+        // (the third stream is taken when a recent call of this context ran the log-domain chains: CallPlan::ctc_wants_aux)
+        if (cx->aux && pl.ctc_wants_aux && hipEventRecord(cx->ev_a, side) == hipSuccess && hipStreamWaitEvent(cx->aux, cx->ev_a, 0) == hipSuccess) {
+            if ((rc = launch_robust_ctc_chains(cx->aux, 1))) return rc;
+            if ((e = hipEventRecord(cx->ev_b, cx->aux)) != hipSuccess) { set_error(std::string("hipEventRecord(aux): ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
+            aux_fix = true;
+            g_call_streams = 3;
+        } else {
+            (void)hipGetLastError();
+            if ((rc = launch_robust_ctc_chains(side, 1))) return rc;
+        }
+    }
+    p.grad_den_acc = 1;
+    // (one launch for the stages 2 ..: behind stage 1's wait -- every recursion has run half of its frames, every den workgroup is resident)
+    const bool gd_one = !pl.segmode && nstage >= 3 && !pl.per_stage;
+    for (int k = 0; k < nstage; ++k) {
+        if (gd_one && k == 1) { if ((rc = launch_grad_den(side, 2, true))) return rc; break; }
+        if (!pl.segmode) {
+            if ((e = hipStreamWaitValue32(side, stage_cnt + k + 1, (uint32_t)(2 * B), hipStreamWaitValueGte, 0xffffffffu)) != hipSuccess) {
+                // not available here: from the next call on, segments.  This call: wait for the recursions to END
+                (void)hipGetLastError();
+                g_use_segments = true;
+                if ((rc = wait_behind(side, cx->ev[0], stream, "hipStreamWaitEvent"))) return rc;
+            }
+        } else if ((e = hipStreamWaitEvent(side, cx->ev[k], 0)) != hipSuccess) {
+            set_error(std::string("hipStreamWaitEvent(segment): ") + hipGetErrorString(e)); return CRF_ERR_HIP;
+        }
+        if ((rc = launch_grad_den(side, k + 1))) return rc;
+    }
+    // The marked frames' posteriors are subtracted at ONE place whichever stream ran the chains -- behind the last stage -- so that
+    // the order of the float additions into `grad` (and with it every bit of the gradient) does not depend on the unsynchronised
+    // hint above (round-3 advisor: with the chains on the side stream the subtraction used to precede the stages).
+    if (aux_fix && (e = hipStreamWaitEvent(side, cx->ev_b, 0)) != hipSuccess) { set_error(std::string("hipStreamWaitEvent(aux): ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
+    if (ctc_pass1 && (rc = launch_robust_ctc_fix(side, 1))) return rc;
+    prof_mark(5, true, side);
+    return join_side();   // the last grad launch is behind every stage of the recursions
+}
+// ... with the den half of the grad pass on the THIRD stream (CallPlan::par3), stage by stage behind the same stream-level waits, adding with
+// atomics; the side stream goes on with the numerator (fallback chains, if any) and takes the third stream back in behind it
+int LossCall::run_staged_par3() {
+    int rc;
+    hipError_t e;
+    if ((e = hipStreamWaitEvent(cx->aux, cx->fork, 0)) != hipSuccess) { set_error(std::string("hipStreamWaitEvent(aux fork): ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
+    p.grad_den_acc = 2;
+    for (int k = 0; k < pl.nstage; ++k) {
+        if ((e = hipStreamWaitValue32(cx->aux, cx->flags + 16 + k + 1, (uint32_t)(2 * a.B), hipStreamWaitValueGte, 0xffffffffu)) != hipSuccess) {
+            // not available here: from the next call on, segments (and no third stream).  This call: wait for the recursions to END
+            (void)hipGetLastError();
+            g_use_segments = true;
+            if ((rc = wait_behind(cx->aux, cx->ev[0], stream, "hipStreamWaitEvent"))) return rc;
+        }
+        if ((rc = launch_grad_den(cx->aux, k + 1))) return rc;
+    }
+    if ((e = hipEventRecord(cx->ev_b, cx->aux)) != hipSuccess) { set_error(std::string("hipEventRecord(aux): ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
+    g_call_streams = 3;
+    ctc_pass1 = pl.robust_env != 0;
+    if (ctc_pass1 && (rc = launch_robust_ctc_chains(side, 1))) return rc;
+    if ((e = hipStreamWaitEvent(side, cx->ev_b, 0)) != hipSuccess) { set_error(std::string("hipStreamWaitEvent(aux): ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
+    // (the marked frames' posteriors are subtracted behind BOTH halves: a plain read-modify-write of rows nobody adds to any more)
+    if (ctc_pass1 && (rc = launch_robust_ctc_fix(side, 1))) return rc;
+    prof_mark(5, true, side);
+    return join_side();
+}
+
+// Denominator pair on the caller's stream, numerator pair beside it on the side stream -- unless the den
+// workgroups own every CU (register-resident layouts with 2B (x K) >= CUs): then the numerator recursions run
+// beside the DEN HALF of the grad pass instead (HBM-bound, small workgroups that share CUs happily).
+int LossCall::run_two_streams() {
+    const HostGraph *h = pl.h;
+    int rc;
+    const int ctc_after_env = opt(kOpt_ctc_after, -1);
+    // (factored, one CU per recursion: the den grid leaves ncu - den_wgs CUs free -- B = 96: 64 of them -- and the numerator
+    // chains, four workgroups to a CU, run there beside it, behind the start gate so that the den workgroups get their CUs first)
+    const bool fac1 = pl.fac && pl.FX->K == 1;
+    // (round 5: not only when the den grid owns EVERY CU.  Between the staged schedule's limit -- three quarters of the CUs -- and a full device the
+    // chains ran beside the recursions on the few CUs they leave, 2 B chain workgroups on 256 - 2 B CUs, and took longer than the recursions: B = 100 /
+    // 104 / 112 / 120 4.40 / 4.54 / 4.82 / 5.16 ms per step; behind them, beside the den half of the grad pass: 4.28 / 4.38 / 4.48 / 4.61,
+    // profiles/round5_ab_grad_one_launch.txt)
+    const bool after = ctc_after_env >= 0 ? ctc_after_env != 0 : fac1 ? pl.den_wgs * 100 > (int64_t)pl.ncu * opt(kOpt_stage_fill, 75) : (pl.res && h->dev.res.K > 1);
+    if (after) {
+        // (the consistency check BEHIND the fork: the numerator chains -- a latency chain that wants its workgroups resident at once -- are
+        // released by the end of the recursions and get the CUs first; with the check in front of the fork the grad launch below, which
+        // follows it on this stream without an event in between, filled the device first: B = 128 ctc chains 1.5 -> 2.4 ms)
+        if ((rc = launch_den(stream, false))) return rc;
+        if ((rc = fork_side())) return rc;            // numerator pair starts when the den recursions have drained
+        if ((rc = launch_den_check(stream))) return rc;
+        if ((rc = launch_ctc_pair(p, pl.lds_ctc, side, a.max_label_len))) return rc;
+        prof_mark(5, false, stream);
+        if ((rc = grad_after_recursions(stream, 1))) return rc;
+        if ((rc = join_side())) return rc;
+        if ((rc = launch_grad_ctc(2, stream))) return rc;
+        prof_mark(5, true, stream);
+        return CRF_OK;
+    }
+    if ((rc = fork_side())) return rc;
+    if (fac1 && pl.have_flags) {   // the chains behind the start gate
+        if ((rc = launch_den(stream))) return rc;
+        if ((rc = launch<crf_gate_kernel>("crf_gate_kernel", dim3(1), dim3(1), 0, side, started(), (int)pl.den_wgs))) return rc;
+        if ((rc = launch_ctc_pair(p, pl.lds_ctc, side, a.max_label_len))) return rc;
+    } else {
+        if ((rc = launch_ctc_pair(p, pl.lds_ctc, side, a.max_label_len))) return rc;
+        if ((rc = launch_den(stream))) return rc;
+    }
+    if ((rc = join_side())) return rc;
+    prof_mark(5, false, stream);
+    if ((rc = grad_after_recursions(stream, 0))) return rc;
+    prof_mark(5, true, stream);
+    return CRF_OK;
+}
+
+// one stream: den only (gpu_den), numerator only (gpu_ctc / WARP_CTC_LOSS), or no side stream available
+int LossCall::run_one_stream() {
+    int rc;
+    if (pl.den && (rc = launch_den(stream))) return rc;
+    if (pl.ctc && (rc = launch_ctc_pair(p, pl.lds_ctc, stream, a.max_label_len))) return rc;
+    prof_mark(5, false, stream);
+    if ((rc = grad_after_recursions(stream, 0))) return rc;
+    prof_mark(5, true, stream);
+    return CRF_OK;
+}
+
+int LossCall::run_fallbacks_and_finalize() {
+    const HostGraph *h = pl.h;
+    int rc;
+    bool fin_folded = false;
+    if (pl.den && pl.robust_env != 0) {
+        // Fallback for utterances whose scaled-fp32 recursion lost all its mass: redone in a per-frame log-shifted form
+        // (crf_robust_den_kernel).  Workgroups of unflagged utterances leave at once -- two near-empty launches per call.
+        const bool rgv = w.gv_robust;
+        const size_t lr = robust_lds_bytes(h, (int)a.V, rgv);
+        const dim3 grid((unsigned)(2 * a.B)), block(kChainThreads);
+        if ((rc = rgv ? launch<crf_robust_den_kernel<true>>("crf_robust_den_kernel", grid, block, lr, stream, p)
+                      : launch<crf_robust_den_kernel<false>>("crf_robust_den_kernel", grid, block, lr, stream, p))) return rc;
+        const size_t lg = (size_t)rup64(h->dev.NC) * 4 + (size_t)rup64((int)a.V) * 12 + 64;
+        // (the call's sums in this launch unless the numerator's second fallback pass, which rewrites costs, is still to come)
+        fin_folded = !(pl.ctc && pl.robust_env != 0 && !ctc_pass1) && !opt_on(kOpt_no_fin_fold) && !g_prof.on;
+        p.fin_fold = fin_folded ? 1 : 0;
+        rc = launch<crf_robust_grad_kernel>("crf_robust_grad_kernel", dim3(16, (unsigned)a.B), dim3(kGradThreads), lg, stream, p);
+        p.fin_fold = 0;
+        if (rc) return rc;
+    }
+    // (the staged schedule's pass 1 ran behind the only kernel that marks frames: nothing is left for a second pass there)
+    if (pl.ctc && pl.robust_env != 0 && !ctc_pass1 && (rc = launch_robust_ctc(stream, 2))) return rc;
+    prof_mark(6, false, stream);
+    rc = fin_folded ? CRF_OK : launch<crf_finalize_kernel>("crf_finalize_kernel", dim3(1), dim3(256), 0, stream, p);
+    prof_mark(6, true, stream);
+    prof_mark(7, true, stream);
+    g_prof.have = g_prof.on;
+    return rc;
+}
+
+static int loss_impl(const crf_graph *g, const float *logp, int fused, int in_dtype, const int32_t *labels, const int32_t *lab_off,
+                     const int32_t *lx, const int32_t *ly, int64_t B, int64_t T, int64_t V,
+                     int64_t max_label_len, float c_den, float c_ctc, float *grad, float *loss,
+                     float *costs_den, float *costs_beta, float *costs_ctc, int32_t *invalid, void *ws,
+                     int64_t ws_bytes, void *stream_, int time_major, int blank) {
+    const LossArgs a{g, logp, fused, in_dtype, labels, lab_off, lx, ly, B, T, V, max_label_len, c_den, c_ctc, grad, loss,
+                     costs_den, costs_beta, costs_ctc, invalid, ws, ws_bytes, time_major, blank};
+    hipStream_t stream = (hipStream_t)stream_;
+    WsLayout w{};
+    CallPlan pl{};
+    int rc;
+    if ((rc = check_loss_args(a, w, pl))) return rc;
+    DevCtx *cx = nullptr;
+    if ((rc = get_ctx(stream, &cx))) return rc;
+    std::lock_guard<std::mutex> call_lock(cx->mu);
+    reprobe_side(cx, stream);
+    DevFacts f;
+    f.call_id = ++cx->call_id;
+    g_call_streams = 1;
+    g_side_desc = cx->side_desc;
+    (void)hipDeviceGetAttribute(&f.ncu, hipDeviceAttributeMultiprocessorCount, cx->dev);
     // The one-launch grad pass's workgroups wait inside the kernel for the recursions' stage counters (bounded: ~2 s of wall clock).  A time-out --
     // a den launch that aborted, a device shared with a process whose kernels keep the recursions off their CUs -- is written to a pinned host word;
     // a context that has seen one goes back to one grad launch per stage behind stream-level waits (round 4's schedule: nothing waits on the
@@ -1096,511 +1585,18 @@ static int loss_impl(const crf_graph *g, const float *logp, int fused, int in_dt
         fprintf(stderr, "[ctc_crf_hip] the one-launch grad pass timed out waiting for the denominator recursions in an earlier call (its loss was NaN): "
                         "this context now launches the grad pass stage by stage behind stream-level waits\n");
     }
-    const bool per_stage = opt_on(kOpt_gd_stage_launches) || cx->gd_fallback;
-    p.gd_timeout_host = cx->hostw ? cx->hostw + 4 : nullptr;
-    if (staged && T >= 256) nstage = plan_grad_stages(T, segmode, stages_env, pieces, bound, &gd_piece, per_stage ? 1 : 0);
-    p.gd_nb = nstage + 1;
-    for (int k = 0; k <= nstage && k < 16; ++k) p.gd_bound[k] = bound[k];
-    float *fstate = (float *)(base + w.off_state), *bstate = fstate + B * w.state_stride;
-    const size_t lds_fac = !fac ? 0 : pair2 ? std::max(fac2u_lds_bytes(*FX, (int)V, 0), fac2u_lds_bytes(*FX, (int)V, 1))
-                                              : std::max(fac_lds_bytes(h, (int)V, 0), fac_lds_bytes(h, (int)V, 1));
-    const size_t lds_ctc = chain_lds_bytes(h, (int)V, Sc, 2);
-
-    const dim3 ggrid((unsigned)((T + kGradFrames - 1) / kGradFrames), (unsigned)B);
-    auto launch_grad_den = [&](hipStream_t st, int stage, bool persist = false) -> int {
-        p.gd_stage = stage;
-        const size_t l = ((size_t)rup64((int)w.Rq + 1) + rup64((int)w.Rb + 1) + 4 * rup64((int)V) + kGDFrames + rup64(gnc)) * sizeof(float);
-        dim3 gg((unsigned)((T + kGDFrames - 1) / kGDFrames), (unsigned)B);
-        p.gd_nf = 0;
-        p.gd_persist = 0;
-        const bool full_grid = opt_on(kOpt_gd_full_grid);
-        if (persist) {   // the stages `stage` .. nstage in one launch (see the kernel): 2 * nf candidates per utterance and stage, stage-major
-            p.gd_persist = 1;
-            p.gd_cnt = cx->flags + 16;
-            p.gd_target = (int)(2 * B);
-            const int64_t tot = plan_grad_grid(p.gd_bound, p.gd_nb - 1, stage, B, gd_piece, p.gd_poff, p.gd_fpb);
-            gg = dim3((unsigned)tot, 1);
-        } else if (stage > 1 && !full_grid) {   // (stage 1 is the middle of every utterance: all blocks are candidates)
-            p.gd_nf = (p.gd_bound[stage] - p.gd_bound[stage - 1] + kGDFrames - 1) / kGDFrames + 3;
-            if (2 * p.gd_nf < (int)gg.x) gg.x = (unsigned)(2 * p.gd_nf); else p.gd_nf = 0;
-        }
-        static LdsMark set1, set2, set3, set5;
-        int r2;
-        if (gcap == 8) {              // chunk lists cut at 8 entries (many labels with few pairs each): 512 threads, two chunks each
-            static LdsMark set7;
-            if ((r2 = ensure_lds((const void *)crf_grad_den_kernel<2, 2, 2 * kGDThreads, 8>, l, set7, "grad den"))) return r2;
-            hipLaunchKernelGGL((crf_grad_den_kernel<2, 2, 2 * kGDThreads, 8>), gg, dim3(2 * kGDThreads), l, st, p);
-        } else if (gnc > 2 * kGDThreads) {   // more than 512 label chunks (graphs over hundreds of classes: V = 500 has ~8 pairs per label,
-                                      // one chunk each): 512 threads with two chunks each
-            static LdsMark set6;
-            if ((r2 = ensure_lds((const void *)crf_grad_den_kernel<2, 2, 2 * kGDThreads>, l, set6, "grad den"))) return r2;
-            hipLaunchKernelGGL((crf_grad_den_kernel<2, 2, 2 * kGDThreads>), gg, dim3(2 * kGDThreads), l, st, p);
-        } else if (gd_wide6) {        // rows of 10 241 .. 12 288 floats: 512 threads with six row registers each
-            static LdsMark set9;
-            if ((r2 = ensure_lds((const void *)crf_grad_den_kernel<1, 2, 2 * kGDThreads, kChunk, 6, 1>, l, set9, "grad den"))) return r2;
-            hipLaunchKernelGGL((crf_grad_den_kernel<1, 2, 2 * kGDThreads, kChunk, 6, 1>), gg, dim3(2 * kGDThreads), l, st, p);
-        } else if (gd_wide && CRF_X_GDW2 && w.Rq <= 32 * kGDThreads && w.Rb <= 32 * kGDThreads) {
-            // rows of 5121 .. 8192 floats: 512 threads with four row registers each, held to 128 VGPRs so that a CU takes TWO workgroups (the
-            // five-register form below compiles to 148 VGPRs: one workgroup, eight waves, per CU -- the estimated S = 6836 graph ran on that)
-            static LdsMark set8;
-            if ((r2 = ensure_lds((const void *)crf_grad_den_kernel<1, 2, 2 * kGDThreads, kChunk, 4, 4>, l, set8, "grad den"))) return r2;
-            hipLaunchKernelGGL((crf_grad_den_kernel<1, 2, 2 * kGDThreads, kChunk, 4, 4>), gg, dim3(2 * kGDThreads), l, st, p);
-        } else if (gd_wide) {   // rows of more than 5120 floats: 512 threads per workgroup (one chunk per thread up to 512 chunks)
-            if ((r2 = ensure_lds((const void *)crf_grad_den_kernel<1, 2, 2 * kGDThreads>, l, set5, "grad den"))) return r2;
-            hipLaunchKernelGGL((crf_grad_den_kernel<1, 2, 2 * kGDThreads>), gg, dim3(2 * kGDThreads), l, st, p);
-        } else if (gnc <= kGDThreads && V <= kGDThreads) {   // small vocabulary
-            if ((r2 = ensure_lds((const void *)crf_grad_den_kernel<1, 1>, l, set3, "grad den"))) return r2;
-            hipLaunchKernelGGL((crf_grad_den_kernel<1, 1>), gg, dim3(kGDThreads), l, st, p);
-        } else if (gnc <= kGDThreads) {
-            if ((r2 = ensure_lds((const void *)crf_grad_den_kernel<1, kGDEpRegs>, l, set1, "grad den"))) return r2;
-            hipLaunchKernelGGL((crf_grad_den_kernel<1, kGDEpRegs>), gg, dim3(kGDThreads), l, st, p);
-        } else {
-            if ((r2 = ensure_lds((const void *)crf_grad_den_kernel<2, kGDEpRegs>, l, set2, "grad den"))) return r2;
-            hipLaunchKernelGGL((crf_grad_den_kernel<2, kGDEpRegs>), gg, dim3(kGDThreads), l, st, p);
-        }
-        if ((e = hipGetLastError()) != hipSuccess) { set_error(std::string("crf_grad_den_kernel: ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
-        return CRF_OK;
-    };
-    auto launch_grad_ctc = [&](int phase, hipStream_t st) -> int {  // phase 2: subtract from the den half; 0: plain CTC (writes)
-        p.grad_phase = phase;
-        if (fast_ctc) {
-            const size_t l = (size_t)4 * rup64((int)V) * sizeof(float) + kGCFrames * sizeof(double) + 64;
-            const dim3 gg((unsigned)((T + kGCFrames - 1) / kGCFrames), (unsigned)B);
-            const int Sxm = 2 * (int)max_label_len + 1;
-            if (Sxm <= 2 * kGCThreads) hipLaunchKernelGGL(crf_grad_ctc_kernel<2>, gg, dim3(kGCThreads), l, st, p);
-            else if (Sxm <= 4 * kGCThreads) hipLaunchKernelGGL(crf_grad_ctc_kernel<4>, gg, dim3(kGCThreads), l, st, p);
-            else hipLaunchKernelGGL(crf_grad_ctc_kernel<kGCRegs>, gg, dim3(kGCThreads), l, st, p);
-        } else {
-            hipLaunchKernelGGL(crf_grad_kernel, ggrid, dim3(kGradThreads), lds_grad, st, p);
-        }
-        if ((e = hipGetLastError()) != hipSuccess) { set_error(std::string("crf_grad(ctc): ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
-        return CRF_OK;
-    };
-    // Numerator fallback: utterances with frames the grad pass marked (or whose scaled chain lost its mass) redo their chains in the
-    // log domain, then the marked frames' posteriors are subtracted from the rows; the other utterances' workgroups leave at once --
-    // two near-empty launches.  Pass 1 runs right behind the numerator's grad half on the side stream of the staged schedule, i.e.
-    // BESIDE the denominator recursions (V = 500: 1.2 ms that followed the call's last grad launch); pass 2 at the end of every call
-    // takes what is marked and was not redone in pass 1.
-    auto launch_robust_ctc_chains = [&](hipStream_t st, int pass) -> int {
-        static LdsMark mrc[4];
-        int r2;
-        const int64_t ni = (2 * max_label_len + 1 + kCtcThreads - 1) / kCtcThreads;
-        const int nri = ni <= 1 ? 0 : ni <= 2 ? 1 : ni <= 4 ? 2 : 3;
-        const void *fn = nri == 0 ? (const void *)crf_robust_ctc_kernel<1> : nri == 1 ? (const void *)crf_robust_ctc_kernel<2>
-                       : nri == 2 ? (const void *)crf_robust_ctc_kernel<4> : (const void *)crf_robust_ctc_kernel<kCtcRegs>;
-        if ((r2 = ensure_lds(fn, lds_ctc, mrc[nri], "robust ctc"))) return r2;
-        p.ctc_pass = pass;
-        switch (nri) {
-            case 0: hipLaunchKernelGGL(crf_robust_ctc_kernel<1>, dim3((unsigned)(2 * B)), dim3(kCtcThreads), lds_ctc, st, p); break;
-            case 1: hipLaunchKernelGGL(crf_robust_ctc_kernel<2>, dim3((unsigned)(2 * B)), dim3(kCtcThreads), lds_ctc, st, p); break;
-            case 2: hipLaunchKernelGGL(crf_robust_ctc_kernel<4>, dim3((unsigned)(2 * B)), dim3(kCtcThreads), lds_ctc, st, p); break;
-            default: hipLaunchKernelGGL(crf_robust_ctc_kernel<kCtcRegs>, dim3((unsigned)(2 * B)), dim3(kCtcThreads), lds_ctc, st, p); break;
-        }
-        if ((e = hipGetLastError()) != hipSuccess) { set_error(std::string("crf_robust_ctc_kernel: ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
-        return CRF_OK;
-    };
-    auto launch_robust_ctc_fix = [&](hipStream_t st, int pass) -> int {
-        p.ctc_pass = pass;
-        hipLaunchKernelGGL(crf_robust_ctc_fix_kernel, dim3((unsigned)((T + kGCFrames - 1) / kGCFrames), (unsigned)B), dim3(kGradThreads),
-                           (size_t)rup64((int)V) * sizeof(float), st, p);
-        if ((e = hipGetLastError()) != hipSuccess) { set_error(std::string("crf_robust_ctc_fix_kernel: ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
-        return CRF_OK;
-    };
-    auto launch_robust_ctc = [&](hipStream_t st, int pass) -> int {
-        const int r2 = launch_robust_ctc_chains(st, pass);
-        return r2 ? r2 : launch_robust_ctc_fix(st, pass);
-    };
-    // forward log Z = backward log Z?  (crf_den_check_kernel: behind every launch of the recursions, on their stream -- in the staged schedule
-    // it runs while the side stream finishes the grad pass -- and in front of the fallback kernels, which take what it flags)
-    auto launch_den_check = [&](hipStream_t st) -> int {
-        if (!den || robust_env == 0) return CRF_OK;
-        hipLaunchKernelGGL(crf_den_check_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, p, (res || fac) ? 1 : 0);
-        if ((e = hipGetLastError()) != hipSuccess) { set_error(std::string("crf_den_check_kernel: ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
-        return CRF_OK;
-    };
-    // the denominator recursions of the whole batch on `st` (every layout; both directions per launch)
-    auto launch_den = [&](hipStream_t st, bool with_check = true) -> int {
-        prof_mark(1, false, st); prof_mark(2, false, st);
-        int r2 = CRF_OK;
-        const CoresGuard cores((fac && FX->K > 1) || (res && !fac && h->dev.res.K > 1), cx->dev, st);
-        if (fac && FX->K > 1) {
-            const int grp = std::max(1, ncu_dev / 4);
-            for (int b0 = 0; b0 < (int)B && !r2; b0 += grp) r2 = launch_fac2_pair(p, lds_fac, st, b0, std::min(grp, (int)B - b0));
-        } else if (fac && pair2) {
-            r2 = launch_fac_pair2<false>(p, lds_fac, st, started);
-        } else if (fac) {
-            r2 = launch_fac_pair<false>(p, lds_fac, st, started, 0, (int)T, fstate, bstate);
-        } else if (res) {
-            // K CUs per utterance and direction exchange the state vector through L2 every frame.  With K > 1 every
-            // workgroup of a launch must be resident at once (its peers spin on it): groups of at most CUs/(2K) utterances.
-            const int K = h->dev.res.K;
-            const int grp = K > 1 ? std::max(1, ncu_dev / (2 * K)) : (int)B;
-            const size_t l = std::max(res_lds_bytes(h, (int)V, 0, h->res_rows_cu_f), res_lds_bytes(h, (int)V, 1, h->res_rows_cu_b));
-            for (int b0 = 0; b0 < (int)B && !r2; b0 += grp) r2 = launch_res_pair(p, l, b0, std::min(grp, (int)B - b0), st);
-        } else if (gv) {
-            r2 = launch_den_pair<true>(p, std::max(chain_lds_bytes(h, (int)V, Sc, 0, true), chain_lds_bytes(h, (int)V, Sc, 1, true)), st);
-            return (r2 || !with_check) ? r2 : launch_den_check(st);
-        } else {
-            r2 = launch_den_pair<false>(p, std::max(chain_lds_bytes(h, (int)V, Sc, 0), chain_lds_bytes(h, (int)V, Sc, 1)), st);
-            return (r2 || !with_check) ? r2 : launch_den_check(st);
-        }
-        prof_mark(1, true, st); prof_mark(2, true, st);
-        return (r2 || !with_check) ? r2 : launch_den_check(st);
-    };
-
-    // Three streams (round 5, switch grad_par3; OFF): the numerator half of the grad pass (side stream) and the staged den half (third stream)
-    // run BESIDE each other and both ADD into gradient rows the prep kernel has zeroed (0 + x + y: two addends per element, the same bits
-    // in either order).  The idea: on one stream the stages queue behind the numerator chains and their grad half, and graphs whose
-    // recursions are shorter than that (S = 513: recursions 1.25 ms, step 1.92) wait for them.  Measured SLOWER everywhere
-    // (profiles/round5_ab_three_streams.txt: metric 2.79 -> 2.85 ms, S = 513 1.92 -> 2.01, V = 217 3.39 -> 3.51, estimated S = 3 006 2.44 -> 2.78):
-    // the stage workgroups then share the free CUs with the numerator chains -- a serial fp64 latency chain whose frames get longer -- and
-    // what the stages gain by starting early the chains lose.  Not when a recent call needed the numerator's log-domain fallback (the
-    // third stream then carries its chains), nor in segment mode.
-    const int aux_env0 = opt(kOpt_aux_stream, -1);
-    const int seen0 = cx->seen ? *(volatile int *)cx->seen : 0;
-    const bool ctc_wants_aux = aux_env0 >= 0 ? aux_env0 != 0 : (seen0 > 0 && p.call_id - seen0 <= 16);
-    const bool par3 = staged && !segmode && cx->aux != nullptr && !(robust_env != 0 && ctc_wants_aux) && opt(kOpt_grad_par3, 0) != 0;
-    p.zero_grad = par3 ? 1 : 0;
-    for (bool &u : g_prof.used) u = false;
-    prof_mark(7, false, stream);
-    prof_mark(0, false, stream);
-    if (V <= 256) hipLaunchKernelGGL(crf_prep_kernel<16>, dim3((unsigned)((frames + 15) / 16)), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL(crf_prep_kernel<64>, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, stream, p);
-    prof_mark(0, true, stream);
-    LAUNCH_CHECK("crf_prep_kernel");
-    if (res && (w.xch_bytes > 0 || !have_flags)) {  // exchange granules (tags) and the error word start at zero in every call
-        if ((e = hipMemsetAsync(p.xch, 0, (size_t)w.xch_bytes + 256 + 8 * (size_t)B, stream)) != hipSuccess) { set_error("hipMemsetAsync(xch)"); return CRF_ERR_HIP; }
-    }
-
-    if (bat) {
-        // Utterance-minor denominator (large graphs): one launch per frame on the caller's stream, forward step of
-        // frame j and backward step of frame T - j together; the numerator pair runs beside them on the side stream.
-        BatchParams bp{};
-        bp.g = h->dev.bat; bp.start_lin = h->dev.start_lin; bp.end_lin = h->dev.end_lin;
-        bp.S = h->dev.S; bp.P = h->dev.P; bp.B = (int)B; bp.Bp = (int)w.Bp; bp.T = (int)T; bp.V = (int)V; bp.max_label = h->dev.max_label;
-        bp.lx = lx; bp.ep = p.ep; bp.moff = p.moff;
-        bp.ept = (float *)(base + w.off_ept); bp.Af = (float *)(base + w.off_Af); bp.Zb = (float *)(base + w.off_Zb);
-        bp.Q = p.Q; bp.BP = p.BP;
-        unsigned *bsm = (unsigned *)(base + w.off_bsm);
-        bp.mxf = bsm; bp.mxb = bsm + 3 * w.Bp; bp.Ef = (int *)(bsm + 6 * w.Bp); bp.Fb = (int *)(bsm + 7 * w.Bp);
-        bp.zs = (float *)(bsm + 8 * w.Bp); bp.zb = (float *)(bsm + 9 * w.Bp);
-        bp.bar = bsm + 12 * w.Bp; bp.err = (int *)(bsm + 12 * w.Bp + 512);
-        bp.den_zs = p.den_zs; bp.cost_alpha = p.cost_alpha; bp.cost_beta = p.cost_beta; bp.den_ez = p.den_ez; bp.redo = p.redo;
-        bp.grad = grad; bp.c_den = c_den;
-        const unsigned ngrp = (unsigned)(w.Bp / w.UL);
-        bp.ngrp = (int)ngrp;
-        // one task per wave, ONE round of workgroups (a second round with a fraction of the device doubled the launch):
-        // the tasks wanted per direction follow from the occupancy the runtime reports, shared by the combos
-        const int64_t ncombo = 2 * (int64_t)ngrp;
-        const bool bfac = stream_fac(g->h, w.UL);                  // factored streams (T o LM graphs, groups of >= 32 utterances)
-        // ALL frames in one persistent launch (round 6) when its grid is co-resident by the runtime's own count -- switch bat_persist: 0 =
-        // one launch per frame (rounds 2 - 5; also the fallback), 1 = persistent (default)
-        const bool want_persist = opt(kOpt_bat_persist, 1) != 0;
-        auto bat_fn = [&](bool persist) -> const void * {
-#define CRF_BAT_FN(K) (w.UL == 64 ? (bfac ? (const void *)K<64, 4, true> : (const void *)K<64, 4, false>)    \
-                     : w.UL == 32 ? (bfac ? (const void *)K<32, 4, true> : (const void *)K<32, 4, false>)    \
-                     : w.UL == 16 ? (bfac ? (const void *)K<16, 4, true> : (const void *)K<16, 4, false>)    \
-                                  : (bfac ? (const void *)K<8, 4, true> : (const void *)K<8, 4, false>))
-            return persist ? CRF_BAT_FN(crf_batch_persist_kernel) : CRF_BAT_FN(crf_batch_frame_kernel);
-#undef CRF_BAT_FN
-        };
-        int wg_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg_cu, bat_fn(want_persist), kBatThreads, 0) != hipSuccess || wg_cu < 1) { (void)hipGetLastError(); wg_cu = want_persist ? 0 : 2; }
-        bool persist = want_persist && wg_cu >= 1;
-        if (want_persist && !persist) wg_cu = 2;
-        // ... times 70 %: a launch is bound by the L2s and the fabric, not by the CUs, and fewer, longer tasks pay the task set-up
-        // (three dependent trips to a cold L2) less often.  Measured, S = 16 385 / B = 64 (repeatable to 0.3 %): 100 / 85 / 70 /
-        // 60 / 55 / 45 / 35 % -> 30.7 / 29.5 / 28.8 / 30.6 / 31.8 / 28.5 / 31.3 ms per step (the dips: workgroups per XCD just
-        // above a multiple of its 32 CUs); config #5 at B = 8: 100 / 70 / 50 % -> 145.3 / 143.6 / 152.6 ms.  CRF_BAT_FILL overrides.
-        const int fill_env = opt(kOpt_bat_fill, 0);
-        const int64_t fill = fill_env > 0 && fill_env <= 100 ? fill_env : 70;
-        const int64_t slots = (int64_t)ncu_dev * wg_cu;            // workgroups the device holds at once
-        const int want = (int)std::max<int64_t>(16, (int64_t)ncu_dev * wg_cu * kBatWaves * 15 / 16 * fill / 100 / ncombo);
-        const StreamDev *sdv = nullptr;
-        if ((rc = ensure_stream_tables(g->h, w.UL, want, &sdv))) return rc;
-        if ((sdv->fac != 0) != bfac) { set_error("arc streams: factored / plain mismatch"); return CRF_ERR_ARG; }
-        bp.SX = h->dev.S + sdv->NU; bp.x_start = sdv->x_start;
-        bp.st = *sdv;
-        // 8 * nslot workgroups (block b -> XCD b % 8, slot b / 8): every combo gets at least one wave per task of its arc
-        // stream (crf_batch_frame_kernel: a combo has nslot * nk or about nslot / ncx workgroups)
-        const int64_t tasks_max = std::max({(int64_t)sdv->f.ntasks, (int64_t)sdv->b.ntasks, (int64_t)1});
-        const int64_t wg_combo = (tasks_max + kBatWaves - 1) / kBatWaves + ((sdv->f.nrest > 64 || sdv->b.nrest > 64) ? (std::max(sdv->f.nrest, sdv->b.nrest) + 4 * kBatWaves - 1) / (4 * kBatWaves) : 0);
-        const unsigned nslot = (unsigned)(ncombo < 8 ? (wg_combo + (8 / ncombo) - 1) / (8 / ncombo) : wg_combo * ((ncombo + 7) / 8));
-        const unsigned G = 8 * nslot;
-        if (persist && (int64_t)G > slots) persist = false;        // (the grid barrier needs every workgroup resident)
-        // The numerator chains run BESIDE the per-frame launches (side stream) but BEHIND the persistent launch, beside the grad pass: a
-        // co-resident grid sized for the device's slots must not share them -- with the chains' 2 B workgroups on the CUs, G = 416 of 512
-        // slots no longer fitted at once (S = 12 289, B = 64: a CU that holds a chain workgroup has LDS for one workgroup of this kernel,
-        // not two), the rest of the grid waited for the chains, and the runtime time-sliced the queues: 1.7 ms per frame instead of 13 us
-        // and barrier time-outs (profiles/round6_ab_persistent_batch.txt)
-        if (ctc && !persist) {
-            if ((rc = fork_side())) return rc;
-            if ((rc = launch_ctc_pair(p, lds_ctc, side, max_label_len))) return rc;
-        }
-        if (opt_on(kOpt_verbose)) fprintf(stderr, "[ctc_crf_hip] utterance-minor: UL %d, %d combos, tasks %d / %d, rest rows %d / %d, grid %u of %lld slots (%d per CU), %s\n", (int)w.UL, (int)ncombo,
-                                          sdv->f.ntasks, sdv->b.ntasks, sdv->f.nrest, sdv->b.nrest, G, (long long)slots, wg_cu, persist ? "one persistent launch" : "one launch per frame");
-        prof_mark(1, false, stream); prof_mark(2, false, stream);
-#define CRF_BAT_UL(KERNEL, GRID, ...)                                                                        \
-        switch (w.UL) {                                                                                       \
-            case 64: hipLaunchKernelGGL(KERNEL<64>, GRID, dim3(kBatThreads), 0, stream, __VA_ARGS__); break;  \
-            case 32: hipLaunchKernelGGL(KERNEL<32>, GRID, dim3(kBatThreads), 0, stream, __VA_ARGS__); break;  \
-            case 16: hipLaunchKernelGGL(KERNEL<16>, GRID, dim3(kBatThreads), 0, stream, __VA_ARGS__); break;  \
-            default: hipLaunchKernelGGL(KERNEL<8>, GRID, dim3(kBatThreads), 0, stream, __VA_ARGS__); break;   \
-        }
-        CRF_BAT_UL(crf_batch_transpose_kernel, dim3((unsigned)((V + 63) / 64), (unsigned)T, ngrp), bp);
-        hipLaunchKernelGGL(crf_batch_init_kernel, dim3((unsigned)(((int64_t)bp.SX * w.Bp + kBatThreads - 1) / kBatThreads)), dim3(kBatThreads), 0, stream, bp);
-        LAUNCH_CHECK("crf_batch_init_kernel");
-        static const char *const kBatNames[2][4][2] = {
-            {{"crf_batch_frame_kernel<8,4,false>", "crf_batch_frame_kernel<8,4,true>"}, {"crf_batch_frame_kernel<16,4,false>", "crf_batch_frame_kernel<16,4,true>"},
-             {"crf_batch_frame_kernel<32,4,false>", "crf_batch_frame_kernel<32,4,true>"}, {"crf_batch_frame_kernel<64,4,false>", "crf_batch_frame_kernel<64,4,true>"}},
-            {{"crf_batch_persist_kernel<8,4,false>", "crf_batch_persist_kernel<8,4,true>"}, {"crf_batch_persist_kernel<16,4,false>", "crf_batch_persist_kernel<16,4,true>"},
-             {"crf_batch_persist_kernel<32,4,false>", "crf_batch_persist_kernel<32,4,true>"}, {"crf_batch_persist_kernel<64,4,false>", "crf_batch_persist_kernel<64,4,true>"}}};
-        g_den_kernel = kBatNames[persist ? 1 : 0][w.UL == 64 ? 3 : w.UL == 32 ? 2 : w.UL == 16 ? 1 : 0][bfac ? 1 : 0];
-        {
-            void *args[] = {(void *)&bp};
-            const void *fn = bat_fn(persist);
-            if (persist) {
-                // (co-resident grids of two callers must not interleave: each could become partially resident and wait for the rest)
-                CoresGuard guard(true, cx->dev, stream);
-                bp.j = 0;
-                if ((e = hipLaunchKernel(fn, dim3(G), dim3(kBatThreads), args, 0, stream)) != hipSuccess) { set_error(std::string("crf_batch_persist_kernel: ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
-            } else {
-                for (int j = 0; j <= (int)T; ++j) {   // (4: batches of gathers in flight per wave; 2 measured 6 % slower, 8 needs more registers than a wave has)
-                    bp.j = j;
-                    if ((e = hipLaunchKernel(fn, dim3(G), dim3(kBatThreads), args, 0, stream)) != hipSuccess) { set_error(std::string("crf_batch_frame_kernel: ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
-                }
-            }
-        }
-        LAUNCH_CHECK("crf_batch_frame_kernel");
-        if (ctc && persist) {
-            if ((rc = fork_side())) return rc;
-            if ((rc = launch_ctc_pair(p, lds_ctc, side, max_label_len))) return rc;
-        }
-        CRF_BAT_UL(crf_batch_zsum_kernel, dim3((unsigned)((h->dev.S + 255) / 256), 1, ngrp), bp);
-        hipLaunchKernelGGL(crf_batch_cost_kernel, dim3((unsigned)B), dim3(kBatThreads), 0, stream, bp);
-        prof_mark(1, true, stream); prof_mark(2, true, stream);
-        if ((rc = launch_den_check(stream))) return rc;
-        prof_mark(5, false, stream);
-        CRF_BAT_UL(crf_batch_grad_kernel, dim3((unsigned)T, 1, ngrp), bp);
-#undef CRF_BAT_UL
-        LAUNCH_CHECK("crf_batch_grad_kernel");
-        if ((rc = join_side())) return rc;
-        if (ctc && (rc = launch_grad_ctc(2, stream))) return rc;
-        prof_mark(5, true, stream);
-    } else if (staged) {
-        // caller's stream: the denominator pair.  Side stream, behind a short bounded start gate: numerator pair, its
-        // grad half (writes -c_ctc * gamma_ctc), then the den half of the grad pass stage by stage (adds gamma_den).
-        if ((rc = fork_side())) return rc;
-        prof_mark(1, false, stream); prof_mark(2, false, stream);
-        if (pair2) {
-            if ((rc = launch_fac_pair2<true>(p, lds_fac, stream, started, nstage + 1, bound, cx->flags + 16))) return rc;
-        } else if (!segmode) {
-            if ((rc = launch_fac_pair<true>(p, lds_fac, stream, started, 0, (int)T, fstate, bstate, nstage + 1, bound, cx->flags + 16))) return rc;
-        } else {
-            for (int k = 0; k < nstage; ++k) {
-                if ((rc = launch_fac_pair<false>(p, lds_fac, stream, started, bound[k], bound[k + 1], fstate, bstate))) return rc;
-                if ((e = hipEventRecord(cx->ev[k], stream)) != hipSuccess) { set_error(std::string("hipEventRecord(segment): ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
-            }
-        }
-        prof_mark(1, true, stream); prof_mark(2, true, stream);
-        if ((rc = launch_den_check(stream))) return rc;
-        // hold the numerator back (briefly, bounded) until the den workgroups have their CUs
-        hipLaunchKernelGGL(crf_gate_kernel, dim3(1), dim3(1), 0, side, started, (int)den_wgs);
-        if ((rc = launch_ctc_pair(p, lds_ctc, side, max_label_len))) return rc;
-        prof_mark(5, false, side);
-        if ((rc = launch_grad_ctc(par3 ? 3 : 0, side))) return rc;
-        if (par3) {
-            // the den half of the grad pass on the THIRD stream, stage by stage behind the same stream-level waits, adding with atomics;
-            // the side stream goes on with the numerator (fallback chains, if any) and takes the third stream back in behind it
-            if ((e = hipStreamWaitEvent(cx->aux, cx->fork, 0)) != hipSuccess) { set_error(std::string("hipStreamWaitEvent(aux fork): ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
-            p.grad_den_acc = 2;
-            for (int k = 0; k < nstage; ++k) {
-                if ((e = hipStreamWaitValue32(cx->aux, cx->flags + 16 + k + 1, (uint32_t)(2 * B), hipStreamWaitValueGte, 0xffffffffu)) != hipSuccess) {
-                    // not available here: from the next call on, segments (and no third stream).  This call: wait for the recursions to END
-                    (void)hipGetLastError();
-                    use_segments = true;
-                    if ((e = hipEventRecord(cx->ev[0], stream)) != hipSuccess || (e = hipStreamWaitEvent(cx->aux, cx->ev[0], 0)) != hipSuccess) {
-                        set_error(std::string("hipStreamWaitEvent: ") + hipGetErrorString(e)); return CRF_ERR_HIP;
-                    }
-                }
-                if ((rc = launch_grad_den(cx->aux, k + 1))) return rc;
-            }
-            if ((e = hipEventRecord(cx->ev_b, cx->aux)) != hipSuccess) { set_error(std::string("hipEventRecord(aux): ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
-            g_call_streams = 3;
-            ctc_pass1 = robust_env != 0;
-            if (ctc_pass1 && (rc = launch_robust_ctc_chains(side, 1))) return rc;
-            if ((e = hipStreamWaitEvent(side, cx->ev_b, 0)) != hipSuccess) { set_error(std::string("hipStreamWaitEvent(aux): ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
-            // (the marked frames' posteriors are subtracted behind BOTH halves: a plain read-modify-write of rows nobody adds to any more)
-            if (ctc_pass1 && (rc = launch_robust_ctc_fix(side, 1))) return rc;
-            prof_mark(5, true, side);
-            if ((rc = join_side())) return rc;
-        } else {
-        // Numerator fallback, pass 1.  The chains of the marked utterances can take as long as the scaled ones did (T = 3 000, L = 500,
-        // every utterance marked: 3 ms): on the third stream they run beside the grad stages instead of in front of them, and the
-        // marked frames' posteriors are subtracted behind the last stage (the stages ADD gamma_den: the order does not matter).
-        // Enqueued BEFORE the stage waits of the side stream: whatever hardware queues the three streams share, the chains' packets
-        // precede the wait for their event.
-        bool aux_fix = false;
-        ctc_pass1 = robust_env != 0;
-        if (robust_env != 0) {
-            // (the third stream costs the call ~20 us of event traffic whether or not an utterance is marked -- B = 64, T = 1 500: 3.172 ->
-            // 3.192 ms -- so it is taken when one of this context's last 16 calls ran the log-domain chains: they write the call's
-            // number to a pinned host word, read here without any synchronisation; `aux_stream` 1 / 0 forces it on / off)
-            const int aux_env = opt(kOpt_aux_stream, -1);
-            const int seen = cx->seen ? *(volatile int *)cx->seen : 0;
-            const bool want_aux = aux_env >= 0 ? aux_env != 0 : (seen > 0 && p.call_id - seen <= 16);
-            if (cx->aux && want_aux && hipEventRecord(cx->ev_a, side) == hipSuccess && hipStreamWaitEvent(cx->aux, cx->ev_a, 0) == hipSuccess) {
-                if ((rc = launch_robust_ctc_chains(cx->aux, 1))) return rc;
-                if ((e = hipEventRecord(cx->ev_b, cx->aux)) != hipSuccess) { set_error(std::string("hipEventRecord(aux): ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
-                aux_fix = true;
-                g_call_streams = 3;
-            } else {
-                (void)hipGetLastError();
-                if ((rc = launch_robust_ctc_chains(side, 1))) return rc;
-            }
-        }
-        p.grad_den_acc = 1;
-        // (one launch for the stages 2 ..: behind stage 1's wait -- every recursion has run half of its frames, every den workgroup is resident)
-        const bool gd_one = !segmode && nstage >= 3 && !per_stage;
-        for (int k = 0; k < nstage; ++k) {
-            if (gd_one && k == 1) { if ((rc = launch_grad_den(side, 2, true))) return rc; break; }
-            if (!segmode) {
-                if ((e = hipStreamWaitValue32(side, cx->flags + 16 + k + 1, (uint32_t)(2 * B), hipStreamWaitValueGte, 0xffffffffu)) != hipSuccess) {
-                    // not available here: from the next call on, segments.  This call: wait for the recursions to END
-                    (void)hipGetLastError();
-                    use_segments = true;
-                    if ((e = hipEventRecord(cx->ev[0], stream)) != hipSuccess || (e = hipStreamWaitEvent(side, cx->ev[0], 0)) != hipSuccess) {
-                        set_error(std::string("hipStreamWaitEvent: ") + hipGetErrorString(e)); return CRF_ERR_HIP;
-                    }
-                }
-            } else if ((e = hipStreamWaitEvent(side, cx->ev[k], 0)) != hipSuccess) {
-                set_error(std::string("hipStreamWaitEvent(segment): ") + hipGetErrorString(e)); return CRF_ERR_HIP;
-            }
-            if ((rc = launch_grad_den(side, k + 1))) return rc;
-        }
-        // The marked frames' posteriors are subtracted at ONE place whichever stream ran the chains -- behind the last stage -- so that
-        // the order of the float additions into `grad` (and with it every bit of the gradient) does not depend on the unsynchronised
-        // hint above (round-3 advisor: with the chains on the side stream the subtraction used to precede the stages).
-        if (aux_fix && (e = hipStreamWaitEvent(side, cx->ev_b, 0)) != hipSuccess) { set_error(std::string("hipStreamWaitEvent(aux): ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
-        if (ctc_pass1 && (rc = launch_robust_ctc_fix(side, 1))) return rc;
-        prof_mark(5, true, side);
-        if ((rc = join_side())) return rc;   // the last grad launch is behind every stage of the recursions
-        }
-    } else if (den && ctc && !serial) {
-        // Denominator pair on the caller's stream, numerator pair beside it on the side stream -- unless the den
-        // workgroups own every CU (register-resident layouts with 2B (x K) >= CUs): then the numerator recursions run
-        // beside the DEN HALF of the grad pass instead (HBM-bound, small workgroups that share CUs happily).
-        const int ctc_after_env = opt(kOpt_ctc_after, -1);
-        // (factored, one CU per recursion: the den grid leaves ncu - den_wgs CUs free -- B = 96: 64 of them -- and the numerator
-        // chains, four workgroups to a CU, run there beside it, behind the start gate so that the den workgroups get their CUs first)
-        const bool fac1 = fac && FX->K == 1;
-        // (round 5: not only when the den grid owns EVERY CU.  Between the staged schedule's limit -- three quarters of the CUs -- and a full device the
-        // chains ran beside the recursions on the few CUs they leave, 2 B chain workgroups on 256 - 2 B CUs, and took longer than the recursions: B = 100 /
-        // 104 / 112 / 120 4.40 / 4.54 / 4.82 / 5.16 ms per step; behind them, beside the den half of the grad pass: 4.28 / 4.38 / 4.48 / 4.61,
-        // profiles/round5_ab_grad_one_launch.txt)
-        const bool after = ctc_after_env >= 0 ? ctc_after_env != 0 : fac1 ? den_wgs * 100 > (int64_t)ncu_dev * opt(kOpt_stage_fill, 75) : (res && h->dev.res.K > 1);
-        if (!after && fac1 && have_flags) {
-            if ((rc = fork_side())) return rc;
-            if ((rc = launch_den(stream))) return rc;
-            hipLaunchKernelGGL(crf_gate_kernel, dim3(1), dim3(1), 0, side, started, (int)den_wgs);
-            if ((rc = launch_ctc_pair(p, lds_ctc, side, max_label_len))) return rc;
-            if ((rc = join_side())) return rc;
-            prof_mark(5, false, stream);
-            if (fast_den) {
-                if ((rc = launch_grad_den(stream, 0))) return rc;
-                if ((rc = launch_grad_ctc(2, stream))) return rc;
-            } else {
-                p.grad_phase = 0;
-                hipLaunchKernelGGL(crf_grad_kernel, ggrid, dim3(kGradThreads), lds_grad, stream, p);
-                LAUNCH_CHECK("crf_grad_kernel");
-            }
-            prof_mark(5, true, stream);
-        } else if (!after) {
-            if ((rc = fork_side())) return rc;
-            if ((rc = launch_ctc_pair(p, lds_ctc, side, max_label_len))) return rc;
-            if ((rc = launch_den(stream))) return rc;
-            if ((rc = join_side())) return rc;
-            prof_mark(5, false, stream);
-            if (fast_den) {
-                if ((rc = launch_grad_den(stream, 0))) return rc;
-                if ((rc = launch_grad_ctc(2, stream))) return rc;
-            } else {
-                p.grad_phase = 0;
-                hipLaunchKernelGGL(crf_grad_kernel, ggrid, dim3(kGradThreads), lds_grad, stream, p);
-                LAUNCH_CHECK("crf_grad_kernel");
-            }
-            prof_mark(5, true, stream);
-        } else {
-            // (the consistency check BEHIND the fork: the numerator chains -- a latency chain that wants its workgroups resident at once -- are
-            // released by the end of the recursions and get the CUs first; with the check in front of the fork the grad launch below, which
-            // follows it on this stream without an event in between, filled the device first: B = 128 ctc chains 1.5 -> 2.4 ms)
-            if ((rc = launch_den(stream, false))) return rc;
-            if ((rc = fork_side())) return rc;            // numerator pair starts when the den recursions have drained
-            if ((rc = launch_den_check(stream))) return rc;
-            if ((rc = launch_ctc_pair(p, lds_ctc, side, max_label_len))) return rc;
-            prof_mark(5, false, stream);
-            if (fast_den) {
-                if ((rc = launch_grad_den(stream, 0))) return rc;
-            } else {
-                p.grad_phase = 1;
-                hipLaunchKernelGGL(crf_grad_kernel, ggrid, dim3(kGradThreads), lds_grad, stream, p);
-                LAUNCH_CHECK("crf_grad_kernel(den)");
-            }
-            if ((rc = join_side())) return rc;
-            if ((rc = launch_grad_ctc(2, stream))) return rc;
-            prof_mark(5, true, stream);
-        }
-    } else {
-        // one stream: den only (gpu_den), numerator only (gpu_ctc / WARP_CTC_LOSS), or no side stream available
-        if (den && (rc = launch_den(stream))) return rc;
-        if (ctc && (rc = launch_ctc_pair(p, lds_ctc, stream, max_label_len))) return rc;
-        prof_mark(5, false, stream);
-        if (den && fast_den) {
-            if ((rc = launch_grad_den(stream, 0))) return rc;
-            if (ctc && (rc = launch_grad_ctc(2, stream))) return rc;
-        } else if (!den && fast_ctc) {
-            if ((rc = launch_grad_ctc(0, stream))) return rc;
-        } else {
-            p.grad_phase = 0;
-            hipLaunchKernelGGL(crf_grad_kernel, ggrid, dim3(kGradThreads), lds_grad, stream, p);
-            LAUNCH_CHECK("crf_grad_kernel");
-        }
-        prof_mark(5, true, stream);
-    }
-    bool fin_folded = false;
-    if (den && robust_env != 0) {
-        // Fallback for utterances whose scaled-fp32 recursion lost all its mass: redone in a per-frame log-shifted form
-        // (crf_robust_den_kernel).  Workgroups of unflagged utterances leave at once -- two near-empty launches per call.
-        static LdsMark mr, mrg, mg;
-        const bool rgv = w.gv_robust;
-        const size_t lr = robust_lds_bytes(h, (int)V, rgv);
-        if (rgv) {
-            if ((rc = ensure_lds((const void *)crf_robust_den_kernel<true>, lr, mrg, "robust den"))) return rc;
-            hipLaunchKernelGGL(crf_robust_den_kernel<true>, dim3((unsigned)(2 * B)), dim3(kChainThreads), lr, stream, p);
-        } else {
-            if ((rc = ensure_lds((const void *)crf_robust_den_kernel<false>, lr, mr, "robust den"))) return rc;
-            hipLaunchKernelGGL(crf_robust_den_kernel<false>, dim3((unsigned)(2 * B)), dim3(kChainThreads), lr, stream, p);
-        }
-        LAUNCH_CHECK("crf_robust_den_kernel");
-        const size_t lg = (size_t)rup64(h->dev.NC) * 4 + (size_t)rup64((int)V) * 12 + 64;
-        if ((rc = ensure_lds((const void *)crf_robust_grad_kernel, lg, mg, "robust grad"))) return rc;
-        // (the call's sums in this launch unless the numerator's second fallback pass, which rewrites costs, is still to come)
-        fin_folded = !(ctc && robust_env != 0 && !ctc_pass1) && !opt_on(kOpt_no_fin_fold) && !g_prof.on;
-        p.fin_fold = fin_folded ? 1 : 0;
-        hipLaunchKernelGGL(crf_robust_grad_kernel, dim3(16, (unsigned)B), dim3(kGradThreads), lg, stream, p);
-        p.fin_fold = 0;
-        LAUNCH_CHECK("crf_robust_grad_kernel");
-    }
-    // (the staged schedule's pass 1 ran behind the only kernel that marks frames: nothing is left for a second pass there)
-    if (ctc && robust_env != 0 && !ctc_pass1 && (rc = launch_robust_ctc(stream, 2))) return rc;
-    prof_mark(6, false, stream);
-    if (!fin_folded) hipLaunchKernelGGL(crf_finalize_kernel, dim3(1), dim3(256), 0, stream, p);
-    prof_mark(6, true, stream);
-    prof_mark(7, true, stream);
-    g_prof.have = g_prof.on;
-    LAUNCH_CHECK("crf_finalize_kernel");
-#undef LAUNCH_CHECK
-    return CRF_OK;
+    f.have_flags = cx->flags != nullptr; f.have_side = cx->side != nullptr; f.have_aux = cx->aux != nullptr;
+    f.segments = g_use_segments.load(); f.gd_fallback = cx->gd_fallback;
+    f.seen = cx->seen ? *(volatile int *)cx->seen : 0;
+    plan_schedule(pl, B, T, f);
+    LossCall c{a, w, pl, cx, stream, pl.serial ? stream : cx->side, bind_params(a, w, pl, cx, f.call_id)};
+    g_last_err_word = c.p.err;
+    if ((rc = c.start())) return rc;
+    if (pl.bat) rc = c.run_batch();
+    else if (pl.staged) rc = c.run_staged();
+    else if (pl.den && pl.ctc && !pl.serial) rc = c.run_two_streams();
+    else rc = c.run_one_stream();
+    return rc ? rc : c.run_fallbacks_and_finalize();
 }
 
 int crf_debug_stage_plan(int64_t T, int64_t B, int32_t *out, int n_out) {
@@ -1624,10 +1620,7 @@ int crf_debug_stage_plan(int64_t T, int64_t B, int32_t *out, int n_out) {
 int crf_stage_i32(int32_t *dst_dev, const int32_t *src_pinned_host, int64_t n, void *stream) {
     if (n <= 0) return CRF_OK;
     if (!dst_dev || !src_pinned_host) { set_error("crf_stage_i32: null pointer"); return CRF_ERR_ARG; }
-    hipLaunchKernelGGL(crf_stage_i32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dst_dev, src_pinned_host, n);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("crf_stage_i32: ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
-    return CRF_OK;
+    return launch<crf_stage_i32_kernel>("crf_stage_i32", dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dst_dev, src_pinned_host, n);
 }
 
 int crf_timing_read(unsigned long long *out, int n) {
