@@ -37,17 +37,46 @@ namespace crf {
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
+// The workspace is a list of sections, every one laid down by WsLayout::add: name, offset and byte count are recorded in layout order, and
+// every pointer of the kernels' parameter blocks is carved from those records (WsLayout::off), so the map crf_debug_ws_sections shows
+// cannot drift from the layout the kernels use.  The enumerators, the names and the order all come from this one list.
+#define CRF_WS_SECTIONS(X) \
+    X(ep) X(mx) X(moff) X(invs) X(Q) X(BP) X(EQ) X(EB) X(CA) X(CB) X(ECA) X(ECB) X(pb) X(cbad) X(xch) X(row0) X(ept) X(Af) X(Zb) X(bsm) X(gvec) X(state) X(dump)
+enum WsSec : int {
+#define CRF_WS_ENUM(name) kWs_##name,
+    CRF_WS_SECTIONS(CRF_WS_ENUM)
+#undef CRF_WS_ENUM
+    kWsCount
+};
+static const char *const kWsNames[kWsCount] = {
+#define CRF_WS_NAME(name) #name,
+    CRF_WS_SECTIONS(CRF_WS_NAME)
+#undef CRF_WS_NAME
+};
+struct WsSection { const char *name; int64_t off, bytes; };
+static int64_t al(int64_t x) { return (x + 255) & ~(int64_t)255; }
+// bytes no kernel may touch behind every section: the switch ws_gap x 256 (tests/guard.py); unset, the sections are packed
+static int64_t ws_gap_bytes() { return 256 * (int64_t)std::max(0, opt(kOpt_ws_gap, 0)); }
 struct WsLayout {
-    int64_t off_ep, off_mx, off_moff, off_invs, off_Q, off_BP, off_EQ, off_EB, off_CA, off_CB, off_ECA, off_ECB, off_pb, off_cbad, off_xch, off_row0, total;
+    WsSection sec[kWsCount];     // in layout order: sec[k] is section k of CRF_WS_SECTIONS
+    int nsec;
+    int64_t total;               // = the running end of the layout while it is being made
+    int64_t gap;
     int64_t xch_bytes;
     int64_t Rq, Rb;
     bool res, gv, fac;
     int p2mode;                  // two utterances per workgroup: 0 no, 1 on the main factored layout, 2 on HostGraph::facp (pair2_mode)
-    bool bat; int UL; int64_t Bp, off_ept, off_Af, off_Zb, off_bsm;   // utterance-minor layout (large graphs)
+    bool bat; int UL; int64_t Bp;   // utterance-minor layout (large graphs)
     bool gv_robust;              // the robust fallback kernels keep their vectors in global memory too
-    int64_t off_gvec, off_state, state_stride, gvec_stride, off_dump, dump_stride;
+    int64_t state_stride, gvec_stride, dump_stride;
+    // the next section: starts at the running end, which then moves past its bytes to the next multiple of 256 (+ the ws_gap bytes)
+    void add(WsSec k, int64_t bytes) {
+        if (k != nsec) abort();   // (the sections are laid down in the order of the list)
+        sec[nsec++] = WsSection{kWsNames[k], total, bytes};
+        total = al(total + bytes) + gap;
+    }
+    int64_t off(WsSec k) const { return sec[k].off; }
 };
-static int64_t al(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
 // the register-resident kernels are used whenever the graph fits them (res.K > 0) and V fits their
 // emission-row prefetch; CRF_NO_RESIDENT=1 at graph creation forces the streaming kernels
@@ -80,7 +109,7 @@ static size_t robust_lds_bytes(const HostGraph *h, int V, bool gv) {
 
 static WsLayout ws_layout(const HostGraph *h, int64_t B, int64_t T, int64_t V, int64_t Sc) {
     WsLayout w{};
-    int64_t o = 0;
+    w.gap = ws_gap_bytes();
     w.fac = use_factored(h, V);
     w.res = w.fac || use_resident(h, V);   // "res": register-resident kernels of either layout
     // graphs that fit neither register-resident layout take the utterance-minor kernels (CRF_NO_BATCH=1: the streaming
@@ -102,42 +131,41 @@ static WsLayout ws_layout(const HostGraph *h, int64_t B, int64_t T, int64_t V, i
     const FacDev *FX = w.fac ? (w.p2mode == 2 ? &h->facp : &h->dev.fac) : nullptr;   // the factored layout this call works with
     w.Rq = h ? std::max<int64_t>(w.fac ? FX->Rq : w.res ? h->dev.res.f.R : h->dev.Pr, h->dev.Pr) : 0;
     w.Rb = h ? std::max<int64_t>(w.fac ? FX->Rbp : w.res ? h->dev.res.b.R : h->dev.Pr, h->dev.Pr) : 0;
-    w.off_ep = o; o = al(o + B * T * V * 4);
-    w.off_mx = o; o = al(o + B * T * 4);
-    w.off_moff = o; o = al(o + B * T * 4);   // fused log_softmax only (crf_loss_fwd_bwd_logits)
-    w.off_invs = o; o = al(o + B * T * 4);
+    w.add(kWs_ep, B * T * V * 4);
+    w.add(kWs_mx, B * T * 4);
+    w.add(kWs_moff, B * T * 4);   // fused log_softmax only (crf_loss_fwd_bwd_logits)
+    w.add(kWs_invs, B * T * 4);
     const int64_t qb = w.bat ? T * (int64_t)h->dev.P * w.Bp : 0;   // utterance-minor rows [T][P][Bp]
-    w.off_Q = o; o = al(o + std::max(B * T * w.Rq, qb) * 4);
-    w.off_BP = o; o = al(o + std::max(B * T * w.Rb, qb) * 4);
-    w.off_EQ = o; o = al(o + B * T * 4);
-    w.off_EB = o; o = al(o + B * T * 4);
-    w.off_CA = o; o = al(o + B * T * Sc * 8);
-    w.off_CB = o; o = al(o + B * T * Sc * 8);
-    w.off_ECA = o; o = al(o + B * T * 4);
-    w.off_ECB = o; o = al(o + B * T * 4);
-    w.off_pb = o; o = al(o + 32 * B * 8);
-    w.off_cbad = o; o = al(o + B * T * 4);   // frames of the numerator marked for the log-domain fallback
+    w.add(kWs_Q, std::max(B * T * w.Rq, qb) * 4);
+    w.add(kWs_BP, std::max(B * T * w.Rb, qb) * 4);
+    w.add(kWs_EQ, B * T * 4);
+    w.add(kWs_EB, B * T * 4);
+    w.add(kWs_CA, B * T * Sc * 8);
+    w.add(kWs_CB, B * T * Sc * 8);
+    w.add(kWs_ECA, B * T * 4);
+    w.add(kWs_ECB, B * T * 4);
+    w.add(kWs_pb, 32 * B * 8);
+    w.add(kWs_cbad, B * T * 4);   // frames of the numerator marked for the log-domain fallback
     // tagged granules [2 slots] of both directions, then one XCD-id word per CU of every recursion
     w.xch_bytes = (w.res && !w.fac && h->dev.res.K > 1) ? al((B * 2 * ((int64_t)h->dev.res.f.G + h->dev.res.b.G) + 2 * B * kResMaxK) * 8)
                 : (w.fac && FX->K > 1) ? al((B * 2 * ((int64_t)FX->f.G + FX->b.G) + 2 * B * kResMaxK) * 8) : 0;
-    w.off_xch = o; o = al(o + w.xch_bytes + 256 + 8 * B);   // granules | error word, start counter | per-utterance progress of the two den recursions
-    w.off_row0 = o; o = al(o + (w.res ? B * w.Rb * 4 : 0));
-    w.off_ept = o; o = al(o + (w.bat ? T * V * w.Bp * 4 : 0));
-    w.off_Af = o; o = al(o + (w.bat ? 2 * ((int64_t)h->dev.S + (h->fb.ok ? h->fb.NU : 0)) * w.Bp * 4 : 0));   // (+ the U entries of factored streams)
-    w.off_Zb = o; o = al(o + (w.bat ? 2 * (int64_t)h->dev.P * w.Bp * 4 : 0));
-    w.off_bsm = o; o = al(o + (w.bat ? (12 * w.Bp + 640) * 4 : 0));   // mxf[3], mxb[3], Ef, Fb, zs, zb | grid barrier words [512], time-out word (persistent launch)
+    w.add(kWs_xch, w.xch_bytes + 256 + 8 * B);   // granules | error word, start counter | per-utterance progress of the two den recursions
+    w.add(kWs_row0, w.res ? B * w.Rb * 4 : 0);
+    w.add(kWs_ept, w.bat ? T * V * w.Bp * 4 : 0);
+    w.add(kWs_Af, w.bat ? 2 * ((int64_t)h->dev.S + (h->fb.ok ? h->fb.NU : 0)) * w.Bp * 4 : 0);   // (+ the U entries of factored streams)
+    w.add(kWs_Zb, w.bat ? 2 * (int64_t)h->dev.P * w.Bp * 4 : 0);
+    w.add(kWs_bsm, w.bat ? (12 * w.Bp + 640) * 4 : 0);   // mxf[3], mxb[3], Ef, Fb, zs, zb | grid barrier words [512], time-out word (persistent launch)
     w.gv = h && !w.res && !w.bat && std::max((size_t)3 * rup64(h->dev.S), (size_t)4 * h->dev.Pr) * 4 + 2 * (size_t)rup64((int)V) * 4 + 1024 > 160 * 1024;
     w.gv_robust = h && robust_lds_bytes(h, (int)V, false) > 160 * 1024;
     // (floats per utterance: the streaming kernels' fp32 vectors, or the log-domain fallback's fp64 ones -- forward A[2][Sp] + Ql[Pr], backward Z[2][Pr] + BPst[2][Pr])
     w.gvec_stride = h ? std::max<int64_t>(3 * (int64_t)rup64(h->dev.S) + 5 * (int64_t)h->dev.Pr, 2 * (2 * (int64_t)rup64(h->dev.S) + 5 * (int64_t)h->dev.Pr)) : 0;
-    w.off_gvec = o; o = al(o + ((w.gv || w.gv_robust) ? B * w.gvec_stride * 4 : 0));
+    w.add(kWs_gvec, (w.gv || w.gv_robust) ? B * w.gvec_stride * 4 : 0);
     // factored recursions launched in segments park their state vector + exponent here: [2 dir][B][stride]
     w.state_stride = w.fac ? rup64(std::max(FX->f.G, FX->b.G)) + 64 : 0;
-    w.off_state = o; o = al(o + 2 * B * w.state_stride * 4);
+    w.add(kWs_state, 2 * B * w.state_stride * 4);
     // two utterances per workgroup: one dump row per (direction, pair) for the row stores of an utterance that has ended
     w.dump_stride = w.fac ? al(std::max(w.Rq, w.Rb)) : 0;
-    w.off_dump = o; o = al(o + (w.fac ? 2 * ((B + 1) / 2) * w.dump_stride * 4 : 0));
-    w.total = o;
+    w.add(kWs_dump, w.fac ? 2 * ((B + 1) / 2) * w.dump_stride * 4 : 0);
     return w;
 }
 
@@ -462,14 +490,29 @@ static int launch_align_logits(const AlignParams &p, hipStream_t st, int64_t max
                                         : launch<crf_align_lse_kernel<64, E>>("crf_align_lse_kernel", dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, st, p);
     return rc ? rc : launch_align<E, true>(p, st, max_label_len);
 }
-// its workspace: the back-pointer words [B][ceil(T / kAlnFrames)][2 * max_label_len + 1 rounded up to 64]; < 0 with the message set
-static int64_t align_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t max_label_len) {
+// its workspace: the back-pointer words [B][ceil(T / kAlnFrames)][2 * max_label_len + 1 rounded up to 64], then -- raw network output
+// (crf_ctc_align_logits) -- the frames' lse values [B][T]; sections laid down as WsLayout's are (256-aligned, the ws_gap bytes behind each)
+constexpr int kAlignWsCount = 2;
+static const char *const kAlignWsNames[kAlignWsCount] = {"bp", "lse"};
+struct AlignWs {
+    WsSection sec[kAlignWsCount];
+    int nsec;
+    int64_t total, gap;
+    void add(int64_t bytes) { sec[nsec] = WsSection{kAlignWsNames[nsec], total, bytes}; ++nsec; total = al(total + bytes) + gap; }
+};
+// < 0 with the message set; lse: with the lse section
+static int64_t align_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t max_label_len, bool lse = false, AlignWs *out = nullptr) {
     if (B <= 0 || T <= 0 || V <= 0 || max_label_len < 0) { set_error("crf_ctc_align: bad B/T/V/max_label_len"); return -CRF_ERR_ARG; }
     if (V > kMaxVocab) { set_error("V > " + std::to_string(kMaxVocab) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
     if (max_label_len > kMaxCtcLabelLen) { set_error("label length > " + std::to_string(kMaxCtcLabelLen) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
     if (B * T > INT32_MAX) { set_error("crf_ctc_align: B * T > INT32_MAX"); return -CRF_ERR_ARG; }
     const int64_t Sc = rup64((int)(2 * max_label_len + 1)), NB = (T + kAlnFrames - 1) / kAlnFrames;
-    return al(B * NB * Sc * (int64_t)sizeof(unsigned));
+    AlignWs w{};
+    w.gap = ws_gap_bytes();
+    w.add(B * NB * Sc * (int64_t)sizeof(unsigned));
+    if (lse) w.add(B * T * (int64_t)sizeof(float));
+    if (out) *out = w;
+    return w.total;
 }
 
 static ResParams res_params(const LossParams &lp, int dir, int b0) {
@@ -653,6 +696,16 @@ static int launch_fac_pair2(const LossParams &lp, size_t lds, hipStream_t st, in
 #undef CRF_DEN_NAME
 
 
+// the section records as the debug exports hand them out: (offset, bytes) pairs, and the names joined by commas
+static int copy_sections(const WsSection *sec, int n, int64_t *out, int n_out) {
+    for (int k = 0; k < n && out && 2 * k + 1 < n_out; ++k) { out[2 * k] = sec[k].off; out[2 * k + 1] = sec[k].bytes; }
+    return n;
+}
+static std::string join_names(const char *const *names, int n) {
+    std::string s;
+    for (int k = 0; k < n; ++k) { if (k) s += ','; s += names[k]; }
+    return s;
+}
 }  // namespace crf
 
 using namespace crf;
@@ -668,6 +721,24 @@ int crf_den_kernels(const crf_graph *g, int64_t B, int64_t T, int64_t V) {
     if (!g || !g->h) { set_error("null graph"); return -1; }
     const WsLayout w = ws_layout(g->h, B, T, V, 64);
     return w.bat ? 3 : w.fac ? 2 : w.res ? 1 : 0;
+}
+
+int crf_debug_ws_sections(const crf_graph *g, int64_t B, int64_t T, int64_t V, int64_t max_label_len, int64_t *out, int n_out) {
+    const WsLayout w = ws_layout(g ? g->h : nullptr, B, T, V, rup64((int)(2 * max_label_len + 1)));
+    return copy_sections(w.sec, w.nsec, out, n_out);
+}
+const char *crf_debug_ws_section_names(void) {
+    static const std::string s = join_names(kWsNames, kWsCount);
+    return s.c_str();
+}
+int crf_debug_align_ws_sections(int logits, int64_t B, int64_t T, int64_t V, int64_t max_label_len, int64_t *out, int n_out) {
+    AlignWs w;
+    if (align_ws_bytes(B, T, V, max_label_len, logits != 0, &w) < 0) return -1;
+    return copy_sections(w.sec, w.nsec, out, n_out);
+}
+const char *crf_debug_align_ws_section_names(void) {
+    static const std::string s = join_names(kAlignWsNames, kAlignWsCount);
+    return s.c_str();
 }
 
 // Stage bounds of the staged grad pass (crf_loss_fwd_bwd; crf_debug_stage_plan shows them to the tests): bound[0] = 0 < bound[1] < ... < bound[nstage] = T,
@@ -793,9 +864,9 @@ static int align_args(const char *who, const void *act, int dtype, int time_majo
                       float *score, int32_t *invalid, void *ws, int64_t ws_bytes, AlignParams &p) {
     if (!act || !labels || !lab_off || !lx || !ly || !pos || !score || !ws) { set_error(std::string(who) + ": null argument"); return CRF_ERR_ARG; }
     if (dtype > 2) { set_error(std::string(who) + ": dtype must be 0 (f32), 1 (bf16) or 2 (f16)"); return CRF_ERR_ARG; }
-    const int64_t bpb = align_ws_bytes(B, T, V, max_label_len);
-    if (bpb < 0) return (int)-bpb;
-    const int64_t need = bpb + (dtype >= 0 ? al(B * T * (int64_t)sizeof(float)) : 0);
+    AlignWs w;
+    const int64_t need = align_ws_bytes(B, T, V, max_label_len, dtype >= 0, &w);
+    if (need < 0) return (int)-need;
     if (blank < 0 || blank >= V) { set_error("blank " + std::to_string(blank) + " outside [0, V=" + std::to_string(V) + ")"); return CRF_ERR_ARG; }
     if (ws_bytes < need) { set_error("workspace too small: need " + std::to_string(need)); return CRF_ERR_WORKSPACE; }
     p = AlignParams{};
@@ -803,8 +874,8 @@ static int align_args(const char *who, const void *act, int dtype, int time_majo
     p.B = (int)B; p.T = (int)T; p.V = (int)V; p.blank = blank;
     p.Sc = rup64((int)(2 * max_label_len + 1)); p.NB = (int)((T + kAlnFrames - 1) / kAlnFrames);
     p.xs_b = time_major ? V : T * V; p.xs_t = time_major ? B * V : V;
-    p.bp = (unsigned *)ws; p.pos = pos; p.score = score; p.invalid = invalid;
-    p.lse = dtype >= 0 ? (float *)((char *)ws + bpb) : nullptr;
+    p.bp = (unsigned *)((char *)ws + w.sec[0].off); p.pos = pos; p.score = score; p.invalid = invalid;
+    p.lse = dtype >= 0 ? (float *)((char *)ws + w.sec[1].off) : nullptr;
     return CRF_OK;
 }
 
@@ -819,8 +890,8 @@ int crf_ctc_align(const float *act, int time_major, int blank, const int32_t *la
 }
 
 int64_t crf_ctc_align_logits_workspace_bytes(int64_t B, int64_t T, int64_t V, int64_t max_label_len) {
-    const int64_t n = align_ws_bytes(B, T, V, max_label_len);
-    return n < 0 ? -1 : n + al(B * T * (int64_t)sizeof(float));
+    const int64_t n = align_ws_bytes(B, T, V, max_label_len, true);
+    return n < 0 ? -1 : n;
 }
 
 int crf_ctc_align_logits(const void *act, int dtype, int time_major, int blank, const int32_t *labels, const int32_t *lab_off,
@@ -1009,10 +1080,10 @@ static LossParams bind_params(const LossArgs &a, const WsLayout &w, const CallPl
     p.blank = a.blank;
     p.c_den = a.c_den; p.c_ctc = a.c_ctc;
     char *base = (char *)a.ws;
-    p.ep = (float *)(base + w.off_ep); p.mx = (float *)(base + w.off_mx);
+    p.ep = (float *)(base + w.off(kWs_ep)); p.mx = (float *)(base + w.off(kWs_mx));
     p.fused = a.fused; p.in_dtype = a.in_dtype;
-    p.moff = a.fused ? (float *)(base + w.off_moff) : p.mx; p.inv_s = (float *)(base + w.off_invs);
-    p.Q = (float *)(base + w.off_Q); p.BP = (float *)(base + w.off_BP);
+    p.moff = a.fused ? (float *)(base + w.off(kWs_moff)) : p.mx; p.inv_s = (float *)(base + w.off(kWs_invs));
+    p.Q = (float *)(base + w.off(kWs_Q)); p.BP = (float *)(base + w.off(kWs_BP));
     p.Rq = (int)w.Rq; p.Rb = (int)w.Rb; p.res = fac ? 2 : res ? 1 : 0; p.grad_stage = pl.grad_stage ? 1 : 0;
     if (fac) {
         const FacDev &F = *pl.FX;
@@ -1023,25 +1094,25 @@ static LossParams bind_params(const LossArgs &a, const WsLayout &w, const CallPl
         p.gNC = res ? h->dev.res.NC : h->dev.NC;
     }
     if (res && !fac) { p.res_lds_rows_f = h->res_rows_cu_f; p.res_lds_rows_b = h->res_rows_cu_b; }
-    p.EQ = (int *)(base + w.off_EQ); p.EB = (int *)(base + w.off_EB);
-    p.CA = (double *)(base + w.off_CA); p.CB = (double *)(base + w.off_CB);
-    p.ECA = (int *)(base + w.off_ECA); p.ECB = (int *)(base + w.off_ECB);
-    p.ctc_zc = (double *)(base + w.off_pb);
+    p.EQ = (int *)(base + w.off(kWs_EQ)); p.EB = (int *)(base + w.off(kWs_EB));
+    p.CA = (double *)(base + w.off(kWs_CA)); p.CB = (double *)(base + w.off(kWs_CB));
+    p.ECA = (int *)(base + w.off(kWs_ECA)); p.ECB = (int *)(base + w.off(kWs_ECB));
+    p.ctc_zc = (double *)(base + w.off(kWs_pb));
     p.cb_mxs = p.ctc_zc + B;
     float *pb = (float *)(p.cb_mxs + B);
     p.cb_part = pb + 8 * B; p.cb_F = (int *)(pb + 8 * B + (int64_t)kResMaxK * B);
     p.redo = (int *)(pb + 16 * B);   // [2][B]
     p.redo_ctc = (int *)(pb + 18 * B);   // [B]
     p.ctc_logdom = (int *)(pb + 19 * B); // [B]
-    p.ctc_bad = (int *)(base + w.off_cbad);
+    p.ctc_bad = (int *)(base + w.off(kWs_cbad));
     p.force_redo = (den && pl.robust_env == 1) ? 1 : 0;
     p.force_redo_ctc = (ctc && (pl.robust_env == 1 || opt_on(kOpt_robust_ctc))) ? 1 : 0;
     p.ctc_tilt = std::min(400, std::max(0, opt(kOpt_ctc_tilt, 100)));
-    p.xch = (unsigned long long *)(base + w.off_xch);
-    p.err = (int *)(base + w.off_xch + w.xch_bytes);
-    p.Row0 = (float *)(base + w.off_row0);
-    p.dump = (float *)(base + w.off_dump); p.dump_stride = (int)w.dump_stride;
-    p.gvec = (float *)(base + w.off_gvec);
+    p.xch = (unsigned long long *)(base + w.off(kWs_xch));
+    p.err = (int *)(base + w.off(kWs_xch) + w.xch_bytes);
+    p.Row0 = (float *)(base + w.off(kWs_row0));
+    p.dump = (float *)(base + w.off(kWs_dump)); p.dump_stride = (int)w.dump_stride;
+    p.gvec = (float *)(base + w.off(kWs_gvec));
     p.gvec_stride = w.gvec_stride;
     p.den_zs = pb; p.den_ez = (int *)(pb + B); p.ctc_ez = (int *)(pb + 2 * B);
     p.cost_alpha = pb + 3 * B; p.cost_beta = pb + 4 * B; p.cost_ctc = pb + 5 * B; p.invalid = (int *)(pb + 6 * B);
@@ -1091,7 +1162,7 @@ struct LossCall {
 
     int *started() const { return p.err + 1; }   // workgroups of the den kernels that hold a CU (cleared with the error word)
     // factored recursions launched in segments park their state vectors here
-    float *fstate() const { return (float *)((char *)a.ws + w.off_state); }
+    float *fstate() const { return (float *)((char *)a.ws + w.off(kWs_state)); }
     float *bstate() const { return fstate() + a.B * w.state_stride; }
 
     int fork_side() {   // the side stream starts behind everything queued on the caller's stream so far
@@ -1251,7 +1322,7 @@ struct LossCall {
         prof_mark(0, true, stream);
         if (rc) return rc;
         if (pl.res && (w.xch_bytes > 0 || !pl.have_flags)) {  // exchange granules (tags) and the error word start at zero in every call
-            if (hipMemsetAsync(p.xch, 0, (size_t)w.xch_bytes + 256 + 8 * (size_t)a.B, stream) != hipSuccess) { set_error("hipMemsetAsync(xch)"); return CRF_ERR_HIP; }
+            if (hipMemsetAsync(p.xch, 0, (size_t)w.sec[kWs_xch].bytes, stream) != hipSuccess) { set_error("hipMemsetAsync(xch)"); return CRF_ERR_HIP; }
         }
         return CRF_OK;
     }
@@ -1276,9 +1347,9 @@ int LossCall::run_batch() {
     bp.g = h->dev.bat; bp.start_lin = h->dev.start_lin; bp.end_lin = h->dev.end_lin;
     bp.S = h->dev.S; bp.P = h->dev.P; bp.B = (int)B; bp.Bp = (int)w.Bp; bp.T = (int)T; bp.V = (int)V; bp.max_label = h->dev.max_label;
     bp.lx = a.lx; bp.ep = p.ep; bp.moff = p.moff;
-    bp.ept = (float *)(base + w.off_ept); bp.Af = (float *)(base + w.off_Af); bp.Zb = (float *)(base + w.off_Zb);
+    bp.ept = (float *)(base + w.off(kWs_ept)); bp.Af = (float *)(base + w.off(kWs_Af)); bp.Zb = (float *)(base + w.off(kWs_Zb));
     bp.Q = p.Q; bp.BP = p.BP;
-    unsigned *bsm = (unsigned *)(base + w.off_bsm);
+    unsigned *bsm = (unsigned *)(base + w.off(kWs_bsm));
     bp.mxf = bsm; bp.mxb = bsm + 3 * w.Bp; bp.Ef = (int *)(bsm + 6 * w.Bp); bp.Fb = (int *)(bsm + 7 * w.Bp);
     bp.zs = (float *)(bsm + 8 * w.Bp); bp.zb = (float *)(bsm + 9 * w.Bp);
     bp.bar = bsm + 12 * w.Bp; bp.err = (int *)(bsm + 12 * w.Bp + 512);

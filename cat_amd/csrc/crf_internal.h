@@ -376,7 +376,8 @@ void set_error(const std::string &msg);
     X(aux_stream,       "C  numerator fallback chains on the third stream: 1 always, 0 never (default: when a recent call needed them)")  \
     X(no_aux_stream,    "X  no third stream for this context (numerator fallback chains in front of the grad stages)")      \
     X(no_facp,          "G  no second (512-thread) factored layout for the two-utterance kernel")                            \
-    X(fac_pair2,        "C  factored recursions with TWO utterances per workgroup: 1 = for any batch, 0 = never (default: batches above CUs / 2)")
+    X(fac_pair2,        "C  factored recursions with TWO utterances per workgroup: 1 = for any batch, 0 = never (default: batches above CUs / 2)") \
+    X(ws_gap,           "C  test aid: n x 256 bytes that no kernel may touch behind every workspace section, in crf_workspace_bytes / crf_ctc_align*_workspace_bytes and in the calls alike; unset (the default), the layout is byte for byte the packed one")
 
 enum Opt : int {
 #define CRF_OPT_ENUM(name, doc) kOpt_##name,

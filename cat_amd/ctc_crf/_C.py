@@ -84,7 +84,7 @@ _lib.crf_build_switches.restype = ctypes.c_char_p
 
 EXPORTED_SYMBOLS = (
     "crf_graph_create", "crf_graph_create_from_arcs", "crf_graph_destroy", "crf_graph_dims", "crf_graph_stats",
-    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
+    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
     "crf_debug_set", "crf_debug_unset", "crf_debug_list", "crf_last_den_kernel", "crf_last_call_streams", "crf_last_side_stream", "crf_last_fallback_counts", "crf_build_switches", "crf_last_error", "crf_version",
 )
 
@@ -284,6 +284,32 @@ def debug_res_emulate(handle: int, T: int = 6, seed: int = 1):
     _lib.crf_debug_res_emulate.restype = ctypes.c_int
     _check(_lib.crf_debug_res_emulate(_vp(handle), T, seed, out))
     return float(out[0]), float(out[1]), float(out[2])
+
+
+def debug_ws_sections(handle: Optional[int], B: int, T: int, V: int, max_label_len: int):
+    """[(name, offset, bytes)] of the loss call's workspace in layout order under the current switches (include/ctc_crf_hip.h:
+    crf_debug_ws_sections; no GPU; handle None / 0: a numerator-only call)."""
+    _lib.crf_debug_ws_sections.argtypes = [_vp, _i64, _i64, _i64, _i64, ctypes.POINTER(_i64), ctypes.c_int]
+    _lib.crf_debug_ws_sections.restype = ctypes.c_int
+    _lib.crf_debug_ws_section_names.restype = ctypes.c_char_p
+    names = _lib.crf_debug_ws_section_names().decode().split(",")
+    out = (_i64 * (2 * len(names)))()
+    n = _lib.crf_debug_ws_sections(_vp(handle or 0), B, T, V, max_label_len, out, len(out))
+    assert n == len(names), (n, names)
+    return [(names[k], int(out[2 * k]), int(out[2 * k + 1])) for k in range(n)]
+
+
+def debug_align_ws_sections(logits: bool, B: int, T: int, V: int, max_label_len: int):
+    """The same for the workspace of crf_ctc_align (logits False: the back-pointer words) / crf_ctc_align_logits (True: + the lse values)."""
+    _lib.crf_debug_align_ws_sections.argtypes = [ctypes.c_int, _i64, _i64, _i64, _i64, ctypes.POINTER(_i64), ctypes.c_int]
+    _lib.crf_debug_align_ws_sections.restype = ctypes.c_int
+    _lib.crf_debug_align_ws_section_names.restype = ctypes.c_char_p
+    names = _lib.crf_debug_align_ws_section_names().decode().split(",")
+    out = (_i64 * (2 * len(names)))()
+    n = _lib.crf_debug_align_ws_sections(1 if logits else 0, B, T, V, max_label_len, out, len(out))
+    if n < 0:
+        _check(1)
+    return [(names[k], int(out[2 * k]), int(out[2 * k + 1])) for k in range(n)]
 
 
 def timing_read(n: int = 16384):

@@ -122,6 +122,19 @@ int crf_debug_stage_plan(int64_t T, int64_t B, int32_t *out, int n_out);
  * layout forward, layout backward}; the grad pass's pair lists are checked frame by frame as well. */
 int crf_debug_res_emulate(const crf_graph *g, int T, unsigned seed, double *out3);
 
+/* Test aid (no GPU, no HIP call; works on host-only graphs and with g = NULL for numerator-only calls): the sections of the workspace
+ * of crf_loss_fwd_bwd / crf_ctc_fwd_bwd and their *_logits twins for this shape under the current debug switches, in layout order, from
+ * the very records the call carves its pointers from.  Writes (offset, bytes) pairs for as many sections as fit n_out int64 and returns
+ * the number of sections; crf_debug_ws_section_names() gives their names, comma-separated, in the same order.  Every section starts on
+ * a multiple of 256, the last one ends at or below crf_workspace_bytes(...); with the switch ws_gap = n every section is followed by
+ * n x 256 bytes that belong to no section and that no kernel may touch (tests/guard.py checks them), unset the layout is the packed one.
+ * crf_debug_align_ws_sections: the same for crf_ctc_align (logits = 0: the back-pointer words "bp") and crf_ctc_align_logits (logits = 1:
+ * "bp", then the lse values "lse"); -1 with crf_last_error() set for a shape the build does not take. */
+int crf_debug_ws_sections(const crf_graph *g, int64_t B, int64_t T, int64_t V, int64_t max_label_len, int64_t *out, int n_out);
+const char *crf_debug_ws_section_names(void);
+int crf_debug_align_ws_sections(int logits, int64_t B, int64_t T, int64_t V, int64_t max_label_len, int64_t *out, int n_out);
+const char *crf_debug_align_ws_section_names(void);
+
 /* The hot path.  Replaces, in one call and with no host synchronisation:
  *   gpu_ctc  (binding.cpp:86-117  -> compute_ctc_loss, ctc_entrypoint.cu:29-60)
  *   gpu_den  (binding.cpp:65-84   -> compute_alpha + compute_beta_and_grad, den_calculate.cu:427-481)
@@ -164,7 +177,8 @@ int crf_ctc_fwd_bwd(const float *act_dev, int time_major, int blank, const int32
 /* crf_ctc_fwd_bwd on the RAW network output: the log_softmax in front of plain CTC and its backward fused in, as
  * crf_loss_fwd_bwd_logits does for the CTC-CRF loss, in either layout and with any blank.  Replaces, besides gpu_ctc,
  *   torch.log_softmax(x.float(), -1)  (cat/ctc/train.py:191-196, the non-CRF branch) and its backward.
- * act_dev: [B][T][V] or [T][B][V] (time_major) of dtype 0 = fp32, 1 = bf16, 2 = fp16, upcast in registers; everything else as
+ * act_dev: [B][T][V] or [T][B][V] (time_major) of dtype 0 = fp32, 1 = bf16, 2 = fp16, read element by element and upcast in registers
+ * (rows of 16-bit elements need 2-byte alignment only, as for crf_ctc_align_logits); everything else as
  * crf_ctc_fwd_bwd (workspace from crf_workspace_bytes(NULL, ...), no host sync):
  *   costs_ctc_dev[b] = logp_ctc[b] under log_softmax of the upcast input,   loss_dev[0] = -c_ctc * sum_b costs_ctc_dev[b],
  *   grad_dev (fp32, the caller's layout): for a valid utterance and t < lx[b]

@@ -433,7 +433,7 @@ def test_debug_switches_are_set_by_name_not_from_the_environment(tmp_path):
     import ctc_crf
     core = ctc_crf._C
     names = [ln.split(":")[0] for ln in core.debug_list().splitlines() if ln]
-    assert "no_factored" in names and "bat_ul" in names and len(names) == len(set(names)) >= 30
+    assert "no_factored" in names and "bat_ul" in names and "ws_gap" in names and len(names) == len(set(names)) >= 31
     with pytest.raises(RuntimeError):
         core.debug_set("no_such_switch", 1)
     p = os.path.join(str(tmp_path), "g.fst")
