@@ -440,6 +440,7 @@ static thread_local int g_call_streams = 1;          // crf_last_call_streams
 static thread_local const char *g_side_desc = "none";   // crf_last_side_stream
 static thread_local const int *g_last_err_word = nullptr;   // error word (+ kFlagFallback: fallback counts) of this thread's last call -- crf_last_fallback_counts
 static thread_local const char *g_den_kernel = "";   // template instantiation of the denominator recursions' kernel in the last call (crf_last_den_kernel)
+static thread_local const char *g_score_kernel = ""; // ... of the kernel of this thread's last crf_ctc_score / crf_ctc_score_logits (crf_last_score_kernel)
 static void prof_mark(int slot, bool stop, hipStream_t st) {
     if (!g_prof.on) return;
     if (!g_prof.made) {
@@ -501,7 +502,36 @@ struct AlignWs {
     void add(int64_t bytes) { sec[nsec] = WsSection{kAlignWsNames[nsec], total, bytes}; ++nsec; total = al(total + bytes) + gap; }
 };
 // < 0 with the message set; lse: with the lse section
-static int64_t align_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t max_label_len, bool lse = false, AlignWs *out = nullptr) {
+static int64_t align_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t max_label_len, bool lse = false, AlignWs *out = nullptr);
+// hypothesis scores (k_score.hip): up to kScoreWaveMaxStates states one wave per hypothesis and kScoreWaves of them per workgroup, beyond one
+// workgroup per hypothesis; states per lane / thread from the call's longest hypothesis
+template <typename E = float, bool LSE = false>
+static int launch_score(const ScoreParams &p, hipStream_t st, int64_t max_hyp_len) {
+    const int64_t ns = 2 * max_hyp_len + 1;
+    if (ns <= kScoreWaveMaxStates) {
+        const dim3 grid((unsigned)((p.H + kScoreWaves - 1) / kScoreWaves)), block(kScoreWaves * 64);
+        if (ns <= 64) return launch<crf_ctc_score_wave_kernel<1, E, LSE>>(g_score_kernel = "crf_ctc_score_wave_kernel<1>", grid, block, 0, st, p);
+        if (ns <= 128) return launch<crf_ctc_score_wave_kernel<2, E, LSE>>(g_score_kernel = "crf_ctc_score_wave_kernel<2>", grid, block, 0, st, p);
+        if (ns <= 256) return launch<crf_ctc_score_wave_kernel<4, E, LSE>>(g_score_kernel = "crf_ctc_score_wave_kernel<4>", grid, block, 0, st, p);
+        return launch<crf_ctc_score_wave_kernel<8, E, LSE>>(g_score_kernel = "crf_ctc_score_wave_kernel<8>", grid, block, 0, st, p);
+    }
+    const int64_t ni = (ns + kCtcThreads - 1) / kCtcThreads;
+    const dim3 grid((unsigned)p.H), block(kCtcThreads);
+    if (ni <= 2) return launch<crf_ctc_score_wg_kernel<2, E, LSE>>(g_score_kernel = "crf_ctc_score_wg_kernel<2>", grid, block, 0, st, p);
+    if (ni <= 4) return launch<crf_ctc_score_wg_kernel<4, E, LSE>>(g_score_kernel = "crf_ctc_score_wg_kernel<4>", grid, block, 0, st, p);
+    return launch<crf_ctc_score_wg_kernel<kCtcRegs, E, LSE>>(g_score_kernel = "crf_ctc_score_wg_kernel<8>", grid, block, 0, st, p);
+}
+// raw network output: the frames' lse values first (the alignment's row kernel), then the scores on the upcast values, on the same stream
+template <typename E>
+static int launch_score_logits(const ScoreParams &p, hipStream_t st, int64_t max_hyp_len) {
+    AlignParams a{};
+    a.x = p.x; a.lx = p.lx; a.B = p.B; a.T = p.T; a.V = p.V; a.xs_b = p.xs_b; a.xs_t = p.xs_t; a.lse = const_cast<float *>(p.lse);
+    const int64_t frames = (int64_t)p.B * p.T;
+    const int rc = p.V <= kAlnLseSmallV ? launch<crf_align_lse_kernel<16, E>>("crf_align_lse_kernel", dim3((unsigned)((frames + 15) / 16)), dim3(256), 0, st, a)
+                                        : launch<crf_align_lse_kernel<64, E>>("crf_align_lse_kernel", dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, st, a);
+    return rc ? rc : launch_score<E, true>(p, st, max_hyp_len);
+}
+static int64_t align_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t max_label_len, bool lse, AlignWs *out) {
     if (B <= 0 || T <= 0 || V <= 0 || max_label_len < 0) { set_error("crf_ctc_align: bad B/T/V/max_label_len"); return -CRF_ERR_ARG; }
     if (V > kMaxVocab) { set_error("V > " + std::to_string(kMaxVocab) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
     if (max_label_len > kMaxCtcLabelLen) { set_error("label length > " + std::to_string(kMaxCtcLabelLen) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
@@ -905,6 +935,61 @@ int crf_ctc_align_logits(const void *act, int dtype, int time_major, int blank, 
     if (dtype == 0) return launch_align_logits<float>(p, (hipStream_t)stream_, max_label_len);
     if (dtype == 1) return launch_align_logits<AlnBf16>(p, (hipStream_t)stream_, max_label_len);
     return launch_align_logits<AlnF16>(p, (hipStream_t)stream_, max_label_len);
+}
+
+// the checks and the argument block both score entry points share; dtype < 0: log-probs (crf_ctc_score, no workspace), else raw output of
+// that dtype with the lse values [B][T] in the workspace.  Every error is answered here, before any HIP call.
+static int64_t score_ws_bytes(int64_t B, int64_t T, int64_t V) {
+    if (B <= 0 || T <= 0 || V <= 0 || V > INT32_MAX) { set_error("crf_ctc_score: bad B/T/V"); return -CRF_ERR_ARG; }
+    if (B * T > INT32_MAX) { set_error("crf_ctc_score: B * T > INT32_MAX"); return -CRF_ERR_ARG; }
+    return al(B * T * (int64_t)sizeof(float)) + ws_gap_bytes();
+}
+static int score_args(const char *who, const void *act, int dtype, int time_major, int blank, const int32_t *labels, const int32_t *hyp_off,
+                      const int32_t *hyp_len, const int32_t *hyp_utt, const int32_t *lx, int64_t B, int64_t H, int64_t T, int64_t V,
+                      int64_t max_hyp_len, float *score, int32_t *invalid, void *ws, int64_t ws_bytes, ScoreParams &p) {
+    if (!act || !labels || !hyp_off || !hyp_len || !hyp_utt || !lx || !score || (dtype >= 0 && !ws)) { set_error(std::string(who) + ": null argument"); return CRF_ERR_ARG; }
+    if (dtype > 2) { set_error(std::string(who) + ": dtype must be 0 (f32), 1 (bf16) or 2 (f16)"); return CRF_ERR_ARG; }
+    if (H <= 0 || H > INT32_MAX || max_hyp_len < 0) { set_error(std::string(who) + ": bad H/max_hyp_len"); return CRF_ERR_ARG; }
+    const int64_t need = score_ws_bytes(B, T, V);
+    if (need < 0) return (int)-need;
+    if (max_hyp_len > kMaxCtcLabelLen) { set_error("hypothesis length > " + std::to_string(kMaxCtcLabelLen) + " not supported by this build"); return CRF_ERR_UNSUPPORTED; }
+    if (blank < 0 || blank >= V) { set_error("blank " + std::to_string(blank) + " outside [0, V=" + std::to_string(V) + ")"); return CRF_ERR_ARG; }
+    if (dtype >= 0 && ws_bytes < need) { set_error("workspace too small: need " + std::to_string(need)); return CRF_ERR_WORKSPACE; }
+    p = ScoreParams{};
+    p.x = act; p.labels = labels; p.hyp_off = hyp_off; p.hyp_len = hyp_len; p.hyp_utt = hyp_utt; p.lx = lx;
+    p.B = (int)B; p.H = (int)H; p.T = (int)T; p.V = (int)V; p.blank = blank;
+    p.xs_b = time_major ? V : T * V; p.xs_t = time_major ? B * V : V;
+    p.score = score; p.invalid = invalid;
+    p.lse = dtype >= 0 ? (const float *)ws : nullptr;
+    return CRF_OK;
+}
+
+int crf_ctc_score(const float *act, int time_major, int blank, const int32_t *labels, const int32_t *hyp_off, const int32_t *hyp_len,
+                  const int32_t *hyp_utt, const int32_t *lx, int64_t B, int64_t H, int64_t T, int64_t V, int64_t max_hyp_len,
+                  float *score, int32_t *invalid, void *stream_) {
+    ScoreParams p;
+    const int rc = score_args("crf_ctc_score", act, -1, time_major, blank, labels, hyp_off, hyp_len, hyp_utt, lx, B, H, T, V, max_hyp_len,
+                              score, invalid, nullptr, 0, p);
+    if (rc) return rc;
+    return launch_score(p, (hipStream_t)stream_, max_hyp_len);
+}
+
+int64_t crf_ctc_score_logits_workspace_bytes(int64_t B, int64_t T, int64_t V) {
+    const int64_t n = score_ws_bytes(B, T, V);
+    return n < 0 ? -1 : n;
+}
+
+int crf_ctc_score_logits(const void *act, int dtype, int time_major, int blank, const int32_t *labels, const int32_t *hyp_off,
+                         const int32_t *hyp_len, const int32_t *hyp_utt, const int32_t *lx, int64_t B, int64_t H, int64_t T, int64_t V,
+                         int64_t max_hyp_len, float *score, int32_t *invalid, void *ws, int64_t ws_bytes, void *stream_) {
+    if (dtype < 0) { set_error("crf_ctc_score_logits: dtype must be 0 (f32), 1 (bf16) or 2 (f16)"); return CRF_ERR_ARG; }
+    ScoreParams p;
+    const int rc = score_args("crf_ctc_score_logits", act, dtype, time_major, blank, labels, hyp_off, hyp_len, hyp_utt, lx, B, H, T, V,
+                              max_hyp_len, score, invalid, ws, ws_bytes, p);
+    if (rc) return rc;
+    if (dtype == 0) return launch_score_logits<float>(p, (hipStream_t)stream_, max_hyp_len);
+    if (dtype == 1) return launch_score_logits<AlnBf16>(p, (hipStream_t)stream_, max_hyp_len);
+    return launch_score_logits<AlnF16>(p, (hipStream_t)stream_, max_hyp_len);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1726,6 +1811,7 @@ const char *crf_build_switches(void) {
 }
 
 const char *crf_last_den_kernel(void) { return g_den_kernel; }
+const char *crf_last_score_kernel(void) { return g_score_kernel; }
 int crf_last_call_streams(void) { return g_call_streams; }
 const char *crf_last_side_stream(void) { return g_side_desc; }
 

@@ -39,6 +39,24 @@ template <int NR, typename E = float, bool LSE = false> __global__ void crf_ctc_
 constexpr int kAlnLseSmallV = 256;
 template <int G, typename E> __global__ void crf_align_lse_kernel(AlignParams p);
 
+// ---- k_score.hip ----
+constexpr int kScoreWaves = 4;            // hypotheses (waves) per workgroup of the wave geometry
+constexpr int kScoreWaveMaxStates = 512;  // 2 max_hyp_len + 1 up to here: one wave per hypothesis (64 lanes x 8 states), beyond: one workgroup
+// Kernel arguments of the hypothesis scores (crf_ctc_score, crf_ctc_score_logits): hypothesis h is the labels [hyp_off[h], + hyp_len[h])
+// on the rows of utterance hyp_utt[h]; the activations as for the alignment (row (u, t) at u * xs_b + t * xs_t ELEMENTS, read in place)
+struct ScoreParams {
+    const void *x;
+    const int *labels, *hyp_off, *hyp_len, *hyp_utt, *lx;
+    int B, H, T, V, blank;
+    int64_t xs_b, xs_t;
+    float *score;               // [H]
+    int *invalid;               // [H] or null
+    const float *lse;           // [B][T] crf_ctc_score_logits: the frames' normalisers (crf_align_lse_kernel), else null
+};
+// E: float, AlnBf16, AlnF16.  LSE: score = raw sum-product - sum_t lse[u][t] in fp64 (raw network output).
+template <int NR, typename E = float, bool LSE = false> __global__ void crf_ctc_score_wave_kernel(ScoreParams p);   // NR 1, 2, 4, 8
+template <int NR, typename E = float, bool LSE = false> __global__ void crf_ctc_score_wg_kernel(ScoreParams p);     // NR 2, 4, kCtcRegs
+
 // ---- k_res.hip ----
 constexpr int kEpRegsR = 2;   // emission-row prefetch registers (V <= 2*512 for the resident kernels)
 constexpr int kPoll = 4;      // granules polled concurrently per thread

@@ -9,4 +9,5 @@
 #include "k_batch.hip"
 #include "k_robust.hip"
 #include "k_align.hip"
+#include "k_score.hip"
 #include "crf_host.hip"

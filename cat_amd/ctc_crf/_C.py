@@ -60,6 +60,14 @@ _lib.crf_ctc_align_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64]
 _lib.crf_ctc_align_workspace_bytes.restype = _i64
 _lib.crf_ctc_align.argtypes = [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]
 _lib.crf_ctc_align.restype = ctypes.c_int
+_lib.crf_ctc_score.argtypes = [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp]
+_lib.crf_ctc_score.restype = ctypes.c_int
+_lib.crf_ctc_score_logits_workspace_bytes.argtypes = [_i64, _i64, _i64]
+_lib.crf_ctc_score_logits_workspace_bytes.restype = _i64
+_lib.crf_ctc_score_logits.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
+                                      _vp, _vp, _vp, _i64, _vp]
+_lib.crf_ctc_score_logits.restype = ctypes.c_int
+_lib.crf_last_score_kernel.restype = ctypes.c_char_p
 _lib.crf_profile_enable.argtypes = [ctypes.c_int]
 _lib.crf_profile_enable.restype = None
 _lib.crf_profile_read.argtypes = [ctypes.POINTER(_f32), ctypes.c_int]
@@ -84,7 +92,7 @@ _lib.crf_build_switches.restype = ctypes.c_char_p
 
 EXPORTED_SYMBOLS = (
     "crf_graph_create", "crf_graph_create_from_arcs", "crf_graph_destroy", "crf_graph_dims", "crf_graph_stats",
-    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
+    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_ctc_score", "crf_ctc_score_logits_workspace_bytes", "crf_ctc_score_logits", "crf_last_score_kernel", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
     "crf_debug_set", "crf_debug_unset", "crf_debug_list", "crf_last_den_kernel", "crf_last_call_streams", "crf_last_side_stream", "crf_last_fallback_counts", "crf_build_switches", "crf_last_error", "crf_version",
 )
 
@@ -106,6 +114,11 @@ def profile_read() -> Dict[str, float]:
 def last_den_kernel() -> str:
     """Template instantiation of the denominator recursions' kernel in this thread's last call (include/ctc_crf_hip.h)."""
     return _lib.crf_last_den_kernel().decode()
+
+
+def last_score_kernel() -> str:
+    """Template instantiation of the kernel of this thread's last ctc_score call (include/ctc_crf_hip.h crf_last_score_kernel)."""
+    return _lib.crf_last_score_kernel().decode()
 
 
 def last_call_streams() -> int:
@@ -612,6 +625,95 @@ def ctc_align(log_probs: torch.Tensor, labels: torch.Tensor, lx: torch.Tensor, l
     tokens = torch.gather(table_d.view(N, max_l + 2), 1, (pos + 2).long())
     del meta
     return pos, tokens, scores, invalid
+
+
+def _stage_score_meta(hyps: torch.Tensor, hyp_lengths: torch.Tensor, lx: torch.Tensor, hyp_utt: Optional[torch.Tensor], N: int, T: int,
+                      V: int, blank: int):
+    """The integer metadata of ctc_score as ONE int32 CPU tensor [lx (N) | hyp_len (H) | hyp_off (H) | hyp_utt (H) | labels], checked on
+    the host; hyps flat [sum(hyp_lengths)] or padded (H, Lmax) -- both forms stage the same words.  Returns (meta, H, max_len)."""
+    if hyps.is_cuda or hyp_lengths.is_cuda or lx.is_cuda or (hyp_utt is not None and hyp_utt.is_cuda):
+        raise RuntimeError("ctc_score: hyps, hyp_lengths, input_lengths and hyp_utt are CPU tensors")
+    lx32 = lx.to(torch.int32).reshape(-1)
+    hl32 = hyp_lengths.to(torch.int32).reshape(-1)
+    H = hl32.numel()
+    if lx32.numel() != N:
+        raise RuntimeError(f"ctc_score: expect {N} input lengths, got {lx32.numel()}")
+    if H == 0:
+        raise RuntimeError("ctc_score: no hypotheses")
+    if hyp_utt is None:
+        if H != N:
+            raise RuntimeError(f"ctc_score: hyp_utt=None scores hypothesis h on utterance h: expect {N} hypotheses, got {H}")
+        hu32 = torch.arange(N, dtype=torch.int32)
+    else:
+        hu32 = hyp_utt.to(torch.int32).reshape(-1)
+        if hu32.numel() != H:
+            raise RuntimeError(f"ctc_score: expect {H} entries of hyp_utt (one per hypothesis), got {hu32.numel()}")
+        if int(hu32.min()) < 0 or int(hu32.max()) >= N:
+            raise RuntimeError(f"ctc_score: hyp_utt must lie in [0, N-1={N - 1}], got [{int(hu32.min())}, {int(hu32.max())}]")
+    if int(hl32.min()) < 0:
+        raise RuntimeError("negative label length")
+    max_l = int(hl32.max())
+    if hyps.dim() == 2:   # padded rows: the first hyp_lengths[h] entries of row h
+        if hyps.size(0) != H:
+            raise RuntimeError(f"ctc_score: expect {H} rows of hyps (one per hypothesis), got {hyps.size(0)}")
+        if max_l > hyps.size(1):
+            raise RuntimeError(f"ctc_score: max(hyp_lengths)={max_l} exceeds the row length {hyps.size(1)} of hyps")
+        lab32 = hyps.to(torch.int32)[torch.arange(hyps.size(1))[None, :] < hl32[:, None]]
+    else:
+        lab32 = hyps.to(torch.int32).reshape(-1)
+    _validate_meta(lx32, hl32, lab32, T, V, blank)
+    nlab = int(hl32.sum())
+    off = (torch.cumsum(hl32, 0, dtype=torch.int32) - hl32).to(torch.int32)
+    lab_pad = lab32[:nlab] if nlab else torch.zeros(1, dtype=torch.int32)
+    return torch.cat([lx32, hl32, off, hu32, lab_pad]), H, max_l
+
+
+def ctc_score(log_probs: torch.Tensor, hyps: torch.Tensor, hyp_lengths: torch.Tensor, lx: torch.Tensor,
+              hyp_utt: Optional[torch.Tensor] = None, blank: int = 0, time_major: bool = False, fused: bool = False,
+              scores_out: Optional[torch.Tensor] = None):
+    """Forward-only CTC log-likelihoods of H hypotheses (include/ctc_crf_hip.h ``crf_ctc_score``): hypothesis h on the rows of utterance
+    hyp_utt[h] (None: H = N, hypothesis h on utterance h).
+
+    log_probs [N,T,V] (time_major: [T,N,V]) f32 on the GPU, contiguous, read in place and never replicated; hyps / hyp_lengths / lx /
+    hyp_utt int tensors on the CPU, hyps flat [sum(hyp_lengths)] or padded (H, Lmax).  Returns (scores [H] f32 = +log p, invalid [H]
+    int32), both on the device, no host synchronisation, no autograd; all integer metadata travels in one staged copy.
+    fused: log_probs is the RAW network output in f32 / bf16 / f16 (``crf_ctc_score_logits``)."""
+    assert log_probs.is_cuda and log_probs.is_contiguous() and log_probs.dim() == 3
+    if fused:
+        if log_probs.dtype not in _FUSED_DTYPES:
+            raise RuntimeError(f"fused log_softmax: expect float32, bfloat16 or float16 network output, got {log_probs.dtype}")
+    else:
+        assert log_probs.dtype == torch.float32
+    dev = log_probs.device
+    N, T, V = log_probs.shape
+    if time_major:
+        T, N = N, T
+    if not 0 <= blank < V:
+        raise RuntimeError(f"blank must lie in [0, V-1={V - 1}], got {blank}")
+    meta_cpu, H, max_l = _stage_score_meta(hyps, hyp_lengths, lx, hyp_utt, N, T, V, blank)
+    meta = _h2d_async(meta_cpu, dev)
+    lx_d, len_d, off_d, utt_d, lab_d = meta[:N], meta[N:N + H], meta[N + H:N + 2 * H], meta[N + 2 * H:N + 3 * H], meta[N + 3 * H:]
+    scores = torch.empty(H, dtype=torch.float32, device=dev) if scores_out is None else scores_out
+    assert scores.shape == (H,) and scores.dtype == torch.float32 and scores.is_contiguous() and scores.device == dev
+    invalid = torch.empty(H, dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        if fused:
+            ws_bytes = _lib.crf_ctc_score_logits_workspace_bytes(N, T, V)
+            if ws_bytes < 0:
+                _check(1)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            if _POISON_WS:
+                ws.fill_(0xFF)
+            rc = _lib.crf_ctc_score_logits(_ptr(log_probs), _FUSED_DTYPES[log_probs.dtype], 1 if time_major else 0, blank, _ptr(lab_d),
+                                           _ptr(off_d), _ptr(len_d), _ptr(utt_d), _ptr(lx_d), N, H, T, V, max_l, _ptr(scores),
+                                           _ptr(invalid), _ptr(ws), ws_bytes, _vp(stream))
+        else:
+            rc = _lib.crf_ctc_score(_ptr(log_probs), 1 if time_major else 0, blank, _ptr(lab_d), _ptr(off_d), _ptr(len_d), _ptr(utt_d),
+                                    _ptr(lx_d), N, H, T, V, max_l, _ptr(scores), _ptr(invalid), _vp(stream))
+    _check(rc)
+    del meta
+    return scores, invalid
 
 
 def gpu_den(logits: torch.Tensor, grad_net: torch.Tensor, input_lengths: torch.Tensor,

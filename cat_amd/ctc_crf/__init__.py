@@ -9,6 +9,8 @@ Same names, arguments and error behaviour as the reference:
   _CTC_CRF, _WARP_CTC_GPU  autograd Functions                                             (:25-94)
   ctc_align(log_probs, labels, input_lengths, label_lengths, blank=0, time_major=False, fuse_log_softmax=False) -> (pos, tokens, scores)
                                                                                          (forced alignment; not in the reference)
+  ctc_score(log_probs, hyps, hyp_lengths, input_lengths, hyp_utt=None, blank=0, time_major=False, fuse_log_softmax=False) -> FloatTensor[H]
+                                                                                         (forward-only scores of many hypotheses per utterance)
 plus the functional form named by BASELINE.json:
   ctc_crf_loss(log_probs, labels, frame_lens, label_lens, den_lm, lamb=0.1, size_average=True)
 
@@ -239,6 +241,37 @@ def ctc_align(log_probs: torch.Tensor, labels: torch.Tensor, input_lengths: torc
         pos, tokens, scores, _ = core.ctc_align(log_probs.detach().contiguous(), labels, input_lengths, label_lengths, int(blank),
                                                 bool(time_major), fused=bool(fuse_log_softmax))
     return pos, tokens, scores
+
+
+def ctc_score(log_probs: torch.Tensor, hyps: torch.Tensor, hyp_lengths: torch.Tensor, input_lengths: torch.Tensor,
+              hyp_utt: torch.Tensor = None, blank: int = 0, time_major: bool = False, fuse_log_softmax: bool = False) -> torch.Tensor:
+    """Forward-only CTC log-likelihoods of H hypotheses over N utterances (not in the reference, whose callers loop over
+    nn.CTCLoss(reduction='none') under no_grad, or score N*K hypotheses on repeat_interleave'd activations: cat/ctc/train_jsa.py:147-160,
+    decode_jsa_mls.py:189-191).  The activations are read in place and never replicated; there is no backward chain and no gradient.
+
+    log_probs (torch.FloatTensor): (N, T, V) log-probs on the GPU, or (T, N, V) with time_major=True.
+    hyps (torch.IntTensor): on the CPU, either flattened (sum(hyp_lengths),) or padded (H, Lmax) as nn.CTCLoss takes targets; of a padded
+        row the first hyp_lengths[h] entries count.
+    hyp_lengths (torch.IntTensor): (H,), on the CPU.   input_lengths (torch.IntTensor): (N,), on the CPU.
+    hyp_utt (torch.IntTensor): (H,), on the CPU: the utterance in [0, N) each hypothesis is scored on, in any order; an utterance may own
+        none.  None: H = N and hypothesis h is scored on utterance h -- under no_grad this is -nn.CTCLoss(reduction='none').
+    blank (int): the blank's column; labels lie in [0, V) without it.
+    fuse_log_softmax (bool): log_probs is the RAW network output in fp32, bf16 or fp16; the scores are those of log_softmax.
+
+    Returns FloatTensor[H] on log_probs' device: +log p(hyp | utterance), -inf for a hypothesis that has no alignment (it does not fit
+    into input_lengths[u] frames, or every alignment has probability 0).  No host synchronisation.  The result carries NO autograd
+    history -- requires_grad is False even for an input that requires grad: this is a scoring call, not a loss.
+    A hypothesis's score is the same bits wherever it stands in the list and in either layout."""
+    if fuse_log_softmax:
+        assert log_probs.dtype in (torch.float, torch.bfloat16, torch.float16), f"expect float/bfloat16/float16 network output, instead: {log_probs.dtype}"
+    else:
+        assert log_probs.dtype == torch.float, f"expect log_probs to be torch.float object, instead: {log_probs.dtype}"
+    if not log_probs.is_cuda:
+        raise RuntimeError("ctc_score: log_probs must be on the GPU (there is no CPU path)")
+    with torch.no_grad():
+        scores, _ = core.ctc_score(log_probs.detach().contiguous(), hyps, hyp_lengths, input_lengths, hyp_utt, int(blank), bool(time_major),
+                                   fused=bool(fuse_log_softmax))
+    return scores
 
 
 _CTX_CACHE: Dict[Tuple[str, int], CRFContext] = {}

@@ -235,6 +235,44 @@ int crf_ctc_align_logits(const void *act_dev, int dtype, int time_major, int bla
                          int32_t *pos_dev, float *score_dev, int32_t *invalid_dev,
                          void *workspace_dev, int64_t workspace_bytes, void *stream);
 
+/* Forward-only CTC log-likelihoods of H hypotheses over B utterances (what cat/ctc/train_jsa.py:147-160 and decode_jsa_mls.py:189-191
+ * get from nn.CTCLoss(reduction='none') under no_grad, the latter on repeat_interleave'd activations; N-best rescoring): hypothesis h is
+ * the labels labels_dev[hyp_off_dev[h] .. + hyp_len_dev[h]) scored on the rows of utterance u = hyp_utt_dev[h].  The activations are read in
+ * place, [B][T][V] (time_major = 0) or [T][B][V] (1), and never replicated; no backward chain, no gradient, no workspace, no host sync,
+ * all work on `stream`.  Log domain, fp32, the largest term subtracted, one fixed operand order:
+ *   v_t[s] = act[u][t][lab(s)] + log(exp(v_{t-1}[s]) + exp(v_{t-1}[s-1]) + [s odd and lab(s) != lab(s-2)] exp(v_{t-1}[s-2])),  t < lx[u],
+ *   score_dev[h] = logaddexp(v[2L], v[2L-1])      (+log p, the sign of costs_ctc_dev)
+ * so a hypothesis's score does not depend on its place in the list, on the other hypotheses or on the layout: the same bits across calls,
+ * across a permutation of the list and across the two layouts, as long as max_hyp_len selects the same kernel (up to 2 max_hyp_len + 1 =
+ * 512 states one wave per hypothesis with 1, 2, 4 or 8 states per lane, beyond one workgroup per hypothesis; crf_last_score_kernel()
+ * names the instantiation of this thread's last call, e.g. "crf_ctc_score_wave_kernel<4>").  -inf entries flow through without NaN.
+ *   hyp_utt_dev[h] in [0, B), in any order; an utterance may own no hypothesis.  Device memory, not checked here (an entry outside
+ *                   [0, B) makes the hypothesis invalid, nothing is read for it);
+ *   invalid_dev[h]  (may be NULL) 1 for a hypothesis with L + repeats > lx[u], lx[u] <= 0 or a label outside [0, V): score -inf -- the
+ *                   alignment's rule.  A valid one whose every alignment has probability 0: score -inf, invalid 0.  L = 0 is valid:
+ *                   the sum of the blank's column.
+ * CRF_ERR_ARG: null pointer (invalid_dev excepted), blank outside [0, V), B, H, T or V <= 0, max_hyp_len < 0, B * T > INT32_MAX (H and V
+ * are ints as well); CRF_ERR_UNSUPPORTED: max_hyp_len > 2047.  No limit on V.  All answered before any HIP call. */
+int crf_ctc_score(const float *act_dev, int time_major, int blank, const int32_t *labels_dev, const int32_t *hyp_off_dev,
+                  const int32_t *hyp_len_dev, const int32_t *hyp_utt_dev, const int32_t *lx_dev,
+                  int64_t B, int64_t H, int64_t T, int64_t V, int64_t max_hyp_len,
+                  float *score_dev, int32_t *invalid_dev, void *stream);
+const char *crf_last_score_kernel(void);
+
+/* crf_ctc_score on the RAW network output: act_dev of dtype 0 = fp32, 1 = bf16, 2 = fp16, read in place (2-byte elements are upcast in
+ * registers; rows of 16-bit elements need 2-byte alignment only).  The contract of crf_ctc_align_logits, with x^ the exact upcast:
+ * the recursion above runs on x^ itself, and
+ *   score_dev[h] = float(double(raw) - sum_{t < lx[u]} double(lse_t)),   lse_t of row (u, t) by crf_ctc_align_logits's row kernel,
+ * the sum in fp64 in a fixed order (no atomics); a raw score of -inf stays -inf.  Reproducible bit for bit as crf_ctc_score is.
+ * Workspace: crf_ctc_score_logits_workspace_bytes (the lse values [B][T], fp32; >= 4 B T; its contents on entry do not matter; -1 for
+ * B, T or V <= 0 or B * T > INT32_MAX).  Errors as crf_ctc_score, plus CRF_ERR_ARG for a dtype outside 0..2 or a null workspace and
+ * CRF_ERR_WORKSPACE (the message names the bytes needed). */
+int64_t crf_ctc_score_logits_workspace_bytes(int64_t B, int64_t T, int64_t V);
+int crf_ctc_score_logits(const void *act_dev, int dtype, int time_major, int blank, const int32_t *labels_dev,
+                         const int32_t *hyp_off_dev, const int32_t *hyp_len_dev, const int32_t *hyp_utt_dev, const int32_t *lx_dev,
+                         int64_t B, int64_t H, int64_t T, int64_t V, int64_t max_hyp_len,
+                         float *score_dev, int32_t *invalid_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+
 /* Replaces the cudaMemcpyAsync calls that bring labels, label lengths and input lengths to the device
  * (gpu_ctc.h:143-229; `input_lengths.cuda()`, ctc_crf/__init__.py:73): copies n int32 from PINNED host
  * memory (hipHostMalloc / torch pin_memory: device-accessible) to device memory with a kernel on `stream` --
