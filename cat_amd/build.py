@@ -17,7 +17,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-FAMILIES = ["k_fac_768.hip", "k_fac_pair2.hip", "k_fac_1024.hip", "k_batch.hip", "k_grad.hip", "k_res.hip", "k_chain.hip", "k_robust.hip", "k_align.hip", "k_score.hip"]   # slowest first
+FAMILIES = ["k_fac_768.hip", "k_fac_pair2.hip", "k_fac_1024.hip", "k_batch.hip", "k_grad.hip", "k_res.hip", "k_chain.hip", "k_robust.hip", "k_align.hip", "k_score.hip", "k_sample.hip"]   # slowest first
 UNITS = FAMILIES + ["crf_host.hip", "res_layout.cpp", "fst_graph.cpp", "ctc_api.cpp"]
 HEADERS = [os.path.join(CSRC, h) for h in ("crf_internal.h", "crf_device.h", "crf_kernels_decl.h", "k_res_common.h", "k_fac_body.h")] + \
           [os.path.join(os.path.dirname(HERE), "include", h) for h in ("ctc_crf_hip.h", "ctc.h")]

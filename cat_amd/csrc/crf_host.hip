@@ -440,6 +440,7 @@ static thread_local int g_call_streams = 1;          // crf_last_call_streams
 static thread_local const char *g_side_desc = "none";   // crf_last_side_stream
 static thread_local const int *g_last_err_word = nullptr;   // error word (+ kFlagFallback: fallback counts) of this thread's last call -- crf_last_fallback_counts
 static thread_local const char *g_den_kernel = "";   // template instantiation of the denominator recursions' kernel in the last call (crf_last_den_kernel)
+static thread_local const char *g_sample_kernel = ""; // ... of the row kernel of this thread's last crf_ctc_sample (crf_last_sample_kernel)
 static thread_local const char *g_score_kernel = ""; // ... of the kernel of this thread's last crf_ctc_score / crf_ctc_score_logits (crf_last_score_kernel)
 static void prof_mark(int slot, bool stop, hipStream_t st) {
     if (!g_prof.on) return;
@@ -530,6 +531,29 @@ static int launch_score_logits(const ScoreParams &p, hipStream_t st, int64_t max
     const int rc = p.V <= kAlnLseSmallV ? launch<crf_align_lse_kernel<16, E>>("crf_align_lse_kernel", dim3((unsigned)((frames + 15) / 16)), dim3(256), 0, st, a)
                                         : launch<crf_align_lse_kernel<64, E>>("crf_align_lse_kernel", dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, st, a);
     return rc ? rc : launch_score<E, true>(p, st, max_hyp_len);
+}
+// sampled / best-path label sequences (k_sample.hip): the row stage over the B T frames -- 16 lanes per row up to kSampleSmallV classes,
+// beyond a wave per row, per row V + 2 G words of dynamic LDS (none for the arg-max) -- then the collapse, one wave per path, on the same stream
+template <typename E>
+static int launch_sample(const SampleParams &p, hipStream_t st, bool greedy) {
+    const int64_t frames = (int64_t)p.B * p.T;
+    int rc;
+    if (p.V <= kSampleSmallV) {
+        constexpr int R = kSampleRowThreads(16) / 16;
+        const dim3 grid((unsigned)((frames + R - 1) / R)), block(kSampleRowThreads(16));
+        rc = greedy ? launch<crf_sample_row_kernel<16, E, true>>(g_sample_kernel = "crf_sample_row_kernel<16, greedy>", grid, block, 0, st, p)
+                    : launch<crf_sample_row_kernel<16, E, false>>(g_sample_kernel = "crf_sample_row_kernel<16>", grid, block,
+                                                                  (size_t)R * (p.V + 2 * 16) * sizeof(float), st, p);
+    } else {
+        const dim3 grid((unsigned)frames), block(kSampleRowThreads(64));
+        rc = greedy ? launch<crf_sample_row_kernel<64, E, true>>(g_sample_kernel = "crf_sample_row_kernel<64, greedy>", grid, block, 0, st, p)
+                    : launch<crf_sample_row_kernel<64, E, false>>(g_sample_kernel = "crf_sample_row_kernel<64>", grid, block,
+                                                                  (size_t)(p.V + 2 * 64) * sizeof(float), st, p);
+    }
+    if (rc) return rc;
+    const int64_t H = (int64_t)p.B * p.K;
+    return launch<crf_sample_collapse_kernel>("crf_sample_collapse_kernel", dim3((unsigned)((H + kSampleWaves - 1) / kSampleWaves)),
+                                              dim3(kSampleWaves * 64), 0, st, p);
 }
 static int64_t align_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t max_label_len, bool lse, AlignWs *out) {
     if (B <= 0 || T <= 0 || V <= 0 || max_label_len < 0) { set_error("crf_ctc_align: bad B/T/V/max_label_len"); return -CRF_ERR_ARG; }
@@ -990,6 +1014,44 @@ int crf_ctc_score_logits(const void *act, int dtype, int time_major, int blank, 
     if (dtype == 0) return launch_score_logits<float>(p, (hipStream_t)stream_, max_hyp_len);
     if (dtype == 1) return launch_score_logits<AlnBf16>(p, (hipStream_t)stream_, max_hyp_len);
     return launch_score_logits<AlnF16>(p, (hipStream_t)stream_, max_hyp_len);
+}
+
+// crf_ctc_sample's workspace: the classes drawn per frame, [B K][T] int32 (one section, laid down as the others are: 256-aligned, the
+// ws_gap bytes behind it)
+static int64_t sample_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t K) {
+    if (B <= 0 || T <= 0 || V <= 0 || K <= 0) { set_error("crf_ctc_sample: bad B/T/V/K"); return -CRF_ERR_ARG; }
+    if (B > INT32_MAX || T > INT32_MAX || K > INT32_MAX || B * T > INT32_MAX) { set_error("crf_ctc_sample: B * T > INT32_MAX"); return -CRF_ERR_ARG; }
+    if (B * K > INT32_MAX) { set_error("crf_ctc_sample: B * K > INT32_MAX"); return -CRF_ERR_ARG; }
+    if (V > kSampleMaxV) { set_error("V > " + std::to_string(kSampleMaxV) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
+    if (K > (INT64_MAX / 8) / (B * T)) { set_error("crf_ctc_sample: B * K * T too large"); return -CRF_ERR_ARG; }
+    return al(B * K * T * (int64_t)sizeof(int32_t)) + ws_gap_bytes();
+}
+
+int64_t crf_ctc_sample_workspace_bytes(int64_t B, int64_t T, int64_t V, int64_t K) {
+    const int64_t n = sample_ws_bytes(B, T, V, K);
+    return n < 0 ? -1 : n;
+}
+
+// Every error is answered here, before any HIP call.
+int crf_ctc_sample(const void *act, int dtype, int time_major, int blank, const int32_t *lx, int64_t B, int64_t T, int64_t V, int64_t K,
+                   uint64_t seed, uint32_t offset, int greedy, int32_t *hyps, int32_t *hyp_len, int32_t *paths, void *ws, int64_t ws_bytes,
+                   void *stream_) {
+    if (!act || !lx || !hyps || !hyp_len || !ws) { set_error("crf_ctc_sample: null argument"); return CRF_ERR_ARG; }
+    if (dtype < 0 || dtype > 2) { set_error("crf_ctc_sample: dtype must be 0 (f32), 1 (bf16) or 2 (f16)"); return CRF_ERR_ARG; }
+    const int64_t need = sample_ws_bytes(B, T, V, K);
+    if (need < 0) return (int)-need;
+    if (blank < 0 || blank >= V) { set_error("blank " + std::to_string(blank) + " outside [0, V=" + std::to_string(V) + ")"); return CRF_ERR_ARG; }
+    if (greedy && K != 1) { set_error("crf_ctc_sample: greedy takes K = 1, got " + std::to_string(K)); return CRF_ERR_ARG; }
+    if (ws_bytes < need) { set_error("workspace too small: need " + std::to_string(need)); return CRF_ERR_WORKSPACE; }
+    SampleParams p{};
+    p.x = act; p.lx = lx;
+    p.B = (int)B; p.T = (int)T; p.V = (int)V; p.K = (int)K; p.blank = blank;
+    p.seed_lo = (unsigned)(seed & 0xffffffffu); p.seed_hi = (unsigned)(seed >> 32); p.offset = offset;
+    p.xs_b = time_major ? V : T * V; p.xs_t = time_major ? B * V : V;
+    p.cls = (int *)ws; p.hyps = hyps; p.hyp_len = hyp_len; p.paths = paths;
+    if (dtype == 0) return launch_sample<float>(p, (hipStream_t)stream_, greedy != 0);
+    if (dtype == 1) return launch_sample<AlnBf16>(p, (hipStream_t)stream_, greedy != 0);
+    return launch_sample<AlnF16>(p, (hipStream_t)stream_, greedy != 0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1812,6 +1874,7 @@ const char *crf_build_switches(void) {
 
 const char *crf_last_den_kernel(void) { return g_den_kernel; }
 const char *crf_last_score_kernel(void) { return g_score_kernel; }
+const char *crf_last_sample_kernel(void) { return g_sample_kernel; }
 int crf_last_call_streams(void) { return g_call_streams; }
 const char *crf_last_side_stream(void) { return g_side_desc; }
 

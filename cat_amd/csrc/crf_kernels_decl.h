@@ -57,6 +57,27 @@ struct ScoreParams {
 template <int NR, typename E = float, bool LSE = false> __global__ void crf_ctc_score_wave_kernel(ScoreParams p);   // NR 1, 2, 4, 8
 template <int NR, typename E = float, bool LSE = false> __global__ void crf_ctc_score_wg_kernel(ScoreParams p);     // NR 2, 4, kCtcRegs
 
+// ---- k_sample.hip ----
+constexpr int kSampleSmallV = 256;        // rows of up to here: 16 lanes per row and 16 rows per workgroup, beyond: a wave per row and workgroup
+constexpr int kSampleMaxV = 8192;         // the row and its running sums are staged in LDS: 32.5 KiB per row at most
+constexpr int kSampleWaves = 4;           // paths (waves) per workgroup of the collapse
+constexpr int kSampleRowThreads(int G) { return G == 16 ? 256 : 64; }
+// Kernel arguments of crf_ctc_sample: the activations as for the alignment (row (n, t) at n * xs_b + t * xs_t ELEMENTS, read in place)
+struct SampleParams {
+    const void *x;
+    const int *lx;
+    int B, T, V, K, blank;
+    unsigned seed_lo, seed_hi, offset;
+    int64_t xs_b, xs_t;
+    int *cls;                   // [B K][T] the class drawn per frame (workspace; frames t >= lx are never written, and never read)
+    int *hyps, *hyp_len;        // [B K][T], [B K]
+    int *paths;                 // [B K][T] or null
+};
+// G lanes per row: 16, 64.  E: float, AlnBf16, AlnF16.  GREEDY: the arg-max instead of the K draws (K = 1).  Dynamic LDS: (rows per
+// workgroup) x (V + 2 G) words, none with GREEDY.
+template <int G, typename E, bool GREEDY> __global__ void crf_sample_row_kernel(SampleParams p);
+__global__ void crf_sample_collapse_kernel(SampleParams p);
+
 // ---- k_res.hip ----
 constexpr int kEpRegsR = 2;   // emission-row prefetch registers (V <= 2*512 for the resident kernels)
 constexpr int kPoll = 4;      // granules polled concurrently per thread

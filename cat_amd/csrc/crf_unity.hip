@@ -10,4 +10,5 @@
 #include "k_robust.hip"
 #include "k_align.hip"
 #include "k_score.hip"
+#include "k_sample.hip"
 #include "crf_host.hip"

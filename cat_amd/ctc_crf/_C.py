@@ -68,6 +68,12 @@ _lib.crf_ctc_score_logits.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_
                                       _vp, _vp, _vp, _i64, _vp]
 _lib.crf_ctc_score_logits.restype = ctypes.c_int
 _lib.crf_last_score_kernel.restype = ctypes.c_char_p
+_lib.crf_ctc_sample_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64]
+_lib.crf_ctc_sample_workspace_bytes.restype = _i64
+_lib.crf_ctc_sample.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _i64, _i64, _i64, _i64, ctypes.c_uint64, ctypes.c_uint32,
+                                ctypes.c_int, _vp, _vp, _vp, _vp, _i64, _vp]
+_lib.crf_ctc_sample.restype = ctypes.c_int
+_lib.crf_last_sample_kernel.restype = ctypes.c_char_p
 _lib.crf_profile_enable.argtypes = [ctypes.c_int]
 _lib.crf_profile_enable.restype = None
 _lib.crf_profile_read.argtypes = [ctypes.POINTER(_f32), ctypes.c_int]
@@ -92,7 +98,7 @@ _lib.crf_build_switches.restype = ctypes.c_char_p
 
 EXPORTED_SYMBOLS = (
     "crf_graph_create", "crf_graph_create_from_arcs", "crf_graph_destroy", "crf_graph_dims", "crf_graph_stats",
-    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_ctc_score", "crf_ctc_score_logits_workspace_bytes", "crf_ctc_score_logits", "crf_last_score_kernel", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
+    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_ctc_score", "crf_ctc_score_logits_workspace_bytes", "crf_ctc_score_logits", "crf_last_score_kernel", "crf_ctc_sample_workspace_bytes", "crf_ctc_sample", "crf_last_sample_kernel", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
     "crf_debug_set", "crf_debug_unset", "crf_debug_list", "crf_last_den_kernel", "crf_last_call_streams", "crf_last_side_stream", "crf_last_fallback_counts", "crf_build_switches", "crf_last_error", "crf_version",
 )
 
@@ -119,6 +125,11 @@ def last_den_kernel() -> str:
 def last_score_kernel() -> str:
     """Template instantiation of the kernel of this thread's last ctc_score call (include/ctc_crf_hip.h crf_last_score_kernel)."""
     return _lib.crf_last_score_kernel().decode()
+
+
+def last_sample_kernel() -> str:
+    """Template instantiation of the row kernel of this thread's last ctc_sample call (include/ctc_crf_hip.h crf_last_sample_kernel)."""
+    return _lib.crf_last_sample_kernel().decode()
 
 
 def last_call_streams() -> int:
@@ -714,6 +725,77 @@ def ctc_score(log_probs: torch.Tensor, hyps: torch.Tensor, hyp_lengths: torch.Te
     _check(rc)
     del meta
     return scores, invalid
+
+
+def ctc_sample(log_probs: torch.Tensor, lx: torch.Tensor, n_samples: int, seed: int, offset: int = 0, blank: int = 0,
+               time_major: bool = False, greedy: bool = False, return_paths: bool = False, hyps_out: Optional[torch.Tensor] = None,
+               paths_out: Optional[torch.Tensor] = None):
+    """Label sequences drawn on the GPU (include/ctc_crf_hip.h ``crf_ctc_sample``): per frame K = n_samples classes from
+    softmax(log_probs) -- counter-based, Philox4x32-10 on (seed, offset, n, t, k) -- or with greedy the arg-max (K = 1), then the CTC
+    collapse of each of the N K frame paths.
+
+    log_probs [N,T,V] (time_major: [T,N,V]) f32 / bf16 / f16 on the GPU, contiguous, read in place; lx an int tensor on the CPU.  Returns
+    (hyps [N K, T] int32, padded with the blank's index; hyp_lengths [N K] int32; paths [N K, T] int32 or None: the class per frame, -1
+    past lx), all on the device, no host synchronisation.  hyps_out / paths_out: contiguous int32 [N K, T] device tensors that receive
+    the results (else allocated; paths_out implies return_paths)."""
+    who = "ctc_greedy" if greedy else "ctc_sample"
+    if log_probs.dtype not in _FUSED_DTYPES:
+        raise RuntimeError(f"{who}: expect float32, bfloat16 or float16 activations, got {log_probs.dtype}")
+    if log_probs.dim() != 3:
+        raise RuntimeError(f"{who}: expect (N, T, V) or (T, N, V) activations, got {log_probs.dim()} dimensions")
+    N, T, V = _check_sample_args(log_probs.shape, lx, n_samples, seed, offset, blank, time_major, greedy)
+    if not log_probs.is_cuda:                  # (after the checks of the arguments: those need no device)
+        raise RuntimeError(f"{who}: log_probs must be on the GPU (there is no CPU path)")
+    assert log_probs.is_contiguous()
+    K = int(n_samples)
+    dev = log_probs.device
+    lx_d = _h2d_async(lx.to(torch.int32).reshape(-1), dev)
+    H = N * K
+    ws_bytes = _lib.crf_ctc_sample_workspace_bytes(N, T, V, K)
+    if ws_bytes < 0:
+        _check(1)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    if _POISON_WS:
+        ws.fill_(0xFF)
+    hyps = torch.empty((H, T), dtype=torch.int32, device=dev) if hyps_out is None else hyps_out
+    paths = paths_out if paths_out is not None else torch.empty((H, T), dtype=torch.int32, device=dev) if return_paths else None
+    for o in (hyps, paths):
+        assert o is None or (o.shape == (H, T) and o.dtype == torch.int32 and o.is_contiguous() and o.device == dev)
+    hyp_len = torch.empty(H, dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        rc = _lib.crf_ctc_sample(_ptr(log_probs), _FUSED_DTYPES[log_probs.dtype], 1 if time_major else 0, int(blank), _ptr(lx_d), N, T, V, K,
+                                 int(seed), int(offset), 1 if greedy else 0, _ptr(hyps), _ptr(hyp_len), _ptr(paths), _ptr(ws), ws_bytes,
+                                 _vp(stream))
+    _check(rc)
+    del lx_d
+    return hyps, hyp_len, paths
+
+
+def _check_sample_args(shape, lx: torch.Tensor, n_samples: int, seed: int, offset: int, blank: int, time_major: bool, greedy: bool):
+    """The host checks of ctc_sample / ctc_greedy, each with the offending value in the message.  -> (N, T, V)."""
+    who = "ctc_greedy" if greedy else "ctc_sample"
+    N, T, V = shape
+    if time_major:
+        T, N = N, T
+    if not 0 <= blank < V:
+        raise RuntimeError(f"blank must lie in [0, V-1={V - 1}], got {blank}")
+    if int(n_samples) < 1:
+        raise RuntimeError(f"{who}: n_samples must be at least 1, got {n_samples}")
+    if greedy and int(n_samples) != 1:
+        raise RuntimeError(f"{who}: the best path is one path per utterance, got n_samples={n_samples}")
+    if not 0 <= int(seed) < 1 << 64:
+        raise RuntimeError(f"{who}: seed must lie in [0, 2^64), got {seed}")
+    if not 0 <= int(offset) < 1 << 32:
+        raise RuntimeError(f"{who}: offset must lie in [0, 2^32), got {offset}")
+    if lx.is_cuda:
+        raise RuntimeError(f"{who}: input_lengths is a CPU tensor")
+    lx32 = lx.to(torch.int32).reshape(-1)
+    if lx32.numel() != N:
+        raise RuntimeError(f"{who}: expect {N} input lengths, got {lx32.numel()}")
+    if N > 0 and int(lx32.max()) > T:
+        raise RuntimeError(f"frame lengths must lie in [0, T={T}], got max {int(lx32.max())}")
+    return N, T, V
 
 
 def gpu_den(logits: torch.Tensor, grad_net: torch.Tensor, input_lengths: torch.Tensor,

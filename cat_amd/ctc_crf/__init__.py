@@ -11,6 +11,10 @@ Same names, arguments and error behaviour as the reference:
                                                                                          (forced alignment; not in the reference)
   ctc_score(log_probs, hyps, hyp_lengths, input_lengths, hyp_utt=None, blank=0, time_major=False, fuse_log_softmax=False) -> FloatTensor[H]
                                                                                          (forward-only scores of many hypotheses per utterance)
+  ctc_sample(log_probs, input_lengths, n_samples, seed, offset=0, blank=0, time_major=False, return_paths=False)
+                                                              -> (hyps IntTensor[N*K, T], hyp_lengths IntTensor[N*K], hyp_utt IntTensor[N*K])
+                                                                                         (K label sequences per utterance drawn on the GPU)
+  ctc_greedy(log_probs, input_lengths, blank=0, time_major=False) -> (hyps IntTensor[N, T], hyp_lengths IntTensor[N])   (best path)
 plus the functional form named by BASELINE.json:
   ctc_crf_loss(log_probs, labels, frame_lens, label_lens, den_lm, lamb=0.1, size_average=True)
 
@@ -272,6 +276,46 @@ def ctc_score(log_probs: torch.Tensor, hyps: torch.Tensor, hyp_lengths: torch.Te
         scores, _ = core.ctc_score(log_probs.detach().contiguous(), hyps, hyp_lengths, input_lengths, hyp_utt, int(blank), bool(time_major),
                                    fused=bool(fuse_log_softmax))
     return scores
+
+
+def ctc_sample(log_probs: torch.Tensor, input_lengths: torch.Tensor, n_samples: int, seed: int, offset: int = 0, blank: int = 0,
+               time_major: bool = False, return_paths: bool = False):
+    """K = n_samples label sequences per utterance drawn on the GPU: per frame K classes from softmax(log_probs), then the CTC collapse
+    (repeats merged, blanks dropped) of each of the N K frame paths -- the reference's `_sample` (cat/ctc/train_jsa.py:256-269:
+    torch.multinomial over N T rows, a transpose, a repeat of the lengths and the third-party ctc_align.align_) in one call.
+
+    log_probs: (N, T, V) on the GPU, or (T, N, V) with time_major=True; fp32, bf16 or fp16, read in place.  Log-probs and raw network
+        output are drawn from alike: the distribution is softmax of the row (for log-probs that is exp), so there is no fuse switch.
+        Rows hold neither NaN nor +inf; a class at -inf is never drawn; a row of -inf only emits the blank.
+    input_lengths (torch.IntTensor): (N,), on the CPU, none above T.
+    seed, offset: Python ints in [0, 2^64) and [0, 2^32).  The draws are counter-based -- Philox4x32-10 on (seed, offset, n, t, k) -- and
+        never touch torch's generator: for fixed (seed, offset) the sample of utterance n, draw k is the same bits in both layouts, in any
+        batch (n is the index in the call), for any n_samples > k and across calls.  Advance offset (or seed) for fresh samples.
+
+    Returns (hyps, hyp_lengths, hyp_utt) and, with return_paths, paths -- IntTensors on log_probs' device, no host synchronisation, no
+    autograd history:
+        hyps (N K, T): row h = n K + k holds the hyp_lengths[h] labels of the sequence, then the BLANK's index up to T (padded as
+            pad_sequence(padding_value=blank) pads: the rows go straight into an embedding);
+        hyp_utt (N K,): h // K, so that ctc_score(log_probs, hyps.cpu(), hyp_lengths.cpu(), input_lengths, hyp_utt.cpu()) scores them;
+        paths (N K, T): the class drawn per frame, -1 for t >= input_lengths[n]."""
+    with torch.no_grad():
+        hyps, hyp_lengths, paths = core.ctc_sample(log_probs.detach().contiguous(), input_lengths, n_samples, seed, offset, int(blank),
+                                                   bool(time_major), return_paths=bool(return_paths))
+        hyp_utt = torch.arange(hyps.size(0), dtype=torch.int32, device=hyps.device).div_(int(n_samples), rounding_mode="floor")
+    return (hyps, hyp_lengths, hyp_utt, paths) if return_paths else (hyps, hyp_lengths, hyp_utt)
+
+
+def ctc_greedy(log_probs: torch.Tensor, input_lengths: torch.Tensor, blank: int = 0, time_major: bool = False):
+    """Best-path CTC decoding on the GPU: the arg-max of every frame (the lowest class among equals, as torch.argmax), collapsed.
+
+    log_probs: (N, T, V) on the GPU, or (T, N, V) with time_major=True; fp32, bf16 or fp16 log-probs or raw network output, read in place.
+    input_lengths (torch.IntTensor): (N,), on the CPU, none above T.
+    Returns (hyps IntTensor[N, T], hyp_lengths IntTensor[N]) on log_probs' device, hyps padded with the blank's index; no host
+    synchronisation, no autograd history."""
+    with torch.no_grad():
+        hyps, hyp_lengths, _ = core.ctc_sample(log_probs.detach().contiguous(), input_lengths, 1, 0, 0, int(blank), bool(time_major),
+                                               greedy=True)
+    return hyps, hyp_lengths
 
 
 _CTX_CACHE: Dict[Tuple[str, int], CRFContext] = {}

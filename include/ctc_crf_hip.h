@@ -273,6 +273,41 @@ int crf_ctc_score_logits(const void *act_dev, int dtype, int time_major, int bla
                          int64_t B, int64_t H, int64_t T, int64_t V, int64_t max_hyp_len,
                          float *score_dev, int32_t *invalid_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
 
+/* Label sequences drawn on the GPU (what cat/ctc/train_jsa.py:256-269 `_sample` gets from torch.multinomial over N T rows, a transpose and
+ * the third-party ctc_align.align_; with greedy = 1 the best path: arg-max per frame): per frame K classes from softmax(x), then the CTC
+ * map B on each of the B K frame paths.  The activations are read in place, [B][T][V] (time_major = 0) or [T][B][V] (1), dtype 0 = fp32,
+ * 1 = bf16, 2 = fp16 (rows of 16-bit elements need 2-byte alignment only), x^ = the exact fp32 upcast of row (n, t), t < lx[n].
+ *   Weights   w_v = exp(x^_v - max_v x^_v); the draws follow w / sum w = softmax(x^) -- for log-probs that is exp(x): ONE code path for
+ *             log-probs and raw output, no fuse switch.  Rows must hold neither NaN nor +inf (their draws are unspecified; no access out
+ *             of bounds whatever a row holds).  A row of -inf only emits the blank.
+ *   Uniforms  (r0, r1, r2, r3) = Philox4x32-10(counter = (t, n, k >> 2, offset), key = (seed & 0xffffffff, seed >> 32));
+ *             draw k uses u = (r[k & 3] >> 8) 2^-24 in [0, 1).  n: the utterance's index in the call, t: the frame.
+ *   Selection the smallest v with C[v] > u C[V-1] (both fp32).  C is the kernel's fp32 inclusive running sum of w: chunks of G consecutive
+ *             classes (G = 16 for V <= 256, else 64), a Hillis-Steele scan inside a chunk, the earlier chunks' sum added last -- and, as
+ *             the partial sums of a parallel scan are not ordered among themselves, of those sums the running maximum over the classes
+ *             of positive weight.  Exact consequences: a class with w_v = 0 (entry -inf, or exp underflows) is never drawn; some class
+ *             with w_v > 0 always is (a search that runs off the end takes the last one).
+ *   Greedy    (K = 1) the smallest v attaining the row maximum of x^ -- torch.argmax's rule, so class 0 for a row of -inf only.
+ *   Collapse  frame t of path h = n K + k is kept iff c_t != blank and (t = 0 or c_t != c_{t-1});  hyps_dev[h][0 .. len) = the kept
+ *             classes in frame order, hyp_len_dev[h] = len, hyps_dev[h][len .. T) = the BLANK's index (the padded rows go straight into
+ *             an embedding).  lx[n] <= 0: length 0, a row of blanks; lx[n] > T counts as T.
+ *   paths_dev (may be NULL) [B K][T]: the class drawn per frame, -1 for t >= lx[n].
+ * Every entry of hyps_dev, hyp_len_dev and paths_dev is written by the call.  For fixed (seed, offset) the outputs of (n, k) are the same
+ * bits in both layouts, for any B and any other utterances in the call, for any K > k and across calls; they may differ between dtypes and
+ * between the two row kernels (crf_last_sample_kernel() names this thread's last one: "crf_sample_row_kernel<16>" for V <= 256,
+ * "crf_sample_row_kernel<64>" beyond, "... , greedy>" for the arg-max).
+ * Workspace: crf_ctc_sample_workspace_bytes (the classes per frame, [B K][T] int32; its contents on entry do not matter; -1 with
+ * crf_last_error() set for a shape not taken).  No host synchronisation, all work on `stream`, no environment variable read.
+ * CRF_ERR_ARG: null pointer (paths_dev excepted), dtype outside 0..2, blank outside [0, V), B, T, V or K <= 0, greedy with K != 1,
+ * B * T or B * K > INT32_MAX; CRF_ERR_UNSUPPORTED: V > 8192 (the row's CDF is staged in LDS); CRF_ERR_WORKSPACE: workspace too small (the
+ * message names the bytes needed) -- all answered before any HIP call. */
+int64_t crf_ctc_sample_workspace_bytes(int64_t B, int64_t T, int64_t V, int64_t K);
+int crf_ctc_sample(const void *act_dev, int dtype, int time_major, int blank, const int32_t *lx_dev,
+                   int64_t B, int64_t T, int64_t V, int64_t K, uint64_t seed, uint32_t offset, int greedy,
+                   int32_t *hyps_dev, int32_t *hyp_len_dev, int32_t *paths_dev,
+                   void *workspace_dev, int64_t workspace_bytes, void *stream);
+const char *crf_last_sample_kernel(void);
+
 /* Replaces the cudaMemcpyAsync calls that bring labels, label lengths and input lengths to the device
  * (gpu_ctc.h:143-229; `input_lengths.cuda()`, ctc_crf/__init__.py:73): copies n int32 from PINNED host
  * memory (hipHostMalloc / torch pin_memory: device-accessible) to device memory with a kernel on `stream` --
