@@ -1,6 +1,6 @@
 // cat_amd/csrc/crf_device.h -- what every kernel family of the CTC-CRF loss shares: the kernel argument block (LossParams), the build-time
 // A/B switches, wave / block reductions, the exact power-of-two rescale helpers, LDS-only barriers, the in-kernel timing stamps.
-// Included by every translation unit under cat_amd/csrc/k_*.hip and by crf_host.hip (the host side and the C ABI).
+// Included by every translation unit under cat_amd/csrc/k_*.hip and by crf_host.hip / crf_host_ctc.hip (the host side and the C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

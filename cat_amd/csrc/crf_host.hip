@@ -1,5 +1,7 @@
 // cat_amd/csrc/crf_host.hip -- the host side of the CTC-CRF loss: workspace layout, streams and schedule, kernel launches, the C-ABI entry
-// points of include/ctc_crf_hip.h.  The kernels live in one translation unit per family (cat_amd/build.py compiles them in parallel):
+// points of include/ctc_crf_hip.h.  (Forced alignment, hypothesis scores and sampling share nothing with the loss call: crf_host_ctc.hip;
+// what both host units use -- the section records, launch<> -- is crf_host_util.h.)  The kernels live in one translation unit per family
+// (cat_amd/build.py compiles them in parallel):
 //   k_chain.hip      prep (e' = exp(logp - rowmax) * 2^64), metadata staging, streaming denominator chains, numerator (CTC) chains in fp64
 //   k_fac_*.hip      register-resident denominator recursions on the factored layout of T o LM graphs (k_fac_body.h): the dominant kernels
 //   k_res.hip        register-resident recursions, generic layout over K compute units
@@ -31,6 +33,7 @@
 
 #include "crf_device.h"
 #include "crf_kernels_decl.h"
+#include "crf_host_util.h"
 
 namespace crf {
 
@@ -53,10 +56,6 @@ static const char *const kWsNames[kWsCount] = {
     CRF_WS_SECTIONS(CRF_WS_NAME)
 #undef CRF_WS_NAME
 };
-struct WsSection { const char *name; int64_t off, bytes; };
-static int64_t al(int64_t x) { return (x + 255) & ~(int64_t)255; }
-// bytes no kernel may touch behind every section: the switch ws_gap x 256 (tests/guard.py); unset, the sections are packed
-static int64_t ws_gap_bytes() { return 256 * (int64_t)std::max(0, opt(kOpt_ws_gap, 0)); }
 struct WsLayout {
     WsSection sec[kWsCount];     // in layout order: sec[k] is section k of CRF_WS_SECTIONS
     int nsec;
@@ -194,7 +193,6 @@ static size_t chain_lds_bytes(const HostGraph *h, int V, int Sc, int role, bool 
 // ---------------------------------------------------------------------------------------------
 constexpr int kMaxStages = 16;
 constexpr int kFlagInts = 2048;
-constexpr int kMaxDev = 64;
 struct DevCtx {
     std::mutex mu;            // one call at a time is ENQUEUED through a context (host side only; nothing waits on the GPU)
     int dev = 0;
@@ -215,31 +213,6 @@ struct DevCtx {
 };
 static std::mutex g_ctx_mu;
 static std::vector<DevCtx *> g_ctxs;
-
-// Dynamic LDS above 64 KiB must be opted into per kernel AND per device (hipFuncSetAttribute acts on the current
-// device's copy of the function): high-water mark per device.
-struct LdsMark { std::atomic<size_t> v[kMaxDev]; };
-static int ensure_lds(const void *fn, size_t bytes, LdsMark &m, const char *what) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) { set_error("hipGetDevice failed"); return CRF_ERR_HIP; }
-    if (bytes <= m.v[dev].load()) return CRF_OK;
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) { set_error(std::string("hipFuncSetAttribute(") + what + "): " + hipGetErrorString(e)); return CRF_ERR_HIP; }
-    m.v[dev] = bytes;
-    return CRF_OK;
-}
-// Every kernel launch of this file.  K is a template argument, so each instantiation has its own mark; a launch with dynamic LDS raises
-// it first; a launch error comes back as CRF_ERR_HIP with the kernel's name (the text is built on failure only).
-template <auto K, typename... A>
-static int launch(const char *name, dim3 grid, dim3 block, size_t lds, hipStream_t st, const A &...args) {
-    static LdsMark mark;
-    int rc;
-    if (lds > 0 && (rc = ensure_lds((const void *)K, lds, mark, name))) return rc;
-    hipLaunchKernelGGL(K, grid, block, lds, st, args...);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string(name) + ": " + hipGetErrorString(e)); return CRF_ERR_HIP; }
-    return CRF_OK;
-}
 
 // Do two streams run side by side?  HIP maps every stream of the process onto GPU_MAX_HW_QUEUES (default 4) hardware
 // queues; two streams on one queue run their kernels one after the other.  Two single-wave kernels shake hands through
@@ -440,8 +413,6 @@ static thread_local int g_call_streams = 1;          // crf_last_call_streams
 static thread_local const char *g_side_desc = "none";   // crf_last_side_stream
 static thread_local const int *g_last_err_word = nullptr;   // error word (+ kFlagFallback: fallback counts) of this thread's last call -- crf_last_fallback_counts
 static thread_local const char *g_den_kernel = "";   // template instantiation of the denominator recursions' kernel in the last call (crf_last_den_kernel)
-static thread_local const char *g_sample_kernel = ""; // ... of the row kernel of this thread's last crf_ctc_sample (crf_last_sample_kernel)
-static thread_local const char *g_score_kernel = ""; // ... of the kernel of this thread's last crf_ctc_score / crf_ctc_score_logits (crf_last_score_kernel)
 static void prof_mark(int slot, bool stop, hipStream_t st) {
     if (!g_prof.on) return;
     if (!g_prof.made) {
@@ -472,101 +443,6 @@ static int launch_ctc_pair(const LossParams &p, size_t lds, hipStream_t st, int6
                            : launch<crf_ctc_pair_kernel<kCtcRegs>>("crf_ctc_pair_kernel", grid, block, lds, st, p);
     prof_mark(3, true, st); prof_mark(4, true, st);
     return rc ? rc : launch<crf_ctc_check_kernel>("crf_ctc_check_kernel", dim3((unsigned)p.B), dim3(256), 0, st, p);
-}
-
-// forced alignment (k_align.hip): one workgroup per utterance, states per thread from the longest label sequence as for the chains
-template <typename E = float, bool LSE = false>
-static int launch_align(const AlignParams &p, hipStream_t st, int64_t max_label_len) {
-    const int64_t ni = (2 * max_label_len + 1 + kCtcThreads - 1) / kCtcThreads;
-    const dim3 grid((unsigned)p.B), block(kCtcThreads);
-    if (ni <= 1) return launch<crf_ctc_align_kernel<1, E, LSE>>("crf_ctc_align_kernel", grid, block, 0, st, p);
-    if (ni <= 2) return launch<crf_ctc_align_kernel<2, E, LSE>>("crf_ctc_align_kernel", grid, block, 0, st, p);
-    if (ni <= 4) return launch<crf_ctc_align_kernel<4, E, LSE>>("crf_ctc_align_kernel", grid, block, 0, st, p);
-    return launch<crf_ctc_align_kernel<kCtcRegs, E, LSE>>("crf_ctc_align_kernel", grid, block, 0, st, p);
-}
-// raw network output: the frames' lse values first (G lanes per frame), then the alignment on the upcast values, on the same stream
-template <typename E>
-static int launch_align_logits(const AlignParams &p, hipStream_t st, int64_t max_label_len) {
-    const int64_t frames = (int64_t)p.B * p.T;
-    const int rc = p.V <= kAlnLseSmallV ? launch<crf_align_lse_kernel<16, E>>("crf_align_lse_kernel", dim3((unsigned)((frames + 15) / 16)), dim3(256), 0, st, p)
-                                        : launch<crf_align_lse_kernel<64, E>>("crf_align_lse_kernel", dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, st, p);
-    return rc ? rc : launch_align<E, true>(p, st, max_label_len);
-}
-// its workspace: the back-pointer words [B][ceil(T / kAlnFrames)][2 * max_label_len + 1 rounded up to 64], then -- raw network output
-// (crf_ctc_align_logits) -- the frames' lse values [B][T]; sections laid down as WsLayout's are (256-aligned, the ws_gap bytes behind each)
-constexpr int kAlignWsCount = 2;
-static const char *const kAlignWsNames[kAlignWsCount] = {"bp", "lse"};
-struct AlignWs {
-    WsSection sec[kAlignWsCount];
-    int nsec;
-    int64_t total, gap;
-    void add(int64_t bytes) { sec[nsec] = WsSection{kAlignWsNames[nsec], total, bytes}; ++nsec; total = al(total + bytes) + gap; }
-};
-// < 0 with the message set; lse: with the lse section
-static int64_t align_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t max_label_len, bool lse = false, AlignWs *out = nullptr);
-// hypothesis scores (k_score.hip): up to kScoreWaveMaxStates states one wave per hypothesis and kScoreWaves of them per workgroup, beyond one
-// workgroup per hypothesis; states per lane / thread from the call's longest hypothesis
-template <typename E = float, bool LSE = false>
-static int launch_score(const ScoreParams &p, hipStream_t st, int64_t max_hyp_len) {
-    const int64_t ns = 2 * max_hyp_len + 1;
-    if (ns <= kScoreWaveMaxStates) {
-        const dim3 grid((unsigned)((p.H + kScoreWaves - 1) / kScoreWaves)), block(kScoreWaves * 64);
-        if (ns <= 64) return launch<crf_ctc_score_wave_kernel<1, E, LSE>>(g_score_kernel = "crf_ctc_score_wave_kernel<1>", grid, block, 0, st, p);
-        if (ns <= 128) return launch<crf_ctc_score_wave_kernel<2, E, LSE>>(g_score_kernel = "crf_ctc_score_wave_kernel<2>", grid, block, 0, st, p);
-        if (ns <= 256) return launch<crf_ctc_score_wave_kernel<4, E, LSE>>(g_score_kernel = "crf_ctc_score_wave_kernel<4>", grid, block, 0, st, p);
-        return launch<crf_ctc_score_wave_kernel<8, E, LSE>>(g_score_kernel = "crf_ctc_score_wave_kernel<8>", grid, block, 0, st, p);
-    }
-    const int64_t ni = (ns + kCtcThreads - 1) / kCtcThreads;
-    const dim3 grid((unsigned)p.H), block(kCtcThreads);
-    if (ni <= 2) return launch<crf_ctc_score_wg_kernel<2, E, LSE>>(g_score_kernel = "crf_ctc_score_wg_kernel<2>", grid, block, 0, st, p);
-    if (ni <= 4) return launch<crf_ctc_score_wg_kernel<4, E, LSE>>(g_score_kernel = "crf_ctc_score_wg_kernel<4>", grid, block, 0, st, p);
-    return launch<crf_ctc_score_wg_kernel<kCtcRegs, E, LSE>>(g_score_kernel = "crf_ctc_score_wg_kernel<8>", grid, block, 0, st, p);
-}
-// raw network output: the frames' lse values first (the alignment's row kernel), then the scores on the upcast values, on the same stream
-template <typename E>
-static int launch_score_logits(const ScoreParams &p, hipStream_t st, int64_t max_hyp_len) {
-    AlignParams a{};
-    a.x = p.x; a.lx = p.lx; a.B = p.B; a.T = p.T; a.V = p.V; a.xs_b = p.xs_b; a.xs_t = p.xs_t; a.lse = const_cast<float *>(p.lse);
-    const int64_t frames = (int64_t)p.B * p.T;
-    const int rc = p.V <= kAlnLseSmallV ? launch<crf_align_lse_kernel<16, E>>("crf_align_lse_kernel", dim3((unsigned)((frames + 15) / 16)), dim3(256), 0, st, a)
-                                        : launch<crf_align_lse_kernel<64, E>>("crf_align_lse_kernel", dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, st, a);
-    return rc ? rc : launch_score<E, true>(p, st, max_hyp_len);
-}
-// sampled / best-path label sequences (k_sample.hip): the row stage over the B T frames -- 16 lanes per row up to kSampleSmallV classes,
-// beyond a wave per row, per row V + 2 G words of dynamic LDS (none for the arg-max) -- then the collapse, one wave per path, on the same stream
-template <typename E>
-static int launch_sample(const SampleParams &p, hipStream_t st, bool greedy) {
-    const int64_t frames = (int64_t)p.B * p.T;
-    int rc;
-    if (p.V <= kSampleSmallV) {
-        constexpr int R = kSampleRowThreads(16) / 16;
-        const dim3 grid((unsigned)((frames + R - 1) / R)), block(kSampleRowThreads(16));
-        rc = greedy ? launch<crf_sample_row_kernel<16, E, true>>(g_sample_kernel = "crf_sample_row_kernel<16, greedy>", grid, block, 0, st, p)
-                    : launch<crf_sample_row_kernel<16, E, false>>(g_sample_kernel = "crf_sample_row_kernel<16>", grid, block,
-                                                                  (size_t)R * (p.V + 2 * 16) * sizeof(float), st, p);
-    } else {
-        const dim3 grid((unsigned)frames), block(kSampleRowThreads(64));
-        rc = greedy ? launch<crf_sample_row_kernel<64, E, true>>(g_sample_kernel = "crf_sample_row_kernel<64, greedy>", grid, block, 0, st, p)
-                    : launch<crf_sample_row_kernel<64, E, false>>(g_sample_kernel = "crf_sample_row_kernel<64>", grid, block,
-                                                                  (size_t)(p.V + 2 * 64) * sizeof(float), st, p);
-    }
-    if (rc) return rc;
-    const int64_t H = (int64_t)p.B * p.K;
-    return launch<crf_sample_collapse_kernel>("crf_sample_collapse_kernel", dim3((unsigned)((H + kSampleWaves - 1) / kSampleWaves)),
-                                              dim3(kSampleWaves * 64), 0, st, p);
-}
-static int64_t align_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t max_label_len, bool lse, AlignWs *out) {
-    if (B <= 0 || T <= 0 || V <= 0 || max_label_len < 0) { set_error("crf_ctc_align: bad B/T/V/max_label_len"); return -CRF_ERR_ARG; }
-    if (V > kMaxVocab) { set_error("V > " + std::to_string(kMaxVocab) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
-    if (max_label_len > kMaxCtcLabelLen) { set_error("label length > " + std::to_string(kMaxCtcLabelLen) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
-    if (B * T > INT32_MAX) { set_error("crf_ctc_align: B * T > INT32_MAX"); return -CRF_ERR_ARG; }
-    const int64_t Sc = rup64((int)(2 * max_label_len + 1)), NB = (T + kAlnFrames - 1) / kAlnFrames;
-    AlignWs w{};
-    w.gap = ws_gap_bytes();
-    w.add(B * NB * Sc * (int64_t)sizeof(unsigned));
-    if (lse) w.add(B * T * (int64_t)sizeof(float));
-    if (out) *out = w;
-    return w.total;
 }
 
 static ResParams res_params(const LossParams &lp, int dir, int b0) {
@@ -750,16 +626,6 @@ static int launch_fac_pair2(const LossParams &lp, size_t lds, hipStream_t st, in
 #undef CRF_DEN_NAME
 
 
-// the section records as the debug exports hand them out: (offset, bytes) pairs, and the names joined by commas
-static int copy_sections(const WsSection *sec, int n, int64_t *out, int n_out) {
-    for (int k = 0; k < n && out && 2 * k + 1 < n_out; ++k) { out[2 * k] = sec[k].off; out[2 * k + 1] = sec[k].bytes; }
-    return n;
-}
-static std::string join_names(const char *const *names, int n) {
-    std::string s;
-    for (int k = 0; k < n; ++k) { if (k) s += ','; s += names[k]; }
-    return s;
-}
 }  // namespace crf
 
 using namespace crf;
@@ -783,15 +649,6 @@ int crf_debug_ws_sections(const crf_graph *g, int64_t B, int64_t T, int64_t V, i
 }
 const char *crf_debug_ws_section_names(void) {
     static const std::string s = join_names(kWsNames, kWsCount);
-    return s.c_str();
-}
-int crf_debug_align_ws_sections(int logits, int64_t B, int64_t T, int64_t V, int64_t max_label_len, int64_t *out, int n_out) {
-    AlignWs w;
-    if (align_ws_bytes(B, T, V, max_label_len, logits != 0, &w) < 0) return -1;
-    return copy_sections(w.sec, w.nsec, out, n_out);
-}
-const char *crf_debug_align_ws_section_names(void) {
-    static const std::string s = join_names(kAlignWsNames, kAlignWsCount);
     return s.c_str();
 }
 
@@ -904,154 +761,6 @@ int crf_ctc_fwd_bwd_logits(const void *act, int dtype, int time_major, int blank
     if (c_ctc == 0.f) { set_error("crf_ctc_fwd_bwd_logits: c_ctc is zero"); return CRF_ERR_ARG; }
     return loss_impl(nullptr, (const float *)act, 1, dtype, labels, lab_off, lx, ly, B, T, V, max_label_len, 0.f, c_ctc, grad, loss, nullptr,
                      nullptr, costs_ctc, invalid, ws, ws_bytes, stream_, time_major, blank);
-}
-
-int64_t crf_ctc_align_workspace_bytes(int64_t B, int64_t T, int64_t V, int64_t max_label_len) {
-    const int64_t n = align_ws_bytes(B, T, V, max_label_len);
-    return n < 0 ? -1 : n;
-}
-
-// the checks and the argument block both entry points share; dtype < 0: log-probs (crf_ctc_align), else raw output of that dtype with
-// the lse values [B][T] behind the back-pointer words.  Every error is answered here, before any HIP call.
-static int align_args(const char *who, const void *act, int dtype, int time_major, int blank, const int32_t *labels, const int32_t *lab_off,
-                      const int32_t *lx, const int32_t *ly, int64_t B, int64_t T, int64_t V, int64_t max_label_len, int32_t *pos,
-                      float *score, int32_t *invalid, void *ws, int64_t ws_bytes, AlignParams &p) {
-    if (!act || !labels || !lab_off || !lx || !ly || !pos || !score || !ws) { set_error(std::string(who) + ": null argument"); return CRF_ERR_ARG; }
-    if (dtype > 2) { set_error(std::string(who) + ": dtype must be 0 (f32), 1 (bf16) or 2 (f16)"); return CRF_ERR_ARG; }
-    AlignWs w;
-    const int64_t need = align_ws_bytes(B, T, V, max_label_len, dtype >= 0, &w);
-    if (need < 0) return (int)-need;
-    if (blank < 0 || blank >= V) { set_error("blank " + std::to_string(blank) + " outside [0, V=" + std::to_string(V) + ")"); return CRF_ERR_ARG; }
-    if (ws_bytes < need) { set_error("workspace too small: need " + std::to_string(need)); return CRF_ERR_WORKSPACE; }
-    p = AlignParams{};
-    p.x = act; p.labels = labels; p.lab_off = lab_off; p.lx = lx; p.ly = ly;
-    p.B = (int)B; p.T = (int)T; p.V = (int)V; p.blank = blank;
-    p.Sc = rup64((int)(2 * max_label_len + 1)); p.NB = (int)((T + kAlnFrames - 1) / kAlnFrames);
-    p.xs_b = time_major ? V : T * V; p.xs_t = time_major ? B * V : V;
-    p.bp = (unsigned *)((char *)ws + w.sec[0].off); p.pos = pos; p.score = score; p.invalid = invalid;
-    p.lse = dtype >= 0 ? (float *)((char *)ws + w.sec[1].off) : nullptr;
-    return CRF_OK;
-}
-
-int crf_ctc_align(const float *act, int time_major, int blank, const int32_t *labels, const int32_t *lab_off, const int32_t *lx,
-                  const int32_t *ly, int64_t B, int64_t T, int64_t V, int64_t max_label_len, int32_t *pos, float *score,
-                  int32_t *invalid, void *ws, int64_t ws_bytes, void *stream_) {
-    AlignParams p;
-    const int rc = align_args("crf_ctc_align", act, -1, time_major, blank, labels, lab_off, lx, ly, B, T, V, max_label_len, pos, score, invalid,
-                              ws, ws_bytes, p);
-    if (rc) return rc;
-    return launch_align(p, (hipStream_t)stream_, max_label_len);
-}
-
-int64_t crf_ctc_align_logits_workspace_bytes(int64_t B, int64_t T, int64_t V, int64_t max_label_len) {
-    const int64_t n = align_ws_bytes(B, T, V, max_label_len, true);
-    return n < 0 ? -1 : n;
-}
-
-int crf_ctc_align_logits(const void *act, int dtype, int time_major, int blank, const int32_t *labels, const int32_t *lab_off,
-                         const int32_t *lx, const int32_t *ly, int64_t B, int64_t T, int64_t V, int64_t max_label_len, int32_t *pos,
-                         float *score, int32_t *invalid, void *ws, int64_t ws_bytes, void *stream_) {
-    if (dtype < 0) { set_error("crf_ctc_align_logits: dtype must be 0 (f32), 1 (bf16) or 2 (f16)"); return CRF_ERR_ARG; }
-    AlignParams p;
-    const int rc = align_args("crf_ctc_align_logits", act, dtype, time_major, blank, labels, lab_off, lx, ly, B, T, V, max_label_len, pos,
-                              score, invalid, ws, ws_bytes, p);
-    if (rc) return rc;
-    if (dtype == 0) return launch_align_logits<float>(p, (hipStream_t)stream_, max_label_len);
-    if (dtype == 1) return launch_align_logits<AlnBf16>(p, (hipStream_t)stream_, max_label_len);
-    return launch_align_logits<AlnF16>(p, (hipStream_t)stream_, max_label_len);
-}
-
-// the checks and the argument block both score entry points share; dtype < 0: log-probs (crf_ctc_score, no workspace), else raw output of
-// that dtype with the lse values [B][T] in the workspace.  Every error is answered here, before any HIP call.
-static int64_t score_ws_bytes(int64_t B, int64_t T, int64_t V) {
-    if (B <= 0 || T <= 0 || V <= 0 || V > INT32_MAX) { set_error("crf_ctc_score: bad B/T/V"); return -CRF_ERR_ARG; }
-    if (B * T > INT32_MAX) { set_error("crf_ctc_score: B * T > INT32_MAX"); return -CRF_ERR_ARG; }
-    return al(B * T * (int64_t)sizeof(float)) + ws_gap_bytes();
-}
-static int score_args(const char *who, const void *act, int dtype, int time_major, int blank, const int32_t *labels, const int32_t *hyp_off,
-                      const int32_t *hyp_len, const int32_t *hyp_utt, const int32_t *lx, int64_t B, int64_t H, int64_t T, int64_t V,
-                      int64_t max_hyp_len, float *score, int32_t *invalid, void *ws, int64_t ws_bytes, ScoreParams &p) {
-    if (!act || !labels || !hyp_off || !hyp_len || !hyp_utt || !lx || !score || (dtype >= 0 && !ws)) { set_error(std::string(who) + ": null argument"); return CRF_ERR_ARG; }
-    if (dtype > 2) { set_error(std::string(who) + ": dtype must be 0 (f32), 1 (bf16) or 2 (f16)"); return CRF_ERR_ARG; }
-    if (H <= 0 || H > INT32_MAX || max_hyp_len < 0) { set_error(std::string(who) + ": bad H/max_hyp_len"); return CRF_ERR_ARG; }
-    const int64_t need = score_ws_bytes(B, T, V);
-    if (need < 0) return (int)-need;
-    if (max_hyp_len > kMaxCtcLabelLen) { set_error("hypothesis length > " + std::to_string(kMaxCtcLabelLen) + " not supported by this build"); return CRF_ERR_UNSUPPORTED; }
-    if (blank < 0 || blank >= V) { set_error("blank " + std::to_string(blank) + " outside [0, V=" + std::to_string(V) + ")"); return CRF_ERR_ARG; }
-    if (dtype >= 0 && ws_bytes < need) { set_error("workspace too small: need " + std::to_string(need)); return CRF_ERR_WORKSPACE; }
-    p = ScoreParams{};
-    p.x = act; p.labels = labels; p.hyp_off = hyp_off; p.hyp_len = hyp_len; p.hyp_utt = hyp_utt; p.lx = lx;
-    p.B = (int)B; p.H = (int)H; p.T = (int)T; p.V = (int)V; p.blank = blank;
-    p.xs_b = time_major ? V : T * V; p.xs_t = time_major ? B * V : V;
-    p.score = score; p.invalid = invalid;
-    p.lse = dtype >= 0 ? (const float *)ws : nullptr;
-    return CRF_OK;
-}
-
-int crf_ctc_score(const float *act, int time_major, int blank, const int32_t *labels, const int32_t *hyp_off, const int32_t *hyp_len,
-                  const int32_t *hyp_utt, const int32_t *lx, int64_t B, int64_t H, int64_t T, int64_t V, int64_t max_hyp_len,
-                  float *score, int32_t *invalid, void *stream_) {
-    ScoreParams p;
-    const int rc = score_args("crf_ctc_score", act, -1, time_major, blank, labels, hyp_off, hyp_len, hyp_utt, lx, B, H, T, V, max_hyp_len,
-                              score, invalid, nullptr, 0, p);
-    if (rc) return rc;
-    return launch_score(p, (hipStream_t)stream_, max_hyp_len);
-}
-
-int64_t crf_ctc_score_logits_workspace_bytes(int64_t B, int64_t T, int64_t V) {
-    const int64_t n = score_ws_bytes(B, T, V);
-    return n < 0 ? -1 : n;
-}
-
-int crf_ctc_score_logits(const void *act, int dtype, int time_major, int blank, const int32_t *labels, const int32_t *hyp_off,
-                         const int32_t *hyp_len, const int32_t *hyp_utt, const int32_t *lx, int64_t B, int64_t H, int64_t T, int64_t V,
-                         int64_t max_hyp_len, float *score, int32_t *invalid, void *ws, int64_t ws_bytes, void *stream_) {
-    if (dtype < 0) { set_error("crf_ctc_score_logits: dtype must be 0 (f32), 1 (bf16) or 2 (f16)"); return CRF_ERR_ARG; }
-    ScoreParams p;
-    const int rc = score_args("crf_ctc_score_logits", act, dtype, time_major, blank, labels, hyp_off, hyp_len, hyp_utt, lx, B, H, T, V,
-                              max_hyp_len, score, invalid, ws, ws_bytes, p);
-    if (rc) return rc;
-    if (dtype == 0) return launch_score_logits<float>(p, (hipStream_t)stream_, max_hyp_len);
-    if (dtype == 1) return launch_score_logits<AlnBf16>(p, (hipStream_t)stream_, max_hyp_len);
-    return launch_score_logits<AlnF16>(p, (hipStream_t)stream_, max_hyp_len);
-}
-
-// crf_ctc_sample's workspace: the classes drawn per frame, [B K][T] int32 (one section, laid down as the others are: 256-aligned, the
-// ws_gap bytes behind it)
-static int64_t sample_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t K) {
-    if (B <= 0 || T <= 0 || V <= 0 || K <= 0) { set_error("crf_ctc_sample: bad B/T/V/K"); return -CRF_ERR_ARG; }
-    if (B > INT32_MAX || T > INT32_MAX || K > INT32_MAX || B * T > INT32_MAX) { set_error("crf_ctc_sample: B * T > INT32_MAX"); return -CRF_ERR_ARG; }
-    if (B * K > INT32_MAX) { set_error("crf_ctc_sample: B * K > INT32_MAX"); return -CRF_ERR_ARG; }
-    if (V > kSampleMaxV) { set_error("V > " + std::to_string(kSampleMaxV) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
-    if (K > (INT64_MAX / 8) / (B * T)) { set_error("crf_ctc_sample: B * K * T too large"); return -CRF_ERR_ARG; }
-    return al(B * K * T * (int64_t)sizeof(int32_t)) + ws_gap_bytes();
-}
-
-int64_t crf_ctc_sample_workspace_bytes(int64_t B, int64_t T, int64_t V, int64_t K) {
-    const int64_t n = sample_ws_bytes(B, T, V, K);
-    return n < 0 ? -1 : n;
-}
-
-// Every error is answered here, before any HIP call.
-int crf_ctc_sample(const void *act, int dtype, int time_major, int blank, const int32_t *lx, int64_t B, int64_t T, int64_t V, int64_t K,
-                   uint64_t seed, uint32_t offset, int greedy, int32_t *hyps, int32_t *hyp_len, int32_t *paths, void *ws, int64_t ws_bytes,
-                   void *stream_) {
-    if (!act || !lx || !hyps || !hyp_len || !ws) { set_error("crf_ctc_sample: null argument"); return CRF_ERR_ARG; }
-    if (dtype < 0 || dtype > 2) { set_error("crf_ctc_sample: dtype must be 0 (f32), 1 (bf16) or 2 (f16)"); return CRF_ERR_ARG; }
-    const int64_t need = sample_ws_bytes(B, T, V, K);
-    if (need < 0) return (int)-need;
-    if (blank < 0 || blank >= V) { set_error("blank " + std::to_string(blank) + " outside [0, V=" + std::to_string(V) + ")"); return CRF_ERR_ARG; }
-    if (greedy && K != 1) { set_error("crf_ctc_sample: greedy takes K = 1, got " + std::to_string(K)); return CRF_ERR_ARG; }
-    if (ws_bytes < need) { set_error("workspace too small: need " + std::to_string(need)); return CRF_ERR_WORKSPACE; }
-    SampleParams p{};
-    p.x = act; p.lx = lx;
-    p.B = (int)B; p.T = (int)T; p.V = (int)V; p.K = (int)K; p.blank = blank;
-    p.seed_lo = (unsigned)(seed & 0xffffffffu); p.seed_hi = (unsigned)(seed >> 32); p.offset = offset;
-    p.xs_b = time_major ? V : T * V; p.xs_t = time_major ? B * V : V;
-    p.cls = (int *)ws; p.hyps = hyps; p.hyp_len = hyp_len; p.paths = paths;
-    if (dtype == 0) return launch_sample<float>(p, (hipStream_t)stream_, greedy != 0);
-    if (dtype == 1) return launch_sample<AlnBf16>(p, (hipStream_t)stream_, greedy != 0);
-    return launch_sample<AlnF16>(p, (hipStream_t)stream_, greedy != 0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1873,8 +1582,6 @@ const char *crf_build_switches(void) {
 }
 
 const char *crf_last_den_kernel(void) { return g_den_kernel; }
-const char *crf_last_score_kernel(void) { return g_score_kernel; }
-const char *crf_last_sample_kernel(void) { return g_sample_kernel; }
 int crf_last_call_streams(void) { return g_call_streams; }
 const char *crf_last_side_stream(void) { return g_side_desc; }
 

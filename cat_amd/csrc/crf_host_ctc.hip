@@ -1,0 +1,268 @@
+// cat_amd/csrc/crf_host_ctc.hip -- the host side of the three surfaces on the plain CTC lattice, which share nothing with the loss call
+// (crf_host.hip) but crf_host_util.h: forced alignment (crf_ctc_align*, k_align.hip), hypothesis scores (crf_ctc_score*, k_score.hip) and
+// sampled / best-path label sequences (crf_ctc_sample, k_sample.hip) -- argument checks, workspace sections, kernel choice, the C-ABI
+// entry points of include/ctc_crf_hip.h.  Every error is answered before any HIP call.  The activations are read in place in either
+// layout and -- the *_logits entry points and crf_ctc_sample -- in f32, bf16 or f16.
+#include <type_traits>
+
+#include "crf_device.h"
+#include "crf_kernels_decl.h"
+#include "crf_host_util.h"
+
+namespace crf {
+
+static thread_local const char *g_sample_kernel = ""; // template instantiation of the row kernel of this thread's last crf_ctc_sample (crf_last_sample_kernel)
+static thread_local const char *g_score_kernel = "";  // ... of the kernel of this thread's last crf_ctc_score / crf_ctc_score_logits (crf_last_score_kernel)
+
+// ---- what the three surfaces share ----
+// f(E{}) with the element type of dtype 0 (f32), 1 (bf16), 2 (f16)
+template <typename F>
+static int with_dtype(int dtype, F &&f) {
+    return dtype == 0 ? f(float{}) : dtype == 1 ? f(AlnBf16{}) : f(AlnF16{});
+}
+// f(NR, k): states per thread (per = kCtcThreads) or lane (per = 64) as a compile-time constant, the smallest of 1, 2, 4, 8 that holds
+// `states` of them, and its index k in that list
+template <typename F>
+static int with_nr(int64_t states, int per, F &&f) {
+    const int64_t ni = (states + per - 1) / per;
+    if (ni <= 1) return f(std::integral_constant<int, 1>{}, 0);
+    if (ni <= 2) return f(std::integral_constant<int, 2>{}, 1);
+    if (ni <= 4) return f(std::integral_constant<int, 4>{}, 2);
+    return f(std::integral_constant<int, kCtcRegs>{}, 3);
+}
+// the activations of a params block: row (b, t) at b * xs_b + t * xs_t elements, read in place in either layout
+template <typename P>
+static void set_act(P &p, const void *act, const int32_t *lx, int64_t B, int64_t T, int64_t V, int blank, int time_major) {
+    p.x = act; p.lx = lx;
+    p.B = (int)B; p.T = (int)T; p.V = (int)V; p.blank = blank;
+    p.xs_b = time_major ? V : T * V; p.xs_t = time_major ? B * V : V;
+}
+// the argument checks with one text: CRF_OK, or the error with the message set
+static int bad_dtype(const char *who) { set_error(std::string(who) + ": dtype must be 0 (f32), 1 (bf16) or 2 (f16)"); return CRF_ERR_ARG; }
+static int check_blank(int blank, int64_t V) {
+    if (blank < 0 || blank >= V) { set_error("blank " + std::to_string(blank) + " outside [0, V=" + std::to_string(V) + ")"); return CRF_ERR_ARG; }
+    return CRF_OK;
+}
+static int check_ws(int64_t ws_bytes, int64_t need) {
+    if (ws_bytes < need) { set_error("workspace too small: need " + std::to_string(need)); return CRF_ERR_WORKSPACE; }
+    return CRF_OK;
+}
+// their workspaces: one or two sections, laid down as the loss call's are (crf_host_util.h)
+struct SideWs {
+    WsSection sec[2];
+    int nsec = 0;
+    int64_t total = 0, gap = ws_gap_bytes();
+    SideWs &add(const char *name, int64_t bytes) { sec[nsec++] = WsSection{name, total, bytes}; total = al(total + bytes) + gap; return *this; }
+};
+// raw network output: the frames' lse values [B][T] (crf_align_lse_kernel, G lanes per frame) in front of the alignment / the scores,
+// on the same stream
+template <typename E>
+static int launch_row_lse(const void *x, const int *lx, int B, int T, int V, int64_t xs_b, int64_t xs_t, float *lse, hipStream_t st) {
+    AlignParams a{};
+    a.x = x; a.lx = lx; a.B = B; a.T = T; a.V = V; a.xs_b = xs_b; a.xs_t = xs_t; a.lse = lse;
+    const int64_t frames = (int64_t)B * T;
+    return V <= kAlnLseSmallV ? launch<crf_align_lse_kernel<16, E>>("crf_align_lse_kernel", dim3((unsigned)((frames + 15) / 16)), dim3(256), 0, st, a)
+                              : launch<crf_align_lse_kernel<64, E>>("crf_align_lse_kernel", dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, st, a);
+}
+
+// ---- forced alignment (k_align.hip) ----
+// one workgroup per utterance, states per thread from the longest label sequence as for the chains; LSE: raw network output, the lse
+// values first, then the alignment on the upcast values
+template <typename E, bool LSE>
+static int launch_align(const AlignParams &p, hipStream_t st, int64_t max_label_len) {
+    if constexpr (LSE)
+        if (const int rc = launch_row_lse<E>(p.x, p.lx, p.B, p.T, p.V, p.xs_b, p.xs_t, p.lse, st)) return rc;
+    return with_nr(2 * max_label_len + 1, kCtcThreads, [&](auto nr, int) {
+        return launch<crf_ctc_align_kernel<decltype(nr)::value, E, LSE>>("crf_ctc_align_kernel", dim3((unsigned)p.B), dim3(kCtcThreads), 0, st, p);
+    });
+}
+// its workspace: the back-pointer words [B][ceil(T / kAlnFrames)][2 * max_label_len + 1 rounded up to 64], then -- raw network output
+// (crf_ctc_align_logits) -- the frames' lse values [B][T]
+static const char *const kAlignWsNames[2] = {"bp", "lse"};
+// < 0 with the message set; lse: with the lse section
+static int64_t align_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t max_label_len, bool lse = false, SideWs *out = nullptr) {
+    if (B <= 0 || T <= 0 || V <= 0 || max_label_len < 0) { set_error("crf_ctc_align: bad B/T/V/max_label_len"); return -CRF_ERR_ARG; }
+    if (V > kMaxVocab) { set_error("V > " + std::to_string(kMaxVocab) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
+    if (max_label_len > kMaxCtcLabelLen) { set_error("label length > " + std::to_string(kMaxCtcLabelLen) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
+    if (B * T > INT32_MAX) { set_error("crf_ctc_align: B * T > INT32_MAX"); return -CRF_ERR_ARG; }
+    const int64_t Sc = rup64((int)(2 * max_label_len + 1)), NB = (T + kAlnFrames - 1) / kAlnFrames;
+    SideWs w;
+    w.add(kAlignWsNames[0], B * NB * Sc * (int64_t)sizeof(unsigned));
+    if (lse) w.add(kAlignWsNames[1], B * T * (int64_t)sizeof(float));
+    if (out) *out = w;
+    return w.total;
+}
+// both entry points: the checks, the argument block, the launch; dtype < 0: log-probs (crf_ctc_align), else raw output of that dtype with
+// the lse values [B][T] behind the back-pointer words
+static int align_call(const char *who, const void *act, int dtype, int time_major, int blank, const int32_t *labels, const int32_t *lab_off,
+                      const int32_t *lx, const int32_t *ly, int64_t B, int64_t T, int64_t V, int64_t max_label_len, int32_t *pos,
+                      float *score, int32_t *invalid, void *ws, int64_t ws_bytes, hipStream_t st) {
+    if (!act || !labels || !lab_off || !lx || !ly || !pos || !score || !ws) { set_error(std::string(who) + ": null argument"); return CRF_ERR_ARG; }
+    if (dtype > 2) return bad_dtype(who);
+    SideWs w;
+    const int64_t need = align_ws_bytes(B, T, V, max_label_len, dtype >= 0, &w);
+    if (need < 0) return (int)-need;
+    if (const int rc = check_blank(blank, V)) return rc;
+    if (const int rc = check_ws(ws_bytes, need)) return rc;
+    AlignParams p{};
+    set_act(p, act, lx, B, T, V, blank, time_major);
+    p.labels = labels; p.lab_off = lab_off; p.ly = ly;
+    p.Sc = rup64((int)(2 * max_label_len + 1)); p.NB = (int)((T + kAlnFrames - 1) / kAlnFrames);
+    p.bp = (unsigned *)((char *)ws + w.sec[0].off); p.pos = pos; p.score = score; p.invalid = invalid;
+    if (dtype < 0) return launch_align<float, false>(p, st, max_label_len);
+    p.lse = (float *)((char *)ws + w.sec[1].off);
+    return with_dtype(dtype, [&](auto e) { return launch_align<decltype(e), true>(p, st, max_label_len); });
+}
+
+// ---- hypothesis scores (k_score.hip) ----
+// up to kScoreWaveMaxStates states one wave per hypothesis and kScoreWaves of them per workgroup, beyond one workgroup per hypothesis (from
+// two states per thread on); states per lane / thread from the call's longest hypothesis; LSE as for the alignment
+template <typename E, bool LSE>
+static int launch_score(const ScoreParams &p, hipStream_t st, int64_t max_hyp_len) {
+    static const char *const wave_names[] = {"crf_ctc_score_wave_kernel<1>", "crf_ctc_score_wave_kernel<2>", "crf_ctc_score_wave_kernel<4>", "crf_ctc_score_wave_kernel<8>"};
+    static const char *const wg_names[] = {"crf_ctc_score_wg_kernel<2>", "crf_ctc_score_wg_kernel<2>", "crf_ctc_score_wg_kernel<4>", "crf_ctc_score_wg_kernel<8>"};
+    if constexpr (LSE)
+        if (const int rc = launch_row_lse<E>(p.x, p.lx, p.B, p.T, p.V, p.xs_b, p.xs_t, const_cast<float *>(p.lse), st)) return rc;
+    const int64_t ns = 2 * max_hyp_len + 1;
+    if (ns <= kScoreWaveMaxStates)
+        return with_nr(ns, 64, [&](auto nr, int k) {
+            return launch<crf_ctc_score_wave_kernel<decltype(nr)::value, E, LSE>>(g_score_kernel = wave_names[k], dim3((unsigned)((p.H + kScoreWaves - 1) / kScoreWaves)),
+                                                                    dim3(kScoreWaves * 64), 0, st, p);
+        });
+    return with_nr(ns, kCtcThreads, [&](auto nr, int k) {
+        constexpr int NR = decltype(nr)::value < 2 ? 2 : decltype(nr)::value;
+        return launch<crf_ctc_score_wg_kernel<NR, E, LSE>>(g_score_kernel = wg_names[k], dim3((unsigned)p.H), dim3(kCtcThreads), 0, st, p);
+    });
+}
+// crf_ctc_score_logits' workspace: the lse values [B][T]
+static int64_t score_ws_bytes(int64_t B, int64_t T, int64_t V) {
+    if (B <= 0 || T <= 0 || V <= 0 || V > INT32_MAX) { set_error("crf_ctc_score: bad B/T/V"); return -CRF_ERR_ARG; }
+    if (B * T > INT32_MAX) { set_error("crf_ctc_score: B * T > INT32_MAX"); return -CRF_ERR_ARG; }
+    return SideWs().add("lse", B * T * (int64_t)sizeof(float)).total;
+}
+// both entry points: the checks, the argument block, the launch; dtype < 0: log-probs (crf_ctc_score, no workspace), else raw output of
+// that dtype with the lse values in the workspace
+static int score_call(const char *who, const void *act, int dtype, int time_major, int blank, const int32_t *labels, const int32_t *hyp_off,
+                      const int32_t *hyp_len, const int32_t *hyp_utt, const int32_t *lx, int64_t B, int64_t H, int64_t T, int64_t V,
+                      int64_t max_hyp_len, float *score, int32_t *invalid, void *ws, int64_t ws_bytes, hipStream_t st) {
+    if (!act || !labels || !hyp_off || !hyp_len || !hyp_utt || !lx || !score || (dtype >= 0 && !ws)) { set_error(std::string(who) + ": null argument"); return CRF_ERR_ARG; }
+    if (dtype > 2) return bad_dtype(who);
+    if (H <= 0 || H > INT32_MAX || max_hyp_len < 0) { set_error(std::string(who) + ": bad H/max_hyp_len"); return CRF_ERR_ARG; }
+    const int64_t need = score_ws_bytes(B, T, V);
+    if (need < 0) return (int)-need;
+    if (max_hyp_len > kMaxCtcLabelLen) { set_error("hypothesis length > " + std::to_string(kMaxCtcLabelLen) + " not supported by this build"); return CRF_ERR_UNSUPPORTED; }
+    if (const int rc = check_blank(blank, V)) return rc;
+    if (dtype >= 0)
+        if (const int rc = check_ws(ws_bytes, need)) return rc;
+    ScoreParams p{};
+    set_act(p, act, lx, B, T, V, blank, time_major);
+    p.labels = labels; p.hyp_off = hyp_off; p.hyp_len = hyp_len; p.hyp_utt = hyp_utt; p.H = (int)H;
+    p.score = score; p.invalid = invalid;
+    if (dtype < 0) return launch_score<float, false>(p, st, max_hyp_len);
+    p.lse = (const float *)ws;
+    return with_dtype(dtype, [&](auto e) { return launch_score<decltype(e), true>(p, st, max_hyp_len); });
+}
+
+// ---- sampled / best-path label sequences (k_sample.hip) ----
+// the row stage over the B T frames -- 16 lanes per row up to kSampleSmallV classes, beyond a wave per row, per row V + 2 G words of
+// dynamic LDS (none for the arg-max) -- then the collapse, one wave per path, on the same stream
+template <typename E>
+static int launch_sample(const SampleParams &p, hipStream_t st, bool greedy) {
+    const int64_t frames = (int64_t)p.B * p.T, H = (int64_t)p.B * p.K;
+    auto rows = [&](auto g, const char *name, const char *name_greedy) {
+        constexpr int G = decltype(g)::value, R = kSampleRowThreads(G) / G;   // rows per workgroup
+        const dim3 grid((unsigned)((frames + R - 1) / R)), block(kSampleRowThreads(G));
+        return greedy ? launch<crf_sample_row_kernel<G, E, true>>(g_sample_kernel = name_greedy, grid, block, 0, st, p)
+                      : launch<crf_sample_row_kernel<G, E, false>>(g_sample_kernel = name, grid, block, (size_t)R * (p.V + 2 * G) * sizeof(float), st, p);
+    };
+    const int rc = p.V <= kSampleSmallV ? rows(std::integral_constant<int, 16>{}, "crf_sample_row_kernel<16>", "crf_sample_row_kernel<16, greedy>")
+                                        : rows(std::integral_constant<int, 64>{}, "crf_sample_row_kernel<64>", "crf_sample_row_kernel<64, greedy>");
+    return rc ? rc : launch<crf_sample_collapse_kernel>("crf_sample_collapse_kernel", dim3((unsigned)((H + kSampleWaves - 1) / kSampleWaves)),
+                                                        dim3(kSampleWaves * 64), 0, st, p);
+}
+// its workspace: the classes drawn per frame, [B K][T] int32
+static int64_t sample_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t K) {
+    if (B <= 0 || T <= 0 || V <= 0 || K <= 0) { set_error("crf_ctc_sample: bad B/T/V/K"); return -CRF_ERR_ARG; }
+    if (B > INT32_MAX || T > INT32_MAX || K > INT32_MAX || B * T > INT32_MAX) { set_error("crf_ctc_sample: B * T > INT32_MAX"); return -CRF_ERR_ARG; }
+    if (B * K > INT32_MAX) { set_error("crf_ctc_sample: B * K > INT32_MAX"); return -CRF_ERR_ARG; }
+    if (V > kSampleMaxV) { set_error("V > " + std::to_string(kSampleMaxV) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
+    if (K > (INT64_MAX / 8) / (B * T)) { set_error("crf_ctc_sample: B * K * T too large"); return -CRF_ERR_ARG; }
+    return SideWs().add("cls", B * K * T * (int64_t)sizeof(int32_t)).total;
+}
+
+}  // namespace crf
+
+using namespace crf;
+
+static int64_t or_minus1(int64_t n) { return n < 0 ? -1 : n; }   // the *_workspace_bytes exports: -1 with the message set
+
+extern "C" {
+
+int64_t crf_ctc_align_workspace_bytes(int64_t B, int64_t T, int64_t V, int64_t max_label_len) { return or_minus1(align_ws_bytes(B, T, V, max_label_len)); }
+int64_t crf_ctc_align_logits_workspace_bytes(int64_t B, int64_t T, int64_t V, int64_t max_label_len) { return or_minus1(align_ws_bytes(B, T, V, max_label_len, true)); }
+int crf_debug_align_ws_sections(int logits, int64_t B, int64_t T, int64_t V, int64_t max_label_len, int64_t *out, int n_out) {
+    SideWs w;
+    if (align_ws_bytes(B, T, V, max_label_len, logits != 0, &w) < 0) return -1;
+    return copy_sections(w.sec, w.nsec, out, n_out);
+}
+const char *crf_debug_align_ws_section_names(void) {
+    static const std::string s = join_names(kAlignWsNames, 2);
+    return s.c_str();
+}
+
+int crf_ctc_align(const float *act, int time_major, int blank, const int32_t *labels, const int32_t *lab_off, const int32_t *lx,
+                  const int32_t *ly, int64_t B, int64_t T, int64_t V, int64_t max_label_len, int32_t *pos, float *score,
+                  int32_t *invalid, void *ws, int64_t ws_bytes, void *stream_) {
+    return align_call("crf_ctc_align", act, -1, time_major, blank, labels, lab_off, lx, ly, B, T, V, max_label_len, pos, score, invalid, ws, ws_bytes,
+                      (hipStream_t)stream_);
+}
+
+int crf_ctc_align_logits(const void *act, int dtype, int time_major, int blank, const int32_t *labels, const int32_t *lab_off,
+                         const int32_t *lx, const int32_t *ly, int64_t B, int64_t T, int64_t V, int64_t max_label_len, int32_t *pos,
+                         float *score, int32_t *invalid, void *ws, int64_t ws_bytes, void *stream_) {
+    if (dtype < 0) return bad_dtype("crf_ctc_align_logits");
+    return align_call("crf_ctc_align_logits", act, dtype, time_major, blank, labels, lab_off, lx, ly, B, T, V, max_label_len, pos, score, invalid, ws,
+                      ws_bytes, (hipStream_t)stream_);
+}
+
+int crf_ctc_score(const float *act, int time_major, int blank, const int32_t *labels, const int32_t *hyp_off, const int32_t *hyp_len,
+                  const int32_t *hyp_utt, const int32_t *lx, int64_t B, int64_t H, int64_t T, int64_t V, int64_t max_hyp_len,
+                  float *score, int32_t *invalid, void *stream_) {
+    return score_call("crf_ctc_score", act, -1, time_major, blank, labels, hyp_off, hyp_len, hyp_utt, lx, B, H, T, V, max_hyp_len, score, invalid, nullptr,
+                      0, (hipStream_t)stream_);
+}
+
+int64_t crf_ctc_score_logits_workspace_bytes(int64_t B, int64_t T, int64_t V) { return or_minus1(score_ws_bytes(B, T, V)); }
+
+int crf_ctc_score_logits(const void *act, int dtype, int time_major, int blank, const int32_t *labels, const int32_t *hyp_off,
+                         const int32_t *hyp_len, const int32_t *hyp_utt, const int32_t *lx, int64_t B, int64_t H, int64_t T, int64_t V,
+                         int64_t max_hyp_len, float *score, int32_t *invalid, void *ws, int64_t ws_bytes, void *stream_) {
+    if (dtype < 0) return bad_dtype("crf_ctc_score_logits");
+    return score_call("crf_ctc_score_logits", act, dtype, time_major, blank, labels, hyp_off, hyp_len, hyp_utt, lx, B, H, T, V, max_hyp_len, score,
+                      invalid, ws, ws_bytes, (hipStream_t)stream_);
+}
+
+int64_t crf_ctc_sample_workspace_bytes(int64_t B, int64_t T, int64_t V, int64_t K) { return or_minus1(sample_ws_bytes(B, T, V, K)); }
+
+int crf_ctc_sample(const void *act, int dtype, int time_major, int blank, const int32_t *lx, int64_t B, int64_t T, int64_t V, int64_t K,
+                   uint64_t seed, uint32_t offset, int greedy, int32_t *hyps, int32_t *hyp_len, int32_t *paths, void *ws, int64_t ws_bytes,
+                   void *stream_) {
+    if (!act || !lx || !hyps || !hyp_len || !ws) { set_error("crf_ctc_sample: null argument"); return CRF_ERR_ARG; }
+    if (dtype < 0 || dtype > 2) return bad_dtype("crf_ctc_sample");
+    const int64_t need = sample_ws_bytes(B, T, V, K);
+    if (need < 0) return (int)-need;
+    if (const int rc = check_blank(blank, V)) return rc;
+    if (greedy && K != 1) { set_error("crf_ctc_sample: greedy takes K = 1, got " + std::to_string(K)); return CRF_ERR_ARG; }
+    if (const int rc = check_ws(ws_bytes, need)) return rc;
+    SampleParams p{};
+    set_act(p, act, lx, B, T, V, blank, time_major);
+    p.K = (int)K;
+    p.seed_lo = (unsigned)(seed & 0xffffffffu); p.seed_hi = (unsigned)(seed >> 32); p.offset = offset;
+    p.cls = (int *)ws; p.hyps = hyps; p.hyp_len = hyp_len; p.paths = paths;
+    return with_dtype(dtype, [&](auto e) { return launch_sample<decltype(e)>(p, (hipStream_t)stream_, greedy != 0); });
+}
+
+const char *crf_last_score_kernel(void) { return g_score_kernel; }
+const char *crf_last_sample_kernel(void) { return g_sample_kernel; }
+
+}  // extern "C"

@@ -1,0 +1,58 @@
+// cat_amd/csrc/crf_host_util.h -- what the host units share (crf_host.hip: the loss call; crf_host_ctc.hip: forced alignment, hypothesis
+// scores, sampling): the records and the rule of a workspace section, and the one kernel launch with its dynamic-LDS mark.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <string>
+
+#include "../../include/ctc_crf_hip.h"
+#include "crf_internal.h"
+
+namespace crf {
+
+// A workspace is a list of sections: every one starts at the running end of the layout, which then moves past its bytes to the next
+// multiple of 256 (+ the ws_gap bytes).
+struct WsSection { const char *name; int64_t off, bytes; };
+static int64_t al(int64_t x) { return (x + 255) & ~(int64_t)255; }
+// bytes no kernel may touch behind every section: the switch ws_gap x 256 (tests/guard.py); unset, the sections are packed
+static int64_t ws_gap_bytes() { return 256 * (int64_t)std::max(0, opt(kOpt_ws_gap, 0)); }
+// the section records as the debug exports hand them out: (offset, bytes) pairs, and the names joined by commas
+static int copy_sections(const WsSection *sec, int n, int64_t *out, int n_out) {
+    for (int k = 0; k < n && out && 2 * k + 1 < n_out; ++k) { out[2 * k] = sec[k].off; out[2 * k + 1] = sec[k].bytes; }
+    return n;
+}
+static std::string join_names(const char *const *names, int n) {
+    std::string s;
+    for (int k = 0; k < n; ++k) { if (k) s += ','; s += names[k]; }
+    return s;
+}
+
+constexpr int kMaxDev = 64;
+// Dynamic LDS above 64 KiB must be opted into per kernel AND per device (hipFuncSetAttribute acts on the current
+// device's copy of the function): high-water mark per device.
+struct LdsMark { std::atomic<size_t> v[kMaxDev]; };
+static int ensure_lds(const void *fn, size_t bytes, LdsMark &m, const char *what) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) { set_error("hipGetDevice failed"); return CRF_ERR_HIP; }
+    if (bytes <= m.v[dev].load()) return CRF_OK;
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) { set_error(std::string("hipFuncSetAttribute(") + what + "): " + hipGetErrorString(e)); return CRF_ERR_HIP; }
+    m.v[dev] = bytes;
+    return CRF_OK;
+}
+// Every kernel launch of the host units.  K is a template argument, so each instantiation has its own mark; a launch with dynamic LDS raises
+// it first; a launch error comes back as CRF_ERR_HIP with the kernel's name (the text is built on failure only).
+template <auto K, typename... A>
+static int launch(const char *name, dim3 grid, dim3 block, size_t lds, hipStream_t st, const A &...args) {
+    static LdsMark mark;
+    int rc;
+    if (lds > 0 && (rc = ensure_lds((const void *)K, lds, mark, name))) return rc;
+    hipLaunchKernelGGL(K, grid, block, lds, st, args...);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error(std::string(name) + ": " + hipGetErrorString(e)); return CRF_ERR_HIP; }
+    return CRF_OK;
+}
+
+}  // namespace crf

@@ -1,4 +1,4 @@
-// cat_amd/csrc/crf_kernels_decl.h -- what the host side (crf_host.hip) needs to know of the kernel families: their argument blocks, the constants
+// cat_amd/csrc/crf_kernels_decl.h -- what the host side (crf_host.hip, crf_host_ctc.hip) needs to know of the kernel families: their argument blocks, the constants
 // that size grids and LDS, and the DECLARATIONS of the kernel templates.  The definitions live in k_*.hip, one translation unit per family,
 // each of which instantiates explicitly what the host launches.
 #pragma once

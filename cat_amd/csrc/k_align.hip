@@ -1,5 +1,5 @@
 // cat_amd/csrc/k_align.hip -- CTC forced alignment: the best path through the numerator's 2L+1 states (the max-plus twin of the forward
-// chain in k_chain.hip), with back-pointers and the back-trace in the same launch.  Host side: crf_ctc_align (crf_host.hip).
+// chain in k_chain.hip), with back-pointers and the back-trace in the same launch.  Host side: crf_ctc_align (crf_host_ctc.hip).
 //
 //   v_t[s] = x[b][t][lab(s)] + max(v_{t-1}[s], v_{t-1}[s-1], v_{t-1}[s-2] if s is odd and lab(s) != lab(s-2))      log domain, fp32
 //
@@ -20,18 +20,11 @@
 // Raw network output (crf_ctc_align_logits): the kernel is instantiated on the element type E -- float, or 2-byte bf16 / fp16 elements
 // upcast in registers -- and runs the SAME recursion on the upcast values: every alignment takes one entry of each of its lx frames, so
 // log_softmax's normaliser sum_t lse_t is common to all of them and the best path is the same.  crf_align_lse_kernel writes lse[b][t]
-// in front of it; with LSE the workgroup sums its utterance's lse values in fp64 in a fixed order at the end (no atomics: the order is
-// part of the contract) and the score is float(double(raw best sum) - that sum).
-#include "crf_device.h"
-#include "crf_kernels_decl.h"
+// in front of it; with LSE the workgroup sums its utterance's lse values in fp64 in a fixed order at the end (k_lattice_common.h: the
+// order is part of the contract) and the score is float(double(raw best sum) - that sum).
+#include "k_lattice_common.h"
 
 namespace crf {
-
-// one element, upcast: a row of 16-bit elements starts on a 2-byte boundary only (odd V), so these are 2-byte loads
-template <typename E> __device__ __forceinline__ float aln_ld(const char *a);
-template <> __device__ __forceinline__ float aln_ld<float>(const char *a) { return *(const float *)a; }
-template <> __device__ __forceinline__ float aln_ld<AlnBf16>(const char *a) { return __uint_as_float((unsigned)*(const unsigned short *)a << 16); }
-template <> __device__ __forceinline__ float aln_ld<AlnF16>(const char *a) { return (float)*(const _Float16 *)a; }
 
 // lse[b][t] = m + log sum_v exp(x[b][t][v] - m), m = max_v x[b][t][v], fp32, for the frames t < lx[b] (the others are never written, and
 // never read).  G lanes per frame: a lane adds its entries v = sub, sub + G, ... in that order, the lanes' sums meet in a butterfly -- the
@@ -51,7 +44,7 @@ __global__ __launch_bounds__(256) void crf_align_lse_kernel(AlignParams p) {
 #pragma unroll
         for (int k = 0; k < NX; ++k) {
             const int v = sub + k * G;
-            x[k] = v < p.V ? aln_ld<E>((const char *)(row + v)) : -INFINITY;
+            x[k] = v < p.V ? lat_ld<E>((const char *)(row + v)) : -INFINITY;
             m = fmaxf(m, x[k]);
         }
 #pragma unroll
@@ -61,11 +54,11 @@ __global__ __launch_bounds__(256) void crf_align_lse_kernel(AlignParams p) {
         for (int k = 0; k < NX; ++k)
             if (sub + k * G < p.V) s += expf(x[k] - m);
     } else {
-        for (int v = sub; v < p.V; v += G) m = fmaxf(m, aln_ld<E>((const char *)(row + v)));
+        for (int v = sub; v < p.V; v += G) m = fmaxf(m, lat_ld<E>((const char *)(row + v)));
 #pragma unroll
         for (int o = G / 2; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, G));
         if (m == -INFINITY) m = 0.f;
-        for (int v = sub; v < p.V; v += G) s += expf(aln_ld<E>((const char *)(row + v)) - m);
+        for (int v = sub; v < p.V; v += G) s += expf(lat_ld<E>((const char *)(row + v)) - m);
     }
 #pragma unroll
     for (int o = G / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, G);
@@ -92,26 +85,7 @@ __global__ __launch_bounds__(kCtcThreads) void crf_ctc_align_kernel(AlignParams 
     const int Sx = fits ? 2 * L + 1 : 1;
     int *prow = p.pos + (int64_t)b * p.T;
 
-    // the label sequence with blanks; repeats and labels outside [0, V) counted in one reduction
-    {
-        const int *ul = p.labels + p.lab_off[b];
-        int cnt = 0;                          // repeats | out-of-range labels << 12  (each <= 2047)
-        for (int s = tid; s < S; s += kCtcThreads) lab[s] = (s < Sx && (s & 1)) ? ul[s >> 1] : p.blank;
-        for (int i = tid; i < (fits ? L : 0); i += kCtcThreads) {
-            const int l = ul[i];
-            if ((unsigned)l >= (unsigned)p.V) cnt += 1 << 12;
-            else if (i > 0 && l == ul[i - 1]) cnt += 1;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
-        if (lane == 0) red[wave] = cnt;
-        if (tid < 2) { A[0][tid] = -INFINITY; A[1][tid] = -INFINITY; }
-    }
-    __syncthreads();
-    int cnt = 0;
-#pragma unroll
-    for (int i = 0; i < kCtcWaves; ++i) cnt += red[i];
-    const bool valid = fits && lx > 0 && (cnt >> 12) == 0 && L + (cnt & 0xfff) <= lx;   // (gpu_ctc.h:161-174: L + repeats <= T_b)
+    const bool valid = lat_valid(fits, lx, L, lat_wg_labels(p.labels + p.lab_off[b], L, fits, p.blank, p.V, lab, red, A, tid, lane, wave));
     for (int t = tid; t < p.T; t += kCtcThreads)
         if (!valid || t >= lx) prow[t] = -2;
     if (!valid) {
@@ -124,28 +98,14 @@ __global__ __launch_bounds__(kCtcThreads) void crf_ctc_align_kernel(AlignParams 
     unsigned bpw[NR];
 #pragma unroll
     for (int i = 0; i < NR; ++i) {
-        const int s = tid + i * kCtcThreads;
-        const int l = lab[s];
-        // a label outside [0, V) has ended the utterance above; the states past Sx hold the blank
-        labo[i] = (unsigned)l * (unsigned)sizeof(E);
-        skip[i] = s < Sx && (s & 1) && s >= 2 && l != lab[s - 2];
+        lat_wg_state<E>(lab, Sx, tid + i * kCtcThreads, labo[i], skip[i], A);
         bpw[i] = 0u;
-        A[0][2 + s] = s == 0 ? 0.f : -INFINITY;
     }
     __syncthreads();
 
     const E *xb = (const E *)p.x + (int64_t)b * p.xs_b;
     unsigned *bpb = p.bp + (int64_t)b * p.NB * p.Sc;
-    // Emissions: unconditional loads (the frame is clamped to lx - 1, the column is always a valid one), so that nothing but the
-    // loop itself branches around them and the compiler can count what is in flight instead of waiting for everything.
-    auto fetch = [&](float (&e)[PF][NR], int t) __attribute__((always_inline)) {
-#pragma unroll
-        for (int f = 0; f < PF; ++f) {
-            const char *row = (const char *)(xb + (int64_t)min(t + f, lx - 1) * p.xs_t);
-#pragma unroll
-            for (int i = 0; i < NR; ++i) e[f][i] = aln_ld<E>(row + labo[i]);
-        }
-    };
+    auto fetch = [&](float (&e)[PF][NR], int t) __attribute__((always_inline)) { lat_fetch<PF, NR, E>(e, xb, p.xs_t, lx, labo, t); };
     // One frame; a frame at or past lx copies the vector (the loop runs in whole batches).
     auto frame = [&](const float (&e)[NR], int t) __attribute__((always_inline)) {
         const float *Ac = &A[t & 1][2];
@@ -211,22 +171,10 @@ __global__ __launch_bounds__(kCtcThreads) void crf_ctc_align_kernel(AlignParams 
         return;
     }
     if constexpr (LSE) {
-        // score = raw best sum - sum_{t < lx} lse_t in fp64, in a fixed order: a thread's frames t = tid, tid + 512, ..., the wave's
-        // butterfly, the eight wave sums in order.  Frames at or past lx are never read.
+        // score = raw best sum - sum_{t < lx} lse_t in fp64, in the fixed order of k_lattice_common.h
         __shared__ double lred[kCtcWaves];
-        const float *lr = p.lse + (int64_t)b * p.T;
-        double part = 0.0;
-        for (int t = tid; t < lx; t += kCtcThreads) part += (double)lr[t];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
-        if (lane == 0) lred[wave] = part;
-        __syncthreads();
-        if (tid == 0) {
-            double sum = 0.0;
-#pragma unroll
-            for (int i = 0; i < kCtcWaves; ++i) sum += lred[i];
-            p.score[b] = (float)((double)raw - sum);
-        }
+        const double sum = lat_lse_sum_wg(p.lse + (int64_t)b * p.T, lx, lred, tid, lane, wave);
+        if (tid == 0) p.score[b] = (float)((double)raw - sum);
     }
 
     constexpr int kTileStates = 2 * kAlnFrames * kAlnG;   // 128 states below the current one

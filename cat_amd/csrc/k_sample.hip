@@ -1,5 +1,5 @@
 // cat_amd/csrc/k_sample.hip -- label sequences drawn on the GPU: per frame K classes from softmax(x) (or the arg-max), then the CTC map B
-// (repeats merged, blanks dropped) on each of the B K frame paths.  Host side: crf_ctc_sample (crf_host.hip).
+// (repeats merged, blanks dropped) on each of the B K frame paths.  Host side: crf_ctc_sample (crf_host_ctc.hip).
 //
 // Row stage (crf_sample_row_kernel<G, E, GREEDY>): G lanes per row (n, t), G = 16 for V <= kSampleSmallV (16 rows per workgroup of 256
 // threads), else a wave per row (one wave per workgroup); rows t >= lx[n] idle.  The row is read ONCE, whatever K is:
@@ -28,15 +28,9 @@
 // DPP shift with the carry of the step before in lane 0, the keep flags are balloted, a kept class lands at base + (kept lanes below),
 // base advances by the popcount; then the tail [len, T) takes the blank.  paths[h][t] (optional) = the class, -1 for t >= lx[n].  No LDS,
 // no atomics; every entry of hyps, hyp_len and paths is written by exactly one plain vector store.
-#include "crf_device.h"
-#include "crf_kernels_decl.h"
+#include "k_lattice_common.h"
 
 namespace crf {
-
-template <typename E> __device__ __forceinline__ float sample_ld(const char *a);
-template <> __device__ __forceinline__ float sample_ld<float>(const char *a) { return *(const float *)a; }
-template <> __device__ __forceinline__ float sample_ld<AlnBf16>(const char *a) { return __uint_as_float((unsigned)*(const unsigned short *)a << 16); }
-template <> __device__ __forceinline__ float sample_ld<AlnF16>(const char *a) { return (float)*(const _Float16 *)a; }
 
 // Philox4x32-10 (Salmon et al., SC'11; Random123's constants)
 __device__ __forceinline__ void sample_philox(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&r)[4]) {
@@ -67,7 +61,7 @@ __global__ __launch_bounds__(kSampleRowThreads(G)) void crf_sample_row_kernel(Sa
         if (live) {
 #pragma unroll 8
             for (int v = sub; v < V; v += G) {
-                const float x = sample_ld<E>((const char *)(row + v));
+                const float x = lat_ld<E>((const char *)(row + v));
                 if (x > bv) { bv = x; bi = v; }                              // (ascending v: the lowest index of the lane's maximum)
             }
         }
@@ -87,7 +81,7 @@ __global__ __launch_bounds__(kSampleRowThreads(G)) void crf_sample_row_kernel(Sa
         if (live) {
 #pragma unroll 8
             for (int v = sub; v < V; v += G) {
-                const float x = sample_ld<E>((const char *)(row + v));
+                const float x = lat_ld<E>((const char *)(row + v));
                 cdf[v] = x;
                 m = fmaxf(m, x);
             }

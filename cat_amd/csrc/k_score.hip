@@ -1,5 +1,5 @@
 // cat_amd/csrc/k_score.hip -- forward-only CTC log-likelihoods of H hypotheses over B utterances: the sum-product twin of k_align.hip, with
-// no backward chain, no gradient and no back-pointers.  Host side: crf_ctc_score / crf_ctc_score_logits (crf_host.hip).
+// no backward chain, no gradient and no back-pointers.  Host side: crf_ctc_score / crf_ctc_score_logits (crf_host_ctc.hip).
 //
 //   v_t[s] = x[u][t][lab(s)] + log(exp(v_{t-1}[s]) + exp(v_{t-1}[s-1]) + [s odd and lab(s) != lab(s-2)] exp(v_{t-1}[s-2]))     u = hyp_utt[h]
 //   score[h] = logaddexp(v[2L], v[2L-1])  after the lx[u] frames of the utterance
@@ -21,17 +21,11 @@
 //
 // Raw network output (crf_ctc_score_logits): the SAME recursion on the upcast values -- every alignment takes one entry of each of
 // the lx frames, so log_softmax's normaliser sum_t lse_t is common to all of them -- and score = float(double(raw) - sum_t double(lse[u][t])),
-// the lse values written by crf_align_lse_kernel in front, their sum taken in fp64 in a fixed order (a lane's / thread's frames in
-// order, the wave's butterfly, the wave sums in order; no atomics).
-#include "crf_device.h"
-#include "crf_kernels_decl.h"
+// the lse values written by crf_align_lse_kernel in front, their sum taken in fp64 in the fixed order of k_lattice_common.h.
+// A hypothesis is valid by the alignment's rule (lat_valid, k_lattice_common.h).
+#include "k_lattice_common.h"
 
 namespace crf {
-
-template <typename E> __device__ __forceinline__ float score_ld(const char *a);
-template <> __device__ __forceinline__ float score_ld<float>(const char *a) { return *(const float *)a; }
-template <> __device__ __forceinline__ float score_ld<AlnBf16>(const char *a) { return __uint_as_float((unsigned)*(const unsigned short *)a << 16); }
-template <> __device__ __forceinline__ float score_ld<AlnF16>(const char *a) { return (float)*(const _Float16 *)a; }
 
 // exp and log on the hardware's base-2 instructions without the library's denormal handling: the sums below lie in [1, 3] (or are 0:
 // log -> -inf), and a term below 2^-126 of the largest adds nothing either way.  exp(-inf) = 0.
@@ -86,21 +80,13 @@ __global__ __launch_bounds__(kScoreWaves * 64) void crf_ctc_score_wave_kernel(Sc
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
-    const bool valid = fits && lx > 0 && (cnt >> 12) == 0 && L + (cnt & 0xfff) <= lx;   // the alignment's rule (k_align.hip)
-    if (!valid) {
+    if (!lat_valid(fits, lx, L, cnt)) {
         if (lane == 0) { p.score[h] = -INFINITY; if (p.invalid) p.invalid[h] = 1; }
         return;
     }
 
     const E *xb = (const E *)p.x + (int64_t)u * p.xs_b;
-    auto fetch = [&](float (&e)[PF][NR], int t) __attribute__((always_inline)) {
-#pragma unroll
-        for (int f = 0; f < PF; ++f) {
-            const char *row = (const char *)(xb + (int64_t)min(t + f, lx - 1) * p.xs_t);
-#pragma unroll
-            for (int i = 0; i < NR; ++i) e[f][i] = score_ld<E>(row + labo[i]);
-        }
-    };
+    auto fetch = [&](float (&e)[PF][NR], int t) __attribute__((always_inline)) { lat_fetch<PF, NR, E>(e, xb, p.xs_t, lx, labo, t); };
     float v[NR];
 #pragma unroll
     for (int i = 0; i < NR; ++i) v[i] = (lane == 0 && i == 0) ? 0.f : -INFINITY;
@@ -148,13 +134,8 @@ __global__ __launch_bounds__(kScoreWaves * 64) void crf_ctc_score_wave_kernel(Sc
     const float raw = score_lse2(last, prev);
     float out = raw;
     if constexpr (LSE) {
-        // a lane's frames t = lane, lane + 64, ... in order, then the butterfly; frames at or past lx are never read
-        const float *lr = p.lse + (int64_t)u * p.T;
-        double part = 0.0;
-        for (int t = lane; t < lx; t += 64) part += (double)lr[t];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
-        out = raw > -INFINITY ? (float)((double)raw - part) : -INFINITY;
+        const double sum = lat_lse_sum_wave(p.lse + (int64_t)u * p.T, lx, lane);
+        out = raw > -INFINITY ? (float)((double)raw - sum) : -INFINITY;
     }
     if (lane == 0) { p.score[h] = out; if (p.invalid) p.invalid[h] = 0; }
 }
@@ -175,27 +156,7 @@ __global__ __launch_bounds__(kCtcThreads) void crf_ctc_score_wg_kernel(ScorePara
     const int lx = fits ? min(p.lx[u], p.T) : 0;
     const int Sx = fits ? 2 * L + 1 : 1;
 
-    // the label sequence with blanks; repeats and labels outside [0, V) counted in one reduction
-    {
-        const int *ul = p.labels + p.hyp_off[h];
-        int cnt = 0;                          // repeats | out-of-range labels << 12  (each <= 2047)
-        for (int s = tid; s < S; s += kCtcThreads) lab[s] = (s < Sx && (s & 1)) ? ul[s >> 1] : p.blank;
-        for (int i = tid; i < (fits ? L : 0); i += kCtcThreads) {
-            const int l = ul[i];
-            if ((unsigned)l >= (unsigned)p.V) cnt += 1 << 12;
-            else if (i > 0 && l == ul[i - 1]) cnt += 1;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
-        if (lane == 0) red[wave] = cnt;
-        if (tid < 2) { A[0][tid] = -INFINITY; A[1][tid] = -INFINITY; }
-    }
-    __syncthreads();
-    int cnt = 0;
-#pragma unroll
-    for (int i = 0; i < kCtcWaves; ++i) cnt += red[i];
-    const bool valid = fits && lx > 0 && (cnt >> 12) == 0 && L + (cnt & 0xfff) <= lx;
-    if (!valid) {                             // (the whole workgroup: nothing below is reached)
+    if (!lat_valid(fits, lx, L, lat_wg_labels(p.labels + p.hyp_off[h], L, fits, p.blank, p.V, lab, red, A, tid, lane, wave))) {   // (the whole workgroup: nothing below is reached)
         if (tid == 0) { p.score[h] = -INFINITY; if (p.invalid) p.invalid[h] = 1; }
         return;
     }
@@ -203,24 +164,11 @@ __global__ __launch_bounds__(kCtcThreads) void crf_ctc_score_wg_kernel(ScorePara
     unsigned labo[NR];
     bool skip[NR];
 #pragma unroll
-    for (int i = 0; i < NR; ++i) {
-        const int s = tid + i * kCtcThreads;
-        const int l = lab[s];                 // a label outside [0, V) has ended the hypothesis above; the states past Sx hold the blank
-        labo[i] = (unsigned)l * (unsigned)sizeof(E);
-        skip[i] = s < Sx && (s & 1) && s >= 2 && l != lab[s - 2];
-        A[0][2 + s] = s == 0 ? 0.f : -INFINITY;
-    }
+    for (int i = 0; i < NR; ++i) lat_wg_state<E>(lab, Sx, tid + i * kCtcThreads, labo[i], skip[i], A);
     __syncthreads();
 
     const E *xb = (const E *)p.x + (int64_t)u * p.xs_b;
-    auto fetch = [&](float (&e)[PF][NR], int t) __attribute__((always_inline)) {
-#pragma unroll
-        for (int f = 0; f < PF; ++f) {
-            const char *row = (const char *)(xb + (int64_t)min(t + f, lx - 1) * p.xs_t);
-#pragma unroll
-            for (int i = 0; i < NR; ++i) e[f][i] = score_ld<E>(row + labo[i]);
-        }
-    };
+    auto fetch = [&](float (&e)[PF][NR], int t) __attribute__((always_inline)) { lat_fetch<PF, NR, E>(e, xb, p.xs_t, lx, labo, t); };
     auto frame = [&](const float (&e)[NR], int t) __attribute__((always_inline)) {
         const float *Ac = &A[t & 1][2];
         float *An = &A[(t + 1) & 1][2];
@@ -253,19 +201,9 @@ __global__ __launch_bounds__(kCtcThreads) void crf_ctc_score_wg_kernel(ScorePara
     const float *Af = &A[t0 & 1][2];          // t0 frames have run (the last frame's barrier has passed)
     const float raw = score_lse2(Af[Sx - 1], Sx > 1 ? Af[Sx - 2] : -INFINITY);
     if constexpr (LSE) {
-        // a thread's frames t = tid, tid + 512, ... in order, the wave's butterfly, the eight wave sums in order
         __shared__ double lred[kCtcWaves];
-        const float *lr = p.lse + (int64_t)u * p.T;
-        double part = 0.0;
-        for (int t = tid; t < lx; t += kCtcThreads) part += (double)lr[t];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
-        if (lane == 0) lred[wave] = part;
-        __syncthreads();
+        const double sum = lat_lse_sum_wg(p.lse + (int64_t)u * p.T, lx, lred, tid, lane, wave);
         if (tid == 0) {
-            double sum = 0.0;
-#pragma unroll
-            for (int i = 0; i < kCtcWaves; ++i) sum += lred[i];
             p.score[h] = raw > -INFINITY ? (float)((double)raw - sum) : -INFINITY;
             if (p.invalid) p.invalid[h] = 0;
         }

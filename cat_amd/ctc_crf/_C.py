@@ -481,6 +481,32 @@ def _validate_meta(lx_cpu, ly_cpu, lab_cpu, T: int, V: int, blank: int = 0) -> N
                                + (" and the blank itself" if bool((lab_cpu[:n] == blank).any()) else ""))
 
 
+def _act_shape(t: torch.Tensor, fused: bool, time_major: bool, blank: int):
+    """The activations' dtype check (fused: raw network output in f32 / bf16 / f16, else f32 log-probs), their shape with the
+    time_major swap and the blank's range.  -> (device, N, T, V)."""
+    if fused:
+        if t.dtype not in _FUSED_DTYPES:
+            raise RuntimeError(f"fused log_softmax: expect float32, bfloat16 or float16 network output, got {t.dtype}")
+    else:
+        assert t.dtype == torch.float32
+    N, T, V = t.shape
+    if time_major:
+        T, N = N, T
+    if not 0 <= blank < V:
+        raise RuntimeError(f"blank must lie in [0, V-1={V - 1}], got {blank}")
+    return t.device, N, T, V
+
+
+def _new_ws(nbytes: int, dev: torch.device) -> torch.Tensor:
+    """A call's workspace; nbytes < 0: the size function has refused the shape and left its message."""
+    if nbytes < 0:
+        _check(1)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if _POISON_WS:
+        ws.fill_(0xFF)   # every float / double / int32 of the workspace reads as NaN / -1
+    return ws
+
+
 def loss_fwd_bwd(logits: torch.Tensor, labels: Optional[torch.Tensor], lx: torch.Tensor,
                  ly: Optional[torch.Tensor], c_den: float, c_ctc: float, graph: Optional[int],
                  want_costs: bool = False, fused: bool = False, time_major: bool = False, blank: int = 0,
@@ -497,17 +523,7 @@ def loss_fwd_bwd(logits: torch.Tensor, labels: Optional[torch.Tensor], lx: torch
     if (time_major or blank != 0) and c_den != 0.0:
         raise RuntimeError("time_major and a blank other than 0 are for numerator-only calls (WARP_CTC_LOSS / gpu_ctc): "
                            "the den_lm fixes the blank at 0 and the CTC-CRF kernels read [N,T,V] log-probs")
-    if fused:   # raw network output, log_softmax fused in (crf_loss_fwd_bwd_logits)
-        if logits.dtype not in _FUSED_DTYPES:
-            raise RuntimeError(f"fused log_softmax: expect float32, bfloat16 or float16 network output, got {logits.dtype}")
-    else:
-        assert logits.dtype == torch.float32
-    dev = logits.device
-    N, T, V = logits.shape
-    if time_major:
-        T, N = N, T
-    if not 0 <= blank < V:
-        raise RuntimeError(f"blank must lie in [0, V-1={V - 1}], got {blank}")
+    dev, N, T, V = _act_shape(logits, fused, time_major, blank)   # fused: raw network output (crf_loss_fwd_bwd_logits)
     lx32 = lx.to(torch.int32)
     if c_ctc != 0.0:
         ly32 = ly.to(torch.int32)
@@ -532,9 +548,7 @@ def loss_fwd_bwd(logits: torch.Tensor, labels: Optional[torch.Tensor], lx: torch
         meta = lx_d
     gh = _vp(graph) if (graph and c_den != 0.0) else _vp(0)
     ws_bytes = _lib.crf_workspace_bytes(gh, N, T, V, max_l)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    if _POISON_WS:
-        ws.fill_(0xFF)   # every float / double / int32 of the workspace reads as NaN / -1
+    ws = _new_ws(ws_bytes, dev)
     if grad_out is not None:
         assert grad_out.shape == logits.shape and grad_out.dtype == torch.float32 and grad_out.is_contiguous() and grad_out.device == dev
         grad = grad_out
@@ -582,17 +596,7 @@ def ctc_align(log_probs: torch.Tensor, labels: torch.Tensor, lx: torch.Tensor, l
     fused: log_probs is the RAW network output in f32 / bf16 / f16 (``crf_ctc_align_logits``): the path is the best one on the upcast
     values, the scores are those of log_softmax (the frames' normalisers subtracted in fp64)."""
     assert log_probs.is_cuda and log_probs.is_contiguous() and log_probs.dim() == 3
-    if fused:
-        if log_probs.dtype not in _FUSED_DTYPES:
-            raise RuntimeError(f"fused log_softmax: expect float32, bfloat16 or float16 network output, got {log_probs.dtype}")
-    else:
-        assert log_probs.dtype == torch.float32
-    dev = log_probs.device
-    N, T, V = log_probs.shape
-    if time_major:
-        T, N = N, T
-    if not 0 <= blank < V:
-        raise RuntimeError(f"blank must lie in [0, V-1={V - 1}], got {blank}")
+    dev, N, T, V = _act_shape(log_probs, fused, time_major, blank)
     if labels.is_cuda or lx.is_cuda or ly.is_cuda:
         raise RuntimeError("ctc_align: labels, input_lengths and label_lengths are CPU tensors")
     lx32 = lx.to(torch.int32).reshape(-1)
@@ -613,11 +617,7 @@ def ctc_align(log_probs: torch.Tensor, labels: torch.Tensor, lx: torch.Tensor, l
     nt = N * (max_l + 2)
     lx_d, ly_d, off_d, table_d, lab_d = meta[:N], meta[N:2 * N], meta[2 * N:3 * N], meta[3 * N:3 * N + nt], meta[3 * N + nt:]
     ws_bytes = (_lib.crf_ctc_align_logits_workspace_bytes if fused else _lib.crf_ctc_align_workspace_bytes)(N, T, V, max_l)
-    if ws_bytes < 0:
-        _check(1)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    if _POISON_WS:
-        ws.fill_(0xFF)
+    ws = _new_ws(ws_bytes, dev)
     pos = torch.empty((N, T), dtype=torch.int32, device=dev) if pos_out is None else pos_out
     scores = torch.empty(N, dtype=torch.float32, device=dev) if scores_out is None else scores_out
     assert pos.shape == (N, T) and pos.dtype == torch.int32 and pos.is_contiguous() and pos.device == dev
@@ -690,17 +690,7 @@ def ctc_score(log_probs: torch.Tensor, hyps: torch.Tensor, hyp_lengths: torch.Te
     int32), both on the device, no host synchronisation, no autograd; all integer metadata travels in one staged copy.
     fused: log_probs is the RAW network output in f32 / bf16 / f16 (``crf_ctc_score_logits``)."""
     assert log_probs.is_cuda and log_probs.is_contiguous() and log_probs.dim() == 3
-    if fused:
-        if log_probs.dtype not in _FUSED_DTYPES:
-            raise RuntimeError(f"fused log_softmax: expect float32, bfloat16 or float16 network output, got {log_probs.dtype}")
-    else:
-        assert log_probs.dtype == torch.float32
-    dev = log_probs.device
-    N, T, V = log_probs.shape
-    if time_major:
-        T, N = N, T
-    if not 0 <= blank < V:
-        raise RuntimeError(f"blank must lie in [0, V-1={V - 1}], got {blank}")
+    dev, N, T, V = _act_shape(log_probs, fused, time_major, blank)
     meta_cpu, H, max_l = _stage_score_meta(hyps, hyp_lengths, lx, hyp_utt, N, T, V, blank)
     meta = _h2d_async(meta_cpu, dev)
     lx_d, len_d, off_d, utt_d, lab_d = meta[:N], meta[N:N + H], meta[N + H:N + 2 * H], meta[N + 2 * H:N + 3 * H], meta[N + 3 * H:]
@@ -711,11 +701,7 @@ def ctc_score(log_probs: torch.Tensor, hyps: torch.Tensor, hyp_lengths: torch.Te
     with torch.cuda.device(dev):
         if fused:
             ws_bytes = _lib.crf_ctc_score_logits_workspace_bytes(N, T, V)
-            if ws_bytes < 0:
-                _check(1)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            if _POISON_WS:
-                ws.fill_(0xFF)
+            ws = _new_ws(ws_bytes, dev)
             rc = _lib.crf_ctc_score_logits(_ptr(log_probs), _FUSED_DTYPES[log_probs.dtype], 1 if time_major else 0, blank, _ptr(lab_d),
                                            _ptr(off_d), _ptr(len_d), _ptr(utt_d), _ptr(lx_d), N, H, T, V, max_l, _ptr(scores),
                                            _ptr(invalid), _ptr(ws), ws_bytes, _vp(stream))
@@ -752,11 +738,7 @@ def ctc_sample(log_probs: torch.Tensor, lx: torch.Tensor, n_samples: int, seed: 
     lx_d = _h2d_async(lx.to(torch.int32).reshape(-1), dev)
     H = N * K
     ws_bytes = _lib.crf_ctc_sample_workspace_bytes(N, T, V, K)
-    if ws_bytes < 0:
-        _check(1)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    if _POISON_WS:
-        ws.fill_(0xFF)
+    ws = _new_ws(ws_bytes, dev)
     hyps = torch.empty((H, T), dtype=torch.int32, device=dev) if hyps_out is None else hyps_out
     paths = paths_out if paths_out is not None else torch.empty((H, T), dtype=torch.int32, device=dev) if return_paths else None
     for o in (hyps, paths):
