@@ -1,5 +1,5 @@
-// cat_amd/csrc/crf_device.h -- what every kernel family of the CTC-CRF loss shares: the kernel argument block (LossParams), the build-time
-// A/B switches, wave / block reductions, the exact power-of-two rescale helpers, LDS-only barriers, the in-kernel timing stamps.
+// cat_amd/csrc/crf_device.h -- what every kernel family of the CTC-CRF loss shares: the kernel argument block (LossParams),
+// wave / block reductions, the exact power-of-two rescale helpers, LDS-only barriers, the in-kernel timing stamps.
 // Included by every translation unit under cat_amd/csrc/k_*.hip and by crf_host.hip / crf_host_ctc.hip (the host side and the C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -13,6 +13,7 @@ namespace crf {
 constexpr int kEpRegs = 8;    // ep row prefetch registers per thread  -> V  <= 8 * 1024
 constexpr int kCtcThreads = 512, kCtcWaves = kCtcThreads / 64;  // numerator chains: 8 waves (S' = 2L+1 is a few hundred)
 constexpr int kCtcRegs = 8;   // ctc states per thread                  -> 2L+1 <= 8 * 512
+constexpr int kCtcPairWavesPerSimd = 5;   // the one-state-per-thread numerator chains are compiled for 5 waves per SIMD: at most 96 registers (tests/test_isa_checks.py)
 static_assert(kEpRegs * kChainThreads == kMaxVocab && 2 * kMaxCtcLabelLen + 1 <= kCtcRegs * kCtcThreads &&
               2 * (kMaxCtcLabelLen + 1) + 1 > kCtcRegs * kCtcThreads, "the host's limits (crf_internal.h) follow the kernels' registers");
 constexpr int kCtcPF = 4;     // frames per emission prefetch batch (ctc_forward)
@@ -28,59 +29,6 @@ constexpr int kGradFrames = 4;  // frames per crf_grad_kernel workgroup
 constexpr int kGradDescale = 4;
 constexpr int kFlagFallback = 40;   // words [40], [41] behind the error word: utterances of the last call redone by the denominator / numerator fallback (crf_finalize_kernel)
 
-// ---- build-time A/B switches of the frame loops (the defaults are the measured best: DESIGN.md section 2, profiles/round4_ab_*) ----
-#ifndef CRF_X_GDEARLY
-#define CRF_X_GDEARLY 1     // crf_grad_den_kernel: the rows of frame t+2 are requested right behind the staging of frame t+1 (0: at the top of frame t+1;
-                            // 1: in the one-chunk, one-emission-register instantiation; 2: in every one-chunk instantiation not held to 128 VGPRs; 3: two-chunk ones too)
-#endif
-#ifndef CRF_X_GDMOVE
-#define CRF_X_GDMOVE 1      // ... with the cur <- next register moves spelled out in front of the requests (0: left to the compiler, which waited for the rows
-                            // of t+2 right behind their requests)
-#endif
-#ifndef CRF_X_GDW2
-#define CRF_X_GDW2 1        // crf_grad_den_kernel, rows of 5121 .. 8192 floats: 1 = four row registers per thread at 128 VGPRs (two workgroups per CU)
-#endif
-#ifndef CRF_X_PRIO
-#define CRF_X_PRIO 2        // fac_chain_body: issue priority by progress through the frame's chunks: 0 off, 1 steps at 1/4, 1/2, 3/4 of the
-                            // chunks, 2 at 1/2, 3/4, 7/8 (product), 3 at 1/8, 1/4, 1/2 -- profiles/round4_ab_setprio_by_progress.txt
-#endif
-#ifndef CRF_X_EARLY
-#define CRF_X_EARLY 1       // fac_chain_body: the frame's scale / exponent bookkeeping behind the first batch of gathers (0: in front of it)
-#endif
-#ifndef CRF_X_CTCSUM
-#define CRF_X_CTCSUM 0      // crf_grad_ctc_kernel: mark a frame whose posteriors do not sum to one (built with the round-5 fixes; +16 % on that kernel, and what it
-                            // caught is decided in front of the grad pass by crf_ctc_check_kernel and the frame factor's range check: the fuzz is green without it)
-#endif
-#ifndef CRF_X_CTCWPE
-#define CRF_X_CTCWPE 5
-#endif
-#ifndef CRF_X_GCHK
-#define CRF_X_GCHK 1        // crf_grad_den_kernel: the emission-weighted lost-term bound per frame (0: only "the frame's mass is a normal float"; A/B of what the check costs)
-#endif
-#ifndef CRF_X_GFIRST
-#define CRF_X_GFIRST 0      // fac_chain_body (one CU per recursion): a frame BEGINS with its first batch of gathers -- everything else a frame starts with
-                            // (stage check, emission prefetch, scale, exponent bookkeeping, row pointers: ~35 scalar instructions, ~4 cycles of a
-                            // wave's issue each) follows behind a scheduling barrier, while the gathers are on their way -- profiles/round5_ab_*.txt
-#endif
-#ifndef CRF_X_KCLATE
-#define CRF_X_KCLATE 0      // fac_chain_body, table geometries: the first slice's row constants are requested behind the first batch of gathers (0: at the frame top)
-#endif
-#ifndef CRF_X_LAG
-#define CRF_X_LAG 0         // fac_chain_body (one CU per recursion): the scale of frame t+1 is worked out in the TAIL of frame t from the maximum
-                            // deposited in frame t-1 -- known before barrier t, so no frame starts with an LDS round trip for its scale (0: the scale of
-                            // frame t from the maximum of its own source vector, read behind the barrier) -- profiles/round5_ab_lagged_scale.txt
-#endif
-// Lagged scale: the vector of frame t+1 is produced with a scale chosen before its size is known.  With u_t = (exponent of max X_t) + k_t
-// the exponent of the SCALED source of frame t, the rule k_{t+1} = kLagTarget - u_t gives u_{t+1} = kLagTarget + kEpExp + g_t, where 2^g_t is
-// what frame t's emissions and weights did to the maximum (g_t in [-8, 1] for ordinary network outputs): the scaled maximum of a frame depends
-// on the growth of ONE earlier frame, nothing accumulates.  Any integer k is exact (a power of two; the exponent word E carries the sum), so
-// only the range is at stake -- and not in the recursions first but in the GRAD pass, which multiplies a row of q ~ 2^u_t with a row of
-// b ~ 2^u'_t and e' 2^-kEpExp ~ 2^g: with the unlagged rule both rows sit at 2^kScaleExp whatever the frame did, here they carry the frame's
-// growth (found by tests/test_gpu_parity.py::test_lagged_scale_window: NaN gradients at 45 nats with the first thresholds).  Hence: a frame
-// whose scaled maximum falls below 2^kLagLow -- it shrank the vector by more than 2^40, 28 nats below the row maximum in ONE frame, against
-// 131 nats with the unlagged rule -- marks the utterance for the log-shifted fallback (crf_robust_den_kernel), as total underflow does.
-constexpr int kLagTarget = -28;   // u_{t+1} = 36 + g_t (the next vector's maximum: 2^(100 + g_t + g_{t+1}) < 2^127)
-constexpr int kLagLow = -4;       // u_t below this: q * b * e' could leave the fp32 range in the grad pass
 struct LossParams {
     GraphDev g;
     const float *logp;

@@ -192,6 +192,7 @@ static size_t chain_lds_bytes(const HostGraph *h, int V, int Sc, int role, bool 
 // n+1 are cleared by its prep kernel, which runs after call n has joined everything back into that stream).
 // ---------------------------------------------------------------------------------------------
 constexpr int kMaxStages = 16;
+constexpr int kStageFill = 75;   // staged schedule (and the numerator chains beside the recursions) for den grids of up to this percent of the CUs
 constexpr int kFlagInts = 2048;
 struct DevCtx {
     std::mutex mu;            // one call at a time is ENQUEUED through a context (host side only; nothing waits on the GPU)
@@ -350,7 +351,7 @@ static int get_ctx(hipStream_t owner, DevCtx **out) {
     }
     // A third stream for work that may take long beside the staged grad pass (the numerator's log-domain chains): it must not sit
     // behind the owner's stream (the den grid), which is all the probe asks; sharing a queue with the side stream only delays it.
-    if (c->side && c->flags && !trust && !opt_on(kOpt_no_aux_stream) &&
+    if (c->side && c->flags && !trust &&
         hipEventCreateWithFlags(&c->ev_a, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&c->ev_b, hipEventDisableTiming) == hipSuccess) {
         (void)hipStreamSynchronize(owner);
         int kind = 0, tries = 0;
@@ -891,7 +892,7 @@ static void plan_schedule(CallPlan &pl, int64_t B, int64_t T, const DevFacts &f)
     const int pieces = stages_env > 0 ? stages_env : (pl.segmode ? 4 : 12);   // measured: 4 / 8 / 12 pieces -> call 4.06 / 3.98 / 3.93 ms (flags)
     pl.den_wgs = pl.pair2 ? 2 * ((B + 1) / 2) : 2 * B;
     // (the two-utterance kernel has no segment relaunches: where stream-level waits are refused it runs unstaged)
-    pl.staged = pl.fac && pl.FX->K == 1 && pl.ctc && pl.fast_den && pl.fast_ctc && !pl.serial && !pl.no_overlap && f.have_flags && !(pl.pair2 && pl.segmode) && pl.den_wgs * 100 <= (int64_t)f.ncu * opt(kOpt_stage_fill, 75);   // (B = 80: 4.16 -> 3.56 ms, B = 96: 4.37 -> 4.26, B = 112 at 90 %: 5.33 -> 5.57)
+    pl.staged = pl.fac && pl.FX->K == 1 && pl.ctc && pl.fast_den && pl.fast_ctc && !pl.serial && !pl.no_overlap && f.have_flags && !(pl.pair2 && pl.segmode) && pl.den_wgs * 100 <= (int64_t)f.ncu * kStageFill;   // (B = 80: 4.16 -> 3.56 ms, B = 96: 4.37 -> 4.26, B = 112 at 90 %: 5.33 -> 5.57)
     // Stage bounds.  Nothing can be released before the two recursions have met, so the first stage ends at half of
     // the frames or later; after that a piece of `piece` iterations releases 2 * piece / 16 frame blocks per
     // utterance.  The grad pass has half of the chip and is bandwidth-bound there (~2 TB/s against the 2.2 TB/s the
@@ -1050,14 +1051,13 @@ struct LossCall {
         dim3 gg((unsigned)((T + kGDFrames - 1) / kGDFrames), (unsigned)B);
         p.gd_nf = 0;
         p.gd_persist = 0;
-        const bool full_grid = opt_on(kOpt_gd_full_grid);
         if (persist) {   // the stages `stage` .. nstage in one launch (see the kernel): 2 * nf candidates per utterance and stage, stage-major
             p.gd_persist = 1;
             p.gd_cnt = cx->flags + 16;
             p.gd_target = (int)(2 * B);
             const int64_t tot = plan_grad_grid(p.gd_bound, p.gd_nb - 1, stage, B, pl.gd_piece, p.gd_poff, p.gd_fpb);
             gg = dim3((unsigned)tot, 1);
-        } else if (stage > 1 && !full_grid) {   // (stage 1 is the middle of every utterance: all blocks are candidates)
+        } else if (stage > 1) {   // (stage 1 is the middle of every utterance: all blocks are candidates)
             p.gd_nf = (p.gd_bound[stage] - p.gd_bound[stage - 1] + kGDFrames - 1) / kGDFrames + 3;
             if (2 * p.gd_nf < (int)gg.x) gg.x = (unsigned)(2 * p.gd_nf); else p.gd_nf = 0;
         }
@@ -1070,7 +1070,7 @@ struct LossCall {
             return launch<crf_grad_den_kernel<2, 2, 2 * kGDThreads>>(name, gg, b2, l, st, p);
         if (pl.gd_wide6)                 // rows of 10 241 .. 12 288 floats: 512 threads with six row registers each
             return launch<crf_grad_den_kernel<1, 2, 2 * kGDThreads, kChunk, 6, 1>>(name, gg, b2, l, st, p);
-        if (pl.gd_wide && CRF_X_GDW2 && w.Rq <= 32 * kGDThreads && w.Rb <= 32 * kGDThreads)
+        if (pl.gd_wide && w.Rq <= 32 * kGDThreads && w.Rb <= 32 * kGDThreads)
             // rows of 5121 .. 8192 floats: 512 threads with four row registers each, held to 128 VGPRs so that a CU takes TWO workgroups (the
             // five-register form below compiles to 148 VGPRs: one workgroup, eight waves, per CU -- the estimated S = 6836 graph ran on that)
             return launch<crf_grad_den_kernel<1, 2, 2 * kGDThreads, kChunk, 4, 4>>(name, gg, b2, l, st, p);
@@ -1409,7 +1409,7 @@ int LossCall::run_two_streams() {
     // chains ran beside the recursions on the few CUs they leave, 2 B chain workgroups on 256 - 2 B CUs, and took longer than the recursions: B = 100 /
     // 104 / 112 / 120 4.40 / 4.54 / 4.82 / 5.16 ms per step; behind them, beside the den half of the grad pass: 4.28 / 4.38 / 4.48 / 4.61,
     // profiles/round5_ab_grad_one_launch.txt)
-    const bool after = ctc_after_env >= 0 ? ctc_after_env != 0 : fac1 ? pl.den_wgs * 100 > (int64_t)pl.ncu * opt(kOpt_stage_fill, 75) : (pl.res && h->dev.res.K > 1);
+    const bool after = ctc_after_env >= 0 ? ctc_after_env != 0 : fac1 ? pl.den_wgs * 100 > (int64_t)pl.ncu * kStageFill : (pl.res && h->dev.res.K > 1);
     if (after) {
         // (the consistency check BEHIND the fork: the numerator chains -- a latency chain that wants its workgroups resident at once -- are
         // released by the end of the recursions and get the CUs first; with the check in front of the fork the grad launch below, which
@@ -1573,8 +1573,9 @@ int crf_last_fallback_counts(int32_t *out2, void *stream) {
 }
 
 const char *crf_build_switches(void) {
-    return "LAG=" CRF_STR(CRF_X_LAG) " KCLATE=" CRF_STR(CRF_X_KCLATE) " PRIO=" CRF_STR(CRF_X_PRIO) " EARLY=" CRF_STR(CRF_X_EARLY)
-           " GFIRST=" CRF_STR(CRF_X_GFIRST) " GCHK=" CRF_STR(CRF_X_GCHK) " CTCSUM=" CRF_STR(CRF_X_CTCSUM) " GDEARLY=" CRF_STR(CRF_X_GDEARLY) " GDMOVE=" CRF_STR(CRF_X_GDMOVE) " GDW2=" CRF_STR(CRF_X_GDW2)
+    return "FAC4_NB=" CRF_STR(CRF_FAC4_NB) " FAC4_NB_ML=" CRF_STR(CRF_FAC4_NB_ML) " FAC5_NB2=" CRF_STR(CRF_FAC5_NB2) " FAC3_NB2=" CRF_STR(CRF_FAC3_NB2)
+           " FAC3_NB_F=" CRF_STR(CRF_FAC3_NB_F) " FAC3_NB_B=" CRF_STR(CRF_FAC3_NB_B) " FAC3L_NCH=" CRF_STR(CRF_FAC3L_NCH) " FAC4_NCH=" CRF_STR(CRF_FAC4_NCH)
+           " GD_FRAMES=" CRF_STR(CRF_GD_FRAMES)
 #ifdef CRF_TIMING
            " TIMING=1"
 #endif

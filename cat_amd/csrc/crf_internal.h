@@ -198,7 +198,7 @@ __host__ __device__ inline void bat_decode(int block, int grid, int ncombo, int 
 
 // bundles per task at most: 8; factored streams of groups of 16 / 8 utterances 4 / 2 (three descriptor words for each of the
 // 16 / 32 rows of a bundle: the wave's slice of LDS)
-constexpr int kBatEpiDefault = 2;   // (switch bat_epi; 0 / 1 / 2 / 4 -> S = 16 385 recursions 25.03 / 24.91 / 24.57 / 25.06 ms, S = 12 289 19.58 / 19.60 / 19.41 / 19.67: one box, round 6)
+constexpr int kBatEpiDefault = 2;   // what a bundle's row epilogues count for when the arc streams are cut into tasks, in batches of 4 steps (0 / 1 / 2 / 4 -> S = 16 385 recursions 25.03 / 24.91 / 24.57 / 25.06 ms, S = 12 289 19.58 / 19.60 / 19.41 / 19.67: one box, round 6)
 __host__ __device__ constexpr int stream_max_bundles(int UL, bool fac) { return !fac || UL >= 32 ? 8 : UL == 16 ? 4 : 2; }
 struct StreamDirDev {
     const int4 *tasks;       // [ntasks] {first batch, batches, first bundle, bundles}
@@ -326,29 +326,18 @@ void set_error(const std::string &msg);
     X(fac_no_k2,        "G  never two CUs per recursion: graphs of 120 k - 240 k arcs take the generic layout")              \
     X(fac_threads,      "G  512 / 768 / 1024: that geometry of the factored layout (default: 1024 threads first, then the 768-thread geometries, then 512)")                                            \
     X(fac_no_dup,       "G  factored layout: no second copy of the gathered entries")                                        \
-    X(fac_bank_shift,   "G  factored layout: bank distance of the second copy (default 5)")                                  \
     X(fac_addtid,       "G  factored layout, 1024 threads: the row epilogues store the next vector with 0 = ds_write_b32 / ds_write2st64_b32, 1 = ds_write_addtid_b32 (the default there)") \
     X(res_mink,         "G  generic layout: at least this many CUs per recursion")                                           \
-    X(res_epi,          "G  layout cost model: slice end in chunks (default 4)")                                             \
-    X(res_piece,        "G  multi-lane rows: piece size in percent of a lane's chunks (default: the cost model's choice)")   \
-    X(res_no_simd_order,"G  layout: no SIMD-aware placement of the waves' slice lists")                                      \
-    X(res_simd0,        "G  factored layouts: handicap of SIMD 0 in the placement's cost model, in chunks (default 0)")                  \
-    X(res_emis,         "G  factored layouts: what the emission staging costs a wave that holds emissions, in chunks (default 8; 0: waves treated alike)") \
     X(res_no_spread,    "G  small graphs: rows that fit a lane are not cut into pieces to give every wave a share")          \
-    X(res_owner_first,  "G  multi-lane rows: the first lane of a group owns the outputs (no rotation)")                      \
-    X(no_bank_arrange,  "G  no bank-aware arc order (edge colouring) in the register-resident layouts")                      \
-    X(no_grad_arrange,  "G  grad pass: (Q, BP) pair lists in plain label order")                                             \
     X(no_regauge,       "G  weight-pushed graphs are not re-gauged")                                                         \
     X(regauge_minhash,  "G  re-gauging: find the two states of a history by min-hashing (what graphs of millions of arcs take)") \
     X(verbose,          "G  print layout statistics to stderr")                                                             \
     X(emu_drop_list,    "-  crf_debug_fac_emulate: drop the two-CU fetch list (negative control of the emulation)")          \
     X(emu_facp,         "-  crf_debug_fac_emulate: the two-utterance kernel's layout (HostGraph::facp) instead of the main one")  \
-    X(emu_verbose,      "-  crf_debug_fac_emulate: per-frame masses to stderr")                                              \
     X(bat_no_fac,       "GC utterance-minor kernels: plain arc streams instead of the factored ones")                        \
     X(bat_task,         "C  utterance-minor kernels: steps per task")                                                        \
     X(bat_ul,           "C  utterance-minor kernels: utterances per group (8, 16, 32, 64)")                                  \
     X(bat_fill,         "C  utterance-minor kernels: percent of the device's workgroup slots a launch takes (default 70)")   \
-    X(bat_epi,          "GC utterance-minor kernels: what a bundle's row epilogues count for when the arc streams are cut into tasks, in batches of 4 steps") \
     X(bat_persist,      "C  utterance-minor kernels: 1 = all frames in ONE persistent launch with a grid barrier per frame (default when the grid is co-resident), 0 = one launch per frame") \
     X(force_batch,      "C  utterance-minor kernels for every graph")                                                        \
     X(no_batch,         "C  streaming kernels instead of the utterance-minor ones")                                          \
@@ -358,11 +347,9 @@ void set_error(const std::string &msg);
     X(no_fast_grad,     "C  generic grad kernel instead of the streaming grad kernels")                                      \
     X(no_overlap,       "C  no staged grad pass beside the recursions")                                                      \
     X(segments,         "C  staged schedule by relaunching the recursions per stage (events) instead of stream-level waits") \
-    X(stage_fill,       "C  staged schedule for den grids of up to this percent of the CUs (default 75)")                     \
     X(stages,           "C  number of grad stages")                                                                          \
     X(piece,            "C  iterations per grad stage")                                                                      \
     X(first_shift,      "C  first grad stage this many 16-frame blocks later (shortens the LAST stage by as much)")           \
-    X(gd_full_grid,     "C  stage launches of the grad pass as full grids")                                                  \
     X(gd_stage_launches,"C  one grad launch per stage behind stream-level waits (round 4) instead of ONE launch whose workgroups wait") \
     X(no_fin_fold,      "C  crf_finalize_kernel as a launch of its own (round 4) instead of in the last fallback launch")                \
     X(gd_sub,           "C  frames per grad workgroup in the short last stages of the one-launch grad pass (default 16 = whole blocks; 8 / 4 / 2 split them: measured not better)") \
@@ -374,7 +361,6 @@ void set_error(const std::string &msg);
     X(side_kind,        "X  side stream candidates of one kind only: 1 plain, 2 high priority, 3 low priority, 4 CU-masked")  \
     X(grad_par3,        "C  staged schedule: 1 = the den half of the grad pass on the third stream beside the numerator half (atomic adds into zeroed rows; measured slower, default 0)") \
     X(aux_stream,       "C  numerator fallback chains on the third stream: 1 always, 0 never (default: when a recent call needed them)")  \
-    X(no_aux_stream,    "X  no third stream for this context (numerator fallback chains in front of the grad stages)")      \
     X(no_facp,          "G  no second (512-thread) factored layout for the two-utterance kernel")                            \
     X(fac_pair2,        "C  factored recursions with TWO utterances per workgroup: 1 = for any batch, 0 = never (default: batches above CUs / 2)") \
     X(ws_gap,           "C  test aid: n x 256 bytes that no kernel may touch behind every workspace section, in crf_workspace_bytes / crf_ctc_align*_workspace_bytes and in the calls alike; unset (the default), the layout is byte for byte the packed one")

@@ -166,7 +166,6 @@ struct EllHost {
 // of 64; each slice is as wide as its first (longest) row, rounded up to an even arc count.
 EllHost build_ell(const std::vector<std::vector<std::pair<int, float>>> &rows) {
     EllHost e;
-    const bool arrange = !opt_on(kOpt_no_bank_arrange);
     const int R = (int)rows.size();
     std::vector<int> order(R);
     std::iota(order.begin(), order.end(), 0);
@@ -207,7 +206,7 @@ EllHost build_ell(const std::vector<std::vector<std::pair<int, float>>> &rows) {
                     if (rv.empty()) continue;
                     size_t best = 0;
                     int best_cost = 1 << 30;
-                    for (size_t k = 0; k < (arrange ? rv.size() : (size_t)1); ++k) {
+                    for (size_t k = 0; k < rv.size(); ++k) {
                         const int bank = rv[k].first & 31;
                         const int cost = (occupant[bank] == rv[k].first) ? 0 : used[bank];
                         if (cost < best_cost) { best_cost = cost; best = k; if (cost == 0) break; }
@@ -285,8 +284,8 @@ static int build_stream_rows(int AL, int UL, int task_steps, int maxb, int NM, c
     const int nbund = ((int)srows.size() + AL - 1) / AL;
     // what a bundle costs a task besides its gather batches: its row epilogues (stores, ring refill), in batches of 4 steps -- the last tasks of a combo hold the
     // shortest rows, i.e. the most bundles per gather step, and were the last to reach the frame's end (profiles/round6_ab_persistent_batch.txt: 15 us where
-    // the first tasks take 10); switch bat_epi, default kBatEpiDefault
-    const int epi = std::max(0, opt(kOpt_bat_epi, kBatEpiDefault)) * kB;
+    // the first tasks take 10): kBatEpiDefault
+    const int epi = kBatEpiDefault * kB;
     int task_b0 = 0, task_batch0 = 0, task_steps_now = 0;
     auto close_task = [&](int b1) {
         if (b1 == task_b0) return;
@@ -627,7 +626,7 @@ int debug_check_facbatch(const HostGraph *h, int64_t *out4) {
 
 // steps per task: the longer direction's steps (rows padded to whole batches of 4) over the tasks wanted; CRF_BAT_TASK overrides
 static int stream_task_steps(const HostGraph *h, int AL, int want, bool fac = false) {
-    const int epi = std::max(0, opt(kOpt_bat_epi, kBatEpiDefault)) * 4;   // (build_stream_rows: what a bundle's row epilogues cost, in steps)
+    const int epi = kBatEpiDefault * 4;   // (build_stream_rows: what a bundle's row epilogues cost, in steps)
     auto steps_of = [&](const std::vector<int4> &rows) {
         int64_t n = 0;
         for (const int4 &d : rows) if ((d.w & 0x40000000) && d.y > d.x) n += (d.y - d.x + 3) / 4 * 4 + epi;

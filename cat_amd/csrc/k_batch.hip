@@ -90,9 +90,6 @@ __device__ __forceinline__ float arc_lane_max(float v) {
 // the per-frame launches.
 // ---------------------------------------------------------------------------------------------
 #define CRF_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-#ifndef CRF_X_BATLD
-#define CRF_X_BATLD 0       // TIMING EXPERIMENTS ONLY (wrong results): the persistent kernel's 16-byte gathers as 1 = plain global loads, 2 = buffer loads without sc1
-#endif
 template <bool PERS>
 struct VecRef {                                                    // a state vector of one utterance group: base + byte size
     const char *base;
@@ -101,7 +98,7 @@ struct VecRef {                                                    // a state ve
         if constexpr (PERS) rs = __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, (int)bytes, 0x27000);
     }
     __device__ __forceinline__ f32x4 ld4(unsigned off) const {      // 16 bytes at byte offset off
-        if constexpr (PERS && CRF_X_BATLD != 1) return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, CRF_X_BATLD == 2 ? 0 : 16));
+        if constexpr (PERS) return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 16));
         else return *(const f32x4 *)(base + off);
     }
     __device__ __forceinline__ float ld1(size_t idx) const {

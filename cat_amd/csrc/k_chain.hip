@@ -824,7 +824,7 @@ __global__ __launch_bounds__(kChainThreads) void crf_den_pair_kernel(LossParams 
 }
 // NR: ctc states per thread, chosen by the host from the batch's longest label sequence.
 template <int NR>
-__global__ __launch_bounds__(kCtcThreads, NR == 1 ? CRF_X_CTCWPE : 1) void crf_ctc_pair_kernel(LossParams p) {
+__global__ __launch_bounds__(kCtcThreads, NR == 1 ? kCtcPairWavesPerSimd : 1) void crf_ctc_pair_kernel(LossParams p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if ((int)blockIdx.x < p.B) ctc_forward<NR>(p, (int)blockIdx.x, lds);
     else ctc_backward<NR>(p, (int)blockIdx.x - p.B, lds);

@@ -229,19 +229,6 @@ __device__ __forceinline__ void fac_chain_body(const FacParams &p, float *lds, c
     };
     const bool pre_w = wave * kWave < V;                     // this wave holds emissions
     float last_sc = 1.f;                                     // scale of the last frame (rowless states, after the loop)
-    // lagged scale (CRF_X_LAG): exponent of the NEXT frame's scale, worked out in the tail of the frame before; the first frame of a
-    // launch takes the unlagged rule on the vector it starts from (any integer is exact).  lag_lo: the smallest scaled maximum seen (below kLagLow: fallback).
-    constexpr bool LAG = CRF_X_LAG != 0 && !K2;
-    // The maximum read in the tail of frame t travels to frame t+1 in a VECTOR register (lag_mx, the same bits in every lane) and is turned
-    // into the scale there, BEHIND the frame's first gathers: lag_k is the exponent of the scale of the frame before.  First frame of a
-    // launch: lag_mx = the maximum of the vector it starts from and lag_k = kLagTarget - kScaleExp give exactly the unlagged rule.
-    [[maybe_unused]] int lag_k = kLagTarget - kScaleExp, lag_lo = 0x7fffffff, lag_mx = 0;
-    if constexpr (LAG) {
-        typedef int i32x4_t __attribute__((ext_vector_type(4)));
-        const i32x4_t m4 = *(const i32x4_t *)(wm + sr * 4);
-        lag_mx = max(max(m4.x, m4.y), max(m4.z, m4.w));
-    }
-    constexpr bool GFIRST = CRF_X_GFIRST != 0 && CRF_X_EARLY != 0 && !K2;
     constexpr int EPR = NTH >= 2 * kResThreads ? 1 : kEpRegsR;   // (V <= 2 * 512 everywhere: use_factored)
     float epn[EPR] = {};                                    // next emission row, in flight across the frame (waves that hold emissions only)
     // this utterance's emissions, rows and exponents (the frame loop adds 32-bit offsets: one s_mul instead of a 64-bit product per address)
@@ -256,19 +243,6 @@ __device__ __forceinline__ void fac_chain_body(const FacParams &p, float *lds, c
         if (b == 3 && i >= 150 && i < 158 && wave == 0) CRF_TM(true, 12288 + 1024 + (DIR * 4) * 8 + (i - 150));  // frame start
 #endif
         const char *xb = (const char *)lds + par * XB;
-        // GFIRST: the frame's first batch of gathers needs the source vector and nothing else -- it is requested before anything else is
-        // worked out (every wave: idle waves hold padding arcs, offset 0 and weight 0).  A wave issues one instruction per ~4 cycles whatever
-        // it is (tools/ubench_issue.py), and the ~35 scalar instructions a frame used to begin with kept the LDS idle for ~200 cycles right
-        // behind every barrier (timing build, round 5: "frame top" 240 cycles with nothing to wait for).
-        constexpr int NB0 = NB < NCHA ? NB : NCHA;
-        [[maybe_unused]] f32x2 g01_0[NB0], g23_0[NB0];
-        if constexpr (GFIRST) {
-#if CRF_X_PRIO
-            __builtin_amdgcn_s_setprio(3);
-#endif
-            CRF_RES_GATHER_N(g01_0, g23_0, A, xb, 0, NB0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
         const int t = DIR == 0 ? i : lx - 1 - i;
         if (FLAG && i == next_bound) publish_stage();
         char *xnb = (char *)lds + (1 - par) * XB;
@@ -290,29 +264,18 @@ __device__ __forceinline__ void fac_chain_body(const FacParams &p, float *lds, c
         }
         const int sw = sr == 2 ? 0 : sr + 1, sz = sw == 2 ? 0 : sw + 1;   // accumulated during this frame / cleared in it
         typedef int i32x4_t __attribute__((ext_vector_type(4)));
-        [[maybe_unused]] i32x4_t m4{};
-        if constexpr (!LAG) m4 = *(const i32x4_t *)(wm + sr * 4);    // (non-negative floats: their bits order like integers)
-        // The frame's scale and exponent are worked out BEHIND the first batch of gathers (EARLY: the batch loop calls `bookkeeping`
+        const i32x4_t m4 = *(const i32x4_t *)(wm + sr * 4);    // (non-negative floats: their bits order like integers)
+        // The frame's scale and exponent are worked out BEHIND the first batch of gathers (the batch loop calls `bookkeeping`
         // once its first gathers are requested -- they need nothing but the vector; the scale enters in the row epilogues only):
-        // with the scale first, every wave of the workgroup sat out one LDS round trip right after the frame barrier, the LDS idle.
+        // with the scale first, every wave of the workgroup sat out one LDS round trip right after the frame barrier, the LDS idle
+        // (also with two CUs per recursion: H = 3 072 recursions 4.22 -> 4.04 ms).
         float sc = 1.f;
         float *Orow = nullptr;
         auto bookkeeping = [&]() __attribute__((always_inline)) {
             // (the maxima's use ends up in FRONT of the first gathers all the same -- the scheduler gives their four registers to the gathers' addresses -- so
             // the frame still starts with one LDS round trip.  Reading them by inline asm BEHIND the gathers instead: metric step 2.833 vs 2.848 ms, but the
             // S = 513 graph 2.012 vs 1.978 -- dropped, profiles/round4_ab_waits_found_in_the_isa.txt)
-            int ksc;
-            if constexpr (LAG) {
-                // lag_mx: maximum of the source vector of the frame BEFORE (read in that frame's tail), lag_k: that frame's scale
-                const unsigned bits = (unsigned)__builtin_amdgcn_readfirstlane(lag_mx);
-                int u = (int)(bits >> 23) - 127 + lag_k;             // exponent of the scaled maximum of that frame's source
-                ksc = kLagTarget - u;
-                // (all on the scalar unit; lag_lo: the smallest u of the recursion -- an all-zero vector lands far below kLagLow too, it is flagged at the end anyway)
-                const int uu = i == i0 ? 0x7fffffff : u;           // (the first frame's u is the start-up convention above, not a measurement)
-                asm("s_min_i32 %0, %0, %1" : "+s"(lag_lo) : "s"(uu) : "scc");
-                asm("s_max_i32 %0, %0, %1\n\ts_min_i32 %0, %0, %2" : "+s"(ksc) : "s"(-100), "s"(100) : "scc");
-                lag_k = ksc;
-            } else ksc = rescale_exp_bits_uniform((unsigned)__builtin_amdgcn_readfirstlane(max(max(m4.x, m4.y), max(m4.z, m4.w))));   // (uniform)
+            const int ksc = rescale_exp_bits_uniform((unsigned)__builtin_amdgcn_readfirstlane(max(max(m4.x, m4.y), max(m4.z, m4.w))));   // (uniform)
             sc = pow2f(ksc);
             if (DIR == 1) last_sc = sc;
             if (DIR == 0) {
@@ -332,8 +295,6 @@ __device__ __forceinline__ void fac_chain_body(const FacParams &p, float *lds, c
                 Orow = t > 0 ? Out_b + (unsigned)(t - 1) * (unsigned)p.Rout : p.Row0 + (int64_t)b * p.Rout;
             }
         };
-        constexpr bool EARLY = CRF_X_EARLY != 0;   // (also with two CUs per recursion: H = 3 072 recursions 4.22 -> 4.04 ms)
-        if constexpr (!EARLY) bookkeeping();
         unsigned ends_f = ends;
         int nch_f = nch;
         asm volatile("" : "+s"(ends_f), "+s"(nch_f));
@@ -341,16 +302,12 @@ __device__ __forceinline__ void fac_chain_body(const FacParams &p, float *lds, c
         float mymax = 0.f;
         CRF_TM(tm_on, tm_i + 1);
         unsigned r4 = (unsigned)(row0 + lane) * 4u;   // 4 * row id
-        constexpr bool EARLY_ = CRF_X_EARLY != 0;
         [[maybe_unused]] gu64 *slot = nullptr;        // K2: the granules of the vector this frame produces
         [[maybe_unused]] const unsigned tag = (unsigned)(i + 1);
         if constexpr (K2) slot = xchd + (size_t)(1 - par) * G;
         typedef std::conditional_t<DIR == 0, uint2, uint4> rct_t;
         [[maybe_unused]] rct_t kc{};                  // RL: constants of the slice that ends next
-        // (KCLATE: the first slice's constants are requested BEHIND the first batch of gathers -- sixteen waves' 8- / 16-byte-per-lane reads
-        // in front of them keep the LDS busy for 64 / 128 cycles right behind the barrier before the first gather is served)
-        constexpr bool KCLATE = CRF_X_KCLATE != 0 && RL && EARLY_ && !K2;
-        if constexpr (RL && !KCLATE) kc = *(const rct_t *)(RMc + (DIR == 0 ? 2u : 4u) * r4);
+        if constexpr (RL) kc = *(const rct_t *)(RMc + (DIR == 0 ? 2u : 4u) * r4);
         // the end of a slice (row): everything between the row's sum and its entries of the next vector
         auto row_end = [&](const unsigned ks) __attribute__((always_inline)) {   // ks: slice number (uniform)
             // rows longer than a lane's registers lie on 2^lg adjacent lanes (res_layout.cpp place_rows): a butterfly
@@ -497,42 +454,29 @@ __device__ __forceinline__ void fac_chain_body(const FacParams &p, float *lds, c
 #pragma unroll
         for (int c0 = 0; c0 < NCHA; c0 += NB) {
             const int nb = NCHA - c0 < NB ? NCHA - c0 : NB;   // (the last batch may be short: 21 chunks in batches of 4)
-#if CRF_X_PRIO
             // least progress first: a wave's issue priority (s_setprio) falls as it advances through its chunks, so that the four
             // waves of a SIMD reach the frame barrier together.  Without it the SIMD issues its OLDEST wave first: in the timing
             // build the oldest waves were through their chunks at 2 560 cycles and the youngest -- alone on their SIMDs at the end,
             // one wave's latency hiding -- at 4 140 of a 4 700-cycle frame; with it 3 050 ... 3 790 of 4 350.  (Round 2 had tried
             // STATIC priorities for the younger waves: slower.)
             {
-                constexpr int f1 = CRF_X_PRIO == 2 ? 4 : CRF_X_PRIO == 3 ? 1 : 2, f2 = CRF_X_PRIO == 2 ? 6 : CRF_X_PRIO == 3 ? 2 : 4, f3 = CRF_X_PRIO == 2 ? 7 : CRF_X_PRIO == 3 ? 4 : 6;   // eighths of the chunks
+                constexpr int f1 = 4, f2 = 6, f3 = 7;   // eighths of the chunks: steps at 1/2, 3/4, 7/8 (profiles/round4_ab_setprio_by_progress.txt)
                 constexpr int qlast = (NCHA - 1) / NB * NB;   // start of the last batch: a threshold rounded up beyond it would never be reached (768 x 20 in batches of 4: 7/8 -> 20)
                 constexpr int q1 = (f1 * NCHA / 8 + NB - 1) / NB * NB, q2 = (f2 * NCHA / 8 + NB - 1) / NB * NB,
                               q3 = (f3 * NCHA / 8 + NB - 1) / NB * NB < qlast ? (f3 * NCHA / 8 + NB - 1) / NB * NB : qlast;
                 // (not with two CUs per recursion: a wave that polls for the peer's entries at the lowest priority delays BOTH CUs -- H = 3 072 recursions 4.17 without, 4.24 ms with)
                 if constexpr (!K2) {
-                    if (c0 == 0) { if constexpr (!GFIRST) __builtin_amdgcn_s_setprio(3); }
+                    if (c0 == 0) __builtin_amdgcn_s_setprio(3);
                     else if (c0 == q1) __builtin_amdgcn_s_setprio(2);
                     else if (c0 == q2) __builtin_amdgcn_s_setprio(1);
                     else if (c0 == q3) __builtin_amdgcn_s_setprio(0);
                 }
             }
-#endif
-            // (EARLY: the first batch is gathered by every wave -- the slots of a wave without arcs hold padding, offset 0 and weight 0)
-            if ((EARLY && c0 == 0) || c0 < nch_f) {
+            // (the first batch is gathered by every wave -- the slots of a wave without arcs hold padding, offset 0 and weight 0)
+            if (c0 == 0 || c0 < nch_f) {
                 f32x2 g01[NB], g23[NB];
-                if (GFIRST && c0 == 0) {
-#pragma unroll
-                    for (int ci = 0; ci < NB0; ++ci) { g01[ci] = g01_0[ci]; g23[ci] = g23_0[ci]; }
-                } else {
-                    CRF_RES_GATHER_N(g01, g23, A, xb, c0, nb);
-                }
-                if constexpr (KCLATE) {
-                    if (c0 == 0) {
-                        asm volatile("" ::: "memory");   // (keeps the read behind the gathers in the instruction stream)
-                        kc = *(const rct_t *)(RMc + (DIR == 0 ? 2u : 4u) * r4);
-                    }
-                }
-                if constexpr (EARLY) { if (c0 == 0) bookkeeping(); }
+                CRF_RES_GATHER_N(g01, g23, A, xb, c0, nb);
+                if (c0 == 0) bookkeeping();
 #pragma unroll
                 for (int ci = 0; ci < nb; ++ci) {
                     CRF_RES_CHUNK_ACC(acc, g01, g23, A, c0 + ci, ci);
@@ -573,11 +517,6 @@ __device__ __forceinline__ void fac_chain_body(const FacParams &p, float *lds, c
             }
             mymax = fmaxf(mymax, fm);
         }
-        // lagged scale: the maximum of THIS frame's source vector (deposited during the frame before, complete since the last barrier) gives
-        // the scale of the NEXT frame -- requested here, where the gathers' registers are free, ahead of the wave maximum's DPP chain; the
-        // scalar arithmetic runs while the deposit below is on its way
-        [[maybe_unused]] i32x4_t m4n{};
-        if constexpr (LAG) m4n = *(const i32x4_t *)(wm + sr * 4);
         mymax = row_max16(mymax);   // (sending the maximum from every row end instead -- no reduction in the tail -- was measured 3 % slower, round 4)
         if (rowlead) lds_fmax(wm + sw * 4 + (lane >> 4), mymax);
         sr = sw;
@@ -586,7 +525,6 @@ __device__ __forceinline__ void fac_chain_body(const FacParams &p, float *lds, c
 #pragma unroll
             for (int q = 0; q < EPR; ++q) { const int v = tid + q * NTH; if (v < V) EPw[v] = epn[q]; }
         }
-        if constexpr (LAG) lag_mx = max(max(m4n.x, m4n.y), max(m4n.z, m4n.w));   // (behind the emission staging: ONE wait for the LDS in the tail, the one the barrier needs anyway)
         CRF_TM(tm_on, tm_i + 3);
 #ifdef CRF_TIMING
         if (b == 3 && i >= 150 && i < 158) CRF_TM(true, 15360 + (DIR * 16 + wave) * 8 + (i - 150));   // this wave's arrival at the frame barrier
@@ -614,7 +552,6 @@ __device__ __forceinline__ void fac_chain_body(const FacParams &p, float *lds, c
         const float *Xc = X + (i1 & 1) * Gp;
         for (int s = tid; s < G; s += NTH) state[s] = Xc[s];
         if (tid == 0) state[Gp] = __int_as_float(E);
-        if (tid == 0 && LAG && lag_lo < kLagLow) p.redo[DIR * p.B + b] = 1;  // (the flag does not travel with the parked state)
         return;
     }
     if (flagged)
@@ -626,7 +563,7 @@ __device__ __forceinline__ void fac_chain_body(const FacParams &p, float *lds, c
         for (int s = tid; s < G; s += NTH) part += Xf[s] * p.x_end[s];
         const float zs = res_block_sum<NW>(part, (float *)red, tid);
         const double mxs = res_mx_total<NW>(p, b, lx, red, tid);
-        if (tid == 0) { p.den_zs[b] = zs; p.den_ez[b] = E; p.cost_alpha[b] = to_log(zs, E, mxs); if (!(zs > 0.f && zs < INFINITY) || (LAG && lag_lo < kLagLow)) p.redo[b] = 1; }
+        if (tid == 0) { p.den_zs[b] = zs; p.den_ez[b] = E; p.cost_alpha[b] = to_log(zs, E, mxs); if (!(zs > 0.f && zs < INFINITY)) p.redo[b] = 1; }
     } else {
         if (lx > 0) {
             __syncthreads();  // drains vmcnt: this workgroup's own stores to the spare row are visible to it
@@ -656,7 +593,7 @@ __device__ __forceinline__ void fac_chain_body(const FacParams &p, float *lds, c
             }
         }
         const double mxs = res_mx_total<NW>(p, b, lx, red, tid);
-        if (tid == 0) { p.cb_part[(size_t)b * kResMaxK] = zb; p.cb_F[b] = E; p.cb_mxs[b] = mxs; if (!(zb > 0.f && zb < INFINITY) || (LAG && lag_lo < kLagLow)) p.redo[p.B + b] = 1; }
+        if (tid == 0) { p.cb_part[(size_t)b * kResMaxK] = zb; p.cb_F[b] = E; p.cb_mxs[b] = mxs; if (!(zb > 0.f && zb < INFINITY)) p.redo[p.B + b] = 1; }
     }
 }
 

@@ -265,9 +265,8 @@ __global__ __launch_bounds__(NT, WPE) void crf_grad_den_kernel(LossParams p) {
     // rows are multiples of 64 floats and 256-byte aligned: 16-byte loads, prefetched one frame ahead
     // (one chunk and one emission register per thread only -- the kernel of graphs over <= 256 classes with <= 256 label chunks: V = 72 step 2.89 -> 2.865 ms;
     // in the other instantiations the same reordering was 4 % slower at V = 217 / 500 while the copy-behind-the-loads wait described below was still in it, and
-    // makes no difference without it (levels 2 / 3 of the switch): profiles/round4_ab_grad_pass_variants.txt, round4_ab_waits_found_in_the_isa.txt)
-    constexpr bool GDE = CRF_X_GDEARLY != 0 && WPE == 1 && ((NCPT == 1 && (EPR == 1 || CRF_X_GDEARLY >= 2)) || CRF_X_GDEARLY >= 3);
-    constexpr bool GDM = GDE && CRF_X_GDMOVE != 0;
+    // makes no difference without it: profiles/round4_ab_grad_pass_variants.txt, round4_ab_waits_found_in_the_isa.txt)
+    constexpr bool GDE = WPE == 1 && NCPT == 1 && EPR == 1;
     f32x4 qr[RR], br[RR];
     unsigned frame_bad = 0;          // (uniform: a frame of this block failed the mass checks below)
     // where a frame's checks are made: behind its normaliser, or -- the metric graph's instantiation, which has no register to spare there (see the
@@ -285,7 +284,7 @@ __global__ __launch_bounds__(NT, WPE) void crf_grad_den_kernel(LossParams p) {
         const float *er_ = p.ep + (bt0 + (t)) * V;                                                       \
         const float *gr_ = p.grad + (bt0 + (t)) * V;                                                     \
         _Pragma("unroll") for (int q = 0; q < EPR; ++q) {                                                \
-            if constexpr (GDM) {   /* clamped, not predicated (every use is behind v < V): the loads write the loop registers themselves */ \
+            if constexpr (GDE) {   /* clamped, not predicated (every use is behind v < V): the loads write the loop registers themselves */ \
                 const int v = min(tid + q * NT, V - 1);                                                  \
                 ern[q] = er_[v];                                                                         \
                 if (p.grad_den_acc == 1) rwn[q] = gr_[v];   /* (else: stays 0) */                        \
@@ -387,8 +386,7 @@ __global__ __launch_bounds__(NT, WPE) void crf_grad_den_kernel(LossParams p) {
                 for (int q = 0; q < EPR; ++q) {
                     // real moves, here: left to the compiler, the copy became "new ern -> its loop register" BEHIND the loads below, with a
                     // vmcnt(0) in front of it -- the frame waited for the rows of t+2 the moment it had asked for them
-                    if constexpr (GDM) asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3" : "=&v"(erx[q]), "=&v"(rwx[q]) : "v"(ern[q]), "v"(rwn[q]));
-                    else { erx[q] = ern[q]; rwx[q] = rwn[q]; }
+                    asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3" : "=&v"(erx[q]), "=&v"(rwx[q]) : "v"(ern[q]), "v"(rwn[q]));
                 }
                 if (t + 2 < tl) CRF_GD_FETCH(t + 2);
             }
@@ -399,12 +397,12 @@ __global__ __launch_bounds__(NT, WPE) void crf_grad_den_kernel(LossParams p) {
                 const int v = tid + q * NT;
                 u[q] = v < V ? (erc[q] * pow2f(-kGradDescale)) * gsum[v] : 0.f;
                 part += u[q];
-                if (CRF_X_GCHK) emx = fmaxf(emx, v <= g.max_label && v < V ? erc[q] : 0.f);
+                emx = fmaxf(emx, v <= g.max_label && v < V ? erc[q] : 0.f);
             }
             part = wave_sum(part);
-            if (CRF_X_GCHK) emx = wave_max(emx);
+            emx = wave_max(emx);
             if ((tid & 63) == 0 && part != 0.f) atomicAdd(&nrm[t & 3], part);
-            if (CRF_X_GCHK && (tid & 63) == 0 && emx > 0.f) atomicMax((int *)&nrm[8 + (t & 3)], __float_as_int(emx));   // (non-negative floats order like their bits)
+            if ((tid & 63) == 0 && emx > 0.f) atomicMax((int *)&nrm[8 + (t & 3)], __float_as_int(emx));   // (non-negative floats order like their bits)
             CRF_TM(tm_on, 8192 + (t - t0) * 8 + 5);
             sync_lds();                             // rows of frame t+1 visible, normaliser complete
             CRF_TM(tm_on, 8192 + (t - t0) * 8 + 6);
@@ -487,16 +485,16 @@ __global__ __launch_bounds__(NT, WPE) void crf_grad_den_kernel(LossParams p) {
                 const int v = tid + q * NT;
                 u[q] = v < V ? (erc[q] * pow2f(-kGradDescale)) * gsum[v] : 0.f;
                 part += u[q];
-                if (CRF_X_GCHK) emx = fmaxf(emx, v <= g.max_label && v < V ? erc[q] : 0.f);
+                emx = fmaxf(emx, v <= g.max_label && v < V ? erc[q] : 0.f);
                 erc[q] = ern[q];
             }
             float rw[EPR];
 #pragma unroll
             for (int q = 0; q < EPR; ++q) { rw[q] = rwc[q]; rwc[q] = rwn[q]; }
             part = wave_sum(part);
-            if (CRF_X_GCHK) emx = wave_max(emx);
+            emx = wave_max(emx);
             if ((tid & 63) == 0 && part != 0.f) atomicAdd(&nrm[t & 3], part);
-            if (CRF_X_GCHK && (tid & 63) == 0 && emx > 0.f) atomicMax((int *)&nrm[8 + (t & 3)], __float_as_int(emx));
+            if ((tid & 63) == 0 && emx > 0.f) atomicMax((int *)&nrm[8 + (t & 3)], __float_as_int(emx));
             CRF_TM(tm_on, 8192 + (t - t0) * 8 + 5);
             sync_lds();                             // rows of frame t+1 visible, normaliser complete
             CRF_TM(tm_on, 8192 + (t - t0) * 8 + 6);
@@ -553,7 +551,6 @@ __global__ __launch_bounds__(kGCThreads) void crf_grad_ctc_kernel(LossParams p) 
     const bool atomic = p.grad_phase == 3;    // the row starts at zero (prep) and the den half adds its part from another stream: add, never read
     float *gc = lds;                          // [4][Vp] in rotation
     double *fcs = (double *)(gc + 4 * Vp);    // [kGCFrames]
-    float *gt = (float *)(fcs + kGCFrames);   // [4] in rotation: a frame's posteriors must sum to one
     const int64_t bt0 = (int64_t)b * p.T;
     const double zc = ctc_zc_for_grad(p, b);
     const int ezc = p.ctc_ez[b], Sx = 2 * p.ly[b] + 1;
@@ -603,7 +600,7 @@ __global__ __launch_bounds__(kGCThreads) void crf_grad_ctc_kernel(LossParams p) 
     double prod[REGS];
     float rowc[kGCVRegs];
     for (int v = tid; v < 4 * Vp; v += kGCThreads) gc[v] = 0.f;
-    if (tid < 4) gt[tid] = 0.f;
+    if (tid < 4) ((float *)(fcs + kGCFrames))[tid] = 0.f;   // (four words nothing reads: the retired per-frame sum check's, docs/HISTORY.md -- kept until a change that may alter this kernel's machine code)
     if (t0 < tl) {
         CRF_GC_FETCH(t0);
         CRF_GC_CONSUME();
@@ -622,35 +619,28 @@ __global__ __launch_bounds__(kGCThreads) void crf_grad_ctc_kernel(LossParams p) 
         if constexpr (more) CRF_GC_FETCH(t + 1);
         const double fc = fcs[t - t0];
         if (zc > 0.0) {
-            float blank = 0.f, tot = 0.f;
+            float blank = 0.f;
 #pragma unroll
             for (int i = 0; i < REGS; ++i)
                 if (tid + i * kGCThreads < Sx) {
                     const float pr = (float)(prod[i] * fc);  // a posterior, in [0,1]
-                    if (tid & 1) { atomicAdd(&g[mylab[i]], pr); if (CRF_X_CTCSUM) tot += pr; }
+                    if (tid & 1) atomicAdd(&g[mylab[i]], pr);
                     else blank += pr;
                 }
             blank = wave_sum(blank);
-            if (CRF_X_CTCSUM) tot = wave_sum(tot);
-            if (lane == 0) { atomicAdd(&g[p.blank], blank); if (CRF_X_CTCSUM) atomicAdd(&gt[t & 3], tot + blank); }
+            if (lane == 0) atomicAdd(&g[p.blank], blank);
         }
 #pragma unroll
         for (int q = 0; q < kGCVRegs; ++q) {
             const int v = tid + q * kGCThreads;
             if (v < V) gz[v] = 0.f;
         }
-        if (CRF_X_CTCSUM && tid == 0) gt[(t + 2) & 3] = 0.f;
         sync_lds();
-        // The posteriors of a frame sum to ONE.  A frame whose scaled products do not -- the chains' rescaled fp64 rows lost the states that
-        // carry it, or Z itself is off -- is left out here and MARKED like the frames beyond the factor's range: the log-domain chains redo
-        // it (round 5: tests/test_gpu_fuzz.py found frames summing to 617, to inf and to 0 behind a finite, correct-looking cost).
-        const bool fbad = CRF_X_CTCSUM != 0 && zc > 0.0 && fc != 0.0 && !(fabsf(gt[t & 3] - 1.f) <= 1e-3f);
-        if (fbad && tid == 0) { p.ctc_bad[bt0 + t] = 1; atomicMax(&p.redo_ctc[b], 1); }
         float out[kGCVRegs];
 #pragma unroll
         for (int q = 0; q < kGCVRegs; ++q) {
             const int v = tid + q * kGCThreads;
-            out[q] = v < V ? (fbad ? rowc[q] : rowc[q] - p.c_ctc * g[v]) : 0.f;
+            out[q] = v < V ? rowc[q] - p.c_ctc * g[v] : 0.f;
         }
         // take the next frame's loads out of their registers BEFORE this frame's stores are issued (a
         // vmcnt wait behind the stores would also wait for their acknowledgement)

@@ -190,13 +190,11 @@ __device__ __forceinline__ void res_chain_body(const ResParams &p, float *lds, c
         char *Sb = (char *)(slot + eoff);
 #pragma unroll
         for (int c0 = 0; c0 < kResNCH; c0 += kResBatch) {
-#if CRF_X_PRIO
             // issue priority by progress through the frame's chunks, as in fac_chain_body (two waves per SIMD here: the older one used to run ahead)
             if (c0 == 0) __builtin_amdgcn_s_setprio(3);
             else if (c0 == 2 * kResBatch) __builtin_amdgcn_s_setprio(2);
             else if (c0 == 3 * kResBatch) __builtin_amdgcn_s_setprio(1);
             else if (c0 == 4 * kResBatch) __builtin_amdgcn_s_setprio(0);
-#endif
             if (c0 < nch_f) {
                 // Row epilogues: two dependent LDS reads (label, then e'[label]).  (Tried and measured
                 // slower, both of them: prefetching label and e' for ALL row ends of a batch ahead of the

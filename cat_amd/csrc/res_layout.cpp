@@ -128,7 +128,7 @@ bool place_rows_piece(const Rows &rows, const std::vector<int> &row_cu, int K, D
         // frame waits for the slowest wave.  Step 1: best-fit-decreasing finds a feasible packing (the
         // registers are ~97% full for the benchmark graph, so balance-first heuristics do not even fit).
         // Step 2: a deterministic annealing over single moves and pair swaps lowers the maximum wave cost.
-        const int kEpiCost = opt(kOpt_res_epi, 4);  // slice end, in chunks
+        const int kEpiCost = 4;  // slice end, in chunks
         std::vector<int> wave_of(nsl, -1), load(gm.waves, 0), cnt(gm.waves, 0);
         bool packed = true;
         for (int strategy = 0; strategy < 2; ++strategy) {   // (second try: best fit also where the slices per wave are limited -- tight bins)
@@ -150,16 +150,15 @@ bool place_rows_piece(const Rows &rows, const std::vector<int> &row_cu, int K, D
         std::vector<std::vector<int>> lists(gm.waves);
         std::vector<int> cost(gm.waves, 0);
         if (packed) {
-            const int kSimd0 = (gm.maxsl && K == 1) ? opt(kOpt_res_simd0, 0) : 0;
-            const int kEmisCost = opt(kOpt_res_emis, 8);   // (metric graph: 0 / 3 / 5 / 8 / 12 -> recursions 2.576 / 2.585 / 2.561 / 2.550 / 2.577 ms; V = 217: 2.690 -> 2.625: profiles/round5_ab_emission_waves.txt)
+            const int kEmisCost = 8;   // (metric graph: 0 / 3 / 5 / 8 / 12 -> recursions 2.576 / 2.585 / 2.561 / 2.550 / 2.577 ms; V = 217: 2.690 -> 2.625: profiles/round5_ab_emission_waves.txt)
             const int nem = (gm.maxsl && K == 1) ? std::min(g_emis_waves, gm.waves / 2) : 0;
             auto wcost = [&](int w) { return load[w] + kEpiCost * cnt[w] + (w < nem ? kEmisCost : 0); };
             // objective: (max cost, sum of squares) lexicographically, folded into one number
-            const bool by_simd = gm.maxsl && gm.waves % 4 == 0 && !opt_on(kOpt_res_no_simd_order);
+            const bool by_simd = gm.maxsl && gm.waves % 4 == 0;
             auto objective = [&]() {
                 int64_t mx = 0, sq = 0;
                 if (by_simd) {   // waves w, w + 4, w + 8 share a SIMD and take turns on it: what the frame waits for is the busiest SIMD
-                    int64_t g[4] = {kSimd0, 0, 0, 0};
+                    int64_t g[4] = {0, 0, 0, 0};
                     for (int w = 0; w < gm.waves; ++w) { const int64_t c = wcost(w); g[w & 3] += c; sq += c * c; }
                     for (int i = 0; i < 4; ++i) mx = std::max(mx, g[i]);
                     return mx * 1000000 + sq;
@@ -207,7 +206,7 @@ bool place_rows_piece(const Rows &rows, const std::vector<int> &row_cu, int K, D
                     for (int w = g; w < gm.waves; w += 4) ws.push_back(w);
                     // (round 5: the waves that stage emissions -- ids below nem -- come LAST in that order and so get the lightest lists: with
                     // issue priorities by progress the age of a wave matters less than the ~400 cycles its tail waits for the row stores)
-                    if (nem > 0 && kEmisCost > 0) std::stable_partition(ws.begin(), ws.end(), [&](int w) { return w >= nem; });
+                    if (nem > 0) std::stable_partition(ws.begin(), ws.end(), [&](int w) { return w >= nem; });
                     std::vector<int> order = ws;
                     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cost[a] - (a < nem ? kEmisCost : 0) > cost[b] - (b < nem ? kEmisCost : 0); });
                     std::vector<std::vector<int>> nl;
@@ -271,7 +270,7 @@ bool place_rows_piece(const Rows &rows, const std::vector<int> &row_cu, int K, D
                     // banks 0 and 16 only (measured by pack_arcs' model: extra LDS cycles per frame 1 919 -> see DESIGN).  Rotate.
                     const int gmask = (1 << lgs[j]) - 1;
                     bool first = r >= 0 && (lane & gmask) == 0;
-                    if (gm.maxsl && lgs[j] > 0 && r >= 0 && !opt_on(kOpt_res_owner_first)) {
+                    if (gm.maxsl && lgs[j] > 0 && r >= 0) {
                         if ((lane & gmask) == 0) { own_off = (nlong + (nlong >> lgs[j])) & gmask; ++nlong; }
                         first = (lane & gmask) == own_off;
                     }
@@ -300,8 +299,7 @@ static bool place_rows_sized(const Rows &rows, const std::vector<int> &row_cu, i
     bool any_long = false;
     if (gm.multilane)
         for (auto &r : rows) if (chunks_of(r.size()) > gm.nch) { any_long = true; break; }
-    const int piece_env = opt(kOpt_res_piece, 0);
-    if (!any_long || piece_env > 0) return place_rows_piece(rows, row_cu, K, o, slices, gm, piece_env > 0 ? std::min(piece_env, gm.nch) : half);
+    if (!any_long) return place_rows_piece(rows, row_cu, K, o, slices, gm, half);
     bool have = false;
     DirOut best;
     std::vector<SliceAt> best_slices;
@@ -320,7 +318,7 @@ bool place_rows(const Rows &rows, const std::vector<int> &row_cu, int K, DirOut 
     if (!place_rows_sized(rows, row_cu, K, o, slices, gm)) {
         // Eight waves of 30 chunks (the two-utterance kernel's geometry) pack worse than sixteen of 15: a row of 16 - 30 chunks fits a lane
         // and makes a slice as long as a whole wave.  Cut such rows too (pieces of half a lane and less), as the 1024-thread geometry has to.
-        if (!(gm.multilane && gm.maxsl && gm.nch >= 2 * kFac4NCH && opt(kOpt_res_piece, 0) <= 0)) return false;
+        if (!(gm.multilane && gm.maxsl && gm.nch >= 2 * kFac4NCH)) return false;
         bool have = false;
         for (int piece : {gm.nch / 2, gm.nch * 2 / 5, gm.nch / 3, gm.nch / 4}) {
             DirOut cand;
@@ -337,7 +335,7 @@ bool place_rows(const Rows &rows, const std::vector<int> &row_cu, int K, DirOut 
     // What a frame then costs is no longer the busiest SIMD's sum but one wave's serial chain (a batch of gathers is an LDS
     // round trip: ~70 cycles per chunk for a wave alone on its SIMD against ~49 per chunk of a saturated SIMD's sum,
     // tools/ubench_issue.py): compare max(5 x busiest SIMD, 7 x heaviest wave).
-    if (gm.multilane && K == 1 && opt(kOpt_res_piece, 0) <= 0 && !opt_on(kOpt_res_no_spread) && (int)slices->size() < gm.waves) {
+    if (gm.multilane && K == 1 && !opt_on(kOpt_res_no_spread) && (int)slices->size() < gm.waves) {
         auto frame_est = [](const DirOut &d) { return std::max<int64_t>((int64_t)d.simd_cost * kSpreadSimdWeight, (int64_t)d.est_cost * kSpreadWaveWeight); };
         int maxlen = 1;
         for (auto &r : rows) maxlen = std::max(maxlen, std::min(gm.nch, chunks_of(r.size())));
@@ -364,7 +362,6 @@ void arrange_grad_pairs(std::vector<int> *gq, std::vector<int> *gb, const std::v
     auto add = [](std::vector<int> (&bk)[32], int a) { auto &v = bk[a & 31]; if (std::find(v.begin(), v.end(), a) == v.end()) v.push_back(a); };
     auto cost_with = [](const std::vector<int> (&bk)[32], int a) { const auto &v = bk[a & 31]; return (int)v.size() + (std::find(v.begin(), v.end(), a) == v.end() ? 1 : 0); };
     *before = *after = 0;
-    const bool on = !opt_on(kOpt_no_grad_arrange);
     for (int c0 = 0; c0 < NC; c0 += 32) {                       // one half-wave: chunks [c0, c0 + 32)
         const int nl = std::min(32, NC - c0);
         std::vector<std::vector<std::pair<int, int>>> rem(nl);
@@ -389,7 +386,7 @@ void arrange_grad_pairs(std::vector<int> *gq, std::vector<int> *gb, const std::v
                 int bc = 1 << 30;
                 for (size_t i = 0; i < rem[l].size(); ++i) {
                     const int cq = cost_with(bq, rem[l][i].first), cb = cost_with(bb, rem[l][i].second);
-                    const int c = on ? std::max(cq, cb) * 64 + cq + cb : (int)i;
+                    const int c = std::max(cq, cb) * 64 + cq + cb;
                     if (c < bc) { bc = c; best = i; }
                 }
                 add(bq, rem[l][best].first); add(bb, rem[l][best].second);
@@ -419,7 +416,6 @@ void arrange_grad_pairs(std::vector<int> *gq, std::vector<int> *gb, const std::v
 // length) extra cycles -- 44 % on the benchmark graph; with a choice of two banks per arc nearly all of it goes.
 void pack_arcs(const Rows &rows, const std::vector<SliceAt> &slices, DirOut *o, int stride = 4, const Geom &gm = kGeomRes,
                int dup_n = 0, int dup_off = 0) {
-    const bool arrange = !opt_on(kOpt_no_bank_arrange);
     auto alt = [&](int idx) { return idx < 0 ? -1 : idx < dup_n ? idx + dup_off : (idx >= dup_off && idx < dup_off + dup_n) ? idx - dup_off : -1; };
     for (const SliceAt &sl : slices) {
         const int NI = sl.len * kResW;
@@ -433,161 +429,128 @@ void pack_arcs(const Rows &rows, const std::vector<SliceAt> &slices, DirOut *o, 
         // place[ins][lane] = arc (index, weight) or index -1
         std::vector<std::vector<std::pair<int, float>>> place(NI, std::vector<std::pair<int, float>>(kWave, {-1, 0.f}));
         std::vector<std::vector<int>> cnt(NI, std::vector<int>(2 * 32, 0));  // lanes per (half, bank)
-        if (!arrange) {
-            for (int ins = 0; ins < NI; ++ins)
-                for (int half = 0; half < 2; ++half) {
-                    int occupant[32];
-                    for (int b = 0; b < 32; ++b) occupant[b] = -1;
-                    int lanes[32];
-                    for (int l = 0; l < 32; ++l) lanes[l] = half * 32 + l;
-                    std::stable_sort(lanes, lanes + 32, [&](int a, int b) { return rem[a].size() < rem[b].size(); });
-                    for (int li = 0; li < 32; ++li) {
-                        const int lane = lanes[li];
-                        auto &rv = rem[lane];
-                        if (rv.empty()) continue;
-                        size_t best = 0;
-                        int best_cost = 1 << 30;
-                        bool best_alt = false;
-                        for (size_t q = 0; q < (arrange ? rv.size() : (size_t)1) && best_cost; ++q)
-                            for (int c = 0; c < 2; ++c) {
-                                const int idx = c ? alt(rv[q].first) : rv[q].first;
-                                if (idx < 0 || (c && !arrange)) continue;
-                                const int bank = idx & 31;
-                                const int cost = occupant[bank] == idx ? 0 : cnt[ins][half * 32 + bank];
-                                if (cost < best_cost) { best_cost = cost; best = q; best_alt = c != 0; if (!cost) break; }
-                            }
-                        if (best_alt) rv[best].first = alt(rv[best].first);
-                        place[ins][lane] = rv[best];
-                        const int bank = rv[best].first & 31;
-                        if (occupant[bank] != rv[best].first) cnt[ins][half * 32 + bank]++;
-                        if (occupant[bank] < 0) occupant[bank] = rv[best].first;
-                        rv.erase(rv.begin() + (long)best);
-                    }
+        // pass 1: per half-wave, (a) choose the copy of every arc so that the 32 banks carry equal numbers of
+        // this slice's gathers, (b) colour the bipartite multigraph lanes x banks with NI colours (Koenig: possible
+        // when no lane and no bank has more than NI edges; alternating-path recolouring) -- colour = position, so
+        // every gather is conflict-free -- and (c) put the edges of over-full banks into their lanes' free
+        // positions, the k-th surplus edge of every bank into the same positions where possible (a gather
+        // costs its BUSIEST bank: two banks with two addresses each cost one extra cycle, not two).
+        for (int half = 0; half < 2; ++half) {
+            struct Edge { int lane, idx, bank, col; float w; bool over; };
+            std::vector<Edge> ed;
+            int load[32] = {0};
+            for (int l = 0; l < 32; ++l)
+                for (auto &a : rem[half * 32 + l]) {
+                    Edge e{half * 32 + l, a.first, a.first & 31, -1, a.second, false};
+                    const int al = alt(e.idx);
+                    if (al >= 0 && load[al & 31] < load[e.bank]) { e.idx = al; e.bank = al & 31; }
+                    ++load[e.bank];
+                    ed.push_back(e);
                 }
-        } else {
-            // pass 1: per half-wave, (a) choose the copy of every arc so that the 32 banks carry equal numbers of
-            // this slice's gathers, (b) colour the bipartite multigraph lanes x banks with NI colours (Koenig: possible
-            // when no lane and no bank has more than NI edges; alternating-path recolouring) -- colour = position, so
-            // every gather is conflict-free -- and (c) put the edges of over-full banks into their lanes' free
-            // positions, the k-th surplus edge of every bank into the same positions where possible (a gather
-            // costs its BUSIEST bank: two banks with two addresses each cost one extra cycle, not two).
-            for (int half = 0; half < 2; ++half) {
-                struct Edge { int lane, idx, bank, col; float w; bool over; };
-                std::vector<Edge> ed;
-                int load[32] = {0};
-                for (int l = 0; l < 32; ++l)
-                    for (auto &a : rem[half * 32 + l]) {
-                        Edge e{half * 32 + l, a.first, a.first & 31, -1, a.second, false};
-                        const int al = alt(e.idx);
-                        if (al >= 0 && load[al & 31] < load[e.bank]) { e.idx = al; e.bank = al & 31; }
-                        ++load[e.bank];
-                        ed.push_back(e);
-                    }
-                // (a) balance: move one arc along a CHAIN of banks (an arc of bank u whose other copy is on bank v is
-                // an edge u -> v) from a bank to one that carries at least two fewer -- breadth-first, until no bank has one
-                for (int iter = 0; iter < 4096; ++iter) {
-                    int order[32];
-                    for (int b = 0; b < 32; ++b) order[b] = b;
-                    std::stable_sort(order, order + 32, [&](int x, int y) { return load[x] > load[y]; });
-                    bool moved = false;
-                    for (int oi = 0; oi < 32 && !moved; ++oi) {
-                        const int b0 = order[oi];
-                        int via[32];                              // edge (index into ed) that reached the bank
-                        for (int b = 0; b < 32; ++b) via[b] = -2;
-                        via[b0] = -1;
-                        std::vector<int> queue{b0};
-                        int found = -1;
-                        for (size_t qi = 0; qi < queue.size() && found < 0; ++qi) {
-                            const int u = queue[qi];
-                            for (size_t i = 0; i < ed.size() && found < 0; ++i) {
-                                if (ed[i].bank != u) continue;
-                                const int al = alt(ed[i].idx);
-                                if (al < 0) continue;
-                                const int v = al & 31;
-                                if (via[v] != -2) continue;
-                                via[v] = (int)i;
-                                if (load[v] + 2 <= load[b0]) found = v; else queue.push_back(v);
-                            }
+            // (a) balance: move one arc along a CHAIN of banks (an arc of bank u whose other copy is on bank v is
+            // an edge u -> v) from a bank to one that carries at least two fewer -- breadth-first, until no bank has one
+            for (int iter = 0; iter < 4096; ++iter) {
+                int order[32];
+                for (int b = 0; b < 32; ++b) order[b] = b;
+                std::stable_sort(order, order + 32, [&](int x, int y) { return load[x] > load[y]; });
+                bool moved = false;
+                for (int oi = 0; oi < 32 && !moved; ++oi) {
+                    const int b0 = order[oi];
+                    int via[32];                              // edge (index into ed) that reached the bank
+                    for (int b = 0; b < 32; ++b) via[b] = -2;
+                    via[b0] = -1;
+                    std::vector<int> queue{b0};
+                    int found = -1;
+                    for (size_t qi = 0; qi < queue.size() && found < 0; ++qi) {
+                        const int u = queue[qi];
+                        for (size_t i = 0; i < ed.size() && found < 0; ++i) {
+                            if (ed[i].bank != u) continue;
+                            const int al = alt(ed[i].idx);
+                            if (al < 0) continue;
+                            const int v = al & 31;
+                            if (via[v] != -2) continue;
+                            via[v] = (int)i;
+                            if (load[v] + 2 <= load[b0]) found = v; else queue.push_back(v);
                         }
-                        if (found < 0) continue;
-                        for (int v = found; v != b0;) {           // move one arc along every edge of the chain
-                            Edge &e = ed[via[v]];
-                            const int u = e.bank;
-                            --load[u]; e.idx = alt(e.idx); e.bank = e.idx & 31; ++load[e.bank];
-                            v = u;
-                        }
-                        moved = true;
                     }
-                    if (!moved) break;
-                }
-                for (int b = 0; b < 32; ++b) {                   // surplus edges of over-full banks
-                    int surplus = load[b] - NI;
-                    for (size_t i = ed.size(); i-- > 0 && surplus > 0;)
-                        if (ed[i].bank == b) { ed[i].over = true; --surplus; }
-                }
-                if (opt(kOpt_verbose, 0) >= 2) {
-                    int mx = 0, nover = 0, tot = 0; for (int b = 0; b < 32; ++b) { mx = std::max(mx, load[b]); tot += load[b]; }
-                    for (auto &e : ed) nover += e.over;
-                    int nalt = 0; for (auto &e : ed) nalt += alt(e.idx) >= 0;
-                    fprintf(stderr, "[pack] w%d c0=%d half %d: NI=%d edges=%d (avg/bank %.1f) max bank %d surplus %d with-alt %d\n", sl.w, sl.c0, half, NI, tot, tot / 32.0, mx, nover, nalt);
-                }
-                std::vector<int> lane_c((size_t)32 * NI, -1), bank_c((size_t)32 * NI, -1);   // edge at (node, colour)
-                auto LC = [&](int lane, int c) -> int & { return lane_c[(size_t)(lane & 31) * NI + c]; };
-                auto BC = [&](int bank, int c) -> int & { return bank_c[(size_t)bank * NI + c]; };
-                for (size_t i = 0; i < ed.size(); ++i) {         // (b)
-                    Edge &e = ed[i];
-                    if (e.over) continue;
-                    int a = -1, b = -1, both = -1;
-                    for (int c = 0; c < NI; ++c) {
-                        const bool fl = LC(e.lane, c) < 0, fb = BC(e.bank, c) < 0;
-                        if (fl && fb) { both = c; break; }
-                        if (fl && a < 0) a = c;
-                        if (fb && b < 0) b = c;
+                    if (found < 0) continue;
+                    for (int v = found; v != b0;) {           // move one arc along every edge of the chain
+                        Edge &e = ed[via[v]];
+                        const int u = e.bank;
+                        --load[u]; e.idx = alt(e.idx); e.bank = e.idx & 31; ++load[e.bank];
+                        v = u;
                     }
-                    if (both < 0) {
-                        // colour a is free at the lane, b at the bank: swap a <-> b along the path that starts with the
-                        // bank's a-edge (it cannot end in this lane, which has no a-edge), then a is free at both
-                        std::vector<int> path;
-                        int node = e.bank, col = a;
-                        bool at_bank = true;
-                        for (;;) {
-                            const int e2 = at_bank ? BC(node, col) : LC(node, col);
-                            if (e2 < 0) break;
-                            path.push_back(e2);
-                            node = at_bank ? ed[e2].lane : ed[e2].bank;
-                            at_bank = !at_bank;
-                            col = col == a ? b : a;
-                        }
-                        for (int e2 : path) { LC(ed[e2].lane, ed[e2].col) = -1; BC(ed[e2].bank, ed[e2].col) = -1; }
-                        for (int e2 : path) { ed[e2].col = ed[e2].col == a ? b : a; LC(ed[e2].lane, ed[e2].col) = e2; BC(ed[e2].bank, ed[e2].col) = e2; }
-                        both = a;
-                    }
-                    e.col = both;
-                    LC(e.lane, both) = (int)i;
-                    BC(e.bank, both) = (int)i;
+                    moved = true;
                 }
-                std::vector<int> extra(NI, 0);                   // (c): positions that already cost a second cycle
-                for (size_t i = 0; i < ed.size(); ++i) {
-                    Edge &e = ed[i];
-                    if (!e.over) continue;
-                    int best = -1, best_key = 1 << 30;
-                    for (int c = 0; c < NI; ++c) {
-                        if (LC(e.lane, c) >= 0) continue;
-                        int same = 0;                             // addresses already on this bank in position c
-                        for (size_t j = 0; j < ed.size(); ++j) if (ed[j].col == c && ed[j].bank == e.bank && ed[j].idx != e.idx) ++same;
-                        const int cost_after = std::max(extra[c], same);   // extra cycles of position c afterwards
-                        const int key = (cost_after - extra[c]) * 1024 + (extra[c] ? 0 : 1) * 32 + same;
-                        if (key < best_key) { best_key = key; best = c; }
-                    }
-                    if (best < 0) continue;                       // cannot happen: a lane has at most NI arcs
-                    int same = 0;
-                    for (size_t j = 0; j < ed.size(); ++j) if (ed[j].col == best && ed[j].bank == e.bank && ed[j].idx != e.idx) ++same;
-                    extra[best] = std::max(extra[best], same);
-                    e.col = best;
-                    LC(e.lane, best) = (int)i;
-                }
-                for (auto &e : ed) if (e.col >= 0) place[e.col][e.lane] = {e.idx, e.w};
+                if (!moved) break;
             }
+            for (int b = 0; b < 32; ++b) {                   // surplus edges of over-full banks
+                int surplus = load[b] - NI;
+                for (size_t i = ed.size(); i-- > 0 && surplus > 0;)
+                    if (ed[i].bank == b) { ed[i].over = true; --surplus; }
+            }
+            if (opt(kOpt_verbose, 0) >= 2) {
+                int mx = 0, nover = 0, tot = 0; for (int b = 0; b < 32; ++b) { mx = std::max(mx, load[b]); tot += load[b]; }
+                for (auto &e : ed) nover += e.over;
+                int nalt = 0; for (auto &e : ed) nalt += alt(e.idx) >= 0;
+                fprintf(stderr, "[pack] w%d c0=%d half %d: NI=%d edges=%d (avg/bank %.1f) max bank %d surplus %d with-alt %d\n", sl.w, sl.c0, half, NI, tot, tot / 32.0, mx, nover, nalt);
+            }
+            std::vector<int> lane_c((size_t)32 * NI, -1), bank_c((size_t)32 * NI, -1);   // edge at (node, colour)
+            auto LC = [&](int lane, int c) -> int & { return lane_c[(size_t)(lane & 31) * NI + c]; };
+            auto BC = [&](int bank, int c) -> int & { return bank_c[(size_t)bank * NI + c]; };
+            for (size_t i = 0; i < ed.size(); ++i) {         // (b)
+                Edge &e = ed[i];
+                if (e.over) continue;
+                int a = -1, b = -1, both = -1;
+                for (int c = 0; c < NI; ++c) {
+                    const bool fl = LC(e.lane, c) < 0, fb = BC(e.bank, c) < 0;
+                    if (fl && fb) { both = c; break; }
+                    if (fl && a < 0) a = c;
+                    if (fb && b < 0) b = c;
+                }
+                if (both < 0) {
+                    // colour a is free at the lane, b at the bank: swap a <-> b along the path that starts with the
+                    // bank's a-edge (it cannot end in this lane, which has no a-edge), then a is free at both
+                    std::vector<int> path;
+                    int node = e.bank, col = a;
+                    bool at_bank = true;
+                    for (;;) {
+                        const int e2 = at_bank ? BC(node, col) : LC(node, col);
+                        if (e2 < 0) break;
+                        path.push_back(e2);
+                        node = at_bank ? ed[e2].lane : ed[e2].bank;
+                        at_bank = !at_bank;
+                        col = col == a ? b : a;
+                    }
+                    for (int e2 : path) { LC(ed[e2].lane, ed[e2].col) = -1; BC(ed[e2].bank, ed[e2].col) = -1; }
+                    for (int e2 : path) { ed[e2].col = ed[e2].col == a ? b : a; LC(ed[e2].lane, ed[e2].col) = e2; BC(ed[e2].bank, ed[e2].col) = e2; }
+                    both = a;
+                }
+                e.col = both;
+                LC(e.lane, both) = (int)i;
+                BC(e.bank, both) = (int)i;
+            }
+            std::vector<int> extra(NI, 0);                   // (c): positions that already cost a second cycle
+            for (size_t i = 0; i < ed.size(); ++i) {
+                Edge &e = ed[i];
+                if (!e.over) continue;
+                int best = -1, best_key = 1 << 30;
+                for (int c = 0; c < NI; ++c) {
+                    if (LC(e.lane, c) >= 0) continue;
+                    int same = 0;                             // addresses already on this bank in position c
+                    for (size_t j = 0; j < ed.size(); ++j) if (ed[j].col == c && ed[j].bank == e.bank && ed[j].idx != e.idx) ++same;
+                    const int cost_after = std::max(extra[c], same);   // extra cycles of position c afterwards
+                    const int key = (cost_after - extra[c]) * 1024 + (extra[c] ? 0 : 1) * 32 + same;
+                    if (key < best_key) { best_key = key; best = c; }
+                }
+                if (best < 0) continue;                       // cannot happen: a lane has at most NI arcs
+                int same = 0;
+                for (size_t j = 0; j < ed.size(); ++j) if (ed[j].col == best && ed[j].bank == e.bank && ed[j].idx != e.idx) ++same;
+                extra[best] = std::max(extra[best], same);
+                e.col = best;
+                LC(e.lane, best) = (int)i;
+            }
+            for (auto &e : ed) if (e.col >= 0) place[e.col][e.lane] = {e.idx, e.w};
         }
         // pass 2: local search on the TRUE cost.  A half-wave gather takes as many LDS cycles as its busiest
         // bank has distinct addresses, so what counts is sum over (position, half) of that maximum -- not the
@@ -595,7 +558,7 @@ void pack_arcs(const Rows &rows, const std::vector<SliceAt> &slices, DirOut *o, 
         // spread over ten gathers cost ten).  Move: swap two arcs of one lane between two positions; accepted
         // if the two positions together get cheaper, or stay equal while the collisions shrink (plateau moves
         // that later allow a maximum to drop).  Deterministic order, bounded passes.
-        if (arrange) {
+        {
             auto half_cost = [&](int ins, int h, int *coll) {  // cycles of one half-wave gather, #colliding lanes
                 int n[32] = {0}, first[32], mx = 1, c = 0;
                 for (int l = 0; l < 32; ++l) {
@@ -1131,7 +1094,7 @@ static int build_factored_impl(HostGraph *h, int S, int P, const std::vector<int
     std::vector<int> entU(S, -1), ent(S, -1);   // entU: by main state; ent: a[s] itself (L, A or plain)
     // ... and a SECOND copy of the U entries (and the sink, which padding rows write) behind everything, on
     // other banks: [U][sink][L][A][plain] [pad] [U'][sink'] -- see pack_arcs
-    const int bank_shift = opt(kOpt_fac_bank_shift, 5) & 31;
+    const int bank_shift = 5;
     // second copy of the gathered entries: per direction (dup_mask bit 0 forward, bit 1 backward); a direction that turns out
     // not to fit with it clears its bit in *new_mask and the caller builds again
     const bool env_nodup = opt_on(kOpt_fac_no_dup);
@@ -1774,7 +1737,6 @@ int debug_emulate_factored(const HostGraph *h, int T, unsigned seed, double *out
                 }
                 tot += e[(size_t)t][(size_t)v] * sc;
             }
-        if (opt_on(kOpt_emu_verbose)) fprintf(stderr, "[emu] frame %d: pair-list mass %.12g, path mass %.12g\n", t, tot, out3[0]);
         if (!(std::fabs(tot - out3[0]) <= 1e-9 * std::fabs(out3[0]))) return fail("the grad pass's pair lists do not give the path mass at frame " + std::to_string(t));
     }
     return CRF_OK;

@@ -175,7 +175,7 @@ def version() -> str:
 
 
 def build_switches() -> Dict[str, int]:
-    """The CRF_X_* build-time switches of the loaded library (include/ctc_crf_hip.h crf_build_switches)."""
+    """The build-time geometry dials (and TIMING) of the loaded library (include/ctc_crf_hip.h crf_build_switches)."""
     return {k: int(v) for k, v in (kv.split("=") for kv in _lib.crf_build_switches().decode().split())}
 
 

@@ -359,8 +359,9 @@ const char *crf_last_side_stream(void);
  * or the pointer dangles.  The reference has no fallback: its log-domain kernels (den_calculate.cu:29-35) pay exp + log1p on every arc
  * instead. */
 int crf_last_fallback_counts(int32_t *out2, void *stream);
-/* The build-time A/B switches of the frame loops this library was compiled with, e.g. "LAG=1 KCLATE=0 PRIO=2 EARLY=1 ..." (crf_kernels.hip,
- * CRF_X_*: the defaults are the measured best; tools build variants with CRF_BUILD_DEFS=-DCRF_X_...=n and tests ask which one they run). */
+/* What can differ between two builds of this library: the geometry dials of the kernel instantiations as "NAME=value" pairs separated by
+ * blanks, e.g. "FAC4_NB=2 FAC4_NB_ML=2 ... GD_FRAMES=16" (NAME: the macro CRF_NAME of cat_amd/csrc, overridden with
+ * CRF_BUILD_DEFS=-DCRF_NAME=n), and "TIMING=1" in a timing build (-DCRF_TIMING). */
 const char *crf_build_switches(void);
 int crf_profile_read(float *ms_out, int n);
 

@@ -458,3 +458,17 @@ def test_debug_switches_are_set_by_name_not_from_the_environment(tmp_path):
     csrc = os.path.join(ROOT, "cat_amd", "csrc")
     src = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h", ".cpp")))
     assert "getenv" not in src
+    assert "CRF" + "_X_" not in src                                # (the settled build-time A/B switches: their names live on in docs/HISTORY.md only)
+
+
+def test_build_switches_report_the_geometry_dials():
+    """crf_build_switches(): what can still differ between two builds of these sources -- the nine geometry dials, each the NAME of an
+    `#ifndef CRF_NAME` in csrc, and TIMING=1 in a timing build."""
+    import re
+    import ctc_crf
+    sw = ctc_crf._C.build_switches()
+    csrc = os.path.join(ROOT, "cat_amd", "csrc")
+    src = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h", ".cpp")))
+    dials = set(re.findall(r"^#ifndef CRF_(\w+)", src, re.M))
+    assert set(sw) - {"TIMING"} <= dials, (sorted(sw), sorted(dials))
+    assert {"FAC4_NB", "FAC4_NB_ML", "FAC5_NB2", "FAC3_NB2", "FAC3_NB_F", "FAC3_NB_B", "FAC3L_NCH", "FAC4_NCH", "GD_FRAMES"} <= set(sw)

@@ -81,8 +81,8 @@ def transform_graph(g, path, seed=0, renumber=True, reorder=True, push=False):
 
 class crf_env:
     """``with crf_env(CRF_NO_FACTORED=1, CRF_BAT_UL=16): ...`` -- the library's debug switches (include/ctc_crf_hip.h
-    crf_debug_set; the library never reads the environment) under their historical upper-case names: CRF_X_Y is the switch
-    x_y.  Values are restored when the block ends."""
+    crf_debug_set; the library never reads the environment) under their historical upper-case names: CRF_NO_FACTORED is the switch
+    no_factored.  Values are restored when the block ends."""
 
     def __init__(self, **kw):
         self.kw = {k[4:].lower() if k.startswith("CRF_") else k: int(v) for k, v in kw.items()}

@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/build_ab.sh name:"-Ddefs" ... -- A/B builds of the library into cat_amd/lib_ab/lib<name>.so, in parallel (hipcc cross-compiles
 # without a GPU; ~45 s each, the kernel families compile in parallel).  `prod` as a name rebuilds the product library cat_amd/lib/libctc_crf_hip.so.
-#   tools/build_ab.sh prod lag0:"-DCRF_X_LAG=0" tm:"-DCRF_TIMING"
+#   tools/build_ab.sh prod nb3:"-DCRF_FAC4_NB=3" tm:"-DCRF_TIMING"
 mkdir -p cat_amd/lib_ab
 for v in "$@"; do
   n=${v%%:*}; d=""; case "$v" in *:*) d=${v#*:};; esac
