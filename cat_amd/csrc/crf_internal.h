@@ -247,7 +247,7 @@ struct GraphDev {
 };
 
 struct ResBuildStats { int K = 0; int64_t slots_f = 0, slots_b = 0, conflicts_f = 0, conflicts_b = 0; };
-struct FacBuildStats { int ok = 0; int64_t matched = 0, solo = 0, tail = 0, slots_f = 0, slots_b = 0, fused = 0, Gf = 0, Gb = 0; };
+struct FacBuildStats { int ok = 0; int64_t matched = 0, tail = 0, slots_f = 0, slots_b = 0, fused = 0, Gf = 0, Gb = 0; };
 
 // host tables of the factored streams (fst_graph.cpp build_batch_factored)
 struct FacRowH {
@@ -298,6 +298,7 @@ struct HostGraph {
     std::vector<StreamDev *> streams;   // one per (AL, tasks wanted) used so far
     FacBatchH fb;                       // factored rows of the utterance-minor kernels (T o LM graphs), see StreamDev
     FacHostCopy fh;                     // host copy of dev.fac's tables
+    int fac_geom_id = -1;               // which named geometry (res_layout.cpp: kFacGeoms) dev.fac was built on; -1: none (fac_geom_public)
     // A SECOND factored layout for the two-utterance kernel (crf_fac_pair2_kernel on 512 threads x 30 chunks, 256 VGPRs per wave): built next
     // to a 1024-thread main layout, taken by calls whose batch is larger than the one-utterance kernel's staged schedule holds
     // (crf_kernels.hip use_facp).  It has its own rows, entries and grad-pass lists, so a call works with one of the two throughout.
@@ -320,11 +321,11 @@ void set_error(const std::string &msg);
 #define CRF_OPTS(X)                                                                                                           \
     X(no_resident,      "G  no register-resident layout at all: the graph takes the utterance-minor or streaming kernels")   \
     X(no_factored,      "G  no factored layout: T o LM graphs take the generic register-resident layout")                    \
-    X(fac_rcl,          "G  factored layout: row constants in the LDS table (fac_geom 1) for every graph")                   \
-    X(fac_no_rcl,       "G  factored layout: row constants in registers even for graphs with long rows")                     \
-    X(fac_k2,           "G  factored layout over TWO CUs per recursion (fac_geom 3) for every T o LM graph")                 \
+    X(fac_rcl,          "G  factored layout: 1 = 768 threads x 20 chunks with the row constants in the LDS table (fac_geom 1), then x 21 chunks; 2 = x 21 chunks (fac_geom 1, fac_chunks 21) at once") \
+    X(fac_no_rcl,       "G  factored layout: 768 threads with the row constants in registers (fac_geom 0) even for graphs with long rows") \
+    X(fac_k2,           "G  factored layout over TWO CUs per recursion for every T o LM graph: 768-thread table geometry (fac_geom 3); with fac_threads = 1024 that geometry (fac_geom 5)") \
     X(fac_no_k2,        "G  never two CUs per recursion: graphs of 120 k - 240 k arcs take the generic layout")              \
-    X(fac_threads,      "G  512 / 768 / 1024: that geometry of the factored layout (default: 1024 threads first, then the 768-thread geometries, then 512)")                                            \
+    X(fac_threads,      "G  512 / 768 / 1024: that geometry of the factored layout (default: 1024 threads (fac_geom 4) first, then the 768-thread geometries (0, 1, 3), then 512 (2))") \
     X(fac_no_dup,       "G  factored layout: no second copy of the gathered entries")                                        \
     X(fac_addtid,       "G  factored layout, 1024 threads: the row epilogues store the next vector with 0 = ds_write_b32 / ds_write2st64_b32, 1 = ds_write_addtid_b32 (the default there)") \
     X(res_mink,         "G  generic layout: at least this many CUs per recursion")                                           \
@@ -386,11 +387,16 @@ int build_resident(HostGraph *h, int S, int P, const std::vector<int> &pair_dst,
                    const std::vector<std::vector<std::pair<int, float>>> &out_arcs_of_state,
                    const std::vector<float> &start_lin, const std::vector<float> &end_lin,
                    const std::vector<int> &label_sorted_pairs);
-// Builds the factored layout into h->dev.fac (fac.ok = 0 when the graph has no such structure or does not fit).
+// Cuts a label-sorted list (labels[i] = label of entry i) into chunks of at most `cap` entries within one label; returns their number
+// (both outputs null: counts only).  The grad-pass lists of every layout.
+int cut_label_chunks(const std::vector<int> &labels, int max_label, int cap, std::vector<int> *chunk_off, std::vector<int> *lab_chunk_off);
+// Builds the factored layout into h->dev.fac (fac.ok = 0 when the graph has no such structure or does not fit), and beside a
+// main layout that the two-utterance kernel does not take as it is, that kernel's own layout into h->facp.
 int build_factored(HostGraph *h, int S, int P, const std::vector<int> &pair_dst, const std::vector<int> &pair_lab,
                    const std::vector<std::vector<std::pair<int, float>>> &in_arcs_of_pair,
                    const std::vector<std::vector<std::pair<int, float>>> &out_arcs_of_state,
                    const std::vector<float> &start_lin, const std::vector<float> &end_lin);
+void fac_geom_public(const HostGraph *h, int64_t *fac_geom, int64_t *fac_chunks);   // crf_graph_stats: the built geometry's public numbers (-1 / 0: none)
 // Arc streams for UL (8, 16, 32 or 64) utterances per group cut into about `want` tasks per direction, built and uploaded
 // on first use (thread-safe; a graph keeps every variant it has been asked for).
 int debug_emulate_factored(const HostGraph *h, int T, unsigned seed, double *out3, int which = 0);   // which = 1: the two-utterance kernel's layout (HostGraph::facp)

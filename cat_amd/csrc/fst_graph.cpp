@@ -928,6 +928,24 @@ static bool regauge_pushed(int64_t S, int64_t A, const int32_t *src, const int32
     return true;
 }
 
+// Grad-pass lists are label-sorted and cut into chunks of at most `cap` entries within one label (labels[i]: the label of entry i):
+// chunk_off [NC + 1] = the chunks' ends, lab_chunk_off [max_label + 2] = the chunk range of each label.  Returns NC; with both
+// outputs null it only counts.
+int cut_label_chunks(const std::vector<int> &labels, int max_label, int cap, std::vector<int> *chunk_off, std::vector<int> *lab_chunk_off) {
+    const int n = (int)labels.size();
+    int nc = 0, r = 0;
+    if (chunk_off) { chunk_off->assign(1, 0); lab_chunk_off->assign((size_t)max_label + 2, 0); }
+    for (int v = 0; v <= max_label; ++v) {
+        if (chunk_off) (*lab_chunk_off)[(size_t)v] = nc;
+        int e = r;
+        while (e < n && labels[(size_t)e] == v) ++e;
+        for (int c = r; c < e; c += cap, ++nc) if (chunk_off) chunk_off->push_back(std::min(e, c + cap));
+        r = e;
+    }
+    if (chunk_off) (*lab_chunk_off)[(size_t)max_label + 1] = nc;
+    return nc;
+}
+
 int compile_graph(int64_t S, int64_t A, const int32_t *src, const int32_t *dst, const int32_t *lab,
                   const float *w_in, const float *start_in, const float *end_in, int device, HostGraph **out) {
     if (S <= 0 || S > INT32_MAX / 4 || A < 0 || A > INT32_MAX / 4) { set_error("graph size out of range"); return CRF_ERR_UNSUPPORTED; }
@@ -981,18 +999,9 @@ int compile_graph(int64_t S, int64_t A, const int32_t *src, const int32_t *dst, 
     perm.reserve(P);
     for (int r = 0; r < Pr; ++r) if (pair_dst[r] >= 0) perm.push_back(r);
     std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return pair_lab[a] < pair_lab[b]; });
-    std::vector<int> chunk_off{0}, lab_chunk_off((size_t)max_label + 2, 0);
-    {
-        size_t i = 0;
-        for (int v = 0; v <= max_label; ++v) {
-            lab_chunk_off[v] = (int)chunk_off.size() - 1;
-            size_t j = i;
-            while (j < perm.size() && pair_lab[perm[j]] == v) ++j;
-            for (size_t c = i; c < j; c += kChunk) chunk_off.push_back((int)std::min(j, c + kChunk));
-            i = j;
-        }
-        lab_chunk_off[(size_t)max_label + 1] = (int)chunk_off.size() - 1;
-    }
+    std::vector<int> chunk_off, lab_chunk_off, perm_lab;
+    for (int r : perm) perm_lab.push_back(pair_lab[r]);
+    cut_label_chunks(perm_lab, max_label, kChunk, &chunk_off, &lab_chunk_off);
     std::vector<int2> pair_meta(Pr);
     // label | (1 << 16) when the pair is the only one into its destination state (plain LDS store)
     for (int r = 0; r < Pr; ++r) {
@@ -1180,6 +1189,8 @@ int crf_graph_dims(const crf_graph *g, int64_t *S, int64_t *A, int64_t *P, int64
 int crf_graph_stats(const crf_graph *g, int64_t *out, int n) {
     if (!g || !g->h || !out) { crf::set_error("null argument"); return CRF_ERR_ARG; }
     const crf::HostGraph *h = g->h;
+    int64_t fac_geom, fac_chunks;
+    crf::fac_geom_public(h, &fac_geom, &fac_chunks);
     const int64_t v[27] = {h->S, h->A, h->P, h->dev.Pr, h->dev.Sr, h->fwd_padded_arcs, h->bwd_padded_arcs,
                            h->fwd_conflicts, h->bwd_conflicts, (int64_t)h->max_in_deg * 100000 + h->max_out_deg,
                            h->res_stats.K, h->res_stats.slots_f, h->res_stats.slots_b, h->res_stats.conflicts_f,
@@ -1187,8 +1198,7 @@ int crf_graph_stats(const crf_graph *g, int64_t *out, int n) {
                            h->fac_stats.ok, h->fac_stats.matched, (int64_t)h->regauged, h->fac_stats.tail,
                            h->fac_stats.slots_f, h->fac_stats.slots_b, h->fac_stats.fused,
                            h->fac_stats.Gf * 100000 + h->fac_stats.Gb,
-                           h->fac_stats.ok ? (h->dev.fac.threads == crf::kFac4Threads ? (h->dev.fac.K > 1 ? 5 : 4) : h->dev.fac.threads != crf::kFac3Threads ? 2 : h->dev.fac.K > 1 ? 3 : h->dev.fac.rcl ? 1 : 0) : -1,
-                           h->fac_stats.ok ? (h->dev.fac.threads == crf::kFac4Threads ? crf::kFac4NCH : h->dev.fac.threads != crf::kFac3Threads ? crf::kResNCH : h->dev.fac.rcl == 2 ? crf::kFac3LNCH : crf::kFac3ArcCh) : 0,
+                           fac_geom, fac_chunks,
                            h->facp.ok};
     for (int i = 0; i < n && i < 27; ++i) out[i] = v[i];
     return CRF_OK;

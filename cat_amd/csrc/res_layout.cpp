@@ -34,25 +34,6 @@ constexpr int kSpreadSimdWeight = 5, kSpreadWaveWeight = 7;
 // threshold sits between them; `fac_threads=768/1024` overrides.
 constexpr size_t kLongRowArcs = 20000, kLongRowShareDen = 5;
 constexpr Geom kGeomRes{kResThreads, kResWaves, kResNCH, kResWords, 0, 0};
-constexpr Geom kGeomFac512{kResThreads, kResWaves, kResNCH, kResWords, 0, 1};   // factored layout, 512 threads (row constants in LDS)
-constexpr Geom kGeomFac3{kFac3Threads, kFac3Threads / kWave, kFac3ArcCh, kFac3NCH * 6, kFac3MaxSl, 1};
-// ... and 768 threads with the row constants in an LDS table that the kernel reads one slice AHEAD (crf_kernels.hip, RL): any
-// number of slices per wave up to the ten that the 3-bit fields of wave_info.w hold -- graphs with many short rows (a den_lm
-// estimated from text: 4 000 rows = 63 slices at 100 k arcs) keep three waves per SIMD instead of falling to 512 threads
-constexpr Geom kGeomFac3L{kFac3Threads, kFac3Threads / kWave, kFac3ArcCh, kFac3ArcCh * 6, 10, 1};
-// ... the same with ALL 21 chunk slots holding arcs (no row constants in the 21st): 5 % more arc slots, which is what keeps a
-// 104 k-arc graph with a few rows of 150 - 500 arcs (V = 143 ... 500 classes) on ONE CU per recursion.  Tried only when the
-// 20-chunk table geometry does not take the graph: measured 0.13 - 0.3 us per frame slower on the graphs that fit both
-// (S = 513: 2.04 -> 2.52 ms, estimated S = 1 212: 2.04 -> 2.48 ms)
-constexpr Geom kGeomFac3L21{kFac3Threads, kFac3Threads / kWave, kFac3LNCH, kFac3LNCH * 6, 10, 1};
-
-// 1024 threads (four waves per SIMD at <= 128 VGPRs), 15 chunks of arcs per thread, row constants in the LDS table: as many arc
-// slots as 768 x 20, and as many registers per wave left beside the arcs (128 - 90 against 168 - 126)
-constexpr Geom kGeomFac4L{kFac4Threads, kFac4Threads / kWave, kFac4NCH, kFac4NCH * 6, 10, 1};
-// 512 threads x 30 chunks with the row constants in the LDS table and implicit entries: the TWO-UTTERANCE kernel's layout (level 6,
-// HostGraph::facp).  Two waves per SIMD own 256 registers each: 180 hold arcs, and what a second set of accumulators, 8-byte gather
-// results and two epilogues need fits beside them -- the 768-thread version of that kernel (168 registers) spilled 26 - 39 dwords.
-constexpr Geom kGeomFac512L{kResThreads, kResWaves, kResNCH, kResWords, 10, 1};
 
 struct DirOut {
     std::vector<unsigned> arcs;   // [K][kResWords][kResThreads]
@@ -70,14 +51,12 @@ inline int chunks_of(size_t deg) { return std::max(1, (int)((deg + kResW - 1) / 
 // Step 1: decide where every row lives (CU, wave, slice, lane) from the row LENGTHS only.
 struct SliceAt { int k, w, c0, len, rid0; std::vector<int> rows; int ord; int lg = 0; };   // ord: number of the slice within its wave;
                                                       // lg > 0: every row of the slice is cut into 2^lg pieces on 2^lg adjacent lanes
-// Waves [0, g_emis_waves) of a factored workgroup also stage the next frame's emission row (crf_kernels.hip fac_chain_body, `pre_w`): the
+// Waves [0, emis_waves) of a factored workgroup also stage the next frame's emission row (crf_kernels.hip fac_chain_body, `pre_w`): the
 // request at the frame top, and in the tail a wait for it that -- vmcnt counts in order -- includes the acknowledgement of the wave's own
 // write-through row stores, ~400 cycles in which that wave alone stands in front of the frame barrier (timing build, round 5: wave 0 arrived
 // 270 cycles behind every other wave of the forward recursion, 6 % of the frame).  The placement charges those waves kEmisCost chunks and
-// hands them the LIGHTEST slice list of their SIMD.  Set by build_factored around its place_rows calls (0: all waves alike).
-static thread_local int g_emis_waves = 0;
-
-bool place_rows_piece(const Rows &rows, const std::vector<int> &row_cu, int K, DirOut *o, std::vector<SliceAt> *slices, const Geom &gm, int piece, bool spread = false) {
+// hands them the LIGHTEST slice list of their SIMD.  The factored planner passes ceil(V / 64), build_resident 0 (all waves alike).
+bool place_rows_piece(const Rows &rows, const std::vector<int> &row_cu, int K, DirOut *o, std::vector<SliceAt> *slices, const Geom &gm, int emis_waves, int piece, bool spread = false) {
     o->arcs.assign((size_t)K * gm.words * gm.threads, 0u);
     o->wave_info.assign((size_t)K * gm.waves, uint4{0u, 0u, 0u, 0u});
     o->rid_of_row.assign(rows.size(), -1);
@@ -151,7 +130,7 @@ bool place_rows_piece(const Rows &rows, const std::vector<int> &row_cu, int K, D
         std::vector<int> cost(gm.waves, 0);
         if (packed) {
             const int kEmisCost = 8;   // (metric graph: 0 / 3 / 5 / 8 / 12 -> recursions 2.576 / 2.585 / 2.561 / 2.550 / 2.577 ms; V = 217: 2.690 -> 2.625: profiles/round5_ab_emission_waves.txt)
-            const int nem = (gm.maxsl && K == 1) ? std::min(g_emis_waves, gm.waves / 2) : 0;
+            const int nem = (gm.maxsl && K == 1) ? std::min(emis_waves, gm.waves / 2) : 0;
             auto wcost = [&](int w) { return load[w] + kEpiCost * cnt[w] + (w < nem ? kEmisCost : 0); };
             // objective: (max cost, sum of squares) lexicographically, folded into one number
             const bool by_simd = gm.maxsl && gm.waves % 4 == 0;
@@ -294,39 +273,27 @@ bool place_rows_piece(const Rows &rows, const std::vector<int> &row_cu, int K, D
 // per row: four rows per epilogue), long pieces mean fewer slices and fewer padding rows but may not pack at all.  The cost
 // model (chunks + kEpiCost per slice, busiest SIMD) follows the measured frame time closely (den_lm of 40 000 sentences:
 // model 1.40 x the benchmark graph's frame, measured 1.38 x), so try a few sizes and keep the cheapest packing.
-static bool place_rows_sized(const Rows &rows, const std::vector<int> &row_cu, int K, DirOut *o, std::vector<SliceAt> *slices, const Geom &gm) {
+// ... each piece size in turn: *o and *slices get the packing with the cheapest busiest SIMD (false, both untouched: none fits)
+static bool place_rows_cheapest(const Rows &rows, const std::vector<int> &row_cu, int K, DirOut *o, std::vector<SliceAt> *slices, const Geom &gm, int emis_waves, std::initializer_list<int> pieces, bool spread) {
+    bool have = false;
+    for (int piece : pieces) {
+        DirOut cand;
+        std::vector<SliceAt> cs;
+        if (!place_rows_piece(rows, row_cu, K, &cand, &cs, gm, emis_waves, piece, spread)) continue;
+        if (!have || cand.simd_cost < o->simd_cost) { *o = std::move(cand); *slices = std::move(cs); have = true; }
+    }
+    return have;
+}
+bool place_rows(const Rows &rows, const std::vector<int> &row_cu, int K, DirOut *o, std::vector<SliceAt> *slices, const Geom &gm, int emis_waves) {
     const int half = (gm.nch + 1) / 2;
     bool any_long = false;
     if (gm.multilane)
         for (auto &r : rows) if (chunks_of(r.size()) > gm.nch) { any_long = true; break; }
-    if (!any_long) return place_rows_piece(rows, row_cu, K, o, slices, gm, half);
-    bool have = false;
-    DirOut best;
-    std::vector<SliceAt> best_slices;
-    for (int piece : {gm.nch * 4 / 5, gm.nch * 7 / 10, gm.nch * 3 / 5, half}) {
-        DirOut cand;
-        std::vector<SliceAt> cs;
-        if (!place_rows_piece(rows, row_cu, K, &cand, &cs, gm, piece)) continue;
-        if (!have || cand.simd_cost < best.simd_cost) { best = std::move(cand); best_slices = std::move(cs); have = true; }
-    }
-    if (!have) return false;
-    *o = std::move(best);
-    *slices = std::move(best_slices);
-    return true;
-}
-bool place_rows(const Rows &rows, const std::vector<int> &row_cu, int K, DirOut *o, std::vector<SliceAt> *slices, const Geom &gm = kGeomRes) {
-    if (!place_rows_sized(rows, row_cu, K, o, slices, gm)) {
+    if (!(any_long ? place_rows_cheapest(rows, row_cu, K, o, slices, gm, emis_waves, {gm.nch * 4 / 5, gm.nch * 7 / 10, gm.nch * 3 / 5, half}, false)
+                   : place_rows_piece(rows, row_cu, K, o, slices, gm, emis_waves, half))) {
         // Eight waves of 30 chunks (the two-utterance kernel's geometry) pack worse than sixteen of 15: a row of 16 - 30 chunks fits a lane
         // and makes a slice as long as a whole wave.  Cut such rows too (pieces of half a lane and less), as the 1024-thread geometry has to.
-        if (!(gm.multilane && gm.maxsl && gm.nch >= 2 * kFac4NCH)) return false;
-        bool have = false;
-        for (int piece : {gm.nch / 2, gm.nch * 2 / 5, gm.nch / 3, gm.nch / 4}) {
-            DirOut cand;
-            std::vector<SliceAt> cs;
-            if (!place_rows_piece(rows, row_cu, K, &cand, &cs, gm, piece, true)) continue;
-            if (!have || cand.simd_cost < o->simd_cost) { *o = std::move(cand); *slices = std::move(cs); have = true; }
-        }
-        return have;
+        return gm.multilane && gm.maxsl && gm.nch >= 2 * kFac4NCH && place_rows_cheapest(rows, row_cu, K, o, slices, gm, emis_waves, {gm.nch / 2, gm.nch * 2 / 5, gm.nch / 3, gm.nch / 4}, true);
     }
     // (kSpreadSimdWeight / kSpreadWaveWeight, at the head of this file: the two cycle counts of the comparison below, in units of 10 cycles per chunk)
     // SMALL graphs (fewer slices than waves: most waves of the workgroup would have no rows at all while a few walk 10 - 15
@@ -343,7 +310,7 @@ bool place_rows(const Rows &rows, const std::vector<int> &row_cu, int K, DirOut 
             const int piece = std::max(2, (maxlen + div - 1) / div);
             DirOut cand;
             std::vector<SliceAt> cs;
-            if (!place_rows_piece(rows, row_cu, K, &cand, &cs, gm, piece, true)) continue;
+            if (!place_rows_piece(rows, row_cu, K, &cand, &cs, gm, emis_waves, piece, true)) continue;
             if (frame_est(cand) < frame_est(*o)) { *o = std::move(cand); *slices = std::move(cs); }
         }
     }
@@ -560,17 +527,16 @@ void pack_arcs(const Rows &rows, const std::vector<SliceAt> &slices, DirOut *o, 
         // that later allow a maximum to drop).  Deterministic order, bounded passes.
         {
             auto half_cost = [&](int ins, int h, int *coll) {  // cycles of one half-wave gather, #colliding lanes
-                int n[32] = {0}, first[32], mx = 1, c = 0;
+                int n[32] = {0}, mx = 1, c = 0;
                 for (int l = 0; l < 32; ++l) {
                     const int idx = place[ins][h + l].first;
                     if (idx < 0) continue;
                     const int bk = idx & 31;
-                    if (n[bk] == 0) { first[bk] = idx; n[bk] = 1; continue; }
+                    if (n[bk] == 0) { n[bk] = 1; continue; }
                     // distinct addresses per bank: count exactly (rows are short lists, 32 lanes)
                     bool seen = false;
                     for (int l2 = 0; l2 < l && !seen; ++l2) seen = place[ins][h + l2].first == idx;
                     if (!seen) { ++n[bk]; ++c; mx = std::max(mx, n[bk]); }
-                    (void)first;
                 }
                 if (coll) *coll = c;
                 return mx;
@@ -782,7 +748,7 @@ int build_resident(HostGraph *h, int S, int P, const std::vector<int> &pair_dst,
             std::vector<int> cu(sub.size());
             for (size_t r = 0; r < sub.size(); ++r) cu[r] = d.owner[subkey[r]];
             std::vector<SliceAt> slices;
-            if (!place_rows(sub, cu, K, &d.o, &slices)) {
+            if (!place_rows(sub, cu, K, &d.o, &slices, kGeomRes, 0)) {
                 if (attempt == 0) {
                     // For attempt 1: every CU has (rows mod 64) rows too many for full slices.  Split THOSE
                     // finely so they fill leftover register space instead of claiming a slice of their own --
@@ -883,7 +849,6 @@ int build_resident(HostGraph *h, int S, int P, const std::vector<int> &pair_dst,
         const DirOut &fo = F.o, &bo = Bk.o;
         const int NRf = (int)F.sub_of.size(), NRb = (int)Bk.sub_of.size();
         auto pair_of_sub = [&](int r) { return label_sorted_pairs[F.sub_of[r]]; };
-        (void)NRf;
 
         // ---- row metadata and side tables
         const int Rf = fo.cu_row_off[K], Rb = bo.cu_row_off[K];
@@ -922,23 +887,12 @@ int build_resident(HostGraph *h, int S, int P, const std::vector<int> &pair_dst,
             }
         // grad pass list: every (forward sub-row, backward sub-row of its dst state), label-sorted, cut into
         // chunks of <= kChunk entries within one label
-        std::vector<int> gq, gb, glabel, gchunk{0}, glab((size_t)max_lab + 2, 0);
+        std::vector<int> gq, gb, glabel, gchunk, glab;
         for (int r = 0; r < NRf; ++r) {
             const int p = pair_of_sub(r);
             for (int bs : bsubs_of[pair_dst[p]]) { gq.push_back(fo.rid_of_row[r]); gb.push_back(bo.rid_of_row[bs]); glabel.push_back(pair_lab[p]); }
         }
-        {
-            const int NL = (int)gq.size();
-            int r = 0;
-            for (int v = 0; v <= max_lab; ++v) {
-                glab[v] = (int)gchunk.size() - 1;
-                int e = r;
-                while (e < NL && glabel[e] == v) ++e;
-                for (int c = r; c < e; c += kChunk) gchunk.push_back(std::min(e, c + kChunk));
-                r = e;
-            }
-            glab[(size_t)max_lab + 1] = (int)gchunk.size() - 1;
-        }
+        cut_label_chunks(glabel, max_lab, kChunk, &gchunk, &glab);
         {
             int64_t gcb = 0, gca = 0;
             arrange_grad_pairs(&gq, &gb, gchunk, &gcb, &gca);
@@ -993,73 +947,128 @@ static std::vector<int> deal_rows(const Rows &rows, int K) {
     return cu;
 }
 
-static int build_factored_impl(HostGraph *h, int S, int P, const std::vector<int> &pair_dst, const std::vector<int> &pair_lab,
-                               const Rows &in_arcs_of_pair, const Rows &out_arcs_of_state, const std::vector<float> &start_lin,
-                               const std::vector<float> &end_lin, int level, bool *retry_next, int dup_mask, int *new_mask, bool short_only = false, bool *long_bail = nullptr, int K = 1) {
-    const bool second = level == 6;                          // the two-utterance kernel's layout: HostGraph::facp / fhp
-    FacDev &F = second ? h->facp : h->dev.fac;
-    F = FacDev{};
-    if (opt_on(kOpt_no_factored) || opt_on(kOpt_no_resident)) return CRF_OK;
-    const bool verbose = opt_on(kOpt_verbose);
-    auto give_up = [&](const char *why) { if (verbose) fprintf(stderr, "[fac_layout] not used: %s\n", why); return CRF_OK; };
-    // ---- precondition: every state is entered with at most one label (true for T o LM: a state of the
-    // composition remembers the last token), so "pair" and "destination state" are the same thing
-    std::vector<int> pair_of(S, -1);
+constexpr int kFacBankShift = 5;   // the second copy of the gathered entries starts at an entry = 5 mod 32: on other banks (pack_arcs)
+// The named geometries of the factored layout: everything the planner, the LDS budget and the statistics need to know of one.
+enum FacGeomId : int { kFg768Regs, kFg768Table, kFg768Table21, kFg1024Table, kFg512Rows, kFg512Pair2, kFacGeomCount };
+struct FacGeomDesc {
+    Geom gm;             // (maxsl: 3 = the row-constant registers; 10 = what the 3-bit fields of wave_info.w hold)
+    bool rc_regs;        // row constants in registers: two words per slice behind the arcs (else in LDS)
+    int rcl;             // FacDev::rcl.  != 0: in LDS they are the TABLE the kernel reads one slice ahead, with 64 rows of slack (2: all 21 chunk slots hold arcs)
+    bool implicit;       // the entries of a row lie where its row id says (FacDev::imp)
+    int esz;             // bytes per element of the state vectors and emission rows in the LDS budget (8: the two-utterance kernel's float2)
+    bool long_row_test;  // graphs with most arcs in rows longer than a lane are passed on (kLongRowArcs)
+    int frow_bytes;      // LDS bytes of row constants per forward row (a backward row: always 16)
+    int fac_geom, fac_geom_k2, fac_chunks;   // crf_graph_stats: `fac_geom` on one CU / on two CUs per recursion (-1: never planned), `fac_chunks`
+};
+constexpr FacGeomDesc kFacGeoms[kFacGeomCount] = {
+    // 768 threads (3 waves per SIMD at <= 168 VGPRs) x 20 chunks of arcs + the constants of up to 3 slices per wave in the 21st
+    /* kFg768Regs    */ {{kFac3Threads, kFac3Threads / kWave, kFac3ArcCh, kFac3NCH * 6, kFac3MaxSl, 1}, true, 0, true, 4, false, 16, 0, -1, kFac3ArcCh},
+    // ... with the table: any number of slices per wave -- graphs with many short rows (a den_lm estimated from text: 4 000 rows = 63 slices at
+    // 100 k arcs) keep three waves per SIMD instead of falling to 512 threads.  The geometry of two CUs per recursion.
+    /* kFg768Table   */ {{kFac3Threads, kFac3Threads / kWave, kFac3ArcCh, kFac3ArcCh * 6, 10, 1}, false, 1, true, 4, false, 8, 1, 3, kFac3ArcCh},
+    // ... with ALL 21 chunk slots holding arcs: 5 % more arc slots, which keeps a 104 k-arc graph with a few rows of 150 - 500 arcs (V = 143 ... 500)
+    // on ONE CU.  After the 20-chunk table: 0.13 - 0.3 us per frame slower on graphs that fit both (S = 513: 2.04 -> 2.52 ms, est. S = 1 212: 2.04 -> 2.48)
+    /* kFg768Table21 */ {{kFac3Threads, kFac3Threads / kWave, kFac3LNCH, kFac3LNCH * 6, 10, 1}, false, 2, true, 4, false, 8, 1, -1, kFac3LNCH},
+    // 1024 threads (four waves per SIMD at <= 128 VGPRs) x 15 chunks, table: as many arc slots as 768 x 20 and as many registers per wave left
+    // beside the arcs (128 - 90 against 168 - 126); measured 2 - 6 % faster on every graph that fits it: the planner's first choice
+    /* kFg1024Table  */ {{kFac4Threads, kFac4Threads / kWave, kFac4NCH, kFac4NCH * 6, 10, 1}, false, 1, true, 4, true, 8, 4, 5, kFac4NCH},
+    // 512 threads x 30 chunks, tabulated entries, 16-byte row descriptors in LDS: the fallback, last in every plan
+    /* kFg512Rows    */ {{kResThreads, kResWaves, kResNCH, kResWords, 0, 1}, false, 0, false, 4, false, 16, 2, -1, kResNCH},
+    // 512 x 30 with the table and implicit entries: the TWO-UTTERANCE kernel's own layout (HostGraph::facp).  Two waves per SIMD own 256 registers each:
+    // 180 hold arcs, and a second set of accumulators, 8-byte gather results and two epilogues fit beside them (at 768 threads it spilled 26 - 39 dwords)
+    /* kFg512Pair2   */ {{kResThreads, kResWaves, kResNCH, kResWords, 10, 1}, false, 1, true, 8, false, 8, -1, -1, kResNCH},
+};
+
+struct FacInput {   // the graph as compile_graph hands it over
+    int S, P;
+    const std::vector<int> &pair_dst, &pair_lab;
+    const Rows &in_arcs_of_pair, &out_arcs_of_state;
+    const std::vector<float> &start_lin, &end_lin;
+};
+static unsigned wbits(float w) { unsigned b; memcpy(&b, &w, 4); return b; }
+static bool verbose() { return opt_on(kOpt_verbose); }
+
+// One backward row: one state, or two matched states with common out-arcs `arcs` (pair, weight) and at most one extra arc each.
+struct BRow { int s0, s1; std::vector<std::pair<int, float>> arcs; int e0 = -1, e1 = -1; float w0 = 0.f, w1 = 0.f; };
+// What a graph's factored layout looks like before a geometry is chosen (analyse_factored): once per build_factored call.
+struct FacStructure {
+    const char *why = nullptr;                  // set: the graph has no factored layout, and why
+    int max_lab = 0, emis_waves = 0;            // emis_waves: waves that hold emissions at V = max label + 1, i.e. ceil(V / 64) (place_rows_piece)
+    std::vector<int> pair_of, mate, tail_of;    // state -> its pair / matched state / (main state ->) its tail state
+    std::vector<float> tail_w;
+    std::vector<char> is_tail, no_row;          // no_row: states that no arc enters
+    // forward rows over PROVISIONAL entries [U of every pair][sink][L of every pair][A of every pair][plain states]
+    std::vector<int> entU, ent, main_rows;      // entU: by main state; ent: a[s] itself (L, A or plain); main_rows: row -> pair
+    int nent = 0, nU = 0, sink = 0;
+    Rows fsub;
+    float bx_se = 0.f;
+    std::vector<BRow> brow;                     // fused, alternated and label-sorted: the order fixes the BP rows in memory
+    Rows bsub;                                  // their arcs over PAIR ids (lengths are all a placement needs)
+    std::vector<int> gchunk, glab;              // grad pass: chunks of the label-sorted pairs
+    int cap = kChunk;
+    int64_t nmatched = 0, ntail = 0, nfused = 0;   // statistics
+};
+
+static void analyse_factored(const FacInput &in, FacStructure *st) {
+    const int S = in.S, P = in.P;
+    const std::vector<int> &pair_dst = in.pair_dst, &pair_lab = in.pair_lab;
+    const Rows &in_arcs_of_pair = in.in_arcs_of_pair, &out_arcs_of_state = in.out_arcs_of_state;
+    auto give_up = [&](const char *why) { st->why = why; };
+    // ---- precondition: every state is entered with at most one label (T o LM: a state remembers the last token), so "pair" and "destination state" are one thing
+    std::vector<int> &pair_of = st->pair_of, &mate = st->mate, &tail_of = st->tail_of;
+    pair_of.assign(S, -1);
     for (int p = 0; p < P; ++p) {
         if (pair_of[pair_dst[p]] >= 0) return give_up("a state is entered with several labels");
         pair_of[pair_dst[p]] = p;
     }
-    auto wbits = [](float w) { unsigned b; memcpy(&b, &w, 4); return b; };
 
     // ---- 1. match states that feed the same rows with the same weights
-    std::vector<int> mate(S, -1);
-    {
-        std::vector<std::pair<uint64_t, int>> cand;  // (s1 << 32 | s2) -> count, via sort
-        std::vector<uint64_t> keys;
-        for (int p = 0; p < P; ++p) {
-            std::vector<std::pair<unsigned, int>> a;
-            for (auto &x : in_arcs_of_pair[p]) a.push_back({wbits(x.second), x.first});
-            std::sort(a.begin(), a.end());
-            for (size_t i = 0; i < a.size();) {
-                size_t j = i;
-                while (j < a.size() && a[j].first == a[i].first) ++j;
-                if (j - i >= 2 && j - i <= 64)
-                    for (size_t u = i; u < j; ++u)
-                        for (size_t v = u + 1; v < j; ++v)
-                            if (a[u].second != a[v].second)
-                                keys.push_back((uint64_t)std::min(a[u].second, a[v].second) << 32 | (unsigned)std::max(a[u].second, a[v].second));
-                i = j;
-            }
-        }
-        std::sort(keys.begin(), keys.end());
-        for (size_t i = 0; i < keys.size();) {
+    mate.assign(S, -1);
+    std::vector<std::pair<uint64_t, int>> cand;  // (s1 << 32 | s2) -> count, via sort
+    std::vector<uint64_t> keys;
+    for (int p = 0; p < P; ++p) {
+        std::vector<std::pair<unsigned, int>> a;
+        for (auto &x : in_arcs_of_pair[p]) a.push_back({wbits(x.second), x.first});
+        std::sort(a.begin(), a.end());
+        for (size_t i = 0; i < a.size();) {
             size_t j = i;
-            while (j < keys.size() && keys[j] == keys[i]) ++j;
-            cand.push_back({keys[i], (int)(j - i)});
+            while (j < a.size() && a[j].first == a[i].first) ++j;
+            if (j - i >= 2 && j - i <= 64)
+                for (size_t u = i; u < j; ++u)
+                    for (size_t v = u + 1; v < j; ++v)
+                        if (a[u].second != a[v].second)
+                            keys.push_back((uint64_t)std::min(a[u].second, a[v].second) << 32 | (unsigned)std::max(a[u].second, a[v].second));
             i = j;
         }
-        std::stable_sort(cand.begin(), cand.end(), [](const std::pair<uint64_t, int> &x, const std::pair<uint64_t, int> &y) { return x.second > y.second; });
-        for (auto &c : cand) {
-            const int s1 = (int)(c.first >> 32), s2 = (int)(c.first & 0xffffffffu);
-            if (c.second < 2) break;
-            if (mate[s1] < 0 && mate[s2] < 0) { mate[s1] = s2; mate[s2] = s1; }
-        }
+    }
+    std::sort(keys.begin(), keys.end());
+    for (size_t i = 0; i < keys.size();) {
+        size_t j = i;
+        while (j < keys.size() && keys[j] == keys[i]) ++j;
+        cand.push_back({keys[i], (int)(j - i)});
+        i = j;
+    }
+    std::stable_sort(cand.begin(), cand.end(), [](const std::pair<uint64_t, int> &x, const std::pair<uint64_t, int> &y) { return x.second > y.second; });
+    for (auto &c : cand) {
+        const int s1 = (int)(c.first >> 32), s2 = (int)(c.first & 0xffffffffu);
+        if (c.second < 2) break;
+        if (mate[s1] < 0 && mate[s2] < 0) { mate[s1] = s2; mate[s2] = s1; }
     }
     int64_t nmatched = 0;
     for (int s = 0; s < S; ++s) if (mate[s] > s) ++nmatched;
     if (nmatched * 4 < S) return give_up("fewer than half of the states pair up");
 
-    // ---- 2. forward: pair SUMS.  In T o LM the row of (g, blank) has exactly two in-arcs, from (g, blank) and
-    // (g, token), with one weight w: a_{t+1}[(g,blank)] = e'[blank] * w * (a_t[(g,blank)] + a_t[(g,token)]).
-    // So the recursion keeps, per matched pair (tail state s1 with such a row, main state s2), three entries:
+    // ---- 2. forward: pair SUMS.  In T o LM the row of (g, blank) has exactly two in-arcs, from (g, blank) and (g, token), with one weight w:
+    // a_{t+1}[(g,blank)] = e'[blank] * w * (a_t[(g,blank)] + a_t[(g,token)]).  So the recursion keeps, per matched pair (tail state s1 with such a
+    // row, main state s2), three entries:
     //     U = a[s1] + a[s2]   (what every other row reads of the pair: ONE gather, ONE weight for two arcs)
     //     L = a[s2], A = a[s1] (read by the few arcs that need one of them alone; logZ at the end)
-    // and the row of s2 updates all three in its epilogue: L' = e'[l2] * rowsum, A' = e'[l1] * w * U, U' = A' + L'
-    // (no subtraction anywhere) -- the row of s1 disappears.  A matched pair without that structure is
-    // un-matched again (generic graphs: everything below still works, there is just nothing to save).
-    const int max_lab = *std::max_element(pair_lab.begin(), pair_lab.end());
-    std::vector<int> tail_of(S, -1);   // main state -> its tail state
-    std::vector<float> tail_w(S, 0.f);
+    // and the row of s2 updates all three in its epilogue: L' = e'[l2] * rowsum, A' = e'[l1] * w * U, U' = A' + L' (no subtraction anywhere) -- the row
+    // of s1 disappears.  A matched pair without that structure is un-matched again (generic graphs: all of this still works, there is nothing to save).
+    st->max_lab = *std::max_element(pair_lab.begin(), pair_lab.end());
+    st->emis_waves = (st->max_lab + kWave) / kWave;
+    tail_of.assign(S, -1);
+    st->tail_w.assign(S, 0.f);
     for (int s = 0; s < S; ++s) {
         const int m = mate[s];
         if (m < 0 || m < s) continue;
@@ -1073,45 +1082,34 @@ static int build_factored_impl(HostGraph *h, int S, int P, const std::vector<int
             return true;
         };
         float w = 0.f;
-        if (pair_of[m] >= 0 && self_pair(s, m, &w)) { tail_of[m] = s; tail_w[m] = w; }
-        else if (pair_of[s] >= 0 && self_pair(m, s, &w)) { tail_of[s] = m; tail_w[s] = w; }
+        if (pair_of[m] >= 0 && self_pair(s, m, &w)) { tail_of[m] = s; st->tail_w[m] = w; }
+        else if (pair_of[s] >= 0 && self_pair(m, s, &w)) { tail_of[s] = m; st->tail_w[s] = w; }
         else { mate[s] = mate[m] = -1; }
     }
     nmatched = 0;
     for (int s = 0; s < S; ++s) if (tail_of[s] >= 0) ++nmatched;
     if (nmatched * 4 < S) return give_up("fewer than half of the states form (tail, main) pairs");
-    std::vector<char> is_tail(S, 0);
+    st->nmatched = nmatched;
+    std::vector<char> &is_tail = st->is_tail;
+    is_tail.assign(S, 0);
     for (int s = 0; s < S; ++s) if (tail_of[s] >= 0) is_tail[tail_of[s]] = 1;
-    // Geometry: 768 threads (3 waves per SIMD at <= 168 VGPRs; 20 chunks of arcs and the constants of up to 3 rows per
-    // thread) when both directions fit it, else 512 threads x 30 chunks (2 waves per SIMD); CRF_FAC_THREADS=512 forces
-    // the latter.
-    const bool lvl_table = level == 1 || level == 3 || level == 4 || level == 6;   // row constants in the LDS table: 20 chunks of arcs per thread (1) or 21 (3)
-    const Geom *gm = level == 0 ? &kGeomFac3 : level == 1 ? &kGeomFac3L : level == 3 ? &kGeomFac3L21 : level == 4 ? &kGeomFac4L : level == 6 ? &kGeomFac512L : &kGeomFac512;
-    const bool allow3 = level != 2 && level != 6; // a larger geometry is left to try
-    const bool rcregs = level == 0;               // row constants in registers
-    const bool implicit = gm->maxsl > 0;   // entries numbered by row id, row constants in registers (below)
-    // entries (512-thread layout): [U of every pair][sink][L of every pair][A of every pair][plain states]
-    std::vector<int> entU(S, -1), ent(S, -1);   // entU: by main state; ent: a[s] itself (L, A or plain)
-    // ... and a SECOND copy of the U entries (and the sink, which padding rows write) behind everything, on
-    // other banks: [U][sink][L][A][plain] [pad] [U'][sink'] -- see pack_arcs
-    const int bank_shift = 5;
-    // second copy of the gathered entries: per direction (dup_mask bit 0 forward, bit 1 backward); a direction that turns out
-    // not to fit with it clears its bit in *new_mask and the caller builds again
-    const bool env_nodup = opt_on(kOpt_fac_no_dup);
-    const bool no_dupf = !(dup_mask & 1) || env_nodup || K > 1, no_dupb = !(dup_mask & 2) || env_nodup || K > 1;   // (two CUs: one copy, the peers' entries are fetched into it)
-    *new_mask = dup_mask;
+    for (int s = 0; s < S; ++s) st->ntail += is_tail[s];
+    // provisional entries (the tabulated 512-thread layout keeps them; implicit geometries renumber them by row id once the rows are placed)
+    std::vector<int> &entU = st->entU, &ent = st->ent;
+    entU.assign(S, -1); ent.assign(S, -1);
     int nent = 0;
     for (int s = 0; s < S; ++s) if (tail_of[s] >= 0) entU[s] = nent++;
-    int nU = nent;
-    int sink = nent++;
+    st->nU = nent;
+    st->sink = nent++;
     for (int s = 0; s < S; ++s) if (tail_of[s] >= 0) ent[s] = nent++;
     for (int s = 0; s < S; ++s) if (tail_of[s] >= 0) ent[tail_of[s]] = nent++;
     for (int s = 0; s < S; ++s) if (ent[s] < 0) ent[s] = nent++;
-    const int64_t nsolo = 0;
+    st->nent = nent;
     // rows: every pair except the tail rows
-    std::vector<int> main_rows;
+    std::vector<int> &main_rows = st->main_rows;
     for (int p = 0; p < P; ++p) if (!is_tail[pair_dst[p]]) main_rows.push_back(p);
-    Rows fsub(main_rows.size());
+    Rows &fsub = st->fsub;
+    fsub.resize(main_rows.size());
     for (size_t i = 0; i < main_rows.size(); ++i) {
         std::vector<std::pair<int, float>> a = in_arcs_of_pair[main_rows[i]];
         std::vector<char> used(a.size(), 0);
@@ -1130,40 +1128,141 @@ static int build_factored_impl(HostGraph *h, int S, int P, const std::vector<int
             else fsub[i].push_back({ent[s], a[u].second});
         }
     }
-    if (level == 4) {
-        // 1024 threads: measured faster (2 - 6 %) on graphs whose rows fit a lane or nearly all do (V = 217 / 500: 3 - 8 % of the arcs
-        // in longer rows), SLOWER on den_lm estimated from text, where most arcs sit in rows of hundreds of arcs on many lanes
-        // (S = 3 006: 2.51 -> 2.64 ms per step, S = 6 836: 4.83 -> 5.26): those keep the 768-thread geometries
+
+    // ---- 3. backward rows: matched states with common out-arcs and at most one extra arc each share a row
+    std::vector<BRow> &brow = st->brow;
+    // States that no arc enters are never gathered: their b_t is needed once, at t = 0, for logZ of the backward recursion (costs_beta).  They get no
+    // row; the kernel adds start * sum_arcs w * z_0 after its last frame (bx list).  In T o LM that is the start state -- and with 2^k histories the row
+    // it does not take is the one that would have opened another slice of 64 rows for itself.
+    std::vector<char> &no_row = st->no_row;
+    no_row.assign(S, 0);
+    for (int s = 0; s < S; ++s)
+        if (pair_of[s] < 0 && mate[s] < 0) { no_row[s] = 1; st->bx_se += in.start_lin[s] * in.end_lin[s]; }
+    // ... and the states the forward matching left alone may still share a backward row (common out-arcs, at most one
+    // extra arc each): (history 0, blank) and (history 0, token) in T o LM, whose forward structure the start state spoils
+    std::vector<int> bmate = mate;
+    auto sorted_arcs = [&](int s) {
+        std::vector<std::pair<int, unsigned>> a;
+        for (auto &x : out_arcs_of_state[s]) a.push_back({x.first, wbits(x.second)});
+        std::sort(a.begin(), a.end());
+        return a;
+    };
+    std::vector<int> alone;
+    for (int s = 0; s < S; ++s) if (mate[s] < 0 && !no_row[s]) alone.push_back(s);
+    if (alone.size() <= 64)
+        for (size_t i = 0; i < alone.size(); ++i)
+            for (size_t j = i + 1; j < alone.size() && bmate[alone[i]] < 0; ++j) {
+                const int s = alone[i], m = alone[j];
+                if (bmate[m] >= 0) continue;
+                const std::vector<std::pair<int, unsigned>> a = sorted_arcs(s), b = sorted_arcs(m);
+                std::vector<std::pair<int, unsigned>> common;
+                std::set_intersection(a.begin(), a.end(), b.begin(), b.end(), std::back_inserter(common));
+                if (!common.empty() && a.size() - common.size() <= 1 && b.size() - common.size() <= 1) { bmate[s] = m; bmate[m] = s; }
+            }
+    std::vector<char> done(S, 0);
+    for (int s = 0; s < S; ++s) {
+        if (done[s] || no_row[s]) continue;
+        const int m = bmate[s];
+        bool fused = false;
+        if (m > s) {
+            const std::vector<std::pair<int, unsigned>> a = sorted_arcs(s), b = sorted_arcs(m);
+            std::vector<std::pair<int, unsigned>> common, ea, eb;
+            std::set_intersection(a.begin(), a.end(), b.begin(), b.end(), std::back_inserter(common));
+            std::set_difference(a.begin(), a.end(), common.begin(), common.end(), std::back_inserter(ea));
+            std::set_difference(b.begin(), b.end(), common.begin(), common.end(), std::back_inserter(eb));
+            if (ea.size() <= 1 && eb.size() <= 1 && !common.empty()) {
+                BRow r{s, m, {}, -1, -1, 0.f, 0.f};
+                for (auto &c : common) { float w; memcpy(&w, &c.second, 4); r.arcs.push_back({c.first, w}); }
+                if (!ea.empty()) { r.e0 = ea[0].first; memcpy(&r.w0, &ea[0].second, 4); }
+                if (!eb.empty()) { r.e1 = eb[0].first; memcpy(&r.w1, &eb[0].second, 4); }
+                // which of the two states is output 0 alternates: in a T o LM graph nearly all arcs enter the "token" state of a pair, and with a
+                // fixed order every gather would hit the entries of ONE output (under the BP rows' numbering 2*rid + output, which the z entries shared
+                // until the slices became planar: half of the LDS banks; the order also fixes the BP rows in memory, which the grad pass reads)
+                if (brow.size() & 1) { std::swap(r.s0, r.s1); std::swap(r.e0, r.e1); std::swap(r.w0, r.w1); }
+                brow.push_back(r);
+                done[s] = done[m] = 1; fused = true; ++st->nfused;
+            }
+        }
+        if (!fused) { brow.push_back(BRow{s, -1, out_arcs_of_state[s], -1, -1, 0.f, 0.f}); done[s] = 1; }
+    }
+    // Rows in label order (rows of equal length keep it through the placement): the 32 lanes of a half-wave then look up the emission of one or two
+    // labels in their epilogue -- a broadcast -- instead of up to 32 (bank conflicts).  The forward rows are pairs, which are label-sorted already.
+    auto key = [&](const BRow &r) {
+        const int l0 = pair_of[r.s0] >= 0 ? pair_lab[pair_of[r.s0]] : -1, l1 = (r.s1 >= 0 && pair_of[r.s1] >= 0) ? pair_lab[pair_of[r.s1]] : -1;
+        return std::max(l0, l1);
+    };
+    std::stable_sort(brow.begin(), brow.end(), [&](const BRow &a, const BRow &b) { return key(a) < key(b); });
+    st->bsub.resize(brow.size());
+    for (size_t i = 0; i < brow.size(); ++i) st->bsub[i] = brow[i].arcs;
+
+    // ---- 4. grad pass list: one (Q position, BP position) per pair, label-sorted (pairs already are), in chunks of at most `cap` entries within one
+    // label: kChunk = 32, or 8 when the labels have few pairs each (hundreds of classes over a graph of this size: V = 500 -> ~8 pairs per label): the grad
+    // kernel's threads walk every slot of a chunk, and chunks a quarter full spend most of their gathers on padding.  (8 only when the chunk count then fits 512 threads x 2.)
+    const int n32 = cut_label_chunks(pair_lab, st->max_lab, kChunk, nullptr, nullptr), n8 = cut_label_chunks(pair_lab, st->max_lab, 8, nullptr, nullptr);
+    if (n32 > 0 && (int64_t)P * 5 < (int64_t)n32 * kChunk * 2 && n8 <= 1024) st->cap = 8;   // chunks of 32 would be less than 40 % full
+    cut_label_chunks(pair_lab, st->max_lab, st->cap, &st->gchunk, &st->glab);
+    for (int p = 1; p < P; ++p) if (pair_lab[p] < pair_lab[p - 1]) return give_up("pairs are not label-sorted");
+}
+
+// ---- placement: one (geometry, K, second-copy mask) on a const structure --------------------------------------------
+enum class Fit { kBuilt, kNextGeometry, kGiveUp, kLessDup };   // kLessDup: build again with Placed::dup_mask (place_factored keeps that to itself)
+struct Placed { Fit fit = Fit::kBuilt; int dup_mask = 0; bool long_bail = false; int rc = CRF_OK; };   // long_bail: a short-rows-only attempt met a long row
+struct Attempt {
+    const FacGeomDesc &g;
+    int K;                    // CUs per recursion
+    bool short_only, more;    // short_only: graphs with rows longer than a lane's registers go on to the next geometry; more: a larger geometry is left
+                              // to try (the plan position), so "does not fit" means "next", not "give up"
+    int dup_mask;             // second copy of the gathered entries: bit 0 forward, bit 1 backward
+};
+static Placed gave_up(const char *why) { if (verbose()) fprintf(stderr, "[fac_layout] not used: %s\n", why); return {Fit::kGiveUp}; }
+static Placed next_or_give_up(const Attempt &at, const char *why) { return at.more ? Placed{Fit::kNextGeometry} : gave_up(why); }
+
+// The rows of one direction onto the geometry: first the two tests on row lengths that pass a graph on before anything is placed.
+static Placed place_dir(const Rows &rows, const FacStructure &st, const Attempt &at, bool forward, DirOut *o, std::vector<SliceAt> *slices) {
+    const int nch = at.g.gm.nch;
+    if (at.g.long_row_test) {   // (kLongRowArcs, at the head of this file; the backward rows decide like the forward ones)
         size_t long_arcs = 0, all_arcs = 0;
-        for (auto &r : fsub) { all_arcs += r.size(); if (chunks_of(r.size()) > gm->nch) long_arcs += r.size(); }
-        if (opt_on(kOpt_verbose)) fprintf(stderr, "[fac_layout] 1024 threads: %zu of %zu forward arcs in rows longer than a lane\n", long_arcs, all_arcs);
-        // (round 4, with issue priorities by progress: S = 3 006 -- 14.9 k of 20.5 k forward arcs in such rows -- is now FASTER on 1024
-        // threads, recursions 2.28 -> 2.13 ms; S = 6 836 -- 27.3 k of 49.0 k -- still slower, 3.41 -> 3.51: the share alone does not
-        // decide, the number of multi-lane slices a wave has to finish per frame does)
-        if (opt(kOpt_fac_threads, 0) != 1024 && long_arcs * kLongRowShareDen > all_arcs && long_arcs > kLongRowArcs) { *retry_next = true; return CRF_OK; }
+        for (auto &r : rows) { all_arcs += r.size(); if (chunks_of(r.size()) > nch) long_arcs += r.size(); }
+        if (forward && verbose()) fprintf(stderr, "[fac_layout] 1024 threads: %zu of %zu forward arcs in rows longer than a lane\n", long_arcs, all_arcs);
+        if (opt(kOpt_fac_threads, 0) != 1024 && long_arcs * kLongRowShareDen > all_arcs && long_arcs > kLongRowArcs) return {Fit::kNextGeometry};
     }
-    if (short_only)   // graphs with rows longer than a lane's registers (every den_lm estimated from text) run 2-3 % faster with the
-        for (auto &r : fsub)   // row constants in the LDS table (level 1; measured): leave them to it
-            if (chunks_of(r.size()) > gm->nch) { if (long_bail) *long_bail = true; *retry_next = true; return CRF_OK; }
-    struct EmisGuard { ~EmisGuard() { g_emis_waves = 0; } } emis_guard;   // (reset on every way out of this function)
-    g_emis_waves = (max_lab + kWave) / kWave;                            // waves that hold emissions at V = max label + 1, i.e. ceil(V / 64): place_rows_piece
-    DirOut fo;
+    if (at.short_only)   // graphs with rows longer than a lane's registers (every den_lm estimated from text) run 2-3 % faster with the
+        for (auto &r : rows)   // row constants in the LDS table (kFg768Table; measured): leave them to it
+            if (chunks_of(r.size()) > nch) return {Fit::kNextGeometry, 0, true};
+    if (!place_rows(rows, deal_rows(rows, at.K), at.K, o, slices, at.g.gm, st.emis_waves))
+        return next_or_give_up(at, forward ? "forward rows do not fit one CU" : "backward rows do not fit one CU");   // (next: both directions then use the larger budget)
+    return {};
+}
+
+// What one attempt has placed so far: the tables (as the host copy keeps them) and, per direction, rows / entries between the two copies
+// (0: one copy) / gather-vector entries.
+struct FacPlaced {
+    FacHostCopy C;
+    struct Dir { DirOut o; int R = 0, dup = 0, G = 0; } f, b;
+    int xlist_off[3] = {0, 0, 0};       // two CUs: C.xlist holds the entries CU 0 fetches, then those CU 1 fetches
+    std::vector<int> fpos, zpos;        // pair -> position in the Q row (main rows [0, Rf), their tails [Rf, 2 Rf)); state -> BP position 2 * rid + output
+};
+static Placed place_forward(const FacInput &in, const FacStructure &st, const Attempt &at, FacPlaced *pl) {
+    const Geom &gm = at.g.gm;
+    const int S = in.S, K = at.K;
+    const std::vector<int> &tail_of = st.tail_of, &main_rows = st.main_rows;
+    FacHostCopy &C = pl->C;
+    DirOut &fo = pl->f.o;
     std::vector<SliceAt> fslices;
-    if (!place_rows(fsub, deal_rows(fsub, K), K, &fo, &fslices, *gm)) {
-        if (allow3) { *retry_next = true; return CRF_OK; }
-        return give_up("forward rows do not fit one CU");
-    }
-    const int Rf = fo.cu_row_off[(size_t)K];
-    if (implicit) {
-        // 768-thread layout: the entries of a row are where its row id says -- U at rid, L at Rf + rid, A at 2 Rf + rid
-        // (then the states nobody enters, a zero entry for padding gathers, and the second copy of the U entries) -- so
-        // a row epilogue needs no table to find them: what is left of the row constants (two labels, the tail weight)
-        // lives in two registers per slice.  The epilogue was a chain of three LDS round trips (constants -> the
-        // values they point to -> emissions), 70 % of the frame loop in the timing build.
+    const Placed placed = place_dir(st.fsub, st, at, true, &fo, &fslices);
+    if (placed.fit != Fit::kBuilt) return placed;
+    const int Rf = pl->f.R = fo.cu_row_off[(size_t)K];
+    Rows fsub = st.fsub;
+    std::vector<int> entU = st.entU, ent = st.ent;
+    int sink = st.sink, nent = st.nent, nU = st.nU;
+    if (at.g.implicit) {
+        // the entries of a row are where its row id says -- U at rid, L at Rf + rid, A at 2 Rf + rid (then the states nobody enters, a zero entry for
+        // padding gathers, and the second copy of the U entries) -- so a row epilogue needs no table to find them: what is left of the row constants
+        // is two labels and the tail weight (with a table of entries the epilogue was a chain of three LDS round trips, 70 % of the frame loop)
         std::vector<int> remap(nent, -1);
         std::vector<int> nentU(S, -1), nentS(S, -1);
         for (size_t r = 0; r < main_rows.size(); ++r) {
-            const int rid = fo.rid_of_row[r], s = pair_dst[main_rows[r]];
+            const int rid = fo.rid_of_row[r], s = in.pair_dst[main_rows[r]];
             nentS[s] = Rf + rid;
             if (tail_of[s] >= 0) { nentU[s] = rid; nentS[tail_of[s]] = 2 * Rf + rid; }
         }
@@ -1175,21 +1274,23 @@ static int build_factored_impl(HostGraph *h, int S, int P, const std::vector<int
         for (auto &row : fsub) for (auto &a : row) a.first = remap[a.first];
         ent = nentS; entU = nentU; sink = nsink; nent = nx; nU = Rf;
     }
-    int fdup = 0;                                        // entries between the two copies
-    if (!no_dupf) { fdup = nent; while ((fdup & 31) != bank_shift) ++fdup; }
+    // ... and a SECOND copy of the U entries (and the sink, which padding rows write) behind everything, on
+    // other banks: [U][sink][L][A][plain] [pad] [U'][sink'] -- see pack_arcs.  (Two CUs: one copy, the peers' entries are fetched into it.)
+    const bool no_dup = !(at.dup_mask & 1) || opt_on(kOpt_fac_no_dup) || K > 1;
+    int fdup = 0;
+    if (!no_dup) { fdup = nent; while ((fdup & 31) != kFacBankShift) ++fdup; }
     const int Gf = fdup ? fdup + nU + 1 : nent;
+    pl->f.dup = fdup; pl->f.G = Gf;
     if ((size_t)Gf * 4 > 65536) {
-        if (!no_dupf) { *new_mask = dup_mask & ~1; return CRF_OK; }   // first without the second copy of the U entries
-        if (allow3) { *retry_next = true; return CRF_OK; }
-        return give_up("forward gather vector > 64 KiB");
+        if (!no_dup) return {Fit::kLessDup, at.dup_mask & ~1};   // first without the second copy of the U entries
+        return next_or_give_up(at, "forward gather vector > 64 KiB");
     }
-    pack_arcs(fsub, fslices, &fo, 4, *gm, fdup ? nU : 0, fdup);
+    pack_arcs(fsub, fslices, &fo, 4, gm, fdup ? nU : 0, fdup);
     // two CUs: the U entries cross every frame as one contiguous range per CU; of the L and A entries (and the plain states, which
     // sit in the L range) only those that a row of the OTHER CU gathers -- in T o LM the L entry of a couple is read by its own
     // row alone (the token's self-loop) -- as a list per CU; everything once more after the last frame, for logZ.
-    std::vector<int> xlist;                      // entries CU 0 fetches, then those CU 1 fetches
-    int xlist_off[3] = {0, 0, 0};
-    if (K > 1 && implicit) {
+    std::vector<int> &xlist = C.xlist;
+    if (K > 1 && at.g.implicit) {
         auto cu_of_rid = [&](int rid) { int k = 0; while (k + 1 < K && rid >= fo.cu_row_off[(size_t)k + 1]) ++k; return k; };
         std::vector<std::vector<int>> need((size_t)K);
         for (size_t r = 0; r < fsub.size(); ++r) {
@@ -1203,361 +1304,267 @@ static int build_factored_impl(HostGraph *h, int S, int P, const std::vector<int
             auto &v = need[(size_t)k];
             std::sort(v.begin(), v.end());
             v.erase(std::unique(v.begin(), v.end()), v.end());
-            xlist_off[k] = (int)xlist.size();
+            pl->xlist_off[k] = (int)xlist.size();
             xlist.insert(xlist.end(), v.begin(), v.end());
         }
-        xlist_off[2] = (int)xlist.size();
-        if (verbose) fprintf(stderr, "[fac_layout] two CUs: of %d L / A entries per CU, CU 0 fetches %d and CU 1 %d every frame\n", 2 * (Rf / K), xlist_off[1] - xlist_off[0], xlist_off[2] - xlist_off[1]);
+        pl->xlist_off[2] = (int)xlist.size();
+        if (verbose()) fprintf(stderr, "[fac_layout] two CUs: of %d L / A entries per CU, CU 0 fetches %d and CU 1 %d every frame\n", 2 * (Rf / K), pl->xlist_off[1] - pl->xlist_off[0], pl->xlist_off[2] - pl->xlist_off[1]);
     }
     if (xlist.empty()) xlist.push_back(0);
-    const int NT = 0;
-    std::vector<int> fpos(P, -1);   // position of pair p in the Q row: main rows [0, Rf), their tails [Rf, 2 Rf)
-    std::vector<int4> frow_meta(Rf, int4{sink * 4, (sink * 4) | ((sink * 4) << 16), 0, 0});   // padding rows: all to the sink
+    pl->fpos.assign(in.P, -1);
+    std::vector<int4> &frow_meta = C.frow_meta;
+    frow_meta.assign(Rf, int4{sink * 4, (sink * 4) | ((sink * 4) << 16), 0, 0});   // padding rows: all to the sink
     for (int rid = 0; rid < Rf; ++rid) {
         const int r = fo.row_of[rid];
         if (r < 0) continue;
-        const int p = main_rows[r], s = pair_dst[p];
-        fpos[p] = rid;
+        const int p = main_rows[r], s = in.pair_dst[p];
+        pl->fpos[p] = rid;
         if (tail_of[s] >= 0) {
-            const int t = tail_of[s], pt = pair_of[t];
-            fpos[pt] = Rf + rid;
-            frow_meta[rid] = int4{(entU[s] * 4) | (pair_lab[p] << 16), (ent[s] * 4) | ((ent[t] * 4) << 16), (int)wbits(tail_w[s]), pair_lab[pt]};
+            const int t = tail_of[s], pt = st.pair_of[t];
+            pl->fpos[pt] = Rf + rid;
+            frow_meta[rid] = int4{(entU[s] * 4) | (in.pair_lab[p] << 16), (ent[s] * 4) | ((ent[t] * 4) << 16), (int)wbits(st.tail_w[s]), in.pair_lab[pt]};
         } else {
-            frow_meta[rid] = int4{(sink * 4) | (pair_lab[p] << 16), (ent[s] * 4) | ((sink * 4) << 16), 0, 0};
+            frow_meta[rid] = int4{(sink * 4) | (in.pair_lab[p] << 16), (ent[s] * 4) | ((sink * 4) << 16), 0, 0};
         }
     }
-    if (rcregs)   // row constants of the slice number `ord` of a wave: words (kFac3ArcCh * 6 + 2 * ord) and the next of its threads
+    if (at.g.rc_regs)   // row constants of the slice number `ord` of a wave: words (kFac3ArcCh * 6 + 2 * ord) and the next of its threads
         for (const SliceAt &sl : fslices)
             for (int lane = 0; lane < kWave; ++lane) {
                 const int rid = sl.rid0 + lane, r = fo.row_of[rid];
                 if (r < 0) continue;
                 const int4 m = frow_meta[rid];
                 const size_t t = (size_t)sl.w * kWave + lane, w0 = (size_t)kFac3ArcCh * 6 + 2 * (size_t)sl.ord;
-                fo.arcs[w0 * gm->threads + t] = (((unsigned)m.x >> 16) * 4u) | (((unsigned)m.w * 4u) << 16);   // BYTE offsets of the two emissions: main label * 4 | tail label * 4 << 16
-                fo.arcs[(w0 + 1) * gm->threads + t] = (unsigned)m.z;                             // tail weight (0: no tail)
+                fo.arcs[w0 * gm.threads + t] = (((unsigned)m.x >> 16) * 4u) | (((unsigned)m.w * 4u) << 16);   // BYTE offsets of the two emissions: main label * 4 | tail label * 4 << 16
+                fo.arcs[(w0 + 1) * gm.threads + t] = (unsigned)m.z;                             // tail weight (0: no tail)
             }
-    const int Rq = 2 * Rf;
-    std::vector<float> x_start(Gf, 0.f), x_end(Gf, 0.f);
+    C.x_start.assign(Gf, 0.f); C.x_end.assign(Gf, 0.f);
     for (int s = 0; s < S; ++s) {
-        x_start[ent[s]] = start_lin[s];
-        x_end[ent[s]] = end_lin[s];
-        if (tail_of[s] >= 0) x_start[entU[s]] = start_lin[s] + start_lin[tail_of[s]];
+        C.x_start[ent[s]] = in.start_lin[s];
+        C.x_end[ent[s]] = in.end_lin[s];
+        if (tail_of[s] >= 0) C.x_start[entU[s]] = in.start_lin[s] + in.start_lin[tail_of[s]];
     }
-    if (fdup) for (int u = 0; u < nU; ++u) x_start[fdup + u] = x_start[u];   // (implicit layout: nU = Rf, unused U slots are 0)
-    std::vector<int4> ftail(1, int4{0, 0, 0, 0});
-    std::vector<int> tail_rows;   // (statistics only)
-    for (int s = 0; s < S; ++s) if (is_tail[s]) tail_rows.push_back(s);
+    if (fdup) for (int u = 0; u < nU; ++u) C.x_start[fdup + u] = C.x_start[u];   // (implicit layout: nU = Rf, unused U slots are 0)
+    return {};
+}
 
-    // ---- 4. backward rows: matched states with common out-arcs and at most one extra arc each share a row
-    struct BRow { int s0, s1; std::vector<std::pair<int, float>> arcs; int e0 = -1, e1 = -1; float w0 = 0.f, w1 = 0.f; };  // arcs: (pair, w)
-    std::vector<BRow> brow;
-    int64_t nfused = 0;
-    // States that no arc enters are never gathered: their b_t is needed once, at t = 0, for logZ of the backward
-    // recursion (costs_beta).  They get no row; the kernel adds start * sum_arcs w * z_0 after its last frame (bx list).
-    // In T o LM that is the start state -- and with 2^k histories the row it does not take is the one that would have
-    // opened another slice of 64 rows for itself.
-    std::vector<int> bx_idx;
-    std::vector<float> bx_w;
-    float bx_se = 0.f;
-    std::vector<char> no_row(S, 0);
-    for (int s = 0; s < S; ++s)
-        if (pair_of[s] < 0 && mate[s] < 0) { no_row[s] = 1; bx_se += start_lin[s] * end_lin[s]; }
-    // ... and the states the forward matching left alone may still share a backward row (common out-arcs, at most one
-    // extra arc each): (history 0, blank) and (history 0, token) in T o LM, whose forward structure the start state spoils
-    std::vector<int> bmate = mate;
-    {
-        std::vector<int> alone;
-        for (int s = 0; s < S; ++s) if (mate[s] < 0 && !no_row[s]) alone.push_back(s);
-        if (alone.size() <= 64)
-            for (size_t i = 0; i < alone.size(); ++i)
-                for (size_t j = i + 1; j < alone.size() && bmate[alone[i]] < 0; ++j) {
-                    const int s = alone[i], m = alone[j];
-                    if (bmate[m] >= 0) continue;
-                    std::vector<std::pair<int, unsigned>> a, b, common;
-                    for (auto &x : out_arcs_of_state[s]) a.push_back({x.first, wbits(x.second)});
-                    for (auto &x : out_arcs_of_state[m]) b.push_back({x.first, wbits(x.second)});
-                    std::sort(a.begin(), a.end());
-                    std::sort(b.begin(), b.end());
-                    std::set_intersection(a.begin(), a.end(), b.begin(), b.end(), std::back_inserter(common));
-                    if (!common.empty() && a.size() - common.size() <= 1 && b.size() - common.size() <= 1) { bmate[s] = m; bmate[m] = s; }
-                }
-    }
-    {
-        std::vector<char> done(S, 0);
-        for (int s = 0; s < S; ++s) {
-            if (done[s] || no_row[s]) continue;
-            const int m = bmate[s];
-            bool fused = false;
-            if (m > s) {
-                std::vector<std::pair<int, unsigned>> a, b;
-                for (auto &x : out_arcs_of_state[s]) a.push_back({x.first, wbits(x.second)});
-                for (auto &x : out_arcs_of_state[m]) b.push_back({x.first, wbits(x.second)});
-                std::sort(a.begin(), a.end());
-                std::sort(b.begin(), b.end());
-                std::vector<std::pair<int, unsigned>> common, ea, eb;
-                std::set_intersection(a.begin(), a.end(), b.begin(), b.end(), std::back_inserter(common));
-                std::set_difference(a.begin(), a.end(), common.begin(), common.end(), std::back_inserter(ea));
-                std::set_difference(b.begin(), b.end(), common.begin(), common.end(), std::back_inserter(eb));
-                if (ea.size() <= 1 && eb.size() <= 1 && !common.empty()) {
-                    BRow r{s, m, {}, -1, -1, 0.f, 0.f};
-                    for (auto &c : common) { float w; memcpy(&w, &c.second, 4); r.arcs.push_back({c.first, w}); }
-                    if (!ea.empty()) { r.e0 = ea[0].first; memcpy(&r.w0, &ea[0].second, 4); }
-                    if (!eb.empty()) { r.e1 = eb[0].first; memcpy(&r.w1, &eb[0].second, 4); }
-                    // which of the two states is output 0 alternates: in a T o LM graph nearly all arcs enter the
-                    // "token" state of a pair, and with a fixed order every gather would hit the entries of ONE output
-                    // (under the BP rows' numbering 2*rid + output, which the z entries shared until the slices became
-                    // planar: half of the LDS banks; the order also fixes the BP rows in memory, which the grad pass reads)
-                    if (brow.size() & 1) { std::swap(r.s0, r.s1); std::swap(r.e0, r.e1); std::swap(r.w0, r.w1); }
-                    brow.push_back(r);
-                    done[s] = done[m] = 1;
-                    fused = true;
-                    ++nfused;
-                }
-            }
-            if (!fused) { brow.push_back(BRow{s, -1, out_arcs_of_state[s], -1, -1, 0.f, 0.f}); done[s] = 1; }
-        }
-    }
-    // Rows in label order (rows of equal length keep it through the placement): the 32 lanes of a half-wave then look up
-    // the emission of one or two labels in their epilogue -- a broadcast -- instead of up to 32 (bank conflicts).  The
-    // forward rows are pairs, which are label-sorted already.
-    {
-        auto key = [&](const BRow &r) {
-            const int l0 = pair_of[r.s0] >= 0 ? pair_lab[pair_of[r.s0]] : -1, l1 = (r.s1 >= 0 && pair_of[r.s1] >= 0) ? pair_lab[pair_of[r.s1]] : -1;
-            return std::max(l0, l1);
-        };
-        std::stable_sort(brow.begin(), brow.end(), [&](const BRow &a, const BRow &b) { return key(a) < key(b); });
-    }
-    Rows bsub(brow.size());
-    for (size_t i = 0; i < brow.size(); ++i) bsub[i] = brow[i].arcs;   // pair ids for now; lengths are all placement needs
-    if (level == 4) {   // (the same test as on the forward rows above: a graph whose BACKWARD rows are mostly multi-lane keeps 768 threads too)
-        size_t long_arcs = 0, all_arcs = 0;
-        for (auto &r : bsub) { all_arcs += r.size(); if (chunks_of(r.size()) > gm->nch) long_arcs += r.size(); }
-        if (opt(kOpt_fac_threads, 0) != 1024 && long_arcs * kLongRowShareDen > all_arcs && long_arcs > kLongRowArcs) { *retry_next = true; return CRF_OK; }
-    }
-    if (short_only)
-        for (auto &r : bsub)
-            if (chunks_of(r.size()) > gm->nch) { if (long_bail) *long_bail = true; *retry_next = true; return CRF_OK; }
-    DirOut bo;
+static Placed place_backward(const FacInput &in, const FacStructure &st, const Attempt &at, FacPlaced *pl) {
+    const Geom &gm = at.g.gm;
+    const int S = in.S, K = at.K;
+    const std::vector<BRow> &brow = st.brow;
+    FacHostCopy &C = pl->C;
+    DirOut &bo = pl->b.o;
     std::vector<SliceAt> bslices;
-    if (!place_rows(bsub, deal_rows(bsub, K), K, &bo, &bslices, *gm)) {
-        if (allow3) { *retry_next = true; return CRF_OK; }   // both directions then use the larger per-thread budget
-        return give_up("backward rows do not fit one CU");
-    }
-    const int Rb = bo.cu_row_off[(size_t)K], Gb0 = 2 * Rb + 2, zsink = 2 * Rb;
+    const Placed placed = place_dir(st.bsub, st, at, false, &bo, &bslices);
+    if (placed.fit != Fit::kBuilt) return placed;
+    const int Rb = pl->b.R = bo.cu_row_off[(size_t)K], Gb0 = 2 * Rb + 2, zsink = 2 * Rb;
+    const bool no_dup = !(at.dup_mask & 2) || opt_on(kOpt_fac_no_dup) || K > 1;
     int bdup = 0;                                        // second copy of every z entry: [z (2 Rb)][sink pair] [pad] [z'][sink']
-    if (!no_dupb) { bdup = Gb0; while ((bdup & 31) != bank_shift) ++bdup; }
+    if (!no_dup) { bdup = Gb0; while ((bdup & 31) != kFacBankShift) ++bdup; }
     const int Gb = bdup ? bdup + Gb0 : Gb0;
+    pl->b.dup = bdup; pl->b.G = Gb;
     if ((size_t)Gb * 4 > 65536) {
-        if (!no_dupb) { *new_mask = dup_mask & ~2; return CRF_OK; }
-        return give_up("backward gather vector > 64 KiB");
+        if (!no_dup) return {Fit::kLessDup, at.dup_mask & ~2};
+        return gave_up("backward gather vector > 64 KiB");
     }
-    // BP position of state s (rows in memory): 2*rid + output.  Its z entry in the LDS vector is PLANAR WITHIN THE SLICE of 64 rows that a wave
-    // finishes together (fac_zent): the slice's 128 entries are the 64 outputs 0, then the 64 outputs 1 -- two runs of 64 consecutive floats
-    // 256 bytes apart (and two more in the second copy), which a wave stores with ONE ds_write2_b32 per copy, or with two
-    // ds_write_addtid_b32 (no address register at all) behind one write of M0.  A slice still owns the entries [2 * rid0, 2 * rid0 + 128),
-    // so whatever speaks of ranges of rows (the second copy, the two-CU exchange) is as before.
-    std::vector<int> zpos(S, -1), zent(S, -1);
+    // BP position of state s (rows in memory): 2*rid + output.  Its z entry in the LDS vector is PLANAR WITHIN THE SLICE of 64 rows that a wave finishes
+    // together (fac_zent): the slice's 128 entries are the 64 outputs 0, then the 64 outputs 1 -- two runs of 64 consecutive floats 256 bytes apart (and
+    // two more in the second copy), which a wave stores with ONE ds_write2_b32 per copy, or with two ds_write_addtid_b32 behind one write of M0.  A slice
+    // still owns the entries [2 * rid0, 2 * rid0 + 128), so whatever speaks of ranges of rows (the second copy, the two-CU exchange) is as before.
+    std::vector<int> zent(S, -1);
+    pl->zpos.assign(S, -1);
     for (int rid = 0; rid < Rb; ++rid) {
         const int r = bo.row_of[rid];
         if (r < 0) continue;
-        zpos[brow[r].s0] = 2 * rid; zent[brow[r].s0] = fac_zent(rid, 0);
-        if (brow[r].s1 >= 0) { zpos[brow[r].s1] = 2 * rid + 1; zent[brow[r].s1] = fac_zent(rid, 1); }
+        pl->zpos[brow[r].s0] = 2 * rid; zent[brow[r].s0] = fac_zent(rid, 0);
+        if (brow[r].s1 >= 0) { pl->zpos[brow[r].s1] = 2 * rid + 1; zent[brow[r].s1] = fac_zent(rid, 1); }
     }
-    auto zof_pair = [&](int p) { return zent[pair_dst[p]]; };
+    auto zof_pair = [&](int p) { return zent[in.pair_dst[p]]; };
+    Rows bsub = st.bsub;
     for (auto &row : bsub)
         for (auto &a : row) a.first = zof_pair(a.first);
     for (int s = 0; s < S; ++s)   // rowless states: b_0[s] * start[s] = start[s] * sum over their arcs of w * z_0[pair]
-        if (no_row[s] && start_lin[s] != 0.f)
-            for (auto &a : out_arcs_of_state[s]) { bx_idx.push_back(zof_pair(a.first)); bx_w.push_back(a.second * start_lin[s]); }
-    if (bx_idx.empty()) { bx_idx.push_back(zsink); bx_w.push_back(0.f); }
-    pack_arcs(bsub, bslices, &bo, 4, *gm, bdup ? 2 * Rb : 0, bdup);
+        if (st.no_row[s] && in.start_lin[s] != 0.f)
+            for (auto &a : in.out_arcs_of_state[s]) { C.bx_idx.push_back(zof_pair(a.first)); C.bx_w.push_back(a.second * in.start_lin[s]); }
+    if (C.bx_idx.empty()) { C.bx_idx.push_back(zsink); C.bx_w.push_back(0.f); }
+    pack_arcs(bsub, bslices, &bo, 4, gm, bdup ? 2 * Rb : 0, bdup);
     const int noLab = -1;
-    std::vector<int4> brow_meta(Rb, int4{(zsink * 4) | ((zsink * 4) << 16), 0, 0, (noLab & 0xffff) | (int)((unsigned)noLab << 16)});
-    std::vector<float> brow_start((size_t)2 * Rb, 0.f), brow_end((size_t)2 * Rb, 0.f), z_end(Gb, 0.f);
-    std::vector<int> z_lab(Gb, -1);
+    std::vector<int4> &brow_meta = C.brow_meta;
+    brow_meta.assign(Rb, int4{(zsink * 4) | ((zsink * 4) << 16), 0, 0, (noLab & 0xffff) | (int)((unsigned)noLab << 16)});
+    C.brow_start.assign((size_t)2 * Rb, 0.f); C.brow_end.assign((size_t)2 * Rb, 0.f); C.z_end.assign(Gb, 0.f);
+    C.z_lab.assign(Gb, -1);
     for (int rid = 0; rid < Rb; ++rid) {
         const int r = bo.row_of[rid];
         if (r < 0) continue;
         const BRow &br = brow[r];
+        const std::vector<int> &pair_of = st.pair_of, &pair_lab = in.pair_lab;
         const int o0 = br.e0 >= 0 ? zof_pair(br.e0) : zsink, o1 = br.e1 >= 0 ? zof_pair(br.e1) : zsink;
         const int l0 = pair_of[br.s0] >= 0 ? pair_lab[pair_of[br.s0]] : noLab;
         const int l1 = (br.s1 >= 0 && pair_of[br.s1] >= 0) ? pair_lab[pair_of[br.s1]] : noLab;
-        brow_meta[rid] = int4{(o0 * 4) | ((o1 * 4) << 16), (int)wbits(br.w0), (int)wbits(br.w1), (l0 & 0xffff) | (l1 << 16)};
-        brow_start[2 * rid] = start_lin[br.s0]; brow_end[2 * rid] = end_lin[br.s0];
-        z_lab[fac_zent(rid, 0)] = l0; z_end[fac_zent(rid, 0)] = end_lin[br.s0];
+        brow_meta[rid] = int4{(o0 * 4) | ((o1 * 4) << 16), (int)wbits(br.w0), (int)wbits(br.w1), (l0 & 0xffff) | (int)((unsigned)l1 << 16)};   // (l1 may be noLab = -1)
+        C.brow_start[2 * rid] = in.start_lin[br.s0]; C.brow_end[2 * rid] = in.end_lin[br.s0];
+        C.z_lab[fac_zent(rid, 0)] = l0; C.z_end[fac_zent(rid, 0)] = in.end_lin[br.s0];
         if (br.s1 >= 0) {
-            brow_start[2 * rid + 1] = start_lin[br.s1]; brow_end[2 * rid + 1] = end_lin[br.s1];
-            z_lab[fac_zent(rid, 1)] = l1; z_end[fac_zent(rid, 1)] = end_lin[br.s1];
+            C.brow_start[2 * rid + 1] = in.start_lin[br.s1]; C.brow_end[2 * rid + 1] = in.end_lin[br.s1];
+            C.z_lab[fac_zent(rid, 1)] = l1; C.z_end[fac_zent(rid, 1)] = in.end_lin[br.s1];
         }
     }
-
-    if (bdup) for (int z = 0; z < 2 * Rb; ++z) { z_lab[bdup + z] = z_lab[z]; z_end[bdup + z] = z_end[z]; }
-    if (rcregs)   // row constants in registers: {extra-arc z offsets, labels (0xffff = none)}; the two extra weights stay in LDS
+    if (bdup) for (int z = 0; z < 2 * Rb; ++z) { C.z_lab[bdup + z] = C.z_lab[z]; C.z_end[bdup + z] = C.z_end[z]; }
+    if (at.g.rc_regs)   // row constants in registers: {extra-arc z offsets, labels (0xffff = none)}; the two extra weights stay in LDS
         for (const SliceAt &sl : bslices)
             for (int lane = 0; lane < kWave; ++lane) {
                 const int rid = sl.rid0 + lane;
                 const int4 m = brow_meta[rid];
                 const size_t t = (size_t)sl.w * kWave + lane, w0 = (size_t)kFac3ArcCh * 6 + 2 * (size_t)sl.ord;
-                bo.arcs[w0 * gm->threads + t] = (unsigned)m.x;
+                bo.arcs[w0 * gm.threads + t] = (unsigned)m.x;
                 {   // byte offsets of the two emissions (0xffff = no label)
                     const unsigned l0 = (unsigned)m.w & 0xffffu, l1 = (unsigned)m.w >> 16;
-                    bo.arcs[(w0 + 1) * gm->threads + t] = (l0 == 0xffffu ? 0xffffu : l0 * 4u) | ((l1 == 0xffffu ? 0xffffu : l1 * 4u) << 16);
+                    bo.arcs[(w0 + 1) * gm.threads + t] = (l0 == 0xffffu ? 0xffffu : l0 * 4u) | ((l1 == 0xffffu ? 0xffffu : l1 * 4u) << 16);
                 }
             }
+    return {};
+}
 
-    // ---- 5. grad pass list: one (Q position, BP position) per pair, label-sorted (pairs already are), chunked
-    std::vector<int> gq, gb, gchunk{0}, glab((size_t)max_lab + 2, 0);
-    for (int p = 0; p < P; ++p) { gq.push_back(fpos[p]); gb.push_back(zpos[pair_dst[p]]); }
-    // Chunks of at most `cap` entries within one label: kChunk = 32, or 8 when the labels have few pairs each (hundreds of classes
-    // over a graph of this size: V = 500 -> ~8 pairs per label): the grad kernel's threads walk every slot of a chunk, and chunks of
-    // 32 slots a quarter full spend most of their gathers on padding.  (8 only when the chunk count then fits 512 threads x 2.)
-    int cap = kChunk;
-    auto count_chunks = [&](int c_) { int n = 0, r = 0; for (int v = 0; v <= max_lab; ++v) { int e = r; while (e < P && pair_lab[e] == v) ++e; n += (e - r + c_ - 1) / c_; r = e; } return n; };
-    {
-        const int n32 = count_chunks(kChunk), n8 = count_chunks(8);
-        if (n32 > 0 && (int64_t)P * 5 < (int64_t)n32 * kChunk * 2 && n8 <= 1024) cap = 8;   // chunks of 32 would be less than 40 % full
-    }
-    {
-        int r = 0;
-        for (int v = 0; v <= max_lab; ++v) {
-            glab[v] = (int)gchunk.size() - 1;
-            int e = r;
-            while (e < P && pair_lab[e] == v) ++e;
-            for (int c = r; c < e; c += cap) gchunk.push_back(std::min(e, c + cap));
-            r = e;
-        }
-        glab[(size_t)max_lab + 1] = (int)gchunk.size() - 1;
-    }
-    for (int p = 1; p < P; ++p) if (pair_lab[p] < pair_lab[p - 1]) return give_up("pairs are not label-sorted");
+// Grad-pass pairs, statistics, the LDS budget, then the device tables and their host copy (main layout: h->dev.fac / fh, second: facp / fhp).
+static Placed finish_factored(HostGraph *h, const FacInput &in, const FacStructure &st, const Attempt &at, bool second, FacPlaced *pl) {
+    const Geom &gm = at.g.gm;
+    const FacPlaced::Dir &f = pl->f, &b = pl->b;
+    const int K = at.K, Rf = f.R, Rb = b.R, Gf = f.G, Gb = b.G;
+    const DirOut &fo = f.o, &bo = b.o;
+    FacHostCopy &C = pl->C;
+    for (int p = 0; p < in.P; ++p) { C.gq.push_back(pl->fpos[p]); C.gb.push_back(pl->zpos[in.pair_dst[p]]); }
     int64_t gcb = 0, gca = 0;
-    arrange_grad_pairs(&gq, &gb, gchunk, &gcb, &gca);
-    if (verbose) fprintf(stderr, "[fac_layout] grad pass: LDS cycles per frame for the pair gathers %lld as listed, %lld arranged (%d chunks)\n", (long long)gcb, (long long)gca, (int)gchunk.size() - 1);
+    arrange_grad_pairs(&C.gq, &C.gb, st.gchunk, &gcb, &gca);
+    if (verbose()) fprintf(stderr, "[fac_layout] grad pass: LDS cycles per frame for the pair gathers %lld as listed, %lld arranged (%d chunks)\n", (long long)gcb, (long long)gca, (int)st.gchunk.size() - 1);
 
-    if (!second) h->fac_stats = FacBuildStats{0, nmatched, nsolo, (int64_t)tail_rows.size(), fo.slots, bo.slots, nfused, Gf, Gb};   // (ok: set with F.ok below)
-    if (verbose)
+    // (written by every attempt that gets here, BEFORE the LDS budget: crf_graph_stats shows the last of them, with ok = 0 when nothing was built)
+    if (!second) h->fac_stats = FacBuildStats{0, st.nmatched, st.ntail, fo.slots, bo.slots, st.nfused, Gf, Gb};
+    if (verbose())
         fprintf(stderr, "[fac_layout] matched pairs %lld, solo slots %lld, tail rows %zu (NT=%d), fwd rows %d slots %lld (extra LDS cycles %lld), bwd rows %d (fused %lld) slots %lld (extra %lld), Gf=%d Gb=%d\n",
-                (long long)nmatched, (long long)nsolo, tail_rows.size(), NT, Rf, (long long)fo.slots, (long long)fo.conflicts, Rb, (long long)nfused, (long long)bo.slots, (long long)bo.conflicts, Gf, Gb);
-    {   // LDS of the recursion kernels (crf_kernels.hip fac_lds_bytes): two state vectors + the row constants + two emission rows
-        // (budgeted for the graph's own label range, at least 256: a call with more classes than fit falls back to the other
-        // kernel families, crf_kernels.hip use_factored).  Too much with the second copy of the gathered entries: build that
-        // direction again without it.  (level 1: the forward table has 8 bytes per row, and both have 64 rows of slack.)
-        const int V0 = std::max(max_lab + 1, 256);
-        const size_t esz = second ? 8 : 4;        // (the two-utterance kernel keeps float2 state vectors and emission rows: fac2u_lds_bytes)
-        const size_t tail = ((size_t)2 * ((V0 + 1 + 63) / 64 * 64) + 4 * (size_t)gm->waves + 16) * esz + 256;
-        auto need = [&](int G, int R, int rb) { return (size_t)2 * ((G + 63) / 64 * 64) * esz + (size_t)(R + (lvl_table ? 64 : 0)) * rb + tail; };
+                (long long)st.nmatched, 0ll, (size_t)st.ntail, 0, Rf, (long long)fo.slots, (long long)fo.conflicts, Rb, (long long)st.nfused, (long long)bo.slots, (long long)bo.conflicts, Gf, Gb);
+    {   // LDS of the recursion kernels (fac_lds_bytes): two state vectors + the row constants + two emission rows (budgeted for the graph's own label
+        // range, at least 256: a call with more classes than fit takes another kernel family, use_factored).  Too much with the second copy: again without it.
+        const int V0 = std::max(st.max_lab + 1, 256);
+        const size_t esz = (size_t)at.g.esz, slack = at.g.rcl ? 64 : 0;
+        const size_t tail = ((size_t)2 * ((V0 + 1 + 63) / 64 * 64) + 4 * (size_t)gm.waves + 16) * esz + 256;
+        auto need = [&](int G, int R, int rb) { return (size_t)2 * ((G + 63) / 64 * 64) * esz + ((size_t)R + slack) * rb + tail; };
         auto cu_rows = [&](const DirOut &o) { int m = 0; for (int k = 0; k < K; ++k) m = std::max(m, o.cu_row_off[(size_t)k + 1] - o.cu_row_off[(size_t)k]); return m; };   // (two CUs: a CU's table holds its own rows)
-        const bool f_ok = need(Gf, K > 1 ? cu_rows(fo) : Rf, lvl_table ? 8 : 16) <= (size_t)160 * 1024, b_ok = need(Gb, K > 1 ? cu_rows(bo) : Rb, 16) <= (size_t)160 * 1024;
+        const bool f_ok = need(Gf, K > 1 ? cu_rows(fo) : Rf, at.g.frow_bytes) <= (size_t)160 * 1024, b_ok = need(Gb, K > 1 ? cu_rows(bo) : Rb, 16) <= (size_t)160 * 1024;
         if (!f_ok || !b_ok) {
-            int m = dup_mask;
-            if (!f_ok && !no_dupf) m &= ~1;
-            if (!b_ok && !no_dupb) m &= ~2;
-            if (m != dup_mask) { *new_mask = m; return CRF_OK; }
-            // (one CU per recursion: the table of ALL rows beside the two vectors -- a den_lm with a state per seen bigram history, S ~ 10 k at
-            // 72 tokens, has few arcs per row and fails HERE, not on the arc slots; with two CUs per recursion a CU's table holds its own rows
-            // only: let the planner go on to that geometry instead of leaving the graph to the generic layout -- round 6: S = 10 608 / A = 78 k
-            // ran on the generic K = 2 layout at 7.1 ms of recursions, S = 10 632 / A = 111 k on generic K = 4 at 13.6 ms, where the factored
-            // two-CU layout takes S = 10 636 / A = 147 k at 6.4 ms)
-            if (K == 1 && allow3 && retry_next) { if (verbose) fprintf(stderr, "[fac_layout] one CU per recursion: state vectors and row constants exceed the LDS\n"); *retry_next = true; return CRF_OK; }
-            return give_up("state vectors and row constants exceed the LDS");
+            int m = at.dup_mask;
+            if (!f_ok && f.dup) m &= ~1;
+            if (!b_ok && b.dup) m &= ~2;
+            if (m != at.dup_mask) return {Fit::kLessDup, m};
+            // (one CU per recursion: the table of ALL rows beside the two vectors -- a den_lm with a state per seen bigram history, S ~ 10 k at 72 tokens, has
+            // few arcs per row and fails HERE, not on the arc slots; on two CUs a CU's table holds its own rows only, so the planner goes on to that geometry
+            // instead of leaving the graph to the generic layout: DESIGN.md section 2, round 6)
+            if (K == 1 && at.more) { if (verbose()) fprintf(stderr, "[fac_layout] one CU per recursion: state vectors and row constants exceed the LDS\n"); return {Fit::kNextGeometry}; }
+            return gave_up("state vectors and row constants exceed the LDS");
         }
     }
-    F.nbx = (int)bx_idx.size(); F.bx_se = bx_se;
+    FacDev &F = second ? h->facp : h->dev.fac;
+    F.nbx = (int)C.bx_idx.size(); F.bx_se = st.bx_se;
     F.multilane = 0;
     for (auto &wi : fo.wave_info) if (wi.w) F.multilane = 1;
     for (auto &wi : bo.wave_info) if (wi.w) F.multilane = 1;
     // Next-vector stores by ds_write_addtid_b32 (fac_chain_body ADT): every graph on the 1024-thread geometry with one CU per recursion -- the only
-    // instantiations that have them.  Measured against the ds_write stores on one box (profiles/ab_row_epilogues.txt): metric graph 2.664 -> 2.622 ms per
-    // step, V = 217 (rows on several lanes) 3.136 -> 3.003, and S = 513 -- four backward slices on sixteen waves, where four M0 writes per forward
-    // epilogue alone had cost 5 % (profiles/round6_ab_addtid.txt) -- 1.905 -> 1.888 with two per backward epilogue beside them.
+    // instantiations that have them (measured against the ds_write stores: profiles/ab_row_epilogues.txt, profiles/round6_ab_addtid.txt)
     F.addtid = 0;
-    if (implicit && K == 1 && gm->threads == kFac4Threads) {
+    if (at.g.implicit && K == 1 && gm.threads == kFac4Threads) {
         const int sw = opt(kOpt_fac_addtid, -1);
         F.addtid = sw >= 0 ? (sw != 0) : 1;
     }
-    F.f.R = Rf; F.f.G = Gf; F.b.R = Rb; F.b.G = Gb; F.f.dup = fdup * 4; F.b.dup = bdup * 4;
-    F.NT = NT; F.Rq = Rq; F.Rbp = 2 * Rb; F.NC = (int)gchunk.size() - 1; F.chunk_cap = cap; F.threads = gm->threads; F.imp = implicit ? 1 : 0; F.rcl = level == 1 ? 1 : level == 3 ? 2 : (level == 4 || level == 6) ? 1 : 0; F.K = K;
-    for (int k = 0; k < 3; ++k) F.xlist_off[k] = xlist_off[k];
+    F.f.R = Rf; F.f.G = Gf; F.b.R = Rb; F.b.G = Gb; F.f.dup = f.dup * 4; F.b.dup = b.dup * 4;
+    F.NT = 0; F.Rq = 2 * Rf; F.Rbp = 2 * Rb; F.NC = (int)st.gchunk.size() - 1; F.chunk_cap = st.cap; F.threads = gm.threads; F.imp = at.g.implicit ? 1 : 0; F.rcl = at.g.rcl; F.K = K;
+    for (int k = 0; k < 3; ++k) F.xlist_off[k] = pl->xlist_off[k];
     for (int k = 0; k <= 2; ++k) { F.f.cu_row[k] = fo.cu_row_off[(size_t)std::min(k, K)]; F.b.cu_row[k] = bo.cu_row_off[(size_t)std::min(k, K)]; }
+    C.farcs = fo.arcs; C.barcs = bo.arcs; C.fwi = fo.wave_info; C.bwi = bo.wave_info; C.gchunk = st.gchunk; C.glab = st.glab;
+    C.start_lin = in.start_lin; C.end_lin = in.end_lin; C.words = gm.words;
     int rc;
-    if ((rc = up(h, fo.arcs, &F.f.arcs)) || (rc = up(h, fo.wave_info, &F.f.wave_info)) || (rc = up(h, bo.arcs, &F.b.arcs)) ||
-        (rc = up(h, bo.wave_info, &F.b.wave_info)) || (rc = up(h, frow_meta, &F.frow_meta)) ||
-        (rc = up(h, x_start, &F.x_start)) || (rc = up(h, x_end, &F.x_end)) || (rc = up(h, brow_meta, &F.brow_meta)) ||
-        (rc = up(h, z_lab, &F.z_lab)) || (rc = up(h, z_end, &F.z_end)) || (rc = up(h, brow_start, &F.brow_start)) ||
-        (rc = up(h, brow_end, &F.brow_end)) || (rc = up(h, bx_idx, &F.bx_idx)) || (rc = up(h, bx_w, &F.bx_w)) || (rc = up(h, gq, &F.gq)) || (rc = up(h, gb, &F.gb)) ||
-        (rc = up(h, gchunk, &F.chunk_off)) || (rc = up(h, glab, &F.lab_chunk_off)) || (rc = up(h, xlist, &F.xlist)))
-        return rc;
+    if ((rc = up(h, C.farcs, &F.f.arcs)) || (rc = up(h, C.fwi, &F.f.wave_info)) || (rc = up(h, C.barcs, &F.b.arcs)) ||
+        (rc = up(h, C.bwi, &F.b.wave_info)) || (rc = up(h, C.frow_meta, &F.frow_meta)) ||
+        (rc = up(h, C.x_start, &F.x_start)) || (rc = up(h, C.x_end, &F.x_end)) || (rc = up(h, C.brow_meta, &F.brow_meta)) ||
+        (rc = up(h, C.z_lab, &F.z_lab)) || (rc = up(h, C.z_end, &F.z_end)) || (rc = up(h, C.brow_start, &F.brow_start)) ||
+        (rc = up(h, C.brow_end, &F.brow_end)) || (rc = up(h, C.bx_idx, &F.bx_idx)) || (rc = up(h, C.bx_w, &F.bx_w)) || (rc = up(h, C.gq, &F.gq)) || (rc = up(h, C.gb, &F.gb)) ||
+        (rc = up(h, C.gchunk, &F.chunk_off)) || (rc = up(h, C.glab, &F.lab_chunk_off)) || (rc = up(h, C.xlist, &F.xlist)))
+        return {Fit::kGiveUp, 0, false, rc};
     F.ok = 1;
     if (!second) h->fac_stats.ok = 1;
-    FacHostCopy &C = second ? h->fhp : h->fh;
-    C.farcs = fo.arcs; C.barcs = bo.arcs; C.fwi = fo.wave_info; C.bwi = bo.wave_info; C.frow_meta = frow_meta; C.brow_meta = brow_meta;
-    C.x_start = x_start; C.x_end = x_end; C.z_end = z_end; C.brow_start = brow_start; C.brow_end = brow_end; C.bx_w = bx_w;
-    C.start_lin = start_lin; C.end_lin = end_lin; C.z_lab = z_lab; C.bx_idx = bx_idx; C.xlist = xlist; C.words = gm->words;
-    C.gq = gq; C.gb = gb; C.gchunk = gchunk; C.glab = glab;
-    return CRF_OK;
+    (second ? h->fhp : h->fh) = std::move(C);
+    return {};
 }
 
+// One geometry on K CUs: first with the second copy of the gathered entries in both directions, then without it in the direction(s)
+// that do not fit with it.  What comes back is built / next geometry / give up.
+static Placed place_factored(HostGraph *h, const FacInput &in, const FacStructure &st, const FacGeomDesc &g, int K, bool short_only, bool more, bool second) {
+    Placed p{Fit::kLessDup, 3};
+    while (p.fit == Fit::kLessDup) {
+        const Attempt at{g, K, short_only, more, p.dup_mask};
+        (second ? h->facp : h->dev.fac) = FacDev{};
+        FacPlaced pl;
+        p = place_forward(in, st, at, &pl);
+        if (p.fit == Fit::kBuilt) p = place_backward(in, st, at, &pl);
+        if (p.fit == Fit::kBuilt) p = finish_factored(h, in, st, at, second, &pl);
+    }
+    return p;
+}
 
+void fac_geom_public(const HostGraph *h, int64_t *fac_geom, int64_t *fac_chunks) {
+    const bool have = h->fac_stats.ok && h->fac_geom_id >= 0;
+    *fac_geom = have ? (h->dev.fac.K > 1 ? kFacGeoms[h->fac_geom_id].fac_geom_k2 : kFacGeoms[h->fac_geom_id].fac_geom) : -1;
+    *fac_chunks = have ? kFacGeoms[h->fac_geom_id].fac_chunks : 0;
+}
+
+// The planner.  The graph's structure is analysed once; then a plan -- a list of (geometry, short rows only, CUs per recursion) -- is walked until an
+// entry builds or gives up; kFg512Rows ends EVERY plan, so whatever does not fit there is given up.  The planner's own order: kFg1024Table (not with
+// fac_threads = 768); kFg768Regs for graphs without rows longer than a lane; kFg768Table; kFg768Regs in full if its first turn passed the graph on for
+// its long rows; kFg768Table21; kFg768Table on TWO CUs per recursion (not with fac_no_k2; they stay on 768 threads: on 1024 x 15 -- fac_k2 with
+// fac_threads = 1024 -- the recursions measured SLOWER, 4.13 -> 4.31 / 5.84 -> 6.3 ms at H = 3 072 / 4 096: the hand-off's polls and granule stores are
+// per wave, and there are a third more waves).  The other switches replace that order by one or two geometries, as listed below.
 int build_factored(HostGraph *h, int S, int P, const std::vector<int> &pair_dst, const std::vector<int> &pair_lab,
                    const Rows &in_arcs_of_pair, const Rows &out_arcs_of_state, const std::vector<float> &start_lin,
                    const std::vector<float> &end_lin) {
-    // Geometry: 768 threads x 21 chunks (3 waves per SIMD at <= 168 VGPRs) when both directions fit it, else
-    // 512 threads x 30 chunks (2 waves per SIMD); CRF_FAC_THREADS=512 forces the latter.
-    // ... then 768 threads with the row constants in LDS (any number of slices per wave; CRF_FAC_RCL=1 starts there,
-    // CRF_FAC_NO_RCL=1 skips it).  Each geometry first with the second copy of the gathered entries, then without it in the direction(s) that do not fit.
+    h->dev.fac = h->facp = FacDev{};
+    h->fac_geom_id = -1;
+    if (opt_on(kOpt_no_factored) || opt_on(kOpt_no_resident)) return CRF_OK;
+    const FacInput in{S, P, pair_dst, pair_lab, in_arcs_of_pair, out_arcs_of_state, start_lin, end_lin};
+    FacStructure st;
+    analyse_factored(in, &st);
+    if (st.why) { gave_up(st.why); return CRF_OK; }
     const int thr = opt(kOpt_fac_threads, 0);          // 0: the planner's order; 512 / 768 / 1024: that geometry (first)
-    const bool no_rcl = opt_on(kOpt_fac_no_rcl);
-    const bool from_rcl = opt_on(kOpt_fac_rcl);
-    int rc = CRF_OK;
-    struct Try { int level; bool short_only; int K = 1; };
+    struct Try { FacGeomId geom; bool short_only = false; int K = 1; };
     std::vector<Try> plan;
     bool dflt = false;
-    if (thr == 512) plan = {{2, false}};
-    else if (opt_on(kOpt_fac_k2)) plan = thr == 1024 ? std::vector<Try>{{4, false, 2}, {2, false}} : std::vector<Try>{{1, false, 2}, {2, false}};   // (tests: two CUs per recursion for any T o LM graph; with fac_threads = 1024 on that geometry)
-    else if (opt(kOpt_fac_rcl, 0) == 2) plan = {{3, false}, {2, false}};   // (tests: the 21-chunk table geometry for any T o LM graph)
-    else if (from_rcl) plan = {{1, false}, {3, false}, {2, false}};
-    else if (no_rcl) plan = {{0, false}, {2, false}};
+    if (thr == 512) plan = {{kFg512Rows}};
+    else if (opt_on(kOpt_fac_k2)) plan = {{thr == 1024 ? kFg1024Table : kFg768Table, false, 2}, {kFg512Rows}};   // (tests: two CUs per recursion for any T o LM graph)
+    else if (opt(kOpt_fac_rcl, 0) == 2) plan = {{kFg768Table21}, {kFg512Rows}};                                  // (tests: the 21-chunk table geometry for any T o LM graph)
+    else if (opt_on(kOpt_fac_rcl)) plan = {{kFg768Table}, {kFg768Table21}, {kFg512Rows}};
+    else if (opt_on(kOpt_fac_no_rcl)) plan = {{kFg768Regs}, {kFg512Rows}};
     else {
-        // 768 threads: level 0 (row constants in registers) only for graphs without long rows -- unless level 1 (LDS table) does not
-        // take them; then the 21-chunk table geometry, two CUs per recursion (table geometry), 512 threads.  In front of all of
-        // them since round 3: 1024 threads x 15 chunks with the table (level 4: four waves per SIMD at 128 VGPRs -- the same
-        // registers per wave are left beside the arcs as at 768 x 21 -- measured 2 - 6 % faster on every graph that fits it)
-        // (Two CUs per recursion stay on 768 threads: built on 1024 x 15 in round 4 -- `fac_k2` with `fac_threads` = 1024, geometry 5 --
-        // and measured SLOWER, H = 3 072 / 4 096 recursions 4.13 -> 4.31 / 5.84 -> 6.3 ms: the hand-off's polls and granule stores are per
-        // wave, and there are a third more waves.)
-        plan = {{0, true}, {1, false}, {0, false}, {3, false}, {1, false, 2}, {2, false}};
+        plan = {{kFg768Regs, true}, {kFg768Table}, {kFg768Regs}, {kFg768Table21}, {kFg768Table, false, 2}, {kFg512Rows}};
         dflt = true;
-        if (thr != 768) plan.insert(plan.begin(), Try{4, false});
+        if (thr != 768) plan.insert(plan.begin(), Try{kFg1024Table});
     }
-    const bool no_k2 = opt_on(kOpt_fac_no_k2);
+    int rc = CRF_OK;
     bool long_bail = false;
-    for (const Try &t : plan) {
-        if (t.level == 0 && !t.short_only && dflt && !long_bail) continue;   // level 0 has been tried in full already
-        if (t.K > 1 && no_k2) continue;
-        bool retry = false;
-        int mask = 3, nm = 3;
-        for (;;) {
-            rc = build_factored_impl(h, S, P, pair_dst, pair_lab, in_arcs_of_pair, out_arcs_of_state, start_lin, end_lin, t.level, &retry, mask, &nm, t.short_only, &long_bail, t.K);
-            if (rc != CRF_OK || retry || nm == mask) break;
-            mask = nm;
-        }
-        if (rc != CRF_OK || !retry) break;
+    for (size_t i = 0; i < plan.size(); ++i) {
+        const Try &t = plan[i];
+        if (dflt && t.geom == kFg768Regs && !t.short_only && !long_bail) continue;   // it has been tried in full already
+        if (t.K > 1 && opt_on(kOpt_fac_no_k2)) continue;
+        const Placed p = place_factored(h, in, st, kFacGeoms[t.geom], t.K, t.short_only, i + 1 < plan.size(), false);
+        long_bail |= p.long_bail;
+        rc = p.rc;
+        if (p.fit == Fit::kBuilt) h->fac_geom_id = t.geom;
+        if (p.fit != Fit::kNextGeometry) break;
     }
     // The two-utterance kernel's own layout (512 threads x 30 chunks, table, implicit entries) beside a main layout on one CU per
-    // recursion that is not a 768-thread one (those the two-utterance kernel takes as they are).  Does not fit / no structure: facp.ok = 0.
-    h->facp = FacDev{};
+    // recursion that is not a 768-thread one (those the two-utterance kernel takes as they are).  Does not fit: facp.ok = 0.
     if (rc == CRF_OK && h->dev.fac.ok && h->dev.fac.K == 1 && h->dev.fac.threads != kFac3Threads && !opt_on(kOpt_no_facp) && thr != 512) {
-        bool retry = false;
-        int mask = 3, nm = 3;
-        for (;;) {
-            rc = build_factored_impl(h, S, P, pair_dst, pair_lab, in_arcs_of_pair, out_arcs_of_state, start_lin, end_lin, 6, &retry, mask, &nm, false, nullptr, 1);
-            if (rc != CRF_OK || retry || nm == mask) break;
-            mask = nm;
-        }
-        if (rc != CRF_OK) { h->facp = FacDev{}; rc = CRF_OK; }   // (the second layout is optional: a failure while building it must not fail a graph whose main layout stands)
-        if (opt_on(kOpt_verbose)) fprintf(stderr, "[fac_layout] second layout (two utterances per workgroup, 512 x 30): %s\n", h->facp.ok ? "built" : "not available");
+        if (place_factored(h, in, st, kFacGeoms[kFg512Pair2], 1, false, false, true).rc != CRF_OK) h->facp = FacDev{};   // (optional: a failure while building it must not fail a graph whose main layout stands)
+        if (verbose()) fprintf(stderr, "[fac_layout] second layout (two utterances per workgroup, 512 x 30): %s\n", h->facp.ok ? "built" : "not available");
     }
     return rc;
 }
+
 
 
 // CPU emulation of the factored recursion kernels' DATA FLOW on the layout tables (tests; no GPU): the packed arc words of
@@ -1567,19 +1574,58 @@ int build_factored(HostGraph *h, int S, int P, const std::vector<int> &pair_dst,
 // NaN, so a gather of an entry that never crosses poisons the result).  fp64, no rescaling, random emissions, T frames.
 // out3 = {plain forward sum over the graph's own tables, factored forward, factored backward}; they must agree.
 static double plain_forward(const HostGraph *h, const std::vector<std::vector<double>> &e);
+static double fl(unsigned b) { float f; memcpy(&f, &b, 4); return (double)f; }
+// ... of chunk c of one wave (its lane 0 is thread `wave_base` of the arc table) as the kernels walk it: four gathers and FMAs per lane into acc[lane]
+// (padding gathers have weight 0).  False: a gather offset outside the vector.
+static bool emu_chunk(const std::vector<unsigned> &A, size_t wave_base, int NTH, int c, int G, const std::vector<double> &src, double *acc) {
+    for (int lane = 0; lane < kWave; ++lane) {
+        auto W = [&](int j) { return A[wave_base + (size_t)lane + (size_t)(6 * c + j) * NTH]; };
+        const unsigned i01 = W(0), i23 = W(1);
+        const unsigned offs[4] = {i01 & 0xffffu, i01 >> 16, i23 & 0xffffu, i23 >> 16};
+        for (int q = 0; q < 4; ++q) {
+            if (offs[q] % 4 || (int)(offs[q] / 4) >= G) return false;
+            const double wq = fl(W(2 + q));
+            if (wq != 0.0) acc[lane] += wq * src[offs[q] / 4];
+        }
+    }
+    return true;
+}
+// ... and of the grad pass's lists (either layout's host copy): for every frame, the sum over the label-sorted (Q position, BP position) pairs of
+// e_t[label] * Q[t][q] * BP[t][b] over the rows the recursions stored is the total path mass again.  Returns what is wrong ("": nothing).
+template <typename HostCopy>
+static std::string grad_lists_wrong(const HostCopy &C, const std::vector<std::vector<double>> &e, int V, const std::vector<std::vector<double>> &Qrows,
+                                    const std::vector<std::vector<double>> &BProws, double mass, int max_chunk) {
+    const int NC = (int)C.gchunk.size() - 1;
+    for (size_t t = 0; t < e.size(); ++t) {
+        double tot = 0.0;
+        for (int v = 0; v < V && v + 1 < (int)C.glab.size(); ++v)
+            for (int c = C.glab[(size_t)v]; c < C.glab[(size_t)v + 1]; ++c) {
+                if (c < 0 || c >= NC) return "label -> chunk table";
+                if (C.gchunk[(size_t)c + 1] - C.gchunk[(size_t)c] > max_chunk) return "a grad chunk is longer than kChunk";
+                double sc = 0.0;
+                for (int j = C.gchunk[(size_t)c]; j < C.gchunk[(size_t)c + 1]; ++j) {
+                    const int q = C.gq[(size_t)j], b = C.gb[(size_t)j];
+                    if (q < 0 || q >= (int)Qrows[t].size() || b < 0 || b >= (int)BProws[t].size()) return "a grad pair outside the rows";
+                    sc += Qrows[t][(size_t)q] * BProws[t][(size_t)b];
+                }
+                tot += e[t][(size_t)v] * sc;
+            }
+        if (!(std::fabs(tot - mass) <= 1e-9 * std::fabs(mass))) return "the grad pass's pair lists do not give the path mass at frame " + std::to_string(t);
+    }
+    return "";
+}
 int debug_emulate_factored(const HostGraph *h, int T, unsigned seed, double *out3, int which) {
     const FacDev &F = which ? h->facp : h->dev.fac;
     const FacHostCopy &C = which ? h->fhp : h->fh;
     out3[0] = out3[1] = out3[2] = 0.0;
     if (!F.ok || C.words == 0) { set_error("no factored layout"); return CRF_ERR_UNSUPPORTED; }
     auto fail = [&](const std::string &why) { set_error("factored layout emulation: " + why); return CRF_ERR_ARG; };
-    const int S = (int)h->S, V = h->dev.max_label + 1, NTH = F.threads, NW = NTH / kWave, K = F.K, words = C.words;
+    const int V = h->dev.max_label + 1, NTH = F.threads, NW = NTH / kWave, K = F.K, words = C.words;
     const bool implicit = F.imp != 0, rcregs = implicit && !F.rcl;
     uint64_t rng = 0x9E3779B97F4A7C15ull ^ seed;
     auto rnd = [&]() { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return 0.5 + (double)(rng % 1000003) / 1000003.0; };
     std::vector<std::vector<double>> e((size_t)T, std::vector<double>((size_t)V + 1, 0.0));   // e[t][V] = 0: "no label"
     for (auto &row : e) for (int v = 0; v < V; ++v) row[(size_t)v] = rnd();
-    auto fl = [](unsigned b) { float f; memcpy(&f, &b, 4); return (double)f; };
     const double nan = std::nan("");
     if (h->h_src.empty() && h->A > 0) { set_error("the graph's arcs were not kept (more than 2^20)"); return CRF_ERR_UNSUPPORTED; }
     out3[0] = plain_forward(h, e);
@@ -1619,17 +1665,7 @@ int debug_emulate_factored(const HostGraph *h, int T, unsigned seed, double *out
                     double acc[kWave];
                     for (double &x : acc) x = 0.0;
                     for (int c = 0; c < nch; ++c) {
-                        for (int lane = 0; lane < kWave; ++lane) {
-                            const size_t base = (size_t)k * words * NTH + (size_t)(w * kWave + lane);
-                            auto W = [&](int j) { return A[base + (size_t)(6 * c + j) * NTH]; };
-                            const unsigned i01 = W(0), i23 = W(1);
-                            const unsigned offs[4] = {i01 & 0xffffu, i01 >> 16, i23 & 0xffffu, i23 >> 16};
-                            for (int q = 0; q < 4; ++q) {
-                                if (offs[q] % 4 || (int)(offs[q] / 4) >= G) return fail("a gather offset outside the vector");
-                                const double wq = fl(W(2 + q));
-                                if (wq != 0.0) acc[lane] += wq * src[offs[q] / 4];     // (padding gathers: weight 0)
-                            }
-                        }
+                        if (!emu_chunk(A, (size_t)k * words * NTH + (size_t)w * kWave, NTH, c, G, src, acc)) return fail("a gather offset outside the vector");
                         if (!(ends >> c & 1u)) continue;
                         const unsigned lg = slice < 10 ? (lgbits >> (3 * slice)) & 7u : 0u;
                         double tot[kWave];
@@ -1722,24 +1758,8 @@ int debug_emulate_factored(const HostGraph *h, int T, unsigned seed, double *out
     if (rc) return rc;
     // ---- the grad pass's lists: for every frame, sum over the label-sorted (Q position, BP position) pairs of
     // e_t[label] * Q[t][q] * BP[t][b] is the total path mass again
-    const int NC = (int)C.gchunk.size() - 1;
-    for (int t = 0; t < T; ++t) {
-        double tot = 0.0;
-        for (int v = 0; v < V && v + 1 < (int)C.glab.size(); ++v)
-            for (int c = C.glab[(size_t)v]; c < C.glab[(size_t)v + 1]; ++c) {
-                if (c < 0 || c >= NC) return fail("label -> chunk table");
-                if (C.gchunk[(size_t)c + 1] - C.gchunk[(size_t)c] > kChunk) return fail("a grad chunk is longer than kChunk");
-                double sc = 0.0;
-                for (int j = C.gchunk[(size_t)c]; j < C.gchunk[(size_t)c + 1]; ++j) {
-                    const int q = C.gq[(size_t)j], b = C.gb[(size_t)j];
-                    if (q < 0 || q >= 2 * F.f.R || b < 0 || b >= 2 * F.b.R) return fail("a grad pair outside the rows");
-                    sc += Qrows[(size_t)t][(size_t)q] * BProws[(size_t)t][(size_t)b];
-                }
-                tot += e[(size_t)t][(size_t)v] * sc;
-            }
-        if (!(std::fabs(tot - out3[0]) <= 1e-9 * std::fabs(out3[0]))) return fail("the grad pass's pair lists do not give the path mass at frame " + std::to_string(t));
-    }
-    return CRF_OK;
+    const std::string why = grad_lists_wrong(C, e, V, Qrows, BProws, out3[0], kChunk);
+    return why.empty() ? CRF_OK : fail(why);
 }
 
 
@@ -1772,7 +1792,6 @@ int debug_emulate_resident(const HostGraph *h, int T, unsigned seed, double *out
     auto rnd = [&]() { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return 0.5 + (double)(rng % 1000003) / 1000003.0; };
     std::vector<std::vector<double>> e((size_t)T, std::vector<double>((size_t)V + 1, 0.0));
     for (auto &row : e) for (int v = 0; v < V; ++v) row[(size_t)v] = rnd();
-    auto fl = [](unsigned b) { float f; memcpy(&f, &b, 4); return (double)f; };
     out3[0] = plain_forward(h, e);
     std::vector<std::vector<double>> Qrows((size_t)T, std::vector<double>((size_t)R.f.R, 0.0)), BProws((size_t)T, std::vector<double>((size_t)R.b.R, 0.0));
     for (int r = 0; r < R.b.R; ++r) BProws[(size_t)T - 1][(size_t)r] = (double)C.brow_end[(size_t)r];
@@ -1801,17 +1820,7 @@ int debug_emulate_resident(const HostGraph *h, int T, unsigned seed, double *out
                     double acc[kWave];
                     for (double &x : acc) x = 0.0;
                     for (int c = 0; c < nch; ++c) {
-                        for (int lane = 0; lane < kWave; ++lane) {
-                            const size_t base = (size_t)k * words * NTH + (size_t)(w * kWave + lane);
-                            auto W = [&](int j) { return A[base + (size_t)(6 * c + j) * NTH]; };
-                            const unsigned i01 = W(0), i23 = W(1);
-                            const unsigned offs[4] = {i01 & 0xffffu, i01 >> 16, i23 & 0xffffu, i23 >> 16};
-                            for (int q = 0; q < 4; ++q) {
-                                if (offs[q] % 4 || (int)(offs[q] / 4) >= G) return fail("a gather offset outside the vector");
-                                const double wq = fl(W(2 + q));
-                                if (wq != 0.0) acc[lane] += wq * src[offs[q] / 4];
-                            }
-                        }
+                        if (!emu_chunk(A, (size_t)k * words * NTH + (size_t)w * kWave, NTH, c, G, src, acc)) return fail("a gather offset outside the vector");
                         if (!(ends >> c & 1u)) continue;
                         for (int lane = 0; lane < kWave; ++lane) {
                             const int rid = row + lane;
@@ -1841,23 +1850,8 @@ int debug_emulate_resident(const HostGraph *h, int T, unsigned seed, double *out
     int rc = run(0, &out3[1]);
     if (!rc) rc = run(1, &out3[2]);
     if (rc) return rc;
-    const int NC = (int)C.gchunk.size() - 1;
-    for (int t = 0; t < T; ++t) {
-        double tot = 0.0;
-        for (int v = 0; v < V && v + 1 < (int)C.glab.size(); ++v)
-            for (int c = C.glab[(size_t)v]; c < C.glab[(size_t)v + 1]; ++c) {
-                if (c < 0 || c >= NC) return fail("label -> chunk table");
-                double sc = 0.0;
-                for (int j = C.gchunk[(size_t)c]; j < C.gchunk[(size_t)c + 1]; ++j) {
-                    const int q = C.gq[(size_t)j], b = C.gb[(size_t)j];
-                    if (q < 0 || q >= R.f.R || b < 0 || b >= R.b.R) return fail("a grad pair outside the rows");
-                    sc += Qrows[(size_t)t][(size_t)q] * BProws[(size_t)t][(size_t)b];
-                }
-                tot += e[(size_t)t][(size_t)v] * sc;
-            }
-        if (!(std::fabs(tot - out3[0]) <= 1e-9 * std::fabs(out3[0]))) return fail("the grad pass's pair lists do not give the path mass at frame " + std::to_string(t));
-    }
-    return CRF_OK;
+    const std::string why = grad_lists_wrong(C, e, V, Qrows, BProws, out3[0], 1 << 30);
+    return why.empty() ? CRF_OK : fail(why);
 }
 
 }  // namespace crf

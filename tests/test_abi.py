@@ -297,6 +297,33 @@ def test_factored_layouts_emulated_on_the_host(tmp_path, golden_dir):
         assert g >= 0 and agree(r), (env, g, r)
 
 
+def test_factored_geometry_of_every_planner_mode(tmp_path):
+    """The planner's named geometries (res_layout.cpp: kFacGeoms) carry the public numbers themselves: under every factored switch the small
+    T o LM graph reports the `fac_geom`, `fac_chunks` and `facp` it reported before the planner had a geometry table (literals recorded from the
+    parent of that change, profiles/refactor_fac_planner_host.txt), and the emulation of the layout it built agrees with the plain recursion."""
+    import math
+    import ctc_crf
+    core = ctc_crf._C
+
+    def agree(r):                                                 # (the rule of test_factored_layouts_emulated_on_the_host)
+        return all(math.isfinite(x) and x > 0 for x in r) and abs(r[1] - r[0]) <= 1e-9 * r[0] and abs(r[2] - r[0]) <= 1e-6 * r[0]
+
+    small = os.path.join(str(tmp_path), "small.fst")
+    synth_den_lm(24, 96, 8, seed=13, path=small)
+    # switches -> (fac_geom, fac_chunks, facp)
+    want = (({}, (4, 15, 1)), ({"CRF_FAC_THREADS": 512}, (2, 30, 0)), ({"CRF_FAC_THREADS": 768}, (0, 20, 0)), ({"CRF_FAC_THREADS": 1024}, (4, 15, 1)),
+            ({"CRF_FAC_K2": 1}, (3, 20, 0)), ({"CRF_FAC_RCL": 1}, (1, 20, 0)), ({"CRF_FAC_RCL": 2}, (1, 21, 0)), ({"CRF_FAC_NO_RCL": 1}, (0, 20, 0)),
+            ({"CRF_FAC_NO_DUP": 1}, (4, 15, 1)), ({"CRF_FAC_NO_K2": 1}, (4, 15, 1)), ({"CRF_NO_FACP": 1}, (4, 15, 0)),
+            ({"CRF_FAC_K2": 1, "CRF_FAC_THREADS": 1024}, (5, 15, 0)))
+    for env, numbers in want:
+        with crf_env(**env):
+            h = core.compile_graph_host_only(small)
+            st = core.graph_stats(h)
+            r = core.debug_fac_emulate(h, 5, 7)
+            core._lib.crf_graph_destroy(ctypes.c_void_p(h))
+        assert st["fac"] == 1 and (st["fac_geom"], st["fac_chunks"], st["facp"]) == numbers and agree(r), (env, st["fac_geom"], st["fac_chunks"], st["facp"], r)
+
+
 def test_second_layout_for_two_utterances_emulated_on_the_host(tmp_path, golden_dir):
     """Round 5: beside a 1024-thread main layout the graph compiler builds a SECOND factored layout -- 512 threads x 30 chunks, row
     constants in the LDS table, implicit entries (HostGraph::facp) -- for the two-utterance kernel (crf_fac_pair2_kernel<.., 512, 30, ..>:
