@@ -1,10 +1,15 @@
-// cat_amd/csrc/crf_internal.h -- shared between the host-side graph compiler (fst_graph.cpp) and the
-// gfx950 kernels (crf_kernels.hip).  Not part of the public ABI (include/ctc_crf_hip.h is).
+// cat_amd/csrc/crf_internal.h -- shared between the host-side graph compiler (graph_compile.cpp, arc_streams.cpp,
+// res_layout.cpp) and the gfx950 kernels (k_*.hip).  Not part of the public ABI (include/ctc_crf_hip.h is).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
+#include "../../include/ctc_crf_hip.h"
+
+#include <algorithm>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace crf {
@@ -196,10 +201,14 @@ __host__ __device__ inline void bat_decode(int block, int grid, int ncombo, int 
     }
 }
 
+// The streams' constants, shared by the host's task cutter (arc_streams.cpp) and the kernels (k_batch.hip)
+constexpr int kStreamBatch = 4, kStreamChunk = 128;   // steps per batch; batches * AL per 4 KB chunk (batches in flight: template parameter D)
+constexpr int kStreamBundles = 8;                     // bundles per task at most (plain streams; factored: stream_max_bundles)
+constexpr int kStreamRecB = kStreamChunk * 32;        // bytes of a chunk of records
 // bundles per task at most: 8; factored streams of groups of 16 / 8 utterances 4 / 2 (three descriptor words for each of the
 // 16 / 32 rows of a bundle: the wave's slice of LDS)
 constexpr int kBatEpiDefault = 2;   // what a bundle's row epilogues count for when the arc streams are cut into tasks, in batches of 4 steps (0 / 1 / 2 / 4 -> S = 16 385 recursions 25.03 / 24.91 / 24.57 / 25.06 ms, S = 12 289 19.58 / 19.60 / 19.41 / 19.67: one box, round 6)
-__host__ __device__ constexpr int stream_max_bundles(int UL, bool fac) { return !fac || UL >= 32 ? 8 : UL == 16 ? 4 : 2; }
+__host__ __device__ constexpr int stream_max_bundles(int UL, bool fac) { return !fac || UL >= 32 ? kStreamBundles : UL == 16 ? 4 : 2; }
 struct StreamDirDev {
     const int4 *tasks;       // [ntasks] {first batch, batches, first bundle, bundles}
     const int2 *recs;        // [batches][AL][4] (+ 8 KB of padding)
@@ -249,7 +258,7 @@ struct GraphDev {
 struct ResBuildStats { int K = 0; int64_t slots_f = 0, slots_b = 0, conflicts_f = 0, conflicts_b = 0; };
 struct FacBuildStats { int ok = 0; int64_t matched = 0, tail = 0, slots_f = 0, slots_b = 0, fused = 0, Gf = 0, Gb = 0; };
 
-// host tables of the factored streams (fst_graph.cpp build_batch_factored)
+// host tables of the factored streams (arc_streams.cpp build_batch_factored)
 struct FacRowH {
     int st0 = -1, pr0 = 0, lab0 = 0, st1 = -1, pr1 = 0, lab1 = 0;   // outputs: state, pair, label (st1 = -1: one output)
     int x0 = 0, x1 = 0;                                            // forward: x0 = U entry; backward: entries of the extra arcs
@@ -288,7 +297,7 @@ struct HostGraph {
     // statistics for diagnostics / DESIGN.md
     int64_t fwd_padded_arcs = 0, bwd_padded_arcs = 0, fwd_conflicts = 0, bwd_conflicts = 0;
     int max_in_deg = 0, max_out_deg = 0;
-    int regauged = 0;            // the weights were re-gauged (fst_graph.cpp: regauge_pushed)
+    int regauged = 0;            // the weights were re-gauged (graph_compile.cpp: regauge_pushed)
     ResBuildStats res_stats;
     FacBuildStats fac_stats;
     // host copies of the utterance-minor tables (BatchDev) and the arc streams derived from them per lane-group count
@@ -301,7 +310,7 @@ struct HostGraph {
     int fac_geom_id = -1;               // which named geometry (res_layout.cpp: kFacGeoms) dev.fac was built on; -1: none (fac_geom_public)
     // A SECOND factored layout for the two-utterance kernel (crf_fac_pair2_kernel on 512 threads x 30 chunks, 256 VGPRs per wave): built next
     // to a 1024-thread main layout, taken by calls whose batch is larger than the one-utterance kernel's staged schedule holds
-    // (crf_kernels.hip use_facp).  It has its own rows, entries and grad-pass lists, so a call works with one of the two throughout.
+    // (crf_host.hip use_facp).  It has its own rows, entries and grad-pass lists, so a call works with one of the two throughout.
     FacDev facp{};
     FacHostCopy fhp;
     int ncu = 256;                      // compute units of the graph's device (0 / host-only: 256)
@@ -377,39 +386,71 @@ inline bool opt_on(Opt k) { return opt(k, 0) != 0; }
 int opt_set(const char *key, int value, bool unset);   // CRF_OK or CRF_ERR_ARG (unknown key)
 const char *opt_list();                             // "name: doc\n" of every switch
 
+// ---------------------------------------------------------------------------------------------
+// The graph compiler's host side (graph_compile.cpp, arc_streams.cpp, res_layout.cpp)
+// ---------------------------------------------------------------------------------------------
+typedef std::vector<std::vector<std::pair<int, float>>> ArcRows;   // per row its arcs (index, exp(weight))
+
+// The INTERMEDIATE graph every table and layout is built from (graph_compile.cpp number_pairs): the arcs grouped by PAIR =
+// distinct (label, destination state), the pairs numbered in (label, destination) order, so the pairs of a label are a contiguous range.
+// Weights are exponentiated here, once per arc, after the re-gauging.
+struct PairGraph {
+    int S = 0, P = 0, max_label = 0;
+    std::vector<int> pair_dst, pair_lab;    // [P]
+    ArcRows in_arcs_of_pair;                // [P] (source state, exp(weight)), in arc order
+    ArcRows out_arcs_of_state;              // [S] (pair, exp(weight)), in arc order
+    std::vector<int> arc_pair;              // [A] pair of each arc
+    std::vector<float> w_lin;               // [A] exp(weight)
+    std::vector<float> start_lin, end_lin;  // [S] exp(start weight), exp(end weight)
+};
+// host side of BatchDev: the utterance-minor tables (arc_streams.cpp build_batch_tables)
+struct BatchHost {
+    std::vector<int2> farcs, barcs;
+    std::vector<int4> stp, frow, brow;
+    std::vector<int> frow_d, brow_s, lab_off;
+};
+
+inline unsigned wbits(float w) { unsigned b; memcpy(&b, &w, 4); return b; }   // a weight as the tables hold it
+// Copies a table to the graph's device, the allocation owned by the graph; a host-only graph (h->device < 0) gets a null pointer.
+template <typename T>
+int upload(HostGraph *h, const std::vector<T> &v, const T **out) {
+    if (h->device < 0) { *out = nullptr; return CRF_OK; }
+    void *d = nullptr;
+    hipError_t e = hipMalloc(&d, std::max<size_t>(v.size(), 1) * sizeof(T));
+    if (e != hipSuccess) { set_error(std::string("hipMalloc: ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
+    h->allocs.push_back(d);
+    if (!v.empty() && (e = hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice)) != hipSuccess) {
+        set_error(std::string("hipMemcpy: ") + hipGetErrorString(e)); return CRF_ERR_HIP;
+    }
+    *out = (const T *)d;
+    return CRF_OK;
+}
+
 // Builds pairs, both ELL tables and the grad-pass chunk tables, and uploads them to `device`.
 int compile_graph(int64_t S, int64_t A, const int32_t *src, const int32_t *dst, const int32_t *lab,
                   const float *w, const float *start_w, const float *end_w, int device, HostGraph **out);
+// The utterance-minor tables and, for T o LM graphs, their factored rows (fb->ok = 0: none).
+void build_batch_tables(const PairGraph &g, BatchHost *bt, FacBatchH *fb);
 // Builds the resident layout (smallest K in {1,2,4} that fits the register budget) into h->dev.res and
 // uploads it (unless h->device < 0).  Returns CRF_OK with res.K == 0 when the graph does not fit.
-int build_resident(HostGraph *h, int S, int P, const std::vector<int> &pair_dst, const std::vector<int> &pair_lab,
-                   const std::vector<std::vector<std::pair<int, float>>> &in_arcs_of_pair,
-                   const std::vector<std::vector<std::pair<int, float>>> &out_arcs_of_state,
-                   const std::vector<float> &start_lin, const std::vector<float> &end_lin,
-                   const std::vector<int> &label_sorted_pairs);
+int build_resident(HostGraph *h, const PairGraph &g);
 // Cuts a label-sorted list (labels[i] = label of entry i) into chunks of at most `cap` entries within one label; returns their number
 // (both outputs null: counts only).  The grad-pass lists of every layout.
 int cut_label_chunks(const std::vector<int> &labels, int max_label, int cap, std::vector<int> *chunk_off, std::vector<int> *lab_chunk_off);
 // Builds the factored layout into h->dev.fac (fac.ok = 0 when the graph has no such structure or does not fit), and beside a
 // main layout that the two-utterance kernel does not take as it is, that kernel's own layout into h->facp.
-int build_factored(HostGraph *h, int S, int P, const std::vector<int> &pair_dst, const std::vector<int> &pair_lab,
-                   const std::vector<std::vector<std::pair<int, float>>> &in_arcs_of_pair,
-                   const std::vector<std::vector<std::pair<int, float>>> &out_arcs_of_state,
-                   const std::vector<float> &start_lin, const std::vector<float> &end_lin);
+int build_factored(HostGraph *h, const PairGraph &g);
 void fac_geom_public(const HostGraph *h, int64_t *fac_geom, int64_t *fac_chunks);   // crf_graph_stats: the built geometry's public numbers (-1 / 0: none)
-// Arc streams for UL (8, 16, 32 or 64) utterances per group cut into about `want` tasks per direction, built and uploaded
-// on first use (thread-safe; a graph keeps every variant it has been asked for).
 int debug_emulate_factored(const HostGraph *h, int T, unsigned seed, double *out3, int which = 0);   // which = 1: the two-utterance kernel's layout (HostGraph::facp)
 int debug_emulate_resident(const HostGraph *h, int T, unsigned seed, double *out3);
+// Arc streams for UL (8, 16, 32 or 64) utterances per group cut into about `want` tasks per direction, built and uploaded
+// on first use (thread-safe; a graph keeps every variant it has been asked for).
 int ensure_stream_tables(HostGraph *h, int UL, int want, const StreamDev **out);
 bool stream_fac(const HostGraph *h, int UL);   // factored streams for groups of UL utterances?
 // Host-side construction + self-check of the arc streams (tests; works on host-only graphs).
 int debug_check_streams(const HostGraph *h, int UL, int want, int64_t *out4);
 // Host-side check of bat_decode for one (grid, #combos): 0 = every (combo, chunk) exactly once.
 int debug_check_decode(int nslot, int ncombo);
-int read_fst_file(const char *path, int64_t *S, std::vector<int32_t> *src, std::vector<int32_t> *dst,
-                  std::vector<int32_t> *lab, std::vector<float> *w, std::vector<float> *start_w,
-                  std::vector<float> *end_w);
 
 }  // namespace crf
 

@@ -216,9 +216,7 @@ struct BatchParams {
     int *err;                      // ... its time-out word (crf_batch_cost_kernel turns the costs into NaN)
 };
 constexpr int kBatThreads = 256, kBatWaves = kBatThreads / kWave;
-constexpr int kStreamBatch = 4, kStreamChunk = 128;   // steps per batch; batches * AL per 4 KB chunk (batches in flight: template parameter D)
-constexpr int kStreamBundles = 8;                     // bundles per task at most (plain streams; factored: crf_internal.h stream_max_bundles)
-constexpr int kStreamRecB = kStreamChunk * 32;        // bytes of a chunk of records
+// (kStreamBatch, kStreamChunk, kStreamBundles, kStreamRecB: crf_internal.h, shared with the host's task cutter)
 // Factored streams (NM = 3 descriptor words per row, crf_internal.h StreamDev): the ring holds NR values per row instead of the
 // one emission row -- forward {e[label 0], e[label 1], U of the row's couple}, backward {e[label 0], e[label 1], z of the two
 // extra arcs} -- all known from the descriptor, so all requested a bundle ahead like the emissions; epi gets them as e[NR].

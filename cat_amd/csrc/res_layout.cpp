@@ -2,7 +2,7 @@
 // graph (crf_internal.h: ResDev).  One recursion (forward or backward) of one utterance is split over
 // K compute units; every thread keeps its share of the arc list in VGPRs for the whole kernel, so the
 // per-frame work is LDS gathers + FMAs only and nothing is streamed from L2 (the streaming kernels of
-// crf_kernels.hip remain the fallback for graphs that do not fit).
+// k_chain.hip remain the fallback for graphs that do not fit).
 //
 // No reference counterpart: the reference keeps one flat arc array per direction in global memory and
 // re-reads it in every one of its T kernel launches (den_calculate.cu:309-355, 75-103, 189-227).
@@ -19,7 +19,7 @@
 namespace crf {
 namespace {
 
-typedef std::vector<std::vector<std::pair<int, float>>> Rows;
+typedef ArcRows Rows;
 
 // geometry of one resident workgroup: threads, waves, chunks per thread (registers), words per thread
 struct Geom { int threads, waves, nch, words, maxsl, multilane; };   // maxsl: slices per wave (0 = any number); multilane: long rows on adjacent lanes
@@ -51,7 +51,7 @@ inline int chunks_of(size_t deg) { return std::max(1, (int)((deg + kResW - 1) / 
 // Step 1: decide where every row lives (CU, wave, slice, lane) from the row LENGTHS only.
 struct SliceAt { int k, w, c0, len, rid0; std::vector<int> rows; int ord; int lg = 0; };   // ord: number of the slice within its wave;
                                                       // lg > 0: every row of the slice is cut into 2^lg pieces on 2^lg adjacent lanes
-// Waves [0, emis_waves) of a factored workgroup also stage the next frame's emission row (crf_kernels.hip fac_chain_body, `pre_w`): the
+// Waves [0, emis_waves) of a factored workgroup also stage the next frame's emission row (k_fac_body.h fac_chain_body, `pre_w`): the
 // request at the frame top, and in the tail a wait for it that -- vmcnt counts in order -- includes the acknowledgement of the wave's own
 // write-through row stores, ~400 cycles in which that wave alone stands in front of the frame barrier (timing build, round 5: wave 0 arrived
 // 270 cycles behind every other wave of the forward recursion, 6 % of the frame).  The placement charges those waves kEmisCost chunks and
@@ -650,26 +650,13 @@ std::vector<int> assign_owner(int S, int K, const std::vector<int64_t> &load) {
     return owner;
 }
 
-template <typename T>
-int up(HostGraph *h, const std::vector<T> &v, const T **out) {
-    if (h->device < 0) { *out = nullptr; return CRF_OK; }
-    void *d = nullptr;
-    size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-    hipError_t e = hipMalloc(&d, bytes);
-    if (e != hipSuccess) { set_error(std::string("hipMalloc: ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
-    h->allocs.push_back(d);
-    if (!v.empty() && (e = hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice)) != hipSuccess) {
-        set_error(std::string("hipMemcpy: ") + hipGetErrorString(e)); return CRF_ERR_HIP;
-    }
-    *out = (const T *)d;
-    return CRF_OK;
-}
-
 }  // namespace
 
-int build_resident(HostGraph *h, int S, int P, const std::vector<int> &pair_dst, const std::vector<int> &pair_lab,
-                   const Rows &in_arcs_of_pair, const Rows &out_arcs_of_state, const std::vector<float> &start_lin,
-                   const std::vector<float> &end_lin, const std::vector<int> &label_sorted_pairs) {
+int build_resident(HostGraph *h, const PairGraph &g) {
+    const int S = g.S, P = g.P;
+    const std::vector<int> &pair_dst = g.pair_dst, &pair_lab = g.pair_lab;
+    const Rows &in_arcs_of_pair = g.in_arcs_of_pair, &out_arcs_of_state = g.out_arcs_of_state;
+    const std::vector<float> &start_lin = g.start_lin, &end_lin = g.end_lin;
     ResDev &R = h->dev.res;
     R = ResDev{};
     if (opt_on(kOpt_no_resident)) return CRF_OK;
@@ -820,15 +807,9 @@ int build_resident(HostGraph *h, int S, int P, const std::vector<int> &pair_dst,
     for (int K = 1; K <= kResMaxK; K *= 2) {
         if (K < min_k) continue;
         std::vector<int> xoff, zoff;
-        // forward rows = pairs, taken in label-sorted order so that sub-rows come out label-sorted; each
-        // produces (a partial sum of) x[dst]
-        Rows fin(P);
-        std::vector<int> fin_key(P), fin_tgt(P);
-        for (int j = 0; j < P; ++j) {
-            const int p = label_sorted_pairs[j];
-            fin[j] = in_arcs_of_pair[p]; fin_key[j] = pair_dst[p]; fin_tgt[j] = pair_dst[p];
-        }
-        Dir F = try_dir(fin, fin_key, fin_tgt, K, gkey_f, &xoff);
+        // forward rows = pairs, taken as they are numbered: the PairGraph's pairs are in (label, destination) order, so the sub-rows come
+        // out label-sorted (the grad-pass lists below rely on it); each produces (a partial sum of) x[dst]
+        Dir F = try_dir(in_arcs_of_pair, pair_dst, pair_dst, K, gkey_f, &xoff);
         if (!F.ok) continue;
         // backward rows = states; a state entered with n > 1 labels is listed n times (same arcs), once per
         // pair it produces z for, so that every row writes exactly one entry (only the first copy feeds the
@@ -848,7 +829,7 @@ int build_resident(HostGraph *h, int S, int P, const std::vector<int> &pair_dst,
         if (!Bk.ok) continue;
         const DirOut &fo = F.o, &bo = Bk.o;
         const int NRf = (int)F.sub_of.size(), NRb = (int)Bk.sub_of.size();
-        auto pair_of_sub = [&](int r) { return label_sorted_pairs[F.sub_of[r]]; };
+        auto pair_of_sub = [&](int r) { return F.sub_of[r]; };
 
         // ---- row metadata and side tables
         const int Rf = fo.cu_row_off[K], Rb = bo.cu_row_off[K];
@@ -908,15 +889,15 @@ int build_resident(HostGraph *h, int S, int P, const std::vector<int> &pair_dst,
         h->res_stats.slots_f = fo.slots; h->res_stats.slots_b = bo.slots;
         h->res_stats.conflicts_f = fo.conflicts; h->res_stats.conflicts_b = bo.conflicts;
         int rc;
-        if ((rc = up(h, fo.arcs, &R.f.arcs)) || (rc = up(h, fo.wave_info, &R.f.wave_info)) ||
-            (rc = up(h, flab, &R.f.row_lab)) || (rc = up(h, fo.cu_row_off, &R.f.cu_row_off)) ||
-            (rc = up(h, xoff, &R.f.own_off)) || (rc = up(h, F.ex_cnt, &R.f.ex_cnt)) || (rc = up(h, Bk.ex_cnt, &R.b.ex_cnt)) || (rc = up(h, bo.arcs, &R.b.arcs)) ||
-            (rc = up(h, bo.wave_info, &R.b.wave_info)) || (rc = up(h, blab, &R.b.row_lab)) ||
-            (rc = up(h, bo.cu_row_off, &R.b.cu_row_off)) || (rc = up(h, zoff, &R.b.own_off)) ||
-            (rc = up(h, x_start, &R.x_start)) || (rc = up(h, x_end, &R.x_end)) || (rc = up(h, z_lab, &R.z_lab)) ||
-            (rc = up(h, z_end, &R.z_end)) || (rc = up(h, brow_start, &R.brow_start)) ||
-            (rc = up(h, brow_end, &R.brow_end)) || (rc = up(h, bcsr, &R.bcsr)) || (rc = up(h, gq, &R.gq)) ||
-            (rc = up(h, gb, &R.gb)) || (rc = up(h, gchunk, &R.chunk_off)) || (rc = up(h, glab, &R.lab_chunk_off)))
+        if ((rc = upload(h, fo.arcs, &R.f.arcs)) || (rc = upload(h, fo.wave_info, &R.f.wave_info)) ||
+            (rc = upload(h, flab, &R.f.row_lab)) || (rc = upload(h, fo.cu_row_off, &R.f.cu_row_off)) ||
+            (rc = upload(h, xoff, &R.f.own_off)) || (rc = upload(h, F.ex_cnt, &R.f.ex_cnt)) || (rc = upload(h, Bk.ex_cnt, &R.b.ex_cnt)) || (rc = upload(h, bo.arcs, &R.b.arcs)) ||
+            (rc = upload(h, bo.wave_info, &R.b.wave_info)) || (rc = upload(h, blab, &R.b.row_lab)) ||
+            (rc = upload(h, bo.cu_row_off, &R.b.cu_row_off)) || (rc = upload(h, zoff, &R.b.own_off)) ||
+            (rc = upload(h, x_start, &R.x_start)) || (rc = upload(h, x_end, &R.x_end)) || (rc = upload(h, z_lab, &R.z_lab)) ||
+            (rc = upload(h, z_end, &R.z_end)) || (rc = upload(h, brow_start, &R.brow_start)) ||
+            (rc = upload(h, brow_end, &R.brow_end)) || (rc = upload(h, bcsr, &R.bcsr)) || (rc = upload(h, gq, &R.gq)) ||
+            (rc = upload(h, gb, &R.gb)) || (rc = upload(h, gchunk, &R.chunk_off)) || (rc = upload(h, glab, &R.lab_chunk_off)))
             return rc;
         ResHostCopy &C = h->rh;
         C.farcs = fo.arcs; C.barcs = bo.arcs; C.fwi = fo.wave_info; C.bwi = bo.wave_info; C.flab = flab; C.blab = blab;
@@ -979,13 +960,6 @@ constexpr FacGeomDesc kFacGeoms[kFacGeomCount] = {
     /* kFg512Pair2   */ {{kResThreads, kResWaves, kResNCH, kResWords, 10, 1}, false, 1, true, 8, false, 8, -1, -1, kResNCH},
 };
 
-struct FacInput {   // the graph as compile_graph hands it over
-    int S, P;
-    const std::vector<int> &pair_dst, &pair_lab;
-    const Rows &in_arcs_of_pair, &out_arcs_of_state;
-    const std::vector<float> &start_lin, &end_lin;
-};
-static unsigned wbits(float w) { unsigned b; memcpy(&b, &w, 4); return b; }
 static bool verbose() { return opt_on(kOpt_verbose); }
 
 // One backward row: one state, or two matched states with common out-arcs `arcs` (pair, weight) and at most one extra arc each.
@@ -1009,7 +983,7 @@ struct FacStructure {
     int64_t nmatched = 0, ntail = 0, nfused = 0;   // statistics
 };
 
-static void analyse_factored(const FacInput &in, FacStructure *st) {
+static void analyse_factored(const PairGraph &in, FacStructure *st) {
     const int S = in.S, P = in.P;
     const std::vector<int> &pair_dst = in.pair_dst, &pair_lab = in.pair_lab;
     const Rows &in_arcs_of_pair = in.in_arcs_of_pair, &out_arcs_of_state = in.out_arcs_of_state;
@@ -1242,7 +1216,7 @@ struct FacPlaced {
     int xlist_off[3] = {0, 0, 0};       // two CUs: C.xlist holds the entries CU 0 fetches, then those CU 1 fetches
     std::vector<int> fpos, zpos;        // pair -> position in the Q row (main rows [0, Rf), their tails [Rf, 2 Rf)); state -> BP position 2 * rid + output
 };
-static Placed place_forward(const FacInput &in, const FacStructure &st, const Attempt &at, FacPlaced *pl) {
+static Placed place_forward(const PairGraph &in, const FacStructure &st, const Attempt &at, FacPlaced *pl) {
     const Geom &gm = at.g.gm;
     const int S = in.S, K = at.K;
     const std::vector<int> &tail_of = st.tail_of, &main_rows = st.main_rows;
@@ -1347,7 +1321,7 @@ static Placed place_forward(const FacInput &in, const FacStructure &st, const At
     return {};
 }
 
-static Placed place_backward(const FacInput &in, const FacStructure &st, const Attempt &at, FacPlaced *pl) {
+static Placed place_backward(const PairGraph &in, const FacStructure &st, const Attempt &at, FacPlaced *pl) {
     const Geom &gm = at.g.gm;
     const int S = in.S, K = at.K;
     const std::vector<BRow> &brow = st.brow;
@@ -1425,7 +1399,7 @@ static Placed place_backward(const FacInput &in, const FacStructure &st, const A
 }
 
 // Grad-pass pairs, statistics, the LDS budget, then the device tables and their host copy (main layout: h->dev.fac / fh, second: facp / fhp).
-static Placed finish_factored(HostGraph *h, const FacInput &in, const FacStructure &st, const Attempt &at, bool second, FacPlaced *pl) {
+static Placed finish_factored(HostGraph *h, const PairGraph &in, const FacStructure &st, const Attempt &at, bool second, FacPlaced *pl) {
     const Geom &gm = at.g.gm;
     const FacPlaced::Dir &f = pl->f, &b = pl->b;
     const int K = at.K, Rf = f.R, Rb = b.R, Gf = f.G, Gb = b.G;
@@ -1480,12 +1454,12 @@ static Placed finish_factored(HostGraph *h, const FacInput &in, const FacStructu
     C.farcs = fo.arcs; C.barcs = bo.arcs; C.fwi = fo.wave_info; C.bwi = bo.wave_info; C.gchunk = st.gchunk; C.glab = st.glab;
     C.start_lin = in.start_lin; C.end_lin = in.end_lin; C.words = gm.words;
     int rc;
-    if ((rc = up(h, C.farcs, &F.f.arcs)) || (rc = up(h, C.fwi, &F.f.wave_info)) || (rc = up(h, C.barcs, &F.b.arcs)) ||
-        (rc = up(h, C.bwi, &F.b.wave_info)) || (rc = up(h, C.frow_meta, &F.frow_meta)) ||
-        (rc = up(h, C.x_start, &F.x_start)) || (rc = up(h, C.x_end, &F.x_end)) || (rc = up(h, C.brow_meta, &F.brow_meta)) ||
-        (rc = up(h, C.z_lab, &F.z_lab)) || (rc = up(h, C.z_end, &F.z_end)) || (rc = up(h, C.brow_start, &F.brow_start)) ||
-        (rc = up(h, C.brow_end, &F.brow_end)) || (rc = up(h, C.bx_idx, &F.bx_idx)) || (rc = up(h, C.bx_w, &F.bx_w)) || (rc = up(h, C.gq, &F.gq)) || (rc = up(h, C.gb, &F.gb)) ||
-        (rc = up(h, C.gchunk, &F.chunk_off)) || (rc = up(h, C.glab, &F.lab_chunk_off)) || (rc = up(h, C.xlist, &F.xlist)))
+    if ((rc = upload(h, C.farcs, &F.f.arcs)) || (rc = upload(h, C.fwi, &F.f.wave_info)) || (rc = upload(h, C.barcs, &F.b.arcs)) ||
+        (rc = upload(h, C.bwi, &F.b.wave_info)) || (rc = upload(h, C.frow_meta, &F.frow_meta)) ||
+        (rc = upload(h, C.x_start, &F.x_start)) || (rc = upload(h, C.x_end, &F.x_end)) || (rc = upload(h, C.brow_meta, &F.brow_meta)) ||
+        (rc = upload(h, C.z_lab, &F.z_lab)) || (rc = upload(h, C.z_end, &F.z_end)) || (rc = upload(h, C.brow_start, &F.brow_start)) ||
+        (rc = upload(h, C.brow_end, &F.brow_end)) || (rc = upload(h, C.bx_idx, &F.bx_idx)) || (rc = upload(h, C.bx_w, &F.bx_w)) || (rc = upload(h, C.gq, &F.gq)) || (rc = upload(h, C.gb, &F.gb)) ||
+        (rc = upload(h, C.gchunk, &F.chunk_off)) || (rc = upload(h, C.glab, &F.lab_chunk_off)) || (rc = upload(h, C.xlist, &F.xlist)))
         return {Fit::kGiveUp, 0, false, rc};
     F.ok = 1;
     if (!second) h->fac_stats.ok = 1;
@@ -1495,7 +1469,7 @@ static Placed finish_factored(HostGraph *h, const FacInput &in, const FacStructu
 
 // One geometry on K CUs: first with the second copy of the gathered entries in both directions, then without it in the direction(s)
 // that do not fit with it.  What comes back is built / next geometry / give up.
-static Placed place_factored(HostGraph *h, const FacInput &in, const FacStructure &st, const FacGeomDesc &g, int K, bool short_only, bool more, bool second) {
+static Placed place_factored(HostGraph *h, const PairGraph &in, const FacStructure &st, const FacGeomDesc &g, int K, bool short_only, bool more, bool second) {
     Placed p{Fit::kLessDup, 3};
     while (p.fit == Fit::kLessDup) {
         const Attempt at{g, K, short_only, more, p.dup_mask};
@@ -1520,13 +1494,10 @@ void fac_geom_public(const HostGraph *h, int64_t *fac_geom, int64_t *fac_chunks)
 // its long rows; kFg768Table21; kFg768Table on TWO CUs per recursion (not with fac_no_k2; they stay on 768 threads: on 1024 x 15 -- fac_k2 with
 // fac_threads = 1024 -- the recursions measured SLOWER, 4.13 -> 4.31 / 5.84 -> 6.3 ms at H = 3 072 / 4 096: the hand-off's polls and granule stores are
 // per wave, and there are a third more waves).  The other switches replace that order by one or two geometries, as listed below.
-int build_factored(HostGraph *h, int S, int P, const std::vector<int> &pair_dst, const std::vector<int> &pair_lab,
-                   const Rows &in_arcs_of_pair, const Rows &out_arcs_of_state, const std::vector<float> &start_lin,
-                   const std::vector<float> &end_lin) {
+int build_factored(HostGraph *h, const PairGraph &in) {
     h->dev.fac = h->facp = FacDev{};
     h->fac_geom_id = -1;
     if (opt_on(kOpt_no_factored) || opt_on(kOpt_no_resident)) return CRF_OK;
-    const FacInput in{S, P, pair_dst, pair_lab, in_arcs_of_pair, out_arcs_of_state, start_lin, end_lin};
     FacStructure st;
     analyse_factored(in, &st);
     if (st.why) { gave_up(st.why); return CRF_OK; }

@@ -7,7 +7,7 @@
                        token n-gram acceptor; what bench.py and the parity tests run on, because the
                        real pipeline (cat/utils/tool/prep_den_lm.sh:40-51) needs Kaldi + OpenFst.
 
-The loader used by the product is the C++ one in cat_amd/csrc/fst_graph.cpp (``crf_graph_create``);
+The loader used by the product is the C++ one in cat_amd/csrc/fst_read.cpp (``crf_graph_create``);
 files written here go through it, so writer and loader check each other.
 """
 import struct

@@ -347,7 +347,7 @@ const char *crf_last_den_kernel(void);
 int crf_last_call_streams(void);
 /* What the side stream of the (device, caller stream) context of this thread's last call is: "plain (candidate 2)", "priority-low
  * (candidate 9)", "cu-mask (candidate 13) + third stream", "none (candidate 13)" -- the kind of stream that was found to run
- * beside the caller's and how many candidates had been probed by then (crf_kernels.hip find_beside).  The reference runs everything
+ * beside the caller's and how many candidates had been probed by then (crf_host.hip find_beside).  The reference runs everything
  * on the caller's stream (binding.cpp:75,102) and has nothing to report. */
 const char *crf_last_side_stream(void);
 /* How many utterances of this thread's last call were redone by a fallback: out2[0] = denominator (crf_robust_den_kernel: the scaled fp32

@@ -1,7 +1,7 @@
 """oracle/fst_io.py -- independent OpenFst `vector`/`standard` binary reader for the ORACLE side.
 
 TEST INFRASTRUCTURE ONLY (see oracle/crf_oracle.c header).  The product has its own reader in
-cat_amd/csrc/fst_graph.cpp; tests cross-check the two.
+cat_amd/csrc/fst_read.cpp; tests cross-check the two.
 
 Restates what the reference obtains through OpenFst 1.6.7 (un-vendored, fetched by
 src/ctc_crf/Makefile:10-14) at its call sites src/ctc_crf/gpu_den/fst_read.cc:23-60:

@@ -116,7 +116,7 @@ def test_factoring_survives_openfst_style_rewrites(tmp_path):
     state numbers and arc order are whatever those tools leave.  The graph compiler must find the T o LM structure
     (factored layout: one CU per recursion) under ANY numbering and arc order, and in a weight-pushed graph too (potentials
     moved along the arcs -- determinizestar does not do this to an input-deterministic graph, but other OpenFst tools
-    would): fst_graph.cpp regauge_pushed.  Host-only compile: no GPU needed."""
+    would): graph_compile.cpp regauge_pushed.  Host-only compile: no GPU needed."""
     from cat_amd.ctc_crf import _C
     from tests.util import crf_env, transform_graph
 
@@ -166,7 +166,7 @@ def test_reference_fixture_layout(golden_dir):
 
 
 def test_factored_rows_of_the_utterance_minor_kernels(tmp_path, golden_dir):
-    """T o LM graphs get FACTORED rows for the utterance-minor kernels (fst_graph.cpp build_batch_factored: an entry U = a[tail] +
+    """T o LM graphs get FACTORED rows for the utterance-minor kernels (arc_streams.cpp build_batch_factored: an entry U = a[tail] +
     a[main] per couple of states, the tail row folded into the main row, one backward row per couple).  Host check
     (crf_debug_facbatch_check): one step of both recursions through the factored rows equals the step through the plain tables
     on random vectors, every one-pair row is produced exactly once, descriptors carry the plain tables' pairs and labels.
@@ -210,7 +210,7 @@ def test_factored_rows_of_the_utterance_minor_kernels(tmp_path, golden_dir):
 
 @pytest.mark.parametrize("UL", [8, 16, 32, 64])
 def test_arc_streams_of_the_utterance_minor_kernels(tmp_path, golden_dir, UL):
-    """The arc streams the utterance-minor kernels walk (fst_graph.cpp: build_stream_host) are built on the HOST for several
+    """The arc streams the utterance-minor kernels walk (arc_streams.cpp: build_stream_host) are built on the HOST for several
     graphs and checked record by record against the graph's row tables (crf_debug_stream_check): every row with one entering
     pair once, its records = its arcs in order, end-of-bundle flags, at most 8 bundles per task; the other rows in the rest
     list.  Graphs: T o LM synthetic, an estimated n-gram graph with rows of hundreds of arcs, random general graphs (states

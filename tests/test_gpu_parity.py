@@ -472,7 +472,7 @@ def test_rewritten_den_lm_vs_oracle(crf, tmp_path, push):
     """A den_lm as OpenFst tools leave it (cat/utils/tool/prep_den_lm.sh:48-49): states re-numbered, arcs of a state in
     another order, optionally weights pushed along the arcs.  Same loss and gradient as the ORIGINAL graph's oracle (the
     rewrites preserve every path weight; pushing only up to fp32 rounding of the new weights), and the rewritten graph
-    keeps the factored layout (a pushed one after the compiler has re-gauged it, fst_graph.cpp regauge_pushed)."""
+    keeps the factored layout (a pushed one after the compiler has re-gauged it, graph_compile.cpp regauge_pushed)."""
     from tests.util import transform_graph
     g, p = small_synth(tmp_path, 24, 96, 8, 13)
     q = os.path.join(str(tmp_path), "rewritten.fst")
@@ -604,7 +604,7 @@ def test_single_frame_shrink_window(crf, tmp_path, nats, mode):
     the fp64 oracle's (the reference's log-domain arithmetic, den_calculate.cu:29-35, has no such window).
     110 nats, every kernel family: what this test FOUND in round 5 -- the streaming grad kernels took 2^-64 out of e' * sum(q * b) before
     normalising the frame, and between ~100 and 131 nats that product left the fp32 range although recursions, loss and flags were fine:
-    the gradient of rounds 1 - 4 was 90 % off there, silently (kGradDescale, crf_kernels.hip)."""
+    the gradient of rounds 1 - 4 was 90 % off there, silently (kGradDescale, crf_device.h)."""
     g, p = small_synth(tmp_path, 9, 24, 5, 7)             # tokens 1..8; label 9 exists only in the network output
     B, T, V = 3, 40, 10
     rng = np.random.default_rng(22)

@@ -1,4 +1,4 @@
-"""CPU test of the staged grad pass's PLAN (round 5: one launch for all stages, crf_kernels.hip crf_grad_den_kernel `gd_persist`).
+"""CPU test of the staged grad pass's PLAN (round 5: one launch for all stages, k_grad.hip crf_grad_den_kernel `gd_persist`).
 
 The reference has no such thing: its beta kernel computes a frame's gradient when it gets there (den_calculate.cu:189-227, one launch per
 frame).  Here the den half of the grad pass follows the two recursions, which work towards each other, in STAGES: a 16-frame block belongs to

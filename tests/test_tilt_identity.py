@@ -1,4 +1,4 @@
-"""The identity behind the tilted numerator chains of the HIP kernels (cat_amd/csrc/crf_kernels.hip: ctc_rho, ctc_forward, ctc_backward;
+"""The identity behind the tilted numerator chains of the HIP kernels (cat_amd/csrc/k_chain.hip: ctc_rho, ctc_forward, ctc_backward;
 reference recursion: src/ctc_crf/gpu_ctc/gpu_ctc_kernels.h:87-458), restated in numpy fp64 and checked against the oracle's plain CTC:
 
     A'_t[s] = A_t[s] rho^s,   Bx'_t[s] = Bx_t[s] rho^(Sx-1-s)

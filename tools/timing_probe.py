@@ -1,4 +1,4 @@
-"""tools/timing_probe.py -- decode the in-kernel phase stamps of a TIMING build (see crf_kernels.hip CRF_TM).
+"""tools/timing_probe.py -- decode the in-kernel phase stamps of a TIMING build (see crf_device.h CRF_TM).
 
     CRF_BUILD_DEFS=-DCRF_TIMING python -m cat_amd.build --force     # here (cross-compile)
     gpurun -- 'python tools/timing_probe.py'                        # on the GPU box

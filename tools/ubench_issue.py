@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """tools/ubench_issue.py -- writes tools/ubench_issue.hip: issue-rate micro-benchmarks for the frame loop of the factored
-recursions (crf_kernels.hip fac_chain_body), whole loops in inline assembly so that nothing is rescheduled:
+recursions (k_fac_body.h fac_chain_body), whole loops in inline assembly so that nothing is rescheduled:
 
   valu_sdwa     32 independent v_add_u32_sdwa (the address unpack of a gather)
   valu_pkfma    16 independent v_pk_fma_f32
