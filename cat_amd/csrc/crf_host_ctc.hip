@@ -1,8 +1,9 @@
-// cat_amd/csrc/crf_host_ctc.hip -- the host side of the three surfaces on the plain CTC lattice, which share nothing with the loss call
-// (crf_host.hip) but crf_host_util.h: forced alignment (crf_ctc_align*, k_align.hip), hypothesis scores (crf_ctc_score*, k_score.hip) and
-// sampled / best-path label sequences (crf_ctc_sample, k_sample.hip) -- argument checks, workspace sections, kernel choice, the C-ABI
-// entry points of include/ctc_crf_hip.h.  Every error is answered before any HIP call.  The activations are read in place in either
-// layout and -- the *_logits entry points and crf_ctc_sample -- in f32, bf16 or f16.
+// cat_amd/csrc/crf_host_ctc.hip -- the host side of the surfaces on the plain CTC lattice, which share nothing with the loss call
+// (crf_host.hip) but crf_host_util.h: forced alignment (crf_ctc_align*, k_align.hip), hypothesis scores (crf_ctc_score*, k_score.hip), their
+// weighted gradient (crf_ctc_score_grad, k_score_grad.hip) and sampled / best-path label sequences (crf_ctc_sample, k_sample.hip) --
+// argument checks, workspace sections, kernel choice, the C-ABI entry points of include/ctc_crf_hip.h.  Every error is answered before
+// any HIP call.  The activations are read in place in either layout and -- the *_logits entry points and crf_ctc_sample -- in f32, bf16
+// or f16.
 #include <type_traits>
 
 #include "crf_device.h"
@@ -13,6 +14,7 @@ namespace crf {
 
 static thread_local const char *g_sample_kernel = ""; // template instantiation of the row kernel of this thread's last crf_ctc_sample (crf_last_sample_kernel)
 static thread_local const char *g_score_kernel = "";  // ... of the kernel of this thread's last crf_ctc_score / crf_ctc_score_logits (crf_last_score_kernel)
+static thread_local const char *g_score_grad_kernel = "";   // ... of the alpha pass of this thread's last crf_ctc_score_grad (crf_last_score_grad_kernel)
 
 // ---- what the three surfaces share ----
 // f(E{}) with the element type of dtype 0 (f32), 1 (bf16), 2 (f16)
@@ -47,9 +49,9 @@ static int check_ws(int64_t ws_bytes, int64_t need) {
     if (ws_bytes < need) { set_error("workspace too small: need " + std::to_string(need)); return CRF_ERR_WORKSPACE; }
     return CRF_OK;
 }
-// their workspaces: one or two sections, laid down as the loss call's are (crf_host_util.h)
+// their workspaces: one to three sections, laid down as the loss call's are (crf_host_util.h)
 struct SideWs {
-    WsSection sec[2];
+    WsSection sec[3];
     int nsec = 0;
     int64_t total = 0, gap = ws_gap_bytes();
     SideWs &add(const char *name, int64_t bytes) { sec[nsec++] = WsSection{name, total, bytes}; total = al(total + bytes) + gap; return *this; }
@@ -163,6 +165,42 @@ static int score_call(const char *who, const void *act, int dtype, int time_majo
     return with_dtype(dtype, [&](auto e) { return launch_score<decltype(e), true>(p, st, max_hyp_len); });
 }
 
+// ---- the weighted gradient of the hypothesis scores (k_score_grad.hip) ----
+// its workspace: the stored alphas / weighted occupancies [H][T][64 NR] (NR from the call's longest hypothesis, as the score kernels'), then
+// the H scores.  < 0 with the message set.
+static int64_t score_grad_ws_bytes(int64_t B, int64_t H, int64_t T, int64_t V, int64_t max_hyp_len, SideWs *out = nullptr) {
+    if (B <= 0 || T <= 0 || V <= 0 || V > INT32_MAX) { set_error("crf_ctc_score_grad: bad B/T/V"); return -CRF_ERR_ARG; }
+    if (H <= 0 || H > INT32_MAX || max_hyp_len < 0) { set_error("crf_ctc_score_grad: bad H/max_hyp_len"); return -CRF_ERR_ARG; }
+    if (B * T > INT32_MAX) { set_error("crf_ctc_score_grad: B * T > INT32_MAX"); return -CRF_ERR_ARG; }
+    if (max_hyp_len > kScoreGradMaxLen) { set_error("crf_ctc_score_grad: hypothesis length > " + std::to_string(kScoreGradMaxLen) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
+    if (V > kScoreGradMaxV) { set_error("crf_ctc_score_grad: V > " + std::to_string(kScoreGradMaxV) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
+    const int64_t S = with_nr(2 * max_hyp_len + 1, 64, [](auto nr, int) { return 64 * decltype(nr)::value; });
+    if (H > (INT64_MAX / 8) / (T * S)) { set_error("crf_ctc_score_grad: H * T * states too large"); return -CRF_ERR_ARG; }
+    SideWs w;
+    w.add("occ", H * T * S * (int64_t)sizeof(float)).add("hscore", H * (int64_t)sizeof(float));
+    if (out) *out = w;
+    return w.total;
+}
+// the four launches on one stream: crf_ctc_score's own kernel (scores into the workspace, invalid to the caller), then the three stages
+static int launch_score_grad(const ScoreGradParams &p, hipStream_t st, int64_t max_hyp_len) {
+    static const char *const names[] = {"crf_ctc_score_grad_alpha_kernel<1>", "crf_ctc_score_grad_alpha_kernel<2>", "crf_ctc_score_grad_alpha_kernel<4>", "crf_ctc_score_grad_alpha_kernel<8>"};
+    ScoreParams sp{};
+    sp.x = p.x; sp.labels = p.labels; sp.hyp_off = p.hyp_off; sp.hyp_len = p.hyp_len; sp.hyp_utt = p.hyp_utt; sp.lx = p.lx;
+    sp.B = p.B; sp.H = p.H; sp.T = p.T; sp.V = p.V; sp.blank = p.blank; sp.xs_b = p.xs_b; sp.xs_t = p.xs_t;
+    sp.score = p.hscore; sp.invalid = p.invalid;
+    const dim3 grid((unsigned)((p.H + kScoreWaves - 1) / kScoreWaves)), block(kScoreWaves * 64);
+    int rc = with_nr(2 * max_hyp_len + 1, 64, [&](auto nr, int k) {
+        constexpr int NR = decltype(nr)::value;
+        if (const int r = launch<crf_ctc_score_wave_kernel<NR, float, false>>("crf_ctc_score_wave_kernel", grid, block, 0, st, sp)) return r;
+        if (const int r = launch<crf_ctc_score_grad_alpha_kernel<NR>>(g_score_grad_kernel = names[k], grid, block, 0, st, p)) return r;
+        return launch<crf_ctc_score_grad_beta_kernel<NR>>("crf_ctc_score_grad_beta_kernel", grid, block, 0, st, p);
+    });
+    if (rc) return rc;
+    const int64_t nbt = (p.T + p.FB - 1) / p.FB;
+    return launch<crf_ctc_score_grad_reduce_kernel>("crf_ctc_score_grad_reduce_kernel", dim3((unsigned)(p.B * nbt)), dim3(kScoreGradReduceThreads),
+                                                    (size_t)p.FB * p.V * sizeof(float), st, p);
+}
+
 // ---- sampled / best-path label sequences (k_sample.hip) ----
 // the row stage over the B T frames -- 16 lanes per row up to kSampleSmallV classes, beyond a wave per row, per row V + 2 G words of
 // dynamic LDS (none for the arg-max) -- then the collapse, one wave per path, on the same stream
@@ -242,6 +280,29 @@ int crf_ctc_score_logits(const void *act, int dtype, int time_major, int blank, 
                       invalid, ws, ws_bytes, (hipStream_t)stream_);
 }
 
+int64_t crf_ctc_score_grad_workspace_bytes(int64_t B, int64_t H, int64_t T, int64_t V, int64_t max_hyp_len) {
+    return or_minus1(score_grad_ws_bytes(B, H, T, V, max_hyp_len));
+}
+
+int crf_ctc_score_grad(const float *act, int time_major, int blank, const int32_t *labels, const int32_t *hyp_off, const int32_t *hyp_len,
+                       const int32_t *hyp_utt, const int32_t *lx, const float *weight, int64_t B, int64_t H, int64_t T, int64_t V,
+                       int64_t max_hyp_len, float *score, int32_t *invalid, float *grad, void *ws, int64_t ws_bytes, void *stream_) {
+    if (!act || !labels || !hyp_off || !hyp_len || !hyp_utt || !lx || !grad || !ws) { set_error("crf_ctc_score_grad: null argument"); return CRF_ERR_ARG; }
+    SideWs w;
+    const int64_t need = score_grad_ws_bytes(B, H, T, V, max_hyp_len, &w);
+    if (need < 0) return (int)-need;
+    if (const int rc = check_blank(blank, V)) return rc;
+    if (const int rc = check_ws(ws_bytes, need)) return rc;
+    ScoreGradParams p{};
+    set_act(p, act, lx, B, T, V, blank, time_major);
+    p.labels = labels; p.hyp_off = hyp_off; p.hyp_len = hyp_len; p.hyp_utt = hyp_utt; p.H = (int)H;
+    p.score = score; p.invalid = invalid; p.weight = weight; p.grad = grad;
+    p.occ = (float *)((char *)ws + w.sec[0].off); p.hscore = (float *)((char *)ws + w.sec[1].off);
+    p.S = (int)(w.sec[0].bytes / (H * T * (int64_t)sizeof(float)));
+    p.FB = (int)std::min<int64_t>(kScoreGradFrames, std::max<int64_t>(1, kScoreGradMaxV / V));
+    return launch_score_grad(p, (hipStream_t)stream_, max_hyp_len);
+}
+
 int64_t crf_ctc_sample_workspace_bytes(int64_t B, int64_t T, int64_t V, int64_t K) { return or_minus1(sample_ws_bytes(B, T, V, K)); }
 
 int crf_ctc_sample(const void *act, int dtype, int time_major, int blank, const int32_t *lx, int64_t B, int64_t T, int64_t V, int64_t K,
@@ -263,6 +324,7 @@ int crf_ctc_sample(const void *act, int dtype, int time_major, int blank, const 
 }
 
 const char *crf_last_score_kernel(void) { return g_score_kernel; }
+const char *crf_last_score_grad_kernel(void) { return g_score_grad_kernel; }
 const char *crf_last_sample_kernel(void) { return g_sample_kernel; }
 
 }  // extern "C"

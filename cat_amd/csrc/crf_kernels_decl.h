@@ -57,6 +57,29 @@ struct ScoreParams {
 template <int NR, typename E = float, bool LSE = false> __global__ void crf_ctc_score_wave_kernel(ScoreParams p);   // NR 1, 2, 4, 8
 template <int NR, typename E = float, bool LSE = false> __global__ void crf_ctc_score_wg_kernel(ScoreParams p);     // NR 2, 4, kCtcRegs
 
+// ---- k_score_grad.hip ----
+constexpr int kScoreGradMaxLen = 255;     // the wave geometry only: 2 max_hyp_len + 1 <= kScoreWaveMaxStates
+constexpr int kScoreGradMaxV = 8192;      // the reduce stage keeps a row of V floats per frame in LDS: 32 KiB per row at most
+constexpr int kScoreGradFrames = 8;       // ... and up to this many frames per workgroup (fewer beyond V = 1024: at most 32 KiB of rows)
+constexpr int kScoreGradReduceThreads = 256;
+// Kernel arguments of crf_ctc_score_grad: ScoreParams' fields, then the weights, the workspace sections and the output
+struct ScoreGradParams {
+    const void *x;
+    const int *labels, *hyp_off, *hyp_len, *hyp_utt, *lx;
+    int B, H, T, V, blank;
+    int64_t xs_b, xs_t;
+    float *score;               // [H] or null
+    int *invalid;               // [H] or null
+    const float *weight;        // [H] or null: all 1
+    float *occ;                 // [H][T][S] workspace, rows t < lx of live hypotheses: alpha_t[s] - (t + 1) score / lx after stage 1, exp(alpha + beta - score) after stage 2
+    float *hscore;              // [H] workspace: the score as crf_ctc_score_wave_kernel wrote it (-inf for an invalid hypothesis)
+    float *grad;                // the activations' layout: row (u, t) at u * xs_b + t * xs_t
+    int S, FB;                  // states per row of occ (64 NR); frames per workgroup of the reduce stage
+};
+template <int NR> __global__ void crf_ctc_score_grad_alpha_kernel(ScoreGradParams p);   // NR 1, 2, 4, 8
+template <int NR> __global__ void crf_ctc_score_grad_beta_kernel(ScoreGradParams p);
+__global__ void crf_ctc_score_grad_reduce_kernel(ScoreGradParams p);   // dynamic LDS: FB x V words
+
 // ---- k_sample.hip ----
 constexpr int kSampleSmallV = 256;        // rows of up to here: 16 lanes per row and 16 rows per workgroup, beyond: a wave per row and workgroup
 constexpr int kSampleMaxV = 8192;         // the row and its running sums are staged in LDS: 32.5 KiB per row at most

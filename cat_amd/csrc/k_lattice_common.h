@@ -1,7 +1,8 @@
 // cat_amd/csrc/k_lattice_common.h -- device helpers the kernels on the CTC lattice of 2L+1 states share (k_align.hip: best path; k_score.hip:
-// sum-product scores; k_sample.hip takes the element load only): the upcast element load, the label set-up and validity rule of a
-// transcript, the clamped emission prefetch, and the fp64 sum of the frames' normalisers.
-// The max-plus / sum-product frame bodies, the back-pointers and the DPP wave recursion stay with their kernels.
+// sum-product scores; k_score_grad.hip: their gradient; k_sample.hip takes the element load only): the upcast element load, the label
+// set-up and validity rule of a transcript, the clamped emission prefetch, the fp64 sum of the frames' normalisers, and the fp32
+// log-sum-exp of the scores with its one operand order.
+// The max-plus / sum-product frame bodies, the back-pointers and the DPP wave recursions stay with their kernels.
 //
 // Validity (lat_valid) is part of the contract of both surfaces: a transcript of L labels is scored on lx frames iff it fits the
 // instantiation, lx > 0, every label lies in [0, V), and L + repeats <= lx (gpu_ctc.h:161-174: L + repeats <= T_b).
@@ -76,6 +77,27 @@ __device__ __forceinline__ void lat_fetch(float (&e)[PF][NR], const E *xb, int64
 // (The batch loop around it -- fetch(ea, 0); for (t0 ...) { fetch(eb, t0 + PF); PF frames on ea; fetch(ea, t0 + 2 PF); PF frames on eb } --
 // is written out in each of the three frame kernels: as a function that takes the fetch and the frame it gave the same arithmetic but
 // another schedule and register allocation in most instantiations, with longer frame loops; profiles/refactor_lattice_isa.txt.)
+
+// ---- the sum-product arithmetic of the hypothesis scores and of their gradient (k_score.hip, k_score_grad.hip: one operand order) ----
+// exp and log on the hardware's base-2 instructions without the library's denormal handling: the sums below lie in [1, 3] (or are 0:
+// log -> -inf), and a term below 2^-126 of the largest adds nothing either way.  exp(-inf) = 0.
+__device__ __forceinline__ float score_exp(float d) { return __builtin_amdgcn_exp2f(d * 1.4426950408889634f); }
+__device__ __forceinline__ float score_log(float s) { return __builtin_amdgcn_logf(s) * 0.6931471805599453f; }
+// log(exp(a0) + exp(a1) + exp(a2)): the sum is (e0 + e1) + e2.  A term of -inf adds an exact 0, so the two-term form below gives the
+// bits of the three-term form with a2 = -inf.  An all -inf triple: the maximum is raised to -FLT_MAX, every difference stays -inf.
+__device__ __forceinline__ float score_lse3(float a0, float a1, float a2) {
+    const float m = fmaxf(fmaxf(fmaxf(a0, a1), a2), -3.402823466e+38f);
+    return m + score_log((score_exp(a0 - m) + score_exp(a1 - m)) + score_exp(a2 - m));
+}
+__device__ __forceinline__ float score_lse2(float a0, float a1) {
+    const float m = fmaxf(fmaxf(a0, a1), -3.402823466e+38f);
+    return m + score_log(score_exp(a0 - m) + score_exp(a1 - m));
+}
+
+// lane l takes lane l - 1's value, lane 0 takes -inf (wave_shr:1; a lane without a source keeps `old`)
+__device__ __forceinline__ float score_shift_up(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp((int)0xff800000u, __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, false));
+}
 
 // sum_{t < lx} lse[t] in fp64, in the order stated at the top.  Wave form (STRIDE 64, id = lane): the sum in every lane.
 template <int STRIDE = 64>

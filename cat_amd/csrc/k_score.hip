@@ -4,7 +4,7 @@
 //   v_t[s] = x[u][t][lab(s)] + log(exp(v_{t-1}[s]) + exp(v_{t-1}[s-1]) + [s odd and lab(s) != lab(s-2)] exp(v_{t-1}[s-2]))     u = hyp_utt[h]
 //   score[h] = logaddexp(v[2L], v[2L-1])  after the lx[u] frames of the utterance
 //
-// Log domain, fp32, the largest term subtracted, ONE operand order (score_lse3 / score_lse2 below: stay, advance, skip; at the end 2L,
+// Log domain, fp32, the largest term subtracted, ONE operand order (score_lse3 / score_lse2, k_lattice_common.h: stay, advance, skip; at the end 2L,
 // 2L-1): a hypothesis's score depends on its own labels and its utterance's rows only -- not on its place in the list, on its
 // neighbours or on the layout -- and is the same bits in every call that takes the same instantiation.  -inf flows through: an
 // all -inf triple stays -inf (the maximum is raised to -FLT_MAX before it is subtracted), -inf + anything finite is -inf, and there is no +inf.
@@ -26,26 +26,6 @@
 #include "k_lattice_common.h"
 
 namespace crf {
-
-// exp and log on the hardware's base-2 instructions without the library's denormal handling: the sums below lie in [1, 3] (or are 0:
-// log -> -inf), and a term below 2^-126 of the largest adds nothing either way.  exp(-inf) = 0.
-__device__ __forceinline__ float score_exp(float d) { return __builtin_amdgcn_exp2f(d * 1.4426950408889634f); }
-__device__ __forceinline__ float score_log(float s) { return __builtin_amdgcn_logf(s) * 0.6931471805599453f; }
-// log(exp(a0) + exp(a1) + exp(a2)): the sum is (e0 + e1) + e2.  A term of -inf adds an exact 0, so the two-term form below gives the
-// bits of the three-term form with a2 = -inf.  An all -inf triple: the maximum is raised to -FLT_MAX, every difference stays -inf.
-__device__ __forceinline__ float score_lse3(float a0, float a1, float a2) {
-    const float m = fmaxf(fmaxf(fmaxf(a0, a1), a2), -3.402823466e+38f);
-    return m + score_log((score_exp(a0 - m) + score_exp(a1 - m)) + score_exp(a2 - m));
-}
-__device__ __forceinline__ float score_lse2(float a0, float a1) {
-    const float m = fmaxf(fmaxf(a0, a1), -3.402823466e+38f);
-    return m + score_log(score_exp(a0 - m) + score_exp(a1 - m));
-}
-
-// lane l takes lane l - 1's value, lane 0 takes -inf (wave_shr:1; a lane without a source keeps `old`)
-__device__ __forceinline__ float score_shift_up(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp((int)0xff800000u, __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, false));
-}
 
 template <int NR, typename E, bool LSE>
 __global__ __launch_bounds__(kScoreWaves * 64) void crf_ctc_score_wave_kernel(ScoreParams p) {

@@ -68,6 +68,12 @@ _lib.crf_ctc_score_logits.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_
                                       _vp, _vp, _vp, _i64, _vp]
 _lib.crf_ctc_score_logits.restype = ctypes.c_int
 _lib.crf_last_score_kernel.restype = ctypes.c_char_p
+_lib.crf_ctc_score_grad_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64, _i64]
+_lib.crf_ctc_score_grad_workspace_bytes.restype = _i64
+_lib.crf_ctc_score_grad.argtypes = [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp,
+                                    _vp, _i64, _vp]
+_lib.crf_ctc_score_grad.restype = ctypes.c_int
+_lib.crf_last_score_grad_kernel.restype = ctypes.c_char_p
 _lib.crf_ctc_sample_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64]
 _lib.crf_ctc_sample_workspace_bytes.restype = _i64
 _lib.crf_ctc_sample.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _i64, _i64, _i64, _i64, ctypes.c_uint64, ctypes.c_uint32,
@@ -98,7 +104,7 @@ _lib.crf_build_switches.restype = ctypes.c_char_p
 
 EXPORTED_SYMBOLS = (
     "crf_graph_create", "crf_graph_create_from_arcs", "crf_graph_destroy", "crf_graph_dims", "crf_graph_stats",
-    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_ctc_score", "crf_ctc_score_logits_workspace_bytes", "crf_ctc_score_logits", "crf_last_score_kernel", "crf_ctc_sample_workspace_bytes", "crf_ctc_sample", "crf_last_sample_kernel", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
+    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_ctc_score", "crf_ctc_score_logits_workspace_bytes", "crf_ctc_score_logits", "crf_last_score_kernel", "crf_ctc_score_grad_workspace_bytes", "crf_ctc_score_grad", "crf_last_score_grad_kernel", "crf_ctc_sample_workspace_bytes", "crf_ctc_sample", "crf_last_sample_kernel", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
     "crf_debug_set", "crf_debug_unset", "crf_debug_list", "crf_last_den_kernel", "crf_last_call_streams", "crf_last_side_stream", "crf_last_fallback_counts", "crf_build_switches", "crf_last_error", "crf_version",
 )
 
@@ -125,6 +131,11 @@ def last_den_kernel() -> str:
 def last_score_kernel() -> str:
     """Template instantiation of the kernel of this thread's last ctc_score call (include/ctc_crf_hip.h crf_last_score_kernel)."""
     return _lib.crf_last_score_kernel().decode()
+
+
+def last_score_grad_kernel() -> str:
+    """Template instantiation of the alpha pass of this thread's last ctc_score_grad call (include/ctc_crf_hip.h crf_last_score_grad_kernel)."""
+    return _lib.crf_last_score_grad_kernel().decode()
 
 
 def last_sample_kernel() -> str:
@@ -711,6 +722,83 @@ def ctc_score(log_probs: torch.Tensor, hyps: torch.Tensor, hyp_lengths: torch.Te
     _check(rc)
     del meta
     return scores, invalid
+
+
+SCORE_GRAD_MAX_LEN = 255     # longest hypothesis crf_ctc_score_grad takes (one wave per hypothesis; include/ctc_crf_hip.h)
+
+
+class ScoreMeta:
+    """The staged integer metadata of one list of hypotheses, on the device: what ctc_score_staged and ctc_score_grad share, so that a
+    backward pass needs no second host-to-device copy.  `meta` = [lx (N) | hyp_len (H) | hyp_off (H) | hyp_utt (H) | labels] int32."""
+
+    def __init__(self, meta: torch.Tensor, N: int, H: int, T: int, V: int, max_len: int, blank: int):
+        self.meta, self.N, self.H, self.T, self.V, self.max_len, self.blank = meta, N, H, T, V, max_len, blank
+
+    def parts(self):
+        m, N, H = self.meta, self.N, self.H
+        return m[:N], m[N:N + H], m[N + H:N + 2 * H], m[N + 2 * H:N + 3 * H], m[N + 3 * H:]   # lx, len, off, utt, labels
+
+
+def stage_score_meta(log_probs: torch.Tensor, hyps: torch.Tensor, hyp_lengths: torch.Tensor, lx: torch.Tensor,
+                     hyp_utt: Optional[torch.Tensor], blank: int, time_major: bool) -> ScoreMeta:
+    """_stage_score_meta's checks and ONE staged copy to log_probs' device (fp32 log-probs, as ctc_score takes them)."""
+    assert log_probs.is_cuda and log_probs.is_contiguous() and log_probs.dim() == 3
+    dev, N, T, V = _act_shape(log_probs, False, time_major, blank)
+    meta_cpu, H, max_l = _stage_score_meta(hyps, hyp_lengths, lx, hyp_utt, N, T, V, blank)
+    return ScoreMeta(_h2d_async(meta_cpu, dev), N, H, T, V, max_l, blank)
+
+
+def _score_args(log_probs: torch.Tensor, sm: ScoreMeta, time_major: bool):
+    dev, N, T, V = _act_shape(log_probs, False, time_major, sm.blank)
+    assert log_probs.is_cuda and log_probs.is_contiguous() and (N, T, V) == (sm.N, sm.T, sm.V) and sm.meta.device == dev
+    return dev, N, T, V
+
+
+def ctc_score_staged(log_probs: torch.Tensor, sm: ScoreMeta, time_major: bool = False, scores_out: Optional[torch.Tensor] = None):
+    """ctc_score's crf_ctc_score call on metadata that is staged already.  Returns (scores [H] f32, invalid [H] int32)."""
+    dev, N, T, V = _score_args(log_probs, sm, time_major)
+    lx_d, len_d, off_d, utt_d, lab_d = sm.parts()
+    scores = torch.empty(sm.H, dtype=torch.float32, device=dev) if scores_out is None else scores_out
+    assert scores.shape == (sm.H,) and scores.dtype == torch.float32 and scores.is_contiguous() and scores.device == dev
+    invalid = torch.empty(sm.H, dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        _check(_lib.crf_ctc_score(_ptr(log_probs), 1 if time_major else 0, sm.blank, _ptr(lab_d), _ptr(off_d), _ptr(len_d), _ptr(utt_d),
+                                  _ptr(lx_d), N, sm.H, T, V, sm.max_len, _ptr(scores), _ptr(invalid), _vp(stream)))
+    return scores, invalid
+
+
+def ctc_score_grad(log_probs: torch.Tensor, meta, weights: Optional[torch.Tensor], blank: int = 0, time_major: bool = False,
+                   grad_out: Optional[torch.Tensor] = None, scores_out: Optional[torch.Tensor] = None):
+    """The weighted gradient of the hypothesis scores as ONE tensor of log_probs' shape (include/ctc_crf_hip.h ``crf_ctc_score_grad``):
+    grad[u] = sum over the hypotheses h of utterance u of weights[h] * d score[h] / d log_probs[u].
+
+    log_probs [N,T,V] (time_major: [T,N,V]) f32 log-probs on the GPU, contiguous, read in place and never replicated; meta: a ScoreMeta
+    (stage_score_meta; its blank counts) or the tuple (hyps, hyp_lengths, input_lengths, hyp_utt) of CPU tensors as ctc_score takes them;
+    weights: [H] f32 on the device, or None for all 1.  Returns (grad, scores [H] f32, invalid [H] int32), all on the device, no host
+    synchronisation; scores and invalid are ctc_score's bits.  grad_out / scores_out: contiguous f32 device tensors of log_probs' shape /
+    [H] that receive the results (else allocated); every entry of grad is written."""
+    assert log_probs.is_cuda and log_probs.is_contiguous() and log_probs.dim() == 3
+    sm = meta if isinstance(meta, ScoreMeta) else stage_score_meta(log_probs, *meta, blank, time_major)
+    dev, N, T, V = _score_args(log_probs, sm, time_major)
+    H = sm.H
+    lx_d, len_d, off_d, utt_d, lab_d = sm.parts()
+    if weights is not None:
+        assert weights.shape == (H,) and weights.dtype == torch.float32 and weights.is_contiguous() and weights.device == dev
+    ws_bytes = _lib.crf_ctc_score_grad_workspace_bytes(N, H, T, V, sm.max_len)
+    ws = _new_ws(ws_bytes, dev)
+    grad = torch.empty(log_probs.shape, dtype=torch.float32, device=dev) if grad_out is None else grad_out
+    assert grad.shape == log_probs.shape and grad.dtype == torch.float32 and grad.is_contiguous() and grad.device == dev
+    scores = torch.empty(H, dtype=torch.float32, device=dev) if scores_out is None else scores_out
+    assert scores.shape == (H,) and scores.dtype == torch.float32 and scores.is_contiguous() and scores.device == dev
+    invalid = torch.empty(H, dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        rc = _lib.crf_ctc_score_grad(_ptr(log_probs), 1 if time_major else 0, sm.blank, _ptr(lab_d), _ptr(off_d), _ptr(len_d), _ptr(utt_d),
+                                     _ptr(lx_d), _ptr(weights), N, H, T, V, sm.max_len, _ptr(scores), _ptr(invalid), _ptr(grad), _ptr(ws),
+                                     ws_bytes, _vp(stream))
+    _check(rc)
+    return grad, scores, invalid
 
 
 def ctc_sample(log_probs: torch.Tensor, lx: torch.Tensor, n_samples: int, seed: int, offset: int = 0, blank: int = 0,

@@ -11,6 +11,8 @@ Same names, arguments and error behaviour as the reference:
                                                                                          (forced alignment; not in the reference)
   ctc_score(log_probs, hyps, hyp_lengths, input_lengths, hyp_utt=None, blank=0, time_major=False, fuse_log_softmax=False) -> FloatTensor[H]
                                                                                          (forward-only scores of many hypotheses per utterance)
+  ctc_logp(log_probs, hyps, hyp_lengths, input_lengths, hyp_utt=None, blank=0, time_major=False) -> (FloatTensor[H], IntTensor[H])
+                                                                                         (the same scores WITH autograd: one [N,T,V] gradient)
   ctc_sample(log_probs, input_lengths, n_samples, seed, offset=0, blank=0, time_major=False, return_paths=False)
                                                               -> (hyps IntTensor[N*K, T], hyp_lengths IntTensor[N*K], hyp_utt IntTensor[N*K])
                                                                                          (K label sequences per utterance drawn on the GPU)
@@ -27,6 +29,7 @@ from typing import Dict, List, Tuple, Union
 
 import torch
 from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 from torch.nn import Module
 
 from . import _C as core
@@ -276,6 +279,57 @@ def ctc_score(log_probs: torch.Tensor, hyps: torch.Tensor, hyp_lengths: torch.Te
         scores, _ = core.ctc_score(log_probs.detach().contiguous(), hyps, hyp_lengths, input_lengths, hyp_utt, int(blank), bool(time_major),
                                    fused=bool(fuse_log_softmax))
     return scores
+
+
+class _CTC_LOGP(Function):
+    """scores [H] = crf_ctc_score; backward = ONE crf_ctc_score_grad call with weight = grad_output, on the metadata forward staged."""
+
+    @staticmethod
+    def forward(ctx, log_probs, sm, time_major):
+        scores, invalid = core.ctc_score_staged(log_probs, sm, time_major)
+        ctx.save_for_backward(log_probs)
+        ctx.sm, ctx.time_major = sm, time_major
+        ctx.mark_non_differentiable(invalid)
+        return scores, invalid
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_scores, _grad_invalid):
+        log_probs, = ctx.saved_tensors
+        w = grad_scores.to(device=log_probs.device, dtype=torch.float32).contiguous()
+        grad, _, _ = core.ctc_score_grad(log_probs, ctx.sm, w, ctx.sm.blank, ctx.time_major)
+        return grad, None, None
+
+
+def ctc_logp(log_probs: torch.Tensor, hyps: torch.Tensor, hyp_lengths: torch.Tensor, input_lengths: torch.Tensor,
+             hyp_utt: torch.Tensor = None, blank: int = 0, time_major: bool = False):
+    """ctc_score with autograd: CTC log-likelihoods of H hypotheses over N utterances whose gradient reaches log_probs as ONE (N, T, V)
+    tensor -- what minimum-risk / MWER training on sampled or N-best hypotheses and the nn.CTCLoss(reduction='none',
+    zero_infinity=True) / length losses (cat/ctc/train_jsa.py:194-201) need, without repeat_interleave'd activations and without an
+    (H, T, V) gradient.  MWER in three lines:
+
+        hyps, hyp_lengths, hyp_utt = ctc_sample(log_probs, input_lengths, K, seed)
+        scores, _ = ctc_logp(log_probs, hyps.cpu(), hyp_lengths.cpu(), input_lengths, hyp_utt.cpu())
+        (torch.softmax(scores.view(N, K), -1) * risk.view(N, K)).sum().backward()
+
+    log_probs (torch.FloatTensor): (N, T, V) fp32 log-probs on the GPU, contiguous, or (T, N, V) with time_major=True; anything else is
+        refused.  hyps, hyp_lengths, input_lengths, hyp_utt, blank: as ctc_score takes them (CPU tensors).
+    Returns (scores FloatTensor[H], invalid IntTensor[H]) on log_probs' device, no host synchronisation.  scores are ctc_score's bits and
+    differentiable with respect to log_probs (once: no double backward); invalid (1: the hypothesis does not fit its utterance) is not.
+    Backward is one call (include/ctc_crf_hip.h crf_ctc_score_grad) whose weights are the incoming grad_output, so any torch expression
+    of the scores trains; a hypothesis that is invalid or scores -inf, or whose weight is exactly 0, adds nothing to the gradient
+    (zero_infinity=True).  With log_probs.requires_grad no hypothesis may be longer than 255 labels."""
+    if log_probs.dtype != torch.float:
+        raise RuntimeError(f"ctc_logp: expect float32 log-probs, got {log_probs.dtype}")
+    if not log_probs.is_cuda:
+        raise RuntimeError("ctc_logp: log_probs must be on the GPU (there is no CPU path)")
+    if log_probs.dim() != 3 or not log_probs.is_contiguous():
+        raise RuntimeError("ctc_logp: expect contiguous (N, T, V) or (T, N, V) log-probs")
+    if log_probs.requires_grad and hyp_lengths.numel() and int(hyp_lengths.max()) > core.SCORE_GRAD_MAX_LEN:
+        raise RuntimeError(f"ctc_logp: the gradient takes hypotheses of up to {core.SCORE_GRAD_MAX_LEN} labels, got {int(hyp_lengths.max())}")
+    with torch.no_grad():
+        sm = core.stage_score_meta(log_probs, hyps, hyp_lengths, input_lengths, hyp_utt, int(blank), bool(time_major))
+    return _CTC_LOGP.apply(log_probs, sm, bool(time_major))
 
 
 def ctc_sample(log_probs: torch.Tensor, input_lengths: torch.Tensor, n_samples: int, seed: int, offset: int = 0, blank: int = 0,

@@ -273,6 +273,43 @@ int crf_ctc_score_logits(const void *act_dev, int dtype, int time_major, int bla
                          int64_t B, int64_t H, int64_t T, int64_t V, int64_t max_hyp_len,
                          float *score_dev, int32_t *invalid_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
 
+/* The weighted gradient of crf_ctc_score's scores, H hypotheses folded into ONE tensor of the activations' shape (minimum-risk / MWER
+ * training on sampled or N-best hypotheses, the nn.CTCLoss(reduction='none', zero_infinity=True) / length losses with gradient of
+ * cat/ctc/train_jsa.py:194-201, any per-hypothesis or per-utterance weighting -- without repeat_interleave'd activations and without an
+ * [H][T][V] gradient):
+ *   grad_dev[u][t][v] = sum over h with hyp_utt_dev[h] = u of  weight_dev[h] * gamma_h[t][v],
+ *   gamma_h[t][v]     = d log p(h | act[u]) / d act[u][t][v] = sum over s with lab_h(s) = v of  exp(alpha_t[s] + beta_t[s] - score_dev[h]).
+ * Inputs: the activations are fp32 log-probs, [B][T][V] (time_major = 0) or [T][B][V] (1), read in place and never replicated; grad_dev
+ * has the layout of act_dev; the hypotheses as for crf_ctc_score; weight_dev [H] fp32, NULL = all 1.
+ * Validity and scores: validity is crf_ctc_score's rule (the alignment's).  score_dev[h] and invalid_dev[h] (either may be NULL) are exactly
+ * what crf_ctc_score writes for the same arguments, bit for bit: the forward recursion is the score kernels', with the same operand order
+ * and the same instantiation chosen from max_hyp_len -- the call launches that very kernel first (crf_last_score_grad_kernel() names
+ * the gradient's own alpha pass, e.g. "crf_ctc_score_grad_alpha_kernel<4>", with the same states per lane).  The occupancies come from a
+ * second pair of recursions that carry their vectors in fp64 (fp32 log-domain vectors lose 1e-4 of a posterior within a few hundred
+ * frames), and each frame's 2 L + 1 of them are normalised by their own sum -- in exact arithmetic exp(score_dev[h]), the score the
+ * caller sees.
+ * Gradient: the call writes EVERY entry of grad_dev; its contents on entry do not matter.  Rows of frames t >= lx[u] and of utterances
+ * that own no hypothesis are 0.  A hypothesis that is invalid, scores -inf or has a weight of exactly 0 contributes nothing (the
+ * zero_infinity=True rule of the caller this replaces).  For finite weights and activations that hold no NaN and no +inf there is no
+ * NaN and no inf in grad_dev; -inf activations are allowed and give occupancy 0.  L = 0 is valid: occupancy 1 in the blank's column
+ * for every frame t < lx[u].  The gradient is NOT promised bit for bit: as the numerator's grad pass does, the states of a frame are
+ * scattered onto their labels with LDS float adds, whose order is not fixed (scores and invalid are bit for bit all the same).
+ * Limits: max_hyp_len <= 255 (one wave per hypothesis, 2 L + 1 <= 512 states) and V <= 8192 (the reduce stage keeps a row in LDS), beyond
+ * CRF_ERR_UNSUPPORTED, the message naming the limit.
+ * Workspace: crf_ctc_score_grad_workspace_bytes (the stored alphas, then the occupancies in their place, [H][T][64 NR] fp32 with NR = 1, 2, 4, 8 the
+ * states per lane, and the H scores; >= 4 H T (2 max_hyp_len + 1); offsets into it are 64-bit; its contents on entry do not matter;
+ * -1 with crf_last_error() set for a shape not taken).
+ * CRF_ERR_ARG: null pointer (weight_dev, score_dev and invalid_dev excepted), blank outside [0, V), B, H, T or V <= 0, max_hyp_len < 0,
+ * B * T > INT32_MAX (H and V are ints as well); CRF_ERR_WORKSPACE: workspace too small (the message names the bytes needed) -- all
+ * answered before any HIP call.  No host synchronisation, all work on `stream`, no environment variable read. */
+int64_t crf_ctc_score_grad_workspace_bytes(int64_t B, int64_t H, int64_t T, int64_t V, int64_t max_hyp_len);
+int crf_ctc_score_grad(const float *act_dev, int time_major, int blank, const int32_t *labels_dev, const int32_t *hyp_off_dev,
+                       const int32_t *hyp_len_dev, const int32_t *hyp_utt_dev, const int32_t *lx_dev, const float *weight_dev,
+                       int64_t B, int64_t H, int64_t T, int64_t V, int64_t max_hyp_len,
+                       float *score_dev, int32_t *invalid_dev, float *grad_dev,
+                       void *workspace_dev, int64_t workspace_bytes, void *stream);
+const char *crf_last_score_grad_kernel(void);
+
 /* Label sequences drawn on the GPU (what cat/ctc/train_jsa.py:256-269 `_sample` gets from torch.multinomial over N T rows, a transpose and
  * the third-party ctc_align.align_; with greedy = 1 the best path: arg-max per frame): per frame K classes from softmax(x), then the CTC
  * map B on each of the B K frame paths.  The activations are read in place, [B][T][V] (time_major = 0) or [T][B][V] (1), dtype 0 = fp32,
