@@ -488,10 +488,14 @@ int crf_graph_create_from_arcs(int64_t S, int64_t A, const int32_t *src, const i
 void crf_graph_destroy(crf_graph *g) {
     if (!g) return;
     if (g->h) {
-        int prev = 0;
-        bool sw = hipGetDevice(&prev) == hipSuccess && hipSetDevice(g->h->device) == hipSuccess;
-        for (void *p : g->h->allocs) (void)hipFree(p);
-        if (sw) (void)hipSetDevice(prev);
+        // a host-only graph (device < 0) owns no device memory and makes no HIP call: hipSetDevice(-1) fails, and the runtime keeps
+        // hipErrorInvalidDevice as the thread's last error, which the next launch check -- the library's or torch's -- then reports
+        if (g->h->device >= 0) {
+            int prev = 0;
+            bool sw = hipGetDevice(&prev) == hipSuccess && hipSetDevice(g->h->device) == hipSuccess;
+            for (void *p : g->h->allocs) (void)hipFree(p);
+            if (sw) (void)hipSetDevice(prev);
+        }
         for (crf::StreamDev *sd : g->h->streams) delete sd;
         delete g->h;
     }

@@ -175,6 +175,29 @@ def test_null_optional_outputs(crf, small, mode):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# I: a graph WITHOUT the T o LM structure -- rows of 300 arcs (sub-rows, virtual copies of their entries), states entered with several
+# labels: most rows of the utterance-minor kernels take the per-row path beside the arc streams
+# ---------------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def hub(tmp_path_factory):
+    from tests import general_graphs as gg
+    p, g, V = gg.catalogue("hub", tmp_path_factory.mktemp("guard_hub"))
+    logits, labels, lx, ly = gg.batch(V, 2.0, seed=41)
+    return frozen(dict(path=p, logits=logits, labels=labels, lx=lx, ly=ly, ref=oracle.ctc_crf(g, logits, labels, lx, ly, lamb=LAMB)))
+
+
+@pytest.mark.parametrize("gap", [0, 1])
+@pytest.mark.parametrize("mode", ["resident", "batch", "streaming"])
+def test_general_graph_families(crf, hub, mode, gap):
+    """Case I: tests/general_graphs.py's `hub` (S = 400, one state entered by 300 arcs of one class and left by 300 arcs), B = 4 with
+    utterances of two frames and of one."""
+    out = loss_call(crf, hub["path"], hub, gap_opts(gap), mode=mode)
+    want = {"resident": "crf_res_pair_kernel", "batch": "crf_batch_persist_kernel<8,4,", "streaming": "crf_den_pair_kernel<false>"}[mode]
+    assert out["kernel"].startswith(want), (mode, out["kernel"])
+    hold(out, hub["ref"], hub["lx"], ("I", mode, gap))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 # B: every schedule row on the S = 513 graph, with 16-frame blocks that do not divide T and utterances around the staging threshold
 # ---------------------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
