@@ -166,8 +166,8 @@ static int score_call(const char *who, const void *act, int dtype, int time_majo
 }
 
 // ---- the weighted gradient of the hypothesis scores (k_score_grad.hip) ----
-// its workspace: the stored alphas / weighted occupancies [H][T][64 NR] (NR from the call's longest hypothesis, as the score kernels'), then
-// the H scores.  < 0 with the message set.
+// its workspace: the stored alphas [H][T][64 NR] in fp64 -- the occupancies, fp32, go over the first half of each row -- (NR from the call's
+// longest hypothesis, as the score kernels'), then the H scores.  < 0 with the message set.
 static int64_t score_grad_ws_bytes(int64_t B, int64_t H, int64_t T, int64_t V, int64_t max_hyp_len, SideWs *out = nullptr) {
     if (B <= 0 || T <= 0 || V <= 0 || V > INT32_MAX) { set_error("crf_ctc_score_grad: bad B/T/V"); return -CRF_ERR_ARG; }
     if (H <= 0 || H > INT32_MAX || max_hyp_len < 0) { set_error("crf_ctc_score_grad: bad H/max_hyp_len"); return -CRF_ERR_ARG; }
@@ -175,9 +175,9 @@ static int64_t score_grad_ws_bytes(int64_t B, int64_t H, int64_t T, int64_t V, i
     if (max_hyp_len > kScoreGradMaxLen) { set_error("crf_ctc_score_grad: hypothesis length > " + std::to_string(kScoreGradMaxLen) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
     if (V > kScoreGradMaxV) { set_error("crf_ctc_score_grad: V > " + std::to_string(kScoreGradMaxV) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
     const int64_t S = with_nr(2 * max_hyp_len + 1, 64, [](auto nr, int) { return 64 * decltype(nr)::value; });
-    if (H > (INT64_MAX / 8) / (T * S)) { set_error("crf_ctc_score_grad: H * T * states too large"); return -CRF_ERR_ARG; }
+    if (H > (INT64_MAX / 16) / (T * S)) { set_error("crf_ctc_score_grad: H * T * states too large"); return -CRF_ERR_ARG; }
     SideWs w;
-    w.add("occ", H * T * S * (int64_t)sizeof(float)).add("hscore", H * (int64_t)sizeof(float));
+    w.add("occ", H * T * S * (int64_t)sizeof(double)).add("hscore", H * (int64_t)sizeof(float));
     if (out) *out = w;
     return w.total;
 }
@@ -298,7 +298,7 @@ int crf_ctc_score_grad(const float *act, int time_major, int blank, const int32_
     p.labels = labels; p.hyp_off = hyp_off; p.hyp_len = hyp_len; p.hyp_utt = hyp_utt; p.H = (int)H;
     p.score = score; p.invalid = invalid; p.weight = weight; p.grad = grad;
     p.occ = (float *)((char *)ws + w.sec[0].off); p.hscore = (float *)((char *)ws + w.sec[1].off);
-    p.S = (int)(w.sec[0].bytes / (H * T * (int64_t)sizeof(float)));
+    p.S = (int)(w.sec[0].bytes / (H * T * (int64_t)sizeof(double)));
     p.FB = (int)std::min<int64_t>(kScoreGradFrames, std::max<int64_t>(1, kScoreGradMaxV / V));
     return launch_score_grad(p, (hipStream_t)stream_, max_hyp_len);
 }

@@ -71,7 +71,7 @@ struct ScoreGradParams {
     float *score;               // [H] or null
     int *invalid;               // [H] or null
     const float *weight;        // [H] or null: all 1
-    float *occ;                 // [H][T][S] workspace, rows t < lx of live hypotheses: alpha_t[s] - (t + 1) score / lx after stage 1, exp(alpha + beta - score) after stage 2
+    float *occ;                 // [H][T] rows of S doubles, workspace; rows t < lx of live hypotheses: alpha_t[s] in fp64 after stage 1; after stage 2 S floats exp(alpha + beta - score) at the row's start
     float *hscore;              // [H] workspace: the score as crf_ctc_score_wave_kernel wrote it (-inf for an invalid hypothesis)
     float *grad;                // the activations' layout: row (u, t) at u * xs_b + t * xs_t
     int S, FB;                  // states per row of occ (64 NR); frames per workgroup of the reduce stage

@@ -5,18 +5,22 @@
 //   gamma_h[t][v] = sum over s with lab_h(s) = v of  exp(alpha_t[s] + beta_t[s] - score_h)
 //
 // Four launches on one stream, the activations read in place and never replicated; what is per hypothesis lives in the workspace
-// (occ[h][t][64 NR] floats and the H scores), never in an [H][T][V] tensor.
+// (occ[h][t]: a row of 64 NR doubles, and the H scores), never in an [H][T][V] tensor.
 //   0. crf_ctc_score_wave_kernel<NR> ITSELF (k_score.hip), the instantiation crf_ctc_score takes for max_hyp_len: it writes invalid and,
 //      into the workspace, the scores -- the bits crf_ctc_score writes because the same code writes them.
 //   1. crf_ctc_score_grad_alpha_kernel<NR>: copies the score out, then for a live hypothesis (valid, score > -inf, weight != 0) the same
 //      recursion in the same geometry (one wave per hypothesis, state s = lane * NR + i, DPP wave_shr:1, emissions prefetched two batches
 //      ahead) with the state vector CARRIED IN FP64 (acc_lse3 below), and per frame t < lx one vector store of the lane's NR states into
-//      occ[h][t], as fp32 relative to the ramp (t + 1) score_h / lx -- the vector's largest entries run from 0 to the score, so what is
-//      stored stays small enough for fp32 (a storage rounding does not accumulate) and no cross-lane step is needed to find an offset.
+//      occ[h][t] AS THEY ARE, in fp64.  The stored vector is as exact as the carried one whatever the input: no offset is taken off, so
+//      none has to be found (a cross-lane step) and none can be wrong.  An fp32 store relative to the ramp (t + 1) score_h / lx was tried
+//      first: it is accurate only while the cost per frame is even.  A confident half followed by a costly one leaves the vector
+//      |score| / 2 off the ramp at mid-utterance -- 3 000 nats at T = 1 500 -- where one fp32 rounding is 1.2e-4, different from state to
+//      state: measured 1.7e-4 .. 2.2e-4 entry-wise on the posteriors (profiles/score_grad_uneven.txt), against the project's 1e-4.
 //   2. crf_ctc_score_grad_beta_kernel<NR>: the same backward in time with the mirror-image shift (wave_shl:1, the top lane takes -inf),
 //        beta_{lx-1}[s] = 0 for s in {2L, 2L-1}, else -inf
 //        beta_t[s] = lse3(c_{t+1}[s], c_{t+1}[s+1], [s+2 may be skipped to] c_{t+1}[s+2]),   c_t[s] = beta_t[s] + x_t[lab(s)]
-//      Per frame it reads the stored alpha and overwrites it in place with exp(alpha_t[s] + beta_t[s] - score_h), the sum in fp64.
+//      Per frame it reads the stored alpha and writes exp(alpha_t[s] + beta_t[s] - score_h), the sum in fp64, as 64 NR floats over the
+//      first half of the same row: every lane holds the row's alphas in registers by then (they were loaded a batch ahead).
 //      Neither recursion has a reduction across the wave: with one wave per SIMD whatever a frame waits for delays the next frame.
 //   3. crf_ctc_score_grad_reduce_kernel: one workgroup per (utterance, block of FB frames).  It zeroes an LDS row of V floats per frame,
 //      lists the live hypotheses of its utterance in ascending h, and per hypothesis and frame sums the 2L+1 occupancies (1 in exact
@@ -53,7 +57,22 @@ template <bool UP> __device__ __forceinline__ double acc_shift(double v) {
     const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp((int)0xfff00000u, (int)(unsigned)(b >> 32), ctrl, 0xf, 0xf, false);
     return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
 }
-// the lane's NR consecutive floats at a (a multiple of 4 NR bytes): one vector store / load of 4, 8 or 16 bytes, two for NR = 8
+// the lane's NR consecutive doubles at a (a multiple of 8 NR bytes): vector stores / loads of 8 or 16 bytes
+template <int NR> __device__ __forceinline__ void alpha_store(double *a, const double (&v)[NR]) {
+    if constexpr (NR == 1) a[0] = v[0];
+    else {
+#pragma unroll
+        for (int i = 0; i < NR; i += 2) *(double2 *)(a + i) = make_double2(v[i], v[i + 1]);
+    }
+}
+template <int NR> __device__ __forceinline__ void alpha_load(double (&v)[NR], const double *a) {
+    if constexpr (NR == 1) v[0] = a[0];
+    else {
+#pragma unroll
+        for (int i = 0; i < NR; i += 2) { const double2 q = *(const double2 *)(a + i); v[i] = q.x; v[i + 1] = q.y; }
+    }
+}
+// the lane's NR consecutive floats at a (a multiple of 4 NR bytes): one vector store of 4, 8 or 16 bytes, two for NR = 8
 template <int NR> __device__ __forceinline__ void occ_store(float *a, const float (&v)[NR]) {
     if constexpr (NR == 1) a[0] = v[0];
     else if constexpr (NR == 2) *(float2 *)a = make_float2(v[0], v[1]);
@@ -62,24 +81,16 @@ template <int NR> __device__ __forceinline__ void occ_store(float *a, const floa
         for (int i = 0; i < NR; i += 4) *(float4 *)(a + i) = make_float4(v[i], v[i + 1], v[i + 2], v[i + 3]);
     }
 }
-template <int NR> __device__ __forceinline__ void occ_load(float (&v)[NR], const float *a) {
-    if constexpr (NR == 1) v[0] = a[0];
-    else if constexpr (NR == 2) { const float2 q = *(const float2 *)a; v[0] = q.x; v[1] = q.y; }
-    else {
-#pragma unroll
-        for (int i = 0; i < NR; i += 4) { const float4 q = *(const float4 *)(a + i); v[i] = q.x; v[i + 1] = q.y; v[i + 2] = q.z; v[i + 3] = q.w; }
-    }
-}
 
 // What stages 1 and 2 share: the wave's hypothesis, whether it is live, its utterance's rows and its rows of occ.
 struct ScoreGradHyp {
     int h, lx, Sx;
     float score;
-    double slope;               // score / lx: frame t's alphas are stored relative to (t + 1) * slope
 
     const int *ul;
     const float *xb;
-    float *ob;
+    double *ab;                 // the lane's alphas of frame 0: frame t's are S doubles further per frame
+    float *ob;                  // the lane's occupancies of frame 0, at the start of the same rows: 2 S floats further per frame
 };
 // false: the wave has nothing to do (no hypothesis, or one that is invalid, scores -inf or weighs exactly 0: stage 3 skips it by the same
 // rule).  A live hypothesis is a valid one: u in [0, B), every label in [0, V), 0 < lx, 2 L + 1 <= S.  COPY: the score goes to the caller.
@@ -95,11 +106,11 @@ __device__ __forceinline__ bool score_grad_hyp(const ScoreGradParams &p, int lan
     const int u = p.hyp_utt[y.h];
     y.lx = min(p.lx[u], p.T);
     y.score = score;
-    y.slope = (double)score / (double)y.lx;
     y.Sx = 2 * p.hyp_len[y.h] + 1;
     y.ul = p.labels + p.hyp_off[y.h];
     y.xb = (const float *)p.x + (int64_t)u * p.xs_b;
-    y.ob = p.occ + ((int64_t)y.h * p.T) * (NR * 64) + lane * NR;
+    y.ab = (double *)p.occ + ((int64_t)y.h * p.T) * (NR * 64) + lane * NR;
+    y.ob = p.occ + ((int64_t)y.h * p.T) * (2 * NR * 64) + lane * NR;
     return true;
 }
 
@@ -142,11 +153,9 @@ __global__ __launch_bounds__(kScoreWaves * 64) void crf_ctc_score_grad_alpha_ker
             for (int i = 2; i < NR; ++i)
                 n[i] = (i & 1) ? (double)e[i] + acc_lse3(v[i], v[i - 1], skip[i] ? v[i - 2] : kNegInf) : (double)e[i] + acc_lse2(v[i], v[i - 1]);
         }
-        const double off = (double)(t + 1) * y.slope;   // what the stored values are relative to: the ramp from 0 to the score
-        float r[NR];
 #pragma unroll
-        for (int i = 0; i < NR; ++i) { v[i] = n[i]; r[i] = (float)(n[i] - off); }
-        occ_store<NR>(y.ob + (int64_t)t * S, r);
+        for (int i = 0; i < NR; ++i) v[i] = n[i];
+        alpha_store<NR>(y.ab + (int64_t)t * S, v);
     };
 
     float ea[PF][NR], eb[PF][NR];
@@ -184,28 +193,28 @@ __global__ __launch_bounds__(kScoreWaves * 64) void crf_ctc_score_grad_beta_kern
     }
     const double kNegInf = -__builtin_huge_val();
     // frames t, t - 1, ..., t - PF + 1, clamped to frame 0: unconditional loads, as lat_fetch's
-    auto fetch = [&](float (&e)[PF][NR], float (&a)[PF][NR], int t) __attribute__((always_inline)) {
+    auto fetch = [&](float (&e)[PF][NR], double (&a)[PF][NR], int t) __attribute__((always_inline)) {
 #pragma unroll
         for (int f = 0; f < PF; ++f) {
             const int tt = max(t - f, 0);
             const char *row = (const char *)(y.xb + (int64_t)tt * p.xs_t);
 #pragma unroll
             for (int i = 0; i < NR; ++i) e[f][i] = lat_ld<E>(row + labo[i]);
-            occ_load<NR>(a[f], y.ob + (int64_t)tt * S);
+            alpha_load<NR>(a[f], y.ab + (int64_t)tt * S);
         }
     };
     // One frame: the occupancies of frame t over its alphas, then beta_{t-1}; a frame below 0 does neither.
-    auto frame = [&](const float (&e)[NR], const float (&a)[NR], int t) __attribute__((always_inline)) {
+    auto frame = [&](const float (&e)[NR], const double (&a)[NR], int t) __attribute__((always_inline)) {
         if (t < 0) return;                    // (the whole wave)
         double c[NR], n[NR];
         float o[NR];
-        const double off = (double)(t + 1) * y.slope - (double)y.score;
+        const double score = (double)y.score;
 #pragma unroll
         for (int i = 0; i < NR; ++i) {
-            o[i] = score_exp((float)(((double)a[i] + off) + b[i]));
+            o[i] = score_exp((float)((a[i] + b[i]) - score));
             c[i] = b[i] + (double)e[i];
         }
-        occ_store<NR>(y.ob + (int64_t)t * S, o);
+        occ_store<NR>(y.ob + (int64_t)t * (2 * S), o);
         if constexpr (NR == 1) {
             const double a1 = acc_shift<false>(c[0]);
             const double a2 = acc_shift<false>(a1);
@@ -223,7 +232,8 @@ __global__ __launch_bounds__(kScoreWaves * 64) void crf_ctc_score_grad_beta_kern
         for (int i = 0; i < NR; ++i) b[i] = n[i];
     };
 
-    float ea[PF][NR], eb[PF][NR], aa[PF][NR], ab[PF][NR];
+    float ea[PF][NR], eb[PF][NR];
+    double aa[PF][NR], ab[PF][NR];
     fetch(ea, aa, lx - 1);
     for (int t0 = lx - 1; t0 >= 0; t0 -= 2 * PF) {
         fetch(eb, ab, t0 - PF);
@@ -270,7 +280,7 @@ __global__ __launch_bounds__(kScoreGradReduceThreads) void crf_ctc_score_grad_re
             const int *ul = p.labels + p.hyp_off[hk];
             const float w = p.weight ? p.weight[hk] : 1.f;
             for (int f = wave; f < nl; f += NW) {
-                const float *o = p.occ + ((int64_t)hk * p.T + (t0 + f)) * S;
+                const float *o = p.occ + ((int64_t)hk * p.T + (t0 + f)) * (2 * S);   // (the floats at the start of a row of S doubles)
                 float *row = rows + f * V;
                 float z = 0.f;                                     // the frame's occupancies sum to 1: their own sum is the normaliser
                 for (int s = lane; s < Sx; s += 64) z += o[s];

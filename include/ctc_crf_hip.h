@@ -296,8 +296,9 @@ int crf_ctc_score_logits(const void *act_dev, int dtype, int time_major, int bla
  * scattered onto their labels with LDS float adds, whose order is not fixed (scores and invalid are bit for bit all the same).
  * Limits: max_hyp_len <= 255 (one wave per hypothesis, 2 L + 1 <= 512 states) and V <= 8192 (the reduce stage keeps a row in LDS), beyond
  * CRF_ERR_UNSUPPORTED, the message naming the limit.
- * Workspace: crf_ctc_score_grad_workspace_bytes (the stored alphas, then the occupancies in their place, [H][T][64 NR] fp32 with NR = 1, 2, 4, 8 the
- * states per lane, and the H scores; >= 4 H T (2 max_hyp_len + 1); offsets into it are 64-bit; its contents on entry do not matter;
+ * Workspace: crf_ctc_score_grad_workspace_bytes (the stored alphas, [H][T][64 NR] fp64 with NR = 1, 2, 4, 8 the states per lane -- fp64 so
+ * that they are exact whatever the cost per frame; the fp32 occupancies then go over the first half of each row -- and the H scores;
+ * >= 8 H T (2 max_hyp_len + 1); offsets into it are 64-bit; its contents on entry do not matter;
  * -1 with crf_last_error() set for a shape not taken).
  * CRF_ERR_ARG: null pointer (weight_dev, score_dev and invalid_dev excepted), blank outside [0, V), B, H, T or V <= 0, max_hyp_len < 0,
  * B * T > INT32_MAX (H and V are ints as well); CRF_ERR_WORKSPACE: workspace too small (the message names the bytes needed) -- all

@@ -1,6 +1,6 @@
 """GPU test: crf_ctc_score_grad through the C ABI on buffers carved from a guard-banded arena (tests/guard.py), as
 tests/test_gpu_sample_guard_bands.py does for the sampler -- the workspace exactly as large as crf_ctc_score_grad_workspace_bytes says,
-one state per lane (NR = 1) and eight (NR = 8), both layouts.  No byte outside the call's own buffers may change, every word of grad, scores
+one state per lane (NR = 1) and eight (NR = 8), and V = 8192 (the largest row the reduce stage keeps in LDS), both layouts.  No byte outside the call's own buffers may change, every word of grad, scores
 and invalid must be written, and the results are those of tests/test_gpu_ctc_score_grad.py's first test."""
 import ctypes
 
@@ -33,7 +33,7 @@ def run_guarded(core, x, hyps, utt, lx, blank, w, time_major):
     lab = i32(flat(hyps)) if int(hl.sum()) else torch.zeros(1, dtype=torch.int32)
     off = (torch.cumsum(hl, 0, dtype=torch.int32) - hl).to(torch.int32)
     nws = core._lib.crf_ctc_score_grad_workspace_bytes(B, H, T, V, max_l)
-    assert nws >= 4 * H * T * (2 * max_l + 1)
+    assert nws >= 8 * H * T * (2 * max_l + 1)
     nact = 4 * x.numel()
     ints = (("labels", lab), ("off", off), ("len", hl), ("utt", i32(utt)), ("lx", i32(lx)))
     arena = Arena(dev, Arena.room([nact, nact, 4 * H, 4 * H, 4 * H, nws] + [4 * t.numel() for _, t in ints]))
@@ -76,6 +76,35 @@ def test_score_grad_writes_only_its_own_memory_nr1(core, time_major):
     assert not np.any(g[1]) and np.array_equal(inv, 1 - c["valid"])
     ok = c["valid"] == 1
     assert np.all(np.isinf(sc[~ok])) and np.all(np.abs(sc[ok] - c["cost"][ok]) <= 1e-4 * np.abs(c["cost"][ok]))
+
+
+_WIDE = {}
+
+
+def wide_batch():
+    """V = 8192, the most the reduce stage takes: one frame per workgroup, its LDS row 32 KiB; the last class is a label."""
+    if not _WIDE:
+        N, T, V, blank = 2, 5, 8192, 0
+        rng = np.random.default_rng(8192)
+        hyps = [np.array([V - 1, 1, V - 1], dtype=np.int32), rng.integers(1, V, size=2).astype(np.int32), np.zeros(0, np.int32),
+                np.array([V - 1], dtype=np.int32)]
+        utt, lx = [0, 0, 1, 1], [5, 3]
+        logp = logp_normal(rng, N, T, V)
+        gamma, cost, valid = ref_gamma(logp, hyps, utt, lx, blank)
+        assert valid.tolist() == [1, 1, 1, 1]
+        _WIDE.update(logp=logp, hyps=hyps, utt=utt, lx=lx, blank=blank, gamma=gamma, cost=cost, valid=valid, w=rng.uniform(0.25, 2.0, size=4))
+    return _WIDE
+
+
+@pytest.mark.parametrize("time_major", [False, True])
+def test_score_grad_writes_only_its_own_memory_v8192(core, time_major):
+    c = wide_batch()
+    x = torch.tensor(c["logp"])
+    g, sc, inv = run_guarded(core, x.transpose(0, 1).contiguous() if time_major else x, c["hyps"], c["utt"], c["lx"], c["blank"], c["w"], time_major)
+    assert core.last_score_grad_kernel() == "crf_ctc_score_grad_alpha_kernel<1>"
+    g = g.transpose(1, 0, 2) if time_major else g
+    check_grad(g, fold(c["gamma"], c["cost"], c["valid"], c["utt"], c["w"], 2), c["lx"], True, f"guarded V = 8192 time_major={time_major}")
+    assert not np.any(inv) and np.all(np.abs(sc - c["cost"]) <= 1e-4 * np.abs(c["cost"]))
 
 
 _LONG = {}
