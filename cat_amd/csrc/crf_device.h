@@ -27,7 +27,15 @@ constexpr int kGradFrames = 4;  // frames per crf_grad_kernel workgroup
 // tests/test_gpu_parity.py::test_single_frame_shrink_window[110]: gradient 90 % off, loss right).  2^-4: the product stays normal wherever
 // e' itself is, and 2^64 * 2^55 * 2^-4 < 2^127 at the other end.
 constexpr int kGradDescale = 4;
+// The flag words of a call (LossParams::err points to the first): the context's fine-grained block or, without one, the block behind the
+// exchange granules in the workspace.  The prep kernel clears the first kFlagWords (LossParams::clear) of the context's block.
+constexpr int kFlagErr = 0;         // error word: an exchange or a stage wait timed out
+constexpr int kFlagStarted = 1;     // start counter: workgroups of the den kernels that hold a CU
+constexpr int kFlagProbe = 0;       // words [0 .. 4) between calls: the handshake of the side-stream probe (two flags, two results) ...
+constexpr int kFlagProbeWarm = 8;   // ... and [8 .. 12): its warm-up launch, which shakes hands with itself
+constexpr int kFlagStage = 16;      // first stage counter: stage k of the recursions bumps word kFlagStage + k (k < kMaxStages of stage_plan.h)
 constexpr int kFlagFallback = 40;   // words [40], [41] behind the error word: utterances of the last call redone by the denominator / numerator fallback (crf_finalize_kernel)
+constexpr int kFlagWords = 64;
 
 struct LossParams {
     GraphDev g;

@@ -1,7 +1,10 @@
-// cat_amd/csrc/crf_host.hip -- the host side of the CTC-CRF loss: workspace layout, streams and schedule, kernel launches, the C-ABI entry
-// points of include/ctc_crf_hip.h.  (Forced alignment, hypothesis scores and sampling share nothing with the loss call: crf_host_ctc.hip;
-// what both host units use -- the section records, launch<> -- is crf_host_util.h.)  The kernels live in one translation unit per family
-// (cat_amd/build.py compiles them in parallel):
+// cat_amd/csrc/crf_host.hip -- the host side of the CTC-CRF loss, in the order of a call: the denominator kernel family is chosen once
+// (DenFamily, choose_den_family), the workspace is laid down for it as a list of sections (ws_layout; the arrays inside the sections pb,
+// xch and bsm come from one field list each), the kernels and the schedule are planned as data (CallPlan; the stage plan itself is host C++
+// in stage_plan.cpp), the sections and fields are bound to the kernels' parameter blocks by name (bind_params), and a LossCall enqueues one
+// of four stream schedules; then the C-ABI entry points of include/ctc_crf_hip.h.  (Forced alignment, hypothesis scores and sampling share
+// nothing with the loss call: crf_host_ctc.hip; what both host units use -- section and field records, launch<>, with_nr -- is
+// crf_host_util.h.)  The kernels live in one translation unit per family (cat_amd/build.py compiles them in parallel):
 //   k_chain.hip      prep (e' = exp(logp - rowmax) * 2^64), metadata staging, streaming denominator chains, numerator (CTC) chains in fp64
 //   k_fac_*.hip      register-resident denominator recursions on the factored layout of T o LM graphs (k_fac_body.h): the dominant kernels
 //   k_res.hip        register-resident recursions, generic layout over K compute units
@@ -34,6 +37,7 @@
 #include "crf_device.h"
 #include "crf_kernels_decl.h"
 #include "crf_host_util.h"
+#include "stage_plan.h"
 
 namespace crf {
 
@@ -61,12 +65,7 @@ struct WsLayout {
     int nsec;
     int64_t total;               // = the running end of the layout while it is being made
     int64_t gap;
-    int64_t xch_bytes;
-    int64_t Rq, Rb;
-    bool res, gv, fac;
-    int p2mode;                  // two utterances per workgroup: 0 no, 1 on the main factored layout, 2 on HostGraph::facp (pair2_mode)
-    bool bat; int UL; int64_t Bp;   // utterance-minor layout (large graphs)
-    bool gv_robust;              // the robust fallback kernels keep their vectors in global memory too
+    int64_t xch_bytes;           // the exchange granules in front of the flag words of section xch
     int64_t state_stride, gvec_stride, dump_stride;
     // the next section: starts at the running end, which then moves past its bytes to the next multiple of 256 (+ the ws_gap bytes)
     void add(WsSec k, int64_t bytes) {
@@ -76,6 +75,35 @@ struct WsLayout {
     }
     int64_t off(WsSec k) const { return sec[k].off; }
 };
+
+// The arrays inside three of the sections, X(name, element bytes, a, c): a * B + c elements (bsm: a * Bp + c), packed in list order.  The
+// section's bytes and every pointer into it come from its list (fields_off; crf_debug_ws_fields shows the map).
+//   pb     per-utterance results and marks (LossParams; [B] unless noted): cb_part [B][kResMaxK], redo [2][B]; 256 B bytes
+//   xch    behind the granules (WsLayout::xch_bytes): the flag words of a call without a context's fine-grained block (crf_device.h kFlag*)
+//   bsm    utterance-minor kernels (BatchParams): mxf, mxb [3][Bp]; bar = the persistent launch's grid barrier [kBatBarWords], its time-out
+//          word (BatchParams::err) and 127 words more, ONE field: crf_batch_init_kernel clears all 640 words through `bar`
+#define CRF_PB_FIELDS(X)                                                                                                                          \
+    X(ctc_zc, 8, 1, 0) X(cb_mxs, 8, 1, 0) X(den_zs, 4, 1, 0) X(den_ez, 4, 1, 0) X(ctc_ez, 4, 1, 0) X(cost_alpha, 4, 1, 0) X(cost_beta, 4, 1, 0)     \
+    X(cost_ctc, 4, 1, 0) X(invalid, 4, 1, 0) X(spare0, 4, 1, 0) X(cb_part, 4, kResMaxK, 0) X(cb_F, 4, 1, 0) X(spare1, 4, 7 - kResMaxK, 0)          \
+    X(redo, 4, 2, 0) X(redo_ctc, 4, 1, 0) X(ctc_logdom, 4, 1, 0) X(spare2, 4, 40, 0)
+#define CRF_XCH_FIELDS(X) X(flags, 4, 0, kFlagWords) X(spare0, 8, 1, 0)
+#define CRF_BSM_FIELDS(X) X(mxf, 4, 3, 0) X(mxb, 4, 3, 0) X(Ef, 4, 1, 0) X(Fb, 4, 1, 0) X(zs, 4, 1, 0) X(zb, 4, 1, 0) X(spare0, 4, 2, 0) X(bar, 4, 0, 640)
+constexpr int kBatBarWords = 512;
+static_assert(kResMaxK <= 7, "cb_part and cb_F share the eight floats per utterance in front of redo");
+#define CRF_FIELD_REC(name, elem, a, c) {#name, elem, a, c},
+#define CRF_PB_ENUM(name, ...) kPb_##name,
+#define CRF_XCH_ENUM(name, ...) kXch_##name,
+#define CRF_BSM_ENUM(name, ...) kBsm_##name,
+enum PbField : int { CRF_PB_FIELDS(CRF_PB_ENUM) kPbCount };
+enum XchField : int { CRF_XCH_FIELDS(CRF_XCH_ENUM) kXchCount };
+enum BsmField : int { CRF_BSM_FIELDS(CRF_BSM_ENUM) kBsmCount };
+static const WsField kPbFields[kPbCount] = {CRF_PB_FIELDS(CRF_FIELD_REC)};
+static const WsField kXchFields[kXchCount] = {CRF_XCH_FIELDS(CRF_FIELD_REC)};
+static const WsField kBsmFields[kBsmCount] = {CRF_BSM_FIELDS(CRF_FIELD_REC)};
+#undef CRF_PB_ENUM
+#undef CRF_XCH_ENUM
+#undef CRF_BSM_ENUM
+#undef CRF_FIELD_REC
 
 // the register-resident kernels are used whenever the graph fits them (res.K > 0) and V fits their
 // emission-row prefetch; CRF_NO_RESIDENT=1 at graph creation forces the streaming kernels
@@ -106,65 +134,89 @@ static size_t robust_lds_bytes(const HostGraph *h, int V, bool gv) {
     return std::max((size_t)2 * rup64(h->dev.S) + h->dev.Pr, (size_t)4 * h->dev.Pr) * 8 + tail;   // (fp64 logarithms: den_forward_robust / den_backward_robust)
 }
 
-static WsLayout ws_layout(const HostGraph *h, int64_t B, int64_t T, int64_t V, int64_t Sc) {
-    WsLayout w{};
-    w.gap = ws_gap_bytes();
-    w.fac = use_factored(h, V);
-    w.res = w.fac || use_resident(h, V);   // "res": register-resident kernels of either layout
+// The denominator kernels of a call, chosen ONCE from the graph, B, V and the switches (read per call): the workspace is laid down for this
+// family, the plan and the launches read it (CallPlan::fam).  The enumerators are what crf_den_kernels returns.
+enum DenKind : int { kDenNone = -1, kDenStreaming = 0, kDenResident = 1, kDenFactored = 2, kDenBatch = 3 };
+struct DenFamily {
+    DenKind kind = kDenNone;     // none: a numerator-only call (no graph)
+    bool gv = false;             // streaming kernels: the state vectors do not fit the LDS and live in the workspace (section gvec)
+    bool gv_robust = false;      // the robust fallback kernels keep their vectors in global memory too
+    int p2mode = 0;              // two utterances per workgroup: 0 no, 1 on the main factored layout, 2 on HostGraph::facp (pair2_mode)
+    const FacDev *FX = nullptr;  // factored: the layout this call works with -- the main one, or (p2mode 2) the second one
+    int UL = 0; int64_t Bp = 0;  // utterance-minor layout (large graphs): utterances per group, B rounded up to it
+    int64_t Rq = 0, Rb = 0;      // row strides of Q / BP
+    bool fac() const { return kind == kDenFactored; }
+    bool res() const { return kind == kDenFactored || kind == kDenResident; }   // register-resident kernels of either layout
+    bool bat() const { return kind == kDenBatch; }
+    bool pair2() const { return p2mode != 0; }
+};
+static DenFamily choose_den_family(const HostGraph *h, int64_t B, int64_t V) {
+    DenFamily f;
+    bool fac = use_factored(h, V), res = fac || use_resident(h, V);
     // graphs that fit neither register-resident layout take the utterance-minor kernels (CRF_NO_BATCH=1: the streaming
     // kernels instead; CRF_FORCE_BATCH=1: every graph, for tests)
     const bool force_bat = opt_on(kOpt_force_batch);
-    w.bat = h && h->dev.bat.ok && (force_bat || (!w.res && !opt_on(kOpt_no_batch)));
-    if (w.bat) w.res = w.fac = false;
+    const bool bat = h && h->dev.bat.ok && (force_bat || (!res && !opt_on(kOpt_no_batch)));
+    if (bat) res = fac = false;
+    f.kind = !h ? kDenNone : bat ? kDenBatch : fac ? kDenFactored : res ? kDenResident : kDenStreaming;
     // utterances per group: as wide as the batch allows (an arc is fetched once per group); 32 instead of 64 when a group's state
     // vector [S][64] would not stay in an XCD's 4 MiB L2 next to the arc stream (> ~2.25 MB) -- but never narrower than 32 for
     // that reason: every group reads the whole arc stream again and narrower gathers are partial lines (measured: S = 16 385,
     // B = 64: UL 64 / 32 / 16 -> 31.6 / 29.7 / 34.5 ms; config #5 with B = 64, where not even [S][8] fits: UL 64 / 32 / 8 -> 379 /
     // 271 / 569 ms).  CRF_BAT_UL overrides, for sweeps.
-    w.UL = B > 32 ? 64 : B > 16 ? 32 : B > 8 ? 16 : 8;
-    if (h && w.UL == 64 && std::max<int64_t>(h->dev.S, h->dev.P) * w.UL * 4 > (int64_t)(2.25 * 1024 * 1024)) w.UL = 32;
-    { const int v = opt(kOpt_bat_ul, 0); if (v == 8 || v == 16 || v == 32 || v == 64) w.UL = v; }
-    w.Bp = (B + w.UL - 1) / w.UL * w.UL;
+    f.UL = B > 32 ? 64 : B > 16 ? 32 : B > 8 ? 16 : 8;
+    if (h && f.UL == 64 && std::max<int64_t>(h->dev.S, h->dev.P) * f.UL * 4 > (int64_t)(2.25 * 1024 * 1024)) f.UL = 32;
+    { const int v = opt(kOpt_bat_ul, 0); if (v == 8 || v == 16 || v == 32 || v == 64) f.UL = v; }
+    f.Bp = (B + f.UL - 1) / f.UL * f.UL;
+    f.p2mode = fac ? pair2_mode(h, B, V) : 0;
+    f.FX = fac ? (f.p2mode == 2 ? &h->facp : &h->dev.fac) : nullptr;
     // (rows are at least Pr wide: the robust fallback stores them in pair order, whatever layout the fast kernels use)
-    w.p2mode = w.fac ? pair2_mode(h, B, V) : 0;
-    const FacDev *FX = w.fac ? (w.p2mode == 2 ? &h->facp : &h->dev.fac) : nullptr;   // the factored layout this call works with
-    w.Rq = h ? std::max<int64_t>(w.fac ? FX->Rq : w.res ? h->dev.res.f.R : h->dev.Pr, h->dev.Pr) : 0;
-    w.Rb = h ? std::max<int64_t>(w.fac ? FX->Rbp : w.res ? h->dev.res.b.R : h->dev.Pr, h->dev.Pr) : 0;
+    f.Rq = h ? std::max<int64_t>(fac ? f.FX->Rq : res ? h->dev.res.f.R : h->dev.Pr, h->dev.Pr) : 0;
+    f.Rb = h ? std::max<int64_t>(fac ? f.FX->Rbp : res ? h->dev.res.b.R : h->dev.Pr, h->dev.Pr) : 0;
+    f.gv = h && !res && !bat && std::max((size_t)3 * rup64(h->dev.S), (size_t)4 * h->dev.Pr) * 4 + 2 * (size_t)rup64((int)V) * 4 + 1024 > 160 * 1024;
+    f.gv_robust = h && robust_lds_bytes(h, (int)V, false) > 160 * 1024;
+    return f;
+}
+
+// the sections of a call of this family and shape, and nothing else
+static WsLayout ws_layout(const DenFamily &fam, const HostGraph *h, int64_t B, int64_t T, int64_t V, int64_t Sc) {
+    WsLayout w{};
+    w.gap = ws_gap_bytes();
+    const bool fac = fam.fac(), res = fam.res(), bat = fam.bat();
+    const FacDev *FX = fam.FX;
     w.add(kWs_ep, B * T * V * 4);
     w.add(kWs_mx, B * T * 4);
     w.add(kWs_moff, B * T * 4);   // fused log_softmax only (crf_loss_fwd_bwd_logits)
     w.add(kWs_invs, B * T * 4);
-    const int64_t qb = w.bat ? T * (int64_t)h->dev.P * w.Bp : 0;   // utterance-minor rows [T][P][Bp]
-    w.add(kWs_Q, std::max(B * T * w.Rq, qb) * 4);
-    w.add(kWs_BP, std::max(B * T * w.Rb, qb) * 4);
+    const int64_t qb = bat ? T * (int64_t)h->dev.P * fam.Bp : 0;   // utterance-minor rows [T][P][Bp]
+    w.add(kWs_Q, std::max(B * T * fam.Rq, qb) * 4);
+    w.add(kWs_BP, std::max(B * T * fam.Rb, qb) * 4);
     w.add(kWs_EQ, B * T * 4);
     w.add(kWs_EB, B * T * 4);
     w.add(kWs_CA, B * T * Sc * 8);
     w.add(kWs_CB, B * T * Sc * 8);
     w.add(kWs_ECA, B * T * 4);
     w.add(kWs_ECB, B * T * 4);
-    w.add(kWs_pb, 32 * B * 8);
+    w.add(kWs_pb, fields_off(kPbFields, kPbCount, B));
     w.add(kWs_cbad, B * T * 4);   // frames of the numerator marked for the log-domain fallback
     // tagged granules [2 slots] of both directions, then one XCD-id word per CU of every recursion
-    w.xch_bytes = (w.res && !w.fac && h->dev.res.K > 1) ? al((B * 2 * ((int64_t)h->dev.res.f.G + h->dev.res.b.G) + 2 * B * kResMaxK) * 8)
-                : (w.fac && FX->K > 1) ? al((B * 2 * ((int64_t)FX->f.G + FX->b.G) + 2 * B * kResMaxK) * 8) : 0;
-    w.add(kWs_xch, w.xch_bytes + 256 + 8 * B);   // granules | error word, start counter | per-utterance progress of the two den recursions
-    w.add(kWs_row0, w.res ? B * w.Rb * 4 : 0);
-    w.add(kWs_ept, w.bat ? T * V * w.Bp * 4 : 0);
-    w.add(kWs_Af, w.bat ? 2 * ((int64_t)h->dev.S + (h->fb.ok ? h->fb.NU : 0)) * w.Bp * 4 : 0);   // (+ the U entries of factored streams)
-    w.add(kWs_Zb, w.bat ? 2 * (int64_t)h->dev.P * w.Bp * 4 : 0);
-    w.add(kWs_bsm, w.bat ? (12 * w.Bp + 640) * 4 : 0);   // mxf[3], mxb[3], Ef, Fb, zs, zb | grid barrier words [512], time-out word (persistent launch)
-    w.gv = h && !w.res && !w.bat && std::max((size_t)3 * rup64(h->dev.S), (size_t)4 * h->dev.Pr) * 4 + 2 * (size_t)rup64((int)V) * 4 + 1024 > 160 * 1024;
-    w.gv_robust = h && robust_lds_bytes(h, (int)V, false) > 160 * 1024;
+    w.xch_bytes = (res && !fac && h->dev.res.K > 1) ? al((B * 2 * ((int64_t)h->dev.res.f.G + h->dev.res.b.G) + 2 * B * kResMaxK) * 8)
+                : (fac && FX->K > 1) ? al((B * 2 * ((int64_t)FX->f.G + FX->b.G) + 2 * B * kResMaxK) * 8) : 0;
+    w.add(kWs_xch, w.xch_bytes + fields_off(kXchFields, kXchCount, B));   // granules | CRF_XCH_FIELDS
+    w.add(kWs_row0, res ? B * fam.Rb * 4 : 0);
+    w.add(kWs_ept, bat ? T * V * fam.Bp * 4 : 0);
+    w.add(kWs_Af, bat ? 2 * ((int64_t)h->dev.S + (h->fb.ok ? h->fb.NU : 0)) * fam.Bp * 4 : 0);   // (+ the U entries of factored streams)
+    w.add(kWs_Zb, bat ? 2 * (int64_t)h->dev.P * fam.Bp * 4 : 0);
+    w.add(kWs_bsm, bat ? fields_off(kBsmFields, kBsmCount, fam.Bp) : 0);
     // (floats per utterance: the streaming kernels' fp32 vectors, or the log-domain fallback's fp64 ones -- forward A[2][Sp] + Ql[Pr], backward Z[2][Pr] + BPst[2][Pr])
     w.gvec_stride = h ? std::max<int64_t>(3 * (int64_t)rup64(h->dev.S) + 5 * (int64_t)h->dev.Pr, 2 * (2 * (int64_t)rup64(h->dev.S) + 5 * (int64_t)h->dev.Pr)) : 0;
-    w.add(kWs_gvec, (w.gv || w.gv_robust) ? B * w.gvec_stride * 4 : 0);
+    w.add(kWs_gvec, (fam.gv || fam.gv_robust) ? B * w.gvec_stride * 4 : 0);
     // factored recursions launched in segments park their state vector + exponent here: [2 dir][B][stride]
-    w.state_stride = w.fac ? rup64(std::max(FX->f.G, FX->b.G)) + 64 : 0;
+    w.state_stride = fac ? rup64(std::max(FX->f.G, FX->b.G)) + 64 : 0;
     w.add(kWs_state, 2 * B * w.state_stride * 4);
     // two utterances per workgroup: one dump row per (direction, pair) for the row stores of an utterance that has ended
-    w.dump_stride = w.fac ? al(std::max(w.Rq, w.Rb)) : 0;
-    w.add(kWs_dump, w.fac ? 2 * ((B + 1) / 2) * w.dump_stride * 4 : 0);
+    w.dump_stride = fac ? al(std::max(fam.Rq, fam.Rb)) : 0;
+    w.add(kWs_dump, fac ? 2 * ((B + 1) / 2) * w.dump_stride * 4 : 0);
     return w;
 }
 
@@ -191,9 +243,8 @@ static size_t chain_lds_bytes(const HostGraph *h, int V, int Sc, int role, bool 
 // not touch each other's events or counters; calls on ONE stream are ordered by the stream (the counters of call
 // n+1 are cleared by its prep kernel, which runs after call n has joined everything back into that stream).
 // ---------------------------------------------------------------------------------------------
-constexpr int kMaxStages = 16;
-constexpr int kStageFill = 75;   // staged schedule (and the numerator chains beside the recursions) for den grids of up to this percent of the CUs
 constexpr int kFlagInts = 2048;
+static_assert(kStageFrames == kGDFrames && kFlagStage + kMaxStages <= kFlagFallback && kFlagFallback + 2 <= kFlagWords, "stage_plan.h plans for the grad kernels' blocks; the stage counters lie between the named flag words");
 struct DevCtx {
     std::mutex mu;            // one call at a time is ENQUEUED through a context (host side only; nothing waits on the GPU)
     int dev = 0;
@@ -206,7 +257,7 @@ struct DevCtx {
     bool gd_fallback = false; // ... and this context has gone back to one grad launch per stage
     int call_id = 0;
     hipEvent_t fork{}, join{}, ev[kMaxStages]{}, evb[kMaxStages]{};
-    int *flags = nullptr;     // fine-grained (uncached, cross-XCD coherent) words: [0] error word, [1] start counter, [16..32) stage counters
+    int *flags = nullptr;     // fine-grained (uncached, cross-XCD coherent) words: crf_device.h kFlagErr, kFlagStarted, kFlagStage ..., kFlagProbe
     bool warned = false;
     int reprobes = 0;         // probes for a side stream after the first one found none (reprobe_side: at calls 256, 1 024, 4 096)
     int side_kind = 0, side_tries = 0;   // find_beside: what kind of stream the side stream is, how many candidates were probed
@@ -264,12 +315,13 @@ static bool runs_beside(hipStream_t owner, hipStream_t cand, int *flags) {
     int res[4] = {0, 0, 0, 0};
     // (a first launch on a new stream may pay for its queue's set-up: get that out of the way, or the owner's probe kernel
     // gives up before the candidate's has started -- the kernel below shakes hands with itself)
-    bool ran = launch<crf_probe_kernel>("crf_probe_kernel", dim3(1), dim3(1), 0, cand, flags + 8, 0, 0) == CRF_OK;
-    ran = ran && hipStreamSynchronize(cand) == hipSuccess && hipMemset(flags, 0, sizeof(res)) == hipSuccess;
-    ran = ran && launch<crf_probe_kernel>("crf_probe_kernel", dim3(1), dim3(1), 0, owner, flags, 0, 1) == CRF_OK;
-    ran = ran && launch<crf_probe_kernel>("crf_probe_kernel", dim3(1), dim3(1), 0, cand, flags, 1, 0) == CRF_OK;
+    int *const warm = flags + kFlagProbeWarm, *const hs = flags + kFlagProbe;
+    bool ran = launch<crf_probe_kernel>("crf_probe_kernel", dim3(1), dim3(1), 0, cand, warm, 0, 0) == CRF_OK;
+    ran = ran && hipStreamSynchronize(cand) == hipSuccess && hipMemset(hs, 0, sizeof(res)) == hipSuccess;
+    ran = ran && launch<crf_probe_kernel>("crf_probe_kernel", dim3(1), dim3(1), 0, owner, hs, 0, 1) == CRF_OK;
+    ran = ran && launch<crf_probe_kernel>("crf_probe_kernel", dim3(1), dim3(1), 0, cand, hs, 1, 0) == CRF_OK;
     ran = ran && hipStreamSynchronize(cand) == hipSuccess && hipStreamSynchronize(owner) == hipSuccess &&
-          hipMemcpy(res, flags, sizeof(res), hipMemcpyDeviceToHost) == hipSuccess;
+          hipMemcpy(res, hs, sizeof(res), hipMemcpyDeviceToHost) == hipSuccess;
     if (!ran) (void)hipGetLastError();
     return ran && res[2] == 1 && res[3] == 1;
 }
@@ -435,13 +487,11 @@ static int launch_den_pair(const LossParams &p, size_t lds, hipStream_t st) {
 }
 // numerator chains, forward + backward in one grid (profile slots 3 and 4); states per thread from the longest label sequence
 static int launch_ctc_pair(const LossParams &p, size_t lds, hipStream_t st, int64_t max_label_len) {
-    const int64_t ni = (2 * max_label_len + 1 + kCtcThreads - 1) / kCtcThreads;
     const dim3 grid((unsigned)(2 * p.B)), block(kCtcThreads);
     prof_mark(3, false, st); prof_mark(4, false, st);
-    const int rc = ni <= 1 ? launch<crf_ctc_pair_kernel<1>>("crf_ctc_pair_kernel", grid, block, lds, st, p)
-                 : ni <= 2 ? launch<crf_ctc_pair_kernel<2>>("crf_ctc_pair_kernel", grid, block, lds, st, p)
-                 : ni <= 4 ? launch<crf_ctc_pair_kernel<4>>("crf_ctc_pair_kernel", grid, block, lds, st, p)
-                           : launch<crf_ctc_pair_kernel<kCtcRegs>>("crf_ctc_pair_kernel", grid, block, lds, st, p);
+    const int rc = with_nr(2 * max_label_len + 1, kCtcThreads, [&](auto nr, int) {
+        return launch<crf_ctc_pair_kernel<decltype(nr)::value>>("crf_ctc_pair_kernel", grid, block, lds, st, p);
+    });
     prof_mark(3, true, st); prof_mark(4, true, st);
     return rc ? rc : launch<crf_ctc_check_kernel>("crf_ctc_check_kernel", dim3((unsigned)p.B), dim3(256), 0, st, p);
 }
@@ -517,7 +567,7 @@ static FacParams fac_params(const LossParams &lp, int dir, int *started, int i0,
     p.Out = dir == 0 ? lp.Q : lp.BP; p.Eout = dir == 0 ? lp.EQ : lp.EB; p.Row0 = lp.Row0;
     p.started = started; p.i0 = i0; p.i1 = i1; p.state = state;
     p.nb = nb; p.stage_cnt = stage_cnt;
-    for (int k = 0; k < 16; ++k) p.bound[k] = (bound && k < nb) ? bound[k] : 0;
+    for (int k = 0; k < kMaxStages; ++k) p.bound[k] = (bound && k < nb) ? bound[k] : 0;
     p.frow_meta = F.frow_meta; p.x_start = F.x_start; p.x_end = F.x_end;
     p.den_zs = lp.den_zs; p.cost_alpha = lp.cost_alpha; p.den_ez = lp.den_ez;
     p.brow_meta = F.brow_meta; p.z_lab = F.z_lab; p.z_end = F.z_end; p.brow_start = F.brow_start; p.brow_end = F.brow_end;
@@ -634,18 +684,19 @@ using namespace crf;
 extern "C" {
 
 int64_t crf_workspace_bytes(const crf_graph *g, int64_t B, int64_t T, int64_t V, int64_t max_label_len) {
-    const int64_t Sc = rup64((int)(2 * max_label_len + 1));
-    return ws_layout(g ? g->h : nullptr, B, T, V, Sc).total;
+    const HostGraph *h = g ? g->h : nullptr;
+    return ws_layout(choose_den_family(h, B, V), h, B, T, V, rup64((int)(2 * max_label_len + 1))).total;
 }
 
 int crf_den_kernels(const crf_graph *g, int64_t B, int64_t T, int64_t V) {
+    (void)T;
     if (!g || !g->h) { set_error("null graph"); return -1; }
-    const WsLayout w = ws_layout(g->h, B, T, V, 64);
-    return w.bat ? 3 : w.fac ? 2 : w.res ? 1 : 0;
+    return choose_den_family(g->h, B, V).kind;
 }
 
 int crf_debug_ws_sections(const crf_graph *g, int64_t B, int64_t T, int64_t V, int64_t max_label_len, int64_t *out, int n_out) {
-    const WsLayout w = ws_layout(g ? g->h : nullptr, B, T, V, rup64((int)(2 * max_label_len + 1)));
+    const HostGraph *h = g ? g->h : nullptr;
+    const WsLayout w = ws_layout(choose_den_family(h, B, V), h, B, T, V, rup64((int)(2 * max_label_len + 1)));
     return copy_sections(w.sec, w.nsec, out, n_out);
 }
 const char *crf_debug_ws_section_names(void) {
@@ -653,72 +704,31 @@ const char *crf_debug_ws_section_names(void) {
     return s.c_str();
 }
 
-// Stage bounds of the staged grad pass (crf_loss_fwd_bwd; crf_debug_stage_plan shows them to the tests): bound[0] = 0 < bound[1] < ... < bound[nstage] = T,
-// stage k = the recursions' iterations [bound[k-1], bound[k]).  Returns nstage; *gd_piece = the length of the equal pieces.
-static int plan_grad_stages(int64_t T, bool segmode, int stages_env, int pieces, int *bound, int *gd_piece_out, int stage_launches = -1) {
-    // stage_launches: one grad launch per stage (round 4's schedule) -- the switch gd_stage_launches, or a context whose one-launch grad pass has
-    // timed out once (DevCtx::gd_fallback)
-    const bool per_stage = stage_launches >= 0 ? stage_launches != 0 : opt_on(kOpt_gd_stage_launches);
-    int nstage = 1, gd_piece = 0;
-    bound[0] = 0;
-    bound[1] = (int)T;
-    if (T >= 256) {
-        const int half = (int)((T / 2 + kGDFrames - 1) / kGDFrames * kGDFrames);
-        int piece, first = half;
-        if (stages_env > 0 || segmode) {
-            const int nshort = std::max(1, std::min(std::min(pieces, kMaxStages - 2), (int)(T - half) / 32));
-            piece = ((int)T - half + nshort - 1) / nshort;
-            piece = (piece + kGDFrames - 1) / kGDFrames * kGDFrames;
-        } else {
-            // (round 5, one grad launch for all stages: a stage costs the grad pass nothing any more and the recursions one drain + barrier;
-            // pieces of 48 .. 96 iterations all give 2.71 ms where 128 gives 2.75 and round 4's per-stage launches 2.82: profiles/round5_ab_grad_one_launch.txt)
-            piece = per_stage ? 128 : 80;
-            while ((kMaxStages - 4) * piece < (int)T - half && piece < (int)T) piece += per_stage ? 128 : 16;   // the stage counters cover T - half
-            const int piece_env = opt(kOpt_piece, 0);
-            if (piece_env > 0) piece = (piece_env + kGDFrames - 1) / kGDFrames * kGDFrames;
-            const int body = std::min((int)T - half, (kMaxStages - 2) * piece);   // (a CRF_PIECE too small for the counters)
-            first = std::max(half, ((int)T - body + kGDFrames - 1) / kGDFrames * kGDFrames);
-            const int fs = opt(kOpt_first_shift, 0);
-            if (fs > 0) first = std::min((int)T - kGDFrames, first + fs * kGDFrames);
-        }
-        nstage = 1;
-        gd_piece = piece;
-        bound[1] = first;
-        while (bound[nstage] < T && nstage < kMaxStages - 1) { bound[nstage + 1] = std::min((int)T, bound[nstage] + piece); ++nstage; }
-        bound[nstage] = (int)T;
-        // taper: the last stage is what is left to do when the recursions have ended; with one grad launch for all stages (its workgroups
-        // wait themselves) a stage costs the grad pass nothing and the recursions one drain + barrier, so the last pieces are halved down
-        // to `taper` iterations: ..., piece, piece / 2, piece / 4, ..., taper
-        const int taper = stages_env > 0 || segmode || per_stage ? 0 : (opt(kOpt_taper, 32) + kGDFrames - 1) / kGDFrames * kGDFrames;
-        if (taper > 0 && taper < piece && nstage >= 3) {
-            int desc[kMaxStages + 8], n = 0, pos = (int)T;             // stage ends from the last one backwards
-            desc[n++] = pos;
-            for (int q = taper; q < piece && n < 8; q *= 2) { pos -= q; desc[n++] = pos; }
-            while (pos - piece > first + kGDFrames && n < kMaxStages + 6) { pos -= piece; desc[n++] = pos; }
-            if (pos > first && n + 1 <= kMaxStages - 1) {               // (the piece behind `first` takes what is left: 16 .. piece + 16 iterations)
-                nstage = n + 1;
-                bound[1] = first;
-                for (int k = 0; k < n; ++k) bound[2 + k] = desc[n - 1 - k];
-            }
-        }
-    }
-    *gd_piece_out = gd_piece;
-    return nstage;
+// the field lists of the sections pb, xch (behind the granules) and bsm
+static int ws_field_list(const char *section, const WsField **f) {
+    const std::string s = section ? section : "";
+    if (s == "pb") { *f = kPbFields; return kPbCount; }
+    if (s == "xch") { *f = kXchFields; return kXchCount; }
+    if (s == "bsm") { *f = kBsmFields; return kBsmCount; }
+    set_error("crf_debug_ws_fields: section '" + s + "' has no field list (pb, xch, bsm)");
+    return -1;
 }
-
-// The one-launch grad pass's grid (crf_grad_den_kernel, gd_persist): first block of the candidates of the stages `stage` .. nstage, frames per
-// workgroup in each; returns the number of workgroups
-static int64_t plan_grad_grid(const int *bound, int nstage, int stage, int64_t B, int gd_piece, int *poff, int *fpb) {
-    int64_t tot = 0;
-    const int sub_env = opt(kOpt_gd_sub, 16);              // frames per workgroup in a last stage shorter than `piece` (16: whole blocks)
-    const int fsub = sub_env == 8 ? 8 : sub_env == 4 ? 4 : sub_env == 2 ? 2 : kGDFrames;
-    for (int k = stage; k <= nstage; ++k) {
-        poff[k] = (int)tot;
-        fpb[k] = (k == nstage && bound[k] - bound[k - 1] < gd_piece) ? fsub : kGDFrames;   // (the LAST stage only)
-        tot += 2 * (int64_t)((bound[k] - bound[k - 1] + kGDFrames - 1) / kGDFrames + 3) * (kGDFrames / fpb[k]) * B;
+int crf_debug_ws_fields(const char *section, int64_t n, int64_t *out, int n_out) {
+    const WsField *f = nullptr;
+    const int nf = ws_field_list(section, &f);
+    for (int k = 0; k < nf && out && 3 * k + 2 < n_out; ++k) {
+        out[3 * k] = fields_off(f, k, n); out[3 * k + 1] = fields_off(f, k + 1, n) - out[3 * k]; out[3 * k + 2] = f[k].elem;
     }
-    poff[nstage + 1] = (int)tot;
-    return tot;
+    return nf;
+}
+const char *crf_debug_ws_field_names(const char *section) {
+    static thread_local std::string s;
+    const WsField *f = nullptr;
+    const int nf = ws_field_list(section, &f);
+    if (nf < 0) return nullptr;
+    s.clear();
+    for (int k = 0; k < nf; ++k) { if (k) s += ','; s += f[k].name; }
+    return s.c_str();
 }
 
 static int loss_impl(const crf_graph *g, const float *logp, int fused, int in_dtype, const int32_t *labels, const int32_t *lab_off,
@@ -786,47 +796,41 @@ struct DevFacts {
     int call_id = 0, seen = 0;   // this call's number; the call that last ran the numerator's log-domain chains (DevCtx::seen: a racing word, ONE read per call)
 };
 struct CallPlan {
-    // kernel families and sizes, from the graph and the shape alone (plan_kernels)
+    // the denominator family (choose_den_family), kernels and sizes, from the graph and the shape alone (plan_kernels)
     const HostGraph *h;
-    bool den, ctc, res, gv, fac, bat;   // "res": register-resident kernels of either layout
-    const FacDev *FX;                   // the factored layout this call works with: the main one, or -- two utterances per workgroup on 512 threads -- the second one
-    bool pair2;
+    DenFamily fam;
+    bool den, ctc;
     int Sc, gnc, gcap, robust_env;
     bool grad_stage, gd_wide, gd_wide6, fast_den, fast_ctc;
     size_t lds_den, lds_ctc, lds_grad;  // dynamic LDS of the den recursions (whichever family), the numerator chains, the generic grad kernel
     // the schedule (plan_schedule)
     int ncu; int64_t den_wgs; bool have_flags, serial, no_overlap, segmode, staged, per_stage, ctc_wants_aux, par3;
-    int nstage, gd_piece, bound[kMaxStages + 1];
+    StagePlan stages;
 };
 static std::atomic<bool> g_use_segments{false};      // set when hipStreamWaitValue32 is refused
 
-static CallPlan plan_kernels(const HostGraph *h, const WsLayout &w, int64_t V, int64_t max_label_len, int Sc, bool den, bool ctc) {
+static CallPlan plan_kernels(const HostGraph *h, const DenFamily &fam, int64_t V, int64_t max_label_len, int Sc, bool den, bool ctc) {
     CallPlan pl{};
-    pl.h = h; pl.den = den; pl.ctc = ctc; pl.Sc = Sc;
-    pl.res = den && w.res; pl.gv = den && w.gv; pl.fac = den && w.fac; pl.bat = den && w.bat;
-    const bool res = pl.res, gv = pl.gv, fac = pl.fac, bat = pl.bat;
-    // (ws_layout has sized the rows for the layout pair2_mode names; everything reads it through p.g.fac / FX)
-    pl.FX = fac ? (w.p2mode == 2 ? &h->facp : &h->dev.fac) : nullptr;
-    // two utterances per workgroup (use_fac_pair2): the den grid is 2 * ceil(B / 2) workgroups instead of 2 B
-    pl.pair2 = fac && w.p2mode != 0;   // (pair2_mode, decided with the workspace layout: the rows are sized for the layout it names)
+    pl.h = h; pl.fam = fam; pl.den = den; pl.ctc = ctc; pl.Sc = Sc;
+    const bool res = fam.res(), gv = fam.gv, fac = fam.fac(), bat = fam.bat();   // (den is false without a graph, and then so are these)
     if (den && !res && !bat) pl.lds_den = std::max(chain_lds_bytes(h, (int)V, pl.Sc, 0, gv), chain_lds_bytes(h, (int)V, pl.Sc, 1, gv));
     if (res && !fac) pl.lds_den = std::max(res_lds_bytes(h, (int)V, 0, h->res_rows_cu_f), res_lds_bytes(h, (int)V, 1, h->res_rows_cu_b));
-    if (fac) pl.lds_den = pl.pair2 ? std::max(fac2u_lds_bytes(*pl.FX, (int)V, 0), fac2u_lds_bytes(*pl.FX, (int)V, 1))
+    if (fac) pl.lds_den = fam.pair2() ? std::max(fac2u_lds_bytes(*fam.FX, (int)V, 0), fac2u_lds_bytes(*fam.FX, (int)V, 1))
                                    : std::max(fac_lds_bytes(h, (int)V, 0), fac_lds_bytes(h, (int)V, 1));
     pl.lds_ctc = chain_lds_bytes(h, (int)V, pl.Sc, 2);
     const int gnc_all = den ? std::max(std::max(h->dev.NC, h->dev.res.NC), std::max(h->dev.fac.ok ? h->dev.fac.NC : 0, h->facp.ok ? h->facp.NC : 0)) : 0;
     // the generic grad kernel stages the two rows of a frame in LDS when they fit, else gathers them from L2
-    pl.grad_stage = !den || bat || ((size_t)rup64((int)w.Rq) + rup64((int)w.Rb) + rup64(gnc_all) + 2 * (size_t)rup64((int)V)) * 4 <= 150 * 1024;
-    pl.lds_grad = ((den && !bat && pl.grad_stage ? (size_t)rup64((int)w.Rq) + rup64((int)w.Rb) : 0) + rup64(bat ? 0 : gnc_all) + 2 * (size_t)rup64((int)V)) * sizeof(float);
+    pl.grad_stage = !den || bat || ((size_t)rup64((int)fam.Rq) + rup64((int)fam.Rb) + rup64(gnc_all) + 2 * (size_t)rup64((int)V)) * 4 <= 150 * 1024;
+    pl.lds_grad = ((den && !bat && pl.grad_stage ? (size_t)rup64((int)fam.Rq) + rup64((int)fam.Rb) : 0) + rup64(bat ? 0 : gnc_all) + 2 * (size_t)rup64((int)V)) * sizeof(float);
     // The denominator half of the grad pass has a streaming kernel (index pairs in registers, rows
     // prefetched); it needs 16-bit row indices, rows of <= kGDRowRegs*256 floats and <= 2 chunks per thread.
-    pl.gnc = den ? (fac ? pl.FX->NC : res ? h->dev.res.NC : h->dev.NC) : 0;
-    pl.gcap = fac ? pl.FX->chunk_cap : kChunk;       // entries per chunk of the grad pass's pair lists
-    pl.gd_wide = den && (w.Rq > 4 * kGDRowRegs * kGDThreads || w.Rb > 4 * kGDRowRegs * kGDThreads);   // 512-thread grad workgroups
+    pl.gnc = den ? (fac ? fam.FX->NC : res ? h->dev.res.NC : h->dev.NC) : 0;
+    pl.gcap = fac ? fam.FX->chunk_cap : kChunk;       // entries per chunk of the grad pass's pair lists
+    pl.gd_wide = den && (fam.Rq > 4 * kGDRowRegs * kGDThreads || fam.Rb > 4 * kGDRowRegs * kGDThreads);   // 512-thread grad workgroups
     // (rows of up to 12 288 floats since round 6 -- 512 threads x 6 row registers: a den_lm with a state per seen bigram history has ~5.3 k forward rows
     // at 72 tokens, Rq = Rb = 10 752, 5 % beyond the 10 240 of five registers, and took the generic grad kernel: 10.8 ms of a 17.5 ms step)
-    pl.gd_wide6 = den && (w.Rq > 8 * kGDRowRegs * kGDThreads || w.Rb > 8 * kGDRowRegs * kGDThreads);
-    pl.fast_den = den && w.Rq <= 8 * 6 * kGDThreads && w.Rb <= 8 * 6 * kGDThreads && w.Rq % 4 == 0 && w.Rb % 4 == 0 && (!pl.gd_wide6 || (pl.gnc <= 2 * kGDThreads && pl.gcap != 8)) &&
+    pl.gd_wide6 = den && (fam.Rq > 8 * kGDRowRegs * kGDThreads || fam.Rb > 8 * kGDRowRegs * kGDThreads);
+    pl.fast_den = den && fam.Rq <= 8 * 6 * kGDThreads && fam.Rb <= 8 * 6 * kGDThreads && fam.Rq % 4 == 0 && fam.Rb % 4 == 0 && (!pl.gd_wide6 || (pl.gnc <= 2 * kGDThreads && pl.gcap != 8)) &&
                   pl.gnc <= 4 * kGDThreads && V <= kGDEpRegs * kGDThreads && !opt_on(kOpt_no_fast_grad);
     // numerator half of the grad pass: streaming kernel when the vocabulary fits its registers
     pl.fast_ctc = ctc && V <= kGCVRegs * kGCThreads && 2 * max_label_len + 1 <= kGCRegs * kGCThreads &&
@@ -859,10 +863,11 @@ static int check_loss_args(const LossArgs &a, WsLayout &w, CallPlan &pl) {
     if (V > kMaxVocab) { set_error("V > " + std::to_string(kMaxVocab) + " not supported by this build"); return CRF_ERR_UNSUPPORTED; }
     const int Sc = rup64((int)(2 * (ctc ? a.max_label_len : 0) + 1));
     if (ctc && a.max_label_len > kMaxCtcLabelLen) { set_error("label length > " + std::to_string(kMaxCtcLabelLen) + " not supported by this build"); return CRF_ERR_UNSUPPORTED; }
-    w = ws_layout(h, B, T, V, Sc);
+    const DenFamily fam = choose_den_family(h, B, V);
+    w = ws_layout(fam, h, B, T, V, Sc);
     if (a.ws_bytes < w.total) { set_error("workspace too small: need " + std::to_string(w.total)); return CRF_ERR_WORKSPACE; }
-    pl = plan_kernels(h, w, V, a.max_label_len, Sc, den, ctc);
-    if (pl.fac && T * std::max<int64_t>(V, std::max(w.Rq, w.Rb)) >= ((int64_t)1 << 32)) {   // (the factored frame loop adds 32-bit row offsets)
+    pl = plan_kernels(h, fam, V, a.max_label_len, Sc, den, ctc);
+    if (fam.fac() && T * std::max<int64_t>(V, std::max(fam.Rq, fam.Rb)) >= ((int64_t)1 << 32)) {   // (the factored frame loop adds 32-bit row offsets)
         set_error("T * max(V, row length) >= 2^32 not supported by the factored kernels"); return CRF_ERR_UNSUPPORTED;
     }
     if (std::max(pl.lds_den, ctc ? pl.lds_ctc : 0) > 160 * 1024 || pl.lds_grad > 160 * 1024) {
@@ -890,9 +895,9 @@ static void plan_schedule(CallPlan &pl, int64_t B, int64_t T, const DevFacts &f)
     pl.segmode = f.segments || opt_on(kOpt_segments);
     const int stages_env = opt(kOpt_stages, 0);
     const int pieces = stages_env > 0 ? stages_env : (pl.segmode ? 4 : 12);   // measured: 4 / 8 / 12 pieces -> call 4.06 / 3.98 / 3.93 ms (flags)
-    pl.den_wgs = pl.pair2 ? 2 * ((B + 1) / 2) : 2 * B;
+    pl.den_wgs = pl.fam.pair2() ? 2 * ((B + 1) / 2) : 2 * B;
     // (the two-utterance kernel has no segment relaunches: where stream-level waits are refused it runs unstaged)
-    pl.staged = pl.fac && pl.FX->K == 1 && pl.ctc && pl.fast_den && pl.fast_ctc && !pl.serial && !pl.no_overlap && f.have_flags && !(pl.pair2 && pl.segmode) && pl.den_wgs * 100 <= (int64_t)f.ncu * kStageFill;   // (B = 80: 4.16 -> 3.56 ms, B = 96: 4.37 -> 4.26, B = 112 at 90 %: 5.33 -> 5.57)
+    pl.staged = pl.fam.fac() && pl.fam.FX->K == 1 && pl.ctc && pl.fast_den && pl.fast_ctc && !pl.serial && !pl.no_overlap && f.have_flags && !(pl.fam.pair2() && pl.segmode) && pl.den_wgs * 100 <= (int64_t)f.ncu * kStageFill;   // (B = 80: 4.16 -> 3.56 ms, B = 96: 4.37 -> 4.26, B = 112 at 90 %: 5.33 -> 5.57)
     // Stage bounds.  Nothing can be released before the two recursions have met, so the first stage ends at half of
     // the frames or later; after that a piece of `piece` iterations releases 2 * piece / 16 frame blocks per
     // utterance.  The grad pass has half of the chip and is bandwidth-bound there (~2 TB/s against the 2.2 TB/s the
@@ -901,11 +906,11 @@ static void plan_schedule(CallPlan &pl, int64_t B, int64_t T, const DevFacts &f)
     // pieces of 32 / 48 / 64 / 96 / 128 / 192 / 256 / 384 iterations -> step 3.88 / 3.62 / 3.42 / 3.38 / 3.33 / 3.35 /
     // 3.41 / 3.53 ms; pieces that shrink towards the end (256,192,128,96,64 ...) were no better than equal ones.
     // CRF_PIECE / CRF_STAGES override (segment mode: 4 pieces, each relaunch costs ~40 us).
-    pl.nstage = 1; pl.gd_piece = 0;
-    pl.bound[1] = (int)T;
+    pl.stages = StagePlan{};   // one stage: everything behind the recursions
+    pl.stages.bound[1] = (int)T;
     // (a context whose one-launch grad pass has timed out goes back to one grad launch per stage: DevCtx::gd_fallback)
     pl.per_stage = opt_on(kOpt_gd_stage_launches) || f.gd_fallback;
-    if (pl.staged && T >= 256) pl.nstage = plan_grad_stages(T, pl.segmode, stages_env, pieces, pl.bound, &pl.gd_piece, pl.per_stage ? 1 : 0);
+    if (pl.staged && T >= 256) pl.stages = plan_grad_stages(T, pl.segmode, stages_env, pieces, pl.per_stage ? 1 : 0);
     // Did a recent call need the numerator's log-domain fallback?  (the third stream costs the call ~20 us of event traffic whether or not an
     // utterance is marked -- B = 64, T = 1 500: 3.172 -> 3.192 ms -- so it is taken when one of this context's last 16 calls ran the log-domain
     // chains: they write the call's number to a pinned host word, read without any synchronisation, once per call; `aux_stream` 1 / 0 forces
@@ -927,10 +932,10 @@ static void plan_schedule(CallPlan &pl, int64_t B, int64_t T, const DevFacts &f)
 static LossParams bind_params(const LossArgs &a, const WsLayout &w, const CallPlan &pl, const DevCtx *cx, int call_id) {
     const int64_t B = a.B, T = a.T, V = a.V;
     const HostGraph *h = pl.h;
-    const bool den = pl.den, ctc = pl.ctc, res = pl.res, fac = pl.fac;
+    const bool den = pl.den, ctc = pl.ctc, res = pl.fam.res(), fac = pl.fam.fac();
     LossParams p{};
     if (den) p.g = h->dev;
-    if (pl.FX) p.g.fac = *pl.FX;
+    if (pl.fam.FX) p.g.fac = *pl.fam.FX;
     p.logp = a.logp; p.labels = a.labels; p.lab_off = a.lab_off; p.lx = a.lx; p.ly = a.ly;
     p.B = (int)B; p.T = (int)T; p.V = (int)V; p.Sc = pl.Sc;
     p.xs_b = a.time_major ? V : T * V; p.xs_t = a.time_major ? B * V : V;
@@ -941,9 +946,9 @@ static LossParams bind_params(const LossArgs &a, const WsLayout &w, const CallPl
     p.fused = a.fused; p.in_dtype = a.in_dtype;
     p.moff = a.fused ? (float *)(base + w.off(kWs_moff)) : p.mx; p.inv_s = (float *)(base + w.off(kWs_invs));
     p.Q = (float *)(base + w.off(kWs_Q)); p.BP = (float *)(base + w.off(kWs_BP));
-    p.Rq = (int)w.Rq; p.Rb = (int)w.Rb; p.res = fac ? 2 : res ? 1 : 0; p.grad_stage = pl.grad_stage ? 1 : 0;
+    p.Rq = (int)pl.fam.Rq; p.Rb = (int)pl.fam.Rb; p.res = fac ? 2 : res ? 1 : 0; p.grad_stage = pl.grad_stage ? 1 : 0;
     if (fac) {
-        const FacDev &F = *pl.FX;
+        const FacDev &F = *pl.fam.FX;
         p.gq = F.gq; p.gb = F.gb; p.gchunk = F.chunk_off; p.glab = F.lab_chunk_off; p.gNC = F.NC;
     } else if (den) {
         p.gq = res ? h->dev.res.gq : h->dev.perm; p.gb = res ? h->dev.res.gb : h->dev.perm;
@@ -954,34 +959,34 @@ static LossParams bind_params(const LossArgs &a, const WsLayout &w, const CallPl
     p.EQ = (int *)(base + w.off(kWs_EQ)); p.EB = (int *)(base + w.off(kWs_EB));
     p.CA = (double *)(base + w.off(kWs_CA)); p.CB = (double *)(base + w.off(kWs_CB));
     p.ECA = (int *)(base + w.off(kWs_ECA)); p.ECB = (int *)(base + w.off(kWs_ECB));
-    p.ctc_zc = (double *)(base + w.off(kWs_pb));
-    p.cb_mxs = p.ctc_zc + B;
-    float *pb = (float *)(p.cb_mxs + B);
-    p.cb_part = pb + 8 * B; p.cb_F = (int *)(pb + 8 * B + (int64_t)kResMaxK * B);
-    p.redo = (int *)(pb + 16 * B);   // [2][B]
-    p.redo_ctc = (int *)(pb + 18 * B);   // [B]
-    p.ctc_logdom = (int *)(pb + 19 * B); // [B]
+    const auto pb = [&](PbField k) { return (void *)(base + w.off(kWs_pb) + fields_off(kPbFields, k, B)); };   // (CRF_PB_FIELDS)
+    p.ctc_zc = (double *)pb(kPb_ctc_zc); p.cb_mxs = (double *)pb(kPb_cb_mxs);
+    p.cb_part = (float *)pb(kPb_cb_part); p.cb_F = (int *)pb(kPb_cb_F);
+    p.redo = (int *)pb(kPb_redo); p.redo_ctc = (int *)pb(kPb_redo_ctc); p.ctc_logdom = (int *)pb(kPb_ctc_logdom);
     p.ctc_bad = (int *)(base + w.off(kWs_cbad));
     p.force_redo = (den && pl.robust_env == 1) ? 1 : 0;
     p.force_redo_ctc = (ctc && (pl.robust_env == 1 || opt_on(kOpt_robust_ctc))) ? 1 : 0;
     p.ctc_tilt = std::min(400, std::max(0, opt(kOpt_ctc_tilt, 100)));
     p.xch = (unsigned long long *)(base + w.off(kWs_xch));
-    p.err = (int *)(base + w.off(kWs_xch) + w.xch_bytes);
     p.Row0 = (float *)(base + w.off(kWs_row0));
     p.dump = (float *)(base + w.off(kWs_dump)); p.dump_stride = (int)w.dump_stride;
     p.gvec = (float *)(base + w.off(kWs_gvec));
     p.gvec_stride = w.gvec_stride;
-    p.den_zs = pb; p.den_ez = (int *)(pb + B); p.ctc_ez = (int *)(pb + 2 * B);
-    p.cost_alpha = pb + 3 * B; p.cost_beta = pb + 4 * B; p.cost_ctc = pb + 5 * B; p.invalid = (int *)(pb + 6 * B);
+    p.den_zs = (float *)pb(kPb_den_zs); p.den_ez = (int *)pb(kPb_den_ez); p.ctc_ez = (int *)pb(kPb_ctc_ez);
+    p.cost_alpha = (float *)pb(kPb_cost_alpha); p.cost_beta = (float *)pb(kPb_cost_beta); p.cost_ctc = (float *)pb(kPb_cost_ctc); p.invalid = (int *)pb(kPb_invalid);
     p.grad = a.grad; p.loss = a.loss; p.out_den = a.costs_den; p.out_beta = a.costs_beta; p.out_ctc = a.costs_ctc;
     p.out_invalid = a.invalid;
-    // error word, start counter and stage counters live in fine-grained memory (get_ctx); the prep kernel clears them
-    p.clear = nullptr; p.nclear = 0;
+    // error word, start counter and stage counters live in fine-grained memory (get_ctx), where the prep kernel clears them; a context
+    // without it has the words behind the granules of section xch (CRF_XCH_FIELDS), cleared with the section
+    int *const ws_flags = (int *)(base + w.off(kWs_xch) + w.xch_bytes + fields_off(kXchFields, kXch_flags, B));
+    p.err = (cx->flags ? cx->flags : ws_flags) + kFlagErr;
+    p.clear = cx->flags; p.nclear = cx->flags ? kFlagWords : 0;
     p.call_id = call_id; p.ctc_seen = cx->seen;
-    if (cx->flags) { p.err = cx->flags; p.clear = cx->flags; p.nclear = 64; }
     p.gd_timeout_host = cx->hostw ? cx->hostw + 4 : nullptr;
-    p.gd_nb = pl.nstage + 1;
-    for (int k = 0; k <= pl.nstage && k < 16; ++k) p.gd_bound[k] = pl.bound[k];
+    p.gd_nb = pl.stages.nstage + 1;
+    static_assert(sizeof(LossParams::gd_bound) == sizeof(StagePlan::bound) && sizeof(FacParams::bound) == sizeof(StagePlan::bound) &&
+                  sizeof(LossParams::gd_poff) == sizeof(GradGrid::poff) && sizeof(LossParams::gd_fpb) == sizeof(GradGrid::fpb), "the parameter blocks hold a whole plan");
+    for (int k = 0; k <= pl.stages.nstage; ++k) p.gd_bound[k] = pl.stages.bound[k];   // (the words behind the last bound stay zero)
     p.zero_grad = pl.par3 ? 1 : 0;
     return p;
 }
@@ -1017,7 +1022,7 @@ struct LossCall {
     bool forked = false, side_used = false;
     bool ctc_pass1 = false;   // the numerator's log-domain fallback has run in this call (staged schedule)
 
-    int *started() const { return p.err + 1; }   // workgroups of the den kernels that hold a CU (cleared with the error word)
+    int *started() const { return p.err + kFlagStarted; }   // workgroups of the den kernels that hold a CU (cleared with the error word)
     // factored recursions launched in segments park their state vectors here
     float *fstate() const { return (float *)((char *)a.ws + w.off(kWs_state)); }
     float *bstate() const { return fstate() + a.B * w.state_stride; }
@@ -1047,16 +1052,18 @@ struct LossCall {
     int launch_grad_den(hipStream_t st, int stage, bool persist = false) {
         const int64_t B = a.B, T = a.T, V = a.V;
         p.gd_stage = stage;
-        const size_t l = ((size_t)rup64((int)w.Rq + 1) + rup64((int)w.Rb + 1) + 4 * rup64((int)V) + kGDFrames + rup64(pl.gnc)) * sizeof(float);
+        const size_t l = ((size_t)rup64((int)pl.fam.Rq + 1) + rup64((int)pl.fam.Rb + 1) + 4 * rup64((int)V) + kGDFrames + rup64(pl.gnc)) * sizeof(float);
         dim3 gg((unsigned)((T + kGDFrames - 1) / kGDFrames), (unsigned)B);
         p.gd_nf = 0;
         p.gd_persist = 0;
         if (persist) {   // the stages `stage` .. nstage in one launch (see the kernel): 2 * nf candidates per utterance and stage, stage-major
             p.gd_persist = 1;
-            p.gd_cnt = cx->flags + 16;
+            p.gd_cnt = cx->flags + kFlagStage;
             p.gd_target = (int)(2 * B);
-            const int64_t tot = plan_grad_grid(p.gd_bound, p.gd_nb - 1, stage, B, pl.gd_piece, p.gd_poff, p.gd_fpb);
-            gg = dim3((unsigned)tot, 1);
+            const GradGrid grid = plan_grad_grid(pl.stages, stage, B);
+            std::copy(grid.poff.begin(), grid.poff.end(), p.gd_poff);
+            std::copy(grid.fpb.begin(), grid.fpb.end(), p.gd_fpb);
+            gg = dim3((unsigned)grid.workgroups, 1);
         } else if (stage > 1) {   // (stage 1 is the middle of every utterance: all blocks are candidates)
             p.gd_nf = (p.gd_bound[stage] - p.gd_bound[stage - 1] + kGDFrames - 1) / kGDFrames + 3;
             if (2 * p.gd_nf < (int)gg.x) gg.x = (unsigned)(2 * p.gd_nf); else p.gd_nf = 0;
@@ -1070,7 +1077,7 @@ struct LossCall {
             return launch<crf_grad_den_kernel<2, 2, 2 * kGDThreads>>(name, gg, b2, l, st, p);
         if (pl.gd_wide6)                 // rows of 10 241 .. 12 288 floats: 512 threads with six row registers each
             return launch<crf_grad_den_kernel<1, 2, 2 * kGDThreads, kChunk, 6, 1>>(name, gg, b2, l, st, p);
-        if (pl.gd_wide && w.Rq <= 32 * kGDThreads && w.Rb <= 32 * kGDThreads)
+        if (pl.gd_wide && pl.fam.Rq <= 32 * kGDThreads && pl.fam.Rb <= 32 * kGDThreads)
             // rows of 5121 .. 8192 floats: 512 threads with four row registers each, held to 128 VGPRs so that a CU takes TWO workgroups (the
             // five-register form below compiles to 148 VGPRs: one workgroup, eight waves, per CU -- the estimated S = 6836 graph ran on that)
             return launch<crf_grad_den_kernel<1, 2, 2 * kGDThreads, kChunk, 4, 4>>(name, gg, b2, l, st, p);
@@ -1112,13 +1119,11 @@ struct LossCall {
     // BESIDE the denominator recursions (V = 500: 1.2 ms that followed the call's last grad launch); pass 2 at the end of every call
     // takes what is marked and was not redone in pass 1.
     int launch_robust_ctc_chains(hipStream_t st, int pass) {
-        const int64_t ni = (2 * a.max_label_len + 1 + kCtcThreads - 1) / kCtcThreads;
         const dim3 grid((unsigned)(2 * a.B)), block(kCtcThreads);
         p.ctc_pass = pass;
-        if (ni <= 1) return launch<crf_robust_ctc_kernel<1>>("crf_robust_ctc_kernel", grid, block, pl.lds_ctc, st, p);
-        if (ni <= 2) return launch<crf_robust_ctc_kernel<2>>("crf_robust_ctc_kernel", grid, block, pl.lds_ctc, st, p);
-        if (ni <= 4) return launch<crf_robust_ctc_kernel<4>>("crf_robust_ctc_kernel", grid, block, pl.lds_ctc, st, p);
-        return launch<crf_robust_ctc_kernel<kCtcRegs>>("crf_robust_ctc_kernel", grid, block, pl.lds_ctc, st, p);
+        return with_nr(2 * a.max_label_len + 1, kCtcThreads, [&](auto nr, int) {
+            return launch<crf_robust_ctc_kernel<decltype(nr)::value>>("crf_robust_ctc_kernel", grid, block, pl.lds_ctc, st, p);
+        });
     }
     int launch_robust_ctc_fix(hipStream_t st, int pass) {
         p.ctc_pass = pass;
@@ -1133,26 +1138,26 @@ struct LossCall {
     // it runs while the side stream finishes the grad pass -- and in front of the fallback kernels, which take what it flags)
     int launch_den_check(hipStream_t st) {
         if (!pl.den || pl.robust_env == 0) return CRF_OK;
-        return launch<crf_den_check_kernel>("crf_den_check_kernel", dim3((unsigned)((a.B + 255) / 256)), dim3(256), 0, st, p, (pl.res || pl.fac) ? 1 : 0);
+        return launch<crf_den_check_kernel>("crf_den_check_kernel", dim3((unsigned)((a.B + 255) / 256)), dim3(256), 0, st, p, (pl.fam.res() || pl.fam.fac()) ? 1 : 0);
     }
     // the denominator recursions of the whole batch on `st` (every layout; both directions per launch)
     int launch_den(hipStream_t st, bool with_check = true) {
         const int B = (int)a.B;
         const HostGraph *h = pl.h;
         int rc = CRF_OK;
-        if (!pl.fac && !pl.res) {   // streaming kernels (launch_den_pair marks the profile slots itself)
-            rc = pl.gv ? launch_den_pair<true>(p, pl.lds_den, st) : launch_den_pair<false>(p, pl.lds_den, st);
+        if (!pl.fam.fac() && !pl.fam.res()) {   // streaming kernels (launch_den_pair marks the profile slots itself)
+            rc = pl.fam.gv ? launch_den_pair<true>(p, pl.lds_den, st) : launch_den_pair<false>(p, pl.lds_den, st);
             return (rc || !with_check) ? rc : launch_den_check(st);
         }
         prof_mark(1, false, st); prof_mark(2, false, st);
         {
-            const CoresGuard cores((pl.fac && pl.FX->K > 1) || (pl.res && !pl.fac && h->dev.res.K > 1), cx->dev, st);
-            if (pl.fac && pl.FX->K > 1) {
+            const CoresGuard cores((pl.fam.fac() && pl.fam.FX->K > 1) || (pl.fam.res() && !pl.fam.fac() && h->dev.res.K > 1), cx->dev, st);
+            if (pl.fam.fac() && pl.fam.FX->K > 1) {
                 const int grp = std::max(1, pl.ncu / 4);
                 for (int b0 = 0; b0 < B && !rc; b0 += grp) rc = launch_fac2_pair(p, pl.lds_den, st, b0, std::min(grp, B - b0));
-            } else if (pl.fac && pl.pair2) {
+            } else if (pl.fam.fac() && pl.fam.pair2()) {
                 rc = launch_fac_pair2<false>(p, pl.lds_den, st, started());
-            } else if (pl.fac) {
+            } else if (pl.fam.fac()) {
                 rc = launch_fac_pair<false>(p, pl.lds_den, st, started(), 0, (int)a.T, fstate(), bstate());
             } else {
                 // K CUs per utterance and direction exchange the state vector through L2 every frame.  With K > 1 every
@@ -1177,7 +1182,7 @@ struct LossCall {
                                   : launch<crf_prep_kernel<64>>("crf_prep_kernel", dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, stream, p);
         prof_mark(0, true, stream);
         if (rc) return rc;
-        if (pl.res && (w.xch_bytes > 0 || !pl.have_flags)) {  // exchange granules (tags) and the error word start at zero in every call
+        if (pl.fam.res() && (w.xch_bytes > 0 || !pl.have_flags)) {  // exchange granules (tags) and the error word start at zero in every call
             if (hipMemsetAsync(p.xch, 0, (size_t)w.sec[kWs_xch].bytes, stream) != hipSuccess) { set_error("hipMemsetAsync(xch)"); return CRF_ERR_HIP; }
         }
         return CRF_OK;
@@ -1201,27 +1206,27 @@ int LossCall::run_batch() {
     hipError_t e;
     BatchParams bp{};
     bp.g = h->dev.bat; bp.start_lin = h->dev.start_lin; bp.end_lin = h->dev.end_lin;
-    bp.S = h->dev.S; bp.P = h->dev.P; bp.B = (int)B; bp.Bp = (int)w.Bp; bp.T = (int)T; bp.V = (int)V; bp.max_label = h->dev.max_label;
+    bp.S = h->dev.S; bp.P = h->dev.P; bp.B = (int)B; bp.Bp = (int)pl.fam.Bp; bp.T = (int)T; bp.V = (int)V; bp.max_label = h->dev.max_label;
     bp.lx = a.lx; bp.ep = p.ep; bp.moff = p.moff;
     bp.ept = (float *)(base + w.off(kWs_ept)); bp.Af = (float *)(base + w.off(kWs_Af)); bp.Zb = (float *)(base + w.off(kWs_Zb));
     bp.Q = p.Q; bp.BP = p.BP;
-    unsigned *bsm = (unsigned *)(base + w.off(kWs_bsm));
-    bp.mxf = bsm; bp.mxb = bsm + 3 * w.Bp; bp.Ef = (int *)(bsm + 6 * w.Bp); bp.Fb = (int *)(bsm + 7 * w.Bp);
-    bp.zs = (float *)(bsm + 8 * w.Bp); bp.zb = (float *)(bsm + 9 * w.Bp);
-    bp.bar = bsm + 12 * w.Bp; bp.err = (int *)(bsm + 12 * w.Bp + 512);
+    const auto bsm = [&](BsmField k) { return (void *)(base + w.off(kWs_bsm) + fields_off(kBsmFields, k, pl.fam.Bp)); };   // (CRF_BSM_FIELDS)
+    bp.mxf = (unsigned *)bsm(kBsm_mxf); bp.mxb = (unsigned *)bsm(kBsm_mxb); bp.Ef = (int *)bsm(kBsm_Ef); bp.Fb = (int *)bsm(kBsm_Fb);
+    bp.zs = (float *)bsm(kBsm_zs); bp.zb = (float *)bsm(kBsm_zb);
+    bp.bar = (unsigned *)bsm(kBsm_bar); bp.err = (int *)(bp.bar + kBatBarWords);
     bp.den_zs = p.den_zs; bp.cost_alpha = p.cost_alpha; bp.cost_beta = p.cost_beta; bp.den_ez = p.den_ez; bp.redo = p.redo;
     bp.grad = a.grad; bp.c_den = a.c_den;
-    const unsigned ngrp = (unsigned)(w.Bp / w.UL);
+    const unsigned ngrp = (unsigned)(pl.fam.Bp / pl.fam.UL);
     bp.ngrp = (int)ngrp;
     // one task per wave, ONE round of workgroups (a second round with a fraction of the device doubled the launch):
     // the tasks wanted per direction follow from the occupancy the runtime reports, shared by the combos
     const int64_t ncombo = 2 * (int64_t)ngrp;
-    const bool bfac = stream_fac(a.g->h, w.UL);                  // factored streams (T o LM graphs, groups of >= 32 utterances)
+    const bool bfac = stream_fac(a.g->h, pl.fam.UL);                  // factored streams (T o LM graphs, groups of >= 32 utterances)
     // ALL frames in one persistent launch (round 6) when its grid is co-resident by the runtime's own count -- switch bat_persist: 0 =
     // one launch per frame (rounds 2 - 5; also the fallback), 1 = persistent (default)
     const bool want_persist = opt(kOpt_bat_persist, 1) != 0;
     int wg_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg_cu, bat_kernel(want_persist, w.UL, bfac), kBatThreads, 0) != hipSuccess || wg_cu < 1) { (void)hipGetLastError(); wg_cu = want_persist ? 0 : 2; }
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg_cu, bat_kernel(want_persist, pl.fam.UL, bfac), kBatThreads, 0) != hipSuccess || wg_cu < 1) { (void)hipGetLastError(); wg_cu = want_persist ? 0 : 2; }
     bool persist = want_persist && wg_cu >= 1;
     if (want_persist && !persist) wg_cu = 2;
     // ... times 70 %: a launch is bound by the L2s and the fabric, not by the CUs, and fewer, longer tasks pay the task set-up
@@ -1233,7 +1238,7 @@ int LossCall::run_batch() {
     const int64_t slots = (int64_t)pl.ncu * wg_cu;            // workgroups the device holds at once
     const int want = (int)std::max<int64_t>(16, (int64_t)pl.ncu * wg_cu * kBatWaves * 15 / 16 * fill / 100 / ncombo);
     const StreamDev *sdv = nullptr;
-    if ((rc = ensure_stream_tables(a.g->h, w.UL, want, &sdv))) return rc;
+    if ((rc = ensure_stream_tables(a.g->h, pl.fam.UL, want, &sdv))) return rc;
     if ((sdv->fac != 0) != bfac) { set_error("arc streams: factored / plain mismatch"); return CRF_ERR_ARG; }
     bp.SX = h->dev.S + sdv->NU; bp.x_start = sdv->x_start;
     bp.st = *sdv;
@@ -1253,20 +1258,20 @@ int LossCall::run_batch() {
         if ((rc = fork_side())) return rc;
         if ((rc = launch_ctc_pair(p, pl.lds_ctc, side, a.max_label_len))) return rc;
     }
-    if (opt_on(kOpt_verbose)) fprintf(stderr, "[ctc_crf_hip] utterance-minor: UL %d, %d combos, tasks %d / %d, rest rows %d / %d, grid %u of %lld slots (%d per CU), %s\n", (int)w.UL, (int)ncombo,
+    if (opt_on(kOpt_verbose)) fprintf(stderr, "[ctc_crf_hip] utterance-minor: UL %d, %d combos, tasks %d / %d, rest rows %d / %d, grid %u of %lld slots (%d per CU), %s\n", (int)pl.fam.UL, (int)ncombo,
                                       sdv->f.ntasks, sdv->b.ntasks, sdv->f.nrest, sdv->b.nrest, G, (long long)slots, wg_cu, persist ? "one persistent launch" : "one launch per frame");
     prof_mark(1, false, stream); prof_mark(2, false, stream);
 #define CRF_BAT_UL(KERNEL, GRID, ...)                                                                          \
-    (w.UL == 64   ? launch<KERNEL<64>>(#KERNEL, GRID, dim3(kBatThreads), 0, stream, __VA_ARGS__)                \
-     : w.UL == 32 ? launch<KERNEL<32>>(#KERNEL, GRID, dim3(kBatThreads), 0, stream, __VA_ARGS__)                \
-     : w.UL == 16 ? launch<KERNEL<16>>(#KERNEL, GRID, dim3(kBatThreads), 0, stream, __VA_ARGS__)                \
+    (pl.fam.UL == 64   ? launch<KERNEL<64>>(#KERNEL, GRID, dim3(kBatThreads), 0, stream, __VA_ARGS__)                \
+     : pl.fam.UL == 32 ? launch<KERNEL<32>>(#KERNEL, GRID, dim3(kBatThreads), 0, stream, __VA_ARGS__)                \
+     : pl.fam.UL == 16 ? launch<KERNEL<16>>(#KERNEL, GRID, dim3(kBatThreads), 0, stream, __VA_ARGS__)                \
                   : launch<KERNEL<8>>(#KERNEL, GRID, dim3(kBatThreads), 0, stream, __VA_ARGS__))
     if ((rc = CRF_BAT_UL(crf_batch_transpose_kernel, dim3((unsigned)((V + 63) / 64), (unsigned)T, ngrp), bp))) return rc;
-    if ((rc = launch<crf_batch_init_kernel>("crf_batch_init_kernel", dim3((unsigned)(((int64_t)bp.SX * w.Bp + kBatThreads - 1) / kBatThreads)), dim3(kBatThreads), 0, stream, bp))) return rc;
-    g_den_kernel = bat_kernel_name(persist, w.UL, bfac);
+    if ((rc = launch<crf_batch_init_kernel>("crf_batch_init_kernel", dim3((unsigned)(((int64_t)bp.SX * pl.fam.Bp + kBatThreads - 1) / kBatThreads)), dim3(kBatThreads), 0, stream, bp))) return rc;
+    g_den_kernel = bat_kernel_name(persist, pl.fam.UL, bfac);
     {
         void *args[] = {(void *)&bp};
-        const void *fn = bat_kernel(persist, w.UL, bfac);
+        const void *fn = bat_kernel(persist, pl.fam.UL, bfac);
         if (persist) {
             // (co-resident grids of two callers must not interleave: each could become partially resident and wait for the rest)
             CoresGuard guard(true, cx->dev, stream);
@@ -1300,19 +1305,19 @@ int LossCall::run_batch() {
 // grad half (writes -c_ctc * gamma_ctc), then the den half of the grad pass stage by stage (adds gamma_den).
 int LossCall::run_staged() {
     const int64_t B = a.B;
-    const int nstage = pl.nstage;
-    int *const stage_cnt = cx->flags + 16;
+    const int nstage = pl.stages.nstage;
+    int *const stage_cnt = cx->flags + kFlagStage;
     int rc;
     hipError_t e;
     if ((rc = fork_side())) return rc;
     prof_mark(1, false, stream); prof_mark(2, false, stream);
-    if (pl.pair2) {
-        if ((rc = launch_fac_pair2<true>(p, pl.lds_den, stream, started(), nstage + 1, pl.bound, stage_cnt))) return rc;
+    if (pl.fam.pair2()) {
+        if ((rc = launch_fac_pair2<true>(p, pl.lds_den, stream, started(), nstage + 1, pl.stages.bound.data(), stage_cnt))) return rc;
     } else if (!pl.segmode) {
-        if ((rc = launch_fac_pair<true>(p, pl.lds_den, stream, started(), 0, (int)a.T, fstate(), bstate(), nstage + 1, pl.bound, stage_cnt))) return rc;
+        if ((rc = launch_fac_pair<true>(p, pl.lds_den, stream, started(), 0, (int)a.T, fstate(), bstate(), nstage + 1, pl.stages.bound.data(), stage_cnt))) return rc;
     } else {
         for (int k = 0; k < nstage; ++k) {
-            if ((rc = launch_fac_pair<false>(p, pl.lds_den, stream, started(), pl.bound[k], pl.bound[k + 1], fstate(), bstate()))) return rc;
+            if ((rc = launch_fac_pair<false>(p, pl.lds_den, stream, started(), pl.stages.bound[k], pl.stages.bound[k + 1], fstate(), bstate()))) return rc;
             if ((e = hipEventRecord(cx->ev[k], stream)) != hipSuccess) { set_error(std::string("hipEventRecord(segment): ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
         }
     }
@@ -1375,8 +1380,8 @@ int LossCall::run_staged_par3() {
     hipError_t e;
     if ((e = hipStreamWaitEvent(cx->aux, cx->fork, 0)) != hipSuccess) { set_error(std::string("hipStreamWaitEvent(aux fork): ") + hipGetErrorString(e)); return CRF_ERR_HIP; }
     p.grad_den_acc = 2;
-    for (int k = 0; k < pl.nstage; ++k) {
-        if ((e = hipStreamWaitValue32(cx->aux, cx->flags + 16 + k + 1, (uint32_t)(2 * a.B), hipStreamWaitValueGte, 0xffffffffu)) != hipSuccess) {
+    for (int k = 0; k < pl.stages.nstage; ++k) {
+        if ((e = hipStreamWaitValue32(cx->aux, cx->flags + kFlagStage + k + 1, (uint32_t)(2 * a.B), hipStreamWaitValueGte, 0xffffffffu)) != hipSuccess) {
             // not available here: from the next call on, segments (and no third stream).  This call: wait for the recursions to END
             (void)hipGetLastError();
             g_use_segments = true;
@@ -1404,12 +1409,12 @@ int LossCall::run_two_streams() {
     const int ctc_after_env = opt(kOpt_ctc_after, -1);
     // (factored, one CU per recursion: the den grid leaves ncu - den_wgs CUs free -- B = 96: 64 of them -- and the numerator
     // chains, four workgroups to a CU, run there beside it, behind the start gate so that the den workgroups get their CUs first)
-    const bool fac1 = pl.fac && pl.FX->K == 1;
+    const bool fac1 = pl.fam.fac() && pl.fam.FX->K == 1;
     // (round 5: not only when the den grid owns EVERY CU.  Between the staged schedule's limit -- three quarters of the CUs -- and a full device the
     // chains ran beside the recursions on the few CUs they leave, 2 B chain workgroups on 256 - 2 B CUs, and took longer than the recursions: B = 100 /
     // 104 / 112 / 120 4.40 / 4.54 / 4.82 / 5.16 ms per step; behind them, beside the den half of the grad pass: 4.28 / 4.38 / 4.48 / 4.61,
     // profiles/round5_ab_grad_one_launch.txt)
-    const bool after = ctc_after_env >= 0 ? ctc_after_env != 0 : fac1 ? pl.den_wgs * 100 > (int64_t)pl.ncu * kStageFill : (pl.res && h->dev.res.K > 1);
+    const bool after = ctc_after_env >= 0 ? ctc_after_env != 0 : fac1 ? pl.den_wgs * 100 > (int64_t)pl.ncu * kStageFill : (pl.fam.res() && h->dev.res.K > 1);
     if (after) {
         // (the consistency check BEHIND the fork: the numerator chains -- a latency chain that wants its workgroups resident at once -- are
         // released by the end of the recursions and get the CUs first; with the check in front of the fork the grad launch below, which
@@ -1459,7 +1464,7 @@ int LossCall::run_fallbacks_and_finalize() {
     if (pl.den && pl.robust_env != 0) {
         // Fallback for utterances whose scaled-fp32 recursion lost all its mass: redone in a per-frame log-shifted form
         // (crf_robust_den_kernel).  Workgroups of unflagged utterances leave at once -- two near-empty launches per call.
-        const bool rgv = w.gv_robust;
+        const bool rgv = pl.fam.gv_robust;
         const size_t lr = robust_lds_bytes(h, (int)a.V, rgv);
         const dim3 grid((unsigned)(2 * a.B)), block(kChainThreads);
         if ((rc = rgv ? launch<crf_robust_den_kernel<true>>("crf_robust_den_kernel", grid, block, lr, stream, p)
@@ -1519,29 +1524,11 @@ static int loss_impl(const crf_graph *g, const float *logp, int fused, int in_dt
     LossCall c{a, w, pl, cx, stream, pl.serial ? stream : cx->side, bind_params(a, w, pl, cx, f.call_id)};
     g_last_err_word = c.p.err;
     if ((rc = c.start())) return rc;
-    if (pl.bat) rc = c.run_batch();
+    if (pl.fam.bat()) rc = c.run_batch();
     else if (pl.staged) rc = c.run_staged();
     else if (pl.den && pl.ctc && !pl.serial) rc = c.run_two_streams();
     else rc = c.run_one_stream();
     return rc ? rc : c.run_fallbacks_and_finalize();
-}
-
-int crf_debug_stage_plan(int64_t T, int64_t B, int32_t *out, int n_out) {
-    if (!out || n_out < 4 + 4 * (kMaxStages + 2) || T < 1 || B < 1) { set_error("crf_debug_stage_plan: out needs 4 + 4 * 18 ints"); return CRF_ERR_ARG; }
-    int bound[kMaxStages + 2] = {0}, poff[kMaxStages + 2] = {0}, fpb[kMaxStages + 2] = {0}, gd_piece = 0;
-    const bool segmode = opt_on(kOpt_segments);
-    const int stages_env = opt(kOpt_stages, 0);
-    const int nstage = plan_grad_stages(T, segmode, stages_env, stages_env > 0 ? stages_env : (segmode ? 4 : 12), bound, &gd_piece);
-    const bool one = !segmode && nstage >= 3 && !opt_on(kOpt_gd_stage_launches);
-    const int64_t tot = one ? plan_grad_grid(bound, nstage, 2, B, gd_piece, poff, fpb) : 0;
-    out[0] = nstage; out[1] = gd_piece; out[2] = one ? 1 : 0; out[3] = (int32_t)tot;
-    for (int k = 0; k < kMaxStages + 2; ++k) {
-        out[4 + k] = bound[k];
-        out[4 + (kMaxStages + 2) + k] = poff[k];
-        out[4 + 2 * (kMaxStages + 2) + k] = fpb[k];
-        out[4 + 3 * (kMaxStages + 2) + k] = k >= 1 && k <= nstage ? (bound[k] - bound[k - 1] + kGDFrames - 1) / kGDFrames + 3 : 0;   // candidates per run (nfc)
-    }
-    return CRF_OK;
 }
 
 int crf_stage_i32(int32_t *dst_dev, const int32_t *src_pinned_host, int64_t n, void *stream) {

@@ -22,16 +22,6 @@ template <typename F>
 static int with_dtype(int dtype, F &&f) {
     return dtype == 0 ? f(float{}) : dtype == 1 ? f(AlnBf16{}) : f(AlnF16{});
 }
-// f(NR, k): states per thread (per = kCtcThreads) or lane (per = 64) as a compile-time constant, the smallest of 1, 2, 4, 8 that holds
-// `states` of them, and its index k in that list
-template <typename F>
-static int with_nr(int64_t states, int per, F &&f) {
-    const int64_t ni = (states + per - 1) / per;
-    if (ni <= 1) return f(std::integral_constant<int, 1>{}, 0);
-    if (ni <= 2) return f(std::integral_constant<int, 2>{}, 1);
-    if (ni <= 4) return f(std::integral_constant<int, 4>{}, 2);
-    return f(std::integral_constant<int, kCtcRegs>{}, 3);
-}
 // the activations of a params block: row (b, t) at b * xs_b + t * xs_t elements, read in place in either layout
 template <typename P>
 static void set_act(P &p, const void *act, const int32_t *lx, int64_t B, int64_t T, int64_t V, int blank, int time_major) {

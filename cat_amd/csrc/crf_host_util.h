@@ -1,14 +1,17 @@
 // cat_amd/csrc/crf_host_util.h -- what the host units share (crf_host.hip: the loss call; crf_host_ctc.hip: forced alignment, hypothesis
-// scores, sampling): the records and the rule of a workspace section, and the one kernel launch with its dynamic-LDS mark.
+// scores, sampling): the records and the rule of a workspace section, the fields inside one, the one kernel launch with its dynamic-LDS
+// mark, and the choice of the numerator kernels' states per thread.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
 #include <string>
+#include <type_traits>
 
 #include "../../include/ctc_crf_hip.h"
 #include "crf_internal.h"
+#include "crf_device.h"
 
 namespace crf {
 
@@ -27,6 +30,27 @@ static std::string join_names(const char *const *names, int n) {
     std::string s;
     for (int k = 0; k < n; ++k) { if (k) s += ','; s += names[k]; }
     return s;
+}
+
+// The arrays INSIDE a section, packed in list order: field k holds a * n + c elements of `elem` bytes (n: B, or Bp for the utterance-minor
+// kernels' section) and starts where field k - 1 ends.  Entries named spare* belong to no kernel.
+struct WsField { const char *name; int elem, a, c; };
+// bytes in front of field k of the list (k = the number of fields: the bytes of the whole list)
+static int64_t fields_off(const WsField *f, int k, int64_t n) {
+    int64_t o = 0;
+    for (int i = 0; i < k; ++i) o += f[i].elem * (f[i].a * n + f[i].c);
+    return o;
+}
+
+// f(NR, k): states per thread (per = kCtcThreads) or lane (per = 64) as a compile-time constant, the smallest of 1, 2, 4, 8 that holds
+// `states` of them, and its index k in that list
+template <typename F>
+static int with_nr(int64_t states, int per, F &&f) {
+    const int64_t ni = (states + per - 1) / per;
+    if (ni <= 1) return f(std::integral_constant<int, 1>{}, 0);
+    if (ni <= 2) return f(std::integral_constant<int, 2>{}, 1);
+    if (ni <= 4) return f(std::integral_constant<int, 4>{}, 2);
+    return f(std::integral_constant<int, kCtcRegs>{}, 3);
 }
 
 constexpr int kMaxDev = 64;

@@ -104,7 +104,7 @@ _lib.crf_build_switches.restype = ctypes.c_char_p
 
 EXPORTED_SYMBOLS = (
     "crf_graph_create", "crf_graph_create_from_arcs", "crf_graph_destroy", "crf_graph_dims", "crf_graph_stats",
-    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_ctc_score", "crf_ctc_score_logits_workspace_bytes", "crf_ctc_score_logits", "crf_last_score_kernel", "crf_ctc_score_grad_workspace_bytes", "crf_ctc_score_grad", "crf_last_score_grad_kernel", "crf_ctc_sample_workspace_bytes", "crf_ctc_sample", "crf_last_sample_kernel", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
+    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_ws_fields", "crf_debug_ws_field_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_ctc_score", "crf_ctc_score_logits_workspace_bytes", "crf_ctc_score_logits", "crf_last_score_kernel", "crf_ctc_score_grad_workspace_bytes", "crf_ctc_score_grad", "crf_last_score_grad_kernel", "crf_ctc_sample_workspace_bytes", "crf_ctc_sample", "crf_last_sample_kernel", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
     "crf_debug_set", "crf_debug_unset", "crf_debug_list", "crf_last_den_kernel", "crf_last_call_streams", "crf_last_side_stream", "crf_last_fallback_counts", "crf_build_switches", "crf_last_error", "crf_version",
 )
 
@@ -332,6 +332,23 @@ def debug_ws_sections(handle: Optional[int], B: int, T: int, V: int, max_label_l
     n = _lib.crf_debug_ws_sections(_vp(handle or 0), B, T, V, max_label_len, out, len(out))
     assert n == len(names), (n, names)
     return [(names[k], int(out[2 * k]), int(out[2 * k + 1])) for k in range(n)]
+
+
+def debug_ws_fields(section: str, n: int):
+    """[(name, offset, bytes, element bytes)] of the arrays inside section "pb", "xch" (from the end of its granules) or "bsm" for a batch
+    of n (bsm: Bp) utterances (include/ctc_crf_hip.h: crf_debug_ws_fields; no GPU)."""
+    _lib.crf_debug_ws_fields.argtypes = [ctypes.c_char_p, _i64, ctypes.POINTER(_i64), ctypes.c_int]
+    _lib.crf_debug_ws_fields.restype = ctypes.c_int
+    _lib.crf_debug_ws_field_names.argtypes = [ctypes.c_char_p]
+    _lib.crf_debug_ws_field_names.restype = ctypes.c_char_p
+    names = _lib.crf_debug_ws_field_names(section.encode())
+    if names is None:
+        _check(1)
+    names = names.decode().split(",")
+    out = (_i64 * (3 * len(names)))()
+    k = _lib.crf_debug_ws_fields(section.encode(), n, out, len(out))
+    assert k == len(names), (k, names)
+    return [(names[i], int(out[3 * i]), int(out[3 * i + 1]), int(out[3 * i + 2])) for i in range(k)]
 
 
 def debug_align_ws_sections(logits: bool, B: int, T: int, V: int, max_label_len: int):

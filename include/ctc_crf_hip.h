@@ -134,6 +134,14 @@ int crf_debug_ws_sections(const crf_graph *g, int64_t B, int64_t T, int64_t V, i
 const char *crf_debug_ws_section_names(void);
 int crf_debug_align_ws_sections(int logits, int64_t B, int64_t T, int64_t V, int64_t max_label_len, int64_t *out, int n_out);
 const char *crf_debug_align_ws_section_names(void);
+/* The arrays INSIDE the sections "pb", "xch" and "bsm" of the loss call's workspace, from the very lists the call takes its pointers
+ * from: (offset, bytes, element bytes) triples for as many fields as fit n_out int64, packed in list order; returns the number of
+ * fields, crf_debug_ws_field_names(section) gives their names.  n is the batch size B ("bsm": B rounded up to the utterance group,
+ * Bp).  Offsets count from the section's start -- for "xch" from the end of the exchange granules, i.e. the fields are the LAST bytes
+ * of that section.  Fields named spare* belong to no kernel.  -1 / NULL with crf_last_error() set for any other section name.  (The
+ * switch ws_gap acts between sections only.) */
+int crf_debug_ws_fields(const char *section, int64_t n, int64_t *out, int n_out);
+const char *crf_debug_ws_field_names(const char *section);
 
 /* The hot path.  Replaces, in one call and with no host synchronisation:
  *   gpu_ctc  (binding.cpp:86-117  -> compute_ctc_loss, ctc_entrypoint.cu:29-60)
