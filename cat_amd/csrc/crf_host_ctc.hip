@@ -1,6 +1,6 @@
 // cat_amd/csrc/crf_host_ctc.hip -- the host side of the surfaces on the plain CTC lattice, which share nothing with the loss call
 // (crf_host.hip) but crf_host_util.h: forced alignment (crf_ctc_align*, k_align.hip), hypothesis scores (crf_ctc_score*, k_score.hip), their
-// weighted gradient (crf_ctc_score_grad, k_score_grad.hip) and sampled / best-path label sequences (crf_ctc_sample, k_sample.hip) --
+// weighted gradient (crf_ctc_score_grad*, k_score_grad.hip) and sampled / best-path label sequences (crf_ctc_sample, k_sample.hip) --
 // argument checks, workspace sections, kernel choice, the C-ABI entry points of include/ctc_crf_hip.h.  Every error is answered before
 // any HIP call.  The activations are read in place in either layout and -- the *_logits entry points and crf_ctc_sample -- in f32, bf16
 // or f16.
@@ -14,7 +14,7 @@ namespace crf {
 
 static thread_local const char *g_sample_kernel = ""; // template instantiation of the row kernel of this thread's last crf_ctc_sample (crf_last_sample_kernel)
 static thread_local const char *g_score_kernel = "";  // ... of the kernel of this thread's last crf_ctc_score / crf_ctc_score_logits (crf_last_score_kernel)
-static thread_local const char *g_score_grad_kernel = "";   // ... of the alpha pass of this thread's last crf_ctc_score_grad (crf_last_score_grad_kernel)
+static thread_local const char *g_score_grad_kernel = "";   // ... of the alpha pass of this thread's last crf_ctc_score_grad / crf_ctc_score_grad_logits (crf_last_score_grad_kernel)
 
 // ---- what the three surfaces share ----
 // f(E{}) with the element type of dtype 0 (f32), 1 (bf16), 2 (f16)
@@ -157,8 +157,11 @@ static int score_call(const char *who, const void *act, int dtype, int time_majo
 
 // ---- the weighted gradient of the hypothesis scores (k_score_grad.hip) ----
 // its workspace: the stored alphas [H][T][64 NR] in fp64 -- the occupancies, fp32, go over the first half of each row -- (NR from the call's
-// longest hypothesis, as the score kernels'), then the H scores.  < 0 with the message set.
-static int64_t score_grad_ws_bytes(int64_t B, int64_t H, int64_t T, int64_t V, int64_t max_hyp_len, SideWs *out = nullptr) {
+// longest hypothesis, as the score kernels'), then the H scores, then -- raw network output (crf_ctc_score_grad_logits) -- the frames' lse
+// values [B][T].  < 0 with the message set; lse: with the lse section.
+enum ScoreGradWs { kSgOcc, kSgHscore, kSgLse };
+static const char *const kScoreGradWsNames[3] = {"occ", "hscore", "lse"};
+static int64_t score_grad_ws_bytes(int64_t B, int64_t H, int64_t T, int64_t V, int64_t max_hyp_len, bool lse = false, SideWs *out = nullptr) {
     if (B <= 0 || T <= 0 || V <= 0 || V > INT32_MAX) { set_error("crf_ctc_score_grad: bad B/T/V"); return -CRF_ERR_ARG; }
     if (H <= 0 || H > INT32_MAX || max_hyp_len < 0) { set_error("crf_ctc_score_grad: bad H/max_hyp_len"); return -CRF_ERR_ARG; }
     if (B * T > INT32_MAX) { set_error("crf_ctc_score_grad: B * T > INT32_MAX"); return -CRF_ERR_ARG; }
@@ -167,28 +170,70 @@ static int64_t score_grad_ws_bytes(int64_t B, int64_t H, int64_t T, int64_t V, i
     const int64_t S = with_nr(2 * max_hyp_len + 1, 64, [](auto nr, int) { return 64 * decltype(nr)::value; });
     if (H > (INT64_MAX / 16) / (T * S)) { set_error("crf_ctc_score_grad: H * T * states too large"); return -CRF_ERR_ARG; }
     SideWs w;
-    w.add("occ", H * T * S * (int64_t)sizeof(double)).add("hscore", H * (int64_t)sizeof(float));
+    w.add(kScoreGradWsNames[kSgOcc], H * T * S * (int64_t)sizeof(double)).add(kScoreGradWsNames[kSgHscore], H * (int64_t)sizeof(float));
+    if (lse) w.add(kScoreGradWsNames[kSgLse], B * T * (int64_t)sizeof(float));
     if (out) *out = w;
     return w.total;
 }
-// the four launches on one stream: crf_ctc_score's own kernel (scores into the workspace, invalid to the caller), then the three stages
-static int launch_score_grad(const ScoreGradParams &p, hipStream_t st, int64_t max_hyp_len) {
+// the launches on one stream: RAW the frames' lse values first; then the score call's own kernel (scores into the workspace, invalid to the
+// caller) -- crf_ctc_score's on log-probs, crf_ctc_score_logits' on raw output of element type E -- then the three stages
+template <typename E, bool RAW>
+static int launch_score_grad(const ScoreGradRawParams &p, hipStream_t st, int64_t max_hyp_len) {
     static const char *const names[] = {"crf_ctc_score_grad_alpha_kernel<1>", "crf_ctc_score_grad_alpha_kernel<2>", "crf_ctc_score_grad_alpha_kernel<4>", "crf_ctc_score_grad_alpha_kernel<8>"};
+    static const char *const raw_names[3][4] = {
+        {"crf_ctc_score_grad_alpha_raw_kernel<1, f32>", "crf_ctc_score_grad_alpha_raw_kernel<2, f32>", "crf_ctc_score_grad_alpha_raw_kernel<4, f32>", "crf_ctc_score_grad_alpha_raw_kernel<8, f32>"},
+        {"crf_ctc_score_grad_alpha_raw_kernel<1, bf16>", "crf_ctc_score_grad_alpha_raw_kernel<2, bf16>", "crf_ctc_score_grad_alpha_raw_kernel<4, bf16>", "crf_ctc_score_grad_alpha_raw_kernel<8, bf16>"},
+        {"crf_ctc_score_grad_alpha_raw_kernel<1, f16>", "crf_ctc_score_grad_alpha_raw_kernel<2, f16>", "crf_ctc_score_grad_alpha_raw_kernel<4, f16>", "crf_ctc_score_grad_alpha_raw_kernel<8, f16>"}};
+    constexpr int ei = std::is_same<E, float>::value ? 0 : std::is_same<E, AlnBf16>::value ? 1 : 2;
+    if constexpr (RAW)
+        if (const int rc = launch_row_lse<E>(p.x, p.lx, p.B, p.T, p.V, p.xs_b, p.xs_t, const_cast<float *>(p.lse), st)) return rc;
     ScoreParams sp{};
     sp.x = p.x; sp.labels = p.labels; sp.hyp_off = p.hyp_off; sp.hyp_len = p.hyp_len; sp.hyp_utt = p.hyp_utt; sp.lx = p.lx;
     sp.B = p.B; sp.H = p.H; sp.T = p.T; sp.V = p.V; sp.blank = p.blank; sp.xs_b = p.xs_b; sp.xs_t = p.xs_t;
-    sp.score = p.hscore; sp.invalid = p.invalid;
+    sp.score = p.hscore; sp.invalid = p.invalid; sp.lse = p.lse;
+    const ScoreGradParams &pl = p;            // the log-prob kernels' block
     const dim3 grid((unsigned)((p.H + kScoreWaves - 1) / kScoreWaves)), block(kScoreWaves * 64);
     int rc = with_nr(2 * max_hyp_len + 1, 64, [&](auto nr, int k) {
         constexpr int NR = decltype(nr)::value;
-        if (const int r = launch<crf_ctc_score_wave_kernel<NR, float, false>>("crf_ctc_score_wave_kernel", grid, block, 0, st, sp)) return r;
-        if (const int r = launch<crf_ctc_score_grad_alpha_kernel<NR>>(g_score_grad_kernel = names[k], grid, block, 0, st, p)) return r;
-        return launch<crf_ctc_score_grad_beta_kernel<NR>>("crf_ctc_score_grad_beta_kernel", grid, block, 0, st, p);
+        if (const int r = launch<crf_ctc_score_wave_kernel<NR, E, RAW>>("crf_ctc_score_wave_kernel", grid, block, 0, st, sp)) return r;
+        if constexpr (RAW) {
+            if (const int r = launch<crf_ctc_score_grad_alpha_raw_kernel<NR, E>>(g_score_grad_kernel = raw_names[ei][k], grid, block, 0, st, p)) return r;
+            return launch<crf_ctc_score_grad_beta_raw_kernel<NR, E>>("crf_ctc_score_grad_beta_raw_kernel", grid, block, 0, st, p);
+        } else {
+            if (const int r = launch<crf_ctc_score_grad_alpha_kernel<NR>>(g_score_grad_kernel = names[k], grid, block, 0, st, pl)) return r;
+            return launch<crf_ctc_score_grad_beta_kernel<NR>>("crf_ctc_score_grad_beta_kernel", grid, block, 0, st, pl);
+        }
     });
     if (rc) return rc;
     const int64_t nbt = (p.T + p.FB - 1) / p.FB;
-    return launch<crf_ctc_score_grad_reduce_kernel>("crf_ctc_score_grad_reduce_kernel", dim3((unsigned)(p.B * nbt)), dim3(kScoreGradReduceThreads),
-                                                    (size_t)p.FB * p.V * sizeof(float), st, p);
+    const dim3 rgrid((unsigned)(p.B * nbt)), rblock(kScoreGradReduceThreads);
+    const size_t lds = (size_t)p.FB * p.V * sizeof(float);
+    if constexpr (RAW) return launch<crf_ctc_score_grad_reduce_raw_kernel<E>>("crf_ctc_score_grad_reduce_raw_kernel", rgrid, rblock, lds, st, p);
+    else return launch<crf_ctc_score_grad_reduce_kernel>("crf_ctc_score_grad_reduce_kernel", rgrid, rblock, lds, st, pl);
+}
+// both entry points: the checks, the argument block, the launches; dtype < 0: log-probs (crf_ctc_score_grad), else raw output of that dtype
+// with the lse values behind the scores
+static int score_grad_call(const char *who, const void *act, int dtype, int time_major, int blank, const int32_t *labels, const int32_t *hyp_off,
+                           const int32_t *hyp_len, const int32_t *hyp_utt, const int32_t *lx, const float *weight, int64_t B, int64_t H,
+                           int64_t T, int64_t V, int64_t max_hyp_len, float *score, int32_t *invalid, float *grad, void *ws, int64_t ws_bytes,
+                           hipStream_t st) {
+    if (!act || !labels || !hyp_off || !hyp_len || !hyp_utt || !lx || !grad || !ws) { set_error(std::string(who) + ": null argument"); return CRF_ERR_ARG; }
+    if (dtype > 2) return bad_dtype(who);
+    SideWs w;
+    const int64_t need = score_grad_ws_bytes(B, H, T, V, max_hyp_len, dtype >= 0, &w);
+    if (need < 0) return (int)-need;
+    if (const int rc = check_blank(blank, V)) return rc;
+    if (const int rc = check_ws(ws_bytes, need)) return rc;
+    ScoreGradRawParams p{};
+    set_act(p, act, lx, B, T, V, blank, time_major);
+    p.labels = labels; p.hyp_off = hyp_off; p.hyp_len = hyp_len; p.hyp_utt = hyp_utt; p.H = (int)H;
+    p.score = score; p.invalid = invalid; p.weight = weight; p.grad = grad;
+    p.occ = (float *)((char *)ws + w.sec[kSgOcc].off); p.hscore = (float *)((char *)ws + w.sec[kSgHscore].off);
+    p.S = (int)(w.sec[kSgOcc].bytes / (H * T * (int64_t)sizeof(double)));
+    p.FB = (int)std::min<int64_t>(kScoreGradFrames, std::max<int64_t>(1, kScoreGradMaxV / V));
+    if (dtype < 0) return launch_score_grad<float, false>(p, st, max_hyp_len);
+    p.lse = (const float *)((char *)ws + w.sec[kSgLse].off);
+    return with_dtype(dtype, [&](auto e) { return launch_score_grad<decltype(e), true>(p, st, max_hyp_len); });
 }
 
 // ---- sampled / best-path label sequences (k_sample.hip) ----
@@ -277,20 +322,21 @@ int64_t crf_ctc_score_grad_workspace_bytes(int64_t B, int64_t H, int64_t T, int6
 int crf_ctc_score_grad(const float *act, int time_major, int blank, const int32_t *labels, const int32_t *hyp_off, const int32_t *hyp_len,
                        const int32_t *hyp_utt, const int32_t *lx, const float *weight, int64_t B, int64_t H, int64_t T, int64_t V,
                        int64_t max_hyp_len, float *score, int32_t *invalid, float *grad, void *ws, int64_t ws_bytes, void *stream_) {
-    if (!act || !labels || !hyp_off || !hyp_len || !hyp_utt || !lx || !grad || !ws) { set_error("crf_ctc_score_grad: null argument"); return CRF_ERR_ARG; }
-    SideWs w;
-    const int64_t need = score_grad_ws_bytes(B, H, T, V, max_hyp_len, &w);
-    if (need < 0) return (int)-need;
-    if (const int rc = check_blank(blank, V)) return rc;
-    if (const int rc = check_ws(ws_bytes, need)) return rc;
-    ScoreGradParams p{};
-    set_act(p, act, lx, B, T, V, blank, time_major);
-    p.labels = labels; p.hyp_off = hyp_off; p.hyp_len = hyp_len; p.hyp_utt = hyp_utt; p.H = (int)H;
-    p.score = score; p.invalid = invalid; p.weight = weight; p.grad = grad;
-    p.occ = (float *)((char *)ws + w.sec[0].off); p.hscore = (float *)((char *)ws + w.sec[1].off);
-    p.S = (int)(w.sec[0].bytes / (H * T * (int64_t)sizeof(double)));
-    p.FB = (int)std::min<int64_t>(kScoreGradFrames, std::max<int64_t>(1, kScoreGradMaxV / V));
-    return launch_score_grad(p, (hipStream_t)stream_, max_hyp_len);
+    return score_grad_call("crf_ctc_score_grad", act, -1, time_major, blank, labels, hyp_off, hyp_len, hyp_utt, lx, weight, B, H, T, V, max_hyp_len,
+                           score, invalid, grad, ws, ws_bytes, (hipStream_t)stream_);
+}
+
+int64_t crf_ctc_score_grad_logits_workspace_bytes(int64_t B, int64_t H, int64_t T, int64_t V, int64_t max_hyp_len) {
+    return or_minus1(score_grad_ws_bytes(B, H, T, V, max_hyp_len, true));
+}
+
+int crf_ctc_score_grad_logits(const void *act, int dtype, int time_major, int blank, const int32_t *labels, const int32_t *hyp_off,
+                              const int32_t *hyp_len, const int32_t *hyp_utt, const int32_t *lx, const float *weight, int64_t B, int64_t H,
+                              int64_t T, int64_t V, int64_t max_hyp_len, float *score, int32_t *invalid, float *grad, void *ws,
+                              int64_t ws_bytes, void *stream_) {
+    if (dtype < 0) return bad_dtype("crf_ctc_score_grad_logits");
+    return score_grad_call("crf_ctc_score_grad_logits", act, dtype, time_major, blank, labels, hyp_off, hyp_len, hyp_utt, lx, weight, B, H, T, V,
+                           max_hyp_len, score, invalid, grad, ws, ws_bytes, (hipStream_t)stream_);
 }
 
 int64_t crf_ctc_sample_workspace_bytes(int64_t B, int64_t T, int64_t V, int64_t K) { return or_minus1(sample_ws_bytes(B, T, V, K)); }

@@ -79,6 +79,15 @@ struct ScoreGradParams {
 template <int NR> __global__ void crf_ctc_score_grad_alpha_kernel(ScoreGradParams p);   // NR 1, 2, 4, 8
 template <int NR> __global__ void crf_ctc_score_grad_beta_kernel(ScoreGradParams p);
 __global__ void crf_ctc_score_grad_reduce_kernel(ScoreGradParams p);   // dynamic LDS: FB x V words
+// crf_ctc_score_grad_logits: the same on raw network output of element type E (float, AlnBf16, AlnF16) -- hscore is then the normalised
+// score crf_ctc_score_wave_kernel<NR, E, true> wrote, and grad takes log_softmax's term as well.  A block of its own, so that the
+// kernels above keep their arguments.
+struct ScoreGradRawParams : ScoreGradParams {
+    const float *lse;           // [B][T] workspace: the frames' normalisers (crf_align_lse_kernel)
+};
+template <int NR, typename E> __global__ void crf_ctc_score_grad_alpha_raw_kernel(ScoreGradRawParams p);   // NR 1, 2, 4, 8
+template <int NR, typename E> __global__ void crf_ctc_score_grad_beta_raw_kernel(ScoreGradRawParams p);
+template <typename E> __global__ void crf_ctc_score_grad_reduce_raw_kernel(ScoreGradRawParams p);          // dynamic LDS: FB x V words
 
 // ---- k_sample.hip ----
 constexpr int kSampleSmallV = 256;        // rows of up to here: 16 lanes per row and 16 rows per workgroup, beyond: a wave per row and workgroup

@@ -1,5 +1,5 @@
 // cat_amd/csrc/k_score_grad.hip -- the weighted gradient of H hypothesis scores over B utterances, written as ONE [B][T][V] tensor: the
-// backward half of k_score.hip.  Host side: crf_ctc_score_grad (crf_host_ctc.hip).
+// backward half of k_score.hip.  Host side: crf_ctc_score_grad / crf_ctc_score_grad_logits (crf_host_ctc.hip).
 //
 //   grad[u][t][v] = sum over h with hyp_utt[h] = u of  w_h * gamma_h[t][v]
 //   gamma_h[t][v] = sum over s with lab_h(s) = v of  exp(alpha_t[s] + beta_t[s] - score_h)
@@ -35,6 +35,16 @@
 // the project's 1e-4.  Here only the DIFFERENCES to the frame's maximum go through fp32 (exp and log on the hardware's instructions, sums
 // in [1, 3]); the accumulation is fp64, so a frame adds about 1e-7 whatever the magnitude.  The scores stay k_score's fp32 bits.
 // -inf flows through: a state at -inf gives exp(-inf) = 0, and there is no +inf to meet it.
+//
+// Raw network output (crf_ctc_score_grad_logits): the stage bodies are templates on the element type E -- float, or 2-byte bf16 / fp16
+// elements upcast in registers by lat_ld -- and the *_raw_kernel<NR, E> instantiations run them behind crf_align_lse_kernel and
+// crf_ctc_score_wave_kernel<NR, E, true> (crf_ctc_score_logits' own two launches: the same score bits).  Both recursions run on the upcast
+// values THEMSELVES: sum_t lse_t is common to all alignments of a hypothesis, so alpha_t[s] + beta_t[s] exceeds its log_softmax value by
+// exactly that sum, and stage 2 takes the RAW sum-product for the exponent, double(score) + sum_t double(lse_t) with the sum in the score
+// kernel's order -- the normalised fp32 score is what the workspace holds; half an ulp of it remains, common to a frame, for stage 3's
+// normaliser.  Stage 3 adds log_softmax's own term: d / d x of -lse_t is -softmax, once per unit of live weight,
+//   grad[u][t][v] = sum_{live h of u} w_h gamma_h[t][v] - W_u exp(x^[u][t][v] - lse_t),   W_u = sum_{live h of u} w_h  (ascending h).
+// The kernels under the old names are the float instantiations of the same bodies without any of this (LSE / RAW = false).
 #include "k_lattice_common.h"
 
 namespace crf {
@@ -83,19 +93,19 @@ template <int NR> __device__ __forceinline__ void occ_store(float *a, const floa
 }
 
 // What stages 1 and 2 share: the wave's hypothesis, whether it is live, its utterance's rows and its rows of occ.
-struct ScoreGradHyp {
+template <typename E> struct ScoreGradHyp {
     int h, lx, Sx;
     float score;
 
     const int *ul;
-    const float *xb;
+    const E *xb;
     double *ab;                 // the lane's alphas of frame 0: frame t's are S doubles further per frame
     float *ob;                  // the lane's occupancies of frame 0, at the start of the same rows: 2 S floats further per frame
 };
 // false: the wave has nothing to do (no hypothesis, or one that is invalid, scores -inf or weighs exactly 0: stage 3 skips it by the same
 // rule).  A live hypothesis is a valid one: u in [0, B), every label in [0, V), 0 < lx, 2 L + 1 <= S.  COPY: the score goes to the caller.
-template <int NR, bool COPY>
-__device__ __forceinline__ bool score_grad_hyp(const ScoreGradParams &p, int lane, ScoreGradHyp &y) {
+template <int NR, bool COPY, typename E>
+__device__ __forceinline__ bool score_grad_hyp(const ScoreGradParams &p, int lane, ScoreGradHyp<E> &y) {
     const int64_t hw = (int64_t)blockIdx.x * kScoreWaves + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     if (hw >= p.H) return false;
     y.h = (int)hw;
@@ -108,19 +118,19 @@ __device__ __forceinline__ bool score_grad_hyp(const ScoreGradParams &p, int lan
     y.score = score;
     y.Sx = 2 * p.hyp_len[y.h] + 1;
     y.ul = p.labels + p.hyp_off[y.h];
-    y.xb = (const float *)p.x + (int64_t)u * p.xs_b;
+    y.xb = (const E *)p.x + (int64_t)u * p.xs_b;
     y.ab = (double *)p.occ + ((int64_t)y.h * p.T) * (NR * 64) + lane * NR;
     y.ob = p.occ + ((int64_t)y.h * p.T) * (2 * NR * 64) + lane * NR;
     return true;
 }
 
-template <int NR>
-__global__ __launch_bounds__(kScoreWaves * 64) void crf_ctc_score_grad_alpha_kernel(ScoreGradParams p) {
-    using E = float;
+// Stage 1 on the element type E (float: log-probs or raw output; AlnBf16 / AlnF16: raw output, upcast in registers by lat_ld).
+template <int NR, typename E>
+__device__ __forceinline__ void score_grad_alpha_body(const ScoreGradParams p) {
     constexpr int S = NR * 64;                // states this instantiation holds
     constexpr int PF = NR >= 8 ? 2 : NR == 4 ? 4 : 8;   // frames per emission prefetch batch (two register sets in flight)
     const int lane = threadIdx.x & 63;
-    ScoreGradHyp y;
+    ScoreGradHyp<E> y;
     if (!score_grad_hyp<NR, true>(p, lane, y)) return;   // (no barrier in this kernel: waves leave on their own)
     const int lx = y.lx, Sx = y.Sx;
 
@@ -169,16 +179,24 @@ __global__ __launch_bounds__(kScoreWaves * 64) void crf_ctc_score_grad_alpha_ker
         for (int f = 0; f < PF; ++f) frame(eb[f], t0 + PF + f);
     }
 }
-
 template <int NR>
-__global__ __launch_bounds__(kScoreWaves * 64) void crf_ctc_score_grad_beta_kernel(ScoreGradParams p) {
-    using E = float;
+__global__ __launch_bounds__(kScoreWaves * 64) void crf_ctc_score_grad_alpha_kernel(ScoreGradParams p) { score_grad_alpha_body<NR, float>(p); }
+template <int NR, typename E>
+__global__ __launch_bounds__(kScoreWaves * 64) void crf_ctc_score_grad_alpha_raw_kernel(ScoreGradRawParams p) { score_grad_alpha_body<NR, E>(p); }
+
+// Stage 2 on the element type E.  LSE (raw output): y.score is the NORMALISED score, float(double(raw) - sum_t lse_t), while alpha and
+// beta are those of the upcast values themselves; the raw sum-product the exponent needs is double(score) + sum_t lse_t, the sum taken
+// as the score kernel took it (lat_lse_sum_wave).  What is left of the score's fp32 rounding is common to a frame: stage 3 normalises.
+template <int NR, typename E, bool LSE>
+__device__ __forceinline__ void score_grad_beta_body(const ScoreGradParams p, const float *lse) {
     constexpr int S = NR * 64;
     constexpr int PF = NR >= 8 ? 2 : NR == 4 ? 4 : 8;   // frames per prefetch batch of emissions and stored alphas (two register sets in flight)
     const int lane = threadIdx.x & 63;
-    ScoreGradHyp y;
+    ScoreGradHyp<E> y;
     if (!score_grad_hyp<NR, false>(p, lane, y)) return;
     const int lx = y.lx, Sx = y.Sx;
+    double lsum = 0.0;
+    if constexpr (LSE) lsum = lat_lse_sum_wave(lse + (int64_t)p.hyp_utt[y.h] * p.T, lx, lane);
 
     unsigned labo[NR];
     bool skipn[NR];                           // state s + 2 exists and may be entered from s
@@ -208,7 +226,7 @@ __global__ __launch_bounds__(kScoreWaves * 64) void crf_ctc_score_grad_beta_kern
         if (t < 0) return;                    // (the whole wave)
         double c[NR], n[NR];
         float o[NR];
-        const double score = (double)y.score;
+        const double score = LSE ? (double)y.score + lsum : (double)y.score;
 #pragma unroll
         for (int i = 0; i < NR; ++i) {
             o[i] = score_exp((float)((a[i] + b[i]) - score));
@@ -244,12 +262,18 @@ __global__ __launch_bounds__(kScoreWaves * 64) void crf_ctc_score_grad_beta_kern
         for (int f = 0; f < PF; ++f) frame(eb[f], ab[f], t0 - PF - f);
     }
 }
+template <int NR>
+__global__ __launch_bounds__(kScoreWaves * 64) void crf_ctc_score_grad_beta_kernel(ScoreGradParams p) { score_grad_beta_body<NR, float, false>(p, nullptr); }
+template <int NR, typename E>
+__global__ __launch_bounds__(kScoreWaves * 64) void crf_ctc_score_grad_beta_raw_kernel(ScoreGradRawParams p) { score_grad_beta_body<NR, E, true>(p, p.lse); }
 
-// Dynamic LDS: FB rows of V floats.  Grid: B * ceil(T / FB) workgroups of kScoreGradReduceThreads.
-__global__ __launch_bounds__(kScoreGradReduceThreads) void crf_ctc_score_grad_reduce_kernel(ScoreGradParams p) {
-    extern __shared__ __attribute__((aligned(16))) float rows[];   // [FB][V]
-    __shared__ int list[kScoreGradReduceThreads];                  // the live hypotheses of this utterance among one chunk of h, ascending
-    __shared__ int wcnt[kScoreGradReduceThreads / 64];
+// Stage 3.  rows: the dynamic LDS, FB rows of V floats; list: the live hypotheses of this utterance among one chunk of h, ascending.
+// RAW (raw output of element type E): the gradient with respect to the raw output has log_softmax's term as well,
+//   - W_u * exp(x^[u][t][v] - lse_t),   W_u = the sum of the live weights in ascending h (every live hypothesis's occupancies sum to 1 per frame),
+// taken off the frames below lx as the rows are stored: thread tid holds the entries v = tid, tid + 256, ... of a row there, the input row is
+// read beside them, one element per thread and step, and nothing more goes through LDS.  W_u = 0 (no live hypothesis): the rows stay exact 0.
+template <typename E, bool RAW>
+__device__ __forceinline__ void score_grad_reduce_body(const ScoreGradParams p, const float *lse, float *rows, int *list, int *wcnt) {
     constexpr int NW = kScoreGradReduceThreads / 64;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -259,6 +283,7 @@ __global__ __launch_bounds__(kScoreGradReduceThreads) void crf_ctc_score_grad_re
     const int nf = min(FB, p.T - t0);                              // frames of this block (>= 1)
     const int nl = min(nf, max(min(p.lx[u], p.T) - t0, 0));        // ... below lx: the ones that take occupancies
     const int S = p.S;
+    float W = 0.f;                                                 // RAW: the live weights of this utterance (the same value in every thread)
 
     for (int i = tid; i < nf * V; i += kScoreGradReduceThreads) rows[i] = 0.f;
     __syncthreads();
@@ -279,6 +304,7 @@ __global__ __launch_bounds__(kScoreGradReduceThreads) void crf_ctc_score_grad_re
             const int Sx = 2 * p.hyp_len[hk] + 1;
             const int *ul = p.labels + p.hyp_off[hk];
             const float w = p.weight ? p.weight[hk] : 1.f;
+            if constexpr (RAW) W += w;
             for (int f = wave; f < nl; f += NW) {
                 const float *o = p.occ + ((int64_t)hk * p.T + (t0 + f)) * (2 * S);   // (the floats at the start of a row of S doubles)
                 float *row = rows + f * V;
@@ -300,8 +326,30 @@ __global__ __launch_bounds__(kScoreGradReduceThreads) void crf_ctc_score_grad_re
     for (int f = 0; f < nf; ++f) {
         float *g = gb + (int64_t)f * p.xs_t;
         const float *row = rows + f * V;
+        if constexpr (RAW) {
+            if (f < nl && W != 0.f) {                              // (the whole workgroup)
+                const char *xr = (const char *)((const E *)p.x + (int64_t)u * p.xs_b + (int64_t)(t0 + f) * p.xs_t);
+                const float l = lse[(int64_t)u * p.T + (t0 + f)];
+                for (int v = tid; v < V; v += kScoreGradReduceThreads) g[v] = row[v] - W * score_exp(lat_ld<E>(xr + (size_t)v * sizeof(E)) - l);
+                continue;
+            }
+        }
         for (int v = tid; v < V; v += kScoreGradReduceThreads) g[v] = row[v];
     }
+}
+// Dynamic LDS: FB rows of V floats.  Grid: B * ceil(T / FB) workgroups of kScoreGradReduceThreads.
+__global__ __launch_bounds__(kScoreGradReduceThreads) void crf_ctc_score_grad_reduce_kernel(ScoreGradParams p) {
+    extern __shared__ __attribute__((aligned(16))) float rows[];   // [FB][V]
+    __shared__ int list[kScoreGradReduceThreads];
+    __shared__ int wcnt[kScoreGradReduceThreads / 64];
+    score_grad_reduce_body<float, false>(p, nullptr, rows, list, wcnt);
+}
+template <typename E>
+__global__ __launch_bounds__(kScoreGradReduceThreads) void crf_ctc_score_grad_reduce_raw_kernel(ScoreGradRawParams p) {
+    extern __shared__ __attribute__((aligned(16))) float rows[];   // [FB][V]
+    __shared__ int list[kScoreGradReduceThreads];
+    __shared__ int wcnt[kScoreGradReduceThreads / 64];
+    score_grad_reduce_body<E, true>(p, p.lse, rows, list, wcnt);
 }
 
 template __global__ void crf_ctc_score_grad_alpha_kernel<1>(ScoreGradParams);
@@ -312,5 +360,19 @@ template __global__ void crf_ctc_score_grad_beta_kernel<1>(ScoreGradParams);
 template __global__ void crf_ctc_score_grad_beta_kernel<2>(ScoreGradParams);
 template __global__ void crf_ctc_score_grad_beta_kernel<4>(ScoreGradParams);
 template __global__ void crf_ctc_score_grad_beta_kernel<8>(ScoreGradParams);
+#define CRF_SCORE_GRAD_RAW_INST(E)                                                              \
+    template __global__ void crf_ctc_score_grad_alpha_raw_kernel<1, E>(ScoreGradRawParams);     \
+    template __global__ void crf_ctc_score_grad_alpha_raw_kernel<2, E>(ScoreGradRawParams);     \
+    template __global__ void crf_ctc_score_grad_alpha_raw_kernel<4, E>(ScoreGradRawParams);     \
+    template __global__ void crf_ctc_score_grad_alpha_raw_kernel<8, E>(ScoreGradRawParams);     \
+    template __global__ void crf_ctc_score_grad_beta_raw_kernel<1, E>(ScoreGradRawParams);      \
+    template __global__ void crf_ctc_score_grad_beta_raw_kernel<2, E>(ScoreGradRawParams);      \
+    template __global__ void crf_ctc_score_grad_beta_raw_kernel<4, E>(ScoreGradRawParams);      \
+    template __global__ void crf_ctc_score_grad_beta_raw_kernel<8, E>(ScoreGradRawParams);      \
+    template __global__ void crf_ctc_score_grad_reduce_raw_kernel<E>(ScoreGradRawParams);
+CRF_SCORE_GRAD_RAW_INST(float)      // crf_ctc_score_grad_logits
+CRF_SCORE_GRAD_RAW_INST(AlnBf16)
+CRF_SCORE_GRAD_RAW_INST(AlnF16)
+#undef CRF_SCORE_GRAD_RAW_INST
 
 }  // namespace crf

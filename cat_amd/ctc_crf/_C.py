@@ -73,6 +73,11 @@ _lib.crf_ctc_score_grad_workspace_bytes.restype = _i64
 _lib.crf_ctc_score_grad.argtypes = [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp,
                                     _vp, _i64, _vp]
 _lib.crf_ctc_score_grad.restype = ctypes.c_int
+_lib.crf_ctc_score_grad_logits_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64, _i64]
+_lib.crf_ctc_score_grad_logits_workspace_bytes.restype = _i64
+_lib.crf_ctc_score_grad_logits.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
+                                           _vp, _vp, _vp, _vp, _i64, _vp]
+_lib.crf_ctc_score_grad_logits.restype = ctypes.c_int
 _lib.crf_last_score_grad_kernel.restype = ctypes.c_char_p
 _lib.crf_ctc_sample_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64]
 _lib.crf_ctc_sample_workspace_bytes.restype = _i64
@@ -104,7 +109,7 @@ _lib.crf_build_switches.restype = ctypes.c_char_p
 
 EXPORTED_SYMBOLS = (
     "crf_graph_create", "crf_graph_create_from_arcs", "crf_graph_destroy", "crf_graph_dims", "crf_graph_stats",
-    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_ws_fields", "crf_debug_ws_field_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_ctc_score", "crf_ctc_score_logits_workspace_bytes", "crf_ctc_score_logits", "crf_last_score_kernel", "crf_ctc_score_grad_workspace_bytes", "crf_ctc_score_grad", "crf_last_score_grad_kernel", "crf_ctc_sample_workspace_bytes", "crf_ctc_sample", "crf_last_sample_kernel", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
+    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_ws_fields", "crf_debug_ws_field_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_ctc_score", "crf_ctc_score_logits_workspace_bytes", "crf_ctc_score_logits", "crf_last_score_kernel", "crf_ctc_score_grad_workspace_bytes", "crf_ctc_score_grad", "crf_ctc_score_grad_logits_workspace_bytes", "crf_ctc_score_grad_logits", "crf_last_score_grad_kernel", "crf_ctc_sample_workspace_bytes", "crf_ctc_sample", "crf_last_sample_kernel", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
     "crf_debug_set", "crf_debug_unset", "crf_debug_list", "crf_last_den_kernel", "crf_last_call_streams", "crf_last_side_stream", "crf_last_fallback_counts", "crf_build_switches", "crf_last_error", "crf_version",
 )
 
@@ -134,7 +139,8 @@ def last_score_kernel() -> str:
 
 
 def last_score_grad_kernel() -> str:
-    """Template instantiation of the alpha pass of this thread's last ctc_score_grad call (include/ctc_crf_hip.h crf_last_score_grad_kernel)."""
+    """Template instantiation of the alpha pass of this thread's last ctc_score_grad call (include/ctc_crf_hip.h crf_last_score_grad_kernel);
+    a fused call's carries its element type: "crf_ctc_score_grad_alpha_raw_kernel<4, bf16>"."""
     return _lib.crf_last_score_grad_kernel().decode()
 
 
@@ -757,38 +763,50 @@ class ScoreMeta:
 
 
 def stage_score_meta(log_probs: torch.Tensor, hyps: torch.Tensor, hyp_lengths: torch.Tensor, lx: torch.Tensor,
-                     hyp_utt: Optional[torch.Tensor], blank: int, time_major: bool) -> ScoreMeta:
-    """_stage_score_meta's checks and ONE staged copy to log_probs' device (fp32 log-probs, as ctc_score takes them)."""
+                     hyp_utt: Optional[torch.Tensor], blank: int, time_major: bool, fused: bool = False) -> ScoreMeta:
+    """_stage_score_meta's checks and ONE staged copy to log_probs' device (fp32 log-probs, as ctc_score takes them; fused: raw network
+    output in f32 / bf16 / f16)."""
     assert log_probs.is_cuda and log_probs.is_contiguous() and log_probs.dim() == 3
-    dev, N, T, V = _act_shape(log_probs, False, time_major, blank)
+    dev, N, T, V = _act_shape(log_probs, fused, time_major, blank)
     meta_cpu, H, max_l = _stage_score_meta(hyps, hyp_lengths, lx, hyp_utt, N, T, V, blank)
     return ScoreMeta(_h2d_async(meta_cpu, dev), N, H, T, V, max_l, blank)
 
 
-def _score_args(log_probs: torch.Tensor, sm: ScoreMeta, time_major: bool):
-    dev, N, T, V = _act_shape(log_probs, False, time_major, sm.blank)
+def _score_args(log_probs: torch.Tensor, sm: ScoreMeta, time_major: bool, fused: bool = False):
+    dev, N, T, V = _act_shape(log_probs, fused, time_major, sm.blank)
     assert log_probs.is_cuda and log_probs.is_contiguous() and (N, T, V) == (sm.N, sm.T, sm.V) and sm.meta.device == dev
     return dev, N, T, V
 
 
-def ctc_score_staged(log_probs: torch.Tensor, sm: ScoreMeta, time_major: bool = False, scores_out: Optional[torch.Tensor] = None):
-    """ctc_score's crf_ctc_score call on metadata that is staged already.  Returns (scores [H] f32, invalid [H] int32)."""
-    dev, N, T, V = _score_args(log_probs, sm, time_major)
+def ctc_score_staged(log_probs: torch.Tensor, sm: ScoreMeta, time_major: bool = False, scores_out: Optional[torch.Tensor] = None,
+                     fused: bool = False):
+    """ctc_score's crf_ctc_score call (fused: its crf_ctc_score_logits call, on raw network output in f32 / bf16 / f16) on metadata that is
+    staged already.  Returns (scores [H] f32, invalid [H] int32)."""
+    dev, N, T, V = _score_args(log_probs, sm, time_major, fused)
     lx_d, len_d, off_d, utt_d, lab_d = sm.parts()
     scores = torch.empty(sm.H, dtype=torch.float32, device=dev) if scores_out is None else scores_out
     assert scores.shape == (sm.H,) and scores.dtype == torch.float32 and scores.is_contiguous() and scores.device == dev
     invalid = torch.empty(sm.H, dtype=torch.int32, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
     with torch.cuda.device(dev):
-        _check(_lib.crf_ctc_score(_ptr(log_probs), 1 if time_major else 0, sm.blank, _ptr(lab_d), _ptr(off_d), _ptr(len_d), _ptr(utt_d),
-                                  _ptr(lx_d), N, sm.H, T, V, sm.max_len, _ptr(scores), _ptr(invalid), _vp(stream)))
+        if fused:
+            ws_bytes = _lib.crf_ctc_score_logits_workspace_bytes(N, T, V)
+            ws = _new_ws(ws_bytes, dev)
+            _check(_lib.crf_ctc_score_logits(_ptr(log_probs), _FUSED_DTYPES[log_probs.dtype], 1 if time_major else 0, sm.blank, _ptr(lab_d),
+                                             _ptr(off_d), _ptr(len_d), _ptr(utt_d), _ptr(lx_d), N, sm.H, T, V, sm.max_len, _ptr(scores),
+                                             _ptr(invalid), _ptr(ws), ws_bytes, _vp(stream)))
+        else:
+            _check(_lib.crf_ctc_score(_ptr(log_probs), 1 if time_major else 0, sm.blank, _ptr(lab_d), _ptr(off_d), _ptr(len_d), _ptr(utt_d),
+                                      _ptr(lx_d), N, sm.H, T, V, sm.max_len, _ptr(scores), _ptr(invalid), _vp(stream)))
     return scores, invalid
 
 
 def ctc_score_grad(log_probs: torch.Tensor, meta, weights: Optional[torch.Tensor], blank: int = 0, time_major: bool = False,
-                   grad_out: Optional[torch.Tensor] = None, scores_out: Optional[torch.Tensor] = None):
+                   grad_out: Optional[torch.Tensor] = None, scores_out: Optional[torch.Tensor] = None, fused: bool = False):
     """The weighted gradient of the hypothesis scores as ONE tensor of log_probs' shape (include/ctc_crf_hip.h ``crf_ctc_score_grad``):
     grad[u] = sum over the hypotheses h of utterance u of weights[h] * d score[h] / d log_probs[u].
+    fused: log_probs is the RAW network output in f32 / bf16 / f16 (``crf_ctc_score_grad_logits``): scores and invalid are
+    ctc_score(fused=True)'s bits, the gradient (f32) is the one with respect to the raw output, log_softmax's backward included.
 
     log_probs [N,T,V] (time_major: [T,N,V]) f32 log-probs on the GPU, contiguous, read in place and never replicated; meta: a ScoreMeta
     (stage_score_meta; its blank counts) or the tuple (hyps, hyp_lengths, input_lengths, hyp_utt) of CPU tensors as ctc_score takes them;
@@ -796,13 +814,13 @@ def ctc_score_grad(log_probs: torch.Tensor, meta, weights: Optional[torch.Tensor
     synchronisation; scores and invalid are ctc_score's bits.  grad_out / scores_out: contiguous f32 device tensors of log_probs' shape /
     [H] that receive the results (else allocated); every entry of grad is written."""
     assert log_probs.is_cuda and log_probs.is_contiguous() and log_probs.dim() == 3
-    sm = meta if isinstance(meta, ScoreMeta) else stage_score_meta(log_probs, *meta, blank, time_major)
-    dev, N, T, V = _score_args(log_probs, sm, time_major)
+    sm = meta if isinstance(meta, ScoreMeta) else stage_score_meta(log_probs, *meta, blank, time_major, fused)
+    dev, N, T, V = _score_args(log_probs, sm, time_major, fused)
     H = sm.H
     lx_d, len_d, off_d, utt_d, lab_d = sm.parts()
     if weights is not None:
         assert weights.shape == (H,) and weights.dtype == torch.float32 and weights.is_contiguous() and weights.device == dev
-    ws_bytes = _lib.crf_ctc_score_grad_workspace_bytes(N, H, T, V, sm.max_len)
+    ws_bytes = (_lib.crf_ctc_score_grad_logits_workspace_bytes if fused else _lib.crf_ctc_score_grad_workspace_bytes)(N, H, T, V, sm.max_len)
     ws = _new_ws(ws_bytes, dev)
     grad = torch.empty(log_probs.shape, dtype=torch.float32, device=dev) if grad_out is None else grad_out
     assert grad.shape == log_probs.shape and grad.dtype == torch.float32 and grad.is_contiguous() and grad.device == dev
@@ -811,9 +829,14 @@ def ctc_score_grad(log_probs: torch.Tensor, meta, weights: Optional[torch.Tensor
     invalid = torch.empty(H, dtype=torch.int32, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
     with torch.cuda.device(dev):
-        rc = _lib.crf_ctc_score_grad(_ptr(log_probs), 1 if time_major else 0, sm.blank, _ptr(lab_d), _ptr(off_d), _ptr(len_d), _ptr(utt_d),
-                                     _ptr(lx_d), _ptr(weights), N, H, T, V, sm.max_len, _ptr(scores), _ptr(invalid), _ptr(grad), _ptr(ws),
-                                     ws_bytes, _vp(stream))
+        if fused:
+            rc = _lib.crf_ctc_score_grad_logits(_ptr(log_probs), _FUSED_DTYPES[log_probs.dtype], 1 if time_major else 0, sm.blank, _ptr(lab_d),
+                                                _ptr(off_d), _ptr(len_d), _ptr(utt_d), _ptr(lx_d), _ptr(weights), N, H, T, V, sm.max_len,
+                                                _ptr(scores), _ptr(invalid), _ptr(grad), _ptr(ws), ws_bytes, _vp(stream))
+        else:
+            rc = _lib.crf_ctc_score_grad(_ptr(log_probs), 1 if time_major else 0, sm.blank, _ptr(lab_d), _ptr(off_d), _ptr(len_d), _ptr(utt_d),
+                                         _ptr(lx_d), _ptr(weights), N, H, T, V, sm.max_len, _ptr(scores), _ptr(invalid), _ptr(grad), _ptr(ws),
+                                         ws_bytes, _vp(stream))
     _check(rc)
     return grad, scores, invalid
 

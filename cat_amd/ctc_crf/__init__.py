@@ -11,7 +11,8 @@ Same names, arguments and error behaviour as the reference:
                                                                                          (forced alignment; not in the reference)
   ctc_score(log_probs, hyps, hyp_lengths, input_lengths, hyp_utt=None, blank=0, time_major=False, fuse_log_softmax=False) -> FloatTensor[H]
                                                                                          (forward-only scores of many hypotheses per utterance)
-  ctc_logp(log_probs, hyps, hyp_lengths, input_lengths, hyp_utt=None, blank=0, time_major=False) -> (FloatTensor[H], IntTensor[H])
+  ctc_logp(log_probs, hyps, hyp_lengths, input_lengths, hyp_utt=None, blank=0, time_major=False, fuse_log_softmax=False)
+                                                                                         -> (FloatTensor[H], IntTensor[H])
                                                                                          (the same scores WITH autograd: one [N,T,V] gradient)
   ctc_sample(log_probs, input_lengths, n_samples, seed, offset=0, blank=0, time_major=False, return_paths=False)
                                                               -> (hyps IntTensor[N*K, T], hyp_lengths IntTensor[N*K], hyp_utt IntTensor[N*K])
@@ -301,8 +302,30 @@ class _CTC_LOGP(Function):
         return grad, None, None
 
 
+class _CTC_LOGP_LOGITS(Function):
+    """_CTC_LOGP on the RAW network output in fp32 / bf16 / fp16: scores [H] = crf_ctc_score_logits; backward = ONE crf_ctc_score_grad_logits
+    call with weight = grad_output, whose fp32 result -- d / d netout, log_softmax's backward included -- is cast once to netout's dtype
+    (as _CTC_CRF_LOGITS).  No fp32 copy of the activations is made or kept."""
+
+    @staticmethod
+    def forward(ctx, netout, sm, time_major):
+        scores, invalid = core.ctc_score_staged(netout, sm, time_major, fused=True)
+        ctx.save_for_backward(netout)
+        ctx.sm, ctx.time_major = sm, time_major
+        ctx.mark_non_differentiable(invalid)
+        return scores, invalid
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_scores, _grad_invalid):
+        netout, = ctx.saved_tensors
+        w = grad_scores.to(device=netout.device, dtype=torch.float32).contiguous()
+        grad, _, _ = core.ctc_score_grad(netout, ctx.sm, w, ctx.sm.blank, ctx.time_major, fused=True)
+        return grad.to(netout.dtype), None, None
+
+
 def ctc_logp(log_probs: torch.Tensor, hyps: torch.Tensor, hyp_lengths: torch.Tensor, input_lengths: torch.Tensor,
-             hyp_utt: torch.Tensor = None, blank: int = 0, time_major: bool = False):
+             hyp_utt: torch.Tensor = None, blank: int = 0, time_major: bool = False, fuse_log_softmax: bool = False):
     """ctc_score with autograd: CTC log-likelihoods of H hypotheses over N utterances whose gradient reaches log_probs as ONE (N, T, V)
     tensor -- what minimum-risk / MWER training on sampled or N-best hypotheses and the nn.CTCLoss(reduction='none',
     zero_infinity=True) / length losses (cat/ctc/train_jsa.py:194-201) need, without repeat_interleave'd activations and without an
@@ -314,12 +337,19 @@ def ctc_logp(log_probs: torch.Tensor, hyps: torch.Tensor, hyp_lengths: torch.Ten
 
     log_probs (torch.FloatTensor): (N, T, V) fp32 log-probs on the GPU, contiguous, or (T, N, V) with time_major=True; anything else is
         refused.  hyps, hyp_lengths, input_lengths, hyp_utt, blank: as ctc_score takes them (CPU tensors).
+    fuse_log_softmax (bool): log_probs is the RAW network output in fp32, bf16 or fp16, read in place -- no log_softmax in front, no fp32
+        copy kept for autograd: the scores are ctc_score(fuse_log_softmax=True)'s bits, those of log_softmax of the upcast values, and
+        backward is one call (crf_ctc_score_grad_logits) whose fp32 gradient with respect to the raw output, log_softmax's backward
+        included, is cast once to the input's dtype.
     Returns (scores FloatTensor[H], invalid IntTensor[H]) on log_probs' device, no host synchronisation.  scores are ctc_score's bits and
     differentiable with respect to log_probs (once: no double backward); invalid (1: the hypothesis does not fit its utterance) is not.
     Backward is one call (include/ctc_crf_hip.h crf_ctc_score_grad) whose weights are the incoming grad_output, so any torch expression
     of the scores trains; a hypothesis that is invalid or scores -inf, or whose weight is exactly 0, adds nothing to the gradient
     (zero_infinity=True).  With log_probs.requires_grad no hypothesis may be longer than 255 labels."""
-    if log_probs.dtype != torch.float:
+    if fuse_log_softmax:
+        if log_probs.dtype not in (torch.float, torch.bfloat16, torch.float16):
+            raise RuntimeError(f"ctc_logp: expect float32, bfloat16 or float16 network output, got {log_probs.dtype}")
+    elif log_probs.dtype != torch.float:
         raise RuntimeError(f"ctc_logp: expect float32 log-probs, got {log_probs.dtype}")
     if not log_probs.is_cuda:
         raise RuntimeError("ctc_logp: log_probs must be on the GPU (there is no CPU path)")
@@ -328,8 +358,8 @@ def ctc_logp(log_probs: torch.Tensor, hyps: torch.Tensor, hyp_lengths: torch.Ten
     if log_probs.requires_grad and hyp_lengths.numel() and int(hyp_lengths.max()) > core.SCORE_GRAD_MAX_LEN:
         raise RuntimeError(f"ctc_logp: the gradient takes hypotheses of up to {core.SCORE_GRAD_MAX_LEN} labels, got {int(hyp_lengths.max())}")
     with torch.no_grad():
-        sm = core.stage_score_meta(log_probs, hyps, hyp_lengths, input_lengths, hyp_utt, int(blank), bool(time_major))
-    return _CTC_LOGP.apply(log_probs, sm, bool(time_major))
+        sm = core.stage_score_meta(log_probs, hyps, hyp_lengths, input_lengths, hyp_utt, int(blank), bool(time_major), bool(fuse_log_softmax))
+    return (_CTC_LOGP_LOGITS if fuse_log_softmax else _CTC_LOGP).apply(log_probs, sm, bool(time_major))
 
 
 def ctc_sample(log_probs: torch.Tensor, input_lengths: torch.Tensor, n_samples: int, seed: int, offset: int = 0, blank: int = 0,

@@ -319,6 +319,34 @@ int crf_ctc_score_grad(const float *act_dev, int time_major, int blank, const in
                        void *workspace_dev, int64_t workspace_bytes, void *stream);
 const char *crf_last_score_grad_kernel(void);
 
+/* crf_ctc_score_grad on the RAW network output: act_dev of dtype 0 = fp32, 1 = bf16, 2 = fp16, read in place in either layout and never
+ * copied or staged as fp32 (2-byte elements are upcast in registers; rows of 16-bit elements need 2-byte alignment only).  With x^ the
+ * exact fp32 upcast and lse_t the normaliser of row (u, t) by crf_ctc_align_logits's row kernel:
+ * Validity and scores: score_dev[h] and invalid_dev[h] (either may be NULL) are exactly what crf_ctc_score_logits writes for the same
+ * arguments, bit for bit -- the call launches that row kernel and that very score kernel first.
+ * Gradient: d (sum_h weight_dev[h] score_dev[h]) / d x^, log_softmax's backward included, fp32 in the layout of act_dev:
+ *   grad_dev[u][t][v] = sum over the live h of u of  weight_dev[h] * gamma_h[t][v]  -  W_u * exp(x^[u][t][v] - lse_t),   t < lx[u],
+ *   W_u = the sum of weight_dev[h] over the live h of u, accumulated in ascending h,
+ * gamma_h the occupancies of log_softmax(x^) as above.  The recursions run on x^ itself, carried in fp64 as crf_ctc_score_grad's:
+ * sum_t lse_t is common to all alignments of a hypothesis, and the exponent alpha + beta - s takes the raw sum-product
+ * s = double(score) + sum_t double(lse_t), that sum in crf_ctc_score_logits's order.  A hypothesis is live as above: valid, score > -inf and a
+ * weight other than 0.  The call writes EVERY entry of grad_dev; rows of frames t >= lx[u] and of utterances without a live hypothesis
+ * are exactly 0, the softmax term included (a dead, invalid or zero-weight hypothesis adds nothing to W_u).  The activations hold no NaN
+ * and no +inf; -inf entries are allowed as long as a row keeps one finite entry, and raw output of -inf on a label of a hypothesis
+ * makes it score -inf, so it is not live.  The gradient is NOT promised bit for bit (LDS float adds, as above).
+ * crf_last_score_grad_kernel() names the alpha pass with its element type, e.g. "crf_ctc_score_grad_alpha_raw_kernel<4, bf16>" (f32, bf16, f16).
+ * Limits as crf_ctc_score_grad: max_hyp_len <= 255 and V <= 8192, beyond CRF_ERR_UNSUPPORTED with the same messages.
+ * Workspace: crf_ctc_score_grad_logits_workspace_bytes = crf_ctc_score_grad_workspace_bytes' sections and behind them the lse values
+ * [B][T], fp32; its contents on entry do not matter; -1 with crf_last_error() set where crf_ctc_score_grad_workspace_bytes returns -1.
+ * CRF_ERR_ARG: a dtype outside 0..2 and what crf_ctc_score_grad answers so; CRF_ERR_WORKSPACE: workspace too small (the message names
+ * the bytes needed) -- all answered before any HIP call.  No host synchronisation, all work on `stream`, no environment variable read. */
+int64_t crf_ctc_score_grad_logits_workspace_bytes(int64_t B, int64_t H, int64_t T, int64_t V, int64_t max_hyp_len);
+int crf_ctc_score_grad_logits(const void *act_dev, int dtype, int time_major, int blank, const int32_t *labels_dev,
+                              const int32_t *hyp_off_dev, const int32_t *hyp_len_dev, const int32_t *hyp_utt_dev, const int32_t *lx_dev,
+                              const float *weight_dev, int64_t B, int64_t H, int64_t T, int64_t V, int64_t max_hyp_len,
+                              float *score_dev, int32_t *invalid_dev, float *grad_dev,
+                              void *workspace_dev, int64_t workspace_bytes, void *stream);
+
 /* Label sequences drawn on the GPU (what cat/ctc/train_jsa.py:256-269 `_sample` gets from torch.multinomial over N T rows, a transpose and
  * the third-party ctc_align.align_; with greedy = 1 the best path: arg-max per frame): per frame K classes from softmax(x), then the CTC
  * map B on each of the B K frame paths.  The activations are read in place, [B][T][V] (time_major = 0) or [T][B][V] (1), dtype 0 = fp32,
