@@ -1,6 +1,7 @@
 // cat_amd/csrc/crf_host_ctc.hip -- the host side of the surfaces on the plain CTC lattice, which share nothing with the loss call
 // (crf_host.hip) but crf_host_util.h: forced alignment (crf_ctc_align*, k_align.hip), hypothesis scores (crf_ctc_score*, k_score.hip), their
-// weighted gradient (crf_ctc_score_grad*, k_score_grad.hip) and sampled / best-path label sequences (crf_ctc_sample, k_sample.hip) --
+// weighted gradient (crf_ctc_score_grad*, k_score_grad.hip), sampled / best-path label sequences (crf_ctc_sample, k_sample.hip) and the
+// prefix beam search (crf_ctc_beam, k_beam.hip) --
 // argument checks, workspace sections, kernel choice, the C-ABI entry points of include/ctc_crf_hip.h.  Every error is answered before
 // any HIP call.  The activations are read in place in either layout and -- the *_logits entry points and crf_ctc_sample -- in f32, bf16
 // or f16.
@@ -13,7 +14,8 @@
 namespace crf {
 
 static thread_local const char *g_sample_kernel = ""; // template instantiation of the row kernel of this thread's last crf_ctc_sample (crf_last_sample_kernel)
-static thread_local const char *g_score_kernel = "";  // ... of the kernel of this thread's last crf_ctc_score / crf_ctc_score_logits (crf_last_score_kernel)
+static thread_local const char *g_beam_kernel = "";   // ... of the row kernel of this thread's last crf_ctc_beam (crf_last_beam_kernel)
+static thread_local const char *g_score_kernel = "";// ... of the kernel of this thread's last crf_ctc_score / crf_ctc_score_logits (crf_last_score_kernel)
 static thread_local const char *g_score_grad_kernel = "";   // ... of the alpha pass of this thread's last crf_ctc_score_grad / crf_ctc_score_grad_logits (crf_last_score_grad_kernel)
 
 // ---- what the three surfaces share ----
@@ -263,6 +265,36 @@ static int64_t sample_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t K) {
     return SideWs().add("cls", B * K * T * (int64_t)sizeof(int32_t)).total;
 }
 
+// ---- prefix beam search (k_beam.hip) ----
+// its workspace: the frames' blank value and top-C (value, class) pairs, [B T][C + 1] floats and as many int32, then the trace words
+// [B][T][W] int32 (not used by a call that brings a trace buffer of its own).  < 0 with the message set.
+enum BeamWs { kBmVal, kBmCls, kBmTrace };
+static const char *const kBeamWsNames[3] = {"val", "cls", "trace"};
+static int64_t beam_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t W, int64_t C, SideWs *out = nullptr) {
+    if (B <= 0 || T <= 0 || V <= 0) { set_error("crf_ctc_beam: bad B/T/V"); return -CRF_ERR_ARG; }
+    if (W < 1 || W > kBeamMaxW) { set_error("crf_ctc_beam: beam width " + std::to_string(W) + " outside [1, " + std::to_string(kBeamMaxW) + "]"); return -CRF_ERR_ARG; }
+    if (C < 1 || C > kBeamMaxC) { set_error("crf_ctc_beam: top_classes " + std::to_string(C) + " outside [1, " + std::to_string(kBeamMaxC) + "]"); return -CRF_ERR_ARG; }
+    if (B > INT32_MAX || T > INT32_MAX || B * T > INT32_MAX) { set_error("crf_ctc_beam: B * T > INT32_MAX"); return -CRF_ERR_ARG; }
+    if (V > kBeamMaxV) { set_error("V > " + std::to_string(kBeamMaxV) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
+    const int64_t rs = std::min(C, V - 1) + 1;
+    SideWs w;
+    w.add(kBeamWsNames[kBmVal], B * T * rs * (int64_t)sizeof(float)).add(kBeamWsNames[kBmCls], B * T * rs * (int64_t)sizeof(int32_t))
+     .add(kBeamWsNames[kBmTrace], B * T * W * (int64_t)sizeof(int32_t));
+    if (out) *out = w;
+    return w.total;
+}
+// the row stage over the B T frames, then one wave per utterance, on the same stream
+template <typename E>
+static int launch_beam(const BeamParams &p, hipStream_t st) {
+    static const char *const names[3] = {"crf_beam_row_kernel<f32>", "crf_beam_row_kernel<bf16>", "crf_beam_row_kernel<f16>"};
+    constexpr int ei = std::is_same<E, float>::value ? 0 : std::is_same<E, AlnBf16>::value ? 1 : 2;
+    const int64_t frames = (int64_t)p.B * p.T;
+    const int R = p.V <= kBeamRowsV ? 4 : 1;
+    if (const int rc = launch<crf_beam_row_kernel<E>>(g_beam_kernel = names[ei], dim3((unsigned)((frames + R - 1) / R)), dim3(64 * R),
+                                                      (size_t)R * p.V * sizeof(float), st, p)) return rc;
+    return launch<crf_beam_search_kernel>("crf_beam_search_kernel", dim3((unsigned)p.B), dim3(64), 0, st, p);
+}
+
 }  // namespace crf
 
 using namespace crf;
@@ -359,6 +391,32 @@ int crf_ctc_sample(const void *act, int dtype, int time_major, int blank, const 
     return with_dtype(dtype, [&](auto e) { return launch_sample<decltype(e)>(p, (hipStream_t)stream_, greedy != 0); });
 }
 
+int64_t crf_ctc_beam_workspace_bytes(int64_t B, int64_t T, int64_t V, int64_t W, int64_t top_classes) {
+    return or_minus1(beam_ws_bytes(B, T, V, W, top_classes));
+}
+
+int crf_ctc_beam(const void *act, int dtype, int time_major, int blank, int normalize, const int32_t *lx, int64_t B, int64_t T, int64_t V,
+                 int64_t W, int64_t nbest, int64_t top_classes, int32_t *hyps, int32_t *hyp_len, float *score, int32_t *trace, void *ws,
+                 int64_t ws_bytes, void *stream_) {
+    if (!act || !lx || !hyps || !hyp_len || !score || !ws) { set_error("crf_ctc_beam: null argument"); return CRF_ERR_ARG; }
+    if (dtype < 0 || dtype > 2) return bad_dtype("crf_ctc_beam");
+    if (normalize != 0 && normalize != 1) { set_error("crf_ctc_beam: normalize must be 0 or 1, got " + std::to_string(normalize)); return CRF_ERR_ARG; }
+    SideWs w;
+    const int64_t need = beam_ws_bytes(B, T, V, W, top_classes, &w);
+    if (need < 0) return (int)-need;
+    if (nbest < 1 || nbest > W) { set_error("crf_ctc_beam: nbest " + std::to_string(nbest) + " outside [1, W=" + std::to_string(W) + "]"); return CRF_ERR_ARG; }
+    if (const int rc = check_blank(blank, V)) return rc;
+    if (const int rc = check_ws(ws_bytes, need)) return rc;
+    BeamParams p{};
+    set_act(p, act, lx, B, T, V, blank, time_major);
+    p.W = (int)W; p.nbest = (int)nbest; p.C = (int)std::min(top_classes, V - 1); p.normalize = normalize;
+    p.val = (float *)((char *)ws + w.sec[kBmVal].off); p.cls = (int *)((char *)ws + w.sec[kBmCls].off);
+    p.trace = trace ? trace : (int *)((char *)ws + w.sec[kBmTrace].off); p.fill_trace = trace != nullptr;
+    p.hyps = hyps; p.hyp_len = hyp_len; p.score = score;
+    return with_dtype(dtype, [&](auto e) { return launch_beam<decltype(e)>(p, (hipStream_t)stream_); });
+}
+
+const char *crf_last_beam_kernel(void) { return g_beam_kernel; }
 const char *crf_last_score_kernel(void) { return g_score_kernel; }
 const char *crf_last_score_grad_kernel(void) { return g_score_grad_kernel; }
 const char *crf_last_sample_kernel(void) { return g_sample_kernel; }

@@ -110,6 +110,29 @@ struct SampleParams {
 template <int G, typename E, bool GREEDY> __global__ void crf_sample_row_kernel(SampleParams p);
 __global__ void crf_sample_collapse_kernel(SampleParams p);
 
+// ---- k_beam.hip ----
+constexpr int kBeamMaxW = 64;             // beam slots: one lane each
+constexpr int kBeamMaxC = 64;             // classes per frame that take part besides the blank: one lane each, one bit each of a slot's mask
+constexpr int kBeamMaxV = 8192;           // the row stage keeps a row of V floats per wave in LDS: 32 KiB per row at most
+constexpr int kBeamRowsV = 4096;          // rows of up to here: four waves (rows) per workgroup of the row stage, beyond one: at most 64 KiB of rows
+// Kernel arguments of crf_ctc_beam: the activations as for the alignment (row (n, t) at n * xs_b + t * xs_t ELEMENTS, read in place)
+struct BeamParams {
+    const void *x;
+    const int *lx;
+    int B, T, V, blank;
+    int W, nbest, C, normalize; // C: min(top_classes, V - 1)
+    int fill_trace;             // trace is the caller's buffer: its rows t >= lx take -1
+    int64_t xs_b, xs_t;
+    float *val;                 // [B T][C + 1] workspace, rows t < lx: the blank's value, then the C values of E_t in descending order
+    int *cls;                   // [B T][C + 1] workspace: the blank, then their classes (-1: no class left above -inf)
+    int *trace;                 // [B][T][W] the caller's trace_dev or the workspace: parent slot + 64 (class + 1), -1 for an empty slot
+    int *hyps, *hyp_len;        // [B nbest][T], [B nbest]
+    float *score;               // [B nbest]
+};
+// E: float, AlnBf16, AlnF16; one wave per row, blockDim.x / 64 rows per workgroup; dynamic LDS: that many x V words
+template <typename E> __global__ void crf_beam_row_kernel(BeamParams p);
+__global__ void crf_beam_search_kernel(BeamParams p);   // one wave (workgroup) per utterance
+
 // ---- k_res.hip ----
 constexpr int kEpRegsR = 2;   // emission-row prefetch registers (V <= 2*512 for the resident kernels)
 constexpr int kPoll = 4;      // granules polled concurrently per thread

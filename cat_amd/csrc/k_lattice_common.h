@@ -1,5 +1,6 @@
 // cat_amd/csrc/k_lattice_common.h -- device helpers the kernels on the CTC lattice of 2L+1 states share (k_align.hip: best path; k_score.hip:
-// sum-product scores; k_score_grad.hip: their gradient; k_sample.hip takes the element load only): the upcast element load, the label
+// sum-product scores; k_score_grad.hip: their gradient; k_sample.hip takes the element load only, k_beam.hip the element load and the
+// fp32 exp / log of the sums): the upcast element load, the label
 // set-up and validity rule of a transcript, the clamped emission prefetch, the fp64 sum of the frames' normalisers, and the fp32
 // log-sum-exp of the scores with its one operand order.
 // The max-plus / sum-product frame bodies, the back-pointers and the DPP wave recursions stay with their kernels.

@@ -85,6 +85,12 @@ _lib.crf_ctc_sample.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _
                                 ctypes.c_int, _vp, _vp, _vp, _vp, _i64, _vp]
 _lib.crf_ctc_sample.restype = ctypes.c_int
 _lib.crf_last_sample_kernel.restype = ctypes.c_char_p
+_lib.crf_ctc_beam_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64, _i64]
+_lib.crf_ctc_beam_workspace_bytes.restype = _i64
+_lib.crf_ctc_beam.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _i64, _i64, _i64, _i64, _i64, _i64,
+                              _vp, _vp, _vp, _vp, _vp, _i64, _vp]
+_lib.crf_ctc_beam.restype = ctypes.c_int
+_lib.crf_last_beam_kernel.restype = ctypes.c_char_p
 _lib.crf_profile_enable.argtypes = [ctypes.c_int]
 _lib.crf_profile_enable.restype = None
 _lib.crf_profile_read.argtypes = [ctypes.POINTER(_f32), ctypes.c_int]
@@ -109,7 +115,7 @@ _lib.crf_build_switches.restype = ctypes.c_char_p
 
 EXPORTED_SYMBOLS = (
     "crf_graph_create", "crf_graph_create_from_arcs", "crf_graph_destroy", "crf_graph_dims", "crf_graph_stats",
-    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_ws_fields", "crf_debug_ws_field_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_ctc_score", "crf_ctc_score_logits_workspace_bytes", "crf_ctc_score_logits", "crf_last_score_kernel", "crf_ctc_score_grad_workspace_bytes", "crf_ctc_score_grad", "crf_ctc_score_grad_logits_workspace_bytes", "crf_ctc_score_grad_logits", "crf_last_score_grad_kernel", "crf_ctc_sample_workspace_bytes", "crf_ctc_sample", "crf_last_sample_kernel", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
+    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_ws_fields", "crf_debug_ws_field_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_ctc_score", "crf_ctc_score_logits_workspace_bytes", "crf_ctc_score_logits", "crf_last_score_kernel", "crf_ctc_score_grad_workspace_bytes", "crf_ctc_score_grad", "crf_ctc_score_grad_logits_workspace_bytes", "crf_ctc_score_grad_logits", "crf_last_score_grad_kernel", "crf_ctc_sample_workspace_bytes", "crf_ctc_sample", "crf_last_sample_kernel", "crf_ctc_beam_workspace_bytes", "crf_ctc_beam", "crf_last_beam_kernel", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
     "crf_debug_set", "crf_debug_unset", "crf_debug_list", "crf_last_den_kernel", "crf_last_call_streams", "crf_last_side_stream", "crf_last_fallback_counts", "crf_build_switches", "crf_last_error", "crf_version",
 )
 
@@ -147,6 +153,11 @@ def last_score_grad_kernel() -> str:
 def last_sample_kernel() -> str:
     """Template instantiation of the row kernel of this thread's last ctc_sample call (include/ctc_crf_hip.h crf_last_sample_kernel)."""
     return _lib.crf_last_sample_kernel().decode()
+
+
+def last_beam_kernel() -> str:
+    """Template instantiation of the row kernel of this thread's last ctc_beam_search call (include/ctc_crf_hip.h crf_last_beam_kernel)."""
+    return _lib.crf_last_beam_kernel().decode()
 
 
 def last_call_streams() -> int:
@@ -906,6 +917,72 @@ def _check_sample_args(shape, lx: torch.Tensor, n_samples: int, seed: int, offse
     if N > 0 and int(lx32.max()) > T:
         raise RuntimeError(f"frame lengths must lie in [0, T={T}], got max {int(lx32.max())}")
     return N, T, V
+
+
+BEAM_MAX_WIDTH = 64          # widest beam and most classes per frame crf_ctc_beam takes (one lane each; include/ctc_crf_hip.h)
+BEAM_MAX_CLASSES = 64
+
+
+def _check_beam_args(shape, lx: torch.Tensor, beam_size: int, nbest: int, top_classes: int, blank: int, time_major: bool):
+    """The host checks of ctc_beam_search, each with the offending value in the message.  -> (N, T, V)."""
+    who = "ctc_beam_search"
+    N, T, V = shape
+    if time_major:
+        T, N = N, T
+    if not 0 <= blank < V:
+        raise RuntimeError(f"blank must lie in [0, V-1={V - 1}], got {blank}")
+    if not 1 <= int(beam_size) <= BEAM_MAX_WIDTH:
+        raise RuntimeError(f"{who}: beam_size must lie in [1, {BEAM_MAX_WIDTH}], got {beam_size}")
+    if not 1 <= int(nbest) <= int(beam_size):
+        raise RuntimeError(f"{who}: nbest must lie in [1, beam_size={beam_size}], got {nbest}")
+    if not 1 <= int(top_classes) <= BEAM_MAX_CLASSES:
+        raise RuntimeError(f"{who}: top_classes must lie in [1, {BEAM_MAX_CLASSES}], got {top_classes}")
+    if lx.is_cuda:
+        raise RuntimeError(f"{who}: input_lengths is a CPU tensor")
+    lx32 = lx.to(torch.int32).reshape(-1)
+    if lx32.numel() != N:
+        raise RuntimeError(f"{who}: expect {N} input lengths, got {lx32.numel()}")
+    if N > 0 and int(lx32.max()) > T:
+        raise RuntimeError(f"frame lengths must lie in [0, T={T}], got max {int(lx32.max())}")
+    return N, T, V
+
+
+def ctc_beam_search(log_probs: torch.Tensor, lx: torch.Tensor, beam_size: int = 16, nbest: int = 1, top_classes: int = 40, blank: int = 0,
+                    time_major: bool = False, fused: bool = False, return_trace: bool = False):
+    """CTC prefix beam search on the GPU (include/ctc_crf_hip.h ``crf_ctc_beam``): the nbest best label sequences of every utterance among
+    a beam of beam_size prefixes, per frame the blank and the top_classes classes of largest value.
+
+    log_probs [N,T,V] (time_major: [T,N,V]) f32 / bf16 / f16 on the GPU, contiguous, read in place: log-probs, or with fused the RAW
+    network output (log_softmax of the upcast values inside the call); lx an int tensor on the CPU.  Returns (hyps [N nbest, T] int32,
+    padded with the blank's index; hyp_lengths [N nbest] int32; scores [N nbest] f32, -inf for a missing rank; trace [N, T, beam_size]
+    int32 or None), all on the device, no host synchronisation."""
+    who = "ctc_beam_search"
+    if log_probs.dtype not in _FUSED_DTYPES:
+        raise RuntimeError(f"{who}: expect float32, bfloat16 or float16 activations, got {log_probs.dtype}")
+    if log_probs.dim() != 3:
+        raise RuntimeError(f"{who}: expect (N, T, V) or (T, N, V) activations, got {log_probs.dim()} dimensions")
+    N, T, V = _check_beam_args(log_probs.shape, lx, beam_size, nbest, top_classes, blank, time_major)
+    if not log_probs.is_cuda:                  # (after the checks of the arguments: those need no device)
+        raise RuntimeError(f"{who}: log_probs must be on the GPU (there is no CPU path)")
+    assert log_probs.is_contiguous()
+    W, K, C = int(beam_size), int(nbest), int(top_classes)
+    dev = log_probs.device
+    lx_d = _h2d_async(lx.to(torch.int32).reshape(-1), dev)
+    H = N * K
+    ws_bytes = _lib.crf_ctc_beam_workspace_bytes(N, T, V, W, C)
+    ws = _new_ws(ws_bytes, dev)
+    hyps = torch.empty((H, T), dtype=torch.int32, device=dev)
+    hyp_len = torch.empty(H, dtype=torch.int32, device=dev)
+    scores = torch.empty(H, dtype=torch.float32, device=dev)
+    trace = torch.empty((N, T, W), dtype=torch.int32, device=dev) if return_trace else None
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        rc = _lib.crf_ctc_beam(_ptr(log_probs), _FUSED_DTYPES[log_probs.dtype], 1 if time_major else 0, int(blank), 1 if fused else 0,
+                               _ptr(lx_d), N, T, V, W, K, C, _ptr(hyps), _ptr(hyp_len), _ptr(scores), _ptr(trace), _ptr(ws), ws_bytes,
+                               _vp(stream))
+    _check(rc)
+    del lx_d
+    return hyps, hyp_len, scores, trace
 
 
 def gpu_den(logits: torch.Tensor, grad_net: torch.Tensor, input_lengths: torch.Tensor,

@@ -18,6 +18,9 @@ Same names, arguments and error behaviour as the reference:
                                                               -> (hyps IntTensor[N*K, T], hyp_lengths IntTensor[N*K], hyp_utt IntTensor[N*K])
                                                                                          (K label sequences per utterance drawn on the GPU)
   ctc_greedy(log_probs, input_lengths, blank=0, time_major=False) -> (hyps IntTensor[N, T], hyp_lengths IntTensor[N])   (best path)
+  ctc_beam_search(log_probs, input_lengths, beam_size=16, nbest=1, top_classes=40, blank=0, time_major=False, fuse_log_softmax=False,
+                  return_trace=False) -> (hyps IntTensor[N*nbest, T], hyp_lengths IntTensor[N*nbest], hyp_utt IntTensor[N*nbest],
+                                          scores FloatTensor[N*nbest])                   (prefix beam search, LM-free: the N-best lists)
 plus the functional form named by BASELINE.json:
   ctc_crf_loss(log_probs, labels, frame_lens, label_lens, den_lm, lamb=0.1, size_average=True)
 
@@ -400,6 +403,37 @@ def ctc_greedy(log_probs: torch.Tensor, input_lengths: torch.Tensor, blank: int 
         hyps, hyp_lengths, _ = core.ctc_sample(log_probs.detach().contiguous(), input_lengths, 1, 0, 0, int(blank), bool(time_major),
                                                greedy=True)
     return hyps, hyp_lengths
+
+
+def ctc_beam_search(log_probs: torch.Tensor, input_lengths: torch.Tensor, beam_size: int = 16, nbest: int = 1, top_classes: int = 40,
+                    blank: int = 0, time_major: bool = False, fuse_log_softmax: bool = False, return_trace: bool = False):
+    """CTC prefix beam search on the GPU, LM-free: the N-best lists that ctc_score rescores and ctc_logp trains on -- what the callers get
+    from the third-party CPU ctcdecode.CTCBeamDecoder(beam_width=16, num_processes=6) after copying the whole (N, T, V) tensor to the host
+    (cat/ctc/train.py:273-281, train_jsa.py:467-476, decode.py:163-222), in one call without a host round trip.  No language model:
+    KenLM fusion is not covered.
+
+    log_probs: (N, T, V) on the GPU, or (T, N, V) with time_major=True; fp32, bf16 or fp16, read in place: log-probs, or with
+        fuse_log_softmax=True the RAW network output (log_softmax of the upcast values inside the call).
+    input_lengths (torch.IntTensor): (N,), on the CPU, none above T.
+    beam_size: prefixes kept per frame, 1 .. 64.  nbest: ranks returned per utterance, 1 .. beam_size.
+    top_classes: besides the blank, only this many classes of largest value take part in a frame (1 .. 64; ctcdecode's cutoff_top_n);
+        with top_classes >= V - 1 nothing is pruned.  A repeat of the last label is pruned with its class, as ctcdecode does.
+    Prefixes are identified by their label sequence: mass that reaches a prefix of the beam along another parent is added to it.
+
+    Returns (hyps, hyp_lengths, hyp_utt, scores) and, with return_trace, trace -- tensors on log_probs' device, no host synchronisation,
+    no autograd history:
+        hyps (N nbest, T) int32: row h = n nbest + r holds the hyp_lengths[h] labels of rank r, then the BLANK's index up to T -- the rows
+            ctc_sample returns: ctc_score(log_probs, hyps.cpu(), hyp_lengths.cpu(), input_lengths, hyp_utt.cpu()) rescores them;
+        hyp_utt (N nbest,): h // nbest;
+        scores (N nbest,) fp32: log of the prefix's probability mass within the search, non-increasing in r, a lower bound of the
+            hypothesis's ctc_score; a rank the beam does not hold has length 0 and score -inf;
+        trace (N, T, beam_size) int32: after frame t, slot k: parent_slot + 64 (class + 1), class -1 for a stay; -1 for an empty slot
+            and for t >= input_lengths[n]."""
+    with torch.no_grad():
+        hyps, hyp_lengths, scores, trace = core.ctc_beam_search(log_probs.detach().contiguous(), input_lengths, beam_size, nbest, top_classes,
+                                                                int(blank), bool(time_major), bool(fuse_log_softmax), bool(return_trace))
+        hyp_utt = torch.arange(hyps.size(0), dtype=torch.int32, device=hyps.device).div_(int(nbest), rounding_mode="floor")
+    return (hyps, hyp_lengths, hyp_utt, scores, trace) if return_trace else (hyps, hyp_lengths, hyp_utt, scores)
 
 
 _CTX_CACHE: Dict[Tuple[str, int], CRFContext] = {}

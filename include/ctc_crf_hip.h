@@ -382,6 +382,48 @@ int crf_ctc_sample(const void *act_dev, int dtype, int time_major, int blank, co
                    void *workspace_dev, int64_t workspace_bytes, void *stream);
 const char *crf_last_sample_kernel(void);
 
+/* CTC prefix beam search on the GPU, LM-free (what cat/ctc/train.py:273-281, train_jsa.py:467-476 and decode.py:163-222 get from the
+ * third-party CPU ctcdecode.CTCBeamDecoder after a host round trip of the whole activations): the N-best label sequences of every
+ * utterance, as rows that go into crf_ctc_score / crf_ctc_score_grad unchanged.  The activations are read in place, [B][T][V]
+ * (time_major = 0) or [T][B][V] (1), dtype 0 = fp32, 1 = bf16, 2 = fp16, x^ = the exact fp32 upcast; normalize = 0: x = x^ are taken as
+ * log-probs, normalize = 1: x = x^ - lse_t (log_softmax; lse_t in fp32).  Any blank in [0, V); beam width W in [1, 64]; nbest in [1, W];
+ * top_classes in [1, 64], of which the call uses C = min(top_classes, V - 1).
+ *   Per frame t < lx[b]:  E_t = the C non-blank classes of largest x^, equal values to the lower index first, as a list in that order.
+ *             The blank always takes part.  With C >= V - 1 nothing is pruned: the textbook search.  (A class at -inf never yields a
+ *             candidate, in E_t or not.)
+ *   Recursion The beam starts as the empty prefix, pb = 0, pnb = -inf.  For a beam prefix l with last label e (a (+) b = log(e^a + e^b)):
+ *             stay       pb' = x[blank] + (pb (+) pnb);  pnb' = x[e] + pnb if e in E_t, else -inf (ctcdecode's rule: a repeat is pruned
+ *                        with its class);
+ *             extension  by c in E_t: pnb' = x[c] + (pb if c == e else pb (+) pnb), pb' = -inf.
+ *             Prefix identity is by LABEL SEQUENCE: if l + c is itself in the beam, the extension's mass is added into that prefix's
+ *             stay candidate (its pnb') and is no candidate of its own -- also when l left the beam and came back while l + c stayed
+ *             (the kernel keeps a 64-bit hash-chain id per prefix and its parent's id: W x W compares per frame).
+ *             A candidate's score is pb' (+) pnb'; candidates at -inf are dropped, the beam may hold fewer than W.  The W best survive
+ *             under the total order: score descending, then stay before extension, then parent slot ascending, then -- among the
+ *             extensions of one parent -- their place in E_t (equal x^: class ascending).  Slot k of the new beam is rank k.
+ *             pb and pnb are carried in fp64 (fp32 exp / log of the differences inside (+)).
+ *   hyps_dev  [B nbest][T]: row b nbest + r = the labels of rank r, then the BLANK's index up to T (crf_ctc_sample's rows).
+ *   hyp_len_dev [B nbest];  score_dev [B nbest] fp32 = pb (+) pnb after frame lx - 1.  A missing rank has length 0 and score -inf.
+ *             lx[b] <= 0: rank 0 is the empty prefix at score 0; lx[b] > T counts as T.
+ *   trace_dev (may be NULL) [B][T][W] int32: after frame t, slot k: parent_slot + 64 (class + 1), class = -1 for a stay; -1 for an empty
+ *             slot and for t >= lx[b].
+ * Every entry of hyps_dev, hyp_len_dev, score_dev and trace_dev is written by the call.  The results are the same bits across calls, in
+ * both layouts and whatever other utterances share the call.  Rows must hold neither NaN nor +inf (results unspecified; no access out of
+ * bounds whatever a row holds).  crf_last_beam_kernel() names the row kernel of this thread's last call: "crf_beam_row_kernel<f32>",
+ * "<bf16>", "<f16>".
+ * Workspace: crf_ctc_beam_workspace_bytes (the frames' blank value and E_t as (value, class) pairs, [B T][C + 1] each, and the trace
+ * words [B][T][W]; its contents on entry do not matter; -1 with crf_last_error() set for a shape not taken).  No host synchronisation,
+ * all work on `stream`, no environment variable read.
+ * CRF_ERR_ARG: null pointer (trace_dev excepted), dtype outside 0..2, normalize outside 0..1, blank outside [0, V), B, T or V <= 0, W or
+ * top_classes outside [1, 64], nbest outside [1, W], B * T > INT32_MAX; CRF_ERR_UNSUPPORTED: V > 8192 (the row stage keeps the row in
+ * LDS); CRF_ERR_WORKSPACE: workspace too small (the message names the bytes needed) -- all answered before any HIP call. */
+int64_t crf_ctc_beam_workspace_bytes(int64_t B, int64_t T, int64_t V, int64_t W, int64_t top_classes);
+int crf_ctc_beam(const void *act_dev, int dtype, int time_major, int blank, int normalize, const int32_t *lx_dev,
+                 int64_t B, int64_t T, int64_t V, int64_t W, int64_t nbest, int64_t top_classes,
+                 int32_t *hyps_dev, int32_t *hyp_len_dev, float *score_dev, int32_t *trace_dev,
+                 void *workspace_dev, int64_t workspace_bytes, void *stream);
+const char *crf_last_beam_kernel(void);
+
 /* Replaces the cudaMemcpyAsync calls that bring labels, label lengths and input lengths to the device
  * (gpu_ctc.h:143-229; `input_lengths.cuda()`, ctc_crf/__init__.py:73): copies n int32 from PINNED host
  * memory (hipHostMalloc / torch pin_memory: device-accessible) to device memory with a kernel on `stream` --
