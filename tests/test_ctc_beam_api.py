@@ -1,5 +1,6 @@
 """CPU tests (no GPU) of ctc_beam_search: the NumPy yardstick itself (tests/beam_ref.py: against brute force over all V^T labellings, a
-hand-worked case, the event counters of the GPU tests' seeded inputs, `replay` on its own trace and on a negative control), the host
+hand-worked case, the event counters of the GPU tests' seeded inputs, `replay` on its own trace and on a negative control, the planted
+rows and the exact-tie cases of the GPU tests with the conditions they must meet and the altered orders they must tell apart), the host
 checks of the Python binding (cat_amd/ctc_crf/_C.py ctc_beam_search) and the C ABI's answers before any HIP call (include/ctc_crf_hip.h
 crf_ctc_beam_workspace_bytes, crf_ctc_beam)."""
 import ctypes
@@ -115,6 +116,156 @@ def test_replay_accepts_its_own_trace_and_sees_a_missing_merge(case_runs):
     assert beam_ref.replay(x, 2, tr, 2, 2, 0)["excess"] > rp["excess"]              # (frame 1: () + a at 0.25 beats the stay of (b) at 0.15)
     tr = np.array([[0, -1], [0, -1]], dtype=np.int32)                               # a slot left empty beside finite candidates
     assert beam_ref.replay(x, 2, tr, 2, 2, 0)["excess"] == np.inf
+
+
+def test_lse32_is_the_kernels_sum():
+    """fp64 maximum and result, fp32 exp / log of the difference: within fp32 rounding of `lse`, exact where a term is -inf, symmetric."""
+    rng = np.random.default_rng(3)
+    for a, b in rng.uniform(-40, 0, (200, 2)):
+        got = beam_ref.lse32(a, b)
+        assert abs(got - beam_ref.lse(a, b)) <= 3e-7 and got == beam_ref.lse32(b, a)
+    NEG = -np.inf
+    assert beam_ref.lse32(NEG, NEG) == NEG and beam_ref.lse32(-3.25, NEG) == -3.25 and beam_ref.lse32(NEG, 0.0) == 0.0
+    assert beam_ref.lse32(-2.0, -2.0) == -2.0 + float(np.log(np.float32(2)))
+    assert beam_ref.lse32(0.0, -200.0) == 0.0                                       # (fp32 exp underflows: the small term is lost)
+
+
+def test_through_rounds_to_the_dtype():
+    a = np.array([1.0, -0.0, 1 + 2 ** -8, 1 + 3 * 2 ** -8, 1 + 2 ** -11, -np.inf, 3.14159, -8.7654], dtype=np.float32)
+    for name, dt in (("fp32", torch.float32), ("bf16", torch.bfloat16), ("fp16", torch.float16)):
+        want = torch.tensor(a).to(dt).float().numpy()
+        assert np.array_equal(beam_ref.through(a, name).view(np.int32), want.view(np.int32)), name
+
+
+@pytest.mark.parametrize("V", [64, 129, 4096, 4097, 8191, 8192])
+def test_planted_rows_have_their_properties(V):
+    """planted_rows, read with the reference's own top_classes: (a) a row whose E_t lies in ONE column, (b) equal values at v and v + 64
+    and, beyond 4096 classes, at v and v + 4096, next to each other in E_t and the lower index first, (c) E_t on both sides of 4096, (d) the
+    value at place C also outside E_t, at a higher index, (e) a row with fewer than C classes above -inf, (f) a row with -0.0 and +0.0 on
+    top, in index order, (g) the blank far below in some rows and on top in another -- each wherever the shape leaves room for it: a
+    column of V holds V / 64 classes, V = 4097 has one class beyond 4096 (none with the blank there), C >= V - 1 leaves no class out."""
+    for dtype in ("fp32", "bf16", "fp16"):
+        for C in (8, 64):
+            for blank in (0, V - 1):
+                Ce = min(C, V - 1)
+                rows = dict(beam_ref.planted_rows(V, dtype, blank, C))
+                assert list(rows) == ["column", "spread", "sparse", "zeros"] and set(beam_ref.PLANTED_LOGPROB_ONLY) == {"zeros"}
+                what = (V, dtype, C, blank)
+                for name, row in rows.items():
+                    assert row.dtype == np.float32 and row.shape == (V,) and not np.isnan(row).any() and row.max() <= 0, (what, name)
+                    assert np.array_equal(beam_ref.through(row, dtype).view(np.int32), row.view(np.int32)), (what, name)
+                E = {name: beam_ref.top_classes(row, blank, Ce) for name, row in rows.items()}
+                pairs = lambda name, step: [(a, b) for a, b in zip(E[name], E[name][1:]) if b == a + step and rows[name][a] == rows[name][b]]
+                # (a), (b), (c): the column row
+                room = len([v for v in range(E["column"][0] & 63, V, 64) if v != blank])
+                if room >= Ce:
+                    assert len({v & 63 for v in E["column"]}) == 1, what
+                if room >= 3:
+                    assert pairs("column", 64), what
+                if V >= 8191:
+                    assert min(len(pairs("column", 4096)), len(pairs("column", 64))) >= (1 if C == 8 else 8), what
+                    assert min(E["column"]) < 4096 <= max(E["column"]), what
+                # (c), (d), (g): the spread row
+                if max(v for v in range(V) if v != blank) >= 4096:
+                    assert min(E["spread"]) < 4096 <= max(E["spread"]), what
+                    assert V == 4097 or sum(v >= 4096 for v in E["spread"]) >= Ce // 4, what
+                if Ce < V - 1:
+                    for name in ("spread",) + (("column",) if room >= Ce + 1 else ()):
+                        full = beam_ref.top_classes(rows[name], blank, V - 1)
+                        assert rows[name][full[Ce]] == rows[name][full[Ce - 1]] and full[Ce] > full[Ce - 1], (what, name)
+                assert rows["spread"][blank] > np.delete(rows["spread"], blank).max(), what
+                for name in ("column", "sparse", "zeros"):
+                    finite = np.delete(rows[name], blank)
+                    assert rows[name][blank] == -30 and rows[name][blank] < finite[np.isfinite(finite)].min() - 20, (what, name)
+                # (e)
+                finite = np.isfinite(np.delete(rows["sparse"], blank)).sum()
+                assert 1 <= finite < Ce and np.isneginf(rows["sparse"]).sum() == V - 1 - finite, what
+                assert np.isfinite(rows["sparse"][E["sparse"][:finite]]).all() and (V < 129 or pairs("sparse", 64)), what
+                # (f)
+                zeros = [v for v in range(V) if rows["zeros"][v] == 0]
+                assert len(zeros) == (4 if V >= 8191 else 3) and E["zeros"][:len(zeros)] == zeros, what
+                sign = [bool(np.signbit(rows["zeros"][v])) for v in zeros]
+                assert sign == [True, False, True, False][:len(zeros)] and (zeros[0] + 64 in zeros or V == 64), what
+                assert len({v & 63 for v in zeros}) >= 2 and (V < 8191 or zeros[0] + 4096 in zeros), what
+
+
+def test_grouped_inputs_share_one_value_per_group():
+    for seed, V, W, C, T, blank, groups in beam_ref.TIE_CASES:
+        x = beam_ref.grouped_inputs(seed, T, V, blank, groups)
+        assert x.dtype == np.float32 and x.shape == (T, V) and x.max() <= -0.3 + 1e-6 and x.min() >= -3.3 - 1e-6
+        assert np.array_equal(x, beam_ref.grouped_inputs(seed, T, V, blank, groups))
+        part = {}
+        for v in range(V):
+            if v != blank:
+                part.setdefault(tuple(x[:, v]), []).append(v)
+        assert len(part) <= groups and sum(len(p) for p in part.values()) == V - 1
+        for t in range(T):
+            shared = any(x[t, blank] == x[t, v] for v in range(V) if v != blank)
+            assert shared == (t % 2 == 0), (seed, V, t)
+            assert len(set(x[t])) == min(groups, V) + (t % 2), (seed, V, t)
+
+
+def test_audit_ties_hand_worked():
+    """One frame, probabilities (0.5, 0.25, 0.25), W = 2, C = 2: the stay of () at 0.5, then () + 1 and () + 2 level at 0.25 -- two places
+    of one parent, ranks W - 1 and W; the one pair that is not level differs by log 2 / |log 0.25| = 0.5.  With the blank at 0.25 too the
+    stay is level with both extensions: one more pair, a stay beside an extension."""
+    a = beam_ref.audit_ties(np.log([[0.5, 0.25, 0.25]]), 1, 2, 2, 0)
+    assert a == dict(gap=0.5, stay_ext=0, slot=0, place=1, cut=1)
+    a = beam_ref.audit_ties(np.log([[0.25, 0.25, 0.25]]), 1, 2, 2, 0)
+    assert a == dict(gap=np.inf, stay_ext=1, slot=0, place=1, cut=1)
+    # two frames, W = 3.  Frame 0 as above (its level pair is ranks 1 and 2: not on the cut).  Frame 1, (0.25, 0.5, 0.5): the stays of (1)
+    # and (2) level at 0.4375 (two slots), then the stay of () at 0.25 * 0.5 level with (1) + 2 at 0.5 * 0.25 -- the same two addends in
+    # the log domain -- a stay beside an extension, ranks W - 1 and W
+    x = np.log([[0.5, 0.25, 0.25], [0.25, 0.5, 0.5]])
+    a = beam_ref.audit_ties(x, 2, 3, 2, 0)
+    r = beam_ref.search(x, 2, 3, 3, 2, 0)
+    assert [p for p, _ in r["nbest"]] == [(1,), (2,), ()] and np.allclose(np.exp([s for _, s in r["nbest"]]), [0.4375, 0.4375, 0.125])
+    assert (a["slot"], a["place"], a["stay_ext"], a["cut"]) == (1, 1, 1, 1) and a["gap"] == 0.5
+
+
+# the total order with one rule altered: what a kernel that mis-writes that rule would compute
+def _own_label(c):
+    return c["kind"] == 1 and len(c["prefix"]) >= 2 and c["prefix"][-2] == c["cls"]
+
+
+ALTERED_ORDERS = {
+    "an extension of a lower slot before a stay": lambda c: (-c["score"], c["parent"], c["kind"], c["place"]),
+    "the highest slot first": lambda c: (-c["score"], c["kind"], -c["parent"], c["place"]),
+    "the extension by the own last label first": lambda c: (-c["score"], c["kind"], c["parent"], -1 if _own_label(c) else c["place"]),
+    "the extension by the own last label last": lambda c: (-c["score"], c["kind"], c["parent"], 99 if _own_label(c) else c["place"]),
+    "places descending": lambda c: (-c["score"], c["kind"], c["parent"], -c["place"]),
+}
+
+
+def test_tie_cases_meet_their_conditions():
+    """TIE_CASES as the GPU test needs them: W in {2, 4, 8, 16, 64}, W = C = 64 at V = 70, blanks first, last and between, T <= 12; every
+    count of audit_ties >= 1, the one on the cut included; the smallest gap that is no tie >= 1e-3 relative (10 x the rtol of a kernel
+    score); one trace in both arithmetics at every lx the GPU test takes; and every altered order changes the trace of some case."""
+    cases = beam_ref.TIE_CASES
+    assert len(cases) >= 5 and {c[2] for c in cases} >= {2, 4, 8, 16, 64} and any(c[1:4] == (70, 64, 64) for c in cases)
+    assert any(c[5] == 0 for c in cases) and any(c[5] == c[1] - 1 for c in cases) and any(0 < c[5] < c[1] - 1 for c in cases)
+    bites = {name: 0 for name in ALTERED_ORDERS}
+    for case in cases:
+        seed, V, W, C, T, blank, groups = case
+        assert T <= 12 and groups >= 2
+        x = beam_ref.grouped_inputs(seed, T, V, blank, groups)
+        a = beam_ref.audit_ties(x, T, W, C, blank)
+        print(case, a)
+        assert min(a["stay_ext"], a["slot"], a["place"], a["cut"]) >= 1, (case, a)
+        assert a["gap"] >= 1e-3, (case, a)
+        for lx in (T, T - 1, 1):
+            r = beam_ref.search(x, lx, W, W, C, blank)
+            r32 = beam_ref.search(x, lx, W, W, C, blank, lse=beam_ref.lse32)
+            assert np.array_equal(r["trace"], r32["trace"]) and [p for p, _ in r["nbest"]] == [p for p, _ in r32["nbest"]], (case, lx)
+            assert np.allclose([s for _, s in r["nbest"]], [s for _, s in r32["nbest"]], rtol=1e-6, atol=0)
+            assert beam_ref.replay(x, lx, r["trace"], W, C, blank)["excess"] == 0
+            for name, key in ALTERED_ORDERS.items():
+                bad = beam_ref.search(x, lx, W, W, C, blank, key=key)
+                if not np.array_equal(bad["trace"], r["trace"]):
+                    bites[name] += 1
+                    assert beam_ref.replay(x, lx, bad["trace"], W, C, blank)["excess"] == 0     # (replay cannot tell: only equality can)
+    print(bites)
+    assert all(n >= 2 for n in bites.values()), bites
 
 
 def test_symbols_exported_and_surface(core):

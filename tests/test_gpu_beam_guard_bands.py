@@ -1,7 +1,8 @@
 """GPU test: crf_ctc_beam through the C ABI on buffers carved from a guard-banded arena (tests/guard.py), as
 tests/test_gpu_sample_guard_bands.py does for the sampler -- the workspace exactly as large as crf_ctc_beam_workspace_bytes says, bf16
 activations with an odd V on rows that are 2-byte aligned only, trace_dev NULL and non-NULL.  No byte outside the call's own buffers may
-change, every output word must be written, and the results equal those of the Python call on the same rows."""
+change, every output word must be written, and the results equal those of the Python call on the same rows.  Also the lengths only the
+C ABI takes: lx > T and lx < 0."""
 import ctypes
 
 import numpy as np
@@ -56,7 +57,8 @@ def run_beam(core, x, lx, W, nbest, C, blank, normalize, time_major=False, with_
     return hyps, hl, sc_bits.view(np.float32), tr
 
 
-@pytest.mark.parametrize("V,T,W,nbest,C", [(73, 65, 16, 5, 40), (301, 17, 64, 64, 64), (3, 30, 3, 2, 8)])
+# (4096: the row stage's launch with four rows and 64 KiB of LDS per workgroup; 8191: an odd wide V, one row per workgroup)
+@pytest.mark.parametrize("V,T,W,nbest,C", [(73, 65, 16, 5, 40), (301, 17, 64, 64, 64), (3, 30, 3, 2, 8), (4096, 5, 16, 4, 64), (8191, 5, 64, 64, 40)])
 @pytest.mark.parametrize("time_major", [False, True])
 def test_beam_writes_only_its_own_memory(core, V, T, W, nbest, C, time_major):
     B, blank = 3, V - 1
@@ -79,3 +81,29 @@ def test_beam_writes_only_its_own_memory(core, V, T, W, nbest, C, time_major):
                         want = pre[r] or ()
                         assert hl[b * nbest + r] == len(want) and tuple(hyps[b * nbest + r, :len(want)]) == want
                         assert (hyps[b * nbest + r, len(want):] == blank).all()
+
+
+@pytest.mark.parametrize("normalize", [False, True])
+@pytest.mark.parametrize("time_major", [False, True])
+def test_lengths_outside_0_T(core, time_major, normalize):
+    """lx[b] > T counts as T and lx[b] <= 0 as 0 (include/ctc_crf_hip.h) -- lengths the Python call refuses, so only the C ABI can bring
+    them: lx = (T + 5, -3, T) on three utterances of which the last repeats the first.  The first equals the last and equals itself at
+    lx = T bit for bit, the second is the empty prefix at score 0 with every trace word -1, and no byte outside the buffers changes."""
+    B, T, V, W, nbest, C, blank = 3, 9, 73, 8, 4, 40, 72
+    rng = np.random.default_rng(11)
+    x = torch.tensor((2.0 * rng.standard_normal((B, T, V))).astype(np.float32)).to(torch.bfloat16)
+    x[2] = x[0]
+    xin = x.transpose(0, 1).contiguous() if time_major else x
+    hyps, hl, sc, tr = run_beam(core, xin, [T + 5, -3, T], W, nbest, C, blank, normalize, time_major, with_trace=True, misalign=2)
+    base = run_beam(core, xin, [T, 0, T], W, nbest, C, blank, normalize, time_major, with_trace=True, misalign=2)
+    for got, want in zip((hyps, hl, sc, tr), base):
+        assert np.array_equal(got.view(np.int32), want.view(np.int32))
+    hyps, hl, sc = hyps.reshape(B, nbest, T), hl.reshape(B, nbest), sc.reshape(B, nbest)
+    for a in (hyps, hl, sc.view(np.int32), tr):
+        assert np.array_equal(a[0], a[2])
+    assert (tr[0] >= 0).any(axis=1).all() and hl[0].max() > 0 and np.isfinite(sc[0]).all()      # (all T frames of the first were searched)
+    assert (tr[1] == -1).all() and (hl[1] == 0).all() and (hyps[1] == blank).all()
+    assert sc[1, 0] == 0.0 and (sc[1, 1:] == -np.inf).all()
+    nt = run_beam(core, xin, [T + 5, -3, T], W, nbest, C, blank, normalize, time_major, with_trace=False, misalign=2)
+    assert np.array_equal(nt[0].reshape(B, nbest, T), hyps) and np.array_equal(nt[1].reshape(B, nbest), hl)
+    assert np.array_equal(nt[2].view(np.int32).reshape(B, nbest), sc.view(np.int32))
