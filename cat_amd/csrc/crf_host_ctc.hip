@@ -1,7 +1,8 @@
 // cat_amd/csrc/crf_host_ctc.hip -- the host side of the surfaces on the plain CTC lattice, which share nothing with the loss call
 // (crf_host.hip) but crf_host_util.h: forced alignment (crf_ctc_align*, k_align.hip), hypothesis scores (crf_ctc_score*, k_score.hip), their
-// weighted gradient (crf_ctc_score_grad*, k_score_grad.hip), sampled / best-path label sequences (crf_ctc_sample, k_sample.hip) and the
-// prefix beam search (crf_ctc_beam, k_beam.hip) --
+// weighted gradient (crf_ctc_score_grad*, k_score_grad.hip), sampled / best-path label sequences (crf_ctc_sample, k_sample.hip), the
+// prefix beam search (crf_ctc_beam, k_beam.hip) and -- on token sequences alone, no lattice -- the edit distance of hypotheses to
+// their transcripts (crf_ctc_edit_distance, k_edit.hip) --
 // argument checks, workspace sections, kernel choice, the C-ABI entry points of include/ctc_crf_hip.h.  Every error is answered before
 // any HIP call.  The activations are read in place in either layout and -- the *_logits entry points and crf_ctc_sample -- in f32, bf16
 // or f16.
@@ -15,6 +16,7 @@ namespace crf {
 
 static thread_local const char *g_sample_kernel = ""; // template instantiation of the row kernel of this thread's last crf_ctc_sample (crf_last_sample_kernel)
 static thread_local const char *g_beam_kernel = "";   // ... of the row kernel of this thread's last crf_ctc_beam (crf_last_beam_kernel)
+static thread_local const char *g_edit_kernel = "";   // ... of the kernel of this thread's last crf_ctc_edit_distance (crf_last_edit_kernel)
 static thread_local const char *g_score_kernel = "";// ... of the kernel of this thread's last crf_ctc_score / crf_ctc_score_logits (crf_last_score_kernel)
 static thread_local const char *g_score_grad_kernel = "";   // ... of the alpha pass of this thread's last crf_ctc_score_grad / crf_ctc_score_grad_logits (crf_last_score_grad_kernel)
 
@@ -295,6 +297,20 @@ static int launch_beam(const BeamParams &p, hipStream_t st) {
     return launch<crf_beam_search_kernel>("crf_beam_search_kernel", dim3((unsigned)p.B), dim3(64), 0, st, p);
 }
 
+// ---- edit distance (k_edit.hip) ----
+// references of up to kEditStripRows tokens: one wave per hypothesis with the rows in registers, kEditWaves of them per workgroup, rows
+// per lane from the call's longest reference; beyond: strips, one wave per workgroup and a cell per hypothesis column in dynamic LDS
+static int launch_edit(const EditParams &p, hipStream_t st) {
+    static const char *const names[] = {"crf_ctc_edit_kernel<1>", "crf_ctc_edit_kernel<2>", "crf_ctc_edit_kernel<4>", "crf_ctc_edit_kernel<8>"};
+    if (p.max_ref > kEditStripRows)
+        return launch<crf_ctc_edit_kernel<8, true>>(g_edit_kernel = "crf_ctc_edit_kernel<8, strips>", dim3((unsigned)p.H), dim3(64),
+                                                    (size_t)p.stride * sizeof(int2), st, p);
+    return with_nr(p.max_ref, 64, [&](auto nr, int k) {
+        return launch<crf_ctc_edit_kernel<decltype(nr)::value, false>>(g_edit_kernel = names[k], dim3((unsigned)((p.H + kEditWaves - 1) / kEditWaves)),
+                                                                       dim3(kEditWaves * 64), 0, st, p);
+    });
+}
+
 }  // namespace crf
 
 using namespace crf;
@@ -416,6 +432,29 @@ int crf_ctc_beam(const void *act, int dtype, int time_major, int blank, int norm
     return with_dtype(dtype, [&](auto e) { return launch_beam<decltype(e)>(p, (hipStream_t)stream_); });
 }
 
+int crf_ctc_edit_distance(const int32_t *hyps, int64_t hyp_stride, const int32_t *hyp_len, const int32_t *hyp_utt, const int32_t *refs,
+                          const int32_t *ref_off, const int32_t *ref_len, int64_t B, int64_t H, int64_t max_ref_len, int32_t *dist,
+                          int32_t *ops, void *stream_) {
+    const char *who = "crf_ctc_edit_distance";
+    if (!hyps || !hyp_len || !hyp_utt || !refs || !ref_off || !ref_len || !dist) { set_error(std::string(who) + ": null argument"); return CRF_ERR_ARG; }
+    if (B <= 0 || B > INT32_MAX || H <= 0 || H > INT32_MAX || hyp_stride <= 0 || hyp_stride > INT32_MAX || max_ref_len < 0) {
+        set_error(std::string(who) + ": bad B/H/hyp_stride/max_ref_len"); return CRF_ERR_ARG;
+    }
+    if (H * hyp_stride > INT32_MAX) { set_error(std::string(who) + ": H * hyp_stride > INT32_MAX"); return CRF_ERR_ARG; }
+    if (max_ref_len > kMaxCtcLabelLen) { set_error("reference length > " + std::to_string(kMaxCtcLabelLen) + " not supported by this build"); return CRF_ERR_UNSUPPORTED; }
+    if (max_ref_len > kEditStripRows && hyp_stride > kEditStripMaxCols) {
+        set_error(std::string(who) + ": hyp_stride " + std::to_string(hyp_stride) + " > " + std::to_string(kEditStripMaxCols) + " with references of more than " +
+                  std::to_string(kEditStripRows) + " tokens not supported by this build");
+        return CRF_ERR_UNSUPPORTED;
+    }
+    EditParams p{};
+    p.hyps = hyps; p.hyp_len = hyp_len; p.hyp_utt = hyp_utt; p.refs = refs; p.ref_off = ref_off; p.ref_len = ref_len;
+    p.B = (int)B; p.H = (int)H; p.stride = (int)hyp_stride; p.max_ref = (int)max_ref_len;
+    p.dist = dist; p.ops = ops;
+    return launch_edit(p, (hipStream_t)stream_);
+}
+
+const char *crf_last_edit_kernel(void) { return g_edit_kernel; }
 const char *crf_last_beam_kernel(void) { return g_beam_kernel; }
 const char *crf_last_score_kernel(void) { return g_score_kernel; }
 const char *crf_last_score_grad_kernel(void) { return g_score_grad_kernel; }

@@ -133,8 +133,25 @@ struct BeamParams {
 template <typename E> __global__ void crf_beam_row_kernel(BeamParams p);
 __global__ void crf_beam_search_kernel(BeamParams p);   // one wave (workgroup) per utterance
 
+// ---- k_edit.hip ----
+constexpr int kEditWaves = 4;             // hypotheses (waves) per workgroup of the register geometry
+constexpr int kEditStripRows = 512;       // reference rows one wave holds (64 lanes x 8): longer references are walked in strips of this many
+constexpr int kEditStripMaxCols = 8192;   // the strip path keeps one (cost, counts) pair per hypothesis column in LDS: 64 KiB at most
+// Kernel arguments of crf_ctc_edit_distance: hypothesis h is the first hyp_len[h] entries of row h of hyps (rows `stride` entries apart),
+// its reference refs[ref_off[u] .. + ref_len[u]) with u = hyp_utt[h]
+struct EditParams {
+    const int *hyps, *hyp_len, *hyp_utt;
+    const int *refs, *ref_off, *ref_len;
+    int B, H, stride, max_ref;
+    int *dist;                  // [H]
+    int *ops;                   // [H][3] (nsub, ndel, nins) or null
+};
+// NR reference rows per lane: 1, 2, 4, 8.  STRIP (NR = 8 only): one wave per workgroup, references of more than kEditStripRows rows in
+// strips; dynamic LDS: stride x 8 bytes.
+template <int NR, bool STRIP> __global__ void crf_ctc_edit_kernel(EditParams p);
+
 // ---- k_res.hip ----
-constexpr int kEpRegsR = 2;   // emission-row prefetch registers (V <= 2*512 for the resident kernels)
+constexpr int kEpRegsR = 2;  // emission-row prefetch registers (V <= 2*512 for the resident kernels)
 constexpr int kPoll = 4;      // granules polled concurrently per thread
 constexpr int kResBatch = 6;   // measured: 5 -> 6 = -2% (fewer, longer straight-line blocks); 10 spills
 static_assert(kResNCH % kResBatch == 0, "kResNCH must be a multiple of kResBatch");

@@ -91,6 +91,9 @@ _lib.crf_ctc_beam.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, cty
                               _vp, _vp, _vp, _vp, _vp, _i64, _vp]
 _lib.crf_ctc_beam.restype = ctypes.c_int
 _lib.crf_last_beam_kernel.restype = ctypes.c_char_p
+_lib.crf_ctc_edit_distance.argtypes = [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]
+_lib.crf_ctc_edit_distance.restype = ctypes.c_int
+_lib.crf_last_edit_kernel.restype = ctypes.c_char_p
 _lib.crf_profile_enable.argtypes = [ctypes.c_int]
 _lib.crf_profile_enable.restype = None
 _lib.crf_profile_read.argtypes = [ctypes.POINTER(_f32), ctypes.c_int]
@@ -115,7 +118,7 @@ _lib.crf_build_switches.restype = ctypes.c_char_p
 
 EXPORTED_SYMBOLS = (
     "crf_graph_create", "crf_graph_create_from_arcs", "crf_graph_destroy", "crf_graph_dims", "crf_graph_stats",
-    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_ws_fields", "crf_debug_ws_field_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_ctc_score", "crf_ctc_score_logits_workspace_bytes", "crf_ctc_score_logits", "crf_last_score_kernel", "crf_ctc_score_grad_workspace_bytes", "crf_ctc_score_grad", "crf_ctc_score_grad_logits_workspace_bytes", "crf_ctc_score_grad_logits", "crf_last_score_grad_kernel", "crf_ctc_sample_workspace_bytes", "crf_ctc_sample", "crf_last_sample_kernel", "crf_ctc_beam_workspace_bytes", "crf_ctc_beam", "crf_last_beam_kernel", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
+    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_ws_fields", "crf_debug_ws_field_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_ctc_score", "crf_ctc_score_logits_workspace_bytes", "crf_ctc_score_logits", "crf_last_score_kernel", "crf_ctc_score_grad_workspace_bytes", "crf_ctc_score_grad", "crf_ctc_score_grad_logits_workspace_bytes", "crf_ctc_score_grad_logits", "crf_last_score_grad_kernel", "crf_ctc_sample_workspace_bytes", "crf_ctc_sample", "crf_last_sample_kernel", "crf_ctc_beam_workspace_bytes", "crf_ctc_beam", "crf_last_beam_kernel", "crf_ctc_edit_distance", "crf_last_edit_kernel", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
     "crf_debug_set", "crf_debug_unset", "crf_debug_list", "crf_last_den_kernel", "crf_last_call_streams", "crf_last_side_stream", "crf_last_fallback_counts", "crf_build_switches", "crf_last_error", "crf_version",
 )
 
@@ -158,6 +161,11 @@ def last_sample_kernel() -> str:
 def last_beam_kernel() -> str:
     """Template instantiation of the row kernel of this thread's last ctc_beam_search call (include/ctc_crf_hip.h crf_last_beam_kernel)."""
     return _lib.crf_last_beam_kernel().decode()
+
+
+def last_edit_kernel() -> str:
+    """Template instantiation of the kernel of this thread's last ctc_edit_distance call (include/ctc_crf_hip.h crf_last_edit_kernel)."""
+    return _lib.crf_last_edit_kernel().decode()
 
 
 def last_call_streams() -> int:
@@ -983,6 +991,94 @@ def ctc_beam_search(log_probs: torch.Tensor, lx: torch.Tensor, beam_size: int = 
     _check(rc)
     del lx_d
     return hyps, hyp_len, scores, trace
+
+
+EDIT_MAX_REF_LEN = 2047      # longest reference crf_ctc_edit_distance takes (kMaxCtcLabelLen; include/ctc_crf_hip.h)
+EDIT_STRIP_ROWS = 512        # references beyond this many tokens are walked in strips, which hold hypothesis rows of up to ...
+EDIT_STRIP_MAX_COLS = 8192   # ... this many entries
+
+
+def _check_edit_args(hyps: torch.Tensor, hyp_lengths: torch.Tensor, labels: torch.Tensor, label_lengths: torch.Tensor,
+                     hyp_utt: Optional[torch.Tensor]):
+    """The host checks of ctc_edit_distance, each with the offending value in the message; none needs a device.
+    -> (H, W, N, ly32, lab32, max_ref_len)."""
+    who = "ctc_edit_distance"
+    if hyps.dim() != 2:
+        raise RuntimeError(f"{who}: expect hyps of shape (H, W), got {hyps.dim()} dimensions")
+    H, W = hyps.shape
+    if hyps.dtype != torch.int32:
+        raise RuntimeError(f"{who}: expect int32 hyps, got {hyps.dtype}")
+    if hyp_lengths.dtype != torch.int32:
+        raise RuntimeError(f"{who}: expect int32 hyp_lengths, got {hyp_lengths.dtype}")
+    if hyp_lengths.dim() != 1 or hyp_lengths.numel() != H:
+        raise RuntimeError(f"{who}: expect hyp_lengths of shape ({H},), one per row of hyps, got {tuple(hyp_lengths.shape)}")
+    if labels.is_cuda or label_lengths.is_cuda:
+        raise RuntimeError(f"{who}: labels and label_lengths are CPU tensors")
+    if labels.is_floating_point() or label_lengths.is_floating_point():
+        raise RuntimeError(f"{who}: expect integer labels and label_lengths, got {labels.dtype} and {label_lengths.dtype}")
+    if label_lengths.dim() != 1:
+        raise RuntimeError(f"{who}: expect label_lengths of shape (N,), got {label_lengths.dim()} dimensions")
+    ly32 = label_lengths.to(torch.int32)
+    lab32 = labels.to(torch.int32).reshape(-1)
+    N = ly32.numel()
+    if N == 0:
+        raise RuntimeError(f"{who}: no utterances")
+    if int(ly32.min()) < 0:
+        raise RuntimeError("negative label length")
+    if int(ly32.sum()) > lab32.numel():
+        raise RuntimeError(f"sum(label_lengths)={int(ly32.sum())} exceeds len(labels)={lab32.numel()}")
+    max_ref = int(ly32.max())
+    if max_ref > EDIT_MAX_REF_LEN:
+        raise RuntimeError(f"{who}: label length {max_ref} > {EDIT_MAX_REF_LEN} not supported by this build")
+    if max_ref > EDIT_STRIP_ROWS and W > EDIT_STRIP_MAX_COLS:
+        raise RuntimeError(f"{who}: rows of hyps of {W} > {EDIT_STRIP_MAX_COLS} entries with references of more than {EDIT_STRIP_ROWS} "
+                           f"tokens not supported by this build")
+    if hyp_utt is None:
+        if H != N:
+            raise RuntimeError(f"{who}: hyp_utt=None takes hypothesis h against utterance h: expect {N} hypotheses, got {H}")
+    else:
+        if hyp_utt.dtype != torch.int32:
+            raise RuntimeError(f"{who}: expect int32 hyp_utt, got {hyp_utt.dtype}")
+        if hyp_utt.dim() != 1 or hyp_utt.numel() != H:
+            raise RuntimeError(f"{who}: expect hyp_utt of shape ({H},), one per row of hyps, got {tuple(hyp_utt.shape)}")
+    if H * max(W, 1) > 2 ** 31 - 1:
+        raise RuntimeError(f"{who}: H * W = {H * W} > INT32_MAX")
+    return H, W, N, ly32, lab32, max_ref
+
+
+def ctc_edit_distance(hyps: torch.Tensor, hyp_lengths: torch.Tensor, labels: torch.Tensor, label_lengths: torch.Tensor,
+                      hyp_utt: Optional[torch.Tensor] = None, return_ops: bool = False):
+    """Token edit distance of H hypotheses to their utterances' transcripts (include/ctc_crf_hip.h ``crf_ctc_edit_distance``).
+
+    hyps [H,W] int32, hyp_lengths [H] int32 and hyp_utt [H] int32 (None: H = N, hypothesis h against utterance h) on the GPU, as ctc_sample
+    / ctc_greedy / ctc_beam_search return them; labels flat and label_lengths [N] int tensors on the CPU, staged in one copy.  Returns
+    (dist [H] int32, ops [H,3] int32 = (nsub, ndel, nins) or None) on the device, no host synchronisation; a row whose hyp_utt or hyp_lengths
+    entry is out of range takes -1."""
+    who = "ctc_edit_distance"
+    H, W, N, ly32, lab32, max_ref = _check_edit_args(hyps, hyp_lengths, labels, label_lengths, hyp_utt)
+    if not hyps.is_cuda:                       # (after the checks of the arguments: those need no device)
+        raise RuntimeError(f"{who}: hyps must be on the GPU (there is no CPU path)")
+    dev = hyps.device
+    if hyp_lengths.device != dev or (hyp_utt is not None and hyp_utt.device != dev):
+        raise RuntimeError(f"{who}: hyp_lengths and hyp_utt must be on the device of hyps ({dev})")
+    dist = torch.empty(H, dtype=torch.int32, device=dev)
+    ops = torch.empty((H, 3), dtype=torch.int32, device=dev) if return_ops else None
+    if H == 0:
+        return dist, ops
+    hyps = hyps.contiguous() if W > 0 else torch.zeros((H, 1), dtype=torch.int32, device=dev)   # (no row of width 0 in the C ABI)
+    hyp_lengths = hyp_lengths.contiguous()
+    nlab = int(ly32.sum())
+    off = (torch.cumsum(ly32, 0, dtype=torch.int32) - ly32).to(torch.int32)
+    meta = _h2d_async(torch.cat([ly32, off, lab32[:nlab] if nlab else torch.zeros(1, dtype=torch.int32)]), dev)
+    len_d, off_d, lab_d = meta[:N], meta[N:2 * N], meta[2 * N:]
+    utt_d = torch.arange(N, dtype=torch.int32, device=dev) if hyp_utt is None else hyp_utt.contiguous()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        rc = _lib.crf_ctc_edit_distance(_ptr(hyps), max(W, 1), _ptr(hyp_lengths), _ptr(utt_d), _ptr(lab_d), _ptr(off_d), _ptr(len_d), N, H,
+                                        max_ref, _ptr(dist), _ptr(ops), _vp(stream))
+    _check(rc)
+    del meta
+    return dist, ops
 
 
 def gpu_den(logits: torch.Tensor, grad_net: torch.Tensor, input_lengths: torch.Tensor,

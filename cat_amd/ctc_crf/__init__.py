@@ -21,6 +21,9 @@ Same names, arguments and error behaviour as the reference:
   ctc_beam_search(log_probs, input_lengths, beam_size=16, nbest=1, top_classes=40, blank=0, time_major=False, fuse_log_softmax=False,
                   return_trace=False) -> (hyps IntTensor[N*nbest, T], hyp_lengths IntTensor[N*nbest], hyp_utt IntTensor[N*nbest],
                                           scores FloatTensor[N*nbest])                   (prefix beam search, LM-free: the N-best lists)
+  ctc_edit_distance(hyps, hyp_lengths, labels, label_lengths, hyp_utt=None, return_ops=False) -> dist IntTensor[H]
+                                                              (with return_ops: (dist, sub, dele, ins), each IntTensor[H])
+                                                                                         (token errors of hypotheses on the GPU: WER / PER sums, the MWER risk)
 plus the functional form named by BASELINE.json:
   ctc_crf_loss(log_probs, labels, frame_lens, label_lens, den_lm, lamb=0.1, size_average=True)
 
@@ -434,6 +437,34 @@ def ctc_beam_search(log_probs: torch.Tensor, input_lengths: torch.Tensor, beam_s
                                                                 int(blank), bool(time_major), bool(fuse_log_softmax), bool(return_trace))
         hyp_utt = torch.arange(hyps.size(0), dtype=torch.int32, device=hyps.device).div_(int(nbest), rounding_mode="floor")
     return (hyps, hyp_lengths, hyp_utt, scores, trace) if return_trace else (hyps, hyp_lengths, hyp_utt, scores)
+
+
+def ctc_edit_distance(hyps: torch.Tensor, hyp_lengths: torch.Tensor, labels: torch.Tensor, label_lengths: torch.Tensor,
+                      hyp_utt: torch.Tensor = None, return_ops: bool = False):
+    """Token edit distance (Levenshtein) of H hypotheses to the transcripts of their utterances, on the GPU: how wrong the rows are that
+    ctc_sample, ctc_greedy and ctc_beam_search return -- what the evaluation inside the training loop computes with a Python loop of
+    Levenshtein.distance over `.cpu().tolist()` (cat/ctc/train.py:200-210 cal_wer, train_jsa.py:371-387 cal_per), and the `risk` of
+    minimum-risk / MWER training:
+
+        hyps, hl, hu = ctc_sample(log_probs, lx, K, seed)                      # or ctc_beam_search(..., nbest=K)
+        risk = ctc_edit_distance(hyps, hl, labels, label_lengths, hu).float()
+        scores, _ = ctc_logp(log_probs, hyps.cpu(), hl.cpu(), lx, hu.cpu())
+        (torch.softmax(scores.view(N, K), -1) * risk.view(N, K)).sum().backward()
+
+    hyps (H, W) int32 on the GPU: row h holds hypothesis h in its first hyp_lengths[h] entries; what stands behind is never read.
+    hyp_lengths (H,), hyp_utt (H,) int32 on the GPU: hypothesis h belongs to utterance hyp_utt[h]; None: H == N, hypothesis h to utterance h.
+    labels, label_lengths (N,): the flattened transcripts and their lengths, int tensors on the CPU as every loss call here takes them;
+        transcripts of up to 2047 tokens (beyond 512 tokens: W <= 8192).  Tokens are compared as integers: no vocabulary, no blank.
+
+    Returns dist (H,) int32 on the device: insertions + deletions + substitutions of the cheapest alignment; with return_ops
+    (dist, sub, dele, ins), each (H,) int32: the counts of ONE optimal alignment, fixed by the rule that among predecessors of equal
+    cost the diagonal one goes before the deletion and that before the insertion, so sub + dele + ins == dist, hits = label_length -
+    sub - dele, and the counts are the same bits in any batch and order.  No autograd history, no host synchronisation.  A row whose
+    hyp_utt lies outside [0, N) or whose length lies outside [0, W] takes -1 in every output.
+    WER of a batch: ctc_edit_distance(...).sum() / label_lengths.sum() -- two sums."""
+    with torch.no_grad():
+        dist, ops = core.ctc_edit_distance(hyps.detach(), hyp_lengths, labels, label_lengths, hyp_utt, bool(return_ops))
+    return (dist, ops[:, 0], ops[:, 1], ops[:, 2]) if return_ops else dist
 
 
 _CTX_CACHE: Dict[Tuple[str, int], CRFContext] = {}

@@ -424,6 +424,37 @@ int crf_ctc_beam(const void *act_dev, int dtype, int time_major, int blank, int 
                  void *workspace_dev, int64_t workspace_bytes, void *stream);
 const char *crf_last_beam_kernel(void);
 
+/* Token edit distance of H hypotheses to the transcripts of their utterances, with the operation counts of one optimal alignment: what
+ * cat/ctc/train.py:200-210 (cal_wer), train_jsa.py:371-387 (cal_per), train_me2e.py:250-256 and train_me2e_kaldi.py:420-426 compute with
+ * a Python loop of Levenshtein.distance after `.cpu().tolist()`, and the risk of minimum-risk / MWER training, for the rows that
+ * crf_ctc_sample / crf_ctc_beam leave on the device.  Tokens are compared as int32: no vocabulary, no blank, no activations.
+ *   Hypothesis h = the first hyp_len_dev[h] entries of row h of hyps_dev, rows hyp_stride entries apart (the padded rows of
+ *             crf_ctc_sample / crf_ctc_beam); entries behind hyp_len are never read.
+ *   Reference of utterance u = hyp_utt_dev[h]: refs_dev[ref_off_dev[u] .. + ref_len_dev[u]) (the flattened labels of the loss calls).
+ *   Distance  With r the reference (length R) and y the hypothesis (length Y): D[0][j] = j, D[i][0] = i, and for i, j >= 1 the cell
+ *             takes the smallest of  diag = D[i-1][j-1] + (r_i != y_j),  del = D[i-1][j] + 1,  ins = D[i][j-1] + 1.
+ *             dist_dev[h] = D[R][Y].
+ *   Counts    ops_dev (may be NULL) [H][3] int32 = (nsub, ndel, nins).  Every cell carries the three counts; the border cells carry
+ *             (0, i, 0) and (0, 0, j); among candidates of equal cost the cell takes the FIRST in the order diag, del, ins (strict
+ *             compares in that order), inherits that predecessor's counts and adds one to the matching count (nothing for a match).
+ *             Hence nsub + ndel + nins = dist, hits = R - nsub - ndel, Y = hits + nsub + nins.
+ *   Invalid   hyp_utt[h] outside [0, B), hyp_len[h] < 0 or > hyp_stride, or ref_len[u] outside [0, max_ref_len]: dist = -1 and
+ *             ops = (-1, -1, -1); neither its row nor its reference is read.
+ * Every entry of dist_dev and ops_dev is written by the call, by a plain store (no atomics).  Integers only: a hypothesis's result
+ * depends on the two token sequences alone -- the same bits across calls, wherever it stands in the list, whatever shares the call and
+ * whichever instantiation max_ref_len selects.  crf_last_edit_kernel() names that of this thread's last call:
+ * "crf_ctc_edit_kernel<1>", "<2>", "<4>", "<8>" (max_ref_len <= 64, 128, 256, 512: one wave per hypothesis, the reference rows in
+ * registers) or "crf_ctc_edit_kernel<8, strips>" (longer references in strips of 512 rows, 8 hyp_stride bytes of LDS).
+ * max_ref_len is a host bound of ref_len_dev; the bound of the hypotheses is hyp_stride.  No workspace, no host synchronisation, all
+ * work on `stream`, no environment variable read.
+ * CRF_ERR_ARG: null pointer (ops_dev excepted), B, H or hyp_stride <= 0, max_ref_len < 0, H * hyp_stride > INT32_MAX;
+ * CRF_ERR_UNSUPPORTED: max_ref_len > 2047, or max_ref_len > 512 together with hyp_stride > 8192 (the strips keep a cell per column in
+ * LDS) -- all answered before any HIP call. */
+int crf_ctc_edit_distance(const int32_t *hyps_dev, int64_t hyp_stride, const int32_t *hyp_len_dev, const int32_t *hyp_utt_dev,
+                          const int32_t *refs_dev, const int32_t *ref_off_dev, const int32_t *ref_len_dev,
+                          int64_t B, int64_t H, int64_t max_ref_len, int32_t *dist_dev, int32_t *ops_dev, void *stream);
+const char *crf_last_edit_kernel(void);
+
 /* Replaces the cudaMemcpyAsync calls that bring labels, label lengths and input lengths to the device
  * (gpu_ctc.h:143-229; `input_lengths.cuda()`, ctc_crf/__init__.py:73): copies n int32 from PINNED host
  * memory (hipHostMalloc / torch pin_memory: device-accessible) to device memory with a kernel on `stream` --
