@@ -1,11 +1,12 @@
 // cat_amd/csrc/crf_host_ctc.hip -- the host side of the surfaces on the plain CTC lattice, which share nothing with the loss call
 // (crf_host.hip) but crf_host_util.h: forced alignment (crf_ctc_align*, k_align.hip), hypothesis scores (crf_ctc_score*, k_score.hip), their
 // weighted gradient (crf_ctc_score_grad*, k_score_grad.hip), sampled / best-path label sequences (crf_ctc_sample, k_sample.hip), the
-// prefix beam search (crf_ctc_beam, k_beam.hip) and -- on token sequences alone, no lattice -- the edit distance of hypotheses to
+// prefix beam search (crf_ctc_beam, k_beam.hip; with an n-gram LM: crf_ctc_beam_lm, k_beam_lm.hip, crf_ngram_tables_check) and -- on token sequences alone, no lattice -- the edit distance of hypotheses to
 // their transcripts (crf_ctc_edit_distance, k_edit.hip) --
 // argument checks, workspace sections, kernel choice, the C-ABI entry points of include/ctc_crf_hip.h.  Every error is answered before
 // any HIP call.  The activations are read in place in either layout and -- the *_logits entry points and crf_ctc_sample -- in f32, bf16
 // or f16.
+#include <cmath>
 #include <type_traits>
 
 #include "crf_device.h"
@@ -296,6 +297,61 @@ static int launch_beam(const BeamParams &p, hipStream_t st) {
                                                       (size_t)R * p.V * sizeof(float), st, p)) return rc;
     return launch<crf_beam_search_kernel>("crf_beam_search_kernel", dim3((unsigned)p.B), dim3(64), 0, st, p);
 }
+// the same row stage, then the fused search of k_beam_lm.hip: one workgroup of kBeamLmWaves waves per utterance
+template <typename E>
+static int launch_beam_lm(const BeamLmParams &q, hipStream_t st) {
+    static const char *const names[3] = {"crf_beam_row_kernel<f32>", "crf_beam_row_kernel<bf16>", "crf_beam_row_kernel<f16>"};
+    constexpr int ei = std::is_same<E, float>::value ? 0 : std::is_same<E, AlnBf16>::value ? 1 : 2;
+    const BeamParams &p = q.b;
+    const int64_t frames = (int64_t)p.B * p.T;
+    const int R = p.V <= kBeamRowsV ? 4 : 1;
+    if (const int rc = launch<crf_beam_row_kernel<E>>(g_beam_kernel = names[ei], dim3((unsigned)((frames + R - 1) / R)), dim3(64 * R),
+                                                      (size_t)R * p.V * sizeof(float), st, p)) return rc;
+    return launch<crf_beamlm_search_kernel>("crf_beamlm_search_kernel", dim3((unsigned)p.B), dim3(64 * kBeamLmWaves), 0, st, q);
+}
+// the argument checks of crf_ctc_beam and crf_ctc_beam_lm (lm: null for the LM-free call), then the launch; every error before any HIP call
+static int beam_call(const char *who, const void *act, int dtype, int time_major, int blank, int normalize, const int32_t *lx, int64_t B,
+                     int64_t T, int64_t V, int64_t W, int64_t nbest, int64_t top_classes, const crf_ngram_tables *lm, bool with_lm, float alpha,
+                     float beta, int32_t *hyps, int32_t *hyp_len, float *score, float *lm_score, int32_t *trace, void *ws, int64_t ws_bytes,
+                     hipStream_t st) {
+    const std::string w0 = std::string(who) + ": ";
+    if (!act || !lx || !hyps || !hyp_len || !score || !ws || (with_lm && !lm)) { set_error(w0 + "null argument"); return CRF_ERR_ARG; }
+    if (dtype < 0 || dtype > 2) return bad_dtype(who);
+    if (normalize != 0 && normalize != 1) { set_error(w0 + "normalize must be 0 or 1, got " + std::to_string(normalize)); return CRF_ERR_ARG; }
+    SideWs w;
+    const int64_t need = beam_ws_bytes(B, T, V, W, top_classes, &w);
+    if (need < 0) return (int)-need;
+    if (nbest < 1 || nbest > W) { set_error(w0 + "nbest " + std::to_string(nbest) + " outside [1, W=" + std::to_string(W) + "]"); return CRF_ERR_ARG; }
+    if (const int rc = check_blank(blank, V)) return rc;
+    if (with_lm) {
+        if (!std::isfinite(alpha) || !std::isfinite(beta)) {
+            set_error(w0 + "alpha and beta must be finite, got " + std::to_string(alpha) + " and " + std::to_string(beta)); return CRF_ERR_ARG;
+        }
+        if (lm->V != V) { set_error(w0 + "the LM's V " + std::to_string(lm->V) + " is not the activations' V " + std::to_string(V)); return CRF_ERR_ARG; }
+        if (lm->S < 1 || lm->S > INT32_MAX || lm->A < 0 || lm->A > INT32_MAX || lm->order < 1 || lm->order > kNgramMaxOrder || lm->start < 0 ||
+            lm->start >= lm->S) {
+            set_error(w0 + "bad LM tables: S " + std::to_string(lm->S) + ", A " + std::to_string(lm->A) + ", order " + std::to_string(lm->order) +
+                      ", start " + std::to_string(lm->start));
+            return CRF_ERR_ARG;
+        }
+        if (!lm->row_off || !lm->bo_state || !lm->bo_weight || !lm->uni_logp || !lm->uni_next ||
+            (lm->A > 0 && (!lm->arc_label || !lm->arc_logp || !lm->arc_next))) { set_error(w0 + "null LM table"); return CRF_ERR_ARG; }
+    }
+    if (const int rc = check_ws(ws_bytes, need)) return rc;
+    BeamLmParams q{};
+    BeamParams &p = q.b;
+    set_act(p, act, lx, B, T, V, blank, time_major);
+    p.W = (int)W; p.nbest = (int)nbest; p.C = (int)std::min(top_classes, V - 1); p.normalize = normalize;
+    p.val = (float *)((char *)ws + w.sec[kBmVal].off); p.cls = (int *)((char *)ws + w.sec[kBmCls].off);
+    p.trace = trace ? trace : (int *)((char *)ws + w.sec[kBmTrace].off); p.fill_trace = trace != nullptr;
+    p.hyps = hyps; p.hyp_len = hyp_len; p.score = score;
+    if (!with_lm) return with_dtype(dtype, [&](auto e) { return launch_beam<decltype(e)>(p, st); });
+    q.lm.row_off = lm->row_off; q.lm.arc_label = lm->arc_label; q.lm.arc_logp = lm->arc_logp; q.lm.arc_next = lm->arc_next;
+    q.lm.bo_state = lm->bo_state; q.lm.bo_weight = lm->bo_weight; q.lm.uni_logp = lm->uni_logp; q.lm.uni_next = lm->uni_next;
+    q.lm.S = (int)lm->S; q.lm.A = (int)lm->A; q.lm.V = (int)lm->V; q.lm.order = lm->order; q.lm.start = lm->start;
+    q.alpha = alpha; q.beta = beta; q.lm_score = lm_score;
+    return with_dtype(dtype, [&](auto e) { return launch_beam_lm<decltype(e)>(q, st); });
+}
 
 // ---- edit distance (k_edit.hip) ----
 // references of up to kEditStripRows tokens: one wave per hypothesis with the rows in registers, kEditWaves of them per workgroup, rows
@@ -414,22 +470,60 @@ int64_t crf_ctc_beam_workspace_bytes(int64_t B, int64_t T, int64_t V, int64_t W,
 int crf_ctc_beam(const void *act, int dtype, int time_major, int blank, int normalize, const int32_t *lx, int64_t B, int64_t T, int64_t V,
                  int64_t W, int64_t nbest, int64_t top_classes, int32_t *hyps, int32_t *hyp_len, float *score, int32_t *trace, void *ws,
                  int64_t ws_bytes, void *stream_) {
-    if (!act || !lx || !hyps || !hyp_len || !score || !ws) { set_error("crf_ctc_beam: null argument"); return CRF_ERR_ARG; }
-    if (dtype < 0 || dtype > 2) return bad_dtype("crf_ctc_beam");
-    if (normalize != 0 && normalize != 1) { set_error("crf_ctc_beam: normalize must be 0 or 1, got " + std::to_string(normalize)); return CRF_ERR_ARG; }
-    SideWs w;
-    const int64_t need = beam_ws_bytes(B, T, V, W, top_classes, &w);
-    if (need < 0) return (int)-need;
-    if (nbest < 1 || nbest > W) { set_error("crf_ctc_beam: nbest " + std::to_string(nbest) + " outside [1, W=" + std::to_string(W) + "]"); return CRF_ERR_ARG; }
-    if (const int rc = check_blank(blank, V)) return rc;
-    if (const int rc = check_ws(ws_bytes, need)) return rc;
-    BeamParams p{};
-    set_act(p, act, lx, B, T, V, blank, time_major);
-    p.W = (int)W; p.nbest = (int)nbest; p.C = (int)std::min(top_classes, V - 1); p.normalize = normalize;
-    p.val = (float *)((char *)ws + w.sec[kBmVal].off); p.cls = (int *)((char *)ws + w.sec[kBmCls].off);
-    p.trace = trace ? trace : (int *)((char *)ws + w.sec[kBmTrace].off); p.fill_trace = trace != nullptr;
-    p.hyps = hyps; p.hyp_len = hyp_len; p.score = score;
-    return with_dtype(dtype, [&](auto e) { return launch_beam<decltype(e)>(p, (hipStream_t)stream_); });
+    return beam_call("crf_ctc_beam", act, dtype, time_major, blank, normalize, lx, B, T, V, W, nbest, top_classes, nullptr, false, 0.f, 0.f, hyps,
+                     hyp_len, score, nullptr, trace, ws, ws_bytes, (hipStream_t)stream_);
+}
+
+int64_t crf_ctc_beam_lm_workspace_bytes(int64_t B, int64_t T, int64_t V, int64_t W, int64_t top_classes) {
+    return or_minus1(beam_ws_bytes(B, T, V, W, top_classes));
+}
+
+int crf_ctc_beam_lm(const void *act, int dtype, int time_major, int blank, int normalize, const int32_t *lx, int64_t B, int64_t T, int64_t V,
+                    int64_t W, int64_t nbest, int64_t top_classes, const crf_ngram_tables *lm, float alpha, float beta, int32_t *hyps,
+                    int32_t *hyp_len, float *score, float *lm_score, int32_t *trace, void *ws, int64_t ws_bytes, void *stream_) {
+    return beam_call("crf_ctc_beam_lm", act, dtype, time_major, blank, normalize, lx, B, T, V, W, nbest, top_classes, lm, true, alpha, beta, hyps,
+                     hyp_len, score, lm_score, trace, ws, ws_bytes, (hipStream_t)stream_);
+}
+
+// HOST copies of the tables, no HIP call: the first offending entry by name
+int crf_ngram_tables_check(const crf_ngram_tables *t) {
+    const std::string who = "crf_ngram_tables_check: ";
+    auto bad = [&](const std::string &m) { set_error(who + m); return CRF_ERR_ARG; };
+    auto str = [](int64_t v) { return std::to_string(v); };
+    if (!t) return bad("null argument");
+    if (t->order < 1 || t->order > kNgramMaxOrder) return bad("order " + str(t->order) + " outside [1, " + str(kNgramMaxOrder) + "]");
+    if (t->V < 1 || t->V > kBeamMaxV) return bad("V " + str(t->V) + " outside [1, " + str(kBeamMaxV) + "]");
+    if (t->S < 1 || t->S > INT32_MAX) return bad("S " + str(t->S) + " outside [1, INT32_MAX]");
+    if (t->A < 0 || t->A > INT32_MAX) return bad("A " + str(t->A) + " outside [0, INT32_MAX]");
+    if (t->start < 0 || t->start >= t->S) return bad("start " + str(t->start) + " outside [0, S=" + str(t->S) + ")");
+    if (!t->row_off || !t->bo_state || !t->bo_weight || !t->uni_logp || !t->uni_next || (t->A > 0 && (!t->arc_label || !t->arc_logp || !t->arc_next)))
+        return bad("null table");
+    const int64_t S = t->S, A = t->A, V = t->V;
+    if (t->row_off[0] != 0) return bad("row_off[0] = " + str(t->row_off[0]) + " is not 0");
+    for (int64_t s = 0; s < S; ++s)
+        if (t->row_off[s + 1] < t->row_off[s]) return bad("row_off[" + str(s + 1) + "] = " + str(t->row_off[s + 1]) + " is below row_off[" + str(s) + "] = " + str(t->row_off[s]));
+    if (t->row_off[S] != A) return bad("row_off[" + str(S) + "] = " + str(t->row_off[S]) + " is not A = " + str(A));
+    if (t->row_off[1] != 0) return bad("row_off[1] = " + str(t->row_off[1]) + ": the root's row is the dense one, its sparse row is empty");
+    for (int64_t s = 0; s < S; ++s) {
+        if (t->row_off[s + 1] - t->row_off[s] > V) return bad("row " + str(s) + " holds " + str(t->row_off[s + 1] - t->row_off[s]) + " arcs, more than V = " + str(V));
+        for (int64_t i = t->row_off[s]; i < t->row_off[s + 1]; ++i) {
+            if (t->arc_label[i] < 0 || t->arc_label[i] >= V) return bad("arc_label[" + str(i) + "] = " + str(t->arc_label[i]) + " outside [0, V=" + str(V) + ")");
+            if (i > t->row_off[s] && t->arc_label[i] <= t->arc_label[i - 1])
+                return bad("arc_label[" + str(i) + "] = " + str(t->arc_label[i]) + " does not ascend in row " + str(s) + " (arc_label[" + str(i - 1) + "] = " + str(t->arc_label[i - 1]) + ")");
+            if (t->arc_next[i] < 0 || t->arc_next[i] >= S) return bad("arc_next[" + str(i) + "] = " + str(t->arc_next[i]) + " outside [0, S=" + str(S) + ")");
+            if (!std::isfinite(t->arc_logp[i])) return bad("arc_logp[" + str(i) + "] is not finite");
+        }
+    }
+    for (int64_t s = 0; s < S; ++s) {
+        if (t->bo_state[s] < 0 || (s > 0 ? t->bo_state[s] >= s : t->bo_state[s] != 0))
+            return bad("bo_state[" + str(s) + "] = " + str(t->bo_state[s]) + " is not below its state (the root's is 0)");
+        if (!std::isfinite(t->bo_weight[s])) return bad("bo_weight[" + str(s) + "] is not finite");
+    }
+    for (int64_t c = 0; c < V; ++c) {
+        if (t->uni_next[c] < 0 || t->uni_next[c] >= S) return bad("uni_next[" + str(c) + "] = " + str(t->uni_next[c]) + " outside [0, S=" + str(S) + ")");
+        if (!std::isfinite(t->uni_logp[c])) return bad("uni_logp[" + str(c) + "] is not finite");
+    }
+    return CRF_OK;
 }
 
 int crf_ctc_edit_distance(const int32_t *hyps, int64_t hyp_stride, const int32_t *hyp_len, const int32_t *hyp_utt, const int32_t *refs,

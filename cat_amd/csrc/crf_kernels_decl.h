@@ -133,6 +133,27 @@ struct BeamParams {
 template <typename E> __global__ void crf_beam_row_kernel(BeamParams p);
 __global__ void crf_beam_search_kernel(BeamParams p);   // one wave (workgroup) per utterance
 
+// ---- k_beam_lm.hip ----
+constexpr int kBeamLmWaves = 4;           // waves per utterance of the fused search: all resolve the frame's LM lookups, the first one searches
+constexpr int kBeamLmStride = 65;         // words a row of the two LDS matrices [slot][place] takes: 64 and one of padding (bank conflicts)
+constexpr int kNgramMaxOrder = 8;         // the back-off walk takes at most this many steps
+constexpr int kNgramRowSteps = 14;        // ... and the search of a row at most this many (rows hold at most kBeamMaxV = 2^13 arcs)
+// The n-gram LM as the kernel walks it (include/ctc_crf_hip.h crf_ngram_tables; device pointers): state 0 is the empty history with a
+// dense row, every other state a sorted row of arcs, a back-off state and a back-off weight
+struct NgramDev {
+    const int *row_off, *arc_label, *arc_next, *bo_state, *uni_next;
+    const float *arc_logp, *bo_weight, *uni_logp;
+    int S, A, V, order, start;
+};
+// Kernel arguments of crf_ctc_beam_lm: the LM-free call's, the tables, the two weights and the LM part of the scores
+struct BeamLmParams {
+    BeamParams b;
+    NgramDev lm;
+    float alpha, beta;
+    float *lm_score;            // [B nbest] or null
+};
+__global__ void crf_beamlm_search_kernel(BeamLmParams p);   // kBeamLmWaves waves (one workgroup) per utterance
+
 // ---- k_edit.hip ----
 constexpr int kEditWaves = 4;             // hypotheses (waves) per workgroup of the register geometry
 constexpr int kEditStripRows = 512;       // reference rows one wave holds (64 lanes x 8): longer references are walked in strips of this many

@@ -91,6 +91,13 @@ _lib.crf_ctc_beam.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, cty
                               _vp, _vp, _vp, _vp, _vp, _i64, _vp]
 _lib.crf_ctc_beam.restype = ctypes.c_int
 _lib.crf_last_beam_kernel.restype = ctypes.c_char_p
+_lib.crf_ngram_tables_check.argtypes = [_vp]
+_lib.crf_ngram_tables_check.restype = ctypes.c_int
+_lib.crf_ctc_beam_lm_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64, _i64]
+_lib.crf_ctc_beam_lm_workspace_bytes.restype = _i64
+_lib.crf_ctc_beam_lm.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _i64, _i64, _i64, _i64, _i64, _i64,
+                                 _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]
+_lib.crf_ctc_beam_lm.restype = ctypes.c_int
 _lib.crf_ctc_edit_distance.argtypes = [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]
 _lib.crf_ctc_edit_distance.restype = ctypes.c_int
 _lib.crf_last_edit_kernel.restype = ctypes.c_char_p
@@ -118,7 +125,7 @@ _lib.crf_build_switches.restype = ctypes.c_char_p
 
 EXPORTED_SYMBOLS = (
     "crf_graph_create", "crf_graph_create_from_arcs", "crf_graph_destroy", "crf_graph_dims", "crf_graph_stats",
-    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_ws_fields", "crf_debug_ws_field_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_ctc_score", "crf_ctc_score_logits_workspace_bytes", "crf_ctc_score_logits", "crf_last_score_kernel", "crf_ctc_score_grad_workspace_bytes", "crf_ctc_score_grad", "crf_ctc_score_grad_logits_workspace_bytes", "crf_ctc_score_grad_logits", "crf_last_score_grad_kernel", "crf_ctc_sample_workspace_bytes", "crf_ctc_sample", "crf_last_sample_kernel", "crf_ctc_beam_workspace_bytes", "crf_ctc_beam", "crf_last_beam_kernel", "crf_ctc_edit_distance", "crf_last_edit_kernel", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
+    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_ws_fields", "crf_debug_ws_field_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_ctc_score", "crf_ctc_score_logits_workspace_bytes", "crf_ctc_score_logits", "crf_last_score_kernel", "crf_ctc_score_grad_workspace_bytes", "crf_ctc_score_grad", "crf_ctc_score_grad_logits_workspace_bytes", "crf_ctc_score_grad_logits", "crf_last_score_grad_kernel", "crf_ctc_sample_workspace_bytes", "crf_ctc_sample", "crf_last_sample_kernel", "crf_ctc_beam_workspace_bytes", "crf_ctc_beam", "crf_last_beam_kernel", "crf_ngram_tables_check", "crf_ctc_beam_lm_workspace_bytes", "crf_ctc_beam_lm", "crf_ctc_edit_distance", "crf_last_edit_kernel", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
     "crf_debug_set", "crf_debug_unset", "crf_debug_list", "crf_last_den_kernel", "crf_last_call_streams", "crf_last_side_stream", "crf_last_fallback_counts", "crf_build_switches", "crf_last_error", "crf_version",
 )
 
@@ -955,10 +962,34 @@ def _check_beam_args(shape, lx: torch.Tensor, beam_size: int, nbest: int, top_cl
     return N, T, V
 
 
+def _check_beam_lm_args(lm, alpha, beta, return_lm_scores, V: int):
+    """The host checks of ctc_beam_search's LM arguments, each with the offending value in the message; none needs a device."""
+    import math
+    import numbers
+    from ..ngram_lm import NgramLM
+    who = "ctc_beam_search"
+    for name, v in (("alpha", alpha), ("beta", beta)):
+        if not isinstance(v, numbers.Real) or not math.isfinite(v):
+            raise RuntimeError(f"{who}: {name} must be a finite number, got {v!r}")
+    if lm is None:
+        if alpha != 0 or beta != 0:
+            raise RuntimeError(f"{who}: alpha and beta weigh a language model: without lm they must be 0, got alpha={alpha!r}, beta={beta!r}")
+        if return_lm_scores:
+            raise RuntimeError(f"{who}: return_lm_scores needs lm")
+        return
+    if not isinstance(lm, NgramLM):
+        raise RuntimeError(f"{who}: lm must be an NgramLM (cat_amd.ngram_lm), got {type(lm).__name__}: {lm!r}")
+    if lm.vocab_size != V:
+        raise RuntimeError(f"{who}: the LM is over {lm.vocab_size} classes, the activations have V={V}")
+
+
 def ctc_beam_search(log_probs: torch.Tensor, lx: torch.Tensor, beam_size: int = 16, nbest: int = 1, top_classes: int = 40, blank: int = 0,
-                    time_major: bool = False, fused: bool = False, return_trace: bool = False):
+                    time_major: bool = False, fused: bool = False, return_trace: bool = False, lm=None, alpha: float = 0.0, beta: float = 0.0,
+                    return_lm_scores: bool = False):
     """CTC prefix beam search on the GPU (include/ctc_crf_hip.h ``crf_ctc_beam``): the nbest best label sequences of every utterance among
-    a beam of beam_size prefixes, per frame the blank and the top_classes classes of largest value.
+    a beam of beam_size prefixes, per frame the blank and the top_classes classes of largest value.  With lm (a cat_amd.ngram_lm.NgramLM)
+    the search is ``crf_ctc_beam_lm``'s: scores are fused, score + alpha log P_lm + beta length, and with return_lm_scores the LM part is
+    returned behind the trace (else None); the tables are uploaded once per device and kept.
 
     log_probs [N,T,V] (time_major: [T,N,V]) f32 / bf16 / f16 on the GPU, contiguous, read in place: log-probs, or with fused the RAW
     network output (log_softmax of the upcast values inside the call); lx an int tensor on the CPU.  Returns (hyps [N nbest, T] int32,
@@ -970,6 +1001,7 @@ def ctc_beam_search(log_probs: torch.Tensor, lx: torch.Tensor, beam_size: int = 
     if log_probs.dim() != 3:
         raise RuntimeError(f"{who}: expect (N, T, V) or (T, N, V) activations, got {log_probs.dim()} dimensions")
     N, T, V = _check_beam_args(log_probs.shape, lx, beam_size, nbest, top_classes, blank, time_major)
+    _check_beam_lm_args(lm, alpha, beta, return_lm_scores, V)
     if not log_probs.is_cuda:                  # (after the checks of the arguments: those need no device)
         raise RuntimeError(f"{who}: log_probs must be on the GPU (there is no CPU path)")
     assert log_probs.is_contiguous()
@@ -984,6 +1016,16 @@ def ctc_beam_search(log_probs: torch.Tensor, lx: torch.Tensor, beam_size: int = 
     scores = torch.empty(H, dtype=torch.float32, device=dev)
     trace = torch.empty((N, T, W), dtype=torch.int32, device=dev) if return_trace else None
     stream = torch.cuda.current_stream(dev).cuda_stream
+    if lm is not None:
+        tables, _keep = lm.tables(dev)
+        lm_scores = torch.empty(H, dtype=torch.float32, device=dev) if return_lm_scores else None
+        with torch.cuda.device(dev):
+            rc = _lib.crf_ctc_beam_lm(_ptr(log_probs), _FUSED_DTYPES[log_probs.dtype], 1 if time_major else 0, int(blank), 1 if fused else 0,
+                                      _ptr(lx_d), N, T, V, W, K, C, ctypes.byref(tables), float(alpha), float(beta), _ptr(hyps), _ptr(hyp_len),
+                                      _ptr(scores), _ptr(lm_scores), _ptr(trace), _ptr(ws), ws_bytes, _vp(stream))
+        _check(rc)
+        del lx_d
+        return hyps, hyp_len, scores, trace, lm_scores
     with torch.cuda.device(dev):
         rc = _lib.crf_ctc_beam(_ptr(log_probs), _FUSED_DTYPES[log_probs.dtype], 1 if time_major else 0, int(blank), 1 if fused else 0,
                                _ptr(lx_d), N, T, V, W, K, C, _ptr(hyps), _ptr(hyp_len), _ptr(scores), _ptr(trace), _ptr(ws), ws_bytes,

@@ -19,8 +19,12 @@ Same names, arguments and error behaviour as the reference:
                                                                                          (K label sequences per utterance drawn on the GPU)
   ctc_greedy(log_probs, input_lengths, blank=0, time_major=False) -> (hyps IntTensor[N, T], hyp_lengths IntTensor[N])   (best path)
   ctc_beam_search(log_probs, input_lengths, beam_size=16, nbest=1, top_classes=40, blank=0, time_major=False, fuse_log_softmax=False,
-                  return_trace=False) -> (hyps IntTensor[N*nbest, T], hyp_lengths IntTensor[N*nbest], hyp_utt IntTensor[N*nbest],
-                                          scores FloatTensor[N*nbest])                   (prefix beam search, LM-free: the N-best lists)
+                  return_trace=False, lm=None, alpha=0.0, beta=0.0, return_lm_scores=False)
+                                       -> (hyps IntTensor[N*nbest, T], hyp_lengths IntTensor[N*nbest], hyp_utt IntTensor[N*nbest],
+                                           scores FloatTensor[N*nbest])                  (prefix beam search: the N-best lists; with lm
+                                                                                         shallow fusion of a token-level n-gram LM)
+  NgramLM.from_arpa(path, vocab_size, unk_logp=None), NgramLM.from_ngrams(dict, vocab_size, unk_logp=None)
+                                                                                         (the LM of ctc_beam_search: cat_amd/ngram_lm.py)
   ctc_edit_distance(hyps, hyp_lengths, labels, label_lengths, hyp_utt=None, return_ops=False) -> dist IntTensor[H]
                                                               (with return_ops: (dist, sub, dele, ins), each IntTensor[H])
                                                                                          (token errors of hypotheses on the GPU: WER / PER sums, the MWER risk)
@@ -40,6 +44,7 @@ from torch.autograd.function import once_differentiable
 from torch.nn import Module
 
 from . import _C as core
+from ..ngram_lm import NgramLM  # noqa: F401
 
 __version__ = "0.1.0"
 
@@ -409,11 +414,14 @@ def ctc_greedy(log_probs: torch.Tensor, input_lengths: torch.Tensor, blank: int 
 
 
 def ctc_beam_search(log_probs: torch.Tensor, input_lengths: torch.Tensor, beam_size: int = 16, nbest: int = 1, top_classes: int = 40,
-                    blank: int = 0, time_major: bool = False, fuse_log_softmax: bool = False, return_trace: bool = False):
-    """CTC prefix beam search on the GPU, LM-free: the N-best lists that ctc_score rescores and ctc_logp trains on -- what the callers get
+                    blank: int = 0, time_major: bool = False, fuse_log_softmax: bool = False, return_trace: bool = False, lm: NgramLM = None,
+                    alpha: float = 0.0, beta: float = 0.0, return_lm_scores: bool = False):
+    """CTC prefix beam search on the GPU: the N-best lists that ctc_score rescores and ctc_logp trains on -- what the callers get
     from the third-party CPU ctcdecode.CTCBeamDecoder(beam_width=16, num_processes=6) after copying the whole (N, T, V) tensor to the host
-    (cat/ctc/train.py:273-281, train_jsa.py:467-476, decode.py:163-222), in one call without a host round trip.  No language model:
-    KenLM fusion is not covered.
+    (cat/ctc/train.py:273-281, train_jsa.py:467-476, decode.py:163-222), in one call without a host round trip.  With lm it is the
+    decoder's other half, CTCBeamDecoder(model_path=<KenLM n-gram>, alpha=, beta=, is_token_based=True): shallow fusion of a token-level
+    n-gram LM read from the ARPA file that lmplz writes (NgramLM.from_arpa; a token is a class of log_probs).  Not covered: an
+    end-of-sentence term, word-level LMs and lexicons, KenLM's binary formats, an LM in ctc_sample.
 
     log_probs: (N, T, V) on the GPU, or (T, N, V) with time_major=True; fp32, bf16 or fp16, read in place: log-probs, or with
         fuse_log_softmax=True the RAW network output (log_softmax of the upcast values inside the call).
@@ -422,21 +430,28 @@ def ctc_beam_search(log_probs: torch.Tensor, input_lengths: torch.Tensor, beam_s
     top_classes: besides the blank, only this many classes of largest value take part in a frame (1 .. 64; ctcdecode's cutoff_top_n);
         with top_classes >= V - 1 nothing is pruned.  A repeat of the last label is pruned with its class, as ctcdecode does.
     Prefixes are identified by their label sequence: mass that reaches a prefix of the beam along another parent is added to it.
+    lm: None (same call and same bits as before; alpha and beta must then be 0), or an NgramLM over V classes: a prefix is ranked by
+        score + alpha * log P_lm(prefix) + beta * len(prefix) (natural logs; the LM starts in the state of <s> where the model has one).
+        The tables are uploaded once per device and kept.  alpha = beta = 0 gives the LM-free results bit for bit.
 
-    Returns (hyps, hyp_lengths, hyp_utt, scores) and, with return_trace, trace -- tensors on log_probs' device, no host synchronisation,
-    no autograd history:
+    Returns (hyps, hyp_lengths, hyp_utt, scores), then trace with return_trace, then lm_scores with return_lm_scores -- tensors on
+    log_probs' device, no host synchronisation, no autograd history:
         hyps (N nbest, T) int32: row h = n nbest + r holds the hyp_lengths[h] labels of rank r, then the BLANK's index up to T -- the rows
             ctc_sample returns: ctc_score(log_probs, hyps.cpu(), hyp_lengths.cpu(), input_lengths, hyp_utt.cpu()) rescores them;
         hyp_utt (N nbest,): h // nbest;
-        scores (N nbest,) fp32: log of the prefix's probability mass within the search, non-increasing in r, a lower bound of the
-            hypothesis's ctc_score; a rank the beam does not hold has length 0 and score -inf;
+        scores (N nbest,) fp32: log of the prefix's probability mass within the search (with lm: plus lm_scores, the fused score),
+            non-increasing in r; scores (minus lm_scores) is a lower bound of the hypothesis's ctc_score; a rank the beam does not hold
+            has length 0 and score -inf;
         trace (N, T, beam_size) int32: after frame t, slot k: parent_slot + 64 (class + 1), class -1 for a stay; -1 for an empty slot
-            and for t >= input_lengths[n]."""
+            and for t >= input_lengths[n];
+        lm_scores (N nbest,) fp32: alpha * log P_lm + beta * length of the rank's hypothesis (0 for a missing rank)."""
     with torch.no_grad():
-        hyps, hyp_lengths, scores, trace = core.ctc_beam_search(log_probs.detach().contiguous(), input_lengths, beam_size, nbest, top_classes,
-                                                                int(blank), bool(time_major), bool(fuse_log_softmax), bool(return_trace))
+        out = core.ctc_beam_search(log_probs.detach().contiguous(), input_lengths, beam_size, nbest, top_classes, int(blank), bool(time_major),
+                                   bool(fuse_log_softmax), bool(return_trace), lm, alpha, beta, bool(return_lm_scores))
+        hyps, hyp_lengths, scores, trace = out[:4]
         hyp_utt = torch.arange(hyps.size(0), dtype=torch.int32, device=hyps.device).div_(int(nbest), rounding_mode="floor")
-    return (hyps, hyp_lengths, hyp_utt, scores, trace) if return_trace else (hyps, hyp_lengths, hyp_utt, scores)
+    res = (hyps, hyp_lengths, hyp_utt, scores) + ((trace,) if return_trace else ()) + ((out[4],) if return_lm_scores else ())
+    return res
 
 
 def ctc_edit_distance(hyps: torch.Tensor, hyp_lengths: torch.Tensor, labels: torch.Tensor, label_lengths: torch.Tensor,

@@ -424,6 +424,62 @@ int crf_ctc_beam(const void *act_dev, int dtype, int time_major, int blank, int 
                  void *workspace_dev, int64_t workspace_bytes, void *stream);
 const char *crf_last_beam_kernel(void);
 
+/* crf_ctc_beam with shallow fusion of a token-level n-gram language model: what the reference's decoders get from
+ * ctcdecode.CTCBeamDecoder(model_path=<KenLM n-gram>, alpha, beta, is_token_based=True) (cat/ctc/decode.py:163-222, the `kenlm:` blocks of
+ * cat/ctc/train.py:258-281, train_jsa.py:452-476, train_me2e.py:308-331; the LM of cat/utils/pipeline/ngram.sh over token indices).  A
+ * token of the LM is a class of the network output, so the LM's factor is a function of the prefix alone and prefixes that merge carry
+ * the same factor.
+ *   Tables    crf_ngram_tables: the back-off n-gram model compiled to states (cat_amd/ngram_lm.py builds them from an ARPA file).  State 0
+ *             is the empty history (the root), every other state a history of 1 .. order - 1 tokens; states are sorted by history length,
+ *             so bo_state[s] < s for s > 0.  Row s of the arcs is arc_*[row_off[s] .. row_off[s + 1]), arc_label ascending strictly; the
+ *             root's row is DENSE instead (uni_logp[V], uni_next[V]; row_off[0] = row_off[1] = 0), so every back-off chain ends in one
+ *             indexed load.  Values are natural logs in fp32, all finite.  `start` is the state the search begins in (that of <s>, or 0).
+ *             The tables are the caller's device memory: the library allocates nothing and keeps no pointer behind the call.
+ *   Lookup    lp(s, c), next(s, c): search c in row s; found at arc i: lp = acc + arc_logp[i], next = arc_next[i]; otherwise
+ *             acc += bo_weight[s] and s = bo_state[s]; at the root lp = acc + uni_logp[c], next = uni_next[c] (acc starts at 0; fp32).
+ *   Recursion The acoustic part is crf_ctc_beam's, unchanged: pb, pnb, the merge rule, E_t, the repeat pruned with its class.  Each
+ *             prefix also carries its LM state and lm = alpha * log P_lm(prefix) + beta * length in fp64: an extension by c has the
+ *             parent's lm + lmw with lmw = alpha * lp(state, c) + beta in fp32 (product and sum rounded separately), a stay keeps both.
+ *             A candidate's score is (pb' (+) pnb') + lm.  The W best survive under the total order: score descending, then stay before
+ *             extension, then parent slot ascending, then -- among the extensions of one parent -- x[c] + lmw descending (the fp64 sum
+ *             of the two fp32 values), then their place in E_t.
+ *   score_dev [B nbest] fp32 = (pb (+) pnb) + lm after frame lx - 1, the fused score; lm_score_dev (may be NULL) [B nbest] fp32 = lm (0
+ *             for a missing rank).  hyps_dev, hyp_len_dev and trace_dev as for crf_ctc_beam.  No end-of-sentence term is added.
+ * The results are the same bits across calls, in both layouts and whatever other utterances share the call.  With alpha == 0 and
+ * beta == 0 every output equals crf_ctc_beam's bit for bit (where two extensions of one parent tie in score, crf_ctc_beam's rule and
+ * this one agree whenever their x are equal).
+ * Memory safety whatever the tables hold: the back-off walk takes at most min(order, 8) rows and then the root's, the search of a row
+ * at most 14 probes (rows hold at most V <= 8192 arcs), every state and arc index is clamped into [0, S) and [0, A).  Tables that do not
+ * pass crf_ngram_tables_check give unspecified results, never an access out of bounds and never a hang.
+ * crf_ngram_tables_check runs on HOST copies of the tables (the struct's pointers are host pointers), with no HIP call: offsets start at
+ * 0, are monotone and end at A, the root's sparse row is empty, labels ascend strictly inside a row and lie in [0, V), arc_next, uni_next
+ * and start lie in [0, S), bo_state[s] < s (0 for the root), order lies in [1, 8], V in [1, 8192], every value is finite.  CRF_ERR_ARG with
+ * a message that names the first offending entry.
+ * crf_last_beam_kernel() names the row kernel as for crf_ctc_beam.  Workspace: crf_ctc_beam_lm_workspace_bytes (crf_ctc_beam's sections).
+ * No host synchronisation, all work on `stream`, no environment variable read.
+ * Errors: crf_ctc_beam's, and CRF_ERR_ARG for a null lm, lm->V != V, alpha or beta not finite, lm->S < 1, lm->order outside [1, 8],
+ * lm->start outside [0, S) or a null table -- all answered before any HIP call.
+ * Not covered: an end-of-sentence term, word-level LMs and lexicons, KenLM's binary formats, an LM in crf_ctc_sample. */
+typedef struct crf_ngram_tables {
+    const int32_t *row_off;    /* [S + 1] */
+    const int32_t *arc_label;  /* [A] */
+    const float *arc_logp;     /* [A] */
+    const int32_t *arc_next;   /* [A] */
+    const int32_t *bo_state;   /* [S] */
+    const float *bo_weight;    /* [S]; 0 where the model gives none */
+    const float *uni_logp;     /* [V] the root's dense row */
+    const int32_t *uni_next;   /* [V] */
+    int64_t S, A, V;
+    int32_t order, start;
+} crf_ngram_tables;
+int crf_ngram_tables_check(const crf_ngram_tables *host_tables);
+int64_t crf_ctc_beam_lm_workspace_bytes(int64_t B, int64_t T, int64_t V, int64_t W, int64_t top_classes);
+int crf_ctc_beam_lm(const void *act_dev, int dtype, int time_major, int blank, int normalize, const int32_t *lx_dev,
+                    int64_t B, int64_t T, int64_t V, int64_t W, int64_t nbest, int64_t top_classes,
+                    const crf_ngram_tables *lm, float alpha, float beta,
+                    int32_t *hyps_dev, int32_t *hyp_len_dev, float *score_dev, float *lm_score_dev, int32_t *trace_dev,
+                    void *workspace_dev, int64_t workspace_bytes, void *stream);
+
 /* Token edit distance of H hypotheses to the transcripts of their utterances, with the operation counts of one optimal alignment: what
  * cat/ctc/train.py:200-210 (cal_wer), train_jsa.py:371-387 (cal_per), train_me2e.py:250-256 and train_me2e_kaldi.py:420-426 compute with
  * a Python loop of Levenshtein.distance after `.cpu().tolist()`, and the risk of minimum-risk / MWER training, for the rows that
