@@ -4,7 +4,7 @@ restatement of the contract of crf_ctc_beam (include/ctc_crf_hip.h), with the be
 `search` runs the contract; `replay` follows a GIVEN trace frame by frame, rebuilds that beam's prefixes, computes every candidate of the
 contract in fp64 from the fp64 state of the slots the trace chose, and reports by how much an unchosen candidate beats a chosen one --
 errors do not cascade, and no case needs to be skipped for a near-tie.  `brute` sums all V^T labellings.  `planted_rows`,
-`grouped_inputs`, `audit_ties` and TIE_CASES build and vet the inputs on which exact ties decide, where only equality with `search` will do."""
+`grouped_inputs` (with `class_groups`, its class-to-group map), `audit_ties` and TIE_CASES build and vet the inputs on which exact ties decide, where only equality with `search` will do."""
 import itertools
 import math
 
@@ -341,13 +341,19 @@ def planted_rows(V, dtype, blank=0, C=64, seed=0):
     return rows
 
 
+def class_groups(seed, V, groups, rng=None):
+    """The group of every class [V] as `grouped_inputs` draws it for this seed (the first draw of its generator; rng: that generator)."""
+    rng = np.random.default_rng(seed) if rng is None else rng
+    return rng.permutation(np.arange(V) % groups)
+
+
 def grouped_inputs(seed, T, V, blank, groups):
     """fp32 rows [T, V] (taken with normalize = False) with EXACT ties between candidates: every class belongs to one of `groups` groups
     for the whole utterance, per frame each group has one random value in about [-3.3, -0.3] that all its classes share; in every second
     frame the blank has a value of its own.  Prefixes that differ by a permutation inside a group carry bit-equal (pb, pnb) in any
     arithmetic, so their candidates tie exactly and only the total order of the contract decides; any other equality has probability 0."""
     rng = np.random.default_rng(seed)
-    group = rng.permutation(np.arange(V) % groups)
+    group = class_groups(seed, V, groups, rng)
     x = (-0.3 - 3.0 * rng.random((T, groups)))[:, group]
     own = -0.3 - 3.0 * rng.random(T)
     x[1::2, blank] = own[1::2]
@@ -377,6 +383,7 @@ REPLAY_CASES = [
     (40, 300, 2, 64, 17, (17, 17), 7),
     (1, 65, 4, 40, 150, (150, 1, 0, 77), 3),
     (1, 2, 64, 64, 1, (1, 0), 1),                   # one frame: the widest beam on the smallest row
+    (1, 9, 64, 8, 130, (130, 129, 128, 65, 64, 1), 4),   # W = 64 with a back-trace of three 64-frame chunks, of two, to and off a boundary
 ]
 
 # The cases of the exact-tie test: (seed, V, W, C, T, blank, groups) of `grouped_inputs`, taken with normalize = False at lx = T, T - 1, 1.

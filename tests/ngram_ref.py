@@ -1,7 +1,9 @@
 """The yardstick of cat_amd/ngram_lm.py (a plain helper module: tests/test_ngram_lm.py, tests/beam_lm_ref.py, the GPU tests of the fused
 beam search): the textbook back-off lookup straight from the n-gram dict {tuple of tokens: (log10 prob, log10 back-off)} -- the longest
 match, else bow(h) + p(c | h[1:]) -- in fp64 and natural logs.  It never looks at the compiled tables.  Also a seeded generator of random
-models (prefix-closed, NOT suffix-closed: pruned contexts) and an ARPA writer for them."""
+models (prefix-closed, NOT suffix-closed: pruned contexts), of models whose values depend on the groups of the tokens only (the exact-tie
+cases of the fused beam search), and an ARPA writer for them."""
+import itertools
 import math
 
 import numpy as np
@@ -42,6 +44,20 @@ class Ref:
                 return acc + self.unk * LN10
             if h in self.ng:
                 acc += self.ng[h][1] * LN10
+            h = h[1:]
+
+    def mass(self, history, c):
+        """The sum of the magnitudes of the terms `cond` adds (back-off weights and the value found): what bounds the rounding of an
+        fp32 sum of them -- positive back-off weights and negative values can cancel, and the result alone does not."""
+        h = tuple(history)[-(self.order - 1):] if self.order > 1 else ()
+        acc = 0.0
+        while True:
+            if h + (c,) in self.ng:
+                return acc + abs(self.ng[h + (c,)][0]) * LN10
+            if not h:
+                return acc + abs(self.unk) * LN10
+            if h in self.ng:
+                acc += abs(self.ng[h][1]) * LN10
             h = h[1:]
 
     def score(self, tokens):
@@ -88,6 +104,39 @@ def random_model(seed, V, order, bos=True, unk=False, eos=False, fanout=3, keep=
             if eos and rng.random() < 0.3:
                 ng[ctx + (EOS,)] = (val()[0], 0.0)
         level = nxt
+    return ng
+
+
+def symmetric_model(seed, V, group, G, order, bos=True, zero_group=None, fanout=3, keep=0.6):
+    """A model over V classes whose values depend on the GROUPS of an n-gram's tokens only (group [V]: the group in [0, G) of every
+    class): a random prefix-closed model over the G group symbols as `random_model` draws one, every group n-gram expanded to all class
+    n-grams of those groups with its (log10 p, log10 bow).  Two token sequences that differ by a permutation inside the groups then take
+    the same n-grams' values in the same order: bit-equal log P and bit-equal look-ups, in the textbook and in the compiled tables alike.
+    zero_group = g: log10 p = 0.0 for every n-gram whose last token is of group g -- found without a back-off, an extension by such a
+    class costs alpha * 0.0 = +0 exactly."""
+    rng = np.random.default_rng([seed, V, G, order])
+    val = lambda: (round(float(-0.1 - 2.9 * rng.random()), 4), round(float(-1.0 + 1.2 * rng.random()), 4))
+    gm = {(g,): val() for g in range(G)}
+    if bos:
+        gm[(BOS,)] = (-99.0, val()[1])
+    level = list(gm)
+    for n in range(2, order + 1):
+        nxt = []
+        for ctx in level:
+            if rng.random() > keep and nxt:
+                continue
+            for g in rng.choice(G, size=min(G, 1 + int(rng.integers(fanout))), replace=False):
+                k = ctx + (int(g),)
+                gm[k] = val() if n < order else (val()[0], 0.0)
+                nxt.append(k)
+        level = nxt
+    members = [[c for c in range(V) if group[c] == g] for g in range(G)]
+    ng = {}
+    for k, (lp, bo) in gm.items():
+        if zero_group is not None and k[-1] == zero_group:
+            lp = 0.0
+        for toks in itertools.product(*[[BOS] if g == BOS else members[g] for g in k]):
+            ng[toks] = (lp, bo)
     return ng
 
 

@@ -1,6 +1,7 @@
 """CPU tests (no GPU) of ctc_beam_search(lm=...): the exports, crf_ngram_tables_check on corrupted host tables, the argument errors of the
 Python binding and of crf_ctc_beam_lm answered before any HIP call (include/ctc_crf_hip.h), the yardstick tests/beam_lm_ref.py against
-brute force and against tests/beam_ref.py at zero weights, and the planted inputs of the GPU tests with the separation they must have."""
+brute force and against tests/beam_ref.py at zero weights, the planted inputs of the GPU tests with the separation they must have, and
+the exact-tie cases under a live LM (beam_lm_ref.LM_TIE_CASES) with the conditions they must meet and the altered orders they must tell apart."""
 import ctypes
 
 import numpy as np
@@ -185,20 +186,132 @@ def test_reference_against_brute_force_and_the_lm_free_reference():
     assert beam_lm_ref.replay(x, 12, plain["trace"], 2, 2, 0, ref, 3.0, 0.0)["excess"] > 1e-3
 
 
+def test_order_key_levels_and_audit_hand_worked():
+    """Every level of beam_lm_ref.order_key on hand-made candidates that differ at that level alone, and audit_ties on one frame with
+    probabilities (0.5, 0.25, 0.25) under a unigram model that gives both labels log10 p = -0.5: W = 2, alpha = 1, beta = 0 -- the stay of
+    () at log 0.5, then () + 1 and () + 2 level at log 0.25 - 0.5 ln 10, two places of one parent on the cut, equal keys."""
+    base = dict(score=-1.0, kind=1, parent=2, key=-0.5, place=3)
+    want = [dict(base, score=-0.5, kind=1, parent=9, key=-9.0, place=9), dict(base, kind=0, parent=9, key=0.0, place=-1),
+            dict(base, parent=1, key=-9.0, place=9), dict(base, key=-0.25, place=9), dict(base, place=2), base, dict(base, score=-1.5, kind=0, parent=0)]
+    for perm in (want[::-1], want[3:] + want[:3]):
+        assert sorted(perm, key=beam_lm_ref.order_key) == want
+    for name, (level, key) in beam_lm_ref.LM_ALTERED_ORDERS.items():
+        assert sorted(want, key=key) != want, name
+    ng = {(0,): (-1.0, 0.0), (1,): (-0.5, 0.0), (2,): (-0.5, 0.0)}
+    ref = ngram_ref.Ref(ng, 3)
+    x = np.log([[0.5, 0.25, 0.25]])
+    a = beam_lm_ref.audit_ties(x, 1, 2, 2, 0, ref, 1.0, 0.0)
+    l = 0.5 * ngram_ref.LN10
+    assert a == dict(gap=(np.log(0.5) - (np.log(0.25) - l)) / (abs(np.log(0.25)) + l), stay_ext=0, slot=0, place=1, cut=1, key_level=0, reordered=0)
+    # label 2 dearer to the LM than label 1: it goes first from place 1 -- a head that is not the next place of E_t
+    ref = ngram_ref.Ref({**ng, (2,): (-0.25, 0.0)}, 3)
+    a = beam_lm_ref.audit_ties(x, 1, 2, 2, 0, ref, 1.0, 0.0)
+    r = beam_lm_ref.search(x, 1, 2, 2, 2, 0, ref, 1.0, 0.0)
+    assert (a["place"], a["reordered"]) == (0, 1) and r["trace"].tolist() == [[0, 0 + 64 * 3]]
+
+
+@pytest.fixture(scope="module")
+def lm_tie_runs():
+    """Per LM_TIE_CASES entry: (x, ref, audit, search at lx = T) -- once."""
+    out = []
+    for case in beam_lm_ref.LM_TIE_CASES:
+        seed, V, W, C, T, blank, G, order, alpha, beta, zero_group = case
+        x, ng = beam_lm_ref.lm_tie_inputs(case)
+        ref = ngram_ref.Ref(ng, V)
+        out.append((x, ng, ref, beam_lm_ref.audit_ties(x, T, W, C, blank, ref, alpha, beta), beam_lm_ref.search(x, T, W, W, C, blank, ref, alpha, beta)))
+    return out
+
+
+def test_symmetric_model_depends_on_the_groups_only(lm_tie_runs):
+    """ngram_ref.symmetric_model as LM_TIE_CASES take it: over the class-to-group map of grouped_inputs (classes of one group share
+    every frame's value), prefix-closed, of the case's order, one (log10 p, log10 bow) per group n-gram, log10 p = 0.0 behind the zero
+    group and nowhere else; the textbook's log P of two sequences that differ inside the groups is the same fp64 number, and so is the
+    compiled tables' fp32 look-up in every state."""
+    import ctc_crf
+    for case, (x, ng, ref, _, _) in zip(beam_lm_ref.LM_TIE_CASES, lm_tie_runs):
+        seed, V, W, C, T, blank, G, order, alpha, beta, zero_group = case
+        group = beam_ref.class_groups(seed, V, G)
+        raw = beam_ref.grouped_inputs(seed, T, V, blank, G)
+        assert np.array_equal(x.view(np.int32), beam_ref.through(x, "bf16").view(np.int32)) and np.abs(x - raw).max() <= 2.0 ** -8 * 3.3
+        assert sorted(np.bincount(group, minlength=G)) == sorted(np.bincount(np.arange(V) % G, minlength=G))
+        for t in range(0, T, 2):                                   # (in the other frames the blank has a value of its own)
+            assert all(len({x[t, c] for c in range(V) if group[c] == g}) == 1 for g in range(G)), (case, t)
+        gof = lambda k: tuple(w if isinstance(w, str) else int(group[w]) for w in k)
+        by = {}
+        for k, v in ng.items():
+            assert len(k) == 1 or k[:-1] in ng, (case, k)
+            assert (v[0] == 0.0) == (zero_group is not None and gof(k)[-1] == zero_group), (case, k, v)
+            assert by.setdefault(gof(k), v) == v, (case, k)
+        assert max(len(k) for k in ng) == order and len(ng) == sum(int(np.prod([1 if g == ngram_ref.BOS else (group == g).sum() for g in gk])) for gk in by)
+        rng = np.random.default_rng(seed)
+        members = [np.flatnonzero(group == g) for g in range(G)]
+        lm = ctc_crf.NgramLM.from_ngrams(ng, V) if V <= 9 else None
+        for _ in range(20):
+            gs = rng.integers(0, G, size=int(rng.integers(1, 7)))
+            a, b = (tuple(int(rng.choice(members[g])) for g in gs) for _ in range(2))
+            assert ref.score(a) == ref.score(b), (case, a, b)
+            if lm is not None:
+                sa, sb = lm.start, lm.start
+                for ca, cb in zip(a, b):
+                    (la, sa), (lb, sb) = lm.lookup(sa, ca), lm.lookup(sb, cb)
+                    assert la == lb and gof(lm.state_history[sa]) == gof(lm.state_history[sb]), (case, a, b)
+
+
+def test_lm_tie_cases_meet_their_conditions(lm_tie_runs):
+    """LM_TIE_CASES as the GPU test needs them (the conditions are listed above the list in tests/beam_lm_ref.py): the shapes are those
+    of beam_ref.TIE_CASES with W = C = 64 among them, live and zero-group cases both; per case the smallest gap that is no tie >= 1e-3,
+    no pair decided by unequal keys, one trace in both arithmetics, an LM that changes the trace and moves heads off the place order,
+    ties at every level the case claims, one on the cut, and a changed trace under every altered order of a level it claims.  (The
+    search is causal: the rows of lx = T - 1 and 1, which the GPU test also takes, are the first rows of lx = T's.)"""
+    cases = beam_lm_ref.LM_TIE_CASES
+    assert 5 <= len(cases) <= 7 and {c[1:7] for c in cases} <= {c[1:] for c in beam_ref.TIE_CASES}
+    zero = [c for c in cases if c[10] is not None]
+    assert len(zero) >= 2 and len(cases) - len(zero) >= 2 and any(c[1:4] == (70, 64, 64) for c in zero) and any(c[1:4] == (70, 64, 64) and c[10] is None for c in cases)
+    for case, (x, ng, ref, a, r) in zip(cases, lm_tie_runs):
+        seed, V, W, C, T, blank, G, order, alpha, beta, zero_group = case
+        assert (alpha, beta) == ((0.5, 1.0) if zero_group is None else (1.5, 0.0)) and order == (2 if V == 70 else 3) and T <= 12
+        print(case, {k: float(v) for k, v in a.items()})
+        assert a["gap"] >= 1e-3, (case, a)
+        assert a["key_level"] == 0 and a["reordered"] > 0, (case, a)
+        levels = ["slot", "place"] + (["stay_ext"] if zero_group is not None else [])
+        assert all(a[k] > 0 for k in levels + ["cut"]), (case, a)
+        assert zero_group is not None or a["stay_ext"] == 0, (case, a)
+        assert r["gap"] == 0.0                                       # (the search's own figure counts the ties: check_equals_search cannot take it)
+        r32 = beam_lm_ref.search(x, T, W, W, C, blank, ref, alpha, beta, lse=beam_ref.lse32)
+        assert np.array_equal(r["trace"], r32["trace"]) and [p for p, _, _ in r["nbest"]] == [p for p, _, _ in r32["nbest"]], case
+        assert np.allclose([s for _, s, _ in r["nbest"]], [s for _, s, _ in r32["nbest"]], rtol=1e-6, atol=0)
+        assert beam_lm_ref.replay(x, T, r["trace"], W, C, blank, ref, alpha, beta)["excess"] == 0
+        assert not np.array_equal(r["trace"], beam_ref.search(x, T, W, W, C, blank)["trace"]), case
+        for name, (level, key) in beam_lm_ref.LM_ALTERED_ORDERS.items():
+            if level not in levels:
+                continue
+            bad = beam_lm_ref.search(x, T, W, W, C, blank, ref, alpha, beta, key=key)
+            assert not np.array_equal(bad["trace"], r["trace"]), (case, name)
+            if V <= 9:
+                assert beam_lm_ref.replay(x, T, bad["trace"], W, C, blank, ref, alpha, beta)["excess"] == 0     # (replay cannot tell)
+
+
 def test_planted_cases_are_well_separated():
     """The inputs of the GPU tests that demand EQUALITY with the reference search: adjacent candidates among the ranks 0 .. W differ by at
     least 1e-5 relative -- a hundred times what fp32 rounding of lmw and of the sums can move them -- and the cases reach what they are for."""
     import ctc_crf
-    for closed in (False, True):
-        ng, x, (V, W, C, T, blank, alpha, beta) = beam_lm_ref.back_off_case(closed)
+    assert beam_lm_ref.back_off_case.__defaults__ == (False, 5)
+    for order, closed in ((5, False), (5, True), (8, False), (8, True)):
+        ng, x, (V, W, C, T, blank, alpha, beta) = beam_lm_ref.back_off_case(closed, order)
         lm, ref = ctc_crf.NgramLM.from_ngrams(ng, V), ngram_ref.Ref(ng, V)
         r = beam_lm_ref.search(x[0], T, W, W, C, blank, ref, alpha, beta)
-        assert r["gap"] >= 1e-5 and (0, 1, 2, 3, 4) in beam_ref.spell(r["trace"], T, W)
-        assert lm.order == 5 and lm.num_arcs == (7 if closed else 4)
-        s, depth = lm.state_history.index((0, 1, 2, 3)), 0
+        assert r["gap"] >= 1e-5 and tuple(range(order)) in beam_ref.spell(r["trace"], T, W)
+        assert V == order + 2 >= 7 and lm.order == order and lm.num_arcs == ((order - 1) * (order - 2) // 2 + 1 if closed else order - 1)
+        s, depth = lm.state_history.index(tuple(range(order - 1))), 0       # (order 8: the state of seven tokens, the longest there is)
         while s:
             s, depth = int(lm.bo_state[s]), depth + 1
-        assert depth == (4 if closed else 2)
+        assert depth == (order - 1 if closed else 2)
+        if closed:                                                  # every class but the chain's last walks order - 1 sparse rows and misses
+            for c in range(V):
+                s, rows = lm.state_history.index(tuple(range(order - 1))), 0
+                while s and c not in lm.arc_label[lm.row_off[s]:lm.row_off[s + 1]]:
+                    s, rows = int(lm.bo_state[s]), rows + 1
+                assert rows == (0 if c == order - 1 else order - 1), (order, c, rows)
     ng, rows, x, (V, W, C, T, blank, alpha, beta) = beam_lm_ref.row_edges_case()
     lm, ref = ctc_crf.NgramLM.from_ngrams(ng, V), ngram_ref.Ref(ng, V)
     assert V == 8192 and lm.order == 2 and sorted(len(v) for v in rows.values()) == [0, 1, 2, 3, 63, 64, 65, 8191]

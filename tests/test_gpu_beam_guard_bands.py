@@ -57,8 +57,10 @@ def run_beam(core, x, lx, W, nbest, C, blank, normalize, time_major=False, with_
     return hyps, hl, sc_bits.view(np.float32), tr
 
 
-# (4096: the row stage's launch with four rows and 64 KiB of LDS per workgroup; 8191: an odd wide V, one row per workgroup)
-@pytest.mark.parametrize("V,T,W,nbest,C", [(73, 65, 16, 5, 40), (301, 17, 64, 64, 64), (3, 30, 3, 2, 8), (4096, 5, 16, 4, 64), (8191, 5, 64, 64, 40)])
+# (4096: the row stage's launch with four rows and 64 KiB of LDS per workgroup; 8191: an odd wide V, one row per workgroup;
+# 9 x 130 at W = nbest = 64: the back-trace's LDS buffer at its full width, three chunks (lx = 130) and two (lx = 65))
+@pytest.mark.parametrize("V,T,W,nbest,C", [(73, 65, 16, 5, 40), (301, 17, 64, 64, 64), (3, 30, 3, 2, 8), (4096, 5, 16, 4, 64), (8191, 5, 64, 64, 40),
+                                           (9, 130, 64, 64, 8)])
 @pytest.mark.parametrize("time_major", [False, True])
 def test_beam_writes_only_its_own_memory(core, V, T, W, nbest, C, time_major):
     B, blank = 3, V - 1

@@ -65,9 +65,10 @@ def run_beam_lm(core, x, lx, W, nbest, C, blank, normalize, lm, alpha, beta, tim
             got["trace"].reshape(B, T, W) if with_optional else None, got["lm_score"].view(np.float32) if with_optional else None)
 
 
-# (73 x 65: several 64-frame chunks of the back-trace; 301: W = C = 64; 3: the smallest rows; 4096 / 8191: the row stage's two launches)
+# (73 x 65: several 64-frame chunks of the back-trace; 301: W = C = 64; 3: the smallest rows; 4096 / 8191: the row stage's two launches;
+# 9 x 130 at W = nbest = 64: the trace comes back through ALL of lm_n's 64 x 64 words of LDS, in three chunks (lx = 130) and two (lx = 65))
 @pytest.mark.parametrize("V,T,W,nbest,C,order", [(73, 65, 16, 5, 40, 3), (301, 17, 64, 64, 64, 4), (3, 30, 3, 2, 8, 2), (4096, 5, 16, 4, 64, 2),
-                                                  (8191, 5, 64, 64, 40, 3)])
+                                                  (8191, 5, 64, 64, 40, 3), (9, 130, 64, 64, 8, 3)])
 @pytest.mark.parametrize("time_major", [False, True])
 def test_beam_lm_writes_only_its_own_memory(core, V, T, W, nbest, C, order, time_major):
     import ctc_crf

@@ -141,8 +141,9 @@ def case_outputs(crf):
 
 @pytest.mark.parametrize("case", beam_ref.REPLAY_CASES, ids=lambda c: "seed%d-V%d-W%d-C%d-T%d" % c[:5])
 def test_replay(case_outputs, case):
-    """The seeded cases (tests/beam_ref.py REPLAY_CASES: V in {2, 3, 5, 65, 72, 300}, W in {1, 2, 4, 16, 64}, C in {1, 8, 40, 64}, T in
-    {1, 17, 64, 150} and the narrow beams at V = 3, T = 30; ragged lx with 0 and 1): replay of the GPU's trace shows no unchosen candidate
+    """The seeded cases (tests/beam_ref.py REPLAY_CASES: V in {2, 3, 5, 9, 65, 72, 300}, W in {1, 2, 4, 16, 64}, C in {1, 8, 40, 64}, T in
+    {1, 17, 64, 130, 150} and the narrow beams at V = 3, T = 30; ragged lx with 0 and 1; at W = 64 and T = 130 the back-trace takes three
+    chunks of the 64-frame LDS buffer at its full width, lx = 128 ends on a chunk boundary, 65 is one frame past it): replay of the GPU's trace shows no unchosen candidate
     beating a chosen one by more than RTOL |score|, the GPU scores match replay's fp64 scores, hyps / hyp_lengths are the sequences the
     trace spells, ranks are in non-increasing score, trace rows past lx and empty slots hold -1."""
     seed, V, W, C, T, lxs, blank = case

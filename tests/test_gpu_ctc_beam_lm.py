@@ -249,13 +249,20 @@ def test_the_lm_decides(crf):
     assert abs(float(fusedr[4][0]) - 2.0 * ref.score((1, 3))) < 1e-5 * 2.0 * abs(ref.score((1, 3)))
 
 
-def check_equals_search(crf, x, lxs, W, C, blank, lm, ref, alpha, beta, what):
+def check_equals_search(crf, x, lxs, W, C, blank, lm, ref, alpha, beta, what, dtype="fp32", wants=None):
     """Inputs whose reference candidates are apart by >= 1e-5 relative (100 x the fp32 roundings of lmw and of the sums): the GPU's trace,
-    hypotheses and lengths must EQUAL beam_lm_ref.search's, the scores within tolerance."""
-    hyps, lens, scores, trace, lms = run(crf, torch.tensor(x, device="cuda:0"), lxs, W, W, C, blank, lm, alpha, beta)
+    hypotheses and lengths must EQUAL beam_lm_ref.search's, the scores within tolerance.  wants: the reference searches of a caller that
+    holds them to conditions of its own in place of that gap (the exact-tie cases); dtype: of the activations, which must hold x exactly."""
+    xg = torch.tensor(x).to(DTYPES[dtype])
+    assert torch.equal(xg.float(), torch.tensor(x))
+    hyps, lens, scores, trace, lms = run(crf, xg.to("cuda:0"), lxs, W, W, C, blank, lm, alpha, beta)
     for b, lx in enumerate(lxs):
-        want = beam_lm_ref.search(x[b], lx, W, W, C, blank, ref, alpha, beta)
-        assert want["gap"] >= 1e-5, (what, b, want["gap"])
+        if wants is None:
+            want = beam_lm_ref.search(x[b], lx, W, W, C, blank, ref, alpha, beta)
+            assert want["gap"] >= 1e-5, (what, b, want["gap"])
+        else:
+            want = wants[b]
+        assert (trace[b, lx:] == -1).all(), (what, b, "trace rows past lx")
         assert np.array_equal(trace[b], want["trace"]), (what, b, trace[b][:lx].tolist(), want["trace"][:lx].tolist())
         for r in range(W):
             pre, sc, l = want["nbest"][r] if r < len(want["nbest"]) else ((), -np.inf, 0.0)
@@ -265,15 +272,40 @@ def check_equals_search(crf, x, lxs, W, C, blank, lm, ref, alpha, beta, what):
     return trace
 
 
-@pytest.mark.parametrize("closed", [False, True], ids=["pruned", "suffix-closed"])
-def test_back_off_depth(crf, closed):
+@pytest.mark.parametrize("closed,order", [(False, 5), (True, 5), (False, 8), (True, 8)], ids=["pruned", "suffix-closed", "pruned-order8", "suffix-closed-order8"])
+def test_back_off_depth(crf, closed, order):
     """beam_lm_ref.back_off_case: an order-5 model of unigrams and ONE 5-gram chain -- from the state of (0 1 2 3) every class but 4 backs
     off four times down to the root (suffix-closed: through four sparse rows of the tables; pruned: the tables skip the contexts the model
-    does not hold).  Equality with the reference search."""
-    ng, x, (V, W, C, T, blank, alpha, beta) = beam_lm_ref.back_off_case(closed)
+    does not hold) -- and the same at order 8, the largest the tables and the kernel's walk take (kNgramMaxOrder): from the state of
+    (0 .. 6) seven sparse rows, then the root's.  Equality with the reference search."""
+    ng, x, (V, W, C, T, blank, alpha, beta) = beam_lm_ref.back_off_case(closed, order)
     lm, ref = crf.NgramLM.from_ngrams(ng, V), ngram_ref.Ref(ng, V)
-    tr = check_equals_search(crf, x, [T], W, C, blank, lm, ref, alpha, beta, "order 5")
-    assert (0, 1, 2, 3, 4) in beam_ref.spell(tr[0], T, W)
+    assert lm.order == order
+    tr = check_equals_search(crf, x, [T], W, C, blank, lm, ref, alpha, beta, f"order {order}")
+    assert tuple(range(order)) in beam_ref.spell(tr[0], T, W)
+
+
+@pytest.mark.parametrize("case", beam_lm_ref.LM_TIE_CASES, ids=lambda c: "seed%d-V%d-W%d-C%d-T%d" % c[:5] + ("-live" if c[10] is None else "-zero%d" % c[10]))
+def test_exact_ties_under_a_live_lm(crf, case):
+    """beam_lm_ref.LM_TIE_CASES: grouped inputs (through bf16: one set of values in all three dtypes) under a model whose values depend
+    on the groups only, so candidates tie EXACTLY in the fused score, in fp64 and in the kernel's arithmetic alike, while alpha and beta
+    are not 0 and the heads of the rows jump (tests/test_ctc_beam_lm_api.py holds the cases to their conditions; the two that guard
+    equality are asserted here again per lx: no two candidates among the ranks 0 .. W that do not tie come nearer than 1e-3 relative, and
+    no tie is decided by unequal keys).  replay counts a tie as no excess whichever way it went; here the GPU's trace, label sequences and
+    lengths must EQUAL the reference's at lx = T, T - 1 and 1, in fp32, bf16 and fp16: a stay that loses a tie to an extension, the higher
+    slot or the higher place first, a head or a next head taken from the wrong end of its ties changes a trace word."""
+    seed, V, W, C, T, blank, G, order, alpha, beta, zero_group = case
+    x, ng = beam_lm_ref.lm_tie_inputs(case)
+    lm, ref = crf.NgramLM.from_ngrams(ng, V), ngram_ref.Ref(ng, V)
+    lxs = (T, T - 1, 1)
+    wants = []
+    for lx in lxs:
+        a = beam_lm_ref.audit_ties(x, lx, W, C, blank, ref, alpha, beta)
+        assert a["gap"] >= 1e-3 and a["key_level"] == 0, (case, lx, a)
+        wants.append(beam_lm_ref.search(x, lx, W, W, C, blank, ref, alpha, beta))
+    assert not np.array_equal(wants[0]["trace"], beam_ref.search(x, T, W, W, C, blank)["trace"])
+    for dtype in sorted(DTYPES):
+        check_equals_search(crf, np.stack([x] * 3), lxs, W, C, blank, lm, ref, alpha, beta, f"{case} {dtype}", dtype, wants)
 
 
 def test_row_search_edges(crf):
@@ -317,6 +349,49 @@ def test_same_bits_across_calls_batches_and_poison(crf, dtype):
     x64 = xg.cpu().double().numpy()
     for b in (0, 2):
         check_against_replay(x64[b], lx[b], W, C, blank, ref, 0.7, 1.0, first[0][b], first[1][b], first[2][b], first[3][b], first[4][b], True, dtype)
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_long_traces_at_the_widest_beam(crf, dtype):
+    """V = 9, C = 8, W = nbest = 64, T = 130 under an order-3 model: the back-trace takes the trace through lm_n's LDS in chunks of 64
+    frames x W words -- at W = 64 all of it -- three chunks at lx = 130 and 129, two that end on the boundary at 128, one frame past a
+    chunk at 65, one chunk at 64 and a single frame.  Replay per utterance, and the label sequences of ALL 64 ranks are those the trace
+    spells."""
+    V, W, C, T, blank = 9, 64, 8, 130, 4
+    lxs = [130, 129, 128, 65, 64, 1]
+    alpha, beta = 0.7, 2.0                                          # (an insertion bonus: the beam's label sequences pass 64 labels)
+    lm, ref = model(5, V, 3)
+    rng = np.random.default_rng(130)
+    xc = torch.log_softmax(torch.tensor((2.0 * rng.standard_normal((len(lxs), T, V))).astype(np.float32)), -1).to(DTYPES[dtype])
+    hyps, lens, scores, trace, lms = run(crf, xc.to("cuda:0"), lxs, W, W, C, blank, lm, alpha, beta)
+    x64 = xc.double().numpy()
+    for b, lx in enumerate(lxs):
+        check_against_replay(x64[b], lx, W, C, blank, ref, alpha, beta, hyps[b], lens[b], scores[b], trace[b], lms[b], False, f"long {dtype}")
+        pre = beam_ref.spell(trace[b], lx, W)
+        assert lx == 1 or all(p is not None for p in pre), (dtype, lx)
+        for r in range(W):
+            want = pre[r] or ()
+            assert lens[b, r] == len(want) and tuple(hyps[b, r, :lens[b, r]]) == want and (hyps[b, r, lens[b, r]:] == blank).all(), (dtype, lx, r)
+    assert max(lens[0]) > 64                                        # (a label sequence longer than one chunk of frames)
+
+
+def test_a_batch_larger_than_the_device(crf):
+    """N = 300 utterances -- more workgroups than the device has compute units -- made of 5 distinct inputs in turn, T = 6, W = 8, ragged
+    lx with 0, an order-3 model at alpha = 0.7, beta = 1: every utterance's outputs are the bits of a call on the 5 alone."""
+    N, T, V, W, C, blank = 300, 6, 11, 8, 8, 2
+    assert N > torch.cuda.get_device_properties(0).multi_processor_count
+    lm, ref = model(7, V, 3)
+    rng = np.random.default_rng(300)
+    x5 = torch.tensor((2.0 * rng.standard_normal((5, T, V))).astype(np.float32))
+    lx5 = [6, 0, 3, 5, 1]
+    idx = np.arange(N) % 5
+    base = run(crf, x5.to("cuda:0"), lx5, W, W, C, blank, lm, 0.7, 1.0, fused=True)
+    big = run(crf, x5[idx].contiguous().to("cuda:0"), [lx5[i] for i in idx], W, W, C, blank, lm, 0.7, 1.0, fused=True)
+    for k in range(5):
+        assert np.array_equal(big[k].view(np.int32), base[k][idx].view(np.int32)), k
+    x64 = x5.double().numpy()
+    for b in range(5):
+        check_against_replay(x64[b], lx5[b], W, C, blank, ref, 0.7, 1.0, base[0][b], base[1][b], base[2][b], base[3][b], base[4][b], True, f"batch b={b}")
 
 
 def test_edges(crf):

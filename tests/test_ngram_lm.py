@@ -5,7 +5,10 @@ import pytest
 
 from tests import ngram_ref
 
-RTOL = 1e-6          # the tables hold fp32 values and the walk adds them in fp32: 2^-24 relative per term, at most order + 1 terms
+RTOL = 1e-6          # the tables hold fp32 values and the walk adds them in fp32: 2^-24 relative per term, at most order + 1 terms --
+                     # of a look-up relative to the sum of the terms' magnitudes (ngram_ref.Ref.mass): a back-off weight above 0 cancels
+                     # against the values below 0 (order 8, history (7 0 7 5 0 2), class 3: the terms sum to -0.017), and one rounding of
+                     # every value plus at most 8 rounded sums are 9 * 2^-24 = 5.4e-7 of that mass
 
 
 @pytest.fixture(scope="module")
@@ -19,7 +22,7 @@ def history_of(lm, s):
 
 
 @pytest.mark.parametrize("bos,unk", [(True, False), (False, True), (True, True), (False, False)])
-@pytest.mark.parametrize("order", [1, 2, 3, 5])
+@pytest.mark.parametrize("order", [1, 2, 3, 5, 8])
 def test_tables_against_the_textbook(NgramLM, order, bos, unk):
     """For every state and every token lm.lookup equals the textbook value from that state's history within 1e-6 relative, and the next
     state is the longest kept suffix of history + token; the tables have the promised shape; score() of random sequences matches."""
@@ -44,7 +47,8 @@ def test_tables_against_the_textbook(NgramLM, order, bos, unk):
         for c in range(V):
             lp, nx = lm.lookup(s, c)
             want = ref.cond(h, c)
-            assert abs(lp - want) <= RTOL * abs(want), (h, c, lp, want)
+            assert abs(lp - want) <= RTOL * ref.mass(h, c), (h, c, lp, want)
+            assert order > 5 or abs(lp - want) <= RTOL * abs(want), (h, c, lp, want)     # (the narrower bound the models up to order 5 also meet)
             assert history_of(lm, nx) == ref.known_suffix(h + (c,)), (h, c, history_of(lm, nx))
     rng = np.random.default_rng(order)
     for _ in range(50):
@@ -71,7 +75,7 @@ def test_dict_forms_and_missing_unigrams(NgramLM):
         NgramLM()
 
 
-@pytest.mark.parametrize("order,bos,unk", [(1, False, False), (3, True, True), (5, True, False)])
+@pytest.mark.parametrize("order,bos,unk", [(1, False, False), (3, True, True), (5, True, False), (8, True, True)])
 def test_arpa_round_trip(NgramLM, tmp_path, order, bos, unk):
     """The model read back from a written file has the tables of the model built from the dict, bit for bit; </s> entries are dropped."""
     V = 7
@@ -83,6 +87,31 @@ def test_arpa_round_trip(NgramLM, tmp_path, order, bos, unk):
         assert np.array_equal(t.view(np.int32), b.host_tables()[name].view(np.int32)), name
     ref = ngram_ref.Ref(ng, V)
     assert abs(a.score([1, 2, 3, 1]) - ref.score([1, 2, 3, 1])) <= 1e-5 * abs(ref.score([1, 2, 3, 1]))
+
+
+def test_order_nine_is_refused(NgramLM, tmp_path):
+    """MAX_ORDER = 8 is the largest order (the kernel's walk is bounded by it): a chain of 8 tokens with its prefixes builds and walks
+    seven sparse rows, the same chain with its 9-gram raises in from_ngrams, and a file with a 9-gram section raises at that section's
+    line, whatever the section holds."""
+    import cat_amd.ngram_lm
+    assert cat_amd.ngram_lm.MAX_ORDER == 8
+    V = 3
+    ng = {(c,): (-0.5, -0.25) for c in range(V)}
+    for n in range(2, 9):
+        ng[(0, 1) * (n // 2) + (0,) * (n % 2)] = (-0.125 * n, -0.5 if n < 8 else 0.0)
+    lm = NgramLM.from_ngrams(ng, V)
+    assert lm.order == 8 and max(len(h) for h in lm.state_history) == 7
+    ref = ngram_ref.Ref(ng, V)
+    seq = [0, 1, 0, 1, 0, 1, 0, 1, 2, 0, 1]
+    assert abs(lm.score(seq) - ref.score(seq)) <= RTOL * sum(abs(ref.cond(tuple(seq[:i]), c)) for i, c in enumerate(seq))
+    nine = {**ng, (0, 1, 0, 1, 0, 1, 0, 1): (-1.0, -0.5), (0, 1, 0, 1, 0, 1, 0, 1, 0): (-1.0, 0.0)}
+    with pytest.raises(ValueError, match=r"NgramLM: order 9 above 8"):
+        NgramLM.from_ngrams(nine, V)
+    path = ngram_ref.write_arpa(nine, str(tmp_path / "nine.arpa"))
+    header = 1 + open(path).read().split("\n").index("\\9-grams:")
+    assert NgramLM.from_arpa(ngram_ref.write_arpa(ng, str(tmp_path / "eight.arpa")), V).order == 8
+    with pytest.raises(ValueError, match=rf"nine\.arpa: line {header}: order 9 above 8"):
+        NgramLM.from_arpa(path, V)
 
 
 GOOD = ["\\data\\", "ngram 1=4", "ngram 2=2", "", "\\1-grams:", "-99\t<s>\t-0.3", "-1.0\t0\t-0.5", "-0.7\t1\t-0.2", "-1.5\t</s>", "", "\\2-grams:",
