@@ -1,6 +1,7 @@
 // cat_amd/csrc/crf_host_ctc.hip -- the host side of the surfaces on the plain CTC lattice, which share nothing with the loss call
 // (crf_host.hip) but crf_host_util.h: forced alignment (crf_ctc_align*, k_align.hip), hypothesis scores (crf_ctc_score*, k_score.hip), their
-// weighted gradient (crf_ctc_score_grad*, k_score_grad.hip), sampled / best-path label sequences (crf_ctc_sample, k_sample.hip), the
+// weighted gradient (crf_ctc_score_grad*, k_score_grad.hip), both on hypotheses that lie on the device as padded rows (crf_ctc_score_rows,
+// crf_ctc_score_grad_rows, k_rows.hip), sampled / best-path label sequences (crf_ctc_sample, k_sample.hip), the
 // prefix beam search (crf_ctc_beam, k_beam.hip; with an n-gram LM: crf_ctc_beam_lm, k_beam_lm.hip, crf_ngram_tables_check) and -- on token sequences alone, no lattice -- the edit distance of hypotheses to
 // their transcripts (crf_ctc_edit_distance, k_edit.hip) --
 // argument checks, workspace sections, kernel choice, the C-ABI entry points of include/ctc_crf_hip.h.  Every error is answered before
@@ -44,9 +45,9 @@ static int check_ws(int64_t ws_bytes, int64_t need) {
     if (ws_bytes < need) { set_error("workspace too small: need " + std::to_string(need)); return CRF_ERR_WORKSPACE; }
     return CRF_OK;
 }
-// their workspaces: one to three sections, laid down as the loss call's are (crf_host_util.h)
+// their workspaces: one to eight sections, laid down as the loss call's are (crf_host_util.h)
 struct SideWs {
-    WsSection sec[3];
+    WsSection sec[8];
     int nsec = 0;
     int64_t total = 0, gap = ws_gap_bytes();
     SideWs &add(const char *name, int64_t bytes) { sec[nsec++] = WsSection{name, total, bytes}; total = al(total + bytes) + gap; return *this; }
@@ -239,6 +240,175 @@ static int score_grad_call(const char *who, const void *act, int dtype, int time
     if (dtype < 0) return launch_score_grad<float, false>(p, st, max_hyp_len);
     p.lse = (const float *)((char *)ws + w.sec[kSgLse].off);
     return with_dtype(dtype, [&](auto e) { return launch_score_grad<decltype(e), true>(p, st, max_hyp_len); });
+}
+
+// ---- scores and their gradient on hypotheses that lie on the device as padded rows (k_rows.hip) ----
+// The host knows a bound len_cap on the lengths, not the lengths: the plan kernel gives every hypothesis the class of its own length, every
+// class up to len_cap's runs the call's existing kernel on a masked length row, the merge kernel picks each hypothesis's result.
+// Workspace: the gradient's occ [H][T][S] fp64 (S = 64 NR of len_cap's class) and hscore [H] in front, then hyp_off [H], cls [H],
+// len [ncls][H], cscore [ncls][H], cinvalid [ncls][H] and -- raw network output -- the lse values [B][T].
+enum RowsWsSec { kRwOcc, kRwHscore, kRwOff, kRwCls, kRwLen, kRwCscore, kRwCinvalid, kRwLse, kRwCount };
+static const char *const kRowsWsNames[kRwCount] = {"occ", "hscore", "hyp_off", "cls", "len", "cscore", "cinvalid", "lse"};
+static const char *rows_who(bool grad) { return grad ? "crf_ctc_score_grad_rows" : "crf_ctc_score_rows"; }
+// < 0 with the message set; the sections of a score call are the gradient's without the first two
+static int64_t rows_ws_bytes(bool grad, int64_t B, int64_t H, int64_t T, int64_t V, int64_t len_cap, int dtype, SideWs *out = nullptr) {
+    const std::string who = rows_who(grad);
+    if (dtype < -1 || dtype > 2) { set_error(who + ": dtype must be -1 (f32 log-probs), 0 (f32), 1 (bf16) or 2 (f16)"); return -CRF_ERR_ARG; }
+    if (B <= 0 || H <= 0 || T <= 0 || V <= 0 || H > INT32_MAX || V > INT32_MAX || len_cap < 0) { set_error(who + ": bad B/H/T/V/len_cap"); return -CRF_ERR_ARG; }
+    if (B > INT32_MAX / T) { set_error(who + ": B * T > INT32_MAX"); return -CRF_ERR_ARG; }
+    const int64_t limit = grad ? kScoreGradMaxLen : kMaxCtcLabelLen;
+    if (len_cap > limit) { set_error(who + ": len_cap > " + std::to_string(limit) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
+    if (grad && V > kScoreGradMaxV) { set_error(who + ": V > " + std::to_string(kScoreGradMaxV) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
+    const int64_t ncls = rows_class((int)len_cap) + 1, hb = H * (int64_t)sizeof(int);
+    SideWs w;
+    if (grad) {
+        const int64_t S = 64ll << (ncls - 1);
+        if (H > (INT64_MAX / 16) / (T * S)) { set_error(who + ": H * T * states too large"); return -CRF_ERR_ARG; }
+        w.add(kRowsWsNames[kRwOcc], H * T * S * (int64_t)sizeof(double)).add(kRowsWsNames[kRwHscore], hb);
+    }
+    w.add(kRowsWsNames[kRwOff], hb).add(kRowsWsNames[kRwCls], hb).add(kRowsWsNames[kRwLen], ncls * hb).add(kRowsWsNames[kRwCscore], ncls * hb)
+     .add(kRowsWsNames[kRwCinvalid], ncls * hb);
+    if (dtype >= 0) w.add(kRowsWsNames[kRwLse], B * T * (int64_t)sizeof(float));
+    if (out) *out = w;
+    return w.total;
+}
+// the checks of both entry points, in the order of include/ctc_crf_hip.h; CRF_OK: w holds the sections
+static int rows_check(bool grad, const void *act, int dtype, int blank, const int32_t *hyps, int64_t hyp_stride, const int32_t *hyp_len,
+                      const int32_t *hyp_utt, const int32_t *lx, int64_t B, int64_t H, int64_t T, int64_t V, int64_t len_cap, const void *out,
+                      const void *ws, int64_t ws_bytes, SideWs &w) {
+    const std::string who = rows_who(grad);
+    if (!act || !hyps || !hyp_len || !hyp_utt || !lx || !out || !ws) { set_error(who + ": null argument"); return CRF_ERR_ARG; }
+    if (dtype < -1 || dtype > 2) return (int)-rows_ws_bytes(grad, 1, 1, 1, 1, 0, dtype);
+    if (B <= 0 || H <= 0 || T <= 0 || V <= 0 || hyp_stride <= 0 || len_cap < 0) { set_error(who + ": bad B/H/T/V/hyp_stride/len_cap"); return CRF_ERR_ARG; }
+    if (H > INT32_MAX / hyp_stride) { set_error(who + ": H * hyp_stride > INT32_MAX"); return CRF_ERR_ARG; }
+    if (B > INT32_MAX / T) { set_error(who + ": B * T > INT32_MAX"); return CRF_ERR_ARG; }
+    if (V > INT32_MAX) { set_error(who + ": bad V"); return CRF_ERR_ARG; }
+    if (const int rc = check_blank(blank, V)) return rc;
+    const int64_t need = rows_ws_bytes(grad, B, H, T, V, len_cap, dtype, &w);
+    if (need < 0) return (int)-need;
+    return check_ws(ws_bytes, need);
+}
+static const char *const kRowsScoreNames[kRowsClasses] = {"crf_ctc_score_wave_kernel<1>", "crf_ctc_score_wave_kernel<2>", "crf_ctc_score_wave_kernel<4>", "crf_ctc_score_wave_kernel<8>",
+                                                          "crf_ctc_score_wg_kernel<2>", "crf_ctc_score_wg_kernel<4>", "crf_ctc_score_wg_kernel<8>"};
+// the score kernel of class c on all H hypotheses (p.hyp_len: the class's masked lengths); the lse values are in place
+template <typename E, bool LSE>
+static int launch_score_class(int c, const ScoreParams &p, hipStream_t st) {
+    const dim3 wgrid((unsigned)((p.H + kScoreWaves - 1) / kScoreWaves)), wblock(kScoreWaves * 64), ggrid((unsigned)p.H), gblock(kCtcThreads);
+    switch (c) {
+    case 0: return launch<crf_ctc_score_wave_kernel<1, E, LSE>>(kRowsScoreNames[0], wgrid, wblock, 0, st, p);
+    case 1: return launch<crf_ctc_score_wave_kernel<2, E, LSE>>(kRowsScoreNames[1], wgrid, wblock, 0, st, p);
+    case 2: return launch<crf_ctc_score_wave_kernel<4, E, LSE>>(kRowsScoreNames[2], wgrid, wblock, 0, st, p);
+    case 3: return launch<crf_ctc_score_wave_kernel<8, E, LSE>>(kRowsScoreNames[3], wgrid, wblock, 0, st, p);
+    case 4: return launch<crf_ctc_score_wg_kernel<2, E, LSE>>(kRowsScoreNames[4], ggrid, gblock, 0, st, p);
+    case 5: return launch<crf_ctc_score_wg_kernel<4, E, LSE>>(kRowsScoreNames[5], ggrid, gblock, 0, st, p);
+    default: return launch<crf_ctc_score_wg_kernel<kCtcRegs, E, LSE>>(kRowsScoreNames[6], ggrid, gblock, 0, st, p);
+    }
+}
+// ... and behind it stages 1 and 2 of the gradient of wave class c, their rows of occ p.S doubles apart
+template <typename E, bool RAW>
+static int launch_score_grad_class(int c, const ScoreParams &sp, const ScoreGradRawParams &p, hipStream_t st) {
+    const dim3 grid((unsigned)((p.H + kScoreWaves - 1) / kScoreWaves)), block(kScoreWaves * 64);
+    const ScoreGradParams &pl = p;
+    if (const int rc = launch_score_class<E, RAW>(c, sp, st)) return rc;
+    auto stages = [&](auto nr) {
+        constexpr int NR = decltype(nr)::value;
+        if constexpr (RAW) {
+            if (const int r = launch<crf_rows_grad_alpha_raw_kernel<NR, E>>("crf_rows_grad_alpha_raw_kernel", grid, block, 0, st, p)) return r;
+            return launch<crf_rows_grad_beta_raw_kernel<NR, E>>("crf_rows_grad_beta_raw_kernel", grid, block, 0, st, p);
+        } else {
+            if (const int r = launch<crf_rows_grad_alpha_kernel<NR>>("crf_rows_grad_alpha_kernel", grid, block, 0, st, pl)) return r;
+            return launch<crf_rows_grad_beta_kernel<NR>>("crf_rows_grad_beta_kernel", grid, block, 0, st, pl);
+        }
+    };
+    switch (c) {
+    case 0: return stages(std::integral_constant<int, 1>{});
+    case 1: return stages(std::integral_constant<int, 2>{});
+    case 2: return stages(std::integral_constant<int, 4>{});
+    default: return stages(std::integral_constant<int, 8>{});
+    }
+}
+// what both calls launch first: the plan, and -- raw network output -- the frames' lse values, ONCE for all classes
+static int launch_rows_front(const RowsPlanParams &pp, const void *act, int dtype, const ScoreParams &p, hipStream_t st) {
+    if (const int rc = launch<crf_rows_plan_kernel>("crf_rows_plan_kernel", dim3((unsigned)((pp.H + kRowsThreads - 1) / kRowsThreads)), dim3(kRowsThreads), 0, st, pp)) return rc;
+    if (dtype < 0) return CRF_OK;
+    return with_dtype(dtype, [&](auto e) { return launch_row_lse<decltype(e)>(act, p.lx, p.B, p.T, p.V, p.xs_b, p.xs_t, const_cast<float *>(p.lse), st); });
+}
+static int launch_rows_merge(const RowsMergeParams &mp, hipStream_t st) {
+    return launch<crf_rows_merge_kernel>("crf_rows_merge_kernel", dim3((unsigned)((mp.H + kRowsThreads - 1) / kRowsThreads)), dim3(kRowsThreads), 0, st, mp);
+}
+// crf_ctc_score_rows: dtype < 0 log-probs, else raw output of that dtype
+static int score_rows_call(const void *act, int dtype, int time_major, int blank, const int32_t *hyps, int64_t hyp_stride, const int32_t *hyp_len,
+                           const int32_t *hyp_utt, const int32_t *lx, int64_t B, int64_t H, int64_t T, int64_t V, int64_t len_cap, float *score,
+                           int32_t *invalid, void *ws, int64_t ws_bytes, hipStream_t st) {
+    SideWs w;
+    if (const int rc = rows_check(false, act, dtype, blank, hyps, hyp_stride, hyp_len, hyp_utt, lx, B, H, T, V, len_cap, score, ws, ws_bytes, w)) return rc;
+    auto sec = [&](int k) { return (char *)ws + w.sec[k - kRwOff].off; };   // (a score call has no occ and no hscore)
+    const int ncls = rows_class((int)len_cap) + 1;
+    const RowsPlanParams pp{hyp_len, (int)H, (int)hyp_stride, (int)len_cap, ncls, (int *)sec(kRwOff), (int *)sec(kRwCls), (int *)sec(kRwLen)};
+    float *cscore = (float *)sec(kRwCscore);
+    int *cinvalid = (int *)sec(kRwCinvalid);
+    ScoreParams p{};
+    set_act(p, act, lx, B, T, V, blank, time_major);
+    p.labels = hyps; p.hyp_off = pp.hyp_off; p.hyp_utt = hyp_utt; p.H = (int)H;
+    if (dtype >= 0) p.lse = (const float *)sec(kRwLse);
+    if (const int rc = launch_rows_front(pp, act, dtype, p, st)) return rc;
+    for (int c = 0; c < ncls; ++c) {
+        p.hyp_len = pp.len_c + (int64_t)c * H; p.score = cscore + (int64_t)c * H; p.invalid = cinvalid + (int64_t)c * H;
+        const int rc = dtype < 0 ? launch_score_class<float, false>(c, p, st)
+                                 : with_dtype(dtype, [&](auto e) { return launch_score_class<decltype(e), true>(c, p, st); });
+        if (rc) return rc;
+    }
+    g_score_kernel = kRowsScoreNames[ncls - 1];
+    return launch_rows_merge(RowsMergeParams{pp.cls, cscore, cinvalid, (int)H, ncls, score, nullptr, invalid}, st);
+}
+// crf_ctc_score_grad_rows: per wave class the score kernel and stages 1 and 2 into ONE occ section, the merge, then the one reduce launch
+// on the merged scores and the true lengths (it reads the length of a live hypothesis only)
+static int score_grad_rows_call(const void *act, int dtype, int time_major, int blank, const int32_t *hyps, int64_t hyp_stride,
+                                const int32_t *hyp_len, const int32_t *hyp_utt, const int32_t *lx, const float *weight, int64_t B, int64_t H,
+                                int64_t T, int64_t V, int64_t len_cap, float *score, int32_t *invalid, float *grad, void *ws, int64_t ws_bytes,
+                                hipStream_t st) {
+    static const char *const names[kRowsWaveClasses] = {"crf_rows_grad_alpha_kernel<1>", "crf_rows_grad_alpha_kernel<2>",
+                                                        "crf_rows_grad_alpha_kernel<4>", "crf_rows_grad_alpha_kernel<8>"};
+    static const char *const raw_names[3][kRowsWaveClasses] = {
+        {"crf_rows_grad_alpha_raw_kernel<1, f32>", "crf_rows_grad_alpha_raw_kernel<2, f32>", "crf_rows_grad_alpha_raw_kernel<4, f32>", "crf_rows_grad_alpha_raw_kernel<8, f32>"},
+        {"crf_rows_grad_alpha_raw_kernel<1, bf16>", "crf_rows_grad_alpha_raw_kernel<2, bf16>", "crf_rows_grad_alpha_raw_kernel<4, bf16>", "crf_rows_grad_alpha_raw_kernel<8, bf16>"},
+        {"crf_rows_grad_alpha_raw_kernel<1, f16>", "crf_rows_grad_alpha_raw_kernel<2, f16>", "crf_rows_grad_alpha_raw_kernel<4, f16>", "crf_rows_grad_alpha_raw_kernel<8, f16>"}};
+    SideWs w;
+    if (const int rc = rows_check(true, act, dtype, blank, hyps, hyp_stride, hyp_len, hyp_utt, lx, B, H, T, V, len_cap, grad, ws, ws_bytes, w)) return rc;
+    auto sec = [&](int k) { return (char *)ws + w.sec[k].off; };
+    const int ncls = rows_class((int)len_cap) + 1;
+    const RowsPlanParams pp{hyp_len, (int)H, (int)hyp_stride, (int)len_cap, ncls, (int *)sec(kRwOff), (int *)sec(kRwCls), (int *)sec(kRwLen)};
+    float *cscore = (float *)sec(kRwCscore);
+    int *cinvalid = (int *)sec(kRwCinvalid);
+    ScoreGradRawParams p{};
+    set_act(p, act, lx, B, T, V, blank, time_major);
+    p.labels = hyps; p.hyp_off = pp.hyp_off; p.hyp_utt = hyp_utt; p.H = (int)H;
+    p.weight = weight; p.grad = grad;         // (score and invalid stay null in the class passes: the merge writes the caller's)
+    p.occ = (float *)sec(kRwOcc);
+    p.S = 64 << (ncls - 1);
+    p.FB = (int)std::min<int64_t>(kScoreGradFrames, std::max<int64_t>(1, kScoreGradMaxV / V));
+    if (dtype >= 0) p.lse = (const float *)sec(kRwLse);
+    ScoreParams sp{};
+    set_act(sp, act, lx, B, T, V, blank, time_major);
+    sp.labels = hyps; sp.hyp_off = pp.hyp_off; sp.hyp_utt = hyp_utt; sp.H = (int)H; sp.lse = p.lse;
+    if (const int rc = launch_rows_front(pp, act, dtype, sp, st)) return rc;
+    for (int c = 0; c < ncls; ++c) {
+        sp.hyp_len = p.hyp_len = pp.len_c + (int64_t)c * H;
+        sp.score = p.hscore = cscore + (int64_t)c * H;
+        sp.invalid = cinvalid + (int64_t)c * H;
+        const int rc = dtype < 0 ? launch_score_grad_class<float, false>(c, sp, p, st)
+                                 : with_dtype(dtype, [&](auto e) { return launch_score_grad_class<decltype(e), true>(c, sp, p, st); });
+        if (rc) return rc;
+    }
+    g_score_grad_kernel = dtype < 0 ? names[ncls - 1] : raw_names[dtype][ncls - 1];
+    p.hscore = (float *)sec(kRwHscore);
+    if (const int rc = launch_rows_merge(RowsMergeParams{pp.cls, cscore, cinvalid, (int)H, ncls, score, p.hscore, invalid}, st)) return rc;
+    p.hyp_len = hyp_len;
+    const int64_t nbt = (p.T + p.FB - 1) / p.FB;
+    const dim3 rgrid((unsigned)(p.B * nbt)), rblock(kScoreGradReduceThreads);
+    const size_t lds = (size_t)p.FB * p.V * sizeof(float);
+    if (dtype < 0) return launch<crf_ctc_score_grad_reduce_kernel>("crf_ctc_score_grad_reduce_kernel", rgrid, rblock, lds, st, (const ScoreGradParams &)p);
+    return with_dtype(dtype, [&](auto e) { return launch<crf_ctc_score_grad_reduce_raw_kernel<decltype(e)>>("crf_ctc_score_grad_reduce_raw_kernel", rgrid, rblock, lds, st, p); });
 }
 
 // ---- sampled / best-path label sequences (k_sample.hip) ----
@@ -441,6 +611,39 @@ int crf_ctc_score_grad_logits(const void *act, int dtype, int time_major, int bl
     if (dtype < 0) return bad_dtype("crf_ctc_score_grad_logits");
     return score_grad_call("crf_ctc_score_grad_logits", act, dtype, time_major, blank, labels, hyp_off, hyp_len, hyp_utt, lx, weight, B, H, T, V,
                            max_hyp_len, score, invalid, grad, ws, ws_bytes, (hipStream_t)stream_);
+}
+
+int64_t crf_ctc_score_rows_workspace_bytes(int64_t B, int64_t H, int64_t T, int64_t V, int64_t len_cap, int dtype) {
+    return or_minus1(rows_ws_bytes(false, B, H, T, V, len_cap, dtype));
+}
+
+int crf_ctc_score_rows(const void *act, int dtype, int time_major, int blank, const int32_t *hyps, int64_t hyp_stride, const int32_t *hyp_len,
+                       const int32_t *hyp_utt, const int32_t *lx, int64_t B, int64_t H, int64_t T, int64_t V, int64_t len_cap, float *score,
+                       int32_t *invalid, void *ws, int64_t ws_bytes, void *stream_) {
+    return score_rows_call(act, dtype, time_major, blank, hyps, hyp_stride, hyp_len, hyp_utt, lx, B, H, T, V, len_cap, score, invalid, ws, ws_bytes,
+                           (hipStream_t)stream_);
+}
+
+int64_t crf_ctc_score_grad_rows_workspace_bytes(int64_t B, int64_t H, int64_t T, int64_t V, int64_t len_cap, int dtype) {
+    return or_minus1(rows_ws_bytes(true, B, H, T, V, len_cap, dtype));
+}
+
+int crf_ctc_score_grad_rows(const void *act, int dtype, int time_major, int blank, const int32_t *hyps, int64_t hyp_stride,
+                            const int32_t *hyp_len, const int32_t *hyp_utt, const int32_t *lx, const float *weight, int64_t B, int64_t H,
+                            int64_t T, int64_t V, int64_t len_cap, float *score, int32_t *invalid, float *grad, void *ws, int64_t ws_bytes,
+                            void *stream_) {
+    return score_grad_rows_call(act, dtype, time_major, blank, hyps, hyp_stride, hyp_len, hyp_utt, lx, weight, B, H, T, V, len_cap, score, invalid,
+                                grad, ws, ws_bytes, (hipStream_t)stream_);
+}
+
+int crf_debug_score_rows_ws_sections(int grad, int64_t B, int64_t H, int64_t T, int64_t V, int64_t len_cap, int dtype, int64_t *out, int n_out) {
+    SideWs w;
+    if (rows_ws_bytes(grad != 0, B, H, T, V, len_cap, dtype, &w) < 0) return -1;
+    return copy_sections(w.sec, w.nsec, out, n_out);
+}
+const char *crf_debug_score_rows_ws_section_names(int grad) {
+    static const std::string s[2] = {join_names(kRowsWsNames + kRwOff, kRwCount - kRwOff), join_names(kRowsWsNames, kRwCount)};
+    return s[grad != 0].c_str();
 }
 
 int64_t crf_ctc_sample_workspace_bytes(int64_t B, int64_t T, int64_t V, int64_t K) { return or_minus1(sample_ws_bytes(B, T, V, K)); }

@@ -89,8 +89,44 @@ template <int NR, typename E> __global__ void crf_ctc_score_grad_alpha_raw_kerne
 template <int NR, typename E> __global__ void crf_ctc_score_grad_beta_raw_kernel(ScoreGradRawParams p);
 template <typename E> __global__ void crf_ctc_score_grad_reduce_raw_kernel(ScoreGradRawParams p);          // dynamic LDS: FB x V words
 
+// ---- k_rows.hip ----
+constexpr int kRowsThreads = 256;         // hypotheses per workgroup of the plan and merge kernels
+constexpr int kRowsClasses = 7;           // the score call's instantiations: wave NR 1, 2, 4, 8, then workgroup NR 2, 4, 8
+constexpr int kRowsWaveClasses = 4;       // ... the first four: the gradient's
+constexpr int kRowsNoClass = -1;          // a length < 0, above the call's len_cap or above the row stride
+// the class of a hypothesis of L >= 0 labels: the instantiation launch_score (crf_host_ctc.hip) takes for max_hyp_len = L
+__host__ __device__ constexpr int rows_class(int L) {
+    return L <= 31 ? 0 : L <= 63 ? 1 : L <= 127 ? 2 : L <= 255 ? 3 : L <= 511 ? 4 : L <= 1023 ? 5 : 6;
+}
+static_assert(2 * 255 + 1 <= kScoreWaveMaxStates && 2 * 256 + 1 > kScoreWaveMaxStates && kScoreGradMaxLen == 255 && kCtcThreads == 512 && kCtcRegs == 8,
+              "rows_class follows the wave and workgroup geometries of k_score.hip");
+// Kernel arguments of the plan: hypothesis h is the first hyp_len[h] words of row h, rows `stride` words apart
+struct RowsPlanParams {
+    const int *hyp_len;         // [H]
+    int H, stride, len_cap, ncls;   // ncls = rows_class(len_cap) + 1 classes are launched
+    int *hyp_off;               // [H] h * stride
+    int *cls;                   // [H] the class, or kRowsNoClass
+    int *len_c;                 // [ncls][H] hyp_len[h] where cls[h] = c, else -1
+};
+// ... and of the merge: the per-class results [ncls][H] into the caller's vectors (each may be null)
+struct RowsMergeParams {
+    const int *cls;
+    const float *cscore;
+    const int *cinvalid;
+    int H, ncls;
+    float *score, *hscore;
+    int *invalid;
+};
+__global__ void crf_rows_plan_kernel(RowsPlanParams p);
+__global__ void crf_rows_merge_kernel(RowsMergeParams p);
+// stages 1 and 2 of the score gradient with the rows of occ p.S doubles apart (k_score_grad_body.h, ROWS)
+template <int NR> __global__ void crf_rows_grad_alpha_kernel(ScoreGradParams p);   // NR 1, 2, 4, 8
+template <int NR> __global__ void crf_rows_grad_beta_kernel(ScoreGradParams p);
+template <int NR, typename E> __global__ void crf_rows_grad_alpha_raw_kernel(ScoreGradRawParams p);
+template <int NR, typename E> __global__ void crf_rows_grad_beta_raw_kernel(ScoreGradRawParams p);
+
 // ---- k_sample.hip ----
-constexpr int kSampleSmallV = 256;        // rows of up to here: 16 lanes per row and 16 rows per workgroup, beyond: a wave per row and workgroup
+constexpr int kSampleSmallV = 256;       // rows of up to here: 16 lanes per row and 16 rows per workgroup, beyond: a wave per row and workgroup
 constexpr int kSampleMaxV = 8192;         // the row and its running sums are staged in LDS: 32.5 KiB per row at most
 constexpr int kSampleWaves = 4;           // paths (waves) per workgroup of the collapse
 constexpr int kSampleRowThreads(int G) { return G == 16 ? 256 : 64; }

@@ -79,6 +79,20 @@ _lib.crf_ctc_score_grad_logits.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctyp
                                            _vp, _vp, _vp, _vp, _i64, _vp]
 _lib.crf_ctc_score_grad_logits.restype = ctypes.c_int
 _lib.crf_last_score_grad_kernel.restype = ctypes.c_char_p
+_lib.crf_ctc_score_rows_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64, _i64, ctypes.c_int]
+_lib.crf_ctc_score_rows_workspace_bytes.restype = _i64
+_lib.crf_ctc_score_rows.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp,
+                                    _vp, _i64, _vp]
+_lib.crf_ctc_score_rows.restype = ctypes.c_int
+_lib.crf_ctc_score_grad_rows_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64, _i64, ctypes.c_int]
+_lib.crf_ctc_score_grad_rows_workspace_bytes.restype = _i64
+_lib.crf_ctc_score_grad_rows.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
+                                         _vp, _vp, _vp, _vp, _i64, _vp]
+_lib.crf_ctc_score_grad_rows.restype = ctypes.c_int
+_lib.crf_debug_score_rows_ws_sections.argtypes = [ctypes.c_int, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.POINTER(_i64), ctypes.c_int]
+_lib.crf_debug_score_rows_ws_sections.restype = ctypes.c_int
+_lib.crf_debug_score_rows_ws_section_names.argtypes = [ctypes.c_int]
+_lib.crf_debug_score_rows_ws_section_names.restype = ctypes.c_char_p
 _lib.crf_ctc_sample_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64]
 _lib.crf_ctc_sample_workspace_bytes.restype = _i64
 _lib.crf_ctc_sample.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _i64, _i64, _i64, _i64, ctypes.c_uint64, ctypes.c_uint32,
@@ -125,7 +139,7 @@ _lib.crf_build_switches.restype = ctypes.c_char_p
 
 EXPORTED_SYMBOLS = (
     "crf_graph_create", "crf_graph_create_from_arcs", "crf_graph_destroy", "crf_graph_dims", "crf_graph_stats",
-    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_ws_fields", "crf_debug_ws_field_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_ctc_score", "crf_ctc_score_logits_workspace_bytes", "crf_ctc_score_logits", "crf_last_score_kernel", "crf_ctc_score_grad_workspace_bytes", "crf_ctc_score_grad", "crf_ctc_score_grad_logits_workspace_bytes", "crf_ctc_score_grad_logits", "crf_last_score_grad_kernel", "crf_ctc_sample_workspace_bytes", "crf_ctc_sample", "crf_last_sample_kernel", "crf_ctc_beam_workspace_bytes", "crf_ctc_beam", "crf_last_beam_kernel", "crf_ngram_tables_check", "crf_ctc_beam_lm_workspace_bytes", "crf_ctc_beam_lm", "crf_ctc_edit_distance", "crf_last_edit_kernel", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
+    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_ws_fields", "crf_debug_ws_field_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_ctc_score", "crf_ctc_score_logits_workspace_bytes", "crf_ctc_score_logits", "crf_last_score_kernel", "crf_ctc_score_grad_workspace_bytes", "crf_ctc_score_grad", "crf_ctc_score_grad_logits_workspace_bytes", "crf_ctc_score_grad_logits", "crf_last_score_grad_kernel", "crf_ctc_score_rows_workspace_bytes", "crf_ctc_score_rows", "crf_ctc_score_grad_rows_workspace_bytes", "crf_ctc_score_grad_rows", "crf_debug_score_rows_ws_sections", "crf_debug_score_rows_ws_section_names", "crf_ctc_sample_workspace_bytes", "crf_ctc_sample", "crf_last_sample_kernel", "crf_ctc_beam_workspace_bytes", "crf_ctc_beam", "crf_last_beam_kernel", "crf_ngram_tables_check", "crf_ctc_beam_lm_workspace_bytes", "crf_ctc_beam_lm", "crf_ctc_edit_distance", "crf_last_edit_kernel", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
     "crf_debug_set", "crf_debug_unset", "crf_debug_list", "crf_last_den_kernel", "crf_last_call_streams", "crf_last_side_stream", "crf_last_fallback_counts", "crf_build_switches", "crf_last_error", "crf_version",
 )
 
@@ -150,13 +164,15 @@ def last_den_kernel() -> str:
 
 
 def last_score_kernel() -> str:
-    """Template instantiation of the kernel of this thread's last ctc_score call (include/ctc_crf_hip.h crf_last_score_kernel)."""
+    """Template instantiation of the kernel of this thread's last ctc_score call (include/ctc_crf_hip.h crf_last_score_kernel); on device
+    rows, where every hypothesis takes the kernel of its own length class, the highest class launched (the bound's)."""
     return _lib.crf_last_score_kernel().decode()
 
 
 def last_score_grad_kernel() -> str:
     """Template instantiation of the alpha pass of this thread's last ctc_score_grad call (include/ctc_crf_hip.h crf_last_score_grad_kernel);
-    a fused call's carries its element type: "crf_ctc_score_grad_alpha_raw_kernel<4, bf16>"."""
+    a fused call's carries its element type: "crf_ctc_score_grad_alpha_raw_kernel<4, bf16>"; on device rows the highest class launched,
+    "crf_rows_grad_alpha_kernel<8>" / "crf_rows_grad_alpha_raw_kernel<8, bf16>"."""
     return _lib.crf_last_score_grad_kernel().decode()
 
 
@@ -391,6 +407,17 @@ def debug_align_ws_sections(logits: bool, B: int, T: int, V: int, max_label_len:
     names = _lib.crf_debug_align_ws_section_names().decode().split(",")
     out = (_i64 * (2 * len(names)))()
     n = _lib.crf_debug_align_ws_sections(1 if logits else 0, B, T, V, max_label_len, out, len(out))
+    if n < 0:
+        _check(1)
+    return [(names[k], int(out[2 * k]), int(out[2 * k + 1])) for k in range(n)]
+
+
+def debug_score_rows_ws_sections(grad: bool, B: int, H: int, T: int, V: int, len_cap: int, dtype: int = -1):
+    """The same for the workspace of crf_ctc_score_rows (grad False) / crf_ctc_score_grad_rows (True); dtype -1: fp32 log-probs, 0 / 1 / 2: raw
+    network output in f32 / bf16 / f16 (+ the lse values)."""
+    names = _lib.crf_debug_score_rows_ws_section_names(1 if grad else 0).decode().split(",")
+    out = (_i64 * (2 * len(names)))()
+    n = _lib.crf_debug_score_rows_ws_sections(1 if grad else 0, B, H, T, V, len_cap, dtype, out, len(out))
     if n < 0:
         _check(1)
     return [(names[k], int(out[2 * k]), int(out[2 * k + 1])) for k in range(n)]
@@ -741,15 +768,19 @@ def _stage_score_meta(hyps: torch.Tensor, hyp_lengths: torch.Tensor, lx: torch.T
 
 def ctc_score(log_probs: torch.Tensor, hyps: torch.Tensor, hyp_lengths: torch.Tensor, lx: torch.Tensor,
               hyp_utt: Optional[torch.Tensor] = None, blank: int = 0, time_major: bool = False, fused: bool = False,
-              scores_out: Optional[torch.Tensor] = None):
+              scores_out: Optional[torch.Tensor] = None, max_hyp_len: Optional[int] = None):
     """Forward-only CTC log-likelihoods of H hypotheses (include/ctc_crf_hip.h ``crf_ctc_score``): hypothesis h on the rows of utterance
-    hyp_utt[h] (None: H = N, hypothesis h on utterance h).
+    hyp_utt[h] (None: H = N, hypothesis h on utterance h).  hyps on the device: padded rows as stage_score_rows takes them, scored where
+    they lie by ``crf_ctc_score_rows`` with the bound max_hyp_len; a hypothesis over the bound comes back invalid with -inf.
 
     log_probs [N,T,V] (time_major: [T,N,V]) f32 on the GPU, contiguous, read in place and never replicated; hyps / hyp_lengths / lx /
     hyp_utt int tensors on the CPU, hyps flat [sum(hyp_lengths)] or padded (H, Lmax).  Returns (scores [H] f32 = +log p, invalid [H]
     int32), both on the device, no host synchronisation, no autograd; all integer metadata travels in one staged copy.
     fused: log_probs is the RAW network output in f32 / bf16 / f16 (``crf_ctc_score_logits``)."""
     assert log_probs.is_cuda and log_probs.is_contiguous() and log_probs.dim() == 3
+    if device_rows("ctc_score", hyps, hyp_lengths, hyp_utt, max_hyp_len):
+        sr = stage_score_rows(log_probs, hyps, hyp_lengths, lx, hyp_utt, blank, time_major, fused, max_hyp_len)
+        return _ctc_score_rows(log_probs, sr, time_major, scores_out, fused)
     dev, N, T, V = _act_shape(log_probs, fused, time_major, blank)
     meta_cpu, H, max_l = _stage_score_meta(hyps, hyp_lengths, lx, hyp_utt, N, T, V, blank)
     meta = _h2d_async(meta_cpu, dev)
@@ -798,6 +829,132 @@ def stage_score_meta(log_probs: torch.Tensor, hyps: torch.Tensor, hyp_lengths: t
     return ScoreMeta(_h2d_async(meta_cpu, dev), N, H, T, V, max_l, blank)
 
 
+SCORE_ROWS_MAX_LEN = 2047    # longest hypothesis crf_ctc_score_rows takes (the workgroup geometry's eight states per thread)
+
+
+class ScoreRows:
+    """ScoreMeta's twin for hypotheses that lie on the device as padded rows (what ctc_sample, ctc_greedy and ctc_beam_search return):
+    nothing of them is known on the host but the shapes and `len_cap`, the caller's bound on the lengths.  ctc_score_staged and
+    ctc_score_grad take either; forward and backward of ctc_logp share one."""
+
+    def __init__(self, hyps: torch.Tensor, hyp_len: torch.Tensor, hyp_utt: torch.Tensor, lx: torch.Tensor, N: int, H: int, T: int, V: int,
+                 stride: int, len_cap: int, blank: int):
+        self.hyps, self.hyp_len, self.hyp_utt, self.lx = hyps, hyp_len, hyp_utt, lx
+        self.N, self.H, self.T, self.V, self.stride, self.len_cap, self.blank = N, H, T, V, stride, len_cap, blank
+        self.meta = hyp_len          # (what _score_args checks the device of)
+
+
+def device_rows(who: str, hyps, hyp_lengths, hyp_utt, max_hyp_len) -> bool:
+    """True: the hypotheses are device rows.  A mix of CPU and CUDA tensors among hyps / hyp_lengths / hyp_utt, and max_hyp_len with CPU
+    hypotheses, raise -- from the tensors' placement alone, before anything touches a device."""
+    named = [("hyps", hyps), ("hyp_lengths", hyp_lengths)] + ([("hyp_utt", hyp_utt)] if hyp_utt is not None else [])
+    for name, t in named[1:]:
+        if t.is_cuda != hyps.is_cuda:
+            raise RuntimeError(f"{who}: {name} is a {'CUDA' if t.is_cuda else 'CPU'} tensor, hyps a {'CUDA' if hyps.is_cuda else 'CPU'} tensor: "
+                               "hypotheses lie on one side, all on the CPU or all on log_probs' device")
+    if not hyps.is_cuda and max_hyp_len is not None:
+        raise RuntimeError(f"{who}: max_hyp_len bounds hypotheses that lie on the device; with CPU hypotheses the host knows the lengths, "
+                           "pass None")
+    return hyps.is_cuda
+
+
+def stage_score_rows(log_probs: torch.Tensor, hyps: torch.Tensor, hyp_lengths: torch.Tensor, lx: torch.Tensor,
+                     hyp_utt: Optional[torch.Tensor], blank: int, time_major: bool, fused: bool = False, max_hyp_len: Optional[int] = None,
+                     grad: bool = False, who: str = "ctc_score") -> ScoreRows:
+    """The checks of device rows -- shapes, dtypes and placement only: NO value of a device tensor is read on the host (no .max(), .item(),
+    .cpu(), int(tensor) or truth test of a tensor) -- and the staged copy of CPU input lengths.  hyps (H, W) int32 with contiguous rows,
+    hyp_lengths (H,) int32, hyp_utt (H,) int32 or None (H = N, an arange built on the device), all on log_probs' device; lx on the CPU
+    (staged without a synchronisation) or on the device.  max_hyp_len: the bound len_cap, default min(W, 2047) -- grad: min(W, 255)."""
+    assert log_probs.is_cuda and log_probs.is_contiguous() and log_probs.dim() == 3
+    dev, N, T, V = _act_shape(log_probs, fused, time_major, blank)
+    if hyps.dim() != 2 or hyps.dtype != torch.int32:
+        raise RuntimeError(f"{who}: device hyps are padded rows (H, W) of int32, got {tuple(hyps.shape)} of {hyps.dtype}")
+    H, W = hyps.shape
+    if H == 0 or W == 0:
+        raise RuntimeError(f"{who}: no hypotheses")
+    if W > 1 and hyps.stride(1) != 1 or H > 1 and hyps.stride(0) < W:
+        raise RuntimeError(f"{who}: the rows of device hyps must be contiguous, got strides {tuple(hyps.stride())}")
+    stride = hyps.stride(0) if H > 1 else W
+    for name, t in (("hyp_lengths", hyp_lengths), ("hyp_utt", hyp_utt)):
+        if t is not None and (t.dtype != torch.int32 or t.shape != (H,) or not t.is_contiguous()):
+            raise RuntimeError(f"{who}: expect {name} as a contiguous int32 tensor ({H},) (one entry per row of hyps), got {tuple(t.shape)} of {t.dtype}")
+    for name, t in (("hyps", hyps), ("hyp_lengths", hyp_lengths), ("hyp_utt", hyp_utt)):
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"{who}: {name} lies on {t.device}, log_probs on {dev}")
+    if H * stride > 2 ** 31 - 1:
+        raise RuntimeError(f"{who}: H * row stride = {H * stride} exceeds INT32_MAX")
+    limit = SCORE_GRAD_MAX_LEN if grad else SCORE_ROWS_MAX_LEN
+    if max_hyp_len is None:
+        len_cap = min(W, limit)
+    else:
+        if isinstance(max_hyp_len, bool) or not isinstance(max_hyp_len, int) or max_hyp_len < 0:
+            raise RuntimeError(f"{who}: max_hyp_len must be a non-negative int or None, got {max_hyp_len!r}")
+        if max_hyp_len > limit:
+            raise RuntimeError(f"{who}: max_hyp_len={max_hyp_len} exceeds {limit}, the longest hypothesis "
+                               + ("the gradient takes" if grad else "the score kernels take"))
+        len_cap = max_hyp_len
+    if lx.is_cuda:
+        if lx.dtype != torch.int32 or lx.shape != (N,) or not lx.is_contiguous() or lx.device != dev:
+            raise RuntimeError(f"{who}: device input_lengths must be a contiguous int32 tensor ({N},) on {dev}, got {tuple(lx.shape)} of {lx.dtype} on {lx.device}")
+        lx_d = lx
+    else:
+        lx32 = lx.to(torch.int32).reshape(-1)
+        if lx32.numel() != N:
+            raise RuntimeError(f"{who}: expect {N} input lengths, got {lx32.numel()}")
+        _validate_meta(lx32, None, None, T, V, blank)
+        lx_d = _h2d_async(lx32, dev)
+    if hyp_utt is None:
+        if H != N:
+            raise RuntimeError(f"{who}: hyp_utt=None scores hypothesis h on utterance h: expect {N} hypotheses, got {H}")
+        hyp_utt = torch.arange(N, dtype=torch.int32, device=dev)
+    return ScoreRows(hyps, hyp_lengths, hyp_utt, lx_d, N, H, T, V, stride, len_cap, blank)
+
+
+def _rows_dtype(log_probs: torch.Tensor, fused: bool) -> int:
+    return _FUSED_DTYPES[log_probs.dtype] if fused else -1
+
+
+def _ctc_score_rows(log_probs: torch.Tensor, sr: ScoreRows, time_major: bool, scores_out: Optional[torch.Tensor], fused: bool):
+    """crf_ctc_score_rows on staged device rows -> (scores [H] f32, invalid [H] int32)."""
+    dev, N, T, V = _score_args(log_probs, sr, time_major, fused)
+    dtype = _rows_dtype(log_probs, fused)
+    scores = torch.empty(sr.H, dtype=torch.float32, device=dev) if scores_out is None else scores_out
+    assert scores.shape == (sr.H,) and scores.dtype == torch.float32 and scores.is_contiguous() and scores.device == dev
+    invalid = torch.empty(sr.H, dtype=torch.int32, device=dev)
+    ws_bytes = _lib.crf_ctc_score_rows_workspace_bytes(N, sr.H, T, V, sr.len_cap, dtype)
+    ws = _new_ws(ws_bytes, dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        _check(_lib.crf_ctc_score_rows(_ptr(log_probs), dtype, 1 if time_major else 0, sr.blank, _ptr(sr.hyps), sr.stride, _ptr(sr.hyp_len),
+                                       _ptr(sr.hyp_utt), _ptr(sr.lx), N, sr.H, T, V, sr.len_cap, _ptr(scores), _ptr(invalid), _ptr(ws), ws_bytes,
+                                       _vp(stream)))
+    return scores, invalid
+
+
+def _ctc_score_grad_rows(log_probs: torch.Tensor, sr: ScoreRows, weights: Optional[torch.Tensor], time_major: bool,
+                         grad_out: Optional[torch.Tensor], scores_out: Optional[torch.Tensor], fused: bool):
+    """crf_ctc_score_grad_rows on staged device rows -> (grad, scores [H] f32, invalid [H] int32)."""
+    dev, N, T, V = _score_args(log_probs, sr, time_major, fused)
+    dtype, H = _rows_dtype(log_probs, fused), sr.H
+    if sr.len_cap > SCORE_GRAD_MAX_LEN:
+        raise RuntimeError(f"ctc_score_grad: max_hyp_len={sr.len_cap} exceeds {SCORE_GRAD_MAX_LEN}, the longest hypothesis the gradient takes")
+    if weights is not None:
+        assert weights.shape == (H,) and weights.dtype == torch.float32 and weights.is_contiguous() and weights.device == dev
+    ws_bytes = _lib.crf_ctc_score_grad_rows_workspace_bytes(N, H, T, V, sr.len_cap, dtype)
+    ws = _new_ws(ws_bytes, dev)
+    grad = torch.empty(log_probs.shape, dtype=torch.float32, device=dev) if grad_out is None else grad_out
+    assert grad.shape == log_probs.shape and grad.dtype == torch.float32 and grad.is_contiguous() and grad.device == dev
+    scores = torch.empty(H, dtype=torch.float32, device=dev) if scores_out is None else scores_out
+    assert scores.shape == (H,) and scores.dtype == torch.float32 and scores.is_contiguous() and scores.device == dev
+    invalid = torch.empty(H, dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        _check(_lib.crf_ctc_score_grad_rows(_ptr(log_probs), dtype, 1 if time_major else 0, sr.blank, _ptr(sr.hyps), sr.stride, _ptr(sr.hyp_len),
+                                            _ptr(sr.hyp_utt), _ptr(sr.lx), _ptr(weights), N, H, T, V, sr.len_cap, _ptr(scores), _ptr(invalid),
+                                            _ptr(grad), _ptr(ws), ws_bytes, _vp(stream)))
+    return grad, scores, invalid
+
+
 def _score_args(log_probs: torch.Tensor, sm: ScoreMeta, time_major: bool, fused: bool = False):
     dev, N, T, V = _act_shape(log_probs, fused, time_major, sm.blank)
     assert log_probs.is_cuda and log_probs.is_contiguous() and (N, T, V) == (sm.N, sm.T, sm.V) and sm.meta.device == dev
@@ -807,7 +964,9 @@ def _score_args(log_probs: torch.Tensor, sm: ScoreMeta, time_major: bool, fused:
 def ctc_score_staged(log_probs: torch.Tensor, sm: ScoreMeta, time_major: bool = False, scores_out: Optional[torch.Tensor] = None,
                      fused: bool = False):
     """ctc_score's crf_ctc_score call (fused: its crf_ctc_score_logits call, on raw network output in f32 / bf16 / f16) on metadata that is
-    staged already.  Returns (scores [H] f32, invalid [H] int32)."""
+    staged already (a ScoreRows: crf_ctc_score_rows on device rows).  Returns (scores [H] f32, invalid [H] int32)."""
+    if isinstance(sm, ScoreRows):
+        return _ctc_score_rows(log_probs, sm, time_major, scores_out, fused)
     dev, N, T, V = _score_args(log_probs, sm, time_major, fused)
     lx_d, len_d, off_d, utt_d, lab_d = sm.parts()
     scores = torch.empty(sm.H, dtype=torch.float32, device=dev) if scores_out is None else scores_out
@@ -840,6 +999,8 @@ def ctc_score_grad(log_probs: torch.Tensor, meta, weights: Optional[torch.Tensor
     synchronisation; scores and invalid are ctc_score's bits.  grad_out / scores_out: contiguous f32 device tensors of log_probs' shape /
     [H] that receive the results (else allocated); every entry of grad is written."""
     assert log_probs.is_cuda and log_probs.is_contiguous() and log_probs.dim() == 3
+    if isinstance(meta, ScoreRows):            # device rows: crf_ctc_score_grad_rows, the workspace sized by the bound meta.len_cap
+        return _ctc_score_grad_rows(log_probs, meta, weights, time_major, grad_out, scores_out, fused)
     sm = meta if isinstance(meta, ScoreMeta) else stage_score_meta(log_probs, *meta, blank, time_major, fused)
     dev, N, T, V = _score_args(log_probs, sm, time_major, fused)
     H = sm.H

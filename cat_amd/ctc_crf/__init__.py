@@ -9,11 +9,14 @@ Same names, arguments and error behaviour as the reference:
   _CTC_CRF, _WARP_CTC_GPU  autograd Functions                                             (:25-94)
   ctc_align(log_probs, labels, input_lengths, label_lengths, blank=0, time_major=False, fuse_log_softmax=False) -> (pos, tokens, scores)
                                                                                          (forced alignment; not in the reference)
-  ctc_score(log_probs, hyps, hyp_lengths, input_lengths, hyp_utt=None, blank=0, time_major=False, fuse_log_softmax=False) -> FloatTensor[H]
-                                                                                         (forward-only scores of many hypotheses per utterance)
-  ctc_logp(log_probs, hyps, hyp_lengths, input_lengths, hyp_utt=None, blank=0, time_major=False, fuse_log_softmax=False)
+  ctc_score(log_probs, hyps, hyp_lengths, input_lengths, hyp_utt=None, blank=0, time_major=False, fuse_log_softmax=False,
+            max_hyp_len=None) -> FloatTensor[H]                                          (forward-only scores of many hypotheses per utterance)
+  ctc_logp(log_probs, hyps, hyp_lengths, input_lengths, hyp_utt=None, blank=0, time_major=False, max_hyp_len=None, fuse_log_softmax=False)
                                                                                          -> (FloatTensor[H], IntTensor[H])
                                                                                          (the same scores WITH autograd: one [N,T,V] gradient)
+                                                                                         (both: hypotheses on the CPU, or on the device as the
+                                                                                         padded rows ctc_sample / ctc_beam_search return, bounded
+                                                                                         by max_hyp_len -- no copy to the host, no stream drain)
   ctc_sample(log_probs, input_lengths, n_samples, seed, offset=0, blank=0, time_major=False, return_paths=False)
                                                               -> (hyps IntTensor[N*K, T], hyp_lengths IntTensor[N*K], hyp_utt IntTensor[N*K])
                                                                                          (K label sequences per utterance drawn on the GPU)
@@ -263,7 +266,8 @@ def ctc_align(log_probs: torch.Tensor, labels: torch.Tensor, input_lengths: torc
 
 
 def ctc_score(log_probs: torch.Tensor, hyps: torch.Tensor, hyp_lengths: torch.Tensor, input_lengths: torch.Tensor,
-              hyp_utt: torch.Tensor = None, blank: int = 0, time_major: bool = False, fuse_log_softmax: bool = False) -> torch.Tensor:
+              hyp_utt: torch.Tensor = None, blank: int = 0, time_major: bool = False, fuse_log_softmax: bool = False,
+              max_hyp_len: int = None) -> torch.Tensor:
     """Forward-only CTC log-likelihoods of H hypotheses over N utterances (not in the reference, whose callers loop over
     nn.CTCLoss(reduction='none') under no_grad, or score N*K hypotheses on repeat_interleave'd activations: cat/ctc/train_jsa.py:147-160,
     decode_jsa_mls.py:189-191).  The activations are read in place and never replicated; there is no backward chain and no gradient.
@@ -277,10 +281,22 @@ def ctc_score(log_probs: torch.Tensor, hyps: torch.Tensor, hyp_lengths: torch.Te
     blank (int): the blank's column; labels lie in [0, V) without it.
     fuse_log_softmax (bool): log_probs is the RAW network output in fp32, bf16 or fp16; the scores are those of log_softmax.
 
+    Hypotheses that are already ON THE DEVICE -- the rows ctc_sample, ctc_greedy and ctc_beam_search return -- are scored where they lie:
+    hyps is then an (H, W) int32 tensor on log_probs' device with contiguous rows, hyp_lengths and hyp_utt are (H,) int32 tensors on
+        that device (hyp_utt=None: H = N, an arange built on the device), input_lengths may stay on the CPU or lie on the device.  The
+        three travel together: a mix of CPU and CUDA tensors among hyps, hyp_lengths and hyp_utt is refused.  Nothing is copied to the
+        host and the stream is never drained.
+    max_hyp_len (int): device hypotheses only (with CPU hypotheses it must be None: the host knows the lengths there).  A bound on
+        hyp_lengths that the caller promises; default min(W, 2047), a larger value is refused.  The host never reads the lengths, so a
+        hypothesis over the bound (or with a negative length, a label outside [0, V) or an utterance outside [0, N)) is NOT an
+        exception: it comes back with -inf.  Each hypothesis is scored by the kernel of its own length class, so its score does not
+        depend on the bound or on its neighbours; a tight bound only saves the passes over the classes above it.
+
     Returns FloatTensor[H] on log_probs' device: +log p(hyp | utterance), -inf for a hypothesis that has no alignment (it does not fit
     into input_lengths[u] frames, or every alignment has probability 0).  No host synchronisation.  The result carries NO autograd
     history -- requires_grad is False even for an input that requires grad: this is a scoring call, not a loss.
     A hypothesis's score is the same bits wherever it stands in the list and in either layout."""
+    on_device = core.device_rows("ctc_score", hyps, hyp_lengths, hyp_utt, max_hyp_len)   # (placement only: needs no device)
     if fuse_log_softmax:
         assert log_probs.dtype in (torch.float, torch.bfloat16, torch.float16), f"expect float/bfloat16/float16 network output, instead: {log_probs.dtype}"
     else:
@@ -289,7 +305,7 @@ def ctc_score(log_probs: torch.Tensor, hyps: torch.Tensor, hyp_lengths: torch.Te
         raise RuntimeError("ctc_score: log_probs must be on the GPU (there is no CPU path)")
     with torch.no_grad():
         scores, _ = core.ctc_score(log_probs.detach().contiguous(), hyps, hyp_lengths, input_lengths, hyp_utt, int(blank), bool(time_major),
-                                   fused=bool(fuse_log_softmax))
+                                   fused=bool(fuse_log_softmax), max_hyp_len=max_hyp_len if on_device else None)
     return scores
 
 
@@ -336,18 +352,27 @@ class _CTC_LOGP_LOGITS(Function):
 
 
 def ctc_logp(log_probs: torch.Tensor, hyps: torch.Tensor, hyp_lengths: torch.Tensor, input_lengths: torch.Tensor,
-             hyp_utt: torch.Tensor = None, blank: int = 0, time_major: bool = False, fuse_log_softmax: bool = False):
+             hyp_utt: torch.Tensor = None, blank: int = 0, time_major: bool = False, max_hyp_len: int = None,
+             fuse_log_softmax: bool = False):
     """ctc_score with autograd: CTC log-likelihoods of H hypotheses over N utterances whose gradient reaches log_probs as ONE (N, T, V)
     tensor -- what minimum-risk / MWER training on sampled or N-best hypotheses and the nn.CTCLoss(reduction='none',
     zero_infinity=True) / length losses (cat/ctc/train_jsa.py:194-201) need, without repeat_interleave'd activations and without an
-    (H, T, V) gradient.  MWER in three lines:
+    (H, T, V) gradient.  MWER in three lines, the hypotheses never leaving the device:
 
         hyps, hyp_lengths, hyp_utt = ctc_sample(log_probs, input_lengths, K, seed)
-        scores, _ = ctc_logp(log_probs, hyps.cpu(), hyp_lengths.cpu(), input_lengths, hyp_utt.cpu())
+        scores, _ = ctc_logp(log_probs, hyps, hyp_lengths, input_lengths, hyp_utt)
         (torch.softmax(scores.view(N, K), -1) * risk.view(N, K)).sum().backward()
 
     log_probs (torch.FloatTensor): (N, T, V) fp32 log-probs on the GPU, contiguous, or (T, N, V) with time_major=True; anything else is
-        refused.  hyps, hyp_lengths, input_lengths, hyp_utt, blank: as ctc_score takes them (CPU tensors).
+        refused.  hyps, hyp_lengths, input_lengths, hyp_utt, blank: as ctc_score takes them -- CPU tensors, or device rows: (H, W) int32
+        hyps with (H,) int32 hyp_lengths and hyp_utt on log_probs' device, scored and differentiated where they lie; forward and backward
+        share one plan, nothing is staged twice, nothing is read on the host.
+    max_hyp_len (int): device rows only (None with CPU hypotheses), the caller's bound on hyp_lengths; pass it by keyword.  Default
+        min(W, 2047) for an input that does not require grad, min(W, 255) for one that does; a larger value is refused before any call.
+        A hypothesis over the bound is NOT an exception -- the host never reads the lengths: it comes back with invalid = 1, a score of
+        -inf and zero gradient.  The gradient's workspace, 8 bytes x H x T x (64, 128, 256 or 512 states for a bound of up to 31, 63,
+        127, 255), grows with the class of max_hyp_len, NOT with the true lengths: a caller who knows a bound should pass it (sampled rows
+        are W = T wide, so the default is the largest class whenever T >= 128).
     fuse_log_softmax (bool): log_probs is the RAW network output in fp32, bf16 or fp16, read in place -- no log_softmax in front, no fp32
         copy kept for autograd: the scores are ctc_score(fuse_log_softmax=True)'s bits, those of log_softmax of the upcast values, and
         backward is one call (crf_ctc_score_grad_logits) whose fp32 gradient with respect to the raw output, log_softmax's backward
@@ -357,6 +382,7 @@ def ctc_logp(log_probs: torch.Tensor, hyps: torch.Tensor, hyp_lengths: torch.Ten
     Backward is one call (include/ctc_crf_hip.h crf_ctc_score_grad) whose weights are the incoming grad_output, so any torch expression
     of the scores trains; a hypothesis that is invalid or scores -inf, or whose weight is exactly 0, adds nothing to the gradient
     (zero_infinity=True).  With log_probs.requires_grad no hypothesis may be longer than 255 labels."""
+    on_device = core.device_rows("ctc_logp", hyps, hyp_lengths, hyp_utt, max_hyp_len)   # (placement only: needs no device)
     if fuse_log_softmax:
         if log_probs.dtype not in (torch.float, torch.bfloat16, torch.float16):
             raise RuntimeError(f"ctc_logp: expect float32, bfloat16 or float16 network output, got {log_probs.dtype}")
@@ -366,6 +392,11 @@ def ctc_logp(log_probs: torch.Tensor, hyps: torch.Tensor, hyp_lengths: torch.Ten
         raise RuntimeError("ctc_logp: log_probs must be on the GPU (there is no CPU path)")
     if log_probs.dim() != 3 or not log_probs.is_contiguous():
         raise RuntimeError("ctc_logp: expect contiguous (N, T, V) or (T, N, V) log-probs")
+    if on_device:                              # (no value of a device tensor is read here: the bound is the caller's)
+        with torch.no_grad():
+            sr = core.stage_score_rows(log_probs, hyps, hyp_lengths, input_lengths, hyp_utt, int(blank), bool(time_major), bool(fuse_log_softmax),
+                                       max_hyp_len, grad=log_probs.requires_grad, who="ctc_logp")
+        return (_CTC_LOGP_LOGITS if fuse_log_softmax else _CTC_LOGP).apply(log_probs, sr, bool(time_major))
     if log_probs.requires_grad and hyp_lengths.numel() and int(hyp_lengths.max()) > core.SCORE_GRAD_MAX_LEN:
         raise RuntimeError(f"ctc_logp: the gradient takes hypotheses of up to {core.SCORE_GRAD_MAX_LEN} labels, got {int(hyp_lengths.max())}")
     with torch.no_grad():
@@ -463,7 +494,7 @@ def ctc_edit_distance(hyps: torch.Tensor, hyp_lengths: torch.Tensor, labels: tor
 
         hyps, hl, hu = ctc_sample(log_probs, lx, K, seed)                      # or ctc_beam_search(..., nbest=K)
         risk = ctc_edit_distance(hyps, hl, labels, label_lengths, hu).float()
-        scores, _ = ctc_logp(log_probs, hyps.cpu(), hl.cpu(), lx, hu.cpu())
+        scores, _ = ctc_logp(log_probs, hyps, hl, lx, hu)
         (torch.softmax(scores.view(N, K), -1) * risk.view(N, K)).sum().backward()
 
     hyps (H, W) int32 on the GPU: row h holds hypothesis h in its first hyp_lengths[h] entries; what stands behind is never read.

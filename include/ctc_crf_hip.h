@@ -347,6 +347,44 @@ int crf_ctc_score_grad_logits(const void *act_dev, int dtype, int time_major, in
                               float *score_dev, int32_t *invalid_dev, float *grad_dev,
                               void *workspace_dev, int64_t workspace_bytes, void *stream);
 
+/* crf_ctc_score / crf_ctc_score_logits and their gradients on hypotheses that LIE ON THE DEVICE as padded rows -- exactly the rows
+ * crf_ctc_sample and crf_ctc_beam write: hypothesis h is the first hyp_len_dev[h] words of row h of hyps_dev, rows hyp_stride words
+ * apart; words behind the length are never read.  dtype -1: act_dev holds fp32 log-probs; 0 / 1 / 2: raw network output in fp32 / bf16 /
+ * fp16 (the *_logits calls' arithmetic; the frames' lse values are computed once per call).
+ * The host does not know the lengths, only a bound: len_cap is the caller's promise about the list and need not be its true maximum.  The
+ * kernel is chosen on the device PER HYPOTHESIS, among the seven instantiations of crf_ctc_score (one wave per hypothesis for L <= 31, 63,
+ * 127, 255; one workgroup for L <= 511, 1023, 2047): the call runs one pass per class whose lower end is at most len_cap, each on a masked
+ * copy of the lengths, and merges the results.  score_dev[h] and invalid_dev[h] are therefore the bits crf_ctc_score / crf_ctc_score_logits
+ * write for a list whose longest hypothesis lies in h's class; they depend on h's own labels and its utterance's rows only -- not on its
+ * place in the list, on the other hypotheses, on len_cap (as long as it admits h) or on the layout.  crf_last_score_kernel() /
+ * crf_last_score_grad_kernel() name the highest class launched (the gradient's: "crf_rows_grad_alpha_kernel<8>",
+ * "crf_rows_grad_alpha_raw_kernel<8, bf16>").
+ * Validity: what the host-list calls mark invalid stays invalid (L + repeats > lx[u], lx[u] <= 0, a label outside [0, V), hyp_utt outside
+ * [0, B)); in addition L < 0, L > len_cap or L > hyp_stride gives score -inf and invalid 1 -- nothing is read for such a hypothesis and it
+ * adds nothing to the gradient.  It is a result, not an error.
+ * crf_ctc_score_grad_rows: crf_ctc_score_grad's contract unchanged (every entry of grad_dev is written, rows t >= lx[u] and utterances
+ * without a live hypothesis are 0, not bit for bit); only the four wave classes take part, so len_cap <= 255 and V <= 8192.  The stored
+ * alphas are [H][T][64 NR] fp64 with NR of len_cap's class: the workspace grows with the bound, not with the true lengths.
+ * Workspace: the *_workspace_bytes functions (-1 with crf_last_error() set where the call would fail); its contents on entry do not
+ * matter.  crf_debug_score_rows_ws_sections / _section_names (grad = 0 / 1) list its sections as crf_debug_align_ws_sections does: the
+ * gradient's "occ", "hscore", then "hyp_off", "cls", "len", "cscore", "cinvalid" and, for raw output, "lse".
+ * CRF_ERR_ARG: a null pointer (invalid_dev, weight_dev and, for the gradient, score_dev may be NULL); a dtype outside -1..2; B, H, T, V or
+ * hyp_stride <= 0; len_cap < 0; H * hyp_stride or B * T > INT32_MAX; blank outside [0, V).  CRF_ERR_UNSUPPORTED: len_cap > 2047 (the
+ * gradient: > 255, or V > 8192), the message names the limit.  CRF_ERR_WORKSPACE: the message names the bytes needed.  All answered
+ * before any HIP call.  No host synchronisation, all work on `stream`, no environment variable read. */
+int64_t crf_ctc_score_rows_workspace_bytes(int64_t B, int64_t H, int64_t T, int64_t V, int64_t len_cap, int dtype);
+int crf_ctc_score_rows(const void *act_dev, int dtype, int time_major, int blank, const int32_t *hyps_dev, int64_t hyp_stride,
+                       const int32_t *hyp_len_dev, const int32_t *hyp_utt_dev, const int32_t *lx_dev, int64_t B, int64_t H, int64_t T,
+                       int64_t V, int64_t len_cap, float *score_dev, int32_t *invalid_dev,
+                       void *workspace_dev, int64_t workspace_bytes, void *stream);
+int64_t crf_ctc_score_grad_rows_workspace_bytes(int64_t B, int64_t H, int64_t T, int64_t V, int64_t len_cap, int dtype);
+int crf_ctc_score_grad_rows(const void *act_dev, int dtype, int time_major, int blank, const int32_t *hyps_dev, int64_t hyp_stride,
+                            const int32_t *hyp_len_dev, const int32_t *hyp_utt_dev, const int32_t *lx_dev, const float *weight_dev,
+                            int64_t B, int64_t H, int64_t T, int64_t V, int64_t len_cap, float *score_dev, int32_t *invalid_dev,
+                            float *grad_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+int crf_debug_score_rows_ws_sections(int grad, int64_t B, int64_t H, int64_t T, int64_t V, int64_t len_cap, int dtype, int64_t *out, int n_out);
+const char *crf_debug_score_rows_ws_section_names(int grad);
+
 /* Label sequences drawn on the GPU (what cat/ctc/train_jsa.py:256-269 `_sample` gets from torch.multinomial over N T rows, a transpose and
  * the third-party ctc_align.align_; with greedy = 1 the best path: arg-max per frame): per frame K classes from softmax(x), then the CTC
  * map B on each of the B K frame paths.  The activations are read in place, [B][T][V] (time_major = 0) or [T][B][V] (1), dtype 0 = fp32,
