@@ -3,7 +3,7 @@
 // weighted gradient (crf_ctc_score_grad*, k_score_grad.hip), both on hypotheses that lie on the device as padded rows (crf_ctc_score_rows,
 // crf_ctc_score_grad_rows, k_rows.hip), sampled / best-path label sequences (crf_ctc_sample, k_sample.hip), the
 // prefix beam search (crf_ctc_beam, k_beam.hip; with an n-gram LM: crf_ctc_beam_lm, k_beam_lm.hip, crf_ngram_tables_check) and -- on token sequences alone, no lattice -- the edit distance of hypotheses to
-// their transcripts (crf_ctc_edit_distance, k_edit.hip) --
+// their transcripts (crf_ctc_edit_distance, k_edit.hip) and their n-gram LM scores (crf_ngram_score, k_ngram.hip) --
 // argument checks, workspace sections, kernel choice, the C-ABI entry points of include/ctc_crf_hip.h.  Every error is answered before
 // any HIP call.  The activations are read in place in either layout and -- the *_logits entry points and crf_ctc_sample -- in f32, bf16
 // or f16.
@@ -19,6 +19,7 @@ namespace crf {
 static thread_local const char *g_sample_kernel = ""; // template instantiation of the row kernel of this thread's last crf_ctc_sample (crf_last_sample_kernel)
 static thread_local const char *g_beam_kernel = "";   // ... of the row kernel of this thread's last crf_ctc_beam (crf_last_beam_kernel)
 static thread_local const char *g_edit_kernel = "";   // ... of the kernel of this thread's last crf_ctc_edit_distance (crf_last_edit_kernel)
+static thread_local const char *g_ngram_kernel = "";  // ... of the kernel of this thread's last crf_ngram_score (crf_last_ngram_score_kernel)
 static thread_local const char *g_score_kernel = "";// ... of the kernel of this thread's last crf_ctc_score / crf_ctc_score_logits (crf_last_score_kernel)
 static thread_local const char *g_score_grad_kernel = "";   // ... of the alpha pass of this thread's last crf_ctc_score_grad / crf_ctc_score_grad_logits (crf_last_score_grad_kernel)
 
@@ -537,6 +538,14 @@ static int launch_edit(const EditParams &p, hipStream_t st) {
     });
 }
 
+// ---- n-gram LM scores of rows (k_ngram.hip) ----
+// one wave per hypothesis, kNgramScoreWaves of them per workgroup, the grid over H in x; the per-token stores only where asked for
+static int launch_ngram_score(const NgramScoreParams &p, hipStream_t st) {
+    const dim3 grid((unsigned)((p.H + kNgramScoreWaves - 1) / kNgramScoreWaves)), block(64 * kNgramScoreWaves);
+    if (p.tok_logp || p.tok_order) return launch<crf_ngram_score_kernel<true>>(g_ngram_kernel = "crf_ngram_score_kernel<tokens>", grid, block, 0, st, p);
+    return launch<crf_ngram_score_kernel<false>>(g_ngram_kernel = "crf_ngram_score_kernel<scores>", grid, block, 0, st, p);
+}
+
 }  // namespace crf
 
 using namespace crf;
@@ -751,6 +760,34 @@ int crf_ctc_edit_distance(const int32_t *hyps, int64_t hyp_stride, const int32_t
     return launch_edit(p, (hipStream_t)stream_);
 }
 
+int crf_ngram_score(const crf_ngram_tables *lm, const float *eos_logp, const int32_t *hyps, int64_t hyp_stride, const int32_t *hyp_len,
+                    int64_t H, int use_start, int add_eos, float *score, int32_t *invalid, float *token_logp, int32_t *token_order,
+                    void *stream_) {
+    const std::string w0 = "crf_ngram_score: ";
+    auto bad = [&](const std::string &m) { set_error(w0 + m); return CRF_ERR_ARG; };
+    auto str = [](int64_t v) { return std::to_string(v); };
+    if (!lm || !hyps || !hyp_len || !score) return bad("null argument");
+    if (lm->S < 1 || lm->S > INT32_MAX || lm->A < 0 || lm->A > INT32_MAX || lm->order < 1 || lm->order > kNgramMaxOrder || lm->start < 0 ||
+        lm->start >= lm->S || lm->V < 1 || lm->V > kBeamMaxV)
+        return bad("bad LM tables: S " + str(lm->S) + ", A " + str(lm->A) + ", V " + str(lm->V) + ", order " + str(lm->order) + ", start " + str(lm->start));
+    if (!lm->row_off || !lm->bo_state || !lm->bo_weight || !lm->uni_logp || !lm->uni_next ||
+        (lm->A > 0 && (!lm->arc_label || !lm->arc_logp || !lm->arc_next))) return bad("null LM table");
+    if (H < 0) return bad("H " + str(H) + " is negative");
+    if (hyp_stride < 1 || hyp_stride > kNgramMaxStride) return bad("hyp_stride " + str(hyp_stride) + " outside [1, " + str(kNgramMaxStride) + "]");
+    if (add_eos && !eos_logp) return bad("add_eos needs eos_logp_dev (a model without a </s> unigram has none)");
+    if (H == 0) return CRF_OK;
+    if ((H + kNgramScoreWaves - 1) / kNgramScoreWaves > INT32_MAX) return bad("H " + str(H) + " exceeds the grid");
+    NgramScoreParams p{};
+    p.lm.row_off = lm->row_off; p.lm.arc_label = lm->arc_label; p.lm.arc_logp = lm->arc_logp; p.lm.arc_next = lm->arc_next;
+    p.lm.bo_state = lm->bo_state; p.lm.bo_weight = lm->bo_weight; p.lm.uni_logp = lm->uni_logp; p.lm.uni_next = lm->uni_next;
+    p.lm.S = (int)lm->S; p.lm.A = (int)lm->A; p.lm.V = (int)lm->V; p.lm.order = lm->order; p.lm.start = lm->start;
+    p.eos = eos_logp; p.hyps = hyps; p.hyp_len = hyp_len; p.H = H; p.stride = (int)hyp_stride;
+    p.use_start = use_start != 0; p.add_eos = add_eos != 0;
+    p.score = score; p.invalid = invalid; p.tok_logp = token_logp; p.tok_order = token_order;
+    return launch_ngram_score(p, (hipStream_t)stream_);
+}
+
+const char *crf_last_ngram_score_kernel(void) { return g_ngram_kernel; }
 const char *crf_last_edit_kernel(void) { return g_edit_kernel; }
 const char *crf_last_beam_kernel(void) { return g_beam_kernel; }
 const char *crf_last_score_kernel(void) { return g_score_kernel; }

@@ -190,6 +190,24 @@ struct BeamLmParams {
 };
 __global__ void crf_beamlm_search_kernel(BeamLmParams p);   // kBeamLmWaves waves (one workgroup) per utterance
 
+// ---- k_ngram.hip ----
+constexpr int kNgramScoreWaves = 4;       // hypotheses (waves) per workgroup
+constexpr int kNgramMaxStride = 8192;     // words between two rows, and the per-token outputs' row length
+// Kernel arguments of crf_ngram_score: hypothesis h is the first hyp_len[h] entries of row h of hyps (rows `stride` entries apart)
+struct NgramScoreParams {
+    NgramDev lm;
+    const float *eos;           // [S] log P(</s> | state), or null without add_eos
+    const int *hyps, *hyp_len;
+    int64_t H;
+    int stride, use_start, add_eos;
+    float *score;               // [H]
+    int *invalid;               // [H] or null
+    float *tok_logp;            // [H][stride] (TOK) or null
+    int *tok_order;             // [H][stride] (TOK) or null; either of the two may be null alone
+};
+// TOK: the per-position outputs are written (at least one of them is asked for).  One wave per hypothesis, no LDS.
+template <bool TOK> __global__ void crf_ngram_score_kernel(NgramScoreParams p);
+
 // ---- k_edit.hip ----
 constexpr int kEditWaves = 4;             // hypotheses (waves) per workgroup of the register geometry
 constexpr int kEditStripRows = 512;       // reference rows one wave holds (64 lanes x 8): longer references are walked in strips of this many

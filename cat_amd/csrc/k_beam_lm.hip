@@ -27,37 +27,9 @@
 // With alpha == 0 and beta == 0 every lmw is +0 and every lm is 0: the keys are the x[c], the fused scores are the acoustic ones, and
 // every output equals crf_ctc_beam's bit for bit.
 #include "k_beam_common.h"
+#include "k_ngram_common.h"   // ngram_lookup: the look-up in the tables, shared with k_ngram.hip
 
 namespace crf {
-
-// (state s, class c) -> lp = log P(c | s) along the back-off chain (fp32: the back-off weights in order, then the arc's value) and the
-// next state.  At most min(order, kNgramMaxOrder) sparse rows, then the root's dense row -- with tables that pass
-// crf_ngram_tables_check a state lies at most order - 1 back-offs above the root, so the walk ends by itself.
-__device__ __forceinline__ void beamlm_lookup(const NgramDev &lm, int s, int c, float &lp, int &nx) {
-    const int S1 = max(lm.S, 1) - 1, A = max(lm.A, 0);
-    c = min(max(c, 0), lm.V - 1);
-    s = min(max(s, 0), S1);
-    float acc = 0.f;
-    const int steps = min(lm.order, kNgramMaxOrder);
-    for (int i = 0; i < steps && s > 0; ++i) {
-        int lo = min(max(lm.row_off[s], 0), A);
-        const int end = min(max(lm.row_off[s + 1], 0), A);
-        int hi = end;
-        for (int it = 0; it < kNgramRowSteps && lo < hi; ++it) {       // (lo <= mid < hi <= A: inside arc_label)
-            const int mid = (lo + hi) >> 1;
-            if (lm.arc_label[mid] < c) lo = mid + 1; else hi = mid;
-        }
-        if (lo < end && lm.arc_label[lo] == c) {
-            lp = acc + lm.arc_logp[lo];
-            nx = lm.arc_next[lo];
-            return;
-        }
-        acc += lm.bo_weight[s];
-        s = min(max(lm.bo_state[s], 0), S1);
-    }
-    lp = acc + lm.uni_logp[c];
-    nx = lm.uni_next[c];
-}
 
 __global__ __launch_bounds__(64 * kBeamLmWaves) void crf_beamlm_search_kernel(BeamLmParams q) {
     __shared__ float lm_w[64 * kBeamLmStride];  // [slot][place] lmw of the slot's extension by the class at that place of E_t
@@ -108,7 +80,7 @@ __global__ __launch_bounds__(64 * kBeamLmWaves) void crf_beamlm_search_kernel(Be
                 int nx = 0;
                 if (c >= 0) {                   // (a filler pair (-1, -inf) is no candidate: nothing to look up)
                     float lp;
-                    beamlm_lookup(lmt, st_lds[k], c, lp, nx);
+                    ngram_lookup<false>(lmt, st_lds[k], c, lp, nx);
                     w = __fadd_rn(__fmul_rn(alpha, lp), beta);
                 }
                 lm_w[k * kBeamLmStride + j] = w;

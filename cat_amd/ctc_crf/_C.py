@@ -115,6 +115,9 @@ _lib.crf_ctc_beam_lm.restype = ctypes.c_int
 _lib.crf_ctc_edit_distance.argtypes = [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]
 _lib.crf_ctc_edit_distance.restype = ctypes.c_int
 _lib.crf_last_edit_kernel.restype = ctypes.c_char_p
+_lib.crf_ngram_score.argtypes = [_vp, _vp, _vp, _i64, _vp, _i64, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]
+_lib.crf_ngram_score.restype = ctypes.c_int
+_lib.crf_last_ngram_score_kernel.restype = ctypes.c_char_p
 _lib.crf_profile_enable.argtypes = [ctypes.c_int]
 _lib.crf_profile_enable.restype = None
 _lib.crf_profile_read.argtypes = [ctypes.POINTER(_f32), ctypes.c_int]
@@ -139,7 +142,7 @@ _lib.crf_build_switches.restype = ctypes.c_char_p
 
 EXPORTED_SYMBOLS = (
     "crf_graph_create", "crf_graph_create_from_arcs", "crf_graph_destroy", "crf_graph_dims", "crf_graph_stats",
-    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_ws_fields", "crf_debug_ws_field_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_ctc_score", "crf_ctc_score_logits_workspace_bytes", "crf_ctc_score_logits", "crf_last_score_kernel", "crf_ctc_score_grad_workspace_bytes", "crf_ctc_score_grad", "crf_ctc_score_grad_logits_workspace_bytes", "crf_ctc_score_grad_logits", "crf_last_score_grad_kernel", "crf_ctc_score_rows_workspace_bytes", "crf_ctc_score_rows", "crf_ctc_score_grad_rows_workspace_bytes", "crf_ctc_score_grad_rows", "crf_debug_score_rows_ws_sections", "crf_debug_score_rows_ws_section_names", "crf_ctc_sample_workspace_bytes", "crf_ctc_sample", "crf_last_sample_kernel", "crf_ctc_beam_workspace_bytes", "crf_ctc_beam", "crf_last_beam_kernel", "crf_ngram_tables_check", "crf_ctc_beam_lm_workspace_bytes", "crf_ctc_beam_lm", "crf_ctc_edit_distance", "crf_last_edit_kernel", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
+    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_ws_fields", "crf_debug_ws_field_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_ctc_score", "crf_ctc_score_logits_workspace_bytes", "crf_ctc_score_logits", "crf_last_score_kernel", "crf_ctc_score_grad_workspace_bytes", "crf_ctc_score_grad", "crf_ctc_score_grad_logits_workspace_bytes", "crf_ctc_score_grad_logits", "crf_last_score_grad_kernel", "crf_ctc_score_rows_workspace_bytes", "crf_ctc_score_rows", "crf_ctc_score_grad_rows_workspace_bytes", "crf_ctc_score_grad_rows", "crf_debug_score_rows_ws_sections", "crf_debug_score_rows_ws_section_names", "crf_ctc_sample_workspace_bytes", "crf_ctc_sample", "crf_last_sample_kernel", "crf_ctc_beam_workspace_bytes", "crf_ctc_beam", "crf_last_beam_kernel", "crf_ngram_tables_check", "crf_ctc_beam_lm_workspace_bytes", "crf_ctc_beam_lm", "crf_ctc_edit_distance", "crf_last_edit_kernel", "crf_ngram_score", "crf_last_ngram_score_kernel", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
     "crf_debug_set", "crf_debug_unset", "crf_debug_list", "crf_last_den_kernel", "crf_last_call_streams", "crf_last_side_stream", "crf_last_fallback_counts", "crf_build_switches", "crf_last_error", "crf_version",
 )
 
@@ -189,6 +192,11 @@ def last_beam_kernel() -> str:
 def last_edit_kernel() -> str:
     """Template instantiation of the kernel of this thread's last ctc_edit_distance call (include/ctc_crf_hip.h crf_last_edit_kernel)."""
     return _lib.crf_last_edit_kernel().decode()
+
+
+def last_ngram_score_kernel() -> str:
+    """Template instantiation of the kernel of this thread's last ngram_score call (include/ctc_crf_hip.h crf_last_ngram_score_kernel)."""
+    return _lib.crf_last_ngram_score_kernel().decode()
 
 
 def last_call_streams() -> int:
@@ -1282,6 +1290,79 @@ def ctc_edit_distance(hyps: torch.Tensor, hyp_lengths: torch.Tensor, labels: tor
     _check(rc)
     del meta
     return dist, ops
+
+
+NGRAM_SCORE_MAX_WIDTH = 8192   # widest row crf_ngram_score takes (kNgramMaxStride; include/ctc_crf_hip.h)
+
+
+def _check_ngram_score_args(hyps: torch.Tensor, hyp_lengths: torch.Tensor, lm, eos: bool):
+    """The host checks of ngram_score, each with the offending value in the message; none needs a device.  -> (H, W)."""
+    from ..ngram_lm import NgramLM
+    who = "ngram_score"
+    if not isinstance(lm, NgramLM):
+        raise RuntimeError(f"{who}: lm must be an NgramLM (cat_amd.ngram_lm), got {type(lm).__name__}: {lm!r}")
+    if hyps.dim() != 2 or hyps.dtype != torch.int32:
+        raise RuntimeError(f"{who}: expect hyps as padded rows (H, W) of int32, got {tuple(hyps.shape)} of {hyps.dtype}")
+    H, W = hyps.shape
+    if hyp_lengths.dtype != torch.int32 or hyp_lengths.dim() != 1 or hyp_lengths.numel() != H:
+        raise RuntimeError(f"{who}: expect hyp_lengths as an int32 tensor ({H},), one entry per row of hyps, got {tuple(hyp_lengths.shape)} "
+                           f"of {hyp_lengths.dtype}")
+    if W > NGRAM_SCORE_MAX_WIDTH:
+        raise RuntimeError(f"{who}: rows of hyps of {W} > {NGRAM_SCORE_MAX_WIDTH} entries not supported by this build")
+    if eos and lm.eos_logp is None:
+        raise ValueError(f"{who}: eos=True needs a model with a </s> unigram (lm.eos_logp is None)")
+    if not hyps.is_cuda or not hyp_lengths.is_cuda:
+        raise ValueError(f"{who}: hyps and hyp_lengths must be on the GPU; on the host NgramLM.score(tokens, eos) and NgramLM.token_scores "
+                         f"give the same values")
+    if hyp_lengths.device != hyps.device:
+        raise RuntimeError(f"{who}: hyp_lengths lies on {hyp_lengths.device}, hyps on {hyps.device}")
+    return H, W
+
+
+def ngram_score(hyps: torch.Tensor, hyp_lengths: torch.Tensor, lm, bos: bool = True, eos: bool = False, return_token_scores: bool = False):
+    """n-gram LM scores of hypothesis rows on the GPU (include/ctc_crf_hip.h ``crf_ngram_score``): per row log P_lm in natural log.
+
+    hyps [H,W] int32 and hyp_lengths [H] int32 on one GPU, as ctc_sample / ctc_greedy / ctc_beam_search return them (rows a stride apart are
+    taken as ctc_score takes them); lm an NgramLM (tables and eos_logp are uploaded once per device and kept).  bos: the walk starts in
+    lm.start, else at the root; eos: plus lm.eos_logp[state behind the last token].  Returns (scores [H] f32, invalid [H] int32) and, with
+    return_token_scores, (token_logp [H,W] f32, token_order [H,W] int32: per position the value of NgramLM.lookup and the length of the
+    n-gram found, 0 behind the length) -- on the device, without autograd history and without a host synchronisation.  A row whose length
+    lies outside [0, W] or that holds a token outside [0, lm.vocab_size) among its first hyp_lengths[h] scores -inf with invalid = 1.  A row's
+    outputs are the same bits in any batch.
+
+    Rescoring an N-best list (ac = ctc_score's or the search's scores, rows of one utterance adjacent)::
+
+        lm_s, _ = ngram_score(hyps, hyp_lengths, lm, eos=True)
+        total = ac + alpha * lm_s + beta * hyp_lengths
+        best = total.view(N, nbest).argmax(1)
+
+    The weight grid of lmweight_search.py, with dist = ctc_edit_distance(...)[0] and alphas, betas of shape (G,)::
+
+        total = ac + alphas[:, None] * lm_s + betas[:, None] * hyp_lengths            # (G, H)
+        best = total.view(G, N, nbest).argmax(2)                                      # (G, N)
+        errs = dist.view(N, nbest).expand(G, N, nbest).gather(2, best[..., None]).sum((1, 2))
+    """
+    H, W = _check_ngram_score_args(hyps, hyp_lengths, lm, eos)
+    dev = hyps.device
+    stride = max(W, 1)
+    scores = torch.empty(H, dtype=torch.float32, device=dev)
+    invalid = torch.empty(H, dtype=torch.int32, device=dev)
+    tok_lp = torch.empty((H, stride), dtype=torch.float32, device=dev) if return_token_scores else None
+    tok_or = torch.empty((H, stride), dtype=torch.int32, device=dev) if return_token_scores else None
+    if H > 0:
+        # (the C ABI has one stride for the rows and the per-token outputs, and a length up to it is valid: rows further apart are copied)
+        # (no row of width 0 in the C ABI: one word that is no token, so that only length 0 is valid)
+        rows = hyps.detach().contiguous() if W > 0 else torch.full((H, 1), -1, dtype=torch.int32, device=dev)
+        tables, keep = lm.tables(dev)
+        eos_t = keep.get("eos_logp") if eos else None
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            rc = _lib.crf_ngram_score(ctypes.byref(tables), _ptr(eos_t), _ptr(rows), stride, _ptr(hyp_lengths.contiguous()), H, 1 if bos else 0,
+                                      1 if eos else 0, _ptr(scores), _ptr(invalid), _ptr(tok_lp), _ptr(tok_or), _vp(stream))
+        _check(rc)
+    if return_token_scores:
+        return scores, invalid, tok_lp[:, :W], tok_or[:, :W]
+    return scores, invalid
 
 
 def gpu_den(logits: torch.Tensor, grad_net: torch.Tensor, input_lengths: torch.Tensor,

@@ -31,6 +31,9 @@ Same names, arguments and error behaviour as the reference:
   ctc_edit_distance(hyps, hyp_lengths, labels, label_lengths, hyp_utt=None, return_ops=False) -> dist IntTensor[H]
                                                               (with return_ops: (dist, sub, dele, ins), each IntTensor[H])
                                                                                          (token errors of hypotheses on the GPU: WER / PER sums, the MWER risk)
+  ngram_score(hyps, hyp_lengths, lm, bos=True, eos=False, return_token_scores=False) -> (scores FloatTensor[H], invalid IntTensor[H])
+                                                              (with return_token_scores: also token_logp [H, W], token_order [H, W])
+                                                                                         (n-gram LM scores of rows on the GPU: N-best rescoring)
 plus the functional form named by BASELINE.json:
   ctc_crf_loss(log_probs, labels, frame_lens, label_lens, den_lm, lamb=0.1, size_average=True)
 
@@ -452,7 +455,8 @@ def ctc_beam_search(log_probs: torch.Tensor, input_lengths: torch.Tensor, beam_s
     (cat/ctc/train.py:273-281, train_jsa.py:467-476, decode.py:163-222), in one call without a host round trip.  With lm it is the
     decoder's other half, CTCBeamDecoder(model_path=<KenLM n-gram>, alpha=, beta=, is_token_based=True): shallow fusion of a token-level
     n-gram LM read from the ARPA file that lmplz writes (NgramLM.from_arpa; a token is a class of log_probs).  Not covered: an
-    end-of-sentence term, word-level LMs and lexicons, KenLM's binary formats, an LM in ctc_sample.
+    end-of-sentence term in the search (it is in ngram_score, not in the search), word-level LMs and lexicons, KenLM's binary formats,
+    an LM in ctc_sample.
 
     log_probs: (N, T, V) on the GPU, or (T, N, V) with time_major=True; fp32, bf16 or fp16, read in place: log-probs, or with
         fuse_log_softmax=True the RAW network output (log_softmax of the upcast values inside the call).
@@ -511,6 +515,44 @@ def ctc_edit_distance(hyps: torch.Tensor, hyp_lengths: torch.Tensor, labels: tor
     with torch.no_grad():
         dist, ops = core.ctc_edit_distance(hyps.detach(), hyp_lengths, labels, label_lengths, hyp_utt, bool(return_ops))
     return (dist, ops[:, 0], ops[:, 1], ops[:, 2]) if return_ops else dist
+
+
+def ngram_score(hyps: torch.Tensor, hyp_lengths: torch.Tensor, lm: NgramLM, bos: bool = True, eos: bool = False,
+                return_token_scores: bool = False):
+    """n-gram LM scores of hypothesis rows that lie on the GPU: log P_lm of the second pass -- what cat/lm/rescore.py:168-177 gets per
+    N-best entry from cat/shared/decoder.py:542-572 (NGram.score: `.cpu()`, a Python list of strings and one kenlm.Model.score call per
+    sentence) and cat/utils/lm/lmweight_search.py computes again for every (alpha, beta) -- for the rows of ctc_sample, ctc_greedy and
+    ctc_beam_search, with any model, independent of the weights.
+
+    Rescoring (ac: the acoustic scores, ctc_score's or the search's; rows of one utterance adjacent):
+
+        lm_s, _ = ngram_score(hyps, hyp_lengths, lm, eos=True)
+        total = ac + alpha * lm_s + beta * hyp_lengths
+        best = total.view(N, nbest).argmax(1)
+
+    The weight grid of lmweight_search.py (alphas, betas of shape (G,); dist = ctc_edit_distance(hyps, hyp_lengths, labels, label_lengths,
+    hyp_utt)): one broadcast, one gather, two sums per grid point --
+
+        total = ac + alphas[:, None] * lm_s + betas[:, None] * hyp_lengths                 # (G, H)
+        best = total.view(G, N, nbest).argmax(2)                                           # (G, N)
+        wer = dist.view(N, nbest).expand(G, N, nbest).gather(2, best[..., None]).sum((1, 2)) / label_lengths.sum()
+
+    hyps (H, W) int32 on the GPU, W <= 8192: row h holds hypothesis h in its first hyp_lengths[h] entries; what stands behind is never read.
+        Rows a stride apart are taken as ctc_score takes them.
+    hyp_lengths (H,) int32 on the same GPU.  CPU tensors raise ValueError: on the host NgramLM.score is the way.
+    lm: an NgramLM; its tables and eos_logp are uploaded once per device and kept.  lm.vocab_size is compared with nothing: there are no
+        activations here, a token outside [0, lm.vocab_size) makes its row invalid.
+    bos: the walk starts in lm.start (the state of <s> where the model has one), else at the root.
+    eos: add log P(</s> | the row) = lm.eos_logp[state behind the last token]; ValueError where the model has no </s> unigram.
+
+    Returns (scores (H,) fp32 in natural log, invalid (H,) int32) and, with return_token_scores, token_logp (H, W) fp32 and token_order
+    (H, W) int32: per position the value NgramLM.lookup gives along the walk, bit for bit, and the number of tokens of the n-gram found
+    (kenlm's full_scores: where a hypothesis backs off), both 0 behind the length -- on hyps' device, no autograd history, no host
+    synchronisation.  scores is the fp64 sum of the row's token_logp (and the end-of-sentence value) rounded once; a row's outputs are the
+    same bits in any batch, order and call.  An invalid row (length outside [0, W], a token outside the vocabulary among its first
+    hyp_lengths[h]) scores -inf with invalid = 1; mask a row with length -1 to keep it out of every sum."""
+    with torch.no_grad():
+        return core.ngram_score(hyps, hyp_lengths, lm, bool(bos), bool(eos), bool(return_token_scores))
 
 
 _CTX_CACHE: Dict[Tuple[str, int], CRFContext] = {}

@@ -6,9 +6,10 @@ crf_ctc_beam_lm walks on the device (include/ctc_crf_hip.h crf_ngram_tables).
     hyps, hl, hu, scores = ctc_beam_search(log_probs, lx, beam_size=16, lm=lm, alpha=0.5, beta=1.0)
 
 Tokens: the string "17" is class 17; "<s>", "</s>" and "<unk>" are the only non-numeric tokens.  Values are log10 in the file and in the
-dict, natural logs in the tables (converted in fp64, stored in fp32).  Dropped: n-grams that contain "</s>" (no end-of-sentence term is
-scored), that hold "<s>" anywhere but first, and n-grams of order >= 2 that contain "<unk>".  A class in [0, vocab_size) without a
-unigram takes <unk>'s unigram value, or unk_logp (log10) where the model has no <unk>.
+dict, natural logs in the tables (converted in fp64, stored in fp32).  Dropped: n-grams that hold "<s>" anywhere but first, and n-grams of
+order >= 2 that contain "<unk>".  N-grams that end in "</s>" enter no table: they are kept aside and resolved into eos_logp (below); a
+"</s>" anywhere but last raises.  A class in [0, vocab_size) without a unigram takes <unk>'s unigram value, or unk_logp (log10) where the
+model has no <unk>.
 
 Tables (numpy, one set per model): the states are the empty history (state 0, the root) and every kept n-gram of order 1 .. N - 1, sorted
 by history length (so bo_state[s] < s for s > 0); row s of the arcs is arc_*[row_off[s] .. row_off[s + 1]) with arc_label ascending; the
@@ -16,7 +17,14 @@ root's row is dense (uni_logp[V], uni_next[V]) and its sparse row empty; arc_nex
 tokens that is a state; bo_state[s] is the longest proper suffix of s that is a state, bo_weight[s] the model's back-off weight of s (0
 where it gives none); start is the state of "<s>", or the root.
 
-Not covered: an end-of-sentence term, word-level LMs and lexicons, KenLM's binary formats, an LM in ctc_sample."""
+The end-of-sentence values: eos_logp[s] = log P(</s> | history of s) in natural log, float32 [S], or None where the model has no "</s>"
+unigram -- resolved here in fp64 by the textbook rule (the longest h + </s> in the model; otherwise the back-off weight of h where h is in
+the model, and on without h's oldest token, down to the "</s>" unigram) and rounded to fp32 once: ngram_score(eos=True) and
+score(tokens, eos=True) add one entry per hypothesis, without a walk.  A "</s>" n-gram whose context is longer than order - 1 tokens is
+the context of no state and is never reached.
+
+Not covered: an end-of-sentence term in the search (it is in ngram_score, not in the search), word-level LMs and lexicons, KenLM's binary
+formats, an LM in ctc_sample."""
 import ctypes
 import math
 from typing import Dict, Optional, Tuple
@@ -57,7 +65,7 @@ class NgramLM:
         V = int(vocab_size)
         if V < 1:
             raise ValueError(f"NgramLM: vocab_size must be positive, got {vocab_size}")
-        kept, unk = {}, None
+        kept, unk, eos_ng = {}, None, {}
         for key, val in ngrams.items():
             key = tuple(key)
             at = _where(_lines, key)
@@ -80,7 +88,13 @@ class NgramLM:
                     if not 0 <= w < V:
                         raise ValueError(f"NgramLM: token {w} outside [0, vocab_size={V}){at}")
                 toks.append(w)
-            if EOS in toks or BOS in toks[1:]:
+            if EOS in toks[:-1]:
+                raise ValueError(f"NgramLM: </s> anywhere but last (inside a context) in n-gram {key}{at}")
+            if BOS in toks[1:]:
+                continue
+            if toks[-1] == EOS:                 # kept aside: no table holds it (eos_logp below)
+                if UNK not in toks:
+                    eos_ng[tuple(_BOS_ID if w == BOS else w for w in toks[:-1])] = lp * LN10
                 continue
             if UNK in toks:
                 if len(toks) == 1:
@@ -90,6 +104,10 @@ class NgramLM:
         for key in kept:
             if len(key) > 1 and key[:-1] not in kept:
                 shown = tuple(BOS if w == _BOS_ID else w for w in key)
+                raise ValueError(f"NgramLM: the prefix of n-gram {shown} is absent{_where(_lines, shown)}")
+        for ctx in eos_ng:
+            if ctx and ctx not in kept:
+                shown = tuple(BOS if w == _BOS_ID else w for w in ctx) + (EOS,)
                 raise ValueError(f"NgramLM: the prefix of n-gram {shown} is absent{_where(_lines, shown)}")
         if unk is None and unk_logp is not None:
             if not math.isfinite(float(unk_logp)):
@@ -143,7 +161,18 @@ class NgramLM:
         self.state_history = [tuple(BOS if w == _BOS_ID else w for w in k) for k in index]   # per state, for inspection
         self._checked = False
         self._device = {}
-        for name in ("arc_logp", "bo_weight", "uni_logp"):
+        self.eos_logp = None
+        if () in eos_ng:                        # log P(</s> | history of s) per state: fp64, one rounding to fp32
+            eos = np.zeros(S, np.float64)
+            for k, s in index.items():
+                h, acc = k, 0.0
+                while h not in eos_ng:          # (ends at the </s> unigram)
+                    if h in kept:
+                        acc += kept[h][1]
+                    h = h[1:]
+                eos[s] = acc + eos_ng[h]
+            self.eos_logp = eos.astype(np.float32)
+        for name in ("arc_logp", "bo_weight", "uni_logp") + (("eos_logp",) if self.eos_logp is not None else ()):
             if not np.isfinite(getattr(self, name)).all():
                 raise ValueError(f"NgramLM: {name} does not fit fp32")
         return self
@@ -233,9 +262,13 @@ class NgramLM:
         except ValueError as err:
             raise ValueError(f"{path}: {err}") from None
 
-    # ---- the walk, exactly as the kernel takes it (k_beam_lm.hip beamlm_lookup) ----
+    # ---- the walk, exactly as the kernels take it (k_ngram_common.h ngram_lookup) ----
     def lookup(self, state: int, token: int) -> Tuple[float, int]:
         """(log P(token | state) in natural log as the fp32 walk gives it, next state)."""
+        return self._lookup(state, token)[:2]
+
+    def _lookup(self, state: int, token: int) -> Tuple[float, int, int]:
+        """lookup's pair and the state in whose row the token was found (0: the root's dense row)."""
         s, c = int(state), int(token)
         if not (0 <= s < self.num_states and 0 <= c < self.vocab_size):
             raise IndexError(f"NgramLM.lookup: state {s} or token {c} out of range")
@@ -246,18 +279,32 @@ class NgramLM:
             lo, hi = int(self.row_off[s]), int(self.row_off[s + 1])
             i = lo + int(np.searchsorted(self.arc_label[lo:hi], c))
             if i < hi and self.arc_label[i] == c:
-                return float(np.float32(acc + self.arc_logp[i])), int(self.arc_next[i])
+                return float(np.float32(acc + self.arc_logp[i])), int(self.arc_next[i]), s
             acc = np.float32(acc + self.bo_weight[s])
             s = int(self.bo_state[s])
-        return float(np.float32(acc + self.uni_logp[c])), int(self.uni_next[c])
+        return float(np.float32(acc + self.uni_logp[c])), int(self.uni_next[c]), 0
 
-    def score(self, tokens) -> float:
-        """log P_lm(tokens) in natural log: the sum of the walk from `start` (no end-of-sentence term)."""
+    def score(self, tokens, eos: bool = False) -> float:
+        """log P_lm(tokens) in natural log: the sum of the walk from `start`; with eos plus eos_logp[state behind the last token] (of
+        `start` for an empty sequence), else no end-of-sentence term."""
+        if eos and self.eos_logp is None:
+            raise ValueError("NgramLM.score: eos=True needs a model with a </s> unigram (eos_logp is None)")
         s, total = self.start, 0.0
         for c in tokens:
             lp, s = self.lookup(s, c)
             total += lp
-        return total
+        return total + float(self.eos_logp[s]) if eos else total
+
+    def token_scores(self, tokens, bos: bool = True):
+        """What ngram_score writes per position: (the values lookup gives along the walk from `start` -- bos=False: from the root --, the
+        lengths of the n-grams found: the tokens of the history of the state whose row held the token, a <s> among them counted, plus 1;
+        1 at the root, also for a class that took <unk>'s value)."""
+        s, lps, orders = self.start if bos else 0, [], []
+        for c in tokens:
+            lp, s, at = self._lookup(s, c)
+            lps.append(lp)
+            orders.append(len(self.state_history[at]) + 1)
+        return lps, orders
 
     # ---- the device side ----
     def host_tables(self) -> Dict[str, np.ndarray]:
@@ -277,7 +324,8 @@ class NgramLM:
         self._checked = True
 
     def tables(self, device):
-        """The tables on `device` (uploaded once per device and kept) as (crf_ngram_tables struct of device pointers, dict of tensors)."""
+        """The tables on `device` (uploaded once per device and kept) as (crf_ngram_tables struct of device pointers, dict of tensors;
+        with "eos_logp" where the model has one)."""
         import torch
         from .ctc_crf import _C
         device = torch.device(device)
@@ -287,6 +335,8 @@ class NgramLM:
             self.check(_C._lib)
             tens = {name: torch.from_numpy(np.ascontiguousarray(a)).to(device) for name, a in self.host_tables().items()}
             st = self._struct(lambda name: tens[name].data_ptr() if tens[name].numel() else None)
+            if self.eos_logp is not None:       # (beside the struct: crf_ngram_score takes it as an argument of its own)
+                tens["eos_logp"] = torch.from_numpy(np.ascontiguousarray(self.eos_logp)).to(device)
             self._device[device] = (st, tens)
         return self._device[device]
 

@@ -497,7 +497,8 @@ const char *crf_last_beam_kernel(void);
  * No host synchronisation, all work on `stream`, no environment variable read.
  * Errors: crf_ctc_beam's, and CRF_ERR_ARG for a null lm, lm->V != V, alpha or beta not finite, lm->S < 1, lm->order outside [1, 8],
  * lm->start outside [0, S) or a null table -- all answered before any HIP call.
- * Not covered: an end-of-sentence term, word-level LMs and lexicons, KenLM's binary formats, an LM in crf_ctc_sample. */
+ * Not covered: an end-of-sentence term in the search (it is in crf_ngram_score, not in the search), word-level LMs and lexicons, KenLM's
+ * binary formats, an LM in crf_ctc_sample. */
 typedef struct crf_ngram_tables {
     const int32_t *row_off;    /* [S + 1] */
     const int32_t *arc_label;  /* [A] */
@@ -517,6 +518,44 @@ int crf_ctc_beam_lm(const void *act_dev, int dtype, int time_major, int blank, i
                     const crf_ngram_tables *lm, float alpha, float beta,
                     int32_t *hyps_dev, int32_t *hyp_len_dev, float *score_dev, float *lm_score_dev, int32_t *trace_dev,
                     void *workspace_dev, int64_t workspace_bytes, void *stream);
+
+/* n-gram LM scores of H hypotheses that lie on the device as padded rows: log P_lm of the second pass, what cat/lm/rescore.py:168-177
+ * (final = score + alpha * log P_lm + beta * len per N-best entry) takes from cat/shared/decoder.py:542-572 (NGram.score: `.cpu()`, a
+ * list of strings and one kenlm.Model.score call per sentence) and cat/utils/lm/lmweight_search.py repeats per (alpha, beta) -- for the
+ * rows crf_ctc_sample / crf_ctc_beam / crf_ctc_beam_lm leave on the device, with any model and independent of the weights.
+ *   Tables    crf_ngram_tables and the Lookup rule as above.  eos_logp_dev (may be NULL without add_eos) [S] fp32: log P(</s> | history
+ *             of state s) in natural log, resolved when the model is compiled (cat_amd/ngram_lm.py eos_logp).
+ *   Hypothesis h = the first hyp_len_dev[h] entries of row h of hyps_dev, rows hyp_stride entries apart; entries behind the length are
+ *             never read.
+ *   Position  token_logp_dev (may be NULL) [H][hyp_stride] fp32: for i < L bit for bit lp(state_i, t_i) of the Lookup rule (acc starts at
+ *             0, the terms are added in fp32 in the walk's order, one rounded addition each; there is no multiply), state_i the state of
+ *             the sequential walk from `start` (use_start != 0) or from the root (use_start == 0) -- the kernel resolves every position
+ *             on its own from the last order - 1 tokens, which gives the same state.  token_order_dev (may be NULL) [H][hyp_stride]
+ *             int32: the tokens of the n-gram found, context tokens used plus 1 (a <s> in the context counts; 1 at the root's row, also
+ *             for a class that took <unk>'s value).  Both are 0 for L <= i < hyp_stride: every word of both is written.
+ *             token_order reads the history length of a state off the order of the states: sorted by history length and, inside one
+ *             length, in the order of the arcs that lead to them (as cat_amd/ngram_lm.py numbers them); with tables numbered otherwise
+ *             it is some value in [1, order].
+ *   Score     score_dev [H] fp32 = float(sum_{i<L} double(token_logp[h][i]) + (add_eos ? double(eos_logp[state_L]) : 0)), state_L the
+ *             state behind the last token (`start`, or the root, for an empty row).  The fp64 sum runs in an order that depends on L
+ *             alone: a row's outputs are the same bits in any batch, at any place of the list, in any call and whichever optional
+ *             outputs are asked for.  An empty row scores 0, or eos_logp[start] (of the root with use_start == 0).
+ *   Invalid   hyp_len[h] < 0 or > hyp_stride, or a token outside [0, V) among the first L: score = -inf, invalid_dev[h] (may be NULL) = 1
+ *             (else 0), its per-token rows all 0; nothing is read outside the row's first min(max(L, 0), hyp_stride) words.
+ * Memory safety whatever the tables hold, as for crf_ctc_beam_lm: at most min(order, 8) rows per look-up and then the root's, at most 14
+ * probes per row, every state and arc index clamped.  Tables that do not pass crf_ngram_tables_check give unspecified values, never an
+ * access out of bounds and never a hang.
+ * crf_last_ngram_score_kernel() names the instantiation of this thread's last call: "crf_ngram_score_kernel<scores>" or
+ * "crf_ngram_score_kernel<tokens>" (a per-token output asked for).  No workspace, no host synchronisation, all work on `stream`, no
+ * environment variable read.
+ * CRF_ERR_ARG: a null lm, a null table, null hyps_dev / hyp_len_dev / score_dev, lm->S < 1, lm->order outside [1, 8], lm->start outside
+ * [0, S), lm->V outside [1, 8192], H < 0, hyp_stride outside [1, 8192], add_eos with a null eos_logp_dev -- all answered before any HIP
+ * call.  H == 0 succeeds and launches nothing.
+ * Not covered: word-level LMs and lexicons, KenLM's binary formats, neural LMs, V or hyp_stride beyond 8192. */
+int crf_ngram_score(const crf_ngram_tables *lm, const float *eos_logp_dev, const int32_t *hyps_dev, int64_t hyp_stride,
+                    const int32_t *hyp_len_dev, int64_t H, int use_start, int add_eos, float *score_dev, int32_t *invalid_dev,
+                    float *token_logp_dev, int32_t *token_order_dev, void *stream);
+const char *crf_last_ngram_score_kernel(void);
 
 /* Token edit distance of H hypotheses to the transcripts of their utterances, with the operation counts of one optimal alignment: what
  * cat/ctc/train.py:200-210 (cal_wer), train_jsa.py:371-387 (cal_per), train_me2e.py:250-256 and train_me2e_kaldi.py:420-426 compute with
