@@ -480,11 +480,12 @@ static int launch_beam_lm(const BeamLmParams &q, hipStream_t st) {
                                                       (size_t)R * p.V * sizeof(float), st, p)) return rc;
     return launch<crf_beamlm_search_kernel>("crf_beamlm_search_kernel", dim3((unsigned)p.B), dim3(64 * kBeamLmWaves), 0, st, q);
 }
-// the argument checks of crf_ctc_beam and crf_ctc_beam_lm (lm: null for the LM-free call), then the launch; every error before any HIP call
-static int beam_call(const char *who, const void *act, int dtype, int time_major, int blank, int normalize, const int32_t *lx, int64_t B,
-                     int64_t T, int64_t V, int64_t W, int64_t nbest, int64_t top_classes, const crf_ngram_tables *lm, bool with_lm, float alpha,
-                     float beta, int32_t *hyps, int32_t *hyp_len, float *score, float *lm_score, int32_t *trace, void *ws, int64_t ws_bytes,
-                     hipStream_t st) {
+// the argument checks of crf_ctc_beam, crf_ctc_beam_lm (lm: null for the LM-free call) and crf_ctc_beam_chunk, and the kernels' arguments;
+// no HIP call
+static int beam_setup(const char *who, const void *act, int dtype, int time_major, int blank, int normalize, const int32_t *lx, int64_t B,
+                      int64_t T, int64_t V, int64_t W, int64_t nbest, int64_t top_classes, const crf_ngram_tables *lm, bool with_lm, float alpha,
+                      float beta, int32_t *hyps, int32_t *hyp_len, float *score, float *lm_score, int32_t *trace, void *ws, int64_t ws_bytes,
+                      BeamLmParams &q) {
     const std::string w0 = std::string(who) + ": ";
     if (!act || !lx || !hyps || !hyp_len || !score || !ws || (with_lm && !lm)) { set_error(w0 + "null argument"); return CRF_ERR_ARG; }
     if (dtype < 0 || dtype > 2) return bad_dtype(who);
@@ -509,19 +510,43 @@ static int beam_call(const char *who, const void *act, int dtype, int time_major
             (lm->A > 0 && (!lm->arc_label || !lm->arc_logp || !lm->arc_next))) { set_error(w0 + "null LM table"); return CRF_ERR_ARG; }
     }
     if (const int rc = check_ws(ws_bytes, need)) return rc;
-    BeamLmParams q{};
+    q = BeamLmParams{};
     BeamParams &p = q.b;
     set_act(p, act, lx, B, T, V, blank, time_major);
     p.W = (int)W; p.nbest = (int)nbest; p.C = (int)std::min(top_classes, V - 1); p.normalize = normalize;
     p.val = (float *)((char *)ws + w.sec[kBmVal].off); p.cls = (int *)((char *)ws + w.sec[kBmCls].off);
     p.trace = trace ? trace : (int *)((char *)ws + w.sec[kBmTrace].off); p.fill_trace = trace != nullptr;
     p.hyps = hyps; p.hyp_len = hyp_len; p.score = score;
-    if (!with_lm) return with_dtype(dtype, [&](auto e) { return launch_beam<decltype(e)>(p, st); });
+    if (!with_lm) return CRF_OK;
     q.lm.row_off = lm->row_off; q.lm.arc_label = lm->arc_label; q.lm.arc_logp = lm->arc_logp; q.lm.arc_next = lm->arc_next;
     q.lm.bo_state = lm->bo_state; q.lm.bo_weight = lm->bo_weight; q.lm.uni_logp = lm->uni_logp; q.lm.uni_next = lm->uni_next;
     q.lm.S = (int)lm->S; q.lm.A = (int)lm->A; q.lm.V = (int)lm->V; q.lm.order = lm->order; q.lm.start = lm->start;
     q.alpha = alpha; q.beta = beta; q.lm_score = lm_score;
+    return CRF_OK;
+}
+// crf_ctc_beam and crf_ctc_beam_lm: the checks, then the launch; every error before any HIP call
+static int beam_call(const char *who, const void *act, int dtype, int time_major, int blank, int normalize, const int32_t *lx, int64_t B,
+                     int64_t T, int64_t V, int64_t W, int64_t nbest, int64_t top_classes, const crf_ngram_tables *lm, bool with_lm, float alpha,
+                     float beta, int32_t *hyps, int32_t *hyp_len, float *score, float *lm_score, int32_t *trace, void *ws, int64_t ws_bytes,
+                     hipStream_t st) {
+    BeamLmParams q;
+    if (const int rc = beam_setup(who, act, dtype, time_major, blank, normalize, lx, B, T, V, W, nbest, top_classes, lm, with_lm, alpha, beta, hyps,
+                                  hyp_len, score, lm_score, trace, ws, ws_bytes, q)) return rc;
+    if (!with_lm) return with_dtype(dtype, [&](auto e) { return launch_beam<decltype(e)>(q.b, st); });
     return with_dtype(dtype, [&](auto e) { return launch_beam_lm<decltype(e)>(q, st); });
+}
+// the row stage on the chunk's frames, then the search that loads and stores the beam (k_beam_chunk.hip), on the same stream
+template <typename E>
+static int launch_beam_chunk(const BeamChunkParams &cp, bool with_lm, hipStream_t st) {
+    static const char *const names[3] = {"crf_beam_row_kernel<f32>", "crf_beam_row_kernel<bf16>", "crf_beam_row_kernel<f16>"};
+    constexpr int ei = std::is_same<E, float>::value ? 0 : std::is_same<E, AlnBf16>::value ? 1 : 2;
+    const BeamParams &p = cp.q.b;
+    const int64_t frames = (int64_t)p.B * p.T;
+    const int R = p.V <= kBeamRowsV ? 4 : 1;
+    if (const int rc = launch<crf_beam_row_kernel<E>>(g_beam_kernel = names[ei], dim3((unsigned)((frames + R - 1) / R)), dim3(64 * R),
+                                                      (size_t)R * p.V * sizeof(float), st, p)) return rc;
+    return with_lm ? launch<crf_beamlm_chunk_kernel>("crf_beamlm_chunk_kernel", dim3((unsigned)p.B), dim3(64 * kBeamLmWaves), 0, st, cp)
+                   : launch<crf_beam_chunk_kernel>("crf_beam_chunk_kernel", dim3((unsigned)p.B), dim3(64), 0, st, cp);
 }
 
 // ---- edit distance (k_edit.hip) ----
@@ -695,6 +720,40 @@ int crf_ctc_beam_lm(const void *act, int dtype, int time_major, int blank, int n
                     int32_t *hyp_len, float *score, float *lm_score, int32_t *trace, void *ws, int64_t ws_bytes, void *stream_) {
     return beam_call("crf_ctc_beam_lm", act, dtype, time_major, blank, normalize, lx, B, T, V, W, nbest, top_classes, lm, true, alpha, beta, hyps,
                      hyp_len, score, lm_score, trace, ws, ws_bytes, (hipStream_t)stream_);
+}
+
+int64_t crf_ctc_beam_state_record_bytes(int64_t W, int64_t cap) {
+    if (W < 1 || W > kBeamMaxW) { set_error("crf_ctc_beam_chunk: beam width " + std::to_string(W) + " outside [1, " + std::to_string(kBeamMaxW) + "]"); return -1; }
+    if (cap < 1 || cap > kBeamStateMaxCap) { set_error("crf_ctc_beam_chunk: cap " + std::to_string(cap) + " outside [1, " + std::to_string(kBeamStateMaxCap) + "]"); return -1; }
+    return beam_state_bytes(W, cap);
+}
+
+int64_t crf_ctc_beam_chunk_workspace_bytes(int64_t B, int64_t Tc, int64_t V, int64_t W, int64_t top_classes) {
+    return or_minus1(beam_ws_bytes(B, Tc, V, W, top_classes));
+}
+
+int crf_ctc_beam_chunk(const void *act, int dtype, int time_major, int blank, int normalize, const int32_t *lx_chunk, int64_t B, int64_t Tc,
+                       int64_t V, int64_t W, int64_t nbest, int64_t top_classes, const crf_ngram_tables *lm, float alpha, float beta,
+                       const void *state_in, const int32_t *reset, void *state_out, int64_t cap, int32_t *hyps, int32_t *hyp_len, float *score,
+                       float *lm_score, int32_t *trace, void *ws, int64_t ws_bytes, void *stream_) {
+    const char *who = "crf_ctc_beam_chunk";
+    const std::string w0 = std::string(who) + ": ";
+    if (!state_out) { set_error(w0 + "null argument (state_out_dev)"); return CRF_ERR_ARG; }
+    BeamChunkParams cp{};
+    if (const int rc = beam_setup(who, act, dtype, time_major, blank, normalize, lx_chunk, B, Tc, V, W, nbest, top_classes, lm, lm != nullptr,
+                                  lm ? alpha : 0.f, lm ? beta : 0.f, hyps, hyp_len, score, lm_score, trace, ws, ws_bytes, cp.q)) return rc;
+    if (cap < 1 || cap > kBeamStateMaxCap) {
+        set_error(w0 + "cap " + std::to_string(cap) + " outside [1, " + std::to_string(kBeamStateMaxCap) + "]"); return CRF_ERR_ARG;
+    }
+    const int64_t rec = beam_state_bytes(W, cap);
+    if (state_in) {
+        const uintptr_t a = (uintptr_t)state_in, o = (uintptr_t)state_out, n = (uintptr_t)(B * rec);
+        if (a < o + n && o < a + n) { set_error(w0 + "state_out_dev overlaps state_in_dev (label rows move between slots)"); return CRF_ERR_ARG; }
+    }
+    if (((uintptr_t)state_out | (uintptr_t)state_in) & 7) { set_error(w0 + "the states must be 8-byte aligned"); return CRF_ERR_ARG; }
+    cp.state_in = (const char *)state_in; cp.reset = reset; cp.state_out = (char *)state_out; cp.cap = (int)cap; cp.rec = rec;
+    const bool with_lm = lm != nullptr;
+    return with_dtype(dtype, [&](auto e) { return launch_beam_chunk<decltype(e)>(cp, with_lm, (hipStream_t)stream_); });
 }
 
 // HOST copies of the tables, no HIP call: the first offending entry by name

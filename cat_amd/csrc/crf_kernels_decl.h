@@ -190,6 +190,26 @@ struct BeamLmParams {
 };
 __global__ void crf_beamlm_search_kernel(BeamLmParams p);   // kBeamLmWaves waves (one workgroup) per utterance
 
+// ---- k_beam_chunk.hip ----
+// The record of one utterance's beam between two crf_ctc_beam_chunk calls (include/ctc_crf_hip.h): the slots' fields as arrays of W
+// entries, one after the other -- pb, pnb, lm (fp64), id, pid (64-bit), alive, e, len, lms (int32): kBeamStateSlotBytes a slot -- then
+// the W label rows of cap int32, then zero bytes up to a multiple of 16.
+constexpr int kBeamStateSlotBytes = 5 * 8 + 4 * 4;
+constexpr int kBeamStateMaxCap = 8192;    // labels kept per prefix at most (kNgramMaxStride, kEditStripMaxCols: what the consumers of the rows take)
+__host__ __device__ constexpr int64_t beam_state_rows_off(int64_t W) { return kBeamStateSlotBytes * W; }
+__host__ __device__ constexpr int64_t beam_state_bytes(int64_t W, int64_t cap) { return (beam_state_rows_off(W) + 4 * W * cap + 15) & ~(int64_t)15; }
+// Kernel arguments of crf_ctc_beam_chunk: the searches' with T = the chunk's frames, lx = the chunk's lengths and hyps rows of cap words
+struct BeamChunkParams {
+    BeamLmParams q;             // (without an LM: q.b alone is read)
+    const char *state_in;       // [B] records or null: every utterance starts fresh
+    const int *reset;           // [B] or null: != 0 starts utterance b fresh
+    char *state_out;            // [B] records
+    int cap;
+    int64_t rec;                // beam_state_bytes(W, cap)
+};
+__global__ void crf_beam_chunk_kernel(BeamChunkParams p);     // one wave (workgroup) per utterance
+__global__ void crf_beamlm_chunk_kernel(BeamChunkParams p);   // kBeamLmWaves waves (one workgroup) per utterance
+
 // ---- k_ngram.hip ----
 constexpr int kNgramScoreWaves = 4;       // hypotheses (waves) per workgroup
 constexpr int kNgramMaxStride = 8192;     // words between two rows, and the per-token outputs' row length

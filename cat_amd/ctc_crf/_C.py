@@ -112,6 +112,13 @@ _lib.crf_ctc_beam_lm_workspace_bytes.restype = _i64
 _lib.crf_ctc_beam_lm.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _i64, _i64, _i64, _i64, _i64, _i64,
                                  _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]
 _lib.crf_ctc_beam_lm.restype = ctypes.c_int
+_lib.crf_ctc_beam_state_record_bytes.argtypes = [_i64, _i64]
+_lib.crf_ctc_beam_state_record_bytes.restype = _i64
+_lib.crf_ctc_beam_chunk_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64, _i64]
+_lib.crf_ctc_beam_chunk_workspace_bytes.restype = _i64
+_lib.crf_ctc_beam_chunk.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _i64, _i64, _i64, _i64, _i64, _i64,
+                                    _vp, _f32, _f32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]
+_lib.crf_ctc_beam_chunk.restype = ctypes.c_int
 _lib.crf_ctc_edit_distance.argtypes = [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]
 _lib.crf_ctc_edit_distance.restype = ctypes.c_int
 _lib.crf_last_edit_kernel.restype = ctypes.c_char_p
@@ -142,7 +149,7 @@ _lib.crf_build_switches.restype = ctypes.c_char_p
 
 EXPORTED_SYMBOLS = (
     "crf_graph_create", "crf_graph_create_from_arcs", "crf_graph_destroy", "crf_graph_dims", "crf_graph_stats",
-    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_ws_fields", "crf_debug_ws_field_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_ctc_score", "crf_ctc_score_logits_workspace_bytes", "crf_ctc_score_logits", "crf_last_score_kernel", "crf_ctc_score_grad_workspace_bytes", "crf_ctc_score_grad", "crf_ctc_score_grad_logits_workspace_bytes", "crf_ctc_score_grad_logits", "crf_last_score_grad_kernel", "crf_ctc_score_rows_workspace_bytes", "crf_ctc_score_rows", "crf_ctc_score_grad_rows_workspace_bytes", "crf_ctc_score_grad_rows", "crf_debug_score_rows_ws_sections", "crf_debug_score_rows_ws_section_names", "crf_ctc_sample_workspace_bytes", "crf_ctc_sample", "crf_last_sample_kernel", "crf_ctc_beam_workspace_bytes", "crf_ctc_beam", "crf_last_beam_kernel", "crf_ngram_tables_check", "crf_ctc_beam_lm_workspace_bytes", "crf_ctc_beam_lm", "crf_ctc_edit_distance", "crf_last_edit_kernel", "crf_ngram_score", "crf_last_ngram_score_kernel", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
+    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_ws_fields", "crf_debug_ws_field_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_ctc_score", "crf_ctc_score_logits_workspace_bytes", "crf_ctc_score_logits", "crf_last_score_kernel", "crf_ctc_score_grad_workspace_bytes", "crf_ctc_score_grad", "crf_ctc_score_grad_logits_workspace_bytes", "crf_ctc_score_grad_logits", "crf_last_score_grad_kernel", "crf_ctc_score_rows_workspace_bytes", "crf_ctc_score_rows", "crf_ctc_score_grad_rows_workspace_bytes", "crf_ctc_score_grad_rows", "crf_debug_score_rows_ws_sections", "crf_debug_score_rows_ws_section_names", "crf_ctc_sample_workspace_bytes", "crf_ctc_sample", "crf_last_sample_kernel", "crf_ctc_beam_workspace_bytes", "crf_ctc_beam", "crf_last_beam_kernel", "crf_ngram_tables_check", "crf_ctc_beam_lm_workspace_bytes", "crf_ctc_beam_lm", "crf_ctc_beam_state_record_bytes", "crf_ctc_beam_chunk_workspace_bytes", "crf_ctc_beam_chunk", "crf_ctc_edit_distance", "crf_last_edit_kernel", "crf_ngram_score", "crf_last_ngram_score_kernel", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
     "crf_debug_set", "crf_debug_unset", "crf_debug_list", "crf_last_den_kernel", "crf_last_call_streams", "crf_last_side_stream", "crf_last_fallback_counts", "crf_build_switches", "crf_last_error", "crf_version",
 )
 
@@ -1202,6 +1209,133 @@ def ctc_beam_search(log_probs: torch.Tensor, lx: torch.Tensor, beam_size: int = 
     _check(rc)
     del lx_d
     return hyps, hyp_len, scores, trace
+
+
+BEAM_STATE_MAX_HYP_LEN = 8192   # most labels a BeamState keeps per prefix (include/ctc_crf_hip.h crf_ctc_beam_chunk: cap)
+
+
+class BeamState:
+    """The beams of N utterances between two ctc_beam_search_chunk calls: the (N, record_bytes) uint8 tensor of records that
+    include/ctc_crf_hip.h ``crf_ctc_beam_chunk`` writes, and the values it was made under.  Immutable: every call allocates the records
+    it returns, none writes to the records it continues from, so a state can be continued any number of times."""
+    FIELDS = ("beam_size", "top_classes", "blank", "max_hyp_len", "lm", "alpha", "beta")
+    __slots__ = ("records",) + FIELDS
+
+    def __init__(self, records: torch.Tensor, beam_size: int, top_classes: int, blank: int, max_hyp_len: int, lm, alpha: float, beta: float):
+        self.records = records
+        self.beam_size, self.top_classes, self.blank, self.max_hyp_len = int(beam_size), int(top_classes), int(blank), int(max_hyp_len)
+        self.lm, self.alpha, self.beta = lm, float(alpha), float(beta)
+
+    def _like(self, records: torch.Tensor) -> "BeamState":
+        return BeamState(records, self.beam_size, self.top_classes, self.blank, self.max_hyp_len, self.lm, self.alpha, self.beta)
+
+    def __len__(self) -> int:
+        return self.records.size(0)
+
+    def index_select(self, index: torch.Tensor) -> "BeamState":
+        """The states of the utterances index[0], index[1], ... (an int tensor; on the CPU it is copied to the records' device)."""
+        return self._like(self.records.index_select(0, index.to(device=self.records.device, dtype=torch.int64)))
+
+    def clone(self) -> "BeamState":
+        return self._like(self.records.clone())
+
+    def __repr__(self) -> str:
+        return "BeamState(N=%d, %s)" % (len(self), ", ".join(f"{k}={getattr(self, k)!r}" for k in self.FIELDS))
+
+
+def ctc_beam_search_chunk(log_probs: torch.Tensor, lx: torch.Tensor, state: Optional[BeamState] = None, reset: Optional[torch.Tensor] = None,
+                          beam_size: int = 16, nbest: int = 1, top_classes: int = 40, blank: int = 0, time_major: bool = False,
+                          fused: bool = False, lm=None, alpha: float = 0.0, beta: float = 0.0, max_hyp_len: int = 512,
+                          return_trace: bool = False, return_lm_scores: bool = False):
+    """ctc_beam_search on a chunk of frames, the beam carried in a BeamState (include/ctc_crf_hip.h ``crf_ctc_beam_chunk``).
+
+    log_probs [N,Tc,V] (time_major: [Tc,N,V]) as for ctc_beam_search; lx (N,): the chunk's frames per utterance, an int tensor on the
+    CPU (checked against [0, Tc]) or an int32 tensor on the GPU (used as is, clamped in the kernel); reset: None or (N,) bool / int, CPU
+    or GPU.  Returns (BeamState, hyps [N nbest, max_hyp_len] int32, hyp_lengths, scores, trace [N, Tc, beam_size] or None, lm_scores or
+    None), all on the device, no host synchronisation."""
+    who = "ctc_beam_search_chunk"
+    if log_probs.dtype not in _FUSED_DTYPES:
+        raise RuntimeError(f"{who}: expect float32, bfloat16 or float16 activations, got {log_probs.dtype}")
+    if log_probs.dim() != 3:
+        raise RuntimeError(f"{who}: expect (N, Tc, V) or (Tc, N, V) activations, got {log_probs.dim()} dimensions")
+    N, T, V = log_probs.shape
+    if time_major:
+        T, N = N, T
+    if N < 1 or T < 1 or V < 1:
+        raise RuntimeError(f"{who}: expect a chunk of at least one utterance, frame and class, got shape {tuple(log_probs.shape)}")
+    if not 0 <= blank < V:
+        raise RuntimeError(f"blank must lie in [0, V-1={V - 1}], got {blank}")
+    if not 1 <= int(beam_size) <= BEAM_MAX_WIDTH:
+        raise RuntimeError(f"{who}: beam_size must lie in [1, {BEAM_MAX_WIDTH}], got {beam_size}")
+    if not 1 <= int(nbest) <= int(beam_size):
+        raise RuntimeError(f"{who}: nbest must lie in [1, beam_size={beam_size}], got {nbest}")
+    if not 1 <= int(top_classes) <= BEAM_MAX_CLASSES:
+        raise RuntimeError(f"{who}: top_classes must lie in [1, {BEAM_MAX_CLASSES}], got {top_classes}")
+    if not 1 <= int(max_hyp_len) <= BEAM_STATE_MAX_HYP_LEN:
+        raise RuntimeError(f"{who}: max_hyp_len must lie in [1, {BEAM_STATE_MAX_HYP_LEN}], got {max_hyp_len}")
+    if lx.dim() != 1 or lx.numel() != N:
+        raise RuntimeError(f"{who}: expect {N} input lengths, got shape {tuple(lx.shape)}")
+    if lx.is_cuda:
+        if lx.dtype != torch.int32:
+            raise RuntimeError(f"{who}: input_lengths on the GPU must be int32, got {lx.dtype}")
+    else:
+        if lx.dtype.is_floating_point or lx.dtype == torch.bool:
+            raise RuntimeError(f"{who}: input_lengths must be an int tensor, got {lx.dtype}")
+        if int(lx.min()) < 0 or int(lx.max()) > T:
+            raise RuntimeError(f"{who}: the chunk's frame lengths must lie in [0, Tc={T}], got min {int(lx.min())}, max {int(lx.max())}")
+    if reset is not None:
+        if reset.dim() != 1 or reset.numel() != N or reset.dtype.is_floating_point:
+            raise RuntimeError(f"{who}: reset must be a bool or int tensor of shape ({N},), got {reset.dtype} of shape {tuple(reset.shape)}")
+    _check_beam_lm_args(lm, alpha, beta, return_lm_scores, V)
+    W, K, C, cap = int(beam_size), int(nbest), int(top_classes), int(max_hyp_len)
+    if state is not None:
+        if not isinstance(state, BeamState):
+            raise RuntimeError(f"{who}: state must be a BeamState (what this call returns) or None, got {type(state).__name__}")
+        mine = dict(beam_size=W, top_classes=C, blank=int(blank), max_hyp_len=cap, alpha=float(alpha), beta=float(beta))
+        for k in BeamState.FIELDS:
+            if (getattr(state, k) is not lm) if k == "lm" else (getattr(state, k) != mine[k]):
+                raise RuntimeError(f"{who}: the state was made with {k}={getattr(state, k)!r}, this call has {k}={(lm if k == 'lm' else mine[k])!r}: "
+                                   f"a state continues only under the values it was made with")
+        if len(state) != N:
+            raise RuntimeError(f"{who}: the state holds {len(state)} utterances, the chunk {N}")
+    if not log_probs.is_cuda:                  # (after the checks of the arguments: those need no device)
+        raise RuntimeError(f"{who}: log_probs must be on the GPU (there is no CPU path)")
+    assert log_probs.is_contiguous()
+    dev = log_probs.device
+    if lx.is_cuda and lx.device != dev:
+        raise RuntimeError(f"{who}: input_lengths is on {lx.device}, log_probs on {dev}")
+    rec = _lib.crf_ctc_beam_state_record_bytes(W, cap)
+    if rec < 0:
+        _check(1)
+    if state is not None and (state.records.device != dev or tuple(state.records.shape) != (N, rec) or state.records.dtype != torch.uint8):
+        raise RuntimeError(f"{who}: the state's records are {tuple(state.records.shape)} {state.records.dtype} on {state.records.device}, "
+                           f"expect ({N}, {rec}) uint8 on {dev}")
+    lx_d = lx.contiguous() if lx.is_cuda else _h2d_async(lx.to(torch.int32).reshape(-1), dev)
+    reset_d = None
+    if reset is not None:
+        reset_d = (reset.to(dev) != 0).to(torch.int32) if reset.is_cuda else _h2d_async((reset != 0).to(torch.int32), dev)
+    rec_in = state.records.contiguous() if state is not None else None
+    H = N * K
+    ws_bytes = _lib.crf_ctc_beam_chunk_workspace_bytes(N, T, V, W, C)
+    ws = _new_ws(ws_bytes, dev)
+    rec_out = torch.empty((N, rec), dtype=torch.uint8, device=dev)
+    hyps = torch.empty((H, cap), dtype=torch.int32, device=dev)
+    hyp_len = torch.empty(H, dtype=torch.int32, device=dev)
+    scores = torch.empty(H, dtype=torch.float32, device=dev)
+    trace = torch.empty((N, T, W), dtype=torch.int32, device=dev) if return_trace else None
+    lm_scores = torch.empty(H, dtype=torch.float32, device=dev) if return_lm_scores else None
+    tables = None
+    if lm is not None:
+        tables, _keep = lm.tables(dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        rc = _lib.crf_ctc_beam_chunk(_ptr(log_probs), _FUSED_DTYPES[log_probs.dtype], 1 if time_major else 0, int(blank), 1 if fused else 0,
+                                     _ptr(lx_d), N, T, V, W, K, C, ctypes.byref(tables) if tables is not None else _vp(0), float(alpha),
+                                     float(beta), _ptr(rec_in), _ptr(reset_d), _ptr(rec_out), cap, _ptr(hyps), _ptr(hyp_len), _ptr(scores),
+                                     _ptr(lm_scores), _ptr(trace), _ptr(ws), ws_bytes, _vp(stream))
+    _check(rc)
+    del lx_d, reset_d
+    return BeamState(rec_out, W, C, int(blank), cap, lm, alpha, beta), hyps, hyp_len, scores, trace, lm_scores
 
 
 EDIT_MAX_REF_LEN = 2047      # longest reference crf_ctc_edit_distance takes (kMaxCtcLabelLen; include/ctc_crf_hip.h)

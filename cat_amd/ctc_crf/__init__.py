@@ -26,6 +26,11 @@ Same names, arguments and error behaviour as the reference:
                                        -> (hyps IntTensor[N*nbest, T], hyp_lengths IntTensor[N*nbest], hyp_utt IntTensor[N*nbest],
                                            scores FloatTensor[N*nbest])                  (prefix beam search: the N-best lists; with lm
                                                                                          shallow fusion of a token-level n-gram LM)
+  ctc_beam_search_chunk(log_probs, input_lengths, state=None, reset=None, beam_size=16, nbest=1, top_classes=40, blank=0,
+                        time_major=False, fuse_log_softmax=False, lm=None, alpha=0.0, beta=0.0, max_hyp_len=512, return_trace=False,
+                        return_lm_scores=False) -> (BeamState, hyps IntTensor[N*nbest, max_hyp_len], hyp_lengths, hyp_utt, scores)
+                                                                                         (streaming: the same search chunk by chunk, the beam
+                                                                                         carried in a BeamState; any split gives the same bits)
   NgramLM.from_arpa(path, vocab_size, unk_logp=None), NgramLM.from_ngrams(dict, vocab_size, unk_logp=None)
                                                                                          (the LM of ctc_beam_search: cat_amd/ngram_lm.py)
   ctc_edit_distance(hyps, hyp_lengths, labels, label_lengths, hyp_utt=None, return_ops=False) -> dist IntTensor[H]
@@ -50,6 +55,7 @@ from torch.autograd.function import once_differentiable
 from torch.nn import Module
 
 from . import _C as core
+from ._C import BeamState  # noqa: F401
 from ..ngram_lm import NgramLM  # noqa: F401
 
 __version__ = "0.1.0"
@@ -487,6 +493,52 @@ def ctc_beam_search(log_probs: torch.Tensor, input_lengths: torch.Tensor, beam_s
         hyp_utt = torch.arange(hyps.size(0), dtype=torch.int32, device=hyps.device).div_(int(nbest), rounding_mode="floor")
     res = (hyps, hyp_lengths, hyp_utt, scores) + ((trace,) if return_trace else ()) + ((out[4],) if return_lm_scores else ())
     return res
+
+
+def ctc_beam_search_chunk(log_probs: torch.Tensor, input_lengths: torch.Tensor, state: BeamState = None, reset: torch.Tensor = None,
+                          beam_size: int = 16, nbest: int = 1, top_classes: int = 40, blank: int = 0, time_major: bool = False,
+                          fuse_log_softmax: bool = False, lm: NgramLM = None, alpha: float = 0.0, beta: float = 0.0, max_hyp_len: int = 512,
+                          return_trace: bool = False, return_lm_scores: bool = False):
+    """Streaming CTC prefix beam search: ctc_beam_search on a CHUNK of frames, the beam carried from call to call in a BeamState -- for
+    encoders that run chunk by chunk (cat/ctc/decode.py --streaming: model.chunk_infer; the CUSIDE / chunked trainers
+    cat/ctc/train_unified.py, train_me2e_chunk.py), whose search today waits for the last chunk.  ANY split of an utterance's frames
+    into chunks gives the bits of the whole-utterance call: scores, lengths, labels, lm_scores, and the chunks' traces one after the
+    other are the whole call's trace.  The loop that replaces decode.py:197-222 for --streaming:
+
+        state = None
+        for chunk, chunk_lens in encoder_chunks:                  # chunk (N, Tc, V) on the GPU, chunk_lens (N,): frames of this chunk
+            state, hyps, hyp_lengths, hyp_utt, scores = ctc_crf.ctc_beam_search_chunk(chunk, chunk_lens, state, beam_size=16, lm=lm,
+                                                                                      alpha=alpha, beta=beta)
+            # hyps[n, :hyp_lengths[n]]: the partial hypothesis of utterance n after the frames so far, on the device
+
+    log_probs: (N, Tc, V) on the GPU, or (Tc, N, V) with time_major=True; the CHUNK's activations, dtypes and fuse_log_softmax as for
+        ctc_beam_search.
+    input_lengths: (N,), how many of the chunk's frames belong to each utterance: an int tensor on the CPU (checked against [0, Tc]) or
+        an int32 tensor on the GPU (used as is; values outside [0, Tc] are clamped).  With 0 an utterance's state passes through
+        unchanged and its outputs repeat what the state holds, so a finished utterance may stay in the batch.
+    state: None (every utterance starts from the empty prefix), or the BeamState of the previous call.  A BeamState is immutable: every
+        call allocates the state it returns and never writes to the one it continues from, so two continuations of one state are
+        independent (branch, rewind).  It remembers beam_size, top_classes, blank, max_hyp_len, lm, alpha and beta; continuing under
+        other values is a RuntimeError that names the field.  len(state), state.index_select(idx) and state.clone() recompose a batch:
+        an utterance's state is one row of state.records, an (N, record_bytes) uint8 tensor.
+    reset: None or (N,) bool / int, CPU or GPU: where set, the utterance starts from the empty prefix whatever the state holds -- a
+        server reuses a batch slot for the next utterance.
+    max_hyp_len: labels kept per prefix, 1 .. 8192.  A longer prefix keeps searching and scoring exactly as with a larger max_hyp_len;
+        only its labels beyond are not kept, and hyp_lengths > max_hyp_len is how the caller sees it (ctc_score and ctc_edit_distance
+        answer such rows with -inf / -1, their convention for rows over the bound).
+    beam_size, nbest, top_classes, blank, lm, alpha, beta: as for ctc_beam_search.
+
+    Returns (state, hyps, hyp_lengths, hyp_utt, scores), then trace with return_trace, then lm_scores with return_lm_scores, as
+    ctc_beam_search does AS IF every utterance ended after the frames seen so far; hyps is (N nbest, max_hyp_len), trace
+    (N, Tc, beam_size) holds the chunk's rows.  Tensors on log_probs' device, no host synchronisation, no autograd history.
+    Not covered: endpointing, an end-of-sentence term, emitting only the stable common prefix of the beam, beam_size or top_classes
+    above 64, a state that survives a change of beam_size or LM."""
+    with torch.no_grad():
+        state, hyps, hyp_lengths, scores, trace, lm_scores = core.ctc_beam_search_chunk(
+            log_probs.detach().contiguous(), input_lengths, state, reset, beam_size, nbest, top_classes, int(blank), bool(time_major),
+            bool(fuse_log_softmax), lm, alpha, beta, max_hyp_len, bool(return_trace), bool(return_lm_scores))
+        hyp_utt = torch.arange(hyps.size(0), dtype=torch.int32, device=hyps.device).div_(int(nbest), rounding_mode="floor")
+    return (state, hyps, hyp_lengths, hyp_utt, scores) + ((trace,) if return_trace else ()) + ((lm_scores,) if return_lm_scores else ())
 
 
 def ctc_edit_distance(hyps: torch.Tensor, hyp_lengths: torch.Tensor, labels: torch.Tensor, label_lengths: torch.Tensor,

@@ -519,6 +519,50 @@ int crf_ctc_beam_lm(const void *act_dev, int dtype, int time_major, int blank, i
                     int32_t *hyps_dev, int32_t *hyp_len_dev, float *score_dev, float *lm_score_dev, int32_t *trace_dev,
                     void *workspace_dev, int64_t workspace_bytes, void *stream);
 
+/* Streaming prefix beam search: crf_ctc_beam (lm == NULL) or crf_ctc_beam_lm (lm != NULL; alpha and beta are read only then) on a CHUNK
+ * of Tc frames, with the beam carried from call to call in a state the caller keeps -- for encoders that run chunk by chunk
+ * (cat/ctc/decode.py --streaming: model.chunk_infer, cat/ctc/train_unified.py, train_me2e_chunk.py).  Any split of an utterance's frames
+ * into chunks gives the bits of the whole-utterance call: the recursion, E_t, the merge rule, the total order of the selection, the fp64
+ * sums and the LM arithmetic are those calls', operation for operation.
+ *   State     B self-contained records of crf_ctc_beam_state_record_bytes(W, cap) bytes (a multiple of 16), utterance-major: utterances
+ *             may be permuted, selected or copied with plain byte copies.  A record holds, per slot k < W, what the searches keep in
+ *             registers, as arrays of W entries one after the other: pb[W], pnb[W], lm[W] (fp64), id[W], parent id[W] (uint64),
+ *             alive[W], last label[W], length[W], LM state[W] (int32) -- 56 W bytes -- then W label rows of cap int32 (row k: the first
+ *             min(length, cap) labels of slot k's prefix, then the blank's index), then zero bytes up to the next multiple of 16:
+ *             record_bytes = (56 W + 4 W cap + 15) & ~15.  The layout is the library's own and one for both searches: without an LM the
+ *             lm entries and LM states are 0.  A state continues only under the W, cap, top_classes, blank, LM, alpha and beta it was made
+ *             with (not checked here).  Both state pointers are 8-byte aligned.
+ *   act_dev   the CHUNK's activations, [B][Tc][V] or [Tc][B][V], dtype and normalize as for crf_ctc_beam.  lx_chunk_dev[b]: how many of
+ *             the chunk's frames belong to utterance b, clamped to [0, Tc]; with 0 the record passes through unchanged and the outputs
+ *             repeat what the state holds.
+ *   Fresh     Where state_in_dev == NULL or reset_dev != NULL and reset_dev[b] != 0, utterance b starts from the empty prefix exactly as
+ *             the whole-utterance calls do and its input record is never read: a first call needs no initialised state, and a batch slot
+ *             is reused for the next utterance by setting its reset word.
+ *   state_out_dev  every byte of every record is written.  It must not overlap state_in_dev (label rows move between slots); the input
+ *             state is never written, so a caller can branch from or rewind to an older state.
+ *   Outputs   the whole calls' outputs as if the utterance ended after the frames seen so far: hyp_len_dev [B nbest] is the TRUE length,
+ *             score_dev = pb (+) pnb (+ lm), lm_score_dev (may be NULL; written only with lm) as for crf_ctc_beam_lm.  hyps_dev
+ *             [B nbest][cap]: rank r's first min(length, cap) labels, then the blank's index up to cap.  A prefix longer than cap keeps
+ *             searching and scoring exactly as if cap were large, only its labels beyond cap are not kept: hyp_len > cap is how the
+ *             caller sees it (the convention crf_ctc_score_rows / crf_ctc_edit_distance have for rows over their bound).  trace_dev (may
+ *             be NULL) [B][Tc][W]: the chunk's trace rows, -1 for t >= lx_chunk.  Every output word is written.
+ * Whatever a record holds, no access leaves the call's buffers (results are unspecified for records no call of this library wrote).
+ * Workspace: crf_ctc_beam_chunk_workspace_bytes = crf_ctc_beam_workspace_bytes at T = Tc.  No host synchronisation, all work on `stream`,
+ * no environment variable read.  crf_last_beam_kernel() names the row kernel as for crf_ctc_beam.
+ * Errors: crf_ctc_beam's, with lm crf_ctc_beam_lm's, and CRF_ERR_ARG for a null state_out_dev, cap outside [1, 8192], overlapping or
+ * misaligned states -- all answered before any HIP call.  crf_ctc_beam_state_record_bytes: -1 with crf_last_error() set for W outside
+ * [1, 64] or cap outside [1, 8192].
+ * Not covered: endpointing, an end-of-sentence term, emitting only the stable common prefix of the beam, W or top_classes above 64, a
+ * state that survives a change of W or LM. */
+int64_t crf_ctc_beam_state_record_bytes(int64_t W, int64_t cap);
+int64_t crf_ctc_beam_chunk_workspace_bytes(int64_t B, int64_t Tc, int64_t V, int64_t W, int64_t top_classes);
+int crf_ctc_beam_chunk(const void *act_dev, int dtype, int time_major, int blank, int normalize, const int32_t *lx_chunk_dev,
+                       int64_t B, int64_t Tc, int64_t V, int64_t W, int64_t nbest, int64_t top_classes,
+                       const crf_ngram_tables *lm, float alpha, float beta,
+                       const void *state_in_dev, const int32_t *reset_dev, void *state_out_dev, int64_t cap,
+                       int32_t *hyps_dev, int32_t *hyp_len_dev, float *score_dev, float *lm_score_dev, int32_t *trace_dev,
+                       void *workspace_dev, int64_t workspace_bytes, void *stream);
+
 /* n-gram LM scores of H hypotheses that lie on the device as padded rows: log P_lm of the second pass, what cat/lm/rescore.py:168-177
  * (final = score + alpha * log P_lm + beta * len per N-best entry) takes from cat/shared/decoder.py:542-572 (NGram.score: `.cpu()`, a
  * list of strings and one kenlm.Model.score call per sentence) and cat/utils/lm/lmweight_search.py repeats per (alpha, beta) -- for the
