@@ -41,7 +41,7 @@ def _compile(unit: str, defs, verbose: bool, force: bool) -> str:
     stamp = obj + ".defs"
     want = " ".join(defs)
     fresh = (not force and os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == want and
-             all(os.path.getmtime(obj) >= os.path.getmtime(d) for d in [src] + HEADERS))
+             all(os.path.getmtime(obj) >= os.path.getmtime(d) for d in ([src] + DEPS if unit == "crf_unity.hip" else [src] + HEADERS)))   # (the unity source includes the others)
     if fresh:
         return obj
     cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-pass-failed", *defs, "-c", src, "-o", obj]

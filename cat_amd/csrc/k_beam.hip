@@ -12,25 +12,14 @@
 // where nothing above -inf is left (or only NaN) the pair is (class -1, -inf): an extension at -inf is no candidate, so it changes nothing.
 // Workspace: val[n T + t][0] = x^[blank] - lse, val[..][1 + j] = x^[c_j] - lse, cls[..][1 + j] = c_j (cls[..][0] = blank), C + 1 words a row.
 //
-// Beam stage (crf_beam_search_kernel): ONE wave per utterance, slot k of the beam in lane k, all state in registers: pb, pnb (fp64, sums
-// as the score gradient takes them: fp64 maximum and result, fp32 exp / log of the difference), the prefix' 64-bit id, its parent's id,
-// its last label and its length.  Lane j holds pair j of the frame (C <= 64); the next frame's C + 1 words are fetched while this frame is
-// worked on (unconditional loads, frame and lane clamped).  Per frame:
-//   1. each slot looks its last label e up among the C classes (C uniform compares): position and x[e], or none -- the stay's repeat;
-//   2. merges: for each live slot k with a parent (a uniform loop over the W slots), the slot whose id is k's parent id gives the mass of
-//      its extension by e_k to k's stay and strikes that extension from its own list: W x W id compares a frame, and a prefix that left
-//      the beam and came back still finds its child, because the child keeps the parent's ID, not its slot;
-//   3. every slot has three candidates: its stay, its extension by e itself (base pb), and the HEAD of its other extensions -- base +
-//      x[c] over the frame's sorted list is sorted too, so the list is a 64-bit mask of struck positions and its lowest zero.  W rounds:
-//      the lanes' best meet in a wave maximum of the fp64 score (DPP on an order-preserving integer image: no LDS round trip), ties go
-//      to a stay, then to the lowest slot; the winner becomes slot r of the new beam -- slot r notes the winner's lane, kind, class and
-//      score, and takes its fields from that lane in ONE gather behind the rounds -- and moves on to its next candidate (a new head's
-//      class and value come by readlane, the place being uniform).  A maximum of -inf ends the frame: the beam may hold fewer than W.
-//   4. the trace word of every slot is stored (parent slot + 64 (class + 1), -1 for an empty slot).
+// Beam stage (crf_beam_search_kernel): ONE wave per utterance, slot k of the beam in lane k, all state in registers (a BeamSlot).  Lane j
+// holds pair j of the frame (C <= 64); the next frame's C + 1 words are fetched while this frame is worked on (unconditional loads, frame
+// and lane clamped).  Per frame: beam_frame_step, steps 1 to 4 as k_beam_body.h describes them (the streaming search of
+// k_beam_chunk.hip calls the same function).
 // Back-trace, same launch behind a barrier: the trace rows come back through LDS 64 frames at a time, lane r < nbest follows rank r from
 // frame lx - 1 down and stores a label wherever a class was appended (its length is known: the labels land at their final places), then
 // the tails take the blank, and with a caller's trace buffer the rows t >= lx take -1.  Every output word is written by one plain store.
-#include "k_beam_common.h"   // the wave helpers, shared with k_beam_lm.hip
+#include "k_beam_body.h"   // the frame step, shared with k_beam_chunk.hip; the wave helpers (k_beam_common.h) come with it
 
 namespace crf {
 
@@ -109,17 +98,13 @@ __global__ __launch_bounds__(64) void crf_beam_search_kernel(BeamParams p) {
     const int lane = threadIdx.x, b = blockIdx.x;
     const int T = p.T, W = p.W, C = p.C, RS = C + 1;
     const int lx = max(0, min(p.lx[b], T));
-    const double kNegInf = -__builtin_huge_val();
     const float *val = p.val + (int64_t)b * T * RS;
     const int *cls = p.cls + (int64_t)b * T * RS;
     int *tr = p.trace + (int64_t)b * T * W;
     const int jl = C > 0 ? 1 + min(lane, C - 1) : 0;   // this lane's word of a row (lanes >= C: clamped, not used)
 
-    // the beam: the empty prefix in slot 0
-    int alive = lane == 0;
-    double pb = lane == 0 ? 0.0 : kNegInf, pnb = kNegInf;
-    beam_u64 id = 0x243F6A8885A308D3ull, pid = 0;
-    int e = -2, len = 0;                        // (no last label: -2 matches neither a class nor a filler pair)
+    BeamSlot s;                                 // the beam: the empty prefix in slot 0
+    beam_slot_fresh(s, lane);
 
     float nv = 0.f, nxb = 0.f;
     int nc = -1;
@@ -131,103 +116,15 @@ __global__ __launch_bounds__(64) void crf_beam_search_kernel(BeamParams p) {
             const int64_t o = (int64_t)min(t + 1, lx - 1) * RS;
             nv = val[o + jl]; nc = cls[o + jl]; nxb = val[o];
         }
-        // 1. the last label among the frame's classes
-        int pos = -1;
-        float ve = -INFINITY;
-        for (int j = 0; j < C; ++j) {
-            const int c = beam_bcast(cj, j);
-            const float v = beam_bcast(vj, j);
-            if (c == e) { pos = j; ve = v; }
-        }
-        const double tot = beam_lse2(pb, pnb);
-        const double spb = alive ? (double)xb + tot : kNegInf;
-        double spnb = (alive && pos >= 0) ? (double)ve + pnb : kNegInf;
-        beam_u64 mask = C >= 64 ? 0ull : ~0ull << C;           // struck positions of the extension list
-        if (pos >= 0) mask |= 1ull << pos;
-        bool rep_ok = alive && pos >= 0;                        // the extension by e itself: base pb
-        // 2. merges into the slots whose parent is in the beam
-        double madd = kNegInf;
-        for (int k = 0; k < W; ++k) {
-            const int kpos = beam_bcast(pos, k);
-            if (!beam_bcast(alive, k) || beam_bcast(len, k) == 0 || kpos < 0) continue;    // (uniform)
-            const beam_u64 kp = beam_bcast(pid, k);
-            const int ke = beam_bcast(e, k);
-            const float kv = beam_bcast(ve, k);
-            const bool match = alive && id == kp;
-            const beam_u64 bal = __ballot(match);
-            if (!bal) continue;
-            double contrib = kNegInf;
-            if (match) {
-                if (ke == e) { contrib = (double)kv + pb; rep_ok = false; }
-                else { contrib = (double)kv + tot; mask |= 1ull << kpos; }
-            }
-            const double cb = beam_bcast(contrib, __ffsll((long long)bal) - 1);
-            if (lane == k) madd = cb;
-        }
-        spnb = beam_lse2(spnb, madd);
-        const double s_stay = alive ? beam_lse2(spb, spnb) : kNegInf;
-        const double s_rep = rep_ok ? (double)ve + pb : kNegInf;
-        bool stay_ok = alive != 0;
-        int h = ~mask ? __ffsll((long long)~mask) - 1 : 64;
-        // 3. W rounds of the best candidate; slot r keeps where it came from, the fields follow in one gather behind the rounds
-        int hc = __shfl(cj, h & 63);                            // the head of the list: its class and value
-        float hv = __shfl(vj, h & 63);
-        int src = -1, n_kind = 0, n_c = -1;
-        double n_s = kNegInf;
-        for (int r = 0; r < W; ++r) {
-            const double s_list = (alive && h < 64) ? (double)hv + tot : kNegInf;
-            const double rr = rep_ok ? s_rep : kNegInf;
-            const bool rep_first = rr > s_list || (rr == s_list && e < hc);
-            const double sx = rep_first ? rr : s_list;
-            double s = stay_ok ? s_stay : kNegInf;
-            int kind = 0;                                       // 0 stay, 1 extension by e, 2 head of the list
-            if (sx > s) { s = sx; kind = rep_first ? 1 : 2; }
-            const double mx = beam_wave_max(s);
-            if (!(mx > kNegInf)) break;                         // (uniform; NaN ends the frame too)
-            const bool top = s == mx;
-            const beam_u64 bs = __ballot(top && kind == 0);
-            const beam_u64 bal = bs ? bs : __ballot(top);
-            if (!bal) break;
-            const int m = __ffsll((long long)bal) - 1;
-            const int c = kind == 0 ? -1 : kind == 1 ? e : hc;
-            const int b_kind = beam_bcast(kind, m), b_c = beam_bcast(c, m);
-            if (lane == r) { src = m; n_kind = b_kind; n_c = b_c; n_s = mx; }
-            // the winner moves on to its next candidate (b_kind and the new head's place are uniform: readlanes, no LDS round trip)
-            if (b_kind == 2) {
-                const beam_u64 nmask = mask | (1ull << (h & 63));
-                const int nh = ~nmask ? __ffsll((long long)~nmask) - 1 : 64;
-                const int hm = beam_bcast(nh, m);
-                const int c2 = beam_bcast(cj, hm & 63);
-                const float v2 = beam_bcast(vj, hm & 63);
-                if (lane == m) { mask = nmask; h = nh; hc = c2; hv = v2; }
-            } else if (lane == m) {
-                if (kind == 0) stay_ok = false; else rep_ok = false;
-            }
-        }
-        // 4. the trace row, the new beam: slot r's fields from its parent's lane
-        if (lane < W) tr[(int64_t)t * W + lane] = src >= 0 ? src + 64 * (n_c + 1) : -1;
-        {
-            const int sl = src >= 0 ? src : lane;
-            const double g_spb = __shfl(spb, sl), g_spnb = __shfl(spnb, sl);
-            const beam_u64 g_id = __shfl(id, sl), g_pid = __shfl(pid, sl);
-            const int g_e = __shfl(e, sl), g_len = __shfl(len, sl);
-            const bool st = n_kind == 0;
-            alive = src >= 0;
-            pb = alive && st ? g_spb : kNegInf;
-            pnb = !alive ? kNegInf : st ? g_spnb : n_s;         // (an extension's pnb' is its score)
-            id = !alive ? 0ull : st ? g_id : beam_mix(g_id, n_c);
-            pid = !alive ? 0ull : st ? g_pid : g_id;
-            e = !alive ? -2 : st ? g_e : n_c;
-            len = !alive ? 0 : g_len + (st ? 0 : 1);
-        }
+        beam_frame_step(s, vj, cj, xb, lane, W, C, tr + (int64_t)t * W);
     }
 
     // results of the ranks, back-trace
     const bool out = lane < p.nbest;
-    const int olen = alive ? len : 0;
+    const int olen = s.alive ? s.len : 0;
     const int64_t h0 = (int64_t)b * p.nbest;
     if (out) {
-        p.score[h0 + lane] = alive ? (float)beam_lse2(pb, pnb) : -INFINITY;
+        p.score[h0 + lane] = s.alive ? (float)beam_lse2(s.pb, s.pnb) : -INFINITY;
         p.hyp_len[h0 + lane] = olen;
     }
     int *hyp = p.hyps + (h0 + (out ? lane : 0)) * T;
@@ -237,7 +134,7 @@ __global__ __launch_bounds__(64) void crf_beam_search_kernel(BeamParams p) {
         __syncthreads();                        // (the trace rows are this wave's own stores; the chunk before has been read)
         for (int i = lane; i < nw; i += 64) tr_lds[i] = tr[(int64_t)t0 * W + i];
         __syncthreads();
-        if (out && alive) {
+        if (out && s.alive) {
             for (int t = t1 - 1; t >= t0; --t) {
                 const int wd = tr_lds[(t - t0) * W + slot];
                 const int c = (wd >> 6) - 1;

@@ -1,8 +1,8 @@
 // cat_amd/csrc/k_beam_chunk.hip -- streaming CTC prefix beam search: the searches of k_beam.hip and k_beam_lm.hip on a CHUNK of frames, with the
 // beam loaded from a record at the start and stored to another at the end (include/ctc_crf_hip.h crf_ctc_beam_chunk; host side:
 // crf_host_ctc.hip).  The row stage is k_beam.hip's crf_beam_row_kernel<E> on the chunk's rows, unchanged.  The frame steps are the
-// device functions of k_beam_body.h / k_beam_lm_body.h: the operations of crf_beam_search_kernel / crf_beamlm_search_kernel in their
-// order (a copy of their text: see k_beam_body.h), so any split of an utterance's frames into chunks gives the bits of the whole call.
+// device functions of k_beam_body.h / k_beam_lm_body.h, the ones crf_beam_search_kernel / crf_beamlm_search_kernel call (the steps are
+// described there), so any split of an utterance's frames into chunks gives the bits of the whole call.
 //
 // crf_beam_chunk_kernel (one wave per utterance) and crf_beamlm_chunk_kernel (kBeamLmWaves waves, wave 0 searches):
 //   Load.    Slot k's fields of the input record (crf_kernels_decl.h: beam_state_bytes) into lane k; a fresh utterance (no input state, or

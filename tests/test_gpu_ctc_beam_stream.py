@@ -1,7 +1,8 @@
 """GPU tests of the streaming beam search, ctc_beam_search_chunk (include/ctc_crf_hip.h crf_ctc_beam_chunk), without an LM.  The yardstick
 is the whole-utterance call ctc_beam_search -- itself held to tests/beam_ref.py and brute force by tests/test_gpu_ctc_beam.py -- and every
 comparison is BIT FOR BIT: hyps[:len], hyp_lengths, scores, and the chunks' traces one after the other against the whole call's trace.
-No tolerance: any split of the frames into chunks runs the same operations on the same operands."""
+No tolerance: any split of the frames into chunks runs the same operations on the same operands -- the whole and the chunk kernels call
+one frame step (cat_amd/csrc/k_beam_body.h); what differs, and what these tests hold, is the load, the store and the back-trace around it."""
 import numpy as np
 import pytest
 import torch

@@ -1,6 +1,7 @@
 """GPU tests of the streaming beam search with an n-gram LM (ctc_beam_search_chunk(lm=...), include/ctc_crf_hip.h crf_ctc_beam_chunk with
 tables).  The yardstick is the whole-utterance call ctc_beam_search(lm=...), held to tests/beam_lm_ref.py by tests/test_gpu_ctc_beam_lm.py;
-every comparison is bit for bit: hyps[:len], hyp_lengths, fused scores, lm_scores and the chunks' traces one after the other."""
+every comparison is bit for bit: hyps[:len], hyp_lengths, fused scores, lm_scores and the chunks' traces one after the other.  Both calls
+run the one frame step of cat_amd/csrc/k_beam_lm_body.h; the state's load and store, st_lds / na_lds rebuilt from it and the back-trace differ."""
 import numpy as np
 import pytest
 import torch
