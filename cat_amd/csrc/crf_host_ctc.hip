@@ -3,7 +3,8 @@
 // weighted gradient (crf_ctc_score_grad*, k_score_grad.hip), both on hypotheses that lie on the device as padded rows (crf_ctc_score_rows,
 // crf_ctc_score_grad_rows, k_rows.hip), sampled / best-path label sequences (crf_ctc_sample, k_sample.hip), the
 // prefix beam search (crf_ctc_beam, k_beam.hip; with an n-gram LM: crf_ctc_beam_lm, k_beam_lm.hip, crf_ngram_tables_check) and -- on token sequences alone, no lattice -- the edit distance of hypotheses to
-// their transcripts (crf_ctc_edit_distance, k_edit.hip) and their n-gram LM scores (crf_ngram_score, k_ngram.hip) --
+// their transcripts (crf_ctc_edit_distance, k_edit.hip) and their n-gram LM scores (crf_ngram_score, k_ngram.hip) -- and the RNN-T
+// transducer loss on the joiner's lattice (crf_rnnt_loss, crf_rnnt_grad, k_rnnt.hip) --
 // argument checks, workspace sections, kernel choice, the C-ABI entry points of include/ctc_crf_hip.h.  Every error is answered before
 // any HIP call.  The activations are read in place in either layout and -- the *_logits entry points and crf_ctc_sample -- in f32, bf16
 // or f16.
@@ -571,6 +572,83 @@ static int launch_ngram_score(const NgramScoreParams &p, hipStream_t st) {
     return launch<crf_ngram_score_kernel<false>>(g_ngram_kernel = "crf_ngram_score_kernel<scores>", grid, block, 0, st, p);
 }
 
+// ---- the RNN-T loss and its gradient (k_rnnt.hip) ----
+// The workspace both calls share, R = the rows of the joiner output (N T U1 padded, compact_rows compact): row [R][3] floats (lse, lb, ll),
+// alpha [R] and beta [R] fp64, utt: total [N] fp64, then node_off [N + 1], lab_off [N], tn [N], un [N] int32.  < 0 with the message set.
+enum RnntWs { kRtRow, kRtAlpha, kRtBeta, kRtUtt, kRtCount };
+static const char *const kRnntWsNames[kRtCount] = {"row", "alpha", "beta", "utt"};
+static int64_t rnnt_ws_bytes(int64_t N, int64_t T, int64_t U1, int64_t V, int64_t compact_rows, SideWs *out = nullptr, int64_t *rows = nullptr) {
+    const std::string who = "crf_rnnt_loss: ";
+    if (N <= 0 || T <= 0 || U1 <= 0 || V <= 0 || N > INT32_MAX || T > INT32_MAX) { set_error(who + "bad N/T/U+1/V"); return -CRF_ERR_ARG; }
+    if (U1 > kRnntMaxU1) { set_error(who + "U > " + std::to_string(kRnntMaxU1 - 1) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
+    if (V > kRnntMaxV) { set_error(who + "V > " + std::to_string(kRnntMaxV) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
+    // (an utterance's nodes are indexed in 32 bits, times three for the row section: T U1 padded, at most all rows compact)
+    if (compact_rows < 0 && T > (INT32_MAX / 4) / U1) { set_error(who + "T * (U + 1) > INT32_MAX / 4"); return -CRF_ERR_ARG; }
+    if (compact_rows > INT32_MAX / 4) { set_error(who + "compact_rows > INT32_MAX / 4"); return -CRF_ERR_ARG; }
+    const int64_t R = compact_rows < 0 ? N * T * U1 : compact_rows;
+    if (R <= 0 || R > INT32_MAX || (compact_rows < 0 && N > INT32_MAX / (T * U1))) { set_error(who + "rows outside [1, INT32_MAX]"); return -CRF_ERR_ARG; }
+    SideWs w;
+    w.add(kRnntWsNames[kRtRow], 3 * R * (int64_t)sizeof(float)).add(kRnntWsNames[kRtAlpha], R * (int64_t)sizeof(double))
+     .add(kRnntWsNames[kRtBeta], R * (int64_t)sizeof(double)).add(kRnntWsNames[kRtUtt], N * (int64_t)sizeof(double) + (4 * N + 1) * (int64_t)sizeof(int32_t));
+    if (out) *out = w;
+    if (rows) *rows = R;
+    return w.total;
+}
+// the checks both calls share, in the order of include/ctc_crf_hip.h, and the kernels' arguments; no HIP call.  dtype < 0: normalised fp32
+static int rnnt_setup(const char *who_, const void *x, int dtype, int blank, const int32_t *labels, const int32_t *lx, const int32_t *ly, int64_t N,
+                      int64_t T, int64_t U1, int64_t V, int64_t compact_rows, int64_t compact_labels, const void *out, const void *ws,
+                      int64_t ws_bytes, RnntParams &p) {
+    const std::string who = who_;
+    if (!x || !labels || !lx || !ly || !out || !ws) { set_error(who + ": null argument"); return CRF_ERR_ARG; }
+    if (dtype > 2) return bad_dtype(who_);
+    SideWs w;
+    int64_t R = 0;
+    const int64_t need = rnnt_ws_bytes(N, T, U1, V, compact_rows, &w, &R);
+    if (need < 0) return (int)-need;
+    if (const int rc = check_blank(blank, V)) return rc;
+    if (compact_rows >= 0 && (compact_labels < 0 || compact_labels > INT32_MAX)) { set_error(who + ": bad compact_labels"); return CRF_ERR_ARG; }
+    if ((uintptr_t)ws & 15) { set_error(who + ": the workspace must be 16-byte aligned"); return CRF_ERR_ARG; }
+    if (const int rc = check_ws(ws_bytes, need)) return rc;
+    p = RnntParams{};
+    p.x = x; p.labels = labels; p.lx = lx; p.ly = ly;
+    p.N = (int)N; p.T = (int)T; p.U1 = (int)U1; p.V = (int)V; p.blank = blank; p.compact = compact_rows >= 0;
+    p.R = R; p.nlab = compact_rows >= 0 ? compact_labels : N * (U1 - 1);
+    char *b = (char *)ws;
+    p.row = (float *)(b + w.sec[kRtRow].off); p.alpha = (double *)(b + w.sec[kRtAlpha].off); p.beta = (double *)(b + w.sec[kRtBeta].off);
+    p.total = (double *)(b + w.sec[kRtUtt].off);
+    p.node_off = (int *)(p.total + N); p.lab_off = p.node_off + N + 1; p.tn = p.lab_off + N; p.un = p.tn + N;
+    return CRF_OK;
+}
+// the forward: offsets and validity, the row stage, both recursions -- three launches on one stream
+static int rnnt_loss_call(const char *who, const void *x, int dtype, int blank, const int32_t *labels, const int32_t *lx, const int32_t *ly, int64_t N,
+                          int64_t T, int64_t U1, int64_t V, int64_t compact_rows, int64_t compact_labels, float *cost, int32_t *invalid, void *ws,
+                          int64_t ws_bytes, hipStream_t st) {
+    RnntParams p;
+    if (const int rc = rnnt_setup(who, x, dtype, blank, labels, lx, ly, N, T, U1, V, compact_rows, compact_labels, cost, ws, ws_bytes, p)) return rc;
+    p.cost = cost; p.invalid = invalid;
+    if (const int rc = launch<crf_rnnt_prep_kernel>("crf_rnnt_prep_kernel", dim3(1), dim3(kRnntPrepThreads), 0, st, p)) return rc;
+    const dim3 wgrid((unsigned)((p.R + kRnntWaves - 1) / kRnntWaves)), wblock(64 * kRnntWaves);
+    int rc;
+    if (dtype < 0) rc = launch<crf_rnnt_gather_kernel>("crf_rnnt_gather_kernel", dim3((unsigned)((p.R + 255) / 256)), dim3(256), 0, st, p);
+    else rc = with_dtype(dtype, [&](auto e) { return launch<crf_rnnt_row_kernel<decltype(e)>>("crf_rnnt_row_kernel", wgrid, wblock, 0, st, p); });
+    if (rc) return rc;
+    const dim3 lgrid((unsigned)N, 2);
+    if (U1 <= 64) return launch<crf_rnnt_lattice_kernel<false>>("crf_rnnt_lattice_kernel<wave>", lgrid, dim3(64), 0, st, p);
+    return launch<crf_rnnt_lattice_kernel<true>>("crf_rnnt_lattice_kernel<workgroup>", lgrid, dim3((unsigned)rup64((int)U1)), 0, st, p);
+}
+// the backward on the forward's workspace: one launch
+static int rnnt_grad_call(const char *who, const void *x, int dtype, int blank, const int32_t *labels, const int32_t *lx, const int32_t *ly, int64_t N,
+                          int64_t T, int64_t U1, int64_t V, int64_t compact_rows, int64_t compact_labels, const float *weight, void *grad, void *ws,
+                          int64_t ws_bytes, hipStream_t st) {
+    RnntParams p;
+    if (!weight) { set_error(std::string(who) + ": null argument"); return CRF_ERR_ARG; }
+    if (const int rc = rnnt_setup(who, x, dtype, blank, labels, lx, ly, N, T, U1, V, compact_rows, compact_labels, grad, ws, ws_bytes, p)) return rc;
+    p.weight = weight; p.grad = grad;
+    const dim3 wgrid((unsigned)((p.R + kRnntWaves - 1) / kRnntWaves)), wblock(64 * kRnntWaves);
+    if (dtype < 0) return launch<crf_rnnt_grad_kernel<float, false>>("crf_rnnt_grad_kernel", wgrid, wblock, 0, st, p);
+    return with_dtype(dtype, [&](auto e) { return launch<crf_rnnt_grad_kernel<decltype(e), true>>("crf_rnnt_grad_kernel", wgrid, wblock, 0, st, p); });
+}
+
 }  // namespace crf
 
 using namespace crf;
@@ -844,6 +922,45 @@ int crf_ngram_score(const crf_ngram_tables *lm, const float *eos_logp, const int
     p.use_start = use_start != 0; p.add_eos = add_eos != 0;
     p.score = score; p.invalid = invalid; p.tok_logp = token_logp; p.tok_order = token_order;
     return launch_ngram_score(p, (hipStream_t)stream_);
+}
+
+int64_t crf_rnnt_workspace_bytes(int64_t N, int64_t T, int64_t U1, int64_t V, int64_t compact_rows) {
+    return or_minus1(rnnt_ws_bytes(N, T, U1, V, compact_rows));
+}
+int crf_debug_rnnt_ws_sections(int64_t N, int64_t T, int64_t U1, int64_t V, int64_t compact_rows, int64_t *out, int n_out) {
+    SideWs w;
+    if (rnnt_ws_bytes(N, T, U1, V, compact_rows, &w) < 0) return -1;
+    return copy_sections(w.sec, w.nsec, out, n_out);
+}
+const char *crf_debug_rnnt_ws_section_names(void) {
+    static const std::string s = join_names(kRnntWsNames, kRtCount);
+    return s.c_str();
+}
+
+int crf_rnnt_loss(const float *log_probs, int blank, const int32_t *labels, const int32_t *lx, const int32_t *ly, int64_t N, int64_t T, int64_t U1,
+                  int64_t V, int64_t compact_rows, int64_t compact_labels, float *cost, int32_t *invalid, void *ws, int64_t ws_bytes, void *stream_) {
+    return rnnt_loss_call("crf_rnnt_loss", log_probs, -1, blank, labels, lx, ly, N, T, U1, V, compact_rows, compact_labels, cost, invalid, ws, ws_bytes,
+                          (hipStream_t)stream_);
+}
+int crf_rnnt_loss_logits(const void *logits, int dtype, int blank, const int32_t *labels, const int32_t *lx, const int32_t *ly, int64_t N, int64_t T,
+                         int64_t U1, int64_t V, int64_t compact_rows, int64_t compact_labels, float *cost, int32_t *invalid, void *ws, int64_t ws_bytes,
+                         void *stream_) {
+    if (dtype < 0) return bad_dtype("crf_rnnt_loss_logits");
+    return rnnt_loss_call("crf_rnnt_loss_logits", logits, dtype, blank, labels, lx, ly, N, T, U1, V, compact_rows, compact_labels, cost, invalid, ws,
+                          ws_bytes, (hipStream_t)stream_);
+}
+int crf_rnnt_grad(const float *log_probs, int blank, const int32_t *labels, const int32_t *lx, const int32_t *ly, int64_t N, int64_t T, int64_t U1,
+                  int64_t V, int64_t compact_rows, int64_t compact_labels, const float *grad_output, float *grad, void *ws, int64_t ws_bytes,
+                  void *stream_) {
+    return rnnt_grad_call("crf_rnnt_grad", log_probs, -1, blank, labels, lx, ly, N, T, U1, V, compact_rows, compact_labels, grad_output, grad, ws,
+                          ws_bytes, (hipStream_t)stream_);
+}
+int crf_rnnt_grad_logits(const void *logits, int dtype, int blank, const int32_t *labels, const int32_t *lx, const int32_t *ly, int64_t N, int64_t T,
+                         int64_t U1, int64_t V, int64_t compact_rows, int64_t compact_labels, const float *grad_output, void *grad, void *ws,
+                         int64_t ws_bytes, void *stream_) {
+    if (dtype < 0) return bad_dtype("crf_rnnt_grad_logits");
+    return rnnt_grad_call("crf_rnnt_grad_logits", logits, dtype, blank, labels, lx, ly, N, T, U1, V, compact_rows, compact_labels, grad_output, grad, ws,
+                          ws_bytes, (hipStream_t)stream_);
 }
 
 const char *crf_last_ngram_score_kernel(void) { return g_ngram_kernel; }

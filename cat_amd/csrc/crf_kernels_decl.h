@@ -228,8 +228,38 @@ struct NgramScoreParams {
 // TOK: the per-position outputs are written (at least one of them is asked for).  One wave per hypothesis, no LDS.
 template <bool TOK> __global__ void crf_ngram_score_kernel(NgramScoreParams p);
 
+// ---- k_rnnt.hip ----
+constexpr int kRnntMaxU1 = 1024;          // lattice columns U + 1 at most: one thread per column, one workgroup per (utterance, direction)
+constexpr int kRnntMaxV = 8192;
+constexpr int kRnntWaves = 4;             // lattice nodes (waves) per workgroup of the row and gradient stages
+constexpr int kRnntPF = 4;                // diagonals per staging batch of the lattice stage (two register sets in flight)
+constexpr int kRnntPrepThreads = 256;
+// Kernel arguments of crf_rnnt_loss / crf_rnnt_grad.  Row r of x (V elements) is lattice node (n, t, u): r = (n T + t) U1 + u in the padded
+// layout, node_off[n] + t (U_n + 1) + u in the compact one; the workspace's per-node arrays are indexed by the same r.
+struct RnntParams {
+    const void *x;
+    const int *labels, *lx, *ly;
+    int N, T, U1, V, blank, compact;
+    int64_t R;                  // rows of x: N T U1, or the compact rows
+    int64_t nlab;               // entries of labels: N (U1 - 1), or the compact total
+    float *row;                 // [R][3] lse, lb = x[blank] - lse, ll = x[y_u] - lse (-inf at u = U_n) of the live nodes
+    double *alpha, *beta;       // [R] of the live nodes
+    double *total;              // [N] log p(y | x), -inf for an invalid utterance or one without a finite path
+    int *node_off;              // [N + 1] first row of utterance n
+    int *lab_off, *tn, *un;     // [N] first label; T_n and U_n of a valid utterance, tn = 0 for an invalid one
+    float *cost;                // [N]
+    int *invalid;               // [N] or null
+    const float *weight;        // [N] d loss / d cost[n] (crf_rnnt_grad)
+    void *grad;                 // [R][V] in x's element type (crf_rnnt_grad)
+};
+__global__ void crf_rnnt_prep_kernel(RnntParams p);                                // one workgroup: offsets, validity
+__global__ void crf_rnnt_gather_kernel(RnntParams p);                              // normalised input: a thread per node
+template <typename E> __global__ void crf_rnnt_row_kernel(RnntParams p);           // raw input: a wave per node
+template <bool WG> __global__ void crf_rnnt_lattice_kernel(RnntParams p);          // grid (N, 2); WG: U1 > 64, rup64(U1) threads
+template <typename E, bool RAW> __global__ void crf_rnnt_grad_kernel(RnntParams p); // a wave per row of grad
+
 // ---- k_edit.hip ----
-constexpr int kEditWaves = 4;             // hypotheses (waves) per workgroup of the register geometry
+constexpr int kEditWaves = 4;            // hypotheses (waves) per workgroup of the register geometry
 constexpr int kEditStripRows = 512;       // reference rows one wave holds (64 lanes x 8): longer references are walked in strips of this many
 constexpr int kEditStripMaxCols = 8192;   // the strip path keeps one (cost, counts) pair per hypothesis column in LDS: 64 KiB at most
 // Kernel arguments of crf_ctc_edit_distance: hypothesis h is the first hyp_len[h] entries of row h of hyps (rows `stride` entries apart),

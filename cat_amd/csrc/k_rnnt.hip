@@ -1,0 +1,371 @@
+// cat_amd/csrc/k_rnnt.hip -- the RNN-T transducer loss and its gradient (include/ctc_crf_hip.h crf_rnnt_loss / crf_rnnt_grad; host side:
+// crf_host_ctc.hip): cost[n] = -log p(y_n | x_n), summed over all monotone alignments of the lattice T_n x (U_n + 1) -- blank moves
+// t -> t + 1, label y[u] moves u -> u + 1, the path ends with a blank at (T_n - 1, U_n).
+//
+//   alpha[0][0] = 0,        alpha[t][u] = lse(alpha[t-1][u] + lb[t-1][u], alpha[t][u-1] + ll[t][u-1])
+//   beta[T-1][U] = lb[T-1][U],  beta[t][u] = lse(beta[t+1][u] + lb[t][u], beta[t][u+1] + ll[t][u])
+//   total = alpha[T-1][U] + lb[T-1][U],   cost = -total
+//   d cost / d lb[t][u] = -exp(alpha[t][u] + lb[t][u] + beta[t+1][u] - total)    (beta[T][U] = 0, beta[T][u < U] = -inf)
+//   d cost / d ll[t][u] = -exp(alpha[t][u] + ll[t][u] + beta[t][u+1] - total)    (u < U)
+//
+// The joiner output x is [R][V]: row r is node (n, t, u), padded ((n T + t) U1 + u) or compact (the utterances back to back, each
+// T_n x (U_n + 1) row-major); it is read in place in its own dtype and never copied.  Everything per node lives in the workspace under
+// the same index r.
+//   0. crf_rnnt_prep_kernel, one workgroup: the prefix sums that give every utterance its first row and first label, and its validity
+//      (T_n in [1, T], U_n in [0, U1 - 1], the rows and labels it claims inside the tensors, every label in [0, V) and not the blank).
+//      tn[n] = 0 marks an invalid utterance; nothing of it is read afterwards.  In the compact layout an utterance whose lengths are out
+//      of range claims no rows.
+//   1. row stage.  crf_rnnt_row_kernel<E> (raw joiner output): one wave per live node reads its V-row ONCE -- an online log-sum-exp, 16-byte
+//      loads where the row starts on a 16-byte boundary, element loads otherwise (odd V, rows that start on a 2-byte boundary), the same
+//      elements in the same lanes either way -- and writes lse, lb = x[blank] - lse, ll = x[y_u] - lse.  A row of -inf gives
+//      lb = ll = -inf, not NaN.
+//      crf_rnnt_gather_kernel (normalised input): the same three floats, lse = 0, a thread per node.
+//   2. crf_rnnt_lattice_kernel<WG>: one workgroup per (utterance, direction), thread j = column (alpha: u = j; beta: u = U_n - j, time
+//      reversed, which makes it the same recursion), T_n + U_n dependent steps along the anti-diagonals.  The running value stays in a
+//      register; the neighbour's previous value comes by a DPP shift inside a wave and, across waves (WG), through two LDS rows with ONE
+//      barrier per step; U1 <= 64 is the single-wave instantiation without LDS or barrier.  The two emissions of the next kRnntPF
+//      diagonals are loaded a batch ahead from clamped addresses (no branch around a load), so the chain does not wait on memory.
+//      The running values are FP64 (acc_lse2 of k_score_grad_body.h: the differences, exp and log in fp32): at T + U = 200 and V = 4 097
+//      they reach 1 600, where one fp32 rounding is 6e-5 and there is one per step -- the occupancies' exponent would be off by 1e-3 against
+//      the project's 1e-4.  alpha and beta are stored in fp64 for the same reason.
+//   3. crf_rnnt_grad_kernel<E, RAW>: one wave per row of grad, live or not.  A live node forms its two occupancies g_blank, g_label
+//      (times weight[n]) from alpha, beta, lb, ll and total; RAW re-reads the row and writes g_v - softmax_v (g_blank + g_label) in the
+//      input's dtype, the normalised form writes the zero row with its two entries.  Every other row (padding, invalid utterance, no finite
+//      path) is written as zeros: every element of grad is stored here, nothing is zeroed in front.
+// No atomics, vector loads and stores only, no scratch.  A node's values depend on its utterance alone: the same bits in any batch and
+// in either layout.
+#include "k_score_grad_body.h"   // acc_lse2, acc_shift
+
+namespace crf {
+
+// ---- a row of V elements of E, 16 bytes at a time ----
+template <typename E> __device__ __forceinline__ void rnnt_unpack(const uint4 &q, float (&x)[16 / sizeof(E)]);
+template <> __device__ __forceinline__ void rnnt_unpack<float>(const uint4 &q, float (&x)[4]) {
+    x[0] = __uint_as_float(q.x); x[1] = __uint_as_float(q.y); x[2] = __uint_as_float(q.z); x[3] = __uint_as_float(q.w);
+}
+template <> __device__ __forceinline__ void rnnt_unpack<AlnBf16>(const uint4 &q, float (&x)[8]) {
+    const unsigned w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { x[2 * i] = __uint_as_float(w[i] << 16); x[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
+}
+template <> __device__ __forceinline__ void rnnt_unpack<AlnF16>(const uint4 &q, float (&x)[8]) {
+    const unsigned w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        x[2 * i] = (float)__builtin_bit_cast(_Float16, (unsigned short)(w[i] & 0xffffu));
+        x[2 * i + 1] = (float)__builtin_bit_cast(_Float16, (unsigned short)(w[i] >> 16));
+    }
+}
+// fp32 -> E, round to nearest even (a gradient is finite: no NaN handling)
+template <typename E> __device__ __forceinline__ unsigned rnnt_bits(float v);
+template <> __device__ __forceinline__ unsigned rnnt_bits<float>(float v) { return __float_as_uint(v); }
+template <> __device__ __forceinline__ unsigned rnnt_bits<AlnBf16>(float v) {
+    const unsigned b = __float_as_uint(v);
+    return (b + 0x7fffu + ((b >> 16) & 1u)) >> 16;
+}
+template <> __device__ __forceinline__ unsigned rnnt_bits<AlnF16>(float v) { return __builtin_bit_cast(unsigned short, (_Float16)v); }
+template <typename E> __device__ __forceinline__ uint4 rnnt_pack(const float (&x)[16 / sizeof(E)]) {
+    if constexpr (sizeof(E) == 4) return uint4{rnnt_bits<E>(x[0]), rnnt_bits<E>(x[1]), rnnt_bits<E>(x[2]), rnnt_bits<E>(x[3])};
+    else return uint4{rnnt_bits<E>(x[0]) | (rnnt_bits<E>(x[1]) << 16), rnnt_bits<E>(x[2]) | (rnnt_bits<E>(x[3]) << 16),
+                      rnnt_bits<E>(x[4]) | (rnnt_bits<E>(x[5]) << 16), rnnt_bits<E>(x[6]) | (rnnt_bits<E>(x[7]) << 16)};
+}
+template <typename E> __device__ __forceinline__ void rnnt_st(char *a, float v) {
+    if constexpr (sizeof(E) == 4) *(float *)a = v;
+    else *(unsigned short *)a = (unsigned short)rnnt_bits<E>(v);
+}
+// A row is taken in chunks of 16 bytes COUNTED FROM ITS START, chunk i by lane i % 64: one 16-byte load (store) where the row starts on a
+// 16-byte boundary and the chunk is whole, element loads (stores) otherwise -- odd V, rows that start on a 2-byte boundary, as the other
+// kernels on raw output read them.  Which lane takes which element, and in which order, does not depend on the address: a row gives the
+// same bits wherever it lies.  Elements past V read as -inf.
+template <typename E> __device__ __forceinline__ void rnnt_chunk_ld(const char *xr, bool aligned, int v0, int V, float (&x)[16 / sizeof(E)]) {
+    constexpr int ES = sizeof(E), EPV = 16 / ES;
+    if (aligned && v0 + EPV <= V) { rnnt_unpack<E>(*(const uint4 *)(xr + (size_t)v0 * ES), x); return; }
+#pragma unroll
+    for (int k = 0; k < EPV; ++k) x[k] = v0 + k < V ? lat_ld<E>(xr + (size_t)(v0 + k) * ES) : -INFINITY;
+}
+template <typename E> __device__ __forceinline__ void rnnt_chunk_st(char *gr, bool aligned, int v0, int V, const float (&x)[16 / sizeof(E)]) {
+    constexpr int ES = sizeof(E), EPV = 16 / ES;
+    if (aligned && v0 + EPV <= V) { *(uint4 *)(gr + (size_t)v0 * ES) = rnnt_pack<E>(x); return; }
+#pragma unroll
+    for (int k = 0; k < EPV; ++k)
+        if (v0 + k < V) rnnt_st<E>(gr + (size_t)(v0 + k) * ES, x[k]);
+}
+
+// log sum_v exp(x_v) of one row, the wave's 64 lanes over it, read once: per lane a running (maximum, sum relative to it), per chunk one
+// rescale; the lanes' pairs meet in a butterfly (the maximum first, so every lane holds the same bits).  -inf for a row of -inf.
+template <typename E> __device__ __forceinline__ float rnnt_row_lse(const char *xr, int V, int lane) {
+    constexpr int EPV = 16 / sizeof(E);
+    const bool aligned = ((unsigned)(uintptr_t)xr & 15u) == 0u;
+    const int nchunk = (V + EPV - 1) / EPV;
+    float m = -INFINITY, s = 0.f;
+    for (int i = lane; i < nchunk; i += 64) {
+        float x[EPV];
+        rnnt_chunk_ld<E>(xr, aligned, i * EPV, V, x);
+        float vm = x[0];
+#pragma unroll
+        for (int k = 1; k < EPV; ++k) vm = fmaxf(vm, x[k]);
+        const float mn = fmaxf(m, vm);
+        if (mn > -INFINITY) {
+            float a = 0.f;
+#pragma unroll
+            for (int k = 0; k < EPV; ++k) a += score_exp(x[k] - mn);
+            s = s * score_exp(m - mn) + a;       // (m = -inf: s = 0, exp(-inf) = 0)
+            m = mn;
+        }
+    }
+    float M = m;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) M = fmaxf(M, __shfl_xor(M, o));
+    if (!(M > -INFINITY)) return -INFINITY;
+    s *= score_exp(m - M);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    return M + logf(s);
+}
+
+// out_v = f(v, x_v) over one row, the wave's 64 lanes over it; READ = false: x is not read (f takes 0)
+template <typename E, bool READ, typename F>
+__device__ __forceinline__ void rnnt_row_map(const char *xr, char *gr, int V, int lane, F &&f) {
+    constexpr int EPV = 16 / sizeof(E);
+    const bool xal = ((unsigned)(uintptr_t)xr & 15u) == 0u, gal = ((unsigned)(uintptr_t)gr & 15u) == 0u;
+    const int nchunk = (V + EPV - 1) / EPV;
+    for (int i = lane; i < nchunk; i += 64) {
+        const int v0 = i * EPV;
+        float x[EPV];
+        if constexpr (READ) rnnt_chunk_ld<E>(xr, xal, v0, V, x);
+#pragma unroll
+        for (int k = 0; k < EPV; ++k) x[k] = f(v0 + k, READ ? x[k] : 0.f);
+        rnnt_chunk_st<E>(gr, gal, v0, V, x);
+    }
+}
+
+// Row r -> its node.  false: r is padding, lies behind the last utterance or belongs to an invalid one.
+struct RnntNode { int n, t, u, Tn, Un; };
+__device__ __forceinline__ bool rnnt_node(const RnntParams &p, int64_t r, RnntNode &y) {
+    if (!p.compact) {
+        const int64_t per = (int64_t)p.T * p.U1;
+        y.n = (int)(r / per);
+        const int rem = (int)(r - (int64_t)y.n * per);
+        y.t = rem / p.U1; y.u = rem - y.t * p.U1;
+        y.Tn = p.tn[y.n]; y.Un = p.un[y.n];
+        return y.Tn > 0 && y.t < y.Tn && y.u <= y.Un;
+    }
+    if (r >= (int64_t)p.node_off[p.N]) return false;
+    int lo = 0, hi = p.N;                        // the last utterance whose first row is at or in front of r (one without rows never is)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((int64_t)p.node_off[mid] <= r) lo = mid; else hi = mid;
+    }
+    y.n = lo; y.Tn = p.tn[lo]; y.Un = p.un[lo];
+    if (y.Tn <= 0) return false;
+    const int local = (int)(r - (int64_t)p.node_off[lo]);
+    y.t = local / (y.Un + 1); y.u = local - y.t * (y.Un + 1);
+    return y.t < y.Tn;
+}
+
+// ---- stage 0 ----
+__global__ __launch_bounds__(kRnntPrepThreads) void crf_rnnt_prep_kernel(RnntParams p) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (wave == 0) {
+        long long cn = 0, cl = 0;                // rows and labels in front of this chunk of 64 utterances
+        for (int n0 = 0; n0 < p.N; n0 += 64) {
+            const int n = n0 + lane;
+            const bool in = n < p.N;
+            const int Tn = in ? p.lx[n] : 0, Un = in ? p.ly[n] : 0;
+            const bool lenok = in && Tn >= 1 && Tn <= p.T && Un >= 0 && Un <= p.U1 - 1;
+            long long ext = 0, lext = 0;
+            if (in) {
+                ext = p.compact ? (lenok ? (long long)Tn * (Un + 1) : 0) : (long long)p.T * p.U1;
+                lext = p.compact ? (lenok ? Un : 0) : p.U1 - 1;
+            }
+            long long se = ext, sl = lext;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const long long a = __shfl_up(se, o), b = __shfl_up(sl, o);
+                if (lane >= o) { se += a; sl += b; }
+            }
+            const long long on = cn + se - ext, ol = cl + sl - lext;
+            const bool ok = lenok && on + ext <= p.R && ol + lext <= p.nlab;
+            if (in) {
+                p.node_off[n] = (int)min(on, (long long)p.R);
+                p.lab_off[n] = (int)min(ol, (long long)p.nlab);
+                p.tn[n] = ok ? Tn : 0;
+                p.un[n] = ok ? Un : 0;
+            }
+            cn += __shfl(se, 63); cl += __shfl(sl, 63);
+        }
+        if (lane == 0) p.node_off[p.N] = (int)min(cn, (long long)p.R);
+    }
+    __syncthreads();
+    for (int n = wave; n < p.N; n += kRnntPrepThreads / 64) {        // the labels, a wave per utterance
+        const int Tn = p.tn[n], Un = p.un[n];
+        if (Tn <= 0) continue;
+        const int *yl = p.labels + p.lab_off[n];
+        bool bad = false;
+        for (int i = lane; i < Un; i += 64) {
+            const int l = yl[i];
+            bad = bad || (unsigned)l >= (unsigned)p.V || l == p.blank;
+        }
+        if (__ballot(bad) && lane == 0) p.tn[n] = 0;
+    }
+}
+
+// ---- stage 1 ----
+__global__ __launch_bounds__(256) void crf_rnnt_gather_kernel(RnntParams p) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    RnntNode y;
+    if (r >= p.R || !rnnt_node(p, r, y)) return;
+    const float *xr = (const float *)p.x + r * p.V;
+    float *o = p.row + 3 * r;
+    o[0] = 0.f;
+    o[1] = xr[p.blank];
+    o[2] = y.u < y.Un ? xr[p.labels[p.lab_off[y.n] + y.u]] : -INFINITY;
+}
+
+template <typename E>
+__global__ __launch_bounds__(64 * kRnntWaves) void crf_rnnt_row_kernel(RnntParams p) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * kRnntWaves + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    RnntNode y;
+    if (r >= p.R || !rnnt_node(p, r, y)) return;  // (no barrier in this kernel: waves leave on their own)
+    const char *xr = (const char *)p.x + (size_t)r * p.V * sizeof(E);
+    const float lse = rnnt_row_lse<E>(xr, p.V, lane);
+    if (lane == 0) {
+        const bool fin = lse > -INFINITY;
+        float *o = p.row + 3 * r;
+        o[0] = lse;
+        o[1] = fin ? lat_ld<E>(xr + (size_t)p.blank * sizeof(E)) - lse : -INFINITY;
+        o[2] = fin && y.u < y.Un ? lat_ld<E>(xr + (size_t)p.labels[p.lab_off[y.n] + y.u] * sizeof(E)) - lse : -INFINITY;
+    }
+}
+
+// ---- stage 2 ----
+template <bool WG>
+__global__ __launch_bounds__(WG ? kRnntMaxU1 : 64) void crf_rnnt_lattice_kernel(RnntParams p) {
+    constexpr int PF = kRnntPF;
+    __shared__ double edge[2][WG ? kRnntMaxU1 / 64 : 1];   // WG: the top lane's value of every wave, this step's and the one before
+    const int j = threadIdx.x, lane = j & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(j >> 6);
+    const int n = blockIdx.x;
+    const bool back = blockIdx.y != 0;
+    const int Tn = p.tn[n], Un = p.un[n];
+    if (Tn <= 0 || Un >= (int)blockDim.x) {                // (the whole workgroup, in front of any barrier)
+        if (!back && j == 0) {
+            p.total[n] = -INFINITY;
+            p.cost[n] = INFINITY;
+            if (p.invalid) p.invalid[n] = 1;
+        }
+        return;
+    }
+    const int S = p.compact ? Un + 1 : p.U1;
+    const int64_t base = p.node_off[n];
+    const float *rb = p.row + 3 * base;
+    double *out = (back ? p.beta : p.alpha) + base;
+    const int u = back ? Un - j : j;
+    const int uc = min(max(u, 0), Un), ul = min(max(u - 1, 0), Un);
+
+    // the two emissions of the steps d0 .. d0 + PF - 1 from clamped nodes: forward lb[t-1][u] and ll[t][u-1], backward lb[t][u] and ll[t][u]
+    auto fetch = [&](float (&eb)[PF], float (&el)[PF], int d0) __attribute__((always_inline)) {
+#pragma unroll
+        for (int f = 0; f < PF; ++f) {
+            const int q = d0 + f - j;
+            if (!back) {
+                eb[f] = rb[3 * (min(max(q - 1, 0), Tn - 1) * S + uc) + 1];
+                el[f] = rb[3 * (min(max(q, 0), Tn - 1) * S + ul) + 2];
+            } else {
+                const float *o = rb + 3 * (min(max(Tn - 1 - q, 0), Tn - 1) * S + uc);
+                eb[f] = o[1];
+                el[f] = o[2];
+            }
+        }
+    };
+    double v = -INFINITY, fin = -INFINITY;
+    auto step = [&](float eb, float el, int d) __attribute__((always_inline)) {
+        double nb = acc_shift<true>(v);
+        if constexpr (WG)
+            if (lane == 0 && wave > 0 && d > 0) nb = edge[(d - 1) & 1][wave - 1];
+        const int q = d - j;
+        double nv = acc_lse2(v + (double)eb, nb + (double)el);
+        if (d == 0 && j == 0) nv = back ? (double)eb : 0.0;
+        const bool act = q >= 0 && q < Tn && j <= Un;
+        v = act ? nv : -INFINITY;
+        if (act) out[(back ? Tn - 1 - q : q) * S + u] = v;
+        if (q == Tn - 1) fin = v;
+        if constexpr (WG) {
+            if (lane == 63) edge[d & 1][wave] = v;
+            __syncthreads();
+        }
+    };
+    const int nsteps = Tn + Un;
+    float ab[PF], al[PF], bb[PF], bl[PF];
+    fetch(ab, al, 0);
+    for (int d0 = 0; d0 < nsteps; d0 += 2 * PF) {           // (whole batches: past the last diagonal no column is active)
+        fetch(bb, bl, d0 + PF);
+#pragma unroll
+        for (int f = 0; f < PF; ++f) step(ab[f], al[f], d0 + f);
+        fetch(ab, al, d0 + 2 * PF);
+#pragma unroll
+        for (int f = 0; f < PF; ++f) step(bb[f], bl[f], d0 + PF + f);
+    }
+    if (!back && j == Un) {
+        const double total = fin + (double)rb[3 * ((Tn - 1) * S + Un) + 1];
+        const bool ok = total > -INFINITY;                  // (false for NaN as well)
+        p.total[n] = ok ? total : -INFINITY;
+        p.cost[n] = ok ? (float)-total : INFINITY;
+        if (p.invalid) p.invalid[n] = 0;
+    }
+}
+
+// ---- stage 3 ----
+template <typename E, bool RAW>
+__global__ __launch_bounds__(64 * kRnntWaves) void crf_rnnt_grad_kernel(RnntParams p) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * kRnntWaves + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    if (r >= p.R) return;
+    char *gr = (char *)p.grad + (size_t)r * p.V * sizeof(E);
+    const char *xr = (const char *)p.x + (size_t)r * p.V * sizeof(E);
+    RnntNode y;
+    double total = -INFINITY;
+    if (rnnt_node(p, r, y)) total = p.total[y.n];
+    if (!(total > -INFINITY)) {
+        rnnt_row_map<E, false>(xr, gr, p.V, lane, [](int, float) { return 0.f; });
+        return;
+    }
+    const int S = p.compact ? y.Un + 1 : p.U1;
+    const float w = p.weight[y.n];
+    const float *o = p.row + 3 * r;
+    const float lse = o[0];
+    const double a = p.alpha[r];
+    const double nb = y.t + 1 < y.Tn ? p.beta[r + S] : (y.u == y.Un ? 0.0 : -INFINITY);
+    const float gb = -w * expf((float)(a + (double)o[1] + nb - total));
+    float gl = 0.f;
+    int label = -1;
+    if (y.u < y.Un) {
+        label = p.labels[p.lab_off[y.n] + y.u];
+        gl = -w * expf((float)(a + (double)o[2] + p.beta[r + 1] - total));
+    }
+    const int blank = p.blank;
+    if constexpr (RAW) {
+        const float gs = gb + gl;
+        const bool fin = lse > -INFINITY;
+        rnnt_row_map<E, true>(xr, gr, p.V, lane, [&](int v, float x) {
+            const float sm = fin ? score_exp(x - lse) : 0.f;
+            return (v == blank ? gb : 0.f) + (v == label ? gl : 0.f) - sm * gs;
+        });
+    } else {
+        rnnt_row_map<E, false>(xr, gr, p.V, lane, [&](int v, float) { return v == blank ? gb : v == label ? gl : 0.f; });
+    }
+}
+
+template __global__ void crf_rnnt_row_kernel<float>(RnntParams);
+template __global__ void crf_rnnt_row_kernel<AlnBf16>(RnntParams);
+template __global__ void crf_rnnt_row_kernel<AlnF16>(RnntParams);
+template __global__ void crf_rnnt_lattice_kernel<false>(RnntParams);
+template __global__ void crf_rnnt_lattice_kernel<true>(RnntParams);
+template __global__ void crf_rnnt_grad_kernel<float, false>(RnntParams);
+template __global__ void crf_rnnt_grad_kernel<float, true>(RnntParams);
+template __global__ void crf_rnnt_grad_kernel<AlnBf16, true>(RnntParams);
+template __global__ void crf_rnnt_grad_kernel<AlnF16, true>(RnntParams);
+
+}  // namespace crf

@@ -39,6 +39,10 @@ Same names, arguments and error behaviour as the reference:
   ngram_score(hyps, hyp_lengths, lm, bos=True, eos=False, return_token_scores=False) -> (scores FloatTensor[H], invalid IntTensor[H])
                                                               (with return_token_scores: also token_logp [H, W], token_order [H, W])
                                                                                          (n-gram LM scores of rows on the GPU: N-best rescoring)
+  rnnt_loss(log_probs, labels, frames_lengths, labels_lengths, average_frames=False, reduction=None, blank=0, compact=False,
+            fuse_log_softmax=False) -> costs                                             (warp_rnnt.rnnt_loss: the RNN-T transducer loss with
+                                                                                         autograd, padded or compact joiner output, normalised
+                                                                                         or raw; the top-level package warp_rnnt re-exports it)
 plus the functional form named by BASELINE.json:
   ctc_crf_loss(log_probs, labels, frame_lens, label_lens, den_lm, lamb=0.1, size_average=True)
 
@@ -608,6 +612,58 @@ def ngram_score(hyps: torch.Tensor, hyp_lengths: torch.Tensor, lm: NgramLM, bos:
 
 
 _CTX_CACHE: Dict[Tuple[str, int], CRFContext] = {}
+
+
+class _RNNT_LOSS(Function):
+    """costs [N] = crf_rnnt_loss / crf_rnnt_loss_logits; backward = ONE crf_rnnt_grad / crf_rnnt_grad_logits call on the forward's workspace
+    with grad_output as the per-utterance weights.  The gradient has the input's shape and dtype; the kernels write every element."""
+
+    @staticmethod
+    def forward(ctx, log_probs, labels, lx, ly, blank, compact, fused):
+        costs, invalid, call = core.rnnt_loss_fwd(log_probs, labels, lx, ly, blank, compact, fused)
+        ctx.call = call
+        ctx.mark_non_differentiable(invalid)
+        return costs, invalid
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_costs, _grad_invalid):
+        return core.rnnt_loss_bwd(ctx.call, grad_costs), None, None, None, None, None, None
+
+
+def rnnt_loss(log_probs: torch.Tensor, labels: torch.Tensor, frames_lengths: torch.Tensor, labels_lengths: torch.Tensor,
+              average_frames: bool = False, reduction: str = None, blank: int = 0, compact: bool = False, fuse_log_softmax: bool = False,
+              return_invalid: bool = False):
+    """The RNN-T transducer loss with autograd, with the arguments and semantics of ``warp_rnnt.rnnt_loss`` (cat/rnnt/train.py:217,
+    train_unified.py:292-306 call it as rnnt_loss(joinout, y, lsub, ly, compact=...)): costs[n] = -log p(y_n | x_n), summed over all
+    monotone alignments -- blank moves t -> t + 1, label y[u] moves u -> u + 1, the path ends with a blank at (T_n - 1, U_n).
+
+    log_probs: (N, T, U+1, V) float32 log-probabilities on the GPU.  Its gradient is zero except at the blank's column and at column
+        labels[n, u] of every live node (t < T_n, u <= U_n).
+    labels: int32 (N, U).  frames_lengths, labels_lengths: int32 (N,), both on the CPU (checked up front: ValueError) or both on the GPU
+        (nothing is read on the host and nothing synchronises; an utterance out of range is invalid, see below).
+    average_frames: each utterance's cost is divided by its T_n.  reduction: None / "none" (costs (N,)), "mean", "sum".
+    blank: the blank's column, any of [0, V).
+    compact: log_probs is (sum_n T_n (U_n + 1), V), the utterances back to back, each T_n x (U_n + 1) row-major -- what cat/rnnt/joiner.py
+        produces -- and labels (sum_n U_n,), what train.py:182 makes of y.  The offsets are prefix sums taken on the device.
+    fuse_log_softmax: log_probs is the RAW joiner output in float32, bfloat16 or float16, read in place: no log_softmax in front and no
+        float32 copy for autograd.  The gradient comes back in the input's dtype with log_softmax's backward folded in,
+        g_v - softmax_v (g_blank + g_label).
+    Invalid utterances (T_n outside [1, T], U_n outside [0, U], a label outside [0, V) or equal to blank) are decided on the device: cost
+    +inf and a zero gradient, as for ctc_score's rows over their bound; return_invalid=True returns (costs, invalid IntTensor[N]).  A
+    lattice without a finite path (-inf entries) also costs +inf with a zero gradient, never NaN.  U <= 1023, V <= 8192.
+    Not covered: gather=True as a separate mode (the kernels read two columns of a normalised row anyway), fastemit_lambda,
+    rnnt_loss_simple, any RNN-T decoding."""
+    if reduction not in (None, "none", "mean", "sum"):
+        raise ValueError(f"rnnt_loss: unknown reduction {reduction!r} (None, 'none', 'mean' or 'sum')")
+    costs, invalid = _RNNT_LOSS.apply(log_probs, labels, frames_lengths, labels_lengths, int(blank), bool(compact), bool(fuse_log_softmax))
+    if average_frames:
+        costs = costs / frames_lengths.to(device=costs.device, dtype=costs.dtype)
+    if reduction == "sum":
+        costs = costs.sum()
+    elif reduction == "mean":
+        costs = costs.mean()
+    return (costs, invalid) if return_invalid else costs
 
 
 def ctc_crf_loss(log_probs: torch.Tensor, labels: torch.Tensor, frame_lens: torch.Tensor,

@@ -601,6 +601,61 @@ int crf_ngram_score(const crf_ngram_tables *lm, const float *eos_logp_dev, const
                     float *token_logp_dev, int32_t *token_order_dev, void *stream);
 const char *crf_last_ngram_score_kernel(void);
 
+/* The RNN-T transducer loss and its gradient: what cat/rnnt/train.py:217 and train_unified.py:292-306 call as
+ * warp_rnnt.rnnt_loss(joinout, y, lsub, ly, compact=...).  cost[n] = -log p(y_n | x_n), summed over all monotone alignments of the lattice
+ * T_n x (U_n + 1): blank moves t -> t + 1, label y[u] moves u -> u + 1, the path ends with a blank at (T_n - 1, U_n).
+ *
+ * The joiner output is read in place as rows of V elements, one per lattice node:
+ *   padded   (compact_rows < 0):  [N][T][U1][V], labels_dev [N][U1 - 1]                        (U1 = U + 1, compact_labels is ignored)
+ *   compact  (compact_rows >= 0): [compact_rows][V], the utterances back to back, each T_n x (U_n + 1) row-major, and labels_dev
+ *            [compact_labels] likewise; the offsets are prefix sums taken ON THE DEVICE from lx_dev / ly_dev (int32 [N], device), T and U1
+ *            are then bounds on the lengths only.
+ * crf_rnnt_loss / crf_rnnt_grad take normalised fp32 log-probabilities; the *_logits forms take the RAW joiner output, dtype 0 = fp32,
+ * 1 = bf16, 2 = fp16 (upcast in registers), and are the loss of log_softmax(logits): no normalised copy is ever made.
+ *
+ * crf_rnnt_loss* is the forward: cost_dev [N], invalid_dev [N] (may be NULL) and the workspace, which keeps what the backward needs.
+ * crf_rnnt_grad* takes THE SAME arguments and the same workspace, unchanged since the forward, and grad_output_dev [N], the derivative of
+ * the caller's scalar with respect to cost[n] (any reduction and scale already folded in).  It writes EVERY element of grad_dev, which has
+ * the shape and -- logits form -- the element type of the input:
+ *   normalised:  grad[r][v] = grad_output[n] * d cost[n] / d log_probs[r][v]: zero except at the blank's column and at column
+ *                labels[n][u] of a live node (t < T_n, u <= U_n);
+ *   logits:      grad[r][v] = g_v - softmax(x[r])_v * (g_blank + g_label), g the two entries above: log_softmax's backward folded in.
+ * Rows of padding nodes, of invalid utterances and of utterances without a finite path are written as zeros; there is no memset.
+ *
+ * Invalid input is decided on the device, without an error and without a host synchronisation: an utterance with T_n outside [1, T], U_n
+ * outside [0, U1 - 1], a label outside [0, V) or equal to `blank`, or (compact) rows or labels that would reach past compact_rows /
+ * compact_labels, gets cost +inf, invalid 1 and a zero gradient; in the compact layout an utterance whose LENGTHS are out of range claims no
+ * rows.  A lattice without a finite path (entries of -inf) gets cost +inf and a zero gradient with invalid 0; no NaN is produced.
+ *
+ * Workspace, with R = N T U1 (padded) or compact_rows and al(x) = x rounded up to a multiple of 256:
+ *   crf_rnnt_workspace_bytes = al(12 R) + al(8 R) + al(8 R) + al(8 N + 4 (4 N + 1))
+ * -- per node three floats (lse, x[blank] - lse, x[label] - lse) and alpha and beta in fp64 (seven floats; fp32 alpha / beta lose the
+ * gradient's fourth digit on long lattices), per utterance the total in fp64, two offsets and the two checked lengths.  It must be
+ * 16-byte aligned.  -1 with the message set for sizes the call would refuse.
+ *
+ * Errors, all answered before any HIP call: a null pointer (CRF_ERR_ARG), dtype outside 0..2, N, T, U1 or V < 1, blank outside [0, V),
+ * rows outside [1, INT32_MAX], T U1 (padded) or compact_rows > INT32_MAX / 4, a misaligned workspace (CRF_ERR_ARG), U1 > 1024 or V > 8192 (CRF_ERR_UNSUPPORTED),
+ * a workspace that is too small (CRF_ERR_WORKSPACE).  One stream, no host synchronisation, no environment variable.
+ * Not covered: warp_rnnt's gather mode as a separate entry (the kernels read two columns of a normalised row anyway), fastemit_lambda,
+ * rnnt_loss_simple, any RNN-T decoding. */
+int64_t crf_rnnt_workspace_bytes(int64_t N, int64_t T, int64_t U1, int64_t V, int64_t compact_rows);
+int crf_rnnt_loss(const float *log_probs_dev, int blank, const int32_t *labels_dev, const int32_t *lx_dev, const int32_t *ly_dev, int64_t N,
+                  int64_t T, int64_t U1, int64_t V, int64_t compact_rows, int64_t compact_labels, float *cost_dev, int32_t *invalid_dev,
+                  void *workspace_dev, int64_t workspace_bytes, void *stream);
+int crf_rnnt_loss_logits(const void *logits_dev, int dtype, int blank, const int32_t *labels_dev, const int32_t *lx_dev, const int32_t *ly_dev,
+                         int64_t N, int64_t T, int64_t U1, int64_t V, int64_t compact_rows, int64_t compact_labels, float *cost_dev,
+                         int32_t *invalid_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+int crf_rnnt_grad(const float *log_probs_dev, int blank, const int32_t *labels_dev, const int32_t *lx_dev, const int32_t *ly_dev, int64_t N,
+                  int64_t T, int64_t U1, int64_t V, int64_t compact_rows, int64_t compact_labels, const float *grad_output_dev, float *grad_dev,
+                  void *workspace_dev, int64_t workspace_bytes, void *stream);
+int crf_rnnt_grad_logits(const void *logits_dev, int dtype, int blank, const int32_t *labels_dev, const int32_t *lx_dev, const int32_t *ly_dev,
+                         int64_t N, int64_t T, int64_t U1, int64_t V, int64_t compact_rows, int64_t compact_labels,
+                         const float *grad_output_dev, void *grad_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+/* The workspace's sections as (offset, bytes) pairs -- "row", "alpha", "beta", "utt" -- for the guard-band tests; with the switch ws_gap
+ * n x 256 untouched bytes follow every section.  Returns the number of sections, -1 for sizes the call would refuse. */
+int crf_debug_rnnt_ws_sections(int64_t N, int64_t T, int64_t U1, int64_t V, int64_t compact_rows, int64_t *out, int n_out);
+const char *crf_debug_rnnt_ws_section_names(void);
+
 /* Token edit distance of H hypotheses to the transcripts of their utterances, with the operation counts of one optimal alignment: what
  * cat/ctc/train.py:200-210 (cal_wer), train_jsa.py:371-387 (cal_per), train_me2e.py:250-256 and train_me2e_kaldi.py:420-426 compute with
  * a Python loop of Levenshtein.distance after `.cpu().tolist()`, and the risk of minimum-risk / MWER training, for the rows that
