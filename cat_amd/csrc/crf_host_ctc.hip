@@ -573,7 +573,7 @@ static int launch_ngram_score(const NgramScoreParams &p, hipStream_t st) {
 }
 
 // ---- the RNN-T loss and its gradient (k_rnnt.hip) ----
-// The workspace both calls share, R = the rows of the joiner output (N T U1 padded, compact_rows compact): row [R][3] floats (lse, lb, ll),
+// The workspace both calls share, R = the rows of the joiner output (N T U1 padded, compact_rows compact): row [R][4] floats (M, log s, lb, ll),
 // alpha [R] and beta [R] fp64, utt: total [N] fp64, then node_off [N + 1], lab_off [N], tn [N], un [N] int32.  < 0 with the message set.
 enum RnntWs { kRtRow, kRtAlpha, kRtBeta, kRtUtt, kRtCount };
 static const char *const kRnntWsNames[kRtCount] = {"row", "alpha", "beta", "utt"};
@@ -582,13 +582,13 @@ static int64_t rnnt_ws_bytes(int64_t N, int64_t T, int64_t U1, int64_t V, int64_
     if (N <= 0 || T <= 0 || U1 <= 0 || V <= 0 || N > INT32_MAX || T > INT32_MAX) { set_error(who + "bad N/T/U+1/V"); return -CRF_ERR_ARG; }
     if (U1 > kRnntMaxU1) { set_error(who + "U > " + std::to_string(kRnntMaxU1 - 1) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
     if (V > kRnntMaxV) { set_error(who + "V > " + std::to_string(kRnntMaxV) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
-    // (an utterance's nodes are indexed in 32 bits, times three for the row section: T U1 padded, at most all rows compact)
+    // (an utterance's nodes are indexed in 32 bits, times four for the row section: T U1 padded, at most all rows compact)
     if (compact_rows < 0 && T > (INT32_MAX / 4) / U1) { set_error(who + "T * (U + 1) > INT32_MAX / 4"); return -CRF_ERR_ARG; }
     if (compact_rows > INT32_MAX / 4) { set_error(who + "compact_rows > INT32_MAX / 4"); return -CRF_ERR_ARG; }
     const int64_t R = compact_rows < 0 ? N * T * U1 : compact_rows;
     if (R <= 0 || R > INT32_MAX || (compact_rows < 0 && N > INT32_MAX / (T * U1))) { set_error(who + "rows outside [1, INT32_MAX]"); return -CRF_ERR_ARG; }
     SideWs w;
-    w.add(kRnntWsNames[kRtRow], 3 * R * (int64_t)sizeof(float)).add(kRnntWsNames[kRtAlpha], R * (int64_t)sizeof(double))
+    w.add(kRnntWsNames[kRtRow], 4 * R * (int64_t)sizeof(float)).add(kRnntWsNames[kRtAlpha], R * (int64_t)sizeof(double))
      .add(kRnntWsNames[kRtBeta], R * (int64_t)sizeof(double)).add(kRnntWsNames[kRtUtt], N * (int64_t)sizeof(double) + (4 * N + 1) * (int64_t)sizeof(int32_t));
     if (out) *out = w;
     if (rows) *rows = R;

@@ -242,7 +242,7 @@ struct RnntParams {
     int N, T, U1, V, blank, compact;
     int64_t R;                  // rows of x: N T U1, or the compact rows
     int64_t nlab;               // entries of labels: N (U1 - 1), or the compact total
-    float *row;                 // [R][3] lse, lb = x[blank] - lse, ll = x[y_u] - lse (-inf at u = U_n) of the live nodes
+    float *row;                 // [R][4], 16-byte aligned: M = max_v x_v, ls = log sum_v exp(x_v - M), lb = (x[blank] - M) - ls, ll = (x[y_u] - M) - ls (-inf at u = U_n) of the live nodes
     double *alpha, *beta;       // [R] of the live nodes
     double *total;              // [N] log p(y | x), -inf for an invalid utterance or one without a finite path
     int *node_off;              // [N + 1] first row of utterance n

@@ -17,9 +17,11 @@
 //      of range claims no rows.
 //   1. row stage.  crf_rnnt_row_kernel<E> (raw joiner output): one wave per live node reads its V-row ONCE -- an online log-sum-exp, 16-byte
 //      loads where the row starts on a 16-byte boundary, element loads otherwise (odd V, rows that start on a 2-byte boundary), the same
-//      elements in the same lanes either way -- and writes lse, lb = x[blank] - lse, ll = x[y_u] - lse.  A row of -inf gives
-//      lb = ll = -inf, not NaN.
-//      crf_rnnt_gather_kernel (normalised input): the same three floats, lse = 0, a thread per node.
+//      elements in the same lanes either way -- and writes the row's maximum M, log s = log sum_v exp(x_v - M), lb = (x[blank] - M) - log s
+//      and ll = (x[y_u] - M) - log s in one 16-byte store.  M and log s stay apart and the maximum is taken off FIRST, as log_softmax does:
+//      x - (M + log s) rounds at ulp(M), and logits with a common offset of 4 096 put the gradient off by 2e-4 of its largest entry
+//      (DESIGN.md 7 (f15)); (x - M) - log s does not know the offset.  A row of -inf gives lb = ll = -inf, not NaN.
+//      crf_rnnt_gather_kernel (normalised input): the same four floats, M = log s = 0, a thread per node.
 //   2. crf_rnnt_lattice_kernel<WG>: one workgroup per (utterance, direction), thread j = column (alpha: u = j; beta: u = U_n - j, time
 //      reversed, which makes it the same recursion), T_n + U_n dependent steps along the anti-diagonals.  The running value stays in a
 //      register; the neighbour's previous value comes by a DPP shift inside a wave and, across waves (WG), through two LDS rows with ONE
@@ -92,8 +94,9 @@ template <typename E> __device__ __forceinline__ void rnnt_chunk_st(char *gr, bo
 }
 
 // log sum_v exp(x_v) of one row, the wave's 64 lanes over it, read once: per lane a running (maximum, sum relative to it), per chunk one
-// rescale; the lanes' pairs meet in a butterfly (the maximum first, so every lane holds the same bits).  -inf for a row of -inf.
-template <typename E> __device__ __forceinline__ float rnnt_row_lse(const char *xr, int V, int lane) {
+// rescale; the lanes' pairs meet in a butterfly (the maximum first, so every lane holds the same bits).  -> the maximum M and
+// log sum_v exp(x_v - M), apart (their sum would round at ulp(M)); false for a row of -inf, M = -inf and 0 then.
+template <typename E> __device__ __forceinline__ bool rnnt_row_lse(const char *xr, int V, int lane, float &M, float &ls) {
     constexpr int EPV = 16 / sizeof(E);
     const bool aligned = ((unsigned)(uintptr_t)xr & 15u) == 0u;
     const int nchunk = (V + EPV - 1) / EPV;
@@ -113,14 +116,15 @@ template <typename E> __device__ __forceinline__ float rnnt_row_lse(const char *
             m = mn;
         }
     }
-    float M = m;
+    M = m; ls = 0.f;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) M = fmaxf(M, __shfl_xor(M, o));
-    if (!(M > -INFINITY)) return -INFINITY;
+    if (!(M > -INFINITY)) return false;
     s *= score_exp(m - M);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    return M + logf(s);
+    ls = logf(s);
+    return true;
 }
 
 // out_v = f(v, x_v) over one row, the wave's 64 lanes over it; READ = false: x is not read (f takes 0)
@@ -217,10 +221,7 @@ __global__ __launch_bounds__(256) void crf_rnnt_gather_kernel(RnntParams p) {
     RnntNode y;
     if (r >= p.R || !rnnt_node(p, r, y)) return;
     const float *xr = (const float *)p.x + r * p.V;
-    float *o = p.row + 3 * r;
-    o[0] = 0.f;
-    o[1] = xr[p.blank];
-    o[2] = y.u < y.Un ? xr[p.labels[p.lab_off[y.n] + y.u]] : -INFINITY;
+    *(float4 *)(p.row + 4 * r) = float4{0.f, 0.f, xr[p.blank], y.u < y.Un ? xr[p.labels[p.lab_off[y.n] + y.u]] : -INFINITY};
 }
 
 template <typename E>
@@ -230,13 +231,12 @@ __global__ __launch_bounds__(64 * kRnntWaves) void crf_rnnt_row_kernel(RnntParam
     RnntNode y;
     if (r >= p.R || !rnnt_node(p, r, y)) return;  // (no barrier in this kernel: waves leave on their own)
     const char *xr = (const char *)p.x + (size_t)r * p.V * sizeof(E);
-    const float lse = rnnt_row_lse<E>(xr, p.V, lane);
+    float M, ls;
+    const bool fin = rnnt_row_lse<E>(xr, p.V, lane, M, ls);
     if (lane == 0) {
-        const bool fin = lse > -INFINITY;
-        float *o = p.row + 3 * r;
-        o[0] = lse;
-        o[1] = fin ? lat_ld<E>(xr + (size_t)p.blank * sizeof(E)) - lse : -INFINITY;
-        o[2] = fin && y.u < y.Un ? lat_ld<E>(xr + (size_t)p.labels[p.lab_off[y.n] + y.u] * sizeof(E)) - lse : -INFINITY;
+        const float lb = fin ? (lat_ld<E>(xr + (size_t)p.blank * sizeof(E)) - M) - ls : -INFINITY;
+        const float ll = fin && y.u < y.Un ? (lat_ld<E>(xr + (size_t)p.labels[p.lab_off[y.n] + y.u] * sizeof(E)) - M) - ls : -INFINITY;
+        *(float4 *)(p.row + 4 * r) = float4{M, ls, lb, ll};
     }
 }
 
@@ -260,7 +260,7 @@ __global__ __launch_bounds__(WG ? kRnntMaxU1 : 64) void crf_rnnt_lattice_kernel(
     }
     const int S = p.compact ? Un + 1 : p.U1;
     const int64_t base = p.node_off[n];
-    const float *rb = p.row + 3 * base;
+    const float *rb = p.row + 4 * base;
     double *out = (back ? p.beta : p.alpha) + base;
     const int u = back ? Un - j : j;
     const int uc = min(max(u, 0), Un), ul = min(max(u - 1, 0), Un);
@@ -271,12 +271,12 @@ __global__ __launch_bounds__(WG ? kRnntMaxU1 : 64) void crf_rnnt_lattice_kernel(
         for (int f = 0; f < PF; ++f) {
             const int q = d0 + f - j;
             if (!back) {
-                eb[f] = rb[3 * (min(max(q - 1, 0), Tn - 1) * S + uc) + 1];
-                el[f] = rb[3 * (min(max(q, 0), Tn - 1) * S + ul) + 2];
+                eb[f] = rb[4 * (min(max(q - 1, 0), Tn - 1) * S + uc) + 2];
+                el[f] = rb[4 * (min(max(q, 0), Tn - 1) * S + ul) + 3];
             } else {
-                const float *o = rb + 3 * (min(max(Tn - 1 - q, 0), Tn - 1) * S + uc);
-                eb[f] = o[1];
-                el[f] = o[2];
+                const float *o = rb + 4 * (min(max(Tn - 1 - q, 0), Tn - 1) * S + uc);
+                eb[f] = o[2];
+                el[f] = o[3];
             }
         }
     };
@@ -309,7 +309,7 @@ __global__ __launch_bounds__(WG ? kRnntMaxU1 : 64) void crf_rnnt_lattice_kernel(
         for (int f = 0; f < PF; ++f) step(bb[f], bl[f], d0 + PF + f);
     }
     if (!back && j == Un) {
-        const double total = fin + (double)rb[3 * ((Tn - 1) * S + Un) + 1];
+        const double total = fin + (double)rb[4 * ((Tn - 1) * S + Un) + 2];
         const bool ok = total > -INFINITY;                  // (false for NaN as well)
         p.total[n] = ok ? total : -INFINITY;
         p.cost[n] = ok ? (float)-total : INFINITY;
@@ -334,23 +334,22 @@ __global__ __launch_bounds__(64 * kRnntWaves) void crf_rnnt_grad_kernel(RnntPara
     }
     const int S = p.compact ? y.Un + 1 : p.U1;
     const float w = p.weight[y.n];
-    const float *o = p.row + 3 * r;
-    const float lse = o[0];
+    const float4 o = *(const float4 *)(p.row + 4 * r);                  // M, log s, lb, ll
     const double a = p.alpha[r];
     const double nb = y.t + 1 < y.Tn ? p.beta[r + S] : (y.u == y.Un ? 0.0 : -INFINITY);
-    const float gb = -w * expf((float)(a + (double)o[1] + nb - total));
+    const float gb = -w * expf((float)(a + (double)o.z + nb - total));
     float gl = 0.f;
     int label = -1;
     if (y.u < y.Un) {
         label = p.labels[p.lab_off[y.n] + y.u];
-        gl = -w * expf((float)(a + (double)o[2] + p.beta[r + 1] - total));
+        gl = -w * expf((float)(a + (double)o.w + p.beta[r + 1] - total));
     }
     const int blank = p.blank;
     if constexpr (RAW) {
         const float gs = gb + gl;
-        const bool fin = lse > -INFINITY;
+        const bool fin = o.x > -INFINITY;
         rnnt_row_map<E, true>(xr, gr, p.V, lane, [&](int v, float x) {
-            const float sm = fin ? score_exp(x - lse) : 0.f;
+            const float sm = fin ? score_exp((x - o.x) - o.y) : 0.f;
             return (v == blank ? gb : 0.f) + (v == label ? gl : 0.f) - sm * gs;
         });
     } else {

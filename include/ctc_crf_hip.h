@@ -628,10 +628,11 @@ const char *crf_last_ngram_score_kernel(void);
  * rows.  A lattice without a finite path (entries of -inf) gets cost +inf and a zero gradient with invalid 0; no NaN is produced.
  *
  * Workspace, with R = N T U1 (padded) or compact_rows and al(x) = x rounded up to a multiple of 256:
- *   crf_rnnt_workspace_bytes = al(12 R) + al(8 R) + al(8 R) + al(8 N + 4 (4 N + 1))
- * -- per node three floats (lse, x[blank] - lse, x[label] - lse) and alpha and beta in fp64 (seven floats; fp32 alpha / beta lose the
- * gradient's fourth digit on long lattices), per utterance the total in fp64, two offsets and the two checked lengths.  It must be
- * 16-byte aligned.  -1 with the message set for sizes the call would refuse.
+ *   crf_rnnt_workspace_bytes = al(16 R) + al(8 R) + al(8 R) + al(8 N + 4 (4 N + 1))
+ * -- per node four floats (the row's maximum M, log s = log sum_v exp(x_v - M), (x[blank] - M) - log s, (x[label] - M) - log s: the
+ * normaliser in two steps, as log_softmax takes it, so that a common offset of the logits costs no digits) and alpha and beta in fp64
+ * (eight floats; fp32 alpha / beta lose the gradient's fourth digit on long lattices), per utterance the total in fp64, two offsets and
+ * the two checked lengths.  It must be 16-byte aligned.  -1 with the message set for sizes the call would refuse.
  *
  * Errors, all answered before any HIP call: a null pointer (CRF_ERR_ARG), dtype outside 0..2, N, T, U1 or V < 1, blank outside [0, V),
  * rows outside [1, INT32_MAX], T U1 (padded) or compact_rows > INT32_MAX / 4, a misaligned workspace (CRF_ERR_ARG), U1 > 1024 or V > 8192 (CRF_ERR_UNSUPPORTED),

@@ -2,7 +2,8 @@
 three independent ones are written here and held to each other by tests/test_rnnt_api.py.
 
   (a) `lattice` / `ref_normalised` / `ref_logits`: the forward / backward recursion in numpy fp64 with the closed-form gradients, for
-      normalised log-probabilities and for raw joiner output (log_softmax's backward folded in);
+      normalised log-probabilities and for raw joiner output (log_softmax's backward folded in); `lattice_diag` is the same recursion a
+      whole anti-diagonal at a time, for the lattices of a million nodes that `lattice` would take a minute for;
   (b) `torch_cost`: the forward recursion in torch fp64 behind log_softmax, differentiated by autograd;
   (c) `brute_force`: every alignment enumerated (T <= 4, U <= 3).
 
@@ -44,6 +45,13 @@ def lattice(lb, ll):
             if u < U:
                 v = np.logaddexp(v, beta[t, u + 1] + ll[t, u])
             beta[t, u] = v
+    return _close(alpha, beta, lb, ll)
+
+
+def _close(alpha, beta, lb, ll):
+    """alpha [T, U+1] and beta [T+1, U+2] (beta[T][U] = 0, the rest of the last row and column -inf) -> (cost, d cost / d lb, d cost / d ll)."""
+    T, U1 = lb.shape
+    U = U1 - 1
     total = alpha[T - 1, U] + lb[T - 1, U]
     g_lb, g_ll = np.zeros((T, U1)), np.zeros((T, U))
     if not np.isfinite(total):
@@ -57,6 +65,42 @@ def lattice(lb, ll):
     return -total, g_lb, g_ll
 
 
+DIAG_FROM = 16384            # lattice nodes from which ref_normalised / ref_logits take lattice_diag (`lattice` needs a second there)
+
+
+def lattice_diag(lb, ll):
+    """`lattice` along the anti-diagonals d = t + u, a numpy operation per diagonal instead of a Python step per node: the same recursion,
+    the same logaddexp per node, for lattices of a million nodes (1024 x 1024 in under a second).  tests/test_rnnt_api.py holds it to
+    `lattice`."""
+    lb, ll = np.asarray(lb, dtype=np.float64), np.asarray(ll, dtype=np.float64)
+    T, U1 = lb.shape
+    U = U1 - 1
+    llp = np.full((T, U1), -np.inf)                   # no label behind the last one
+    llp[:, :U] = ll
+    alpha = np.full((T, U1), -np.inf)
+    beta = np.full((T + 1, U1 + 1), -np.inf)
+    alpha[0, 0] = 0.0
+    beta[T, U] = 0.0
+    for d in range(1, T + U):                         # alpha[t][u] from (t - 1, u) and (t, u - 1), both on diagonal d - 1
+        u = np.arange(max(0, d - T + 1), min(d, U) + 1)
+        t = d - u
+        tp, up = np.maximum(t - 1, 0), np.maximum(u - 1, 0)
+        stay = np.where(t > 0, alpha[tp, u] + lb[tp, u], -np.inf)
+        move = np.where(u > 0, alpha[t, up] + llp[t, up], -np.inf)
+        alpha[t, u] = np.logaddexp(stay, move)
+    for d in range(T + U - 1, -1, -1):                # beta[t][u] from (t + 1, u) and (t, u + 1), both on diagonal d + 1
+        u = np.arange(max(0, d - T + 1), min(d, U) + 1)
+        t = d - u
+        beta[t, u] = np.logaddexp(beta[t + 1, u] + lb[t, u], beta[t, u + 1] + llp[t, u])
+    return _close(alpha, beta, lb, ll)
+
+
+def _lattice(lb, ll, diag=None):
+    if diag is None:
+        diag = lb.size >= DIAG_FROM
+    return (lattice_diag if diag else lattice)(lb, ll)
+
+
 def _split(lp, labels, blank):
     T, U1, _ = lp.shape
     labels = np.asarray(labels, dtype=np.int64).reshape(-1)
@@ -66,12 +110,13 @@ def _split(lp, labels, blank):
     return lb, ll, labels
 
 
-def ref_normalised(log_probs, labels, blank=0):
-    """log_probs [T, U+1, V] (any real numbers: nothing normalises them).  -> (cost, d cost / d log_probs)."""
+def ref_normalised(log_probs, labels, blank=0, diag=None):
+    """log_probs [T, U+1, V] (any real numbers: nothing normalises them).  -> (cost, d cost / d log_probs).  diag: True = lattice_diag,
+    False = lattice, None = by the lattice's size (DIAG_FROM)."""
     lp = np.asarray(log_probs, dtype=np.float64)
     T, U1, _ = lp.shape
     lb, ll, labels = _split(lp, labels, blank)
-    cost, g_lb, g_ll = lattice(lb, ll)
+    cost, g_lb, g_ll = _lattice(lb, ll, diag)
     g = np.zeros_like(lp)
     g[:, :, blank] = g_lb
     for u in range(U1 - 1):
@@ -79,11 +124,11 @@ def ref_normalised(log_probs, labels, blank=0):
     return cost, g
 
 
-def ref_logits(x, labels, blank=0):
+def ref_logits(x, labels, blank=0, diag=None):
     """x [T, U+1, V] raw joiner output.  -> (cost of log_softmax(x), d cost / d x = g - softmax(x) * sum_v g)."""
     x = np.asarray(x, dtype=np.float64)
     lp = log_softmax(x)
-    cost, g = ref_normalised(lp, labels, blank)
+    cost, g = ref_normalised(lp, labels, blank, diag)
     with np.errstate(invalid="ignore"):
         sm = np.exp(lp)
     sm = np.where(np.isnan(sm), 0.0, sm)

@@ -81,6 +81,67 @@ def test_minus_infinity_entries():
     assert np.isfinite(cost) and np.isfinite(grad).all() and not grad[1, 1].any()
 
 
+def _same_by_diagonals(lp, labels, blank, logits=False):
+    """ref_normalised / ref_logits node by node (`lattice`) and by anti-diagonals (`lattice_diag`): the cost within 1e-12 relative, the
+    gradient within 1e-12 absolute.  -> (cost, grad) of the diagonal form."""
+    ref = rnnt_ref.ref_logits if logits else rnnt_ref.ref_normalised
+    cost, grad = ref(lp, labels, blank, diag=False)
+    dcost, dgrad = ref(lp, labels, blank, diag=True)
+    assert dcost == cost if np.isinf(cost) else abs(dcost - cost) <= 1e-12 * abs(cost), (cost, dcost)
+    assert np.isfinite(dgrad).all() and np.max(np.abs(dgrad - grad)) <= 1e-12
+    return dcost, dgrad
+
+
+@pytest.mark.parametrize("T,U1", [(1, 1), (1, 5), (5, 1), (7, 5), (70, 33)])
+def test_the_recursion_by_anti_diagonals_equals_the_one_node_by_node(T, U1):
+    x, labels = _rand(T * 100 + U1, T, U1 - 1, 5, 2)
+    _same_by_diagonals(rnnt_ref.log_softmax(x), labels, 2)
+    _same_by_diagonals(x, labels, 2, logits=True)
+    lb, ll = x[:, :, 2], x[:, :U1 - 1, 0]                            # the two functions themselves, on numbers nothing normalised
+    (cost, g_lb, g_ll), (dcost, dg_lb, dg_ll) = rnnt_ref.lattice(lb, ll), rnnt_ref.lattice_diag(lb, ll)
+    assert abs(dcost - cost) <= 1e-12 * abs(cost)
+    assert np.max(np.abs(dg_lb - g_lb)) <= 1e-12 and np.max(np.abs(dg_ll - g_ll), initial=0.0) <= 1e-12
+
+
+def test_the_recursion_by_anti_diagonals_with_minus_infinity_entries():
+    x, labels = _rand(5, 3, 2, 4, 0)
+    lp = rnnt_ref.log_softmax(x)
+    cut = lp.copy()
+    cut[2, 2, 0] = -np.inf                                           # the final blank: every path
+    cost, grad = _same_by_diagonals(cut, labels, 0)
+    assert cost == np.inf and not grad.any()
+    some = lp.copy()
+    some[0, 0, 0] = -np.inf                                          # the first blank: only the paths that start with it
+    cost, _ = _same_by_diagonals(some, labels, 0)
+    assert abs(cost - rnnt_ref.brute_force(some, labels, 0)) <= EPS * cost
+    raw = x.copy()
+    raw[1, 1, :] = -np.inf                                           # a whole row of the raw output
+    cost, grad = _same_by_diagonals(raw, labels, 0, logits=True)
+    assert np.isfinite(cost) and not grad[1, 1].any()
+    x, labels = _rand(6, 7, 5, 4, 1)                                 # no finite path: a column of labels and a frame of blanks cut
+    dead = rnnt_ref.log_softmax(x)
+    dead[:, 2, labels[2]] = -np.inf
+    cost, grad = _same_by_diagonals(dead, labels, 1)
+    assert cost == np.inf and not grad.any()
+    dead = rnnt_ref.log_softmax(x)
+    dead[3, :, 1] = -np.inf
+    cost, grad = _same_by_diagonals(dead, labels, 1)
+    assert cost == np.inf and not grad.any()
+
+
+def test_the_reference_goes_by_anti_diagonals_from_a_size_on(monkeypatch):
+    """Below DIAG_FROM nodes the node-by-node form, from there on the diagonal one: every size the GPU tests had before keeps its yardstick."""
+    assert 130 * 70 < rnnt_ref.DIAG_FROM <= 1000 * 200
+    calls = []
+    node, diag = rnnt_ref.lattice, rnnt_ref.lattice_diag
+    monkeypatch.setattr(rnnt_ref, "lattice", lambda lb, ll: calls.append("node") or node(lb, ll))
+    monkeypatch.setattr(rnnt_ref, "lattice_diag", lambda lb, ll: calls.append("diag") or diag(lb, ll))
+    z = np.zeros((rnnt_ref.DIAG_FROM // 4, 4, 2))
+    rnnt_ref.ref_normalised(z[:-1], [1, 1, 1], 0)
+    rnnt_ref.ref_normalised(z, [1, 1, 1], 0)
+    assert calls == ["node", "diag"]
+
+
 # ---- the surface ----
 def test_symbols_exported_and_surface(core):
     import ctc_crf
@@ -140,14 +201,14 @@ def test_workspace_formula(core):
     al = lambda n: (n + 255) // 256 * 256
     for N, T, U1, V, rows in ((1, 1, 1, 1, -1), (3, 7, 5, 9, -1), (16, 250, 51, 1024, -1), (5, 130, 70, 65, 389 * 37), (2, 9, 4, 8192, 40)):
         R = N * T * U1 if rows < 0 else rows
-        want = al(12 * R) + al(8 * R) + al(8 * R) + al(8 * N + 4 * (4 * N + 1))
+        want = al(16 * R) + al(8 * R) + al(8 * R) + al(8 * N + 4 * (4 * N + 1))
         assert core._lib.crf_rnnt_workspace_bytes(N, T, U1, V, rows) == want, (N, T, U1, V, rows)
         secs = core.debug_rnnt_ws_sections(N, T, U1, V, rows)
-        assert [s[0] for s in secs] == ["row", "alpha", "beta", "utt"] and [s[2] for s in secs] == [12 * R, 8 * R, 8 * R, 8 * N + 4 * (4 * N + 1)]
+        assert [s[0] for s in secs] == ["row", "alpha", "beta", "utt"] and [s[2] for s in secs] == [16 * R, 8 * R, 8 * R, 8 * N + 4 * (4 * N + 1)]
         assert secs[0][1] == 0 and all(b[1] == al(a[1] + a[2]) for a, b in zip(secs, secs[1:]))
     core.debug_set("ws_gap", 2)
     try:
-        assert core._lib.crf_rnnt_workspace_bytes(3, 7, 5, 9, -1) == al(12 * 105) + al(8 * 105) * 2 + al(8 * 3 + 4 * 13) + 4 * 512
+        assert core._lib.crf_rnnt_workspace_bytes(3, 7, 5, 9, -1) == al(16 * 105) + al(8 * 105) * 2 + al(8 * 3 + 4 * 13) + 4 * 512
     finally:
         core.debug_set("ws_gap", None)
     for bad in ((0, 1, 1, 1, -1), (1, 1, 1025, 1, -1), (1, 1, 1, 8193, -1), (1, 1, 1, 1, 0)):
