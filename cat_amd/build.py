@@ -19,7 +19,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-FAMILIES = ["k_fac_768.hip", "k_fac_pair2.hip", "k_fac_1024.hip", "k_batch.hip", "k_grad.hip", "k_res.hip", "k_chain.hip", "k_robust.hip", "k_align.hip", "k_score.hip", "k_score_grad.hip", "k_rows.hip", "k_sample.hip", "k_beam.hip", "k_beam_lm.hip", "k_beam_chunk.hip", "k_edit.hip", "k_ngram.hip", "k_rnnt.hip"]   # slowest first
+FAMILIES = ["k_fac_768.hip", "k_fac_pair2.hip", "k_fac_1024.hip", "k_batch.hip", "k_grad.hip", "k_res.hip", "k_chain.hip", "k_robust.hip", "k_align.hip", "k_score.hip", "k_score_grad.hip", "k_rows.hip", "k_sample.hip", "k_beam.hip", "k_beam_lm.hip", "k_beam_chunk.hip", "k_edit.hip", "k_ngram.hip", "k_rnnt.hip", "k_rnnt_join.hip"]   # slowest first
 GRAPH_UNITS = ["res_layout.cpp", "graph_compile.cpp", "arc_streams.cpp", "fst_read.cpp", "crf_opts.cpp", "stage_plan.cpp"]   # host C++ only: no kernels
 UNITS = FAMILIES + ["crf_host.hip", "crf_host_ctc.hip"] + GRAPH_UNITS + ["ctc_api.cpp"]
 MAX_JOBS = 16

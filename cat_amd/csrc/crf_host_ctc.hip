@@ -649,6 +649,73 @@ static int rnnt_grad_call(const char *who, const void *x, int dtype, int blank, 
     return with_dtype(dtype, [&](auto e) { return launch<crf_rnnt_grad_kernel<decltype(e), true>>("crf_rnnt_grad_kernel", wgrid, wblock, 0, st, p); });
 }
 
+// ---- the RNN-T loss of a joiner that is a plain sum f + g (k_rnnt_join.hip) ----
+// Its workspace: the padded one of crf_rnnt_loss, then df [N][T][V] and dg [kJoinSplit][N][U1][V] in fp32 -- nothing proportional to T U1 V.
+enum JoinWs { kJnDf = kRtCount, kJnDg, kJnCount };
+static const char *const kJoinWsNames[kJnCount] = {"row", "alpha", "beta", "utt", "df", "dg"};
+static int64_t join_ws_bytes(int64_t N, int64_t T, int64_t U1, int64_t V, SideWs *out = nullptr) {
+    SideWs w;
+    const int64_t base = rnnt_ws_bytes(N, T, U1, V, -1, &w);
+    if (base < 0) return base;
+    w.add(kJoinWsNames[kJnDf], N * T * V * (int64_t)sizeof(float)).add(kJoinWsNames[kJnDg], kJoinSplit * N * U1 * V * (int64_t)sizeof(float));
+    if (out) *out = w;
+    return w.total;
+}
+// the checks both calls share, in the order of include/ctc_crf_hip.h, and the kernels' arguments; no HIP call
+static int join_setup(const char *who_, const void *f, const void *g, int dtype, int blank, const int32_t *labels, const int32_t *lx, const int32_t *ly,
+                      int64_t N, int64_t T, int64_t U1, int64_t V, const void *out, const void *ws, int64_t ws_bytes, JoinParams &q) {
+    const std::string who = who_;
+    if (!f || !g || !labels || !lx || !ly || !out || !ws) { set_error(who + ": null argument"); return CRF_ERR_ARG; }
+    if (dtype < 0 || dtype > 2) return bad_dtype(who_);
+    SideWs w;
+    const int64_t need = join_ws_bytes(N, T, U1, V, &w);
+    if (need < 0) return (int)-need;
+    if (const int rc = check_blank(blank, V)) return rc;
+    if ((uintptr_t)ws & 15) { set_error(who + ": the workspace must be 16-byte aligned"); return CRF_ERR_ARG; }
+    if (const int rc = check_ws(ws_bytes, need)) return rc;
+    q = JoinParams{};
+    RnntParams &p = q.r;
+    p.labels = labels; p.lx = lx; p.ly = ly;
+    p.N = (int)N; p.T = (int)T; p.U1 = (int)U1; p.V = (int)V; p.blank = blank; p.compact = 0;
+    p.R = N * T * U1; p.nlab = N * (U1 - 1);
+    char *b = (char *)ws;
+    p.row = (float *)(b + w.sec[kRtRow].off); p.alpha = (double *)(b + w.sec[kRtAlpha].off); p.beta = (double *)(b + w.sec[kRtBeta].off);
+    p.total = (double *)(b + w.sec[kRtUtt].off);
+    p.node_off = (int *)(p.total + N); p.lab_off = p.node_off + N + 1; p.tn = p.lab_off + N; p.un = p.tn + N;
+    q.f = f; q.g = g;
+    q.df_part = (float *)(b + w.sec[kJnDf].off); q.dg_part = (float *)(b + w.sec[kJnDg].off);
+    return CRF_OK;
+}
+// the forward: crf_rnnt_loss's prep and lattice launches around the join row stage
+static int join_loss_call(const char *who, const void *f, const void *g, int dtype, int blank, const int32_t *labels, const int32_t *lx, const int32_t *ly,
+                          int64_t N, int64_t T, int64_t U1, int64_t V, float *cost, int32_t *invalid, void *ws, int64_t ws_bytes, hipStream_t st) {
+    JoinParams q;
+    if (const int rc = join_setup(who, f, g, dtype, blank, labels, lx, ly, N, T, U1, V, cost, ws, ws_bytes, q)) return rc;
+    q.r.cost = cost; q.r.invalid = invalid;
+    if (const int rc = launch<crf_rnnt_prep_kernel>("crf_rnnt_prep_kernel", dim3(1), dim3(kRnntPrepThreads), 0, st, q.r)) return rc;
+    const dim3 rgrid((unsigned)(N * ((T + kJoinTT - 1) / kJoinTT)), (unsigned)((U1 + kJoinTU - 1) / kJoinTU));
+    if (const int rc = with_dtype(dtype, [&](auto e) { return launch<crf_join_row_kernel<decltype(e)>>("crf_join_row_kernel", rgrid, dim3(kJoinRowThreads), 0, st, q); }))
+        return rc;
+    const dim3 lgrid((unsigned)N, 2);
+    if (U1 <= 64) return launch<crf_rnnt_lattice_kernel<false>>("crf_rnnt_lattice_kernel<wave>", lgrid, dim3(64), 0, st, q.r);
+    return launch<crf_rnnt_lattice_kernel<true>>("crf_rnnt_lattice_kernel<workgroup>", lgrid, dim3((unsigned)rup64((int)U1)), 0, st, q.r);
+}
+// the backward on the forward's workspace: the partial sums, then every element of the gradients asked for
+static int join_grad_call(const char *who, const void *f, const void *g, int dtype, int blank, const int32_t *labels, const int32_t *lx, const int32_t *ly,
+                          int64_t N, int64_t T, int64_t U1, int64_t V, const float *weight, void *grad_f, void *grad_g, void *ws, int64_t ws_bytes,
+                          hipStream_t st) {
+    JoinParams q;
+    if (!weight) { set_error(std::string(who) + ": null argument"); return CRF_ERR_ARG; }
+    if (const int rc = join_setup(who, f, g, dtype, blank, labels, lx, ly, N, T, U1, V, weight, ws, ws_bytes, q)) return rc;
+    if (!grad_f && !grad_g) return CRF_OK;
+    q.r.weight = weight; q.grad_f = grad_f; q.grad_g = grad_g;
+    const dim3 ggrid((unsigned)(N * ((V + kJoinGV - 1) / kJoinGV)), kJoinSplit), fgrid((unsigned)(N * std::max(T, U1)), 2);
+    return with_dtype(dtype, [&](auto e) {
+        if (const int rc = launch<crf_join_grad_kernel<decltype(e)>>("crf_join_grad_kernel", ggrid, dim3(kJoinGV), 0, st, q)) return rc;
+        return launch<crf_join_fold_kernel<decltype(e)>>("crf_join_fold_kernel", fgrid, dim3(256), 0, st, q);
+    });
+}
+
 }  // namespace crf
 
 using namespace crf;
@@ -961,6 +1028,27 @@ int crf_rnnt_grad_logits(const void *logits, int dtype, int blank, const int32_t
     if (dtype < 0) return bad_dtype("crf_rnnt_grad_logits");
     return rnnt_grad_call("crf_rnnt_grad_logits", logits, dtype, blank, labels, lx, ly, N, T, U1, V, compact_rows, compact_labels, grad_output, grad, ws,
                           ws_bytes, (hipStream_t)stream_);
+}
+
+int64_t crf_rnnt_simple_workspace_bytes(int64_t N, int64_t T, int64_t U1, int64_t V) { return or_minus1(join_ws_bytes(N, T, U1, V)); }
+int crf_debug_rnnt_simple_ws_sections(int64_t N, int64_t T, int64_t U1, int64_t V, int64_t *out, int n_out) {
+    SideWs w;
+    if (join_ws_bytes(N, T, U1, V, &w) < 0) return -1;
+    return copy_sections(w.sec, w.nsec, out, n_out);
+}
+const char *crf_debug_rnnt_simple_ws_section_names(void) {
+    static const std::string s = join_names(kJoinWsNames, kJnCount);
+    return s.c_str();
+}
+int crf_rnnt_simple_loss(const void *f, const void *g, int dtype, int blank, const int32_t *labels, const int32_t *lx, const int32_t *ly, int64_t N,
+                         int64_t T, int64_t U1, int64_t V, float *cost, int32_t *invalid, void *ws, int64_t ws_bytes, void *stream_) {
+    return join_loss_call("crf_rnnt_simple_loss", f, g, dtype, blank, labels, lx, ly, N, T, U1, V, cost, invalid, ws, ws_bytes, (hipStream_t)stream_);
+}
+int crf_rnnt_simple_grad(const void *f, const void *g, int dtype, int blank, const int32_t *labels, const int32_t *lx, const int32_t *ly, int64_t N,
+                         int64_t T, int64_t U1, int64_t V, const float *grad_output, void *grad_f, void *grad_g, void *ws, int64_t ws_bytes,
+                         void *stream_) {
+    return join_grad_call("crf_rnnt_simple_grad", f, g, dtype, blank, labels, lx, ly, N, T, U1, V, grad_output, grad_f, grad_g, ws, ws_bytes,
+                          (hipStream_t)stream_);
 }
 
 const char *crf_last_ngram_score_kernel(void) { return g_ngram_kernel; }

@@ -258,6 +258,27 @@ template <typename E> __global__ void crf_rnnt_row_kernel(RnntParams p);        
 template <bool WG> __global__ void crf_rnnt_lattice_kernel(RnntParams p);          // grid (N, 2); WG: U1 > 64, rup64(U1) threads
 template <typename E, bool RAW> __global__ void crf_rnnt_grad_kernel(RnntParams p); // a wave per row of grad
 
+// ---- k_rnnt_join.hip ----
+constexpr int kJoinRowThreads = 256;      // row stage: a 16 x 16 grid of threads, 2 x 2 nodes each ...
+constexpr int kJoinTT = 32;               // ... over kJoinTT frames x kJoinTU rows of one utterance,
+constexpr int kJoinTU = 32;
+constexpr int kJoinVC = 128;              // columns of the tile's f and g rows staged in LDS at a time (fp32: 2 x 32 x (128 + 4) x 4 bytes)
+constexpr int kJoinGV = 256;              // grad stage: class columns (threads) per workgroup,
+constexpr int kJoinGU = 32;               // lattice rows whose g and d g a thread holds in registers at a time,
+constexpr int kJoinGL = 16;               // frames per chunk: the nodes' scalars of kJoinGL x kJoinGU nodes are formed once per workgroup,
+constexpr int kJoinSplit = 4;             // partial sums of d g over the frames: split s takes the chunks s, s + kJoinSplit, ...
+// Kernel arguments of crf_rnnt_simple_loss / crf_rnnt_simple_grad: the padded RnntParams (x unused, grad unused) and the joiner's two inputs.
+struct JoinParams {
+    RnntParams r;
+    const void *f, *g;          // [N][T][V] and [N][U1][V] in one element type, raw
+    float *df_part;             // [N][T][V] d f of the live rows (crf_rnnt_simple_grad)
+    float *dg_part;             // [kJoinSplit][N][U1][V] partial d g of the live rows and splits
+    void *grad_f, *grad_g;      // like f and g, either may be null
+};
+template <typename E> __global__ void crf_join_row_kernel(JoinParams q);          // grid (N ceil(T / kJoinTT), ceil(U1 / kJoinTU))
+template <typename E> __global__ void crf_join_grad_kernel(JoinParams q);         // grid (N ceil(V / kJoinGV), kJoinSplit)
+template <typename E> __global__ void crf_join_fold_kernel(JoinParams q);         // grid (N max(T, U1), 2): a workgroup per row of d f / d g
+
 // ---- k_edit.hip ----
 constexpr int kEditWaves = 4;            // hypotheses (waves) per workgroup of the register geometry
 constexpr int kEditStripRows = 512;       // reference rows one wave holds (64 lanes x 8): longer references are walked in strips of this many

@@ -9,7 +9,7 @@ import os
 import sys
 import threading
 import warnings
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -138,6 +138,15 @@ _lib.crf_rnnt_grad_logits.restype = ctypes.c_int
 _lib.crf_debug_rnnt_ws_sections.argtypes = [_i64, _i64, _i64, _i64, _i64, ctypes.POINTER(_i64), ctypes.c_int]
 _lib.crf_debug_rnnt_ws_sections.restype = ctypes.c_int
 _lib.crf_debug_rnnt_ws_section_names.restype = ctypes.c_char_p
+_lib.crf_rnnt_simple_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64]
+_lib.crf_rnnt_simple_workspace_bytes.restype = _i64
+_lib.crf_rnnt_simple_loss.argtypes = [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp]
+_lib.crf_rnnt_simple_loss.restype = ctypes.c_int
+_lib.crf_rnnt_simple_grad.argtypes = [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]
+_lib.crf_rnnt_simple_grad.restype = ctypes.c_int
+_lib.crf_debug_rnnt_simple_ws_sections.argtypes = [_i64, _i64, _i64, _i64, ctypes.POINTER(_i64), ctypes.c_int]
+_lib.crf_debug_rnnt_simple_ws_sections.restype = ctypes.c_int
+_lib.crf_debug_rnnt_simple_ws_section_names.restype = ctypes.c_char_p
 _lib.crf_profile_enable.argtypes = [ctypes.c_int]
 _lib.crf_profile_enable.restype = None
 _lib.crf_profile_read.argtypes = [ctypes.POINTER(_f32), ctypes.c_int]
@@ -162,7 +171,7 @@ _lib.crf_build_switches.restype = ctypes.c_char_p
 
 EXPORTED_SYMBOLS = (
     "crf_graph_create", "crf_graph_create_from_arcs", "crf_graph_destroy", "crf_graph_dims", "crf_graph_stats",
-    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_ws_fields", "crf_debug_ws_field_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_ctc_score", "crf_ctc_score_logits_workspace_bytes", "crf_ctc_score_logits", "crf_last_score_kernel", "crf_ctc_score_grad_workspace_bytes", "crf_ctc_score_grad", "crf_ctc_score_grad_logits_workspace_bytes", "crf_ctc_score_grad_logits", "crf_last_score_grad_kernel", "crf_ctc_score_rows_workspace_bytes", "crf_ctc_score_rows", "crf_ctc_score_grad_rows_workspace_bytes", "crf_ctc_score_grad_rows", "crf_debug_score_rows_ws_sections", "crf_debug_score_rows_ws_section_names", "crf_ctc_sample_workspace_bytes", "crf_ctc_sample", "crf_last_sample_kernel", "crf_ctc_beam_workspace_bytes", "crf_ctc_beam", "crf_last_beam_kernel", "crf_ngram_tables_check", "crf_ctc_beam_lm_workspace_bytes", "crf_ctc_beam_lm", "crf_ctc_beam_state_record_bytes", "crf_ctc_beam_chunk_workspace_bytes", "crf_ctc_beam_chunk", "crf_ctc_edit_distance", "crf_last_edit_kernel", "crf_ngram_score", "crf_last_ngram_score_kernel", "crf_rnnt_workspace_bytes", "crf_rnnt_loss", "crf_rnnt_loss_logits", "crf_rnnt_grad", "crf_rnnt_grad_logits", "crf_debug_rnnt_ws_sections", "crf_debug_rnnt_ws_section_names", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
+    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_ws_fields", "crf_debug_ws_field_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_ctc_score", "crf_ctc_score_logits_workspace_bytes", "crf_ctc_score_logits", "crf_last_score_kernel", "crf_ctc_score_grad_workspace_bytes", "crf_ctc_score_grad", "crf_ctc_score_grad_logits_workspace_bytes", "crf_ctc_score_grad_logits", "crf_last_score_grad_kernel", "crf_ctc_score_rows_workspace_bytes", "crf_ctc_score_rows", "crf_ctc_score_grad_rows_workspace_bytes", "crf_ctc_score_grad_rows", "crf_debug_score_rows_ws_sections", "crf_debug_score_rows_ws_section_names", "crf_ctc_sample_workspace_bytes", "crf_ctc_sample", "crf_last_sample_kernel", "crf_ctc_beam_workspace_bytes", "crf_ctc_beam", "crf_last_beam_kernel", "crf_ngram_tables_check", "crf_ctc_beam_lm_workspace_bytes", "crf_ctc_beam_lm", "crf_ctc_beam_state_record_bytes", "crf_ctc_beam_chunk_workspace_bytes", "crf_ctc_beam_chunk", "crf_ctc_edit_distance", "crf_last_edit_kernel", "crf_ngram_score", "crf_last_ngram_score_kernel", "crf_rnnt_workspace_bytes", "crf_rnnt_loss", "crf_rnnt_loss_logits", "crf_rnnt_grad", "crf_rnnt_grad_logits", "crf_debug_rnnt_ws_sections", "crf_debug_rnnt_ws_section_names", "crf_rnnt_simple_workspace_bytes", "crf_rnnt_simple_loss", "crf_rnnt_simple_grad", "crf_debug_rnnt_simple_ws_sections", "crf_debug_rnnt_simple_ws_section_names", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
     "crf_debug_set", "crf_debug_unset", "crf_debug_list", "crf_last_den_kernel", "crf_last_call_streams", "crf_last_side_stream", "crf_last_fallback_counts", "crf_build_switches", "crf_last_error", "crf_version",
 )
 
@@ -456,6 +465,16 @@ def debug_rnnt_ws_sections(N: int, T: int, U1: int, V: int, compact_rows: int = 
     names = _lib.crf_debug_rnnt_ws_section_names().decode().split(",")
     out = (_i64 * (2 * len(names)))()
     n = _lib.crf_debug_rnnt_ws_sections(N, T, U1, V, compact_rows, out, len(out))
+    if n < 0:
+        _check(1)
+    return [(names[k], int(out[2 * k]), int(out[2 * k + 1])) for k in range(n)]
+
+
+def debug_rnnt_simple_ws_sections(N: int, T: int, U1: int, V: int):
+    """The same for the workspace of crf_rnnt_simple_loss / crf_rnnt_simple_grad."""
+    names = _lib.crf_debug_rnnt_simple_ws_section_names().decode().split(",")
+    out = (_i64 * (2 * len(names)))()
+    n = _lib.crf_debug_rnnt_simple_ws_sections(N, T, U1, V, out, len(out))
     if n < 0:
         _check(1)
     return [(names[k], int(out[2 * k]), int(out[2 * k + 1])) for k in range(n)]
@@ -1635,6 +1654,105 @@ def rnnt_loss_bwd(call: RnntCall, grad_output: torch.Tensor, grad_out: Optional[
         rc = _lib.crf_rnnt_grad_logits(_ptr(c.x), _FUSED_DTYPES[c.x.dtype], *tail) if c.fused else _lib.crf_rnnt_grad(_ptr(c.x), *tail)
     _check(rc)
     return grad
+
+
+class RnntSimpleCall:
+    """What rnnt_simple_fwd leaves for rnnt_simple_bwd: the C call's arguments (the staged tensors are kept alive here) and the workspace."""
+
+    def __init__(self, f, g, blank, labels, lx, ly, N, T, U1, V, ws):
+        self.f, self.g, self.blank, self.labels, self.lx, self.ly = f, g, blank, labels, lx, ly
+        self.N, self.T, self.U1, self.V, self.ws = N, T, U1, V, ws
+
+
+def _check_rnnt_simple_args(f: torch.Tensor, g: torch.Tensor, labels: torch.Tensor, lx: torch.Tensor, ly: torch.Tensor, blank: int):
+    """The host checks of rnnt_loss_simple, each with the offending value in the message; none needs a device.  -> (N, T, U1, V)."""
+    who = "rnnt_loss_simple"
+    if f.dtype != g.dtype or f.dtype not in _FUSED_DTYPES:
+        raise ValueError(f"{who}: f_enc and g_pred must be of one dtype among float32, bfloat16 and float16, got {f.dtype} and {g.dtype}")
+    if f.dim() != 3 or g.dim() != 3:
+        raise ValueError(f"{who}: expect f_enc (N, T, V) and g_pred (N, U+1, V), got {tuple(f.shape)} and {tuple(g.shape)}")
+    if f.shape[0] != g.shape[0]:
+        raise ValueError(f"{who}: f_enc has {f.shape[0]} utterances, g_pred {g.shape[0]}")
+    if f.shape[2] != g.shape[2]:
+        raise ValueError(f"{who}: f_enc has {f.shape[2]} classes, g_pred {g.shape[2]}")
+    if not f.is_contiguous() or not g.is_contiguous():
+        raise ValueError(f"{who}: f_enc and g_pred must be contiguous (they are read in place)")
+    N, T, V = f.shape
+    U1 = g.shape[1]
+    if labels.dtype != torch.int32 or lx.dtype != torch.int32 or ly.dtype != torch.int32:
+        raise RuntimeError(f"{who}: labels, frames_lengths and labels_lengths must be int32, got {labels.dtype}, {lx.dtype}, {ly.dtype}")
+    if lx.dim() != 1 or ly.dim() != 1 or lx.numel() != N or ly.numel() != N or N == 0:
+        raise ValueError(f"{who}: expect frames_lengths and labels_lengths as (N={N},) with N >= 1, got {tuple(lx.shape)} and {tuple(ly.shape)}")
+    if T < 1 or U1 < 1:
+        raise ValueError(f"{who}: empty lattice: f_enc {tuple(f.shape)}, g_pred {tuple(g.shape)}")
+    if not 1 <= V <= RNNT_MAX_VOCAB:
+        raise ValueError(f"{who}: V = {V} outside [1, {RNNT_MAX_VOCAB}] not supported by this build")
+    if U1 - 1 > RNNT_MAX_LABELS:
+        raise ValueError(f"{who}: U = {U1 - 1} > {RNNT_MAX_LABELS} not supported by this build")
+    if not 0 <= blank < V:
+        raise ValueError(f"{who}: blank must lie in [0, V-1={V - 1}], got {blank}")
+    if tuple(labels.shape) != (N, U1 - 1):
+        raise ValueError(f"{who}: expect labels (N={N}, U={U1 - 1}), got {tuple(labels.shape)}")
+    if lx.is_cuda != ly.is_cuda:
+        raise RuntimeError(f"{who}: frames_lengths and labels_lengths must both be on the CPU or both on the GPU")
+    if not lx.is_cuda:
+        if int(lx.min()) < 1 or int(lx.max()) > T:
+            raise ValueError(f"{who}: frames_lengths must lie in [1, T={T}], got [{int(lx.min())}, {int(lx.max())}]")
+        if int(ly.min()) < 0 or int(ly.max()) > U1 - 1:
+            raise ValueError(f"{who}: labels_lengths must lie in [0, U={U1 - 1}], got [{int(ly.min())}, {int(ly.max())}]")
+    return N, T, U1, V
+
+
+def rnnt_simple_fwd(f: torch.Tensor, g: torch.Tensor, labels: torch.Tensor, lx: torch.Tensor, ly: torch.Tensor, blank: int = 0):
+    """The forward of the RNN-T loss of the joiner f + g (include/ctc_crf_hip.h ``crf_rnnt_simple_loss``) -> (costs [N] f32, invalid [N]
+    int32, RnntSimpleCall for rnnt_simple_bwd) on the device, without a host synchronisation when the lengths are on the device.  f and g
+    are read in place: nothing of size T (U + 1) V is allocated."""
+    N, T, U1, V = _check_rnnt_simple_args(f, g, labels, lx, ly, blank)
+    if not f.is_cuda or g.device != f.device:
+        raise RuntimeError("rnnt_loss_simple: f_enc and g_pred must be on one GPU (there is no CPU path)")
+    dev = f.device
+    f, g = f.detach(), g.detach()
+    lab_d = labels.to(dev).contiguous() if labels.numel() else torch.zeros(1, dtype=torch.int32, device=dev)   # (no NULL in the C ABI)
+    if lx.is_cuda:
+        lx_d, ly_d = lx.contiguous(), ly.contiguous()
+    else:
+        meta = _h2d_async(torch.cat([lx, ly]), dev)
+        lx_d, ly_d = meta[:N], meta[N:]
+    costs = torch.empty(N, dtype=torch.float32, device=dev)
+    invalid = torch.empty(N, dtype=torch.int32, device=dev)
+    ws = _new_ws(_lib.crf_rnnt_simple_workspace_bytes(N, T, U1, V), dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        rc = _lib.crf_rnnt_simple_loss(_ptr(f), _ptr(g), _FUSED_DTYPES[f.dtype], blank, _ptr(lab_d), _ptr(lx_d), _ptr(ly_d), N, T, U1, V,
+                                       _ptr(costs), _ptr(invalid), _ptr(ws), ws.numel(), _vp(stream))
+    _check(rc)
+    return costs, invalid, RnntSimpleCall(f, g, blank, lab_d, lx_d, ly_d, N, T, U1, V, ws)
+
+
+def rnnt_simple_bwd(call: RnntSimpleCall, grad_output: torch.Tensor, want_f: bool = True, want_g: bool = True,
+                    grad_out: Optional[Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]] = None):
+    """The backward on the forward's workspace (``crf_rnnt_simple_grad``): grad_output [N] is d loss / d costs; returns (grad_f, grad_g) in
+    the inputs' shapes and dtype, every element written by the kernels, None where want_f / want_g is false (that gradient is not formed).
+    grad_out: a pair of contiguous tensors of those shapes and that dtype to write into, whatever they hold."""
+    c = call
+    dev = c.f.device
+    w = grad_output.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if w.numel() != c.N:
+        raise RuntimeError(f"rnnt_loss_simple: expect grad_output ({c.N},), got {tuple(grad_output.shape)}")
+    outs = []
+    for k, (want, like) in enumerate(((want_f, c.f), (want_g, c.g))):
+        t = None
+        if want:
+            t = grad_out[k] if grad_out is not None and grad_out[k] is not None else torch.empty_like(like)
+            if t.shape != like.shape or t.dtype != like.dtype or t.device != dev or not t.is_contiguous():
+                raise RuntimeError("rnnt_loss_simple: grad_out must be contiguous, of the inputs' shapes and dtype and on their device")
+        outs.append(t)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        rc = _lib.crf_rnnt_simple_grad(_ptr(c.f), _ptr(c.g), _FUSED_DTYPES[c.f.dtype], c.blank, _ptr(c.labels), _ptr(c.lx), _ptr(c.ly), c.N, c.T,
+                                       c.U1, c.V, _ptr(w), _ptr(outs[0]), _ptr(outs[1]), _ptr(c.ws), c.ws.numel(), _vp(stream))
+    _check(rc)
+    return outs[0], outs[1]
 
 
 def gpu_den(logits: torch.Tensor, grad_net: torch.Tensor, input_lengths: torch.Tensor,

@@ -43,6 +43,10 @@ Same names, arguments and error behaviour as the reference:
             fuse_log_softmax=False) -> costs                                             (warp_rnnt.rnnt_loss: the RNN-T transducer loss with
                                                                                          autograd, padded or compact joiner output, normalised
                                                                                          or raw; the top-level package warp_rnnt re-exports it)
+  rnnt_loss_simple(f_enc, g_pred, labels, frames_lengths, labels_lengths, average_frames=False, reduction=None, blank=0) -> costs
+                                                                                         (warp_rnnt.rnnt_loss_simple: the same loss of the joiner
+                                                                                         f + g from f (N, T, V) and g (N, U+1, V) alone, the
+                                                                                         (N, T, U+1, V) tensor never formed; re-exported likewise)
 plus the functional form named by BASELINE.json:
   ctc_crf_loss(log_probs, labels, frame_lens, label_lens, den_lm, lamb=0.1, size_average=True)
 
@@ -652,11 +656,63 @@ def rnnt_loss(log_probs: torch.Tensor, labels: torch.Tensor, frames_lengths: tor
     Invalid utterances (T_n outside [1, T], U_n outside [0, U], a label outside [0, V) or equal to blank) are decided on the device: cost
     +inf and a zero gradient, as for ctc_score's rows over their bound; return_invalid=True returns (costs, invalid IntTensor[N]).  A
     lattice without a finite path (-inf entries) also costs +inf with a zero gradient, never NaN.  U <= 1023, V <= 8192.
-    Not covered: gather=True as a separate mode (the kernels read two columns of a normalised row anyway), fastemit_lambda,
-    rnnt_loss_simple, any RNN-T decoding."""
+    Not covered: gather=True as a separate mode (the kernels read two columns of a normalised row anyway), fastemit_lambda, any RNN-T
+    decoding.  A joiner that is a plain sum f + g has rnnt_loss_simple below, which never forms the (N, T, U+1, V) tensor."""
     if reduction not in (None, "none", "mean", "sum"):
         raise ValueError(f"rnnt_loss: unknown reduction {reduction!r} (None, 'none', 'mean' or 'sum')")
     costs, invalid = _RNNT_LOSS.apply(log_probs, labels, frames_lengths, labels_lengths, int(blank), bool(compact), bool(fuse_log_softmax))
+    if average_frames:
+        costs = costs / frames_lengths.to(device=costs.device, dtype=costs.dtype)
+    if reduction == "sum":
+        costs = costs.sum()
+    elif reduction == "mean":
+        costs = costs.mean()
+    return (costs, invalid) if return_invalid else costs
+
+
+class _RNNT_LOSS_SIMPLE(Function):
+    """costs [N] = crf_rnnt_simple_loss; backward = ONE crf_rnnt_simple_grad call on the forward's workspace with grad_output as the
+    per-utterance weights.  Each gradient has its input's shape and dtype and is formed only where needs_input_grad asks; the kernels write
+    every element."""
+
+    @staticmethod
+    def forward(ctx, f_enc, g_pred, labels, lx, ly, blank):
+        costs, invalid, call = core.rnnt_simple_fwd(f_enc, g_pred, labels, lx, ly, blank)
+        ctx.call = call
+        ctx.mark_non_differentiable(invalid)
+        return costs, invalid
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_costs, _grad_invalid):
+        want_f, want_g = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gf, gg = core.rnnt_simple_bwd(ctx.call, grad_costs, want_f, want_g) if want_f or want_g else (None, None)
+        return gf, gg, None, None, None, None
+
+
+def rnnt_loss_simple(f_enc: torch.Tensor, g_pred: torch.Tensor, labels: torch.Tensor, frames_lengths: torch.Tensor,
+                     labels_lengths: torch.Tensor, average_frames: bool = False, reduction: str = None, blank: int = 0,
+                     return_invalid: bool = False):
+    """The RNN-T transducer loss of a joiner that is a plain sum, with autograd, with the arguments of ``warp_rnnt.rnnt_loss_simple``
+    (cat/rnnt/train.py:206-213 calls it as rnnt_loss_simple(enc_out, pred_out, y, lsub, ly) for every model whose joiner is
+    joiner_zoo.LogAdd, cat/rnnt/joiner.py:231-232):
+
+        rnnt_loss_simple(f, g, labels, lf, ll, ...) == rnnt_loss((f.unsqueeze(2) + g.unsqueeze(1)).log_softmax(-1), labels, lf, ll, ...)
+
+    computed from f and g alone: the (N, T, U+1, V) tensor is never formed, nothing of that size is allocated, and the gradients are those
+    of the expression above with respect to f and g.
+
+    f_enc (N, T, V), g_pred (N, U+1, V): raw, unnormalised, contiguous, of one dtype among float32, bfloat16 and float16, on the GPU, read
+        in place; f + g is formed in float32 from their exact values.  Each gradient comes back in the input's dtype, every element
+        written by the kernels (zeros for t >= T_n and u > U_n), and only where autograd asks for it.
+    labels: int32 (N, U).  frames_lengths, labels_lengths: int32 (N,), both on the CPU (checked up front: ValueError) or both on the GPU
+        (nothing is read on the host and nothing synchronises).  average_frames, reduction, blank, return_invalid, invalid utterances
+        (cost +inf, zero gradient, invalid = 1) and lattices without a finite path (+inf, zero gradient, never NaN): as for rnnt_loss.
+    Mismatched dtypes, vocabulary sizes or batch sizes and non-contiguous inputs raise ValueError.  U <= 1023, V <= 8192.
+    The same bits run to run, and for an utterance alone or anywhere in a batch."""
+    if reduction not in (None, "none", "mean", "sum"):
+        raise ValueError(f"rnnt_loss_simple: unknown reduction {reduction!r} (None, 'none', 'mean' or 'sum')")
+    costs, invalid = _RNNT_LOSS_SIMPLE.apply(f_enc, g_pred, labels, frames_lengths, labels_lengths, int(blank))
     if average_frames:
         costs = costs / frames_lengths.to(device=costs.device, dtype=costs.dtype)
     if reduction == "sum":

@@ -638,7 +638,7 @@ const char *crf_last_ngram_score_kernel(void);
  * rows outside [1, INT32_MAX], T U1 (padded) or compact_rows > INT32_MAX / 4, a misaligned workspace (CRF_ERR_ARG), U1 > 1024 or V > 8192 (CRF_ERR_UNSUPPORTED),
  * a workspace that is too small (CRF_ERR_WORKSPACE).  One stream, no host synchronisation, no environment variable.
  * Not covered: warp_rnnt's gather mode as a separate entry (the kernels read two columns of a normalised row anyway), fastemit_lambda,
- * rnnt_loss_simple, any RNN-T decoding. */
+ * any RNN-T decoding.  rnnt_loss_simple is crf_rnnt_simple_loss below. */
 int64_t crf_rnnt_workspace_bytes(int64_t N, int64_t T, int64_t U1, int64_t V, int64_t compact_rows);
 int crf_rnnt_loss(const float *log_probs_dev, int blank, const int32_t *labels_dev, const int32_t *lx_dev, const int32_t *ly_dev, int64_t N,
                   int64_t T, int64_t U1, int64_t V, int64_t compact_rows, int64_t compact_labels, float *cost_dev, int32_t *invalid_dev,
@@ -656,6 +656,30 @@ int crf_rnnt_grad_logits(const void *logits_dev, int dtype, int blank, const int
  * n x 256 untouched bytes follow every section.  Returns the number of sections, -1 for sizes the call would refuse. */
 int crf_debug_rnnt_ws_sections(int64_t N, int64_t T, int64_t U1, int64_t V, int64_t compact_rows, int64_t *out, int n_out);
 const char *crf_debug_rnnt_ws_section_names(void);
+
+/* The same loss for a joiner that is a plain sum (cat/rnnt/joiner.py:231-232 LogAdd; cat/rnnt/train.py:206-213 calls it as
+ * warp_rnnt.rnnt_loss_simple(enc_out, pred_out, y, lsub, ly)):
+ *   crf_rnnt_simple_loss(f, g, ...) == crf_rnnt_loss_logits(f[:, :, None, :] + g[:, None, :, :], ...)
+ * from f_dev [N][T][V] and g_dev [N][U1][V] alone, both raw, contiguous and of one dtype (0 = fp32, 1 = bf16, 2 = fp16), read in place;
+ * f + g is formed in fp32 from their exact values and the joint tensor [N][T][U1][V] is never formed.  Labels, lengths, validity, cost,
+ * invalid (may be NULL) and the no-finite-path rule are those of crf_rnnt_loss in the padded layout.
+ * crf_rnnt_simple_grad takes the same arguments and the forward's workspace, and grad_output_dev [N]; it writes EVERY element of
+ * grad_f_dev [N][T][V] and grad_g_dev [N][U1][V] (the inputs' dtype; either pointer may be NULL, that gradient is then not formed):
+ *   d f[t][v] = sum over u <= U_n, d g[u][v] = sum over t < T_n   of   gb [v = blank] + gl [v = y_u] - (gb + gl) softmax_v(f[t] + g[u])
+ * with gb, gl the node's two occupancies times grad_output[n]; zeros for t >= T_n, u > U_n, invalid utterances and lattices without a
+ * finite path.  No atomics: the same bits run to run and for an utterance alone or in any batch.
+ * Workspace: crf_rnnt_simple_workspace_bytes = crf_rnnt_workspace_bytes(N, T, U1, V, -1) + al(4 N T V) + al(16 N U1 V): the sections
+ * "row", "alpha", "beta", "utt" as above, then "df" (d f in fp32) and "dg" (four partial sums of d g over interleaved chunks of 16 frames,
+ * added in a fixed order); nothing is proportional to T U1 V.  Errors and limits as for crf_rnnt_loss (U1 <= 1024, V <= 8192). */
+int64_t crf_rnnt_simple_workspace_bytes(int64_t N, int64_t T, int64_t U1, int64_t V);
+int crf_rnnt_simple_loss(const void *f_dev, const void *g_dev, int dtype, int blank, const int32_t *labels_dev, const int32_t *lx_dev,
+                         const int32_t *ly_dev, int64_t N, int64_t T, int64_t U1, int64_t V, float *cost_dev, int32_t *invalid_dev,
+                         void *workspace_dev, int64_t workspace_bytes, void *stream);
+int crf_rnnt_simple_grad(const void *f_dev, const void *g_dev, int dtype, int blank, const int32_t *labels_dev, const int32_t *lx_dev,
+                         const int32_t *ly_dev, int64_t N, int64_t T, int64_t U1, int64_t V, const float *grad_output_dev, void *grad_f_dev,
+                         void *grad_g_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+int crf_debug_rnnt_simple_ws_sections(int64_t N, int64_t T, int64_t U1, int64_t V, int64_t *out, int n_out);
+const char *crf_debug_rnnt_simple_ws_section_names(void);
 
 /* Token edit distance of H hypotheses to the transcripts of their utterances, with the operation counts of one optimal alignment: what
  * cat/ctc/train.py:200-210 (cal_wer), train_jsa.py:371-387 (cal_per), train_me2e.py:250-256 and train_me2e_kaldi.py:420-426 compute with
