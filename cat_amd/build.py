@@ -19,11 +19,11 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-FAMILIES = ["k_fac_768.hip", "k_fac_pair2.hip", "k_fac_1024.hip", "k_batch.hip", "k_grad.hip", "k_res.hip", "k_chain.hip", "k_robust.hip", "k_align.hip", "k_score.hip", "k_score_grad.hip", "k_rows.hip", "k_sample.hip", "k_beam.hip", "k_beam_lm.hip", "k_beam_chunk.hip", "k_edit.hip", "k_ngram.hip", "k_rnnt.hip", "k_rnnt_join.hip"]   # slowest first
+FAMILIES = ["k_fac_768.hip", "k_fac_pair2.hip", "k_fac_1024.hip", "k_batch.hip", "k_grad.hip", "k_res.hip", "k_chain.hip", "k_robust.hip", "k_align.hip", "k_score.hip", "k_score_grad.hip", "k_rows.hip", "k_sample.hip", "k_beam.hip", "k_beam_lm.hip", "k_beam_chunk.hip", "k_edit.hip", "k_ngram.hip", "k_rnnt.hip", "k_rnnt_join.hip", "k_ctct.hip"]   # slowest first
 GRAPH_UNITS = ["res_layout.cpp", "graph_compile.cpp", "arc_streams.cpp", "fst_read.cpp", "crf_opts.cpp", "stage_plan.cpp"]   # host C++ only: no kernels
 UNITS = FAMILIES + ["crf_host.hip", "crf_host_ctc.hip"] + GRAPH_UNITS + ["ctc_api.cpp"]
 MAX_JOBS = 16
-HEADERS = [os.path.join(CSRC, h) for h in ("crf_internal.h", "crf_device.h", "crf_kernels_decl.h", "crf_host_util.h", "stage_plan.h", "k_res_common.h", "k_lattice_common.h", "k_beam_common.h", "k_ngram_common.h", "k_fac_body.h", "k_score_grad_body.h", "k_beam_body.h", "k_beam_lm_body.h")] + \
+HEADERS = [os.path.join(CSRC, h) for h in ("crf_internal.h", "crf_device.h", "crf_kernels_decl.h", "crf_host_util.h", "stage_plan.h", "k_res_common.h", "k_lattice_common.h", "k_beam_common.h", "k_ngram_common.h", "k_rnnt_common.h", "k_fac_body.h", "k_score_grad_body.h", "k_beam_body.h", "k_beam_lm_body.h")] + \
           [os.path.join(os.path.dirname(HERE), "include", h) for h in ("ctc_crf_hip.h", "ctc.h")]
 OUT = os.environ.get("CRF_BUILD_OUT") or os.path.join(HERE, "lib", "libctc_crf_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

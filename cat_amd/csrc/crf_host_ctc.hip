@@ -4,7 +4,8 @@
 // crf_ctc_score_grad_rows, k_rows.hip), sampled / best-path label sequences (crf_ctc_sample, k_sample.hip), the
 // prefix beam search (crf_ctc_beam, k_beam.hip; with an n-gram LM: crf_ctc_beam_lm, k_beam_lm.hip, crf_ngram_tables_check) and -- on token sequences alone, no lattice -- the edit distance of hypotheses to
 // their transcripts (crf_ctc_edit_distance, k_edit.hip) and their n-gram LM scores (crf_ngram_score, k_ngram.hip) -- and the RNN-T
-// transducer loss on the joiner's lattice (crf_rnnt_loss, crf_rnnt_grad, k_rnnt.hip) --
+// transducer loss on the joiner's lattice (crf_rnnt_loss, crf_rnnt_grad, k_rnnt.hip) and the CTC-Transducer loss on the same lattice
+// (crf_ctct_loss, crf_ctct_grad, k_ctct.hip) --
 // argument checks, workspace sections, kernel choice, the C-ABI entry points of include/ctc_crf_hip.h.  Every error is answered before
 // any HIP call.  The activations are read in place in either layout and -- the *_logits entry points and crf_ctc_sample -- in f32, bf16
 // or f16.
@@ -716,6 +717,78 @@ static int join_grad_call(const char *who, const void *f, const void *g, int dty
     });
 }
 
+// ---- the CTC-Transducer loss and its gradient (k_ctct.hip) ----
+// The workspace both calls share, R = N T U1 (padded only): row [R][4] floats (b, r, e, log s), rmax [R] floats (M), alpha [R][2] and
+// beta [R][2] fp64, utt as for crf_rnnt_loss.  < 0 with the message set.
+enum CtctWs { kCtRow, kCtMax, kCtAlpha, kCtBeta, kCtUtt, kCtCount };
+static const char *const kCtctWsNames[kCtCount] = {"row", "rmax", "alpha", "beta", "utt"};
+static int64_t ctct_ws_bytes(int64_t N, int64_t T, int64_t U1, int64_t V, SideWs *out = nullptr) {
+    const std::string who = "crf_ctct_loss: ";
+    if (N <= 0 || T <= 0 || U1 <= 0 || V <= 0 || N > INT32_MAX || T > INT32_MAX) { set_error(who + "bad N/T/U+1/V"); return -CRF_ERR_ARG; }
+    if (U1 > kRnntMaxU1) { set_error(who + "U > " + std::to_string(kRnntMaxU1 - 1) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
+    if (V > kRnntMaxV) { set_error(who + "V > " + std::to_string(kRnntMaxV) + " not supported by this build"); return -CRF_ERR_UNSUPPORTED; }
+    if (T > (INT32_MAX / 4) / U1) { set_error(who + "T * (U + 1) > INT32_MAX / 4"); return -CRF_ERR_ARG; }   // (an utterance's nodes are indexed in 32 bits)
+    if (N > INT32_MAX / (T * U1)) { set_error(who + "rows outside [1, INT32_MAX]"); return -CRF_ERR_ARG; }
+    const int64_t R = N * T * U1;
+    SideWs w;
+    w.add(kCtctWsNames[kCtRow], 4 * R * (int64_t)sizeof(float)).add(kCtctWsNames[kCtMax], R * (int64_t)sizeof(float))
+     .add(kCtctWsNames[kCtAlpha], 2 * R * (int64_t)sizeof(double)).add(kCtctWsNames[kCtBeta], 2 * R * (int64_t)sizeof(double))
+     .add(kCtctWsNames[kCtUtt], N * (int64_t)sizeof(double) + (4 * N + 1) * (int64_t)sizeof(int32_t));
+    if (out) *out = w;
+    return w.total;
+}
+// the checks both calls share, in the order of include/ctc_crf_hip.h, and the kernels' arguments; no HIP call.  dtype < 0: normalised fp32
+static int ctct_setup(const char *who_, const void *x, int dtype, int blank, const int32_t *labels, const int32_t *lx, const int32_t *ly, int64_t N,
+                      int64_t T, int64_t U1, int64_t V, const void *out, const void *ws, int64_t ws_bytes, CtctParams &q) {
+    const std::string who = who_;
+    if (!x || !labels || !lx || !ly || !out || !ws) { set_error(who + ": null argument"); return CRF_ERR_ARG; }
+    if (dtype > 2) return bad_dtype(who_);
+    SideWs w;
+    const int64_t need = ctct_ws_bytes(N, T, U1, V, &w);
+    if (need < 0) return (int)-need;
+    if (const int rc = check_blank(blank, V)) return rc;
+    if ((uintptr_t)ws & 15) { set_error(who + ": the workspace must be 16-byte aligned"); return CRF_ERR_ARG; }
+    if (const int rc = check_ws(ws_bytes, need)) return rc;
+    q = CtctParams{};
+    RnntParams &p = q.r;
+    p.x = x; p.labels = labels; p.lx = lx; p.ly = ly;
+    p.N = (int)N; p.T = (int)T; p.U1 = (int)U1; p.V = (int)V; p.blank = blank; p.compact = 0;
+    p.R = N * T * U1; p.nlab = N * (U1 - 1);
+    char *b = (char *)ws;
+    p.row = (float *)(b + w.sec[kCtRow].off); q.rmax = (float *)(b + w.sec[kCtMax].off);
+    p.alpha = (double *)(b + w.sec[kCtAlpha].off); p.beta = (double *)(b + w.sec[kCtBeta].off);
+    p.total = (double *)(b + w.sec[kCtUtt].off);
+    p.node_off = (int *)(p.total + N); p.lab_off = p.node_off + N + 1; p.tn = p.lab_off + N; p.un = p.tn + N;
+    return CRF_OK;
+}
+// the forward: crf_rnnt_loss's prep launch, the row stage, both recursions -- three launches on one stream
+static int ctct_loss_call(const char *who, const void *x, int dtype, int blank, const int32_t *labels, const int32_t *lx, const int32_t *ly, int64_t N,
+                          int64_t T, int64_t U1, int64_t V, float *cost, int32_t *invalid, void *ws, int64_t ws_bytes, hipStream_t st) {
+    CtctParams q;
+    if (const int rc = ctct_setup(who, x, dtype, blank, labels, lx, ly, N, T, U1, V, cost, ws, ws_bytes, q)) return rc;
+    q.r.cost = cost; q.r.invalid = invalid;
+    if (const int rc = launch<crf_rnnt_prep_kernel>("crf_rnnt_prep_kernel", dim3(1), dim3(kRnntPrepThreads), 0, st, q.r)) return rc;
+    const dim3 wgrid((unsigned)((q.r.R + kRnntWaves - 1) / kRnntWaves)), wblock(64 * kRnntWaves);
+    int rc;
+    if (dtype < 0) rc = launch<crf_ctct_gather_kernel>("crf_ctct_gather_kernel", dim3((unsigned)((q.r.R + 255) / 256)), dim3(256), 0, st, q);
+    else rc = with_dtype(dtype, [&](auto e) { return launch<crf_ctct_row_kernel<decltype(e)>>("crf_ctct_row_kernel", wgrid, wblock, 0, st, q); });
+    if (rc) return rc;
+    const dim3 lgrid((unsigned)N, 2);
+    if (U1 <= 64) return launch<crf_ctct_lattice_kernel<false>>("crf_ctct_lattice_kernel<wave>", lgrid, dim3(64), 0, st, q);
+    return launch<crf_ctct_lattice_kernel<true>>("crf_ctct_lattice_kernel<workgroup>", lgrid, dim3((unsigned)rup64((int)U1)), 0, st, q);
+}
+// the backward on the forward's workspace: one launch
+static int ctct_grad_call(const char *who, const void *x, int dtype, int blank, const int32_t *labels, const int32_t *lx, const int32_t *ly, int64_t N,
+                          int64_t T, int64_t U1, int64_t V, const float *weight, void *grad, void *ws, int64_t ws_bytes, hipStream_t st) {
+    CtctParams q;
+    if (!weight) { set_error(std::string(who) + ": null argument"); return CRF_ERR_ARG; }
+    if (const int rc = ctct_setup(who, x, dtype, blank, labels, lx, ly, N, T, U1, V, grad, ws, ws_bytes, q)) return rc;
+    q.r.weight = weight; q.r.grad = grad;
+    const dim3 wgrid((unsigned)((q.r.R + kRnntWaves - 1) / kRnntWaves)), wblock(64 * kRnntWaves);
+    if (dtype < 0) return launch<crf_ctct_grad_kernel<float, false>>("crf_ctct_grad_kernel", wgrid, wblock, 0, st, q);
+    return with_dtype(dtype, [&](auto e) { return launch<crf_ctct_grad_kernel<decltype(e), true>>("crf_ctct_grad_kernel", wgrid, wblock, 0, st, q); });
+}
+
 }  // namespace crf
 
 using namespace crf;
@@ -1048,6 +1121,36 @@ int crf_rnnt_simple_grad(const void *f, const void *g, int dtype, int blank, con
                          int64_t T, int64_t U1, int64_t V, const float *grad_output, void *grad_f, void *grad_g, void *ws, int64_t ws_bytes,
                          void *stream_) {
     return join_grad_call("crf_rnnt_simple_grad", f, g, dtype, blank, labels, lx, ly, N, T, U1, V, grad_output, grad_f, grad_g, ws, ws_bytes,
+                          (hipStream_t)stream_);
+}
+
+int64_t crf_ctct_workspace_bytes(int64_t N, int64_t T, int64_t U1, int64_t V) { return or_minus1(ctct_ws_bytes(N, T, U1, V)); }
+int crf_debug_ctct_ws_sections(int64_t N, int64_t T, int64_t U1, int64_t V, int64_t *out, int n_out) {
+    SideWs w;
+    if (ctct_ws_bytes(N, T, U1, V, &w) < 0) return -1;
+    return copy_sections(w.sec, w.nsec, out, n_out);
+}
+const char *crf_debug_ctct_ws_section_names(void) {
+    static const std::string s = join_names(kCtctWsNames, kCtCount);
+    return s.c_str();
+}
+int crf_ctct_loss(const float *log_probs, int blank, const int32_t *labels, const int32_t *lx, const int32_t *ly, int64_t N, int64_t T, int64_t U1,
+                  int64_t V, float *cost, int32_t *invalid, void *ws, int64_t ws_bytes, void *stream_) {
+    return ctct_loss_call("crf_ctct_loss", log_probs, -1, blank, labels, lx, ly, N, T, U1, V, cost, invalid, ws, ws_bytes, (hipStream_t)stream_);
+}
+int crf_ctct_loss_logits(const void *logits, int dtype, int blank, const int32_t *labels, const int32_t *lx, const int32_t *ly, int64_t N, int64_t T,
+                         int64_t U1, int64_t V, float *cost, int32_t *invalid, void *ws, int64_t ws_bytes, void *stream_) {
+    if (dtype < 0) return bad_dtype("crf_ctct_loss_logits");
+    return ctct_loss_call("crf_ctct_loss_logits", logits, dtype, blank, labels, lx, ly, N, T, U1, V, cost, invalid, ws, ws_bytes, (hipStream_t)stream_);
+}
+int crf_ctct_grad(const float *log_probs, int blank, const int32_t *labels, const int32_t *lx, const int32_t *ly, int64_t N, int64_t T, int64_t U1,
+                  int64_t V, const float *grad_output, float *grad, void *ws, int64_t ws_bytes, void *stream_) {
+    return ctct_grad_call("crf_ctct_grad", log_probs, -1, blank, labels, lx, ly, N, T, U1, V, grad_output, grad, ws, ws_bytes, (hipStream_t)stream_);
+}
+int crf_ctct_grad_logits(const void *logits, int dtype, int blank, const int32_t *labels, const int32_t *lx, const int32_t *ly, int64_t N, int64_t T,
+                         int64_t U1, int64_t V, const float *grad_output, void *grad, void *ws, int64_t ws_bytes, void *stream_) {
+    if (dtype < 0) return bad_dtype("crf_ctct_grad_logits");
+    return ctct_grad_call("crf_ctct_grad_logits", logits, dtype, blank, labels, lx, ly, N, T, U1, V, grad_output, grad, ws, ws_bytes,
                           (hipStream_t)stream_);
 }
 

@@ -279,6 +279,19 @@ template <typename E> __global__ void crf_join_row_kernel(JoinParams q);        
 template <typename E> __global__ void crf_join_grad_kernel(JoinParams q);         // grid (N ceil(V / kJoinGV), kJoinSplit)
 template <typename E> __global__ void crf_join_fold_kernel(JoinParams q);         // grid (N max(T, U1), 2): a workgroup per row of d f / d g
 
+// ---- k_ctct.hip ----
+constexpr int kCtctPF = 4;                // frames per staging batch of the lattice stage (two register sets in flight)
+// Kernel arguments of crf_ctct_loss / crf_ctct_grad: the padded RnntParams (stage 0 is crf_rnnt_prep_kernel as it is) with the sections read
+// as the CTC-T node record -- row [R][4] = (b, r, e, log s), alpha [R][2] and beta [R][2] fp64 -- and the rows' maxima beside them.
+struct CtctParams {
+    RnntParams r;
+    float *rmax;                // [R] the row's maximum M (0 for normalised input)
+};
+__global__ void crf_ctct_gather_kernel(CtctParams q);                              // normalised input: a thread per node
+template <typename E> __global__ void crf_ctct_row_kernel(CtctParams q);           // raw input: a wave per node
+template <bool WG> __global__ void crf_ctct_lattice_kernel(CtctParams q);          // grid (N, 2); WG: U1 > 64, rup64(U1) threads
+template <typename E, bool RAW> __global__ void crf_ctct_grad_kernel(CtctParams q); // a wave per row of grad
+
 // ---- k_edit.hip ----
 constexpr int kEditWaves = 4;            // hypotheses (waves) per workgroup of the register geometry
 constexpr int kEditStripRows = 512;       // reference rows one wave holds (64 lanes x 8): longer references are walked in strips of this many

@@ -147,6 +147,19 @@ _lib.crf_rnnt_simple_grad.restype = ctypes.c_int
 _lib.crf_debug_rnnt_simple_ws_sections.argtypes = [_i64, _i64, _i64, _i64, ctypes.POINTER(_i64), ctypes.c_int]
 _lib.crf_debug_rnnt_simple_ws_sections.restype = ctypes.c_int
 _lib.crf_debug_rnnt_simple_ws_section_names.restype = ctypes.c_char_p
+_lib.crf_ctct_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64]
+_lib.crf_ctct_workspace_bytes.restype = _i64
+_lib.crf_ctct_loss.argtypes = [_vp, ctypes.c_int, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp]
+_lib.crf_ctct_loss.restype = ctypes.c_int
+_lib.crf_ctct_loss_logits.argtypes = [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp]
+_lib.crf_ctct_loss_logits.restype = ctypes.c_int
+_lib.crf_ctct_grad.argtypes = [_vp, ctypes.c_int, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp]
+_lib.crf_ctct_grad.restype = ctypes.c_int
+_lib.crf_ctct_grad_logits.argtypes = [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp]
+_lib.crf_ctct_grad_logits.restype = ctypes.c_int
+_lib.crf_debug_ctct_ws_sections.argtypes = [_i64, _i64, _i64, _i64, ctypes.POINTER(_i64), ctypes.c_int]
+_lib.crf_debug_ctct_ws_sections.restype = ctypes.c_int
+_lib.crf_debug_ctct_ws_section_names.restype = ctypes.c_char_p
 _lib.crf_profile_enable.argtypes = [ctypes.c_int]
 _lib.crf_profile_enable.restype = None
 _lib.crf_profile_read.argtypes = [ctypes.POINTER(_f32), ctypes.c_int]
@@ -171,7 +184,7 @@ _lib.crf_build_switches.restype = ctypes.c_char_p
 
 EXPORTED_SYMBOLS = (
     "crf_graph_create", "crf_graph_create_from_arcs", "crf_graph_destroy", "crf_graph_dims", "crf_graph_stats",
-    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_ws_fields", "crf_debug_ws_field_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_ctc_score", "crf_ctc_score_logits_workspace_bytes", "crf_ctc_score_logits", "crf_last_score_kernel", "crf_ctc_score_grad_workspace_bytes", "crf_ctc_score_grad", "crf_ctc_score_grad_logits_workspace_bytes", "crf_ctc_score_grad_logits", "crf_last_score_grad_kernel", "crf_ctc_score_rows_workspace_bytes", "crf_ctc_score_rows", "crf_ctc_score_grad_rows_workspace_bytes", "crf_ctc_score_grad_rows", "crf_debug_score_rows_ws_sections", "crf_debug_score_rows_ws_section_names", "crf_ctc_sample_workspace_bytes", "crf_ctc_sample", "crf_last_sample_kernel", "crf_ctc_beam_workspace_bytes", "crf_ctc_beam", "crf_last_beam_kernel", "crf_ngram_tables_check", "crf_ctc_beam_lm_workspace_bytes", "crf_ctc_beam_lm", "crf_ctc_beam_state_record_bytes", "crf_ctc_beam_chunk_workspace_bytes", "crf_ctc_beam_chunk", "crf_ctc_edit_distance", "crf_last_edit_kernel", "crf_ngram_score", "crf_last_ngram_score_kernel", "crf_rnnt_workspace_bytes", "crf_rnnt_loss", "crf_rnnt_loss_logits", "crf_rnnt_grad", "crf_rnnt_grad_logits", "crf_debug_rnnt_ws_sections", "crf_debug_rnnt_ws_section_names", "crf_rnnt_simple_workspace_bytes", "crf_rnnt_simple_loss", "crf_rnnt_simple_grad", "crf_debug_rnnt_simple_ws_sections", "crf_debug_rnnt_simple_ws_section_names", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
+    "crf_workspace_bytes", "crf_den_kernels", "crf_debug_stream_check", "crf_debug_decode_check", "crf_debug_facbatch_check", "crf_debug_fac_emulate", "crf_debug_res_emulate", "crf_debug_stage_plan", "crf_debug_ws_sections", "crf_debug_ws_section_names", "crf_debug_ws_fields", "crf_debug_ws_field_names", "crf_debug_align_ws_sections", "crf_debug_align_ws_section_names", "crf_loss_fwd_bwd", "crf_loss_fwd_bwd_logits", "crf_ctc_fwd_bwd", "crf_ctc_fwd_bwd_logits", "crf_ctc_align_workspace_bytes", "crf_ctc_align", "crf_ctc_align_logits_workspace_bytes", "crf_ctc_align_logits", "crf_ctc_score", "crf_ctc_score_logits_workspace_bytes", "crf_ctc_score_logits", "crf_last_score_kernel", "crf_ctc_score_grad_workspace_bytes", "crf_ctc_score_grad", "crf_ctc_score_grad_logits_workspace_bytes", "crf_ctc_score_grad_logits", "crf_last_score_grad_kernel", "crf_ctc_score_rows_workspace_bytes", "crf_ctc_score_rows", "crf_ctc_score_grad_rows_workspace_bytes", "crf_ctc_score_grad_rows", "crf_debug_score_rows_ws_sections", "crf_debug_score_rows_ws_section_names", "crf_ctc_sample_workspace_bytes", "crf_ctc_sample", "crf_last_sample_kernel", "crf_ctc_beam_workspace_bytes", "crf_ctc_beam", "crf_last_beam_kernel", "crf_ngram_tables_check", "crf_ctc_beam_lm_workspace_bytes", "crf_ctc_beam_lm", "crf_ctc_beam_state_record_bytes", "crf_ctc_beam_chunk_workspace_bytes", "crf_ctc_beam_chunk", "crf_ctc_edit_distance", "crf_last_edit_kernel", "crf_ngram_score", "crf_last_ngram_score_kernel", "crf_rnnt_workspace_bytes", "crf_rnnt_loss", "crf_rnnt_loss_logits", "crf_rnnt_grad", "crf_rnnt_grad_logits", "crf_debug_rnnt_ws_sections", "crf_debug_rnnt_ws_section_names", "crf_rnnt_simple_workspace_bytes", "crf_rnnt_simple_loss", "crf_rnnt_simple_grad", "crf_debug_rnnt_simple_ws_sections", "crf_debug_rnnt_simple_ws_section_names", "crf_ctct_workspace_bytes", "crf_ctct_loss", "crf_ctct_loss_logits", "crf_ctct_grad", "crf_ctct_grad_logits", "crf_debug_ctct_ws_sections", "crf_debug_ctct_ws_section_names", "crf_profile_enable", "crf_profile_read", "crf_timing_read", "crf_stage_i32",
     "crf_debug_set", "crf_debug_unset", "crf_debug_list", "crf_last_den_kernel", "crf_last_call_streams", "crf_last_side_stream", "crf_last_fallback_counts", "crf_build_switches", "crf_last_error", "crf_version",
 )
 
@@ -475,6 +488,16 @@ def debug_rnnt_simple_ws_sections(N: int, T: int, U1: int, V: int):
     names = _lib.crf_debug_rnnt_simple_ws_section_names().decode().split(",")
     out = (_i64 * (2 * len(names)))()
     n = _lib.crf_debug_rnnt_simple_ws_sections(N, T, U1, V, out, len(out))
+    if n < 0:
+        _check(1)
+    return [(names[k], int(out[2 * k]), int(out[2 * k + 1])) for k in range(n)]
+
+
+def debug_ctct_ws_sections(N: int, T: int, U1: int, V: int):
+    """The same for the workspace of crf_ctct_loss / crf_ctct_grad."""
+    names = _lib.crf_debug_ctct_ws_section_names().decode().split(",")
+    out = (_i64 * (2 * len(names)))()
+    n = _lib.crf_debug_ctct_ws_sections(N, T, U1, V, out, len(out))
     if n < 0:
         _check(1)
     return [(names[k], int(out[2 * k]), int(out[2 * k + 1])) for k in range(n)]
@@ -1652,6 +1675,97 @@ def rnnt_loss_bwd(call: RnntCall, grad_output: torch.Tensor, grad_out: Optional[
             _vp(stream))
     with torch.cuda.device(dev):
         rc = _lib.crf_rnnt_grad_logits(_ptr(c.x), _FUSED_DTYPES[c.x.dtype], *tail) if c.fused else _lib.crf_rnnt_grad(_ptr(c.x), *tail)
+    _check(rc)
+    return grad
+
+
+class CtctCall:
+    """What ctct_loss_fwd leaves for ctct_loss_bwd: the C call's arguments (the staged tensors are kept alive here) and the workspace."""
+
+    def __init__(self, x, fused, blank, labels, lx, ly, N, T, U1, V, ws):
+        self.x, self.fused, self.blank, self.labels, self.lx, self.ly = x, fused, blank, labels, lx, ly
+        self.N, self.T, self.U1, self.V, self.ws = N, T, U1, V, ws
+
+
+def _check_ctct_args(x: torch.Tensor, labels: torch.Tensor, lx: torch.Tensor, ly: torch.Tensor, blank: int, fused: bool):
+    """The host checks of ctct_loss, each a ValueError with the offending value in the message; none needs a device.  -> (N, T, U1, V)."""
+    who = "ctct_loss"
+    if fused:
+        if x.dtype not in _FUSED_DTYPES:
+            raise ValueError(f"{who}: fuse_log_softmax expects float32, bfloat16 or float16 joiner output, got {x.dtype}")
+    elif x.dtype != torch.float32:
+        raise ValueError(f"{who}: expect normalised float32 log_probs (or fuse_log_softmax=True for raw output), got {x.dtype}")
+    if labels.dtype != torch.int32 or lx.dtype != torch.int32 or ly.dtype != torch.int32:
+        raise ValueError(f"{who}: labels, frames_lengths and labels_lengths must be int32, got {labels.dtype}, {lx.dtype}, {ly.dtype}")
+    if lx.dim() != 1 or ly.dim() != 1 or lx.numel() != ly.numel() or lx.numel() == 0:
+        raise ValueError(f"{who}: expect frames_lengths and labels_lengths as (N,) with N >= 1, got {tuple(lx.shape)} and {tuple(ly.shape)}")
+    N = lx.numel()
+    if x.dim() != 4 or x.shape[0] != N:
+        raise ValueError(f"{who}: expect log_probs (N={N}, T, U+1, V), got {tuple(x.shape)}")
+    _, T, U1, V = x.shape
+    if T < 1 or U1 < 1:
+        raise ValueError(f"{who}: empty lattice {tuple(x.shape)}")
+    if not 1 <= V <= RNNT_MAX_VOCAB:
+        raise ValueError(f"{who}: V = {V} outside [1, {RNNT_MAX_VOCAB}] not supported by this build")
+    if not 0 <= blank < V:
+        raise ValueError(f"{who}: blank must lie in [0, V-1={V - 1}], got {blank}")
+    if U1 - 1 > RNNT_MAX_LABELS:
+        raise ValueError(f"{who}: U = {U1 - 1} > {RNNT_MAX_LABELS} not supported by this build")
+    if tuple(labels.shape) != (N, U1 - 1):
+        raise ValueError(f"{who}: expect labels (N={N}, U={U1 - 1}), got {tuple(labels.shape)}")
+    if not x.is_contiguous() or not labels.is_contiguous():
+        raise ValueError(f"{who}: log_probs and labels must be contiguous (the joiner output is read in place)")
+    if lx.is_cuda != ly.is_cuda:
+        raise ValueError(f"{who}: frames_lengths and labels_lengths must both be on the CPU or both on the GPU")
+    if not lx.is_cuda:
+        if int(lx.min()) < 1 or int(lx.max()) > T:
+            raise ValueError(f"{who}: frames_lengths must lie in [1, T={T}], got [{int(lx.min())}, {int(lx.max())}]")
+        if int(ly.min()) < 0 or int(ly.max()) > U1 - 1:
+            raise ValueError(f"{who}: labels_lengths must lie in [0, U={U1 - 1}], got [{int(ly.min())}, {int(ly.max())}]")
+    return N, T, U1, V
+
+
+def ctct_loss_fwd(x: torch.Tensor, labels: torch.Tensor, lx: torch.Tensor, ly: torch.Tensor, blank: int = 0, fused: bool = False):
+    """The forward of the CTC-Transducer loss (include/ctc_crf_hip.h ``crf_ctct_loss`` / ``crf_ctct_loss_logits``) -> (costs [N] f32, invalid
+    [N] int32, CtctCall for ctct_loss_bwd) on the device, without a host synchronisation when the lengths are on the device."""
+    N, T, U1, V = _check_ctct_args(x, labels, lx, ly, blank, fused)
+    if not x.is_cuda:
+        raise RuntimeError("ctct_loss: log_probs must be on the GPU (there is no CPU path)")
+    dev = x.device
+    x = x.detach()
+    lab_d = labels.to(dev) if labels.numel() else torch.zeros(1, dtype=torch.int32, device=dev)   # (no NULL in the C ABI)
+    if lx.is_cuda:
+        lx_d, ly_d = lx.contiguous(), ly.contiguous()
+    else:
+        meta = _h2d_async(torch.cat([lx, ly]), dev)
+        lx_d, ly_d = meta[:N], meta[N:]
+    costs = torch.empty(N, dtype=torch.float32, device=dev)
+    invalid = torch.empty(N, dtype=torch.int32, device=dev)
+    ws = _new_ws(_lib.crf_ctct_workspace_bytes(N, T, U1, V), dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    tail = (blank, _ptr(lab_d), _ptr(lx_d), _ptr(ly_d), N, T, U1, V, _ptr(costs), _ptr(invalid), _ptr(ws), ws.numel(), _vp(stream))
+    with torch.cuda.device(dev):
+        rc = _lib.crf_ctct_loss_logits(_ptr(x), _FUSED_DTYPES[x.dtype], *tail) if fused else _lib.crf_ctct_loss(_ptr(x), *tail)
+    _check(rc)
+    return costs, invalid, CtctCall(x, fused, blank, lab_d, lx_d, ly_d, N, T, U1, V, ws)
+
+
+def ctct_loss_bwd(call: CtctCall, grad_output: torch.Tensor, grad_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The backward on the forward's workspace (``crf_ctct_grad`` / ``crf_ctct_grad_logits``): grad_output [N] is d loss / d costs; returns
+    the gradient in the input's shape and dtype, every element written by the kernel (grad_out: a contiguous tensor of that shape and
+    dtype to write into, whatever it holds)."""
+    c = call
+    dev = c.x.device
+    w = grad_output.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if w.numel() != c.N:
+        raise RuntimeError(f"ctct_loss: expect grad_output ({c.N},), got {tuple(grad_output.shape)}")
+    grad = torch.empty_like(c.x) if grad_out is None else grad_out
+    if grad.shape != c.x.shape or grad.dtype != c.x.dtype or grad.device != dev or not grad.is_contiguous():
+        raise RuntimeError("ctct_loss: grad_out must be contiguous, of the input's shape and dtype and on its device")
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    tail = (c.blank, _ptr(c.labels), _ptr(c.lx), _ptr(c.ly), c.N, c.T, c.U1, c.V, _ptr(w), _ptr(grad), _ptr(c.ws), c.ws.numel(), _vp(stream))
+    with torch.cuda.device(dev):
+        rc = _lib.crf_ctct_grad_logits(_ptr(c.x), _FUSED_DTYPES[c.x.dtype], *tail) if c.fused else _lib.crf_ctct_grad(_ptr(c.x), *tail)
     _check(rc)
     return grad
 

@@ -47,6 +47,10 @@ Same names, arguments and error behaviour as the reference:
                                                                                          (warp_rnnt.rnnt_loss_simple: the same loss of the joiner
                                                                                          f + g from f (N, T, V) and g (N, U+1, V) alone, the
                                                                                          (N, T, U+1, V) tensor never formed; re-exported likewise)
+  ctct_loss(log_probs, labels, frames_lengths, labels_lengths, average_frames=False, reduction=None, blank=0, fuse_log_softmax=False)
+            -> costs                                                                     (warp_ctct.ctct_loss: the CTC-Transducer loss with
+                                                                                         autograd on the padded joiner output, normalised or
+                                                                                         raw; the top-level package warp_ctct re-exports it)
 plus the functional form named by BASELINE.json:
   ctc_crf_loss(log_probs, labels, frame_lens, label_lens, den_lm, lamb=0.1, size_average=True)
 
@@ -713,6 +717,69 @@ def rnnt_loss_simple(f_enc: torch.Tensor, g_pred: torch.Tensor, labels: torch.Te
     if reduction not in (None, "none", "mean", "sum"):
         raise ValueError(f"rnnt_loss_simple: unknown reduction {reduction!r} (None, 'none', 'mean' or 'sum')")
     costs, invalid = _RNNT_LOSS_SIMPLE.apply(f_enc, g_pred, labels, frames_lengths, labels_lengths, int(blank))
+    if average_frames:
+        costs = costs / frames_lengths.to(device=costs.device, dtype=costs.dtype)
+    if reduction == "sum":
+        costs = costs.sum()
+    elif reduction == "mean":
+        costs = costs.mean()
+    return (costs, invalid) if return_invalid else costs
+
+
+class _CTCT_LOSS(Function):
+    """costs [N] = crf_ctct_loss / crf_ctct_loss_logits; backward = ONE crf_ctct_grad / crf_ctct_grad_logits call on the forward's workspace
+    with grad_output as the per-utterance weights.  The gradient has the input's shape and dtype; the kernels write every element."""
+
+    @staticmethod
+    def forward(ctx, log_probs, labels, lx, ly, blank, fused):
+        costs, invalid, call = core.ctct_loss_fwd(log_probs, labels, lx, ly, blank, fused)
+        ctx.call = call
+        ctx.mark_non_differentiable(invalid)
+        return costs, invalid
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_costs, _grad_invalid):
+        return core.ctct_loss_bwd(ctx.call, grad_costs), None, None, None, None, None
+
+
+def ctct_loss(log_probs: torch.Tensor, labels: torch.Tensor, frames_lengths: torch.Tensor, labels_lengths: torch.Tensor,
+              average_frames: bool = False, reduction: str = None, blank: int = 0, fuse_log_softmax: bool = False,
+              return_invalid: bool = False):
+    """The CTC-Transducer (CTC-T) loss with autograd: what cat/rnnt/train.py:216-219 calls as ``warp_ctct.ctct_loss(xys, y, lsub, ly)`` for
+    topo="ctct".  The four positional arguments are that call's; warp_ctct's source is not available, so the keywords are those of
+    ``rnnt_loss`` here, not necessarily warp_ctct's own.
+
+    A path labels EVERY frame t < T_n with one class; blanks and repeats collapse as in CTC and the collapse is the label sequence; frame
+    t's emission is read from row u = the number of labels emitted before frame t.  costs[n] = -log of the sum over those paths: with
+    b(t,u) = lp[t][u][blank], r(t,u) = lp[t][u][y_u] (u >= 1), e(t,u) = lp[t][u][y_{u+1}] (u < U) and the masses Ab / An after t frames with
+    u labels emitted, ending in a blank (or nothing yet) / in y_u,
+
+        Ab[0][0] = 0, everything else -inf
+        Ab[t+1][u] = lse(Ab[t][u], An[t][u]) + b(t,u)
+        An[t+1][u] = lse(An[t][u] + r(t,u), Ab[t][u-1] + e(t,u-1), An[t][u-1] + e(t,u-1) only if y_u != y_{u-1})
+        cost = -lse(Ab[T][U], An[T][U])
+
+    (the frame-synchronous search of cat/rnnt/ctct_decoder.py read as a sum).  With log_probs independent of u this is plain CTC.
+
+    log_probs: (N, T, U+1, V) float32 log-probabilities on the GPU, contiguous -- the padded layout only.  Its gradient is zero except at
+        the blank's column, column y_u and column y_{u+1} of every live node (t < T_n, u <= U_n); where y_u == y_{u+1} the two share a
+        column and their terms add.  Over the rows u of one frame the gradient sums to -1 (times the utterance's weight).
+    labels: int32 (N, U), contiguous.  frames_lengths, labels_lengths: int32 (N,), both on the CPU (checked up front) or both on the GPU
+        (nothing is read on the host and nothing synchronises; an utterance out of range is invalid, see below).
+    average_frames: each utterance's cost is divided by its T_n.  reduction: None / "none" (costs (N,)), "mean", "sum".
+    blank: the blank's column, any of [0, V).
+    fuse_log_softmax: log_probs is the RAW joiner output in float32, bfloat16 or float16, read in place; the gradient comes back in the
+        input's dtype with log_softmax's backward folded in, g_v - softmax_v (g_b + g_r + g_e).
+    Shapes, dtypes, non-contiguous inputs and CPU lengths out of range raise ValueError before any device call.  Invalid utterances (T_n
+    outside [1, T], U_n outside [0, U], a label outside [0, V) or equal to blank) are decided on the device: cost +inf and a zero gradient;
+    return_invalid=True returns (costs, invalid IntTensor[N]).  A lattice without a path -- T_n < U_n + #{u: y_u == y_{u+1}}, or -inf
+    entries -- also costs +inf with a zero gradient, never NaN.  U <= 1023, V <= 8192.  The same bits run to run and for an utterance alone
+    or anywhere in a batch.
+    Not covered: a compact layout, the form on f and g without the joint tensor (warp_ctct.ctct_simple_loss), any CTC-T or RNN-T decoding."""
+    if reduction not in (None, "none", "mean", "sum"):
+        raise ValueError(f"ctct_loss: unknown reduction {reduction!r} (None, 'none', 'mean' or 'sum')")
+    costs, invalid = _CTCT_LOSS.apply(log_probs, labels, frames_lengths, labels_lengths, int(blank), bool(fuse_log_softmax))
     if average_frames:
         costs = costs / frames_lengths.to(device=costs.device, dtype=costs.dtype)
     if reduction == "sum":

@@ -681,6 +681,54 @@ int crf_rnnt_simple_grad(const void *f_dev, const void *g_dev, int dtype, int bl
 int crf_debug_rnnt_simple_ws_sections(int64_t N, int64_t T, int64_t U1, int64_t V, int64_t *out, int n_out);
 const char *crf_debug_rnnt_simple_ws_section_names(void);
 
+/* The CTC-Transducer (CTC-T) loss and its gradient: what cat/rnnt/train.py:216-219 calls as warp_ctct.ctct_loss(xys, y, lsub, ly) with
+ * topo="ctct".  A path labels EVERY frame t < T_n with one class; blanks and repeats collapse as in CTC and the collapse is y_n; frame
+ * t's emission is read from row u = the number of labels the path has emitted before frame t.  cost[n] = -log of the sum over those paths.
+ * With b(t,u) = lp[t][u][blank], r(t,u) = lp[t][u][y_u] (u >= 1) and e(t,u) = lp[t][u][y_{u+1}] (u < U), and per column the two masses
+ * Ab / An after t frames with u labels emitted that end in a blank (or in nothing yet) / in y_u:
+ *   Ab[0][0] = 0, everything else -inf
+ *   Ab[t+1][u] = lse(Ab[t][u], An[t][u]) + b(t,u)
+ *   An[t+1][u] = lse(An[t][u] + r(t,u), Ab[t][u-1] + e(t,u-1), An[t][u-1] + e(t,u-1) only if y_u != y_{u-1})
+ *   total = lse(Ab[T][U], An[T][U]),  cost = -total
+ * A lattice with T_n < U_n + #{u: y_u = y_{u+1}} has no path.  With lp independent of u this is plain CTC.
+ *
+ * The joiner output is read in place as [N][T][U1][V] (U1 = U + 1; the padded layout only: the caller's call has no compact argument),
+ * labels_dev [N][U1 - 1], lx_dev / ly_dev int32 [N] on the device.  crf_ctct_loss / crf_ctct_grad take normalised fp32 log-probabilities;
+ * the *_logits forms take the RAW joiner output, dtype 0 = fp32, 1 = bf16, 2 = fp16, and are the loss of log_softmax(logits).
+ * crf_ctct_loss* is the forward: cost_dev [N], invalid_dev [N] (may be NULL) and the workspace.  crf_ctct_grad* takes THE SAME arguments and
+ * the same workspace, unchanged since the forward, and grad_output_dev [N]; it writes EVERY element of grad_dev (the input's shape and --
+ * logits form -- element type):
+ *   normalised:  grad[r][v] = grad_output[n] (g_b [v = blank] + g_r [v = y_u] + g_e [v = y_{u+1}]), the three occupancies of a live node
+ *                (y_u = y_{u+1}: one column, the terms add); sum over u of a frame's entries = -grad_output[n];
+ *   logits:      grad[r][v] = g_v - softmax(x[r])_v * (g_b + g_r + g_e).
+ * Rows of padding nodes, of invalid utterances and of utterances without a path are written as zeros; there is no memset.
+ * Invalid input (T_n outside [1, T], U_n outside [0, U1 - 1], a label outside [0, V) or equal to `blank`) is decided on the device: cost
+ * +inf, invalid 1, zero gradient.  A lattice without a finite path gets cost +inf and a zero gradient with invalid 0; no NaN is produced.
+ *
+ * Workspace, with R = N T U1 and al(x) = x rounded up to a multiple of 256:
+ *   crf_ctct_workspace_bytes = al(16 R) + al(4 R) + al(16 R) + al(16 R) + al(8 N + 4 (4 N + 1))
+ * -- per node the record (b, r, e, log s) and, apart, the row's maximum M (the normaliser in two steps, as for crf_rnnt_loss), forward
+ * (X, An) and backward (Bb, Bn) in fp64, X = lse(Ab, An) where y_{u+1} may follow y_u directly and Ab where not; per utterance as for
+ * crf_rnnt_loss.  It must be 16-byte aligned.  -1 with the message set for sizes the call would refuse.
+ * Errors, all answered before any HIP call, and limits (U1 <= 1024, V <= 8192, T U1 <= INT32_MAX / 4) as for crf_rnnt_loss.
+ * Not covered: the compact layout, a form on f and g without the joint tensor (warp_ctct.ctct_simple_loss), any CTC-T or RNN-T decoding. */
+int64_t crf_ctct_workspace_bytes(int64_t N, int64_t T, int64_t U1, int64_t V);
+int crf_ctct_loss(const float *log_probs_dev, int blank, const int32_t *labels_dev, const int32_t *lx_dev, const int32_t *ly_dev, int64_t N,
+                  int64_t T, int64_t U1, int64_t V, float *cost_dev, int32_t *invalid_dev, void *workspace_dev, int64_t workspace_bytes,
+                  void *stream);
+int crf_ctct_loss_logits(const void *logits_dev, int dtype, int blank, const int32_t *labels_dev, const int32_t *lx_dev, const int32_t *ly_dev,
+                         int64_t N, int64_t T, int64_t U1, int64_t V, float *cost_dev, int32_t *invalid_dev, void *workspace_dev,
+                         int64_t workspace_bytes, void *stream);
+int crf_ctct_grad(const float *log_probs_dev, int blank, const int32_t *labels_dev, const int32_t *lx_dev, const int32_t *ly_dev, int64_t N,
+                  int64_t T, int64_t U1, int64_t V, const float *grad_output_dev, float *grad_dev, void *workspace_dev, int64_t workspace_bytes,
+                  void *stream);
+int crf_ctct_grad_logits(const void *logits_dev, int dtype, int blank, const int32_t *labels_dev, const int32_t *lx_dev, const int32_t *ly_dev,
+                         int64_t N, int64_t T, int64_t U1, int64_t V, const float *grad_output_dev, void *grad_dev, void *workspace_dev,
+                         int64_t workspace_bytes, void *stream);
+/* The workspace's sections -- "row", "rmax", "alpha", "beta", "utt" -- as crf_debug_rnnt_ws_sections gives them. */
+int crf_debug_ctct_ws_sections(int64_t N, int64_t T, int64_t U1, int64_t V, int64_t *out, int n_out);
+const char *crf_debug_ctct_ws_section_names(void);
+
 /* Token edit distance of H hypotheses to the transcripts of their utterances, with the operation counts of one optimal alignment: what
  * cat/ctc/train.py:200-210 (cal_wer), train_jsa.py:371-387 (cal_per), train_me2e.py:250-256 and train_me2e_kaldi.py:420-426 compute with
  * a Python loop of Levenshtein.distance after `.cpu().tolist()`, and the risk of minimum-risk / MWER training, for the rows that
